@@ -4,12 +4,15 @@
 One "step" = ONE full Newton iteration of the implicit step on the workload, inputs resident in HBM:
   residual (F,P,f_int) -> gradient + norm -> tangent blocks -> row assembly of H -> PCG solve of H dv = -g
   -> v += dv, x = x_prev + h v         (SyncedNewton.cu:1046-1119); every 3rd iteration starts a new time step.
-value = elements * steps / seconds (whole job, max over ranks).  The JSON line also carries
+value = elements * steps / seconds (whole job, max over ranks); ms_per_step = milliseconds per timed step.
+A plain run sets up, warms up, times the K steps and prints the JSON line.  With --full the line also carries
   roofline     : dominant kernel, algorithmic bytes per launch / mean launch duration (hipEvents on the launch stream)
   roofline_all : the same for every hot kernel
+  element_stage, stage_ms_per_step, comm_ms_per_step (N > 1): per-stage times of a separate profiling pass
   cpu_baseline : the CPU oracle (C restatement of the reference, OpenMP) on the same workload, rank 0, N=1 only.
+--dump-outputs DIR writes what the last timed step computed (rank 0) to DIR/*.npy, see dump_outputs().
 
-Launch:  python bench.py [--gpus N --steps K --warmup W --config C|B]
+Launch:  python bench.py [--gpus N --steps K --warmup W --config C|B --full --dump-outputs DIR]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run`, spawned before this process imports torch or touches the GPU) and relays rank 0's line.
@@ -65,7 +68,12 @@ def main():
     ap.add_argument("--config", default="C",
                     help="C (default): T10 bar, 972 000 elements per GPU; B: T10 cube, 10 368 elements; D/A: ANCF")
     ap.add_argument("--rel-tol", type=float, default=1e-12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel durations and roofline fractions, "
+                         "element-stage and per-stage times, communication time per step (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--max-pcg", type=int, default=50000, help="cap on PCG iterations (kernel experiments only)")
     ap.add_argument("--cheb-deg", type=int, default=0, help="Chebyshev preconditioner degree (1 = block-Jacobi, 0 = auto)")
     ap.add_argument("--prewarm-s", type=float, default=1.0,
@@ -194,6 +202,7 @@ def main():
     nnz_coef = int(d.RetrieveMassCSRToCPU()[0][-1])
 
     step_ms = []
+    last_norm_g = [float("nan")]
 
     def run(k, count_from=0):
         its = []
@@ -203,6 +212,7 @@ def main():
                 s.BeginStep()
             ng, it = s.NewtonIteration()   # returns ||g||: the host has the result, i.e. the iteration is complete
             its.append(it)
+            last_norm_g[0] = ng
             step_ms.append(round((time.perf_counter() - t_it) * 1e3, 3))
         return its
 
@@ -242,85 +252,88 @@ def main():
     value = E * world * args.steps / dt
     if os.environ.get("TLFEA_BENCH_VERBOSE") and rank == 0:
         print("per-iteration ms (warm-up first):", step_ms, "CG iterations:", pcg_its, file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d, s, last_norm_g[0])
 
-    # ---- per-kernel durations, live, hipEvents on the launch stream (separate pass: adds host syncs) ------
-    s.SetProfiling(True)
-    s.GetStageMs(reset=True)
-    nprof = max(3, min(args.steps, 9))
-    cs_prof0 = s.GetCommStats()
-    run(nprof, args.warmup + args.steps)
-    torch.cuda.synchronize()
-    cs_prof1 = s.GetCommStats()
-    st = s.GetStageMs(reset=True)
-    s.SetProfiling(False)
     deg_eff, bits_eff, vec_bits = s.GetLinSolveInfo()
-    ab = alg_bytes(E_local, N, nnz_coef, d.S, d.Q, bits_eff, vec_bits)
+    pmg = s.GetPmgInfo()                              # (coarse nodes, coarse blocks, coarse polynomial degree) | None
+    cyc = s.GetPmgCycleInfo() if pmg else None
     fused = s.GetAssemblyMode() >= 2  # one fused tangent + assembly launch instead of tangent_blocks + assemble_rows
     fkey = "assemble_affine" if s.GetAssemblyMode() == 3 else "assemble_direct"
-    if fused:   # the residual launch also writes what the fused assembly stages: F at every point
-        ab["residual"] += E_local * (80 if fkey == "assemble_affine" else 72) * d.Q   # (general form: 72 B, affine form: 80 B per point)
-    # mean launch duration: `reps` back-to-back launches per kernel between one hipEvent pair on the launch stream
-    # (kernel time + same-stream boundary; agrees with rocprofv3 --kernel-trace, profiles/*kernel_stats.csv)
-    kt = s.TimeKernels(reps=40 if E < 200000 else 10)
-    if fused:
-        kt[fkey] = kt.pop("assemble_rows")
-        st = dict(st, **{fkey: st["assemble_rows"]})
-        st.pop("assemble_rows")
-        st["tangent_blocks"] = (0.0, 0)
-    roof_all = {}
-    n_outer = st["spmv"][1] // max(1, deg_eff)       # stage counter tallies deg launches per outer iteration
-    pmg = s.GetPmgInfo()                              # (coarse nodes, coarse blocks, coarse polynomial degree) | None
-    if pmg:   # V-cycle: 4 fine-level steps (2-term smoother before and after) + kc-1 coarse-level steps per CG iteration
-        ab["cheb_step_coarse"] = pmg[1] * (9 * bits_eff // 8 + 4) + pmg[0] * (24 + 48 + 72 + 48 + 24) * vec_bits // 64
-        # The polynomial-step kernel runs as three instantiations per CG iteration: fine level, non-final (3 launches: the
-        # `cheb_step` entry, the iteration's largest share), fine level, final (1 launch, writes z in fp64 and the r.z
-        # slots; same matrix stream, timed with the non-final ones), coarse level (kc - 1 launches).  They are reported
-        # separately: the coarse level's 74 MB per launch live in the 256 MB Infinity Cache, so ITS rate is cache
-        # bandwidth and must not be averaged into an HBM fraction.
-        cyc = s.GetPmgCycleInfo()
-        # two levels: kc - 1 vertex-level steps; three levels: 2 x vertex_terms smoothing passes on the vertex level and a
-        # degree-k3 polynomial on the (few thousand) rigid-body-mode nodes below it
-        ncs = 2 * cyc["vertex_terms"] if cyc["levels"] == 3 else pmg[2] - 1
-        st = dict(st, spmv=(st["spmv"][0], n_outer), cheb_step=(0.0, n_outer * (2 * cyc["fine_terms"] - 1)),
-                  cheb_step_coarse=(0.0, n_outer * ncs))
-    else:
-        st = dict(st, spmv=(st["spmv"][0], n_outer), cheb_step=(0.0, n_outer * (deg_eff - 1)))
-    for k in ("residual", "tangent_blocks", "assemble_rows", "assemble_direct", "assemble_affine", "spmv", "cheb_step",
-              "cheb_step_coarse"):
-        if k not in st:
-            continue
-        ms, n = st[k]
-        if n == 0:
-            continue
-        avg_s = kt[k] * 1e-3
-        ach = ab[k] / avg_s / 1e9
-        roof_all[k] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                       "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "avg_us": round(avg_s * 1e6, 2),
-                       "launches": n, "alg_bytes": ab[k], "total_ms": round(kt[k] * n, 3)}
-    pmc, pmc_file = load_pmc_traffic(args.config) if world == 1 else ({}, None)
-    for k, v in roof_all.items():
-        if k in pmc:
-            v["traffic"] = pmc[k]
-            v["traffic_note"] = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, {pmc_file}): (2*FETCH_SIZE + "
-                                 "WRITE_SIZE)*1024 B per launch; FETCH_SIZE counts 64 B per 128-B request on gfx950, calibrated "
-                                 "for this engine's 8-/16-byte and scattered-row loads with tools/microbench/pmc_calib.hip")
-    if pmg and "cheb_step" in roof_all and "cheb_step_coarse" in roof_all:   # (absent with --linsolve-method 1)
-        roof_all["cheb_step"]["note"] = ("fine level of the V-cycle, non-final instantiation: 3 launches per CG iteration "
-                                         "(the 4th fine pass is the final instantiation, same stream, not in `launches`)")
-        roof_all["cheb_step_coarse"]["note"] = ("coarse level of the V-cycle: 74 MB per launch, resident in the 256 MB Infinity "
-                                                "Cache -- cache bandwidth, NOT an HBM fraction; listed for completeness")
-        roof_all["cheb_step_coarse"]["bound"] = "infinity-cache"
-    # dominant = the single kernel instantiation with the largest total time (the cache-resident coarse step is not an
-    # HBM-roofline candidate)
-    dominant = max((k for k in roof_all if k != "cheb_step_coarse"), key=lambda k: roof_all[k]["total_ms"])
-    roofline = dict(roof_all[dominant], kernel=dominant)
-    if args.linsolve_method == 1:
-        roofline["note"] = ("--linsolve-method 1: the step is the multifrontal factorisation (fp64 FMA bound, see `linear_solver`); the "
-                            "kernel priced here is the largest of the HBM-bound launches that remain")
-    elem_keys = ("residual", "grad", fkey) if fused else ("residual", "grad", "tangent_blocks", "assemble_rows")
-    elem_ms = sum(st[k][0] for k in elem_keys) / nprof
-    b_alg = 4 * d.S + 24 * d.S * d.Q + 8 * d.Q + 24 * d.S + 72.0 * nnz_coef / E + 24.0 * N / E
-    stage_share = {k: round(st[k][0] / nprof, 4) for k in elem_keys + ("pcg", "update")}
+    if args.full:
+        # ---- per-kernel durations, live, hipEvents on the launch stream (separate pass: adds host syncs) ------
+        s.SetProfiling(True)
+        s.GetStageMs(reset=True)
+        nprof = max(3, min(args.steps, 9))
+        cs_prof0 = s.GetCommStats()
+        run(nprof, args.warmup + args.steps)
+        torch.cuda.synchronize()
+        cs_prof1 = s.GetCommStats()
+        st = s.GetStageMs(reset=True)
+        s.SetProfiling(False)
+        ab = alg_bytes(E_local, N, nnz_coef, d.S, d.Q, bits_eff, vec_bits)
+        if fused:   # the residual launch also writes what the fused assembly stages: F at every point
+            ab["residual"] += E_local * (80 if fkey == "assemble_affine" else 72) * d.Q   # (general form: 72 B, affine form: 80 B per point)
+        # mean launch duration: `reps` back-to-back launches per kernel between one hipEvent pair on the launch stream
+        # (kernel time + same-stream boundary; agrees with rocprofv3 --kernel-trace, profiles/*kernel_stats.csv)
+        kt = s.TimeKernels(reps=40 if E < 200000 else 10)
+        if fused:
+            kt[fkey] = kt.pop("assemble_rows")
+            st = dict(st, **{fkey: st["assemble_rows"]})
+            st.pop("assemble_rows")
+            st["tangent_blocks"] = (0.0, 0)
+        roof_all = {}
+        n_outer = st["spmv"][1] // max(1, deg_eff)       # stage counter tallies deg launches per outer iteration
+        if pmg:   # V-cycle: 4 fine-level steps (2-term smoother before and after) + kc-1 coarse-level steps per CG iteration
+            ab["cheb_step_coarse"] = pmg[1] * (9 * bits_eff // 8 + 4) + pmg[0] * (24 + 48 + 72 + 48 + 24) * vec_bits // 64
+            # The polynomial-step kernel runs as three instantiations per CG iteration: fine level, non-final (3 launches: the
+            # `cheb_step` entry, the iteration's largest share), fine level, final (1 launch, writes z in fp64 and the r.z
+            # slots; same matrix stream, timed with the non-final ones), coarse level (kc - 1 launches).  They are reported
+            # separately: the coarse level's 74 MB per launch live in the 256 MB Infinity Cache, so ITS rate is cache
+            # bandwidth and must not be averaged into an HBM fraction.
+            # two levels: kc - 1 vertex-level steps; three levels: 2 x vertex_terms smoothing passes on the vertex level and a
+            # degree-k3 polynomial on the (few thousand) rigid-body-mode nodes below it
+            ncs = 2 * cyc["vertex_terms"] if cyc["levels"] == 3 else pmg[2] - 1
+            st = dict(st, spmv=(st["spmv"][0], n_outer), cheb_step=(0.0, n_outer * (2 * cyc["fine_terms"] - 1)),
+                      cheb_step_coarse=(0.0, n_outer * ncs))
+        else:
+            st = dict(st, spmv=(st["spmv"][0], n_outer), cheb_step=(0.0, n_outer * (deg_eff - 1)))
+        for k in ("residual", "tangent_blocks", "assemble_rows", "assemble_direct", "assemble_affine", "spmv", "cheb_step",
+                  "cheb_step_coarse"):
+            if k not in st:
+                continue
+            ms, n = st[k]
+            if n == 0:
+                continue
+            avg_s = kt[k] * 1e-3
+            ach = ab[k] / avg_s / 1e9
+            roof_all[k] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "avg_us": round(avg_s * 1e6, 2),
+                           "launches": n, "alg_bytes": ab[k], "total_ms": round(kt[k] * n, 3)}
+        pmc, pmc_file = load_pmc_traffic(args.config) if world == 1 else ({}, None)
+        for k, v in roof_all.items():
+            if k in pmc:
+                v["traffic"] = pmc[k]
+                v["traffic_note"] = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, {pmc_file}): (2*FETCH_SIZE + "
+                                     "WRITE_SIZE)*1024 B per launch; FETCH_SIZE counts 64 B per 128-B request on gfx950, calibrated "
+                                     "for this engine's 8-/16-byte and scattered-row loads with tools/microbench/pmc_calib.hip")
+        if pmg and "cheb_step" in roof_all and "cheb_step_coarse" in roof_all:   # (absent with --linsolve-method 1)
+            roof_all["cheb_step"]["note"] = ("fine level of the V-cycle, non-final instantiation: 3 launches per CG iteration "
+                                             "(the 4th fine pass is the final instantiation, same stream, not in `launches`)")
+            roof_all["cheb_step_coarse"]["note"] = ("coarse level of the V-cycle: 74 MB per launch, resident in the 256 MB Infinity "
+                                                    "Cache -- cache bandwidth, NOT an HBM fraction; listed for completeness")
+            roof_all["cheb_step_coarse"]["bound"] = "infinity-cache"
+        # dominant = the single kernel instantiation with the largest total time (the cache-resident coarse step is not an
+        # HBM-roofline candidate)
+        dominant = max((k for k in roof_all if k != "cheb_step_coarse"), key=lambda k: roof_all[k]["total_ms"])
+        roofline = dict(roof_all[dominant], kernel=dominant)
+        if args.linsolve_method == 1:
+            roofline["note"] = ("--linsolve-method 1: the step is the multifrontal factorisation (fp64 FMA bound, see `linear_solver`); the "
+                                "kernel priced here is the largest of the HBM-bound launches that remain")
+        elem_keys = ("residual", "grad", fkey) if fused else ("residual", "grad", "tangent_blocks", "assemble_rows")
+        elem_ms = sum(st[k][0] for k in elem_keys) / nprof
+        b_alg = 4 * d.S + 24 * d.S * d.Q + 8 * d.Q + 24 * d.S + 72.0 * nnz_coef / E + 24.0 * N / E
+        stage_share = {k: round(st[k][0] / nprof, 4) for k in elem_keys + ("pcg", "update")}
 
     comm_report = {}
     if world > 1:
@@ -337,12 +350,15 @@ def main():
                                                                 (cs1["allreduces_in_cg"] - cs0["allreduces_in_cg"])) / args.steps, 2),
             "bytes_per_neighbour_exchange": round((cs1["bytes_exchanged"] - cs0["bytes_exchanged"]) / max(1, dx), 1),
             "bytes_per_allreduce": round((cs1["bytes_allreduced"] - cs0["bytes_allreduced"]) / max(1, da), 1),
-            # profiling pass (eager launches, hipEvent pair around every exchange / all-reduce on the launch stream, rank 0)
-            "comm_ms_per_step": round((cs_prof1["comm_ms"] - cs_prof0["comm_ms"]) / nprof, 4),
-            "comm_note": "comm_ms_per_step: device time inside neighbour exchanges and all-reduces per Newton iteration on "
-                         "rank 0, eager profiling pass; the timed region replays them inside hipGraphs with the built-in "
-                         "RCCL exchange",
         }
+        if args.full:
+            comm_report.update({
+                # profiling pass (eager launches, hipEvent pair around every exchange / all-reduce on the launch stream, rank 0)
+                "comm_ms_per_step": round((cs_prof1["comm_ms"] - cs_prof0["comm_ms"]) / nprof, 4),
+                "comm_note": "comm_ms_per_step: device time inside neighbour exchanges and all-reduces per Newton iteration on "
+                             "rank 0, eager profiling pass; the timed region replays them inside hipGraphs with the built-in "
+                             "RCCL exchange",
+            })
 
     out = {
         "metric": "T10-tet element-updates/sec per Newton step", "value": round(value, 1), "unit": "element-updates/s",
@@ -378,22 +394,24 @@ def main():
                                       f"{'scaled fp%d copy of H' % bits_eff if bits_eff != 64 else 'fp64 H'} "
                                       f"with fp{vec_bits} work vectors; "
                                       "outer CG, residual and convergence test in fp64 on H")},
-        "element_stage": {"ms_per_step": round(elem_ms, 4), "value": round(E / (elem_ms * 1e-3), 1),
-                          # connectivity + grad N + det J + x gather + H written once + f_int
-                          "alg_bytes_per_element": round(b_alg, 1),
-                          "roofline_frac": round(E * b_alg / (elem_ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4),
-                          "kernels": list(elem_keys),
-                          "note": "residual+gradient+tangent+assembly only (no linear solve), profiling pass; "
-                                  "roofline_frac = E * alg_bytes_per_element / time / 8 TB/s"},
-        "stage_ms_per_step": stage_share,
-        "prewarm": {"seconds": args.prewarm_s, "newton_iterations": n_prewarm,
-                    "note": "untimed device warm-up before the W warm-up steps; state reset afterwards"},
-        "roofline": roofline, "roofline_all": roof_all,
     }
+    if args.full:
+        out["element_stage"] = {"ms_per_step": round(elem_ms, 4), "value": round(E / (elem_ms * 1e-3), 1),
+                                # connectivity + grad N + det J + x gather + H written once + f_int
+                                "alg_bytes_per_element": round(b_alg, 1),
+                                "roofline_frac": round(E * b_alg / (elem_ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4),
+                                "kernels": list(elem_keys),
+                                "note": "residual+gradient+tangent+assembly only (no linear solve), profiling pass; "
+                                        "roofline_frac = E * alg_bytes_per_element / time / 8 TB/s"}
+        out["stage_ms_per_step"] = stage_share
+    out["prewarm"] = {"seconds": args.prewarm_s, "newton_iterations": n_prewarm,
+                      "note": "untimed device warm-up before the W warm-up steps; state reset afterwards"}
+    if args.full:
+        out["roofline"], out["roofline_all"] = roofline, roof_all
 
     if is_ancf:
         out["metric"] = "ANCF element-updates/sec per Newton step (not the BASELINE metric: T10 is)"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not is_ancf:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not is_ancf:
         out["cpu_baseline"] = cpu_baseline(w, args)
     del s
     d.Destroy()
@@ -401,6 +419,25 @@ def main():
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ROWS = 1_000_000   # position + velocity (24 B each per row) + row index (8 B): at most 56 MB in all
+
+
+def dump_outputs(out_dir, d, s, norm_g):
+    """What a caller of the timed path holds after its last step, as float64 arrays in out_dir:
+      position.npy (k, 3)  positions x, y, z (T10: nodes; ANCF: coefficient vectors)
+      velocity.npy (k, 3)  the Newton solver's velocities, same rows
+      rows.npy     (k,)    indices of those rows: all of them, or a fixed seeded sample of DUMP_MAX_ROWS
+      norm_g.npy   (1,)    the ||g|| that NewtonIteration() returned"""
+    os.makedirs(out_dir, exist_ok=True)
+    x = np.stack(d.RetrievePositionToCPU(), axis=1)
+    v = s.RetrieveVelocityToCPU().reshape(x.shape)
+    rows = np.arange(x.shape[0])
+    if rows.size > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(12345).choice(rows.size, DUMP_MAX_ROWS, replace=False))
+    for name, a in (("position", x[rows]), ("velocity", v[rows]), ("rows", rows), ("norm_g", [norm_g])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def load_pmc_traffic(config):

@@ -146,7 +146,7 @@ def test_direct_reports_indefinite_matrix():
 @pytest.mark.skipif(not os.environ.get("TLFEA_TEST_DIRECT"),
                     reason="opt-in TLFEA_TEST_DIRECT=1: the rocSOLVER backend maps librocsolver/librocsparse/librocblas "
                            "(1.4 GB of code objects, 4-7 minutes cold on a fresh box; profiles/r03_direct_solver_tests.log)")
-def test_rocsolver_backend_in_its_own_process():
+def test_rocsolver_backend_in_its_own_process(tmp_path):
     """The rocSOLVER backend against the engine's own factorisation, in a child process (a process that has mapped
     /opt/rocm's rocBLAS must not import torch afterwards)."""
     code = (
@@ -165,8 +165,7 @@ def test_rocsolver_backend_in_its_own_process():
         "assert rel < 1e-9\n")
     outs = []
     for be in ("native", "rocsolver"):
-        out = os.path.join(ROOT, "gpurun_out", f"direct_{be}.npy")
-        os.makedirs(os.path.dirname(out), exist_ok=True)
+        out = str(tmp_path / f"direct_{be}.npy")
         env = dict(os.environ, TLFEA_DIRECT_BACKEND=be, OUT=out)
         subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, check=True, timeout=840)
         outs.append(np.load(out))

@@ -8,7 +8,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 run() { # name precond env...
   name=$1; pre=$2; shift 2
-  env "$@" python bench.py --no-cpu-baseline --config $CFG --steps 4 --warmup 2 --max-pcg 400 --precond $pre > $O/$name.json 2> $O/$name.err || { tail -3 $O/$name.err; return; }
+  env "$@" python bench.py --full --no-cpu-baseline --config $CFG --steps 4 --warmup 2 --max-pcg 400 --precond $pre > $O/$name.json 2> $O/$name.err || { tail -3 $O/$name.err; return; }
   python - <<PY
 import json
 j=json.loads(open("$O/$name.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/${1:-sweepBig}
 mkdir -p $O
 run() { name=$1; cfg=$2; shift; shift
-  env "$@" python bench.py --no-cpu-baseline --config $cfg --steps 9 --warmup 3 --prewarm-s 0 > $O/$name.json 2> $O/$name.err || { tail -3 $O/$name.err; }
+  env "$@" python bench.py --full --no-cpu-baseline --config $cfg --steps 9 --warmup 3 --prewarm-s 0 > $O/$name.json 2> $O/$name.err || { tail -3 $O/$name.err; }
   if grep -q "Memory access fault" $O/$name.err; then echo "GPU fault in $name: stopping"; exit 9; fi
   [ -s $O/$name.json ] || return
   python - <<PY

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/${1:-sweepB12}
 mkdir -p $O
 run() { name=$1; shift; args=$1; shift
-  env "$@" python bench.py --no-cpu-baseline --config D --steps 6 --warmup 2 $args > $O/$name.json 2> $O/$name.err || { tail -3 $O/$name.err; }
+  env "$@" python bench.py --full --no-cpu-baseline --config D --steps 6 --warmup 2 $args > $O/$name.json 2> $O/$name.err || { tail -3 $O/$name.err; }
   if grep -q "Memory access fault" $O/$name.err; then echo "GPU fault in $name: stopping"; exit 9; fi
   [ -s $O/$name.json ] || return
   python - <<PY

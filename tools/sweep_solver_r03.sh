@@ -8,7 +8,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 run() { # name env...
   name=$1; shift
-  env "$@" python bench.py --no-cpu-baseline --config C --steps 6 --warmup 2 > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; return; }
+  env "$@" python bench.py --full --no-cpu-baseline --config C --steps 6 --warmup 2 > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; return; }
   python - <<PY
 import json
 j=json.loads(open("$O/$name.json").read().strip().splitlines()[-1])
