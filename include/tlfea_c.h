@@ -417,6 +417,56 @@ int tlfea_vbd_retrieve_lambda(tlfea_vbd_t a, double *lam);
 int tlfea_vbd_get_stats(tlfea_vbd_t a, double *out6);
 int tlfea_vbd_set_verbose(tlfea_vbd_t a, int v);
 
+/* ---- HydroelasticPatchCollisionSystem (lib_src/collision/HydroelasticPatchCollisionSystem.h) ------------------------
+ * Hydroelastic contact between tetrahedral meshes (T10 or T4): per-element AABB broadphase on a uniform grid,
+ * one narrowphase work item per candidate pair (the plane where the two affine corner-pressure fields are equal,
+ * clipped by both tets), and p_eq * area along the patch normal (optional normal damping and regularised friction)
+ * distributed to the 8 corner nodes with the barycentric weights of the centroid.  The nodal sum is atomic-free and
+ * bitwise reproducible: every node adds its contributions in patch order.  Pairs come out sorted by
+ * (lower element id, higher element id).  Positions are read each step from a bound element object or a bound device
+ * buffer; every launch runs on the default stream. */
+typedef struct tlfea_contact_s *tlfea_contact_t;
+/* ContactPatch (HydroelasticCollisionTypes / HydroelasticNarrowphase.cuh): tetA is on the mesh with the lower id; the
+ * normal points from tet A into tet B; a patch with isValid == 0 or validOrientation == 0 applies no force */
+typedef struct {
+  double vertices[8][3];
+  int count;
+  double normal[3];
+  double centroid[3];
+  double area, g_A, g_B, p_equilibrium;
+  int tetA, tetB;
+  int isValid, validOrientation;
+} tlfea_contact_patch;
+/* ctor HydroelasticPatchCollisionSystem(nodes, elements, pressure, elementMeshIds, enableSelfCollision):
+ * conn column-major n_elems x nodes_per_elem (10 or 4; the first 4 are the corners), pressure per node,
+ * elem_mesh_ids per element (NULL: all elements on mesh 0).  Deviation: no neighbour set is built here -- with
+ * self-collision the broadphase compares the node ids of a same-mesh candidate pair directly (equivalent filter) -- and
+ * the node -> contribution lists of the force sum are rebuilt every step from that step's patches */
+int tlfea_contact_create(int n_nodes, int n_elems, int nodes_per_elem, const int *conn_colmajor, const double *pressure,
+                         const int *elem_mesh_ids, int self_collision, tlfea_contact_t *out);
+int tlfea_contact_destroy(tlfea_contact_t c); /* dtor */
+/* BindNodesDevicePtr: positions from the element object's own x / y / z buffers, read at every step (no copy) */
+int tlfea_contact_bind_t10(tlfea_contact_t c, tlfea_t10_t data);
+/* BindNodesDevicePtr(d_nodes): a device buffer [x..., y..., z...] of n_nodes nodes, read at every step */
+int tlfea_contact_bind_nodes(tlfea_contact_t c, const double *d_colmajor, int n_nodes);
+/* Step(CollisionSystemInput{d_vel}, CollisionSystemParams{damping, friction}): broadphase, narrowphase and the nodal
+ * contact forces into the context's 3N buffer (xyz-interleaved); d_vel: device 3N interleaved velocities or NULL */
+int tlfea_contact_step(tlfea_contact_t c, const double *d_vel, double damping, double friction);
+/* engine extra: a host 3N force (gravity and the like) copied once and added by tlfea_contact_apply_to_t10 */
+int tlfea_contact_set_base_force(tlfea_contact_t c, const double *f, int n);
+/* engine extra: f_ext of the bound element object = base + contact force, on the device */
+int tlfea_contact_apply_to_t10(tlfea_contact_t c);
+/* GetExternalForcesDevicePtr */
+double *tlfea_contact_force_device_ptr(tlfea_contact_t c);
+/* GetNumContacts: candidate pairs of the last step */
+int tlfea_contact_num_pairs(tlfea_contact_t c, int *n);
+/* patches of the last step with isValid set */
+int tlfea_contact_num_patches(tlfea_contact_t c, int *n);
+/* RetrieveResults: pairs [n_pairs][2] (lower element id first), patches [n_pairs] in pair order, forces [3N] */
+int tlfea_contact_retrieve_pairs(tlfea_contact_t c, int *pairs);
+int tlfea_contact_retrieve_patches(tlfea_contact_t c, tlfea_contact_patch *patches);
+int tlfea_contact_retrieve_force(tlfea_contact_t c, double *f);
+
 #ifdef __cplusplus
 }
 #endif

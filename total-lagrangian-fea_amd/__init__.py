@@ -15,6 +15,9 @@ from .solvers import (SyncedNewtonParams, SyncedNewtonSolver, LinSolveOpts, Sync
                       SyncedVBDSolver)
 from . import mesh_utils, quadrature  # noqa: F401
 from .mesh_manager import MeshManager  # noqa: F401
+from .contact import (CollisionSystemInput, CollisionSystemParams, ContactPatch,  # noqa: F401
+                      HydroelasticPatchCollisionSystem)
 
-__all__ = ["GPU_FEAT10_Data", "GPU_ANCF3243_Data", "GPU_ANCF3443_Data", "SyncedNewtonSolver", "SyncedNewtonParams", "LinSolveOpts", "SyncedAdamWNocoopSolver", "SyncedAdamWNocoopParams", "SyncedAdamWSolver", "SyncedAdamWParams", "SyncedNesterovSolver", "SyncedNesterovParams", "SyncedVBDSolver", "SyncedVBDParams", "mesh_utils", "MeshManager",
+__all__ = ["GPU_FEAT10_Data", "GPU_ANCF3243_Data", "GPU_ANCF3443_Data", "SyncedNewtonSolver", "SyncedNewtonParams", "LinSolveOpts", "SyncedAdamWNocoopSolver", "SyncedAdamWNocoopParams", "SyncedAdamWSolver", "SyncedAdamWParams", "SyncedNesterovSolver", "SyncedNesterovParams", "SyncedVBDSolver", "SyncedVBDParams", "mesh_utils", "MeshManager", "HydroelasticPatchCollisionSystem",
+           "CollisionSystemInput", "CollisionSystemParams", "ContactPatch",
            "quadrature", "load_library", "device_count", "TlfeaError", "LIB_PATH", "exported_symbols"]

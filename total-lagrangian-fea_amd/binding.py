@@ -55,6 +55,30 @@ class LinSolveOptsC(C.Structure):
                 ("on_unconverged", C.c_int)]
 
 
+class ContactPatchC(C.Structure):  # tlfea_contact_patch == ContactPatch (HydroelasticNarrowphase.cuh)
+    _fields_ = [("vertices", (C.c_double * 3) * 8), ("count", C.c_int), ("normal", C.c_double * 3),
+                ("centroid", C.c_double * 3), ("area", C.c_double), ("g_A", C.c_double), ("g_B", C.c_double),
+                ("p_equilibrium", C.c_double), ("tetA", C.c_int), ("tetB", C.c_int), ("isValid", C.c_int),
+                ("validOrientation", C.c_int)]
+
+
+def _contact_signatures(lib):
+    """ctypes signatures of the tlfea_contact_* entry points (pointer arguments are c_void_p: device pointers pass as
+    integers, host arrays through dp / ip)."""
+    vp, i, d = C.c_void_p, C.c_int, C.c_double
+    sig = {"tlfea_contact_create": [i, i, i, c_ip, c_dp, c_ip, i, C.POINTER(C.c_void_p)],
+           "tlfea_contact_destroy": [vp], "tlfea_contact_bind_t10": [vp, vp], "tlfea_contact_bind_nodes": [vp, vp, i],
+           "tlfea_contact_step": [vp, vp, d, d], "tlfea_contact_set_base_force": [vp, c_dp, i],
+           "tlfea_contact_apply_to_t10": [vp], "tlfea_contact_num_pairs": [vp, c_ip],
+           "tlfea_contact_num_patches": [vp, c_ip], "tlfea_contact_retrieve_pairs": [vp, c_ip],
+           "tlfea_contact_retrieve_patches": [vp, C.POINTER(ContactPatchC)], "tlfea_contact_retrieve_force": [vp, c_dp]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+    lib.tlfea_contact_force_device_ptr.argtypes = [vp]
+    lib.tlfea_contact_force_device_ptr.restype = vp
+
+
 def exported_symbols():
     """Names of every function declared in include/tlfea_c.h (parsed from the header)."""
     txt = open(HEADER_PATH).read()
@@ -100,6 +124,7 @@ def load_library():
                  "tlfea_vbd_velocity_guess_device_ptr"):
         getattr(lib, name).restype = C.c_void_p
         getattr(lib, name).argtypes = [C.c_void_p]
+    _contact_signatures(lib)
     _LIB = lib
     return lib
 

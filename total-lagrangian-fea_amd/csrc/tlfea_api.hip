@@ -127,6 +127,8 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
 };
 
 extern "C" const char* tlfea_last_error(void) { return g_err.c_str(); }
+// the other C-ABI translation units (contact_api.hip) report through the same message
+int tlfea::api_fail(const std::string& msg) { return fail(msg); }
 extern "C" int tlfea_version(void) { return 100; }
 extern "C" int tlfea_device_count(void) {
   int n = 0;

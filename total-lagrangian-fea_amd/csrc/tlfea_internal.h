@@ -5,10 +5,14 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <string>
 
 #include "mf_host.h"
 
 namespace tlfea {
+
+// sets the message of tlfea_last_error(), prints it on stderr and returns 1 (tlfea_api.hip)
+int api_fail(const std::string& msg);
 
 constexpr int kNQ = 5;      // T10: Keast 5-point rule (quadrature_utils.h:134)
 constexpr int kNN = 10;     // T10: nodes per element

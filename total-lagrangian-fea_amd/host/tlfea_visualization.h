@@ -3,8 +3,8 @@
 // :848-955 ExportANCF3443ToVTU, :974-1097 ExportANCF3243ToVTU).  Same static member names / argument order under
 // ANCFCPUUtils::VisualizationUtils, same ASCII UnstructuredGrid layout (precision 15, scientific) so that ParaView
 // states written for the reference's files open these.  One emitter serves all of them: a writer hands it the points,
-// the cells (fixed arity) and optional point data.  The contact-patch exporters (VTP/CSV/JSON) belong to the collision
-// subsystem and are not built.  Included by tlfea_facade.h.
+// the cells (fixed arity) and optional point data.  The contact-patch exporters (VTP/CSV/JSON) of the collision subsystem
+// are not built: RetrieveResults / GetValidPatches of tlfea_collision.h hand the patches to the host.  Included by tlfea_facade.h.
 #pragma once
 #include <array>
 #include <cmath>
