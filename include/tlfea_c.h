@@ -85,6 +85,20 @@ int tlfea_t10_set_damping(tlfea_t10_t h, double eta_damp, double lambda_damp); /
 int tlfea_t10_set_svk_select(tlfea_t10_t h);                                   /* SetSVK() :568-587 */
 int tlfea_t10_set_svk(tlfea_t10_t h, double E, double nu);                     /* SetSVK(E,nu) :594-611 */
 int tlfea_t10_set_mooney_rivlin(tlfea_t10_t h, double mu10, double mu01, double kappa); /* :618-634 */
+
+/* Per-element materials (no reference counterpart).  A table of n_mat entries (1..256) and one id per element
+ * (elem_material[E], each in 0..n_mat-1); `model` (0 SVK: E, nu; 1 Mooney-Rivlin: mu10, mu01, kappa) applies to every
+ * entry.  After Setup only, T10 handles only.  Stiffness and damping take effect at the next evaluation, the densities
+ * at the next CalcMassMatrix (the mass matrix assembled before keeps its densities).  While a table is set, the uniform
+ * setters (set_svk, set_mooney_rivlin, set_density, set_damping) fail, and so do tlfea_newton_set_halo and
+ * tlfea_newton_set_interface.  clear returns the object to its uniform material; a mass matrix assembled under the
+ * table is dropped (CalcMassMatrix again).  get: n_mat (0 = uniform) and, when elem_material is not null and a table
+ * is set, the E ids. */
+typedef struct { double E, nu, mu10, mu01, kappa, rho0, eta, lamd; } tlfea_material_entry;
+int tlfea_t10_set_element_materials(tlfea_t10_t h, int model, int n_mat, const tlfea_material_entry *table,
+                                    const int *elem_material, int n_elem);
+int tlfea_t10_clear_element_materials(tlfea_t10_t h);
+int tlfea_t10_get_element_materials(tlfea_t10_t h, int *n_mat, int *elem_material);
 int tlfea_t10_set_external_force(tlfea_t10_t h, const double *f_ext, int n);   /* :636-646 (n must be 3N) */
 int tlfea_t10_set_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed);    /* FEAT10Data.cu:728-749 */
 int tlfea_t10_update_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed); /* FEAT10Data.cu:751-832 */

@@ -9,7 +9,7 @@ Import with importlib (the directory name carries a hyphen):
     tl = importlib.import_module("total-lagrangian-fea_amd")
 """
 from .binding import (LIB_PATH, TlfeaError, load_library, device_count, exported_symbols)  # noqa: F401
-from .elements import GPU_ANCF3243_Data, GPU_ANCF3443_Data, GPU_FEAT10_Data  # noqa: F401
+from .elements import ElementMaterial, GPU_ANCF3243_Data, GPU_ANCF3443_Data, GPU_FEAT10_Data  # noqa: F401
 from .solvers import (SyncedNewtonParams, SyncedNewtonSolver, LinSolveOpts, SyncedAdamWNocoopParams,  # noqa: F401
                       SyncedAdamWNocoopSolver, SyncedAdamWSolver, SyncedAdamWParams, SyncedNesterovParams, SyncedNesterovSolver, SyncedVBDParams,
                       SyncedVBDSolver)
@@ -18,6 +18,6 @@ from .mesh_manager import MeshManager  # noqa: F401
 from .contact import (CollisionSystemInput, CollisionSystemParams, ContactPatch,  # noqa: F401
                       HydroelasticPatchCollisionSystem)
 
-__all__ = ["GPU_FEAT10_Data", "GPU_ANCF3243_Data", "GPU_ANCF3443_Data", "SyncedNewtonSolver", "SyncedNewtonParams", "LinSolveOpts", "SyncedAdamWNocoopSolver", "SyncedAdamWNocoopParams", "SyncedAdamWSolver", "SyncedAdamWParams", "SyncedNesterovSolver", "SyncedNesterovParams", "SyncedVBDSolver", "SyncedVBDParams", "mesh_utils", "MeshManager", "HydroelasticPatchCollisionSystem",
+__all__ = ["GPU_FEAT10_Data", "ElementMaterial", "GPU_ANCF3243_Data", "GPU_ANCF3443_Data", "SyncedNewtonSolver", "SyncedNewtonParams", "LinSolveOpts", "SyncedAdamWNocoopSolver", "SyncedAdamWNocoopParams", "SyncedAdamWSolver", "SyncedAdamWParams", "SyncedNesterovSolver", "SyncedNesterovParams", "SyncedVBDSolver", "SyncedVBDParams", "mesh_utils", "MeshManager", "HydroelasticPatchCollisionSystem",
            "CollisionSystemInput", "CollisionSystemParams", "ContactPatch",
            "quadrature", "load_library", "device_count", "TlfeaError", "LIB_PATH", "exported_symbols"]

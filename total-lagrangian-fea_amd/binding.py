@@ -62,6 +62,20 @@ class ContactPatchC(C.Structure):  # tlfea_contact_patch == ContactPatch (Hydroe
                 ("validOrientation", C.c_int)]
 
 
+class MaterialEntryC(C.Structure):  # tlfea_material_entry
+    _fields_ = [(n, C.c_double) for n in ("E", "nu", "mu10", "mu01", "kappa", "rho0", "eta", "lamd")]
+
+
+def _material_signatures(lib):
+    """ctypes signatures of the per-element material entry points."""
+    vp, i = C.c_void_p, C.c_int
+    sig = {"tlfea_t10_set_element_materials": [vp, i, i, C.POINTER(MaterialEntryC), c_ip, i],
+           "tlfea_t10_clear_element_materials": [vp], "tlfea_t10_get_element_materials": [vp, c_ip, c_ip]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+
+
 def _contact_signatures(lib):
     """ctypes signatures of the tlfea_contact_* entry points (pointer arguments are c_void_p: device pointers pass as
     integers, host arrays through dp / ip)."""
@@ -125,6 +139,7 @@ def load_library():
         getattr(lib, name).restype = C.c_void_p
         getattr(lib, name).argtypes = [C.c_void_p]
     _contact_signatures(lib)
+    _material_signatures(lib)
     _LIB = lib
     return lib
 

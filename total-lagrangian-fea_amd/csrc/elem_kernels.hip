@@ -32,6 +32,7 @@
 #include "pair_runs.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace tlfea {
 
@@ -265,8 +266,9 @@ __device__ __forceinline__ void wave_sync() {
 // residual: fused compute_p + compute_internal_force (FEAT10DataFunc.cuh:85-293,397-458)
 // thread per element; fbuf[e][a][d] = sum_q (P_q grad N_a) detJ_q w_q
 // ------------------------------------------------------------------------------------------------
-template <int S, int Q, bool STORE, bool MASS>
-__global__ __launch_bounds__(128) void residual_kernel(ElemView m, Material mat, const double* __restrict__ v,
+// MT: Material (one material, by value) or MaterialPE (per-element records, loaded once per thread at the top)
+template <int S, int Q, bool STORE, bool MASS, class MT = Material>
+__global__ __launch_bounds__(128) void residual_kernel(ElemView m, MT mat_in, const double* __restrict__ v,
                                                       double* __restrict__ fbuf, double* __restrict__ Fo,
                                                       double* __restrict__ Po, double* __restrict__ Fdo,
                                                       double* __restrict__ Pvo, double* __restrict__ Fq, MassTerm mt,
@@ -285,6 +287,8 @@ __global__ __launch_bounds__(128) void residual_kernel(ElemView m, Material mat,
     if (!kTr) return;
     e = m.E - 1;  // lanes past the end stay for the transposes: they recompute the last element and store its values again
   }
+  constexpr bool kPE = !std::is_same<MT, Material>::value;
+  const Material mat = mat_at(mat_in, e);
   const bool damp = (v != nullptr) && (mat.eta != 0.0 || mat.lamd != 0.0);  // FEAT10DataFunc.cuh:137
   int gn[S];
   double xn[S][3];
@@ -314,7 +318,8 @@ __global__ __launch_bounds__(128) void residual_kernel(ElemView m, Material mat,
       for (int a = 0; a < S; a++)
 #pragma unroll
         for (int i = 0; i < 3; i++) w[i] += mt.Nq[q][a < kNN ? a : 0] * dv[a][i];
-      cq[q] = mt.rho_inv_h * m.detJ[(size_t)e * Q + q] * m.qw[q];
+      // per-element: rho_inv_h is 1/h and the element's mass-matrix density comes from its record
+      cq[q] = (kPE ? mat.rho0 * mt.rho_inv_h : mt.rho_inv_h) * m.detJ[(size_t)e * Q + q] * m.qw[q];
 #pragma unroll
       for (int i = 0; i < 3; i++) Wq[q][i] = w[i];
     }
@@ -486,27 +491,30 @@ __global__ __launch_bounds__(128) void residual_kernel(ElemView m, Material mat,
     for (int i = 0; i < 3; i++) out[a * 3 + i] = f[a][i];
 }
 
-template <int S, int Q>
-static void launch_residual_t(hipStream_t s, const ElemView& m, const Material& mat, const double* v, double* fbuf,
+template <int S, int Q, class MT = Material>
+static void launch_residual_t(hipStream_t s, const ElemView& m, const MT& mat, const double* v, double* fbuf,
                               double* F, double* P, double* Fdot, double* Pvis, double* Fq, const MassTerm* mt,
                               double fq_h, int fq_slots) {
   const dim3 grid((m.E + 127) / 128), block(128);
   MassTerm none{};
   none.vprev = nullptr;
   if (F)
-    hipLaunchKernelGGL((residual_kernel<S, Q, true, false>), grid, block, 0, s, m, mat, v, fbuf, F, P, Fdot, Pvis, Fq, none,
+    hipLaunchKernelGGL((residual_kernel<S, Q, true, false, MT>), grid, block, 0, s, m, mat, v, fbuf, F, P, Fdot, Pvis, Fq, none,
                        fq_h, fq_slots);
   else if (S == kNN && mt && mt->vprev && v)
-    hipLaunchKernelGGL((residual_kernel<S, Q, false, (S == kNN)>), grid, block, 0, s, m, mat, v, fbuf, nullptr, nullptr,
+    hipLaunchKernelGGL((residual_kernel<S, Q, false, (S == kNN), MT>), grid, block, 0, s, m, mat, v, fbuf, nullptr, nullptr,
                        nullptr, nullptr, Fq, *mt, fq_h, fq_slots);
   else
-    hipLaunchKernelGGL((residual_kernel<S, Q, false, false>), grid, block, 0, s, m, mat, v, fbuf, nullptr, nullptr, nullptr,
+    hipLaunchKernelGGL((residual_kernel<S, Q, false, false, MT>), grid, block, 0, s, m, mat, v, fbuf, nullptr, nullptr, nullptr,
                        nullptr, Fq, none, fq_h, fq_slots);
 }
 
 void launch_residual(hipStream_t s, const ElemView& m, const Material& mat, const double* v, double* fbuf, double* F,
-                     double* P, double* Fdot, double* Pvis, double* Fq, const MassTerm* mt, double fq_h, int fq_slots) {
-  if (m.S == 10) launch_residual_t<10, 5>(s, m, mat, v, fbuf, F, P, Fdot, Pvis, Fq, mt, fq_h, fq_slots);
+                     double* P, double* Fdot, double* Pvis, double* Fq, const MassTerm* mt, double fq_h, int fq_slots,
+                     const double* emat) {
+  if (emat && m.S == 10)  // per-element materials: T10 only (the C-ABI refuses a table on the ANCF kinds)
+    launch_residual_t<10, 5, MaterialPE>(s, m, MaterialPE{mat, emat}, v, fbuf, F, P, Fdot, Pvis, Fq, mt, fq_h, fq_slots);
+  else if (m.S == 10) launch_residual_t<10, 5>(s, m, mat, v, fbuf, F, P, Fdot, Pvis, Fq, mt, fq_h, fq_slots);
   else if (m.S == 8) launch_residual_t<8, 12>(s, m, mat, v, fbuf, F, P, Fdot, Pvis, Fq, nullptr, 0.0, 0);
   else launch_residual_t<16, 48>(s, m, mat, v, fbuf, F, P, Fdot, Pvis, Fq, nullptr, 0.0, 0);
 }
@@ -777,8 +785,8 @@ struct TangentLds {
 
 // WPB wavefronts per workgroup, one element each (own LDS slice); all waves run the same barrier sequence, so
 // __syncthreads() stays legal; WPB > 1 cuts the workgroup dispatch count (972k single-wave groups at config C).
-template <int S, int Q, int QC, int MODEL, int WPB>
-__global__ __launch_bounds__(64 * WPB, (S == 16 && MODEL == kSVK && WPB == 1) ? 3 : 1) void tangent_blocks_kernel(ElemView m, Material mat, double h,
+template <int S, int Q, int QC, int MODEL, int WPB, class MT = Material>  // MT: as residual_kernel
+__global__ __launch_bounds__(64 * WPB, (S == 16 && MODEL == kSVK && WPB == 1) ? 3 : 1) void tangent_blocks_kernel(ElemView m, MT mat_in, double h,
                                                                  double* __restrict__ Kbuf) {
   using LD = TangentLds<S, Q, QC, MODEL>;
   constexpr int P = LD::kPairs;
@@ -793,6 +801,7 @@ __global__ __launch_bounds__(64 * WPB, (S == 16 && MODEL == kSVK && WPB == 1) ? 
   const int e_raw = blockIdx.x * WPB + (threadIdx.x >> 6);
   const bool live = e_raw < E;
   const int e = live ? e_raw : E - 1;  // idle waves shadow the last element (they must still hit every barrier)
+  const Material mat = mat_at(mat_in, e);
   const int lane = threadIdx.x & 63;
   // one wavefront per workgroup: LDS hand-offs need program order only (wave_sync), not s_barrier + s_waitcnt vmcnt(0) --
   // which would also drain the next chunk's gradient loads issued ahead of the pair loop
@@ -1109,8 +1118,16 @@ static void launch_tangent_t(hipStream_t s, const ElemView& m, const Material& m
     hipLaunchKernelGGL((tangent_blocks_kernel<S, Q, QC, kSVK, 1>), dim3(m.E), dim3(64), 0, s, m, mat, h, Kbuf);
 }
 
-void launch_tangent_blocks(hipStream_t s, const ElemView& m, const Material& mat, double h, double* Kbuf) {
-  if (m.S == 10) launch_tangent_t<10, 5, 5>(s, m, mat, h, Kbuf);
+void launch_tangent_blocks(hipStream_t s, const ElemView& m, const Material& mat, double h, double* Kbuf,
+                           const double* emat) {
+  if (emat && m.S == 10) {  // per-element materials (T10): one wave per element, its record read at the top
+    const MaterialPE pe{mat, emat};
+    if (mat.model == kMooneyRivlin)
+      hipLaunchKernelGGL((tangent_blocks_kernel<10, 5, 5, kMooneyRivlin, 1, MaterialPE>), dim3(m.E), dim3(64), 0, s, m, pe, h,
+                         Kbuf);
+    else
+      hipLaunchKernelGGL((tangent_blocks_kernel<10, 5, 5, kSVK, 1, MaterialPE>), dim3(m.E), dim3(64), 0, s, m, pe, h, Kbuf);
+  } else if (m.S == 10) launch_tangent_t<10, 5, 5>(s, m, mat, h, Kbuf);
   else if (m.S == 8) launch_tangent_t<8, 12, 6>(s, m, mat, h, Kbuf);
   else launch_tangent_t<16, 48, 6>(s, m, mat, h, Kbuf);
 }
@@ -1259,8 +1276,10 @@ __device__ __forceinline__ void store_through(double* p, double v, int mode) {
 //   q = F^-T h_j, fb = F h_j, fcb = F C h_j (column side, 27 multiply-adds per lane and point),
 // checked against the tensor form to round-off (tests/test_gpu_parity.py::test_hessian[mr|neo|mr_damped]); the
 // Kelvin-Voigt block has the same rank-1 structure and rides on the same vectors.
-template <int ROLLED, int EXP, int MR = 0>  // ROLLED 0: points unrolled (234 VGPRs, 2 waves per SIMD), 1: rolled (168 VGPRs, 3 waves per SIMD)
-__global__ __launch_bounds__(64, (ROLLED && !MR) ? 3 : 2) void assemble_direct_kernel(ElemView m, Material mat, double h, RowGroups rg,
+// MT: Material, or MaterialPE (per-element materials: the staging lanes load the record of their instance's element with
+// its F, at the top of the pass; the coefficients live until the records are staged, never across a pass)
+template <int ROLLED, int EXP, int MR = 0, class MT = Material>  // ROLLED 0: points unrolled (234 VGPRs, 2 waves per SIMD), 1: rolled (168 VGPRs, 3 waves per SIMD)
+__global__ __launch_bounds__(64, (ROLLED && !MR) ? 3 : 2) void assemble_direct_kernel(ElemView m, MT mat_in, double h, RowGroups rg,
                                                                const double* __restrict__ Fq,
                                                                const double* __restrict__ mval, double inv_h,
                                                                const int* __restrict__ fixed_slot,
@@ -1348,6 +1367,7 @@ __global__ __launch_bounds__(64, (ROLLED && !MR) ? 3 : 2) void assemble_direct_k
     double mh = 0.0;
     if (act && pk < 0) mh = mval[mb + (pk & 0xffff) / 3];
     const int es = (store_mode & 256) ? 0 : code_s / kNN;
+    const Material mat = mat_at(mat_in, es);
     double F[9], s0 = 0.0;  // s0: det J (material half)
     if (stager) {
       // the 72 bytes of F as four 16-byte loads + one: the five points of an element are contiguous, so the 30 lanes of
@@ -1575,7 +1595,42 @@ __global__ __launch_bounds__(64, (ROLLED && !MR) ? 3 : 2) void assemble_direct_k
 
 void launch_assemble_direct(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups& rg,
                             const double* Fq, const double* mval, const int* fixed_slot, const double* nw,
-                            double penalty, double* Hval) {
+                            double penalty, double* Hval, const double* emat) {
+  if (emat) {
+    // per-element materials: the default forms (rolled SVK, Mooney-Rivlin) with the records; no tuning knobs
+    const MaterialPE pe{mat, emat};
+    const bool mr = mat.model == kMooneyRivlin;
+    const size_t lds = (size_t)((mr ? kAdInst * kNQ * kAdRecMR : kAdRecTotal) + kAdHraw + rg.acc_max) * sizeof(double);
+    const void* fn = mr ? (const void*)assemble_direct_kernel<1, 0, 1, MaterialPE>
+                        : (const void*)assemble_direct_kernel<1, 0, 0, MaterialPE>;
+    static size_t lds_attr_pe[2] = {0, 0};
+    if (lds > 64 * 1024 && lds > lds_attr_pe[mr]) {
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      lds_attr_pe[mr] = lds;
+    }
+    static int n_cu_pe = 0;
+    if (!n_cu_pe) {
+      int dev = 0;
+      (void)hipGetDevice(&dev);
+      (void)hipDeviceGetAttribute(&n_cu_pe, hipDeviceAttributeMultiprocessorCount, dev);
+      if (n_cu_pe <= 0) n_cu_pe = 256;
+    }
+    static size_t occ_lds_pe[2] = {~(size_t)0, ~(size_t)0};
+    static int occ_pe[2] = {4, 4};
+    if (occ_lds_pe[mr] != lds) {
+      int o = 0;
+      occ_pe[mr] = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, 64, lds) == hipSuccess && o > 0) ? o : 4;
+      occ_lds_pe[mr] = lds;
+    }
+    const int per_xcd = std::max(1, std::min((n_cu_pe / 8) * std::min(occ_pe[mr], mr ? 8 : 12), (rg.G + 7) / 8));
+    if (mr)
+      hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 1, MaterialPE>), dim3(8 * per_xcd), dim3(64), lds, s, m, pe, h, rg, Fq,
+                         mval, 1.0 / h, fixed_slot, nw, penalty, Hval, 0);
+    else
+      hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 0, MaterialPE>), dim3(8 * per_xcd), dim3(64), lds, s, m, pe, h, rg, Fq,
+                         mval, 1.0 / h, fixed_slot, nw, penalty, Hval, 0);
+    return;
+  }
   if (mat.model == kMooneyRivlin) {
     // Mooney-Rivlin: the same walk with 60-double records (assemble_direct_kernel<1, 0, 1>); one form, no tuning knobs
     const size_t lds = (size_t)(kAdInst * kNQ * kAdRecMR + kAdHraw + rg.acc_max) * sizeof(double);
@@ -1679,6 +1734,7 @@ namespace {
 constexpr int kAfInst = 16;                 // instances per pass
 constexpr int kAfRec = 66;                  // doubles per staged instance: 16 (g, det J) + 5 x 10 (F at the points)
 constexpr int kAfStage = kAfInst * kAfRec;  // 1 056 doubles = 8.25 KiB
+constexpr int kAfRecPE = 72;                // per-element materials: + lambda, mu | eta, lamd | kappa, rho of the mass
 }  // namespace
 
 __global__ void affine_pre_kernel(ElemView m, AffineView av, double* __restrict__ gvec, double* __restrict__ dev_max) {
@@ -1731,9 +1787,17 @@ void launch_affine_pre(hipStream_t s, const ElemView& m, const AffineView& av, d
 struct AffineCoef {  // per rule point in the kernel's order (q0, then q_0 .. q_3 = the record slots the residual launch writes)
   double cA[5], cB[5], cC[5], cL[5];  // w_q (h lambda + lamd), w_q (h mu + eta), w_q h mu, w_q h lambda   (x det J)
 };
+// per-element materials: the same four coefficients per element, formed from the element's record (staged with the
+// instance's g and F records, kAfRecPE) when the pass evaluates it; qw: weight of the centroid point | the outer points
+struct AffineCoefPE {
+  double qw[2], h;
+  const double* emat;  // [E][kEmRec]
+};
 
-template <int TIMING, int EXP>  // EXP: as assemble_direct_kernel (experiment bits honoured by the tools-only instantiation)
-__global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, AffineCoef ac,
+// EXP: as assemble_direct_kernel (experiment bits honoured by the tools-only instantiation); AC: AffineCoef, or
+// AffineCoefPE for per-element materials
+template <int TIMING, int EXP, class AC = AffineCoef>
+__global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, AC ac,
                                                                 const double* __restrict__ gvec,
                                                                 const double* __restrict__ Fq16,
                                                                 const double* __restrict__ cmass, double mscale,
@@ -1742,10 +1806,12 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
                                                                 double* __restrict__ Hval, int store_mode_arg,
                                                                 unsigned long long* __restrict__ tdbg) {
   const int store_mode = EXP ? store_mode_arg : (store_mode_arg & 3);
+  constexpr bool kPE = !std::is_same<AC, AffineCoef>::value;
+  constexpr int kRec = kPE ? kAfRecPE : kAfRec, kStage = kAfInst * kRec;
   extern __shared__ __attribute__((aligned(16))) double lds_af[];
-  double* stage = lds_af;                  // [kAfInst][kAfRec]
-  double* cml = lds_af + kAfStage;         // [10][16] mass coefficients of (row node, vertex n, p) x rho / h
-  double* acc = lds_af + kAfStage + 160;   // the group's rows, each in H's layout [d][3 deg]
+  double* stage = lds_af;                  // [kAfInst][kRec]
+  double* cml = lds_af + kStage;           // [10][16] mass coefficients of (row node, vertex n, p) x rho / h (per-element: x 1/h)
+  double* acc = lds_af + kStage + 160;     // the group's rows, each in H's layout [d][3 deg]
   // same walk as assemble_direct_kernel: XCD x owns a contiguous range of groups, its resident waves take them side by side
   const int W = gridDim.x >> 3;
   const int Gper = (rg.G + 7) >> 3;
@@ -1809,10 +1875,10 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
   if (lane < (ecur.y >> 8)) ri_n = rg.gr_info[ecur.z + lane];
   int fs = -1;
   double wv = 1.0;
-  double* Sk = stage + k * kAfRec;
+  double* Sk = stage + k * kRec;
   // records in flight: the four lanes of an instance fetch its 528 bytes (g record + F at the five points) 16 at a
   // time, one pass ahead of the pass that computes, so that a pass never waits for a round trip to memory
-  double2 sa, sb, s0, s1, s2, s3, s4, s5, s6 = make_double2(0.0, 0.0);
+  double2 sa, sb, s0, s1, s2, s3, s4, s5, s6 = make_double2(0.0, 0.0), sm = make_double2(0.0, 0.0);
   auto fetch = [&](const int2& hd) __attribute__((always_inline)) {
     const int e = (store_mode & 256) ? 0 : hd.x / kNN;
     const double2* gp = reinterpret_cast<const double2*>(gvec + (size_t)e * 16) + n;
@@ -1820,6 +1886,9 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
     sa = gp[0]; sb = gp[4];
     s0 = fp[0]; s1 = fp[4]; s2 = fp[8]; s3 = fp[12]; s4 = fp[16]; s5 = fp[20];
     if (n == 0) s6 = fp[24];  // 25 16-byte pieces: the last one has one taker
+    if constexpr (kPE) {      // the element's record: lanes 0, 1, 2 take slots 0-1, 2-3, 6-7
+      if (n < 3) sm = reinterpret_cast<const double2*>(ac.emat + (size_t)e * kEmRec)[n == 2 ? 3 : n];
+    }
   };
   fetch(head);
 
@@ -1868,6 +1937,7 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
       S2[0] = sa; S2[4] = sb;
       S2[8] = s0; S2[12] = s1; S2[16] = s2; S2[20] = s3; S2[24] = s4; S2[28] = s5;
       if (n == 0) S2[32] = s6;
+      if (kPE && n < 3) S2[33] = sm;  // doubles 66..71
     }
     wave_sync();
     TLFEA_TICK(1)  // records into LDS (waits for the loads of the previous pass)
@@ -1884,6 +1954,16 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
       gB[0] = b01.x; gB[1] = b01.y; gB[2] = Sk[4 * B + 2];
       gn[0] = n01.x; gn[1] = n01.y; gn[2] = Sk[4 * n + 2];
       detJ = Sk[3];
+    }
+    // per-element materials: the instance's coefficients, formed once per pass from its staged record
+    double eA = 0.0, eB = 0.0, eC = 0.0, eL = 0.0, eR = 0.0;
+    if constexpr (kPE) {
+      const double2 lm = *reinterpret_cast<const double2*>(Sk + 66), ed = *reinterpret_cast<const double2*>(Sk + 68);
+      eA = ac.h * lm.x + ed.y;
+      eB = ac.h * lm.y + ed.x;
+      eC = ac.h * lm.y;
+      eL = ac.h * lm.x;
+      eR = Sk[71];
     }
     TLFEA_TICK(2)  // next pass's loads issued, g / mass coefficients read
     double R0[9], D[4][9];
@@ -1921,9 +2001,19 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
                    b2 = F6 * gn[0] + F7 * gn[1] + F8 * gn[2];
       const double sv = h0 * gn[0] + h1 * gn[1] + h2 * gn[2];  // grad N_i . g_n
       const double tv = fi0 * b0 + fi1 * b1 + fi2 * b2;        // F grad N_i . F g_n
-      const double A1 = detJ * (ci ? ac.cA[1] : ac.cA[0]), B1 = detJ * (ci ? ac.cB[1] : ac.cB[0]),
-                   C1 = detJ * (ci ? ac.cC[1] : ac.cC[0]);
-      const double C0 = detJ * (ci ? ac.cL[1] : ac.cL[0]) * trE - C1;  // dV h (lambda tr E - mu)   (SVK.cuh:35-55)
+      double A1, B1, C1, C0;
+      if constexpr (kPE) {
+        const double wq = ci ? ac.qw[1] : ac.qw[0];
+        A1 = detJ * (wq * eA);
+        B1 = detJ * (wq * eB);
+        C1 = detJ * (wq * eC);
+        C0 = detJ * (wq * eL) * trE - C1;
+      } else {
+        A1 = detJ * (ci ? ac.cA[1] : ac.cA[0]);
+        B1 = detJ * (ci ? ac.cB[1] : ac.cB[0]);
+        C1 = detJ * (ci ? ac.cC[1] : ac.cC[0]);
+        C0 = detJ * (ci ? ac.cL[1] : ac.cL[0]) * trE - C1;  // dV h (lambda tr E - mu)   (SVK.cuh:35-55)
+      }
       const double cd = C0 * sv + C1 * tv;
       const double sb1 = sv * B1;                              // (grad N_i . g_n) B1 F F^T
       const double u0 = A1 * fi0, u1 = A1 * fi1, u2 = A1 * fi2;
@@ -1952,7 +2042,7 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
     {
       const double* cq = cml + il * 16 + 4 * n;
 #pragma unroll
-      for (int r = 0; r < 4; r++) cmv[r] = detJ * cq[(n + r) & 3];
+      for (int r = 0; r < 4; r++) cmv[r] = (kPE ? detJ * eR : detJ) * cq[(n + r) & 3];
     }
     TLFEA_TICK(3)  // five block evaluations
     // ---- (5) the lane's blocks into the row accumulator ------------------------------------------------------------
@@ -2049,7 +2139,38 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
 
 void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups4& rg,
                             const AffineView& av, const double* Fq16, const double* cmass, double rho0,
-                            const int* fixed_slot, const double* nw, double penalty, double* Hval) {
+                            const int* fixed_slot, const double* nw, double penalty, double* Hval, const double* emat) {
+  if (emat) {
+    // per-element materials: the default form (no timing, no experiment bits) on 72-double records
+    const void* fpe = (const void*)assemble_affine_kernel<0, 0, AffineCoefPE>;
+    const size_t lds = (size_t)(kAfInst * kAfRecPE + 160 + rg.acc_max) * sizeof(double);
+    static size_t lds_attr_pe = 0, occ_lds_pe = ~(size_t)0;
+    static int n_cu_pe = 0, occ_pe = 8;
+    if (lds > 64 * 1024 && lds > lds_attr_pe) {
+      (void)hipFuncSetAttribute(fpe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      lds_attr_pe = lds;
+    }
+    if (!n_cu_pe) {
+      int dev = 0;
+      (void)hipGetDevice(&dev);
+      (void)hipDeviceGetAttribute(&n_cu_pe, hipDeviceAttributeMultiprocessorCount, dev);
+      if (n_cu_pe <= 0) n_cu_pe = 256;
+    }
+    if (occ_lds_pe != lds) {
+      int o = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fpe, 64, lds) == hipSuccess && o > 0) occ_pe = o;
+      occ_lds_pe = lds;
+    }
+    const int per_xcd = std::max(1, std::min((n_cu_pe / 8) * occ_pe, (rg.G + 7) / 8));
+    AffineCoefPE ac;
+    ac.qw[0] = m.qw[av.q0];
+    ac.qw[1] = m.qw[av.qv[0]];  // the four outer points carry one weight (checked by the solver's set-up)
+    ac.h = h;
+    ac.emat = emat;
+    hipLaunchKernelGGL((assemble_affine_kernel<0, 0, AffineCoefPE>), dim3(8 * per_xcd), dim3(64), lds, s, rg, ac, av.gvec, Fq16,
+                       cmass, rho0 / h, fixed_slot, nw, penalty, Hval, 0, nullptr);
+    return;
+  }
   const void* fn = (const void*)assemble_affine_kernel<0, 0>;
   const size_t lds = (size_t)(kAfStage + 160 + rg.acc_max) * sizeof(double);
   static size_t lds_attr = 0;
@@ -2116,9 +2237,10 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
 // ------------------------------------------------------------------------------------------------
 // consistent mass (FEAT10Data.cu:206-278), row-owner form: thread per node row, fixed order
 // ------------------------------------------------------------------------------------------------
+template <bool PE>  // PE: per-element densities (slot kEmRhoM of emat), rho0 unused
 __global__ void mass_values_kernel(ElemView m, Incidence inc, const double* __restrict__ qx,
                                    const double* __restrict__ qy, const double* __restrict__ qz, double rho0,
-                                   double* __restrict__ mval) {
+                                   double* __restrict__ mval, const double* __restrict__ emat) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m.N) return;
   const int edges[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};
@@ -2137,17 +2259,22 @@ __global__ void mass_values_kernel(ElemView m, Incidence inc, const double* __re
     const int code = inc.n2e[k];
     const int e = code / 10, il = code - e * 10;
     const int* pos = inc.n2e_pos + (size_t)k * 10;
+    const double rho = PE ? emat[(size_t)e * kEmRec + kEmRhoM] : rho0;
     for (int j = 0; j < kNN; j++) {
       double s = 0.0;
-      for (int q = 0; q < kNQ; q++) s += rho0 * Nq[q][il] * Nq[q][j] * m.detJ[e * kNQ + q] * m.qw[q];
+      for (int q = 0; q < kNQ; q++) s += rho * Nq[q][il] * Nq[q][j] * m.detJ[e * kNQ + q] * m.qw[q];
       mval[off0 + pos[j]] += s;
     }
   }
 }
 
 void launch_mass_values(hipStream_t s, const ElemView& m, const Incidence& inc, const double* qx, const double* qy,
-                        const double* qz, double rho0, double* mval) {
-  hipLaunchKernelGGL(mass_values_kernel, dim3((m.N + 127) / 128), dim3(128), 0, s, m, inc, qx, qy, qz, rho0, mval);
+                        const double* qz, double rho0, double* mval, const double* emat) {
+  if (emat)
+    hipLaunchKernelGGL(mass_values_kernel<true>, dim3((m.N + 127) / 128), dim3(128), 0, s, m, inc, qx, qy, qz, rho0, mval, emat);
+  else
+    hipLaunchKernelGGL(mass_values_kernel<false>, dim3((m.N + 127) / 128), dim3(128), 0, s, m, inc, qx, qy, qz, rho0, mval,
+                       nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2220,8 +2347,8 @@ __device__ __forceinline__ void vbd_diag_block(const double F[3][3], const doubl
     }
 }
 
-template <int S, int Q, int LPN, int MODEL, bool DAMP>
-__global__ __launch_bounds__(256) void vbd_color_kernel(ElemView m, Material mat_in, Incidence inc,
+template <int S, int Q, int LPN, int MODEL, bool DAMP, class MT = Material>  // MT: as residual_kernel (record per item)
+__global__ __launch_bounds__(256) void vbd_color_kernel(ElemView m, MT mat_in, Incidence inc,
                                                         const int* __restrict__ nodes, int count,
                                                         const double* __restrict__ mval, const double* __restrict__ f_ext,
                                                         const int* __restrict__ fixed_slot, const double* __restrict__ xt,
@@ -2238,7 +2365,8 @@ __global__ __launch_bounds__(256) void vbd_color_kernel(ElemView m, Material mat
   if (slot >= count) return;  // whole group
   const int i = nodes[slot];
   const double inv_h = 1.0 / h;
-  Material mat = mat_in;
+  constexpr bool kPE = !std::is_same<MT, Material>::value;
+  Material mat = mat_at(mat_in, 0);
   mat.model = MODEL;  // compile-time material and damping: the other branch's registers (42 doubles of Mooney-Rivlin
   constexpr bool damp = DAMP;  // state, the 9 of Fdot) are not reserved -- occupancy is what hides the gathers here
   double acc[12];
@@ -2257,6 +2385,10 @@ __global__ __launch_bounds__(256) void vbd_color_kernel(ElemView m, Material mat
     const int k = w / Q, q = w - k * Q;
     const int code = inc.n2e[i0 + k];
     const int e = code / S, a = code - e * S;
+    if constexpr (kPE) {
+      mat = mat_at(mat_in, e);
+      mat.model = MODEL;
+    }
     const double* g = m.gradN + ((size_t)e * Q + q) * 3 * S;
     double F[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Fd[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
 #pragma unroll 2
@@ -2388,8 +2520,8 @@ void launch_interleave_xyz(hipStream_t s, int N, const double* x, const double* 
   hipLaunchKernelGGL(interleave_xyz_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, x, y, z, xyz);
 }
 
-template <int S, int Q, int MODEL, bool DAMP>
-static void launch_vbd_color_t(hipStream_t s, int lanes, const ElemView& m, const Material& mat, const Incidence& inc,
+template <int S, int Q, int MODEL, bool DAMP, class MT = Material>
+static void launch_vbd_color_t(hipStream_t s, int lanes, const ElemView& m, const MT& mat, const Incidence& inc,
                                const int* nodes, int count, const double* mval, const double* f_ext, const int* fixed_slot,
                                const double* xt, const double* yt, const double* zt, const double* lam, double h, double rho,
                                double omega, double hess_eps, const double* v_prev, const double* xp, const double* yp,
@@ -2397,9 +2529,9 @@ static void launch_vbd_color_t(hipStream_t s, int lanes, const ElemView& m, cons
                                double* xyz) {
   const dim3 block(256), grid((count + 256 / lanes - 1) / (256 / lanes));
 #define TLFEA_VBD_ARGS m, mat, inc, nodes, count, mval, f_ext, fixed_slot, xt, yt, zt, lam, h, rho, omega, hess_eps, v_prev, xp, yp, zp, v, x, y, z, conn_rm, xyz
-  if (lanes == 16) hipLaunchKernelGGL((vbd_color_kernel<S, Q, 16, MODEL, DAMP>), grid, block, 0, s, TLFEA_VBD_ARGS);
-  else if (lanes == 32) hipLaunchKernelGGL((vbd_color_kernel<S, Q, 32, MODEL, DAMP>), grid, block, 0, s, TLFEA_VBD_ARGS);
-  else hipLaunchKernelGGL((vbd_color_kernel<S, Q, 64, MODEL, DAMP>), grid, block, 0, s, TLFEA_VBD_ARGS);
+  if (lanes == 16) hipLaunchKernelGGL((vbd_color_kernel<S, Q, 16, MODEL, DAMP, MT>), grid, block, 0, s, TLFEA_VBD_ARGS);
+  else if (lanes == 32) hipLaunchKernelGGL((vbd_color_kernel<S, Q, 32, MODEL, DAMP, MT>), grid, block, 0, s, TLFEA_VBD_ARGS);
+  else hipLaunchKernelGGL((vbd_color_kernel<S, Q, 64, MODEL, DAMP, MT>), grid, block, 0, s, TLFEA_VBD_ARGS);
 #undef TLFEA_VBD_ARGS
 }
 
@@ -2426,8 +2558,22 @@ void launch_vbd_color(hipStream_t s, int lanes, const ElemView& m, const Materia
                       const int* nodes, int count, const double* mval, const double* f_ext, const int* fixed_slot,
                       const double* xt, const double* yt, const double* zt, const double* lam, double h, double rho,
                       double omega, double hess_eps, const double* v_prev, const double* xp, const double* yp,
-                      const double* zp, double* v, double* x, double* y, double* z, const int* conn_rm, double* xyz) {
+                      const double* zp, double* v, double* x, double* y, double* z, const int* conn_rm, double* xyz,
+                      const double* emat, bool emat_damp) {
   if (count <= 0) return;
+  if (emat && m.S == 10) {  // per-element materials (T10): each item reads its element's record
+    const MaterialPE pe{mat, emat};
+#define TLFEA_VBD_FWD s, lanes, m, pe, inc, nodes, count, mval, f_ext, fixed_slot, xt, yt, zt, lam, h, rho, omega, hess_eps, v_prev, xp, yp, zp, v, x, y, z, conn_rm, xyz
+    if (mat.model == kMooneyRivlin) {
+      if (emat_damp) launch_vbd_color_t<10, 5, kMooneyRivlin, true, MaterialPE>(TLFEA_VBD_FWD);
+      else launch_vbd_color_t<10, 5, kMooneyRivlin, false, MaterialPE>(TLFEA_VBD_FWD);
+    } else {
+      if (emat_damp) launch_vbd_color_t<10, 5, kSVK, true, MaterialPE>(TLFEA_VBD_FWD);
+      else launch_vbd_color_t<10, 5, kSVK, false, MaterialPE>(TLFEA_VBD_FWD);
+    }
+#undef TLFEA_VBD_FWD
+    return;
+  }
 #define TLFEA_VBD_FWD s, lanes, m, mat, inc, nodes, count, mval, f_ext, fixed_slot, xt, yt, zt, lam, h, rho, omega, hess_eps, v_prev, xp, yp, zp, v, x, y, z, conn_rm, xyz
   if (m.S == 10) launch_vbd_color_m<10, 5>(TLFEA_VBD_FWD);
   else if (m.S == 8) launch_vbd_color_m<8, 12>(TLFEA_VBD_FWD);

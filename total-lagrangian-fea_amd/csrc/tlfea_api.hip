@@ -81,6 +81,16 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   double *d_fbuf = nullptr, *d_fint = nullptr, *d_fext = nullptr;
   Material mat{kSVK, 0, 0, 0, 0, 0, 0, 0, 0};
   double E_mod = 0, nu = 0;
+  // per-element materials (tlfea_t10_set_element_materials): null d_emat = one material (mat) for every element.  While
+  // a table is set, mat.model is the table's model and mat_saved the uniform material that ClearElementMaterials restores
+  double* d_emat = nullptr;         // [E][kEmRec], tlfea_internal.h
+  int n_mat = 0;
+  bool emat_damp = false;           // some entry has eta or lamd != 0
+  std::vector<double> h_table;      // [n_mat][kEmRec] (slot kEmRhoM: the entry's density)
+  std::vector<int> h_eid;           // [E]
+  std::vector<double> h_rho_mass;   // [E] density each element's share of the mass matrix was assembled with
+  bool mass_pe = false;             // the mass matrix was assembled from h_rho_mass under a table
+  Material mat_saved{kSVK, 0, 0, 0, 0, 0, 0, 0, 0};
   // constraints
   double* d_cons = nullptr;
   int *d_fixed = nullptr, *d_fixed_slot = nullptr;
@@ -189,7 +199,7 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_gradN, h->d_gradN_t, h->d_detJ, h->d_F, h->d_P, h->d_Fdot, h->d_Pvis, h->d_fbuf, h->d_fint,
                   h->d_fext, h->d_cons, h->d_fixed, h->d_fixed_slot, h->d_off, h->d_cols, h->d_n2e_off, h->d_n2e,
                   h->d_n2e_pos, h->d_diagpos, h->d_mval, h->d_joff, h->d_jcol, h->d_jtoff, h->d_jtcol, h->d_jval,
-                  h->d_jtval, h->d_rhs};
+                  h->d_jtval, h->d_rhs, h->d_emat};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -237,15 +247,21 @@ extern "C" int tlfea_t10_setup(tlfea_t10_t h, const double* qx, const double* qy
 
 #define NEED_SETUP(h, what) \
   if (!(h) || !(h)->is_setup) return fail(std::string("GPU_FEAT10_Data must be set up before ") + what)
+#define NO_TABLE(h, what)                                                                                               \
+  if ((h)->d_emat)                                                                                                    \
+  return fail(std::string(what) + ": per-element materials are set (tlfea_t10_set_element_materials); clear them first " \
+                                  "(tlfea_t10_clear_element_materials)")
 
 extern "C" int tlfea_t10_set_density(tlfea_t10_t h, double rho0) {
   NEED_SETUP(h, "setting density.");
+  NO_TABLE(h, "tlfea_t10_set_density");
   h->gen++;
   h->mat.rho0 = rho0;
   return 0;
 }
 extern "C" int tlfea_t10_set_damping(tlfea_t10_t h, double eta, double lamd) {
   NEED_SETUP(h, "setting damping.");
+  NO_TABLE(h, "tlfea_t10_set_damping");
   h->gen++;
   h->mat.eta = eta;
   h->mat.lamd = lamd;
@@ -253,6 +269,7 @@ extern "C" int tlfea_t10_set_damping(tlfea_t10_t h, double eta, double lamd) {
 }
 extern "C" int tlfea_t10_set_svk_select(tlfea_t10_t h) {
   NEED_SETUP(h, "setting material.");
+  NO_TABLE(h, "tlfea_t10_set_svk_select");
   h->gen++;
   h->mat.model = kSVK;
   h->mat.mu10 = h->mat.mu01 = h->mat.kappa = 0.0;
@@ -260,6 +277,7 @@ extern "C" int tlfea_t10_set_svk_select(tlfea_t10_t h) {
 }
 extern "C" int tlfea_t10_set_svk(tlfea_t10_t h, double E, double nu) {
   NEED_SETUP(h, "setting material.");
+  NO_TABLE(h, "tlfea_t10_set_svk");
   h->E_mod = E;
   h->nu = nu;
   h->mat.mu = E / (2 * (1 + nu));
@@ -268,6 +286,7 @@ extern "C" int tlfea_t10_set_svk(tlfea_t10_t h, double E, double nu) {
 }
 extern "C" int tlfea_t10_set_mooney_rivlin(tlfea_t10_t h, double mu10, double mu01, double kappa) {
   NEED_SETUP(h, "setting material.");
+  NO_TABLE(h, "tlfea_t10_set_mooney_rivlin");
   h->gen++;
   h->mat.model = kMooneyRivlin;
   h->mat.mu10 = mu10;
@@ -275,6 +294,99 @@ extern "C" int tlfea_t10_set_mooney_rivlin(tlfea_t10_t h, double mu10, double mu
   h->mat.kappa = kappa;
   return 0;
 }
+// ---- per-element materials --------------------------------------------------------------------------------------------
+// the device records of every element: the entry of its id, with the density its mass-matrix share was assembled with
+static int upload_emat(tlfea_t10_t h) {
+  const int E = h->E;
+  std::vector<double> rec((size_t)E * kEmRec);
+  for (int e = 0; e < E; e++) {
+    std::copy_n(&h->h_table[(size_t)h->h_eid[e] * kEmRec], kEmRec, &rec[(size_t)e * kEmRec]);
+    rec[(size_t)e * kEmRec + kEmRhoM] = h->h_rho_mass[e];
+  }
+  if (!h->d_emat) TRY(dmalloc(&h->d_emat, rec.size()));
+  HIP_TRY(hipMemcpy(h->d_emat, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+extern "C" int tlfea_t10_set_element_materials(tlfea_t10_t h, int model, int n_mat, const tlfea_material_entry* table,
+                                               const int* elem_material, int n_elem) {
+  if (h && h->kind != kT10) return fail("tlfea_t10_set_element_materials: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "setting element materials.");
+  if (model != kSVK && model != kMooneyRivlin)
+    return fail("tlfea_t10_set_element_materials: unknown model " + std::to_string(model) + " (0 SVK, 1 Mooney-Rivlin)");
+  if (n_mat < 1 || n_mat > kMaxMaterials)
+    return fail("tlfea_t10_set_element_materials: n_mat must be in 1.." + std::to_string(kMaxMaterials) + ", got " +
+                std::to_string(n_mat));
+  if (!table || !elem_material) return fail("tlfea_t10_set_element_materials: null table or element ids");
+  if (n_elem != h->E)
+    return fail("tlfea_t10_set_element_materials: n_elem " + std::to_string(n_elem) + " != number of elements " +
+                std::to_string(h->E));
+  for (int e = 0; e < n_elem; e++)
+    if (elem_material[e] < 0 || elem_material[e] >= n_mat)
+      return fail("tlfea_t10_set_element_materials: element " + std::to_string(e) + " has material id " +
+                  std::to_string(elem_material[e]) + " outside 0.." + std::to_string(n_mat - 1));
+  std::vector<double> tab((size_t)n_mat * kEmRec);
+  bool damp = false;
+  for (int k = 0; k < n_mat; k++) {
+    const tlfea_material_entry& t = table[k];
+    if (model == kSVK && !(t.nu > -1.0 && t.nu < 0.5))
+      return fail("tlfea_t10_set_element_materials: entry " + std::to_string(k) + ": nu must be in (-1, 0.5)");
+    if (!(t.rho0 >= 0.0)) return fail("tlfea_t10_set_element_materials: entry " + std::to_string(k) + ": negative density");
+    double* r = &tab[(size_t)k * kEmRec];
+    // the same arithmetic as tlfea_t10_set_svk: a one-entry table reproduces the uniform path
+    r[kEmMu] = model == kSVK ? t.E / (2 * (1 + t.nu)) : 0.0;
+    r[kEmLambda] = model == kSVK ? (t.E * t.nu) / ((1 + t.nu) * (1 - 2 * t.nu)) : 0.0;
+    r[kEmEta] = t.eta;
+    r[kEmLamd] = t.lamd;
+    r[kEmMu10] = model == kMooneyRivlin ? t.mu10 : 0.0;
+    r[kEmMu01] = model == kMooneyRivlin ? t.mu01 : 0.0;
+    r[kEmKappa] = model == kMooneyRivlin ? t.kappa : 0.0;
+    r[kEmRhoM] = t.rho0;
+    damp = damp || t.eta != 0.0 || t.lamd != 0.0;
+  }
+  // launches in flight on a solver's stream may still read the old records
+  HIP_TRY(hipDeviceSynchronize());
+  if (!h->d_emat) {
+    h->mat_saved = h->mat;
+    // the mass matrix assembled so far (uniform density) stays until the next CalcMassMatrix
+    h->h_rho_mass.assign(h->E, h->mass_rho0 > 0.0 ? h->mass_rho0 : 0.0);
+  }
+  h->h_table.swap(tab);
+  h->h_eid.assign(elem_material, elem_material + n_elem);
+  h->n_mat = n_mat;
+  h->emat_damp = damp;
+  h->mat.model = model;
+  TRY(upload_emat(h));
+  h->gen++;
+  return 0;
+}
+extern "C" int tlfea_t10_clear_element_materials(tlfea_t10_t h) {
+  NEED_SETUP(h, "clearing element materials.");
+  if (!h->d_emat) return 0;
+  HIP_TRY(hipDeviceSynchronize());
+  (void)hipFree(h->d_emat);
+  h->d_emat = nullptr;
+  h->mat = h->mat_saved;
+  if (h->mass_pe) {
+    // a mass matrix of per-element densities has no uniform density: it is dropped until the next CalcMassMatrix
+    if (h->d_mval && h->nnz_coef > 0) HIP_TRY(hipMemset(h->d_mval, 0, (size_t)h->nnz_coef * sizeof(double)));
+    h->mass_rho0 = -1.0;
+    h->mass_pe = false;
+  }
+  h->n_mat = 0;
+  h->emat_damp = false;
+  h->h_table.clear();
+  h->h_eid.clear();
+  h->h_rho_mass.clear();
+  h->gen++;
+  return 0;
+}
+extern "C" int tlfea_t10_get_element_materials(tlfea_t10_t h, int* n_mat, int* elem_material) {
+  if (!h) return fail("null handle");
+  if (n_mat) *n_mat = h->n_mat;
+  if (elem_material && h->d_emat) std::copy(h->h_eid.begin(), h->h_eid.end(), elem_material);
+  return 0;
+}
+
 extern "C" int tlfea_t10_set_external_force(tlfea_t10_t h, const double* f, int n) {
   if (!h) return fail("null handle");
   if (n != 3 * h->N) return fail("External force vector size mismatch.");
@@ -550,10 +662,19 @@ extern "C" int tlfea_t10_calc_mass_matrix(tlfea_t10_t h) {
   NEED_SETUP(h, "CalcMassMatrix.");
   if (!h->is_csr_setup) TRY(tlfea_t10_build_mass_csr_pattern(h));
   if (h->kind != kT10) return ancf_mass_host(h);
-  launch_mass_values(h->stream, h->view(), h->inc(), h->d_qx, h->d_qy, h->d_qz, h->mat.rho0, h->d_mval);
+  if (h->d_emat) {
+    // per-element densities: the snapshot of the table's densities goes into the records' kEmRhoM slot first
+    HIP_TRY(hipDeviceSynchronize());
+    for (int e = 0; e < h->E; e++) h->h_rho_mass[e] = h->h_table[(size_t)h->h_eid[e] * kEmRec + kEmRhoM];
+    TRY(upload_emat(h));
+    h->gen++;
+  }
+  launch_mass_values(h->stream, h->view(), h->inc(), h->d_qx, h->d_qy, h->d_qz, h->mat.rho0, h->d_mval, h->d_emat);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  h->mass_rho0 = h->mat.rho0;
+  // per-element: 1 flags an assembled mass (the solvers scale by 1/h and take each element's density from its record)
+  h->mass_rho0 = h->d_emat ? 1.0 : h->mat.rho0;
+  h->mass_pe = h->d_emat != nullptr;
   return 0;
 }
 
@@ -737,7 +858,8 @@ extern "C" int tlfea_t10_calc_p(tlfea_t10_t h) {
   NEED_SETUP(h, "CalcP.");
   TRY(ensure_fp_buffers(h));
   // standalone CalcP passes a null v_guess: no viscous part (FEAT10Data.cu:302-304)
-  launch_residual(h->stream, h->view(), h->mat, nullptr, h->d_fbuf, h->d_F, h->d_P, h->d_Fdot, h->d_Pvis);
+  launch_residual(h->stream, h->view(), h->mat, nullptr, h->d_fbuf, h->d_F, h->d_P, h->d_Fdot, h->d_Pvis, nullptr, nullptr, 0.0,
+                  0x43210, h->d_emat);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   h->fbuf_valid = true;
@@ -1427,6 +1549,8 @@ extern "C" int tlfea_newton_set_interface(tlfea_newton_t s, const int* iface_nod
                                           tlfea_allreduce_fn fn, void* user, int sync_before_callback) {
   // every rejection comes before anything is released: a caller that catches the error keeps a working solver
   if (!s) return fail("tlfea_newton_set_interface: null solver");
+  if (s->d->d_emat)
+    return fail("tlfea_newton_set_interface: per-element materials are not supported on the partitioned path");
   if (s->pmg.tried)
     return fail("tlfea_newton_set_interface: set the interface before the first linear solve (the p-multigrid hierarchy "
                 "is partitioned with it)");
@@ -1781,6 +1905,7 @@ extern "C" int tlfea_newton_set_halo(tlfea_newton_t s, const int* node_layer, in
                                      tlfea_allreduce_fn allreduce, tlfea_halo_exchange_fn exchange, void* user,
                                      int sync_before_callback) {
   if (!s || !node_layer || !lists || !allreduce || !exchange) return fail("tlfea_newton_set_halo: null argument");
+  if (s->d->d_emat) return fail("tlfea_newton_set_halo: per-element materials are not supported on the partitioned path");
   if (s->pmg.tried || s->ar)
     return fail("tlfea_newton_set_halo: set the halo on a fresh solver, before the first linear solve and instead of "
                 "tlfea_newton_set_interface");
@@ -2177,7 +2302,7 @@ static int fq_slots(tlfea_newton_t s);
 static void launch_residual_newton(tlfea_newton_t s, double* Fq, const MassTerm* mt) {
   tlfea_t10_t d = s->d;
   launch_residual(s->stream, d->view(), d->mat, s->d_v, d->d_fbuf, nullptr, nullptr, nullptr, nullptr, Fq, mt, fq_h(s),
-                  fq_slots(s));
+                  fq_slots(s), d->d_emat);
 }
 // record slots of the affine assembly: point q0 first, then the points where vertex 0, 1, 2, 3 has L = 1/2
 static int fq_slots(tlfea_newton_t s) {
@@ -2194,11 +2319,11 @@ static void launch_fused(tlfea_newton_t s) {
   const int* fixed = pinned_on(s) ? d->d_fixed_slot : nullptr;
   if (affine_now(s))
     launch_assemble_affine(s->stream, d->view(), d->mat, p.time_step, s->rg4, s->av, s->d_Fq, s->d_cmass,
-                           d->mass_rho0 > 0.0 ? d->mass_rho0 : 0.0, fixed, s->d_nw, p.time_step * p.time_step * p.rho,
-                           s->d_H);
+                           d->d_emat ? 1.0 : (d->mass_rho0 > 0.0 ? d->mass_rho0 : 0.0), fixed, s->d_nw,
+                           p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
   else
     launch_assemble_direct(s->stream, d->view(), d->mat, p.time_step, s->rg, s->d_Fq, d->d_mval, fixed, s->d_nw,
-                           p.time_step * p.time_step * p.rho, s->d_H);
+                           p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
 }
 static int ensure_kbuf(tlfea_newton_t s) {
   if (s->d_Kbuf) return 0;
@@ -2216,7 +2341,7 @@ static int fill_mass_term(tlfea_newton_t s, MassTerm& mt) {
   if (!s->d_mbuf) TRY(dmalloc(&s->d_mbuf, (size_t)d->Epad * 6 * d->S));
   mt.vprev = s->d_vprev;
   mt.mbuf = s->d_mbuf;
-  mt.rho_inv_h = d->mass_rho0 / s->prm.time_step;
+  mt.rho_inv_h = (d->d_emat ? 1.0 : d->mass_rho0) / s->prm.time_step;  // per-element: x the record's density
   const int edges[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};  // FEAT10Data.cu:143
   for (int q = 0; q < kNQ; q++) {
     const double L[4] = {1.0 - d->h_q[0][q] - d->h_q[1][q] - d->h_q[2][q], d->h_q[0][q], d->h_q[1][q], d->h_q[2][q]};
@@ -2297,7 +2422,7 @@ static int assemble(tlfea_newton_t s, bool fq_fresh = true) {
   TRY(ensure_kbuf(s));
   {
     StageTimer t(s, 2);
-    launch_tangent_blocks(s->stream, d->view(), d->mat, p.time_step, s->d_Kbuf);
+    launch_tangent_blocks(s->stream, d->view(), d->mat, p.time_step, s->d_Kbuf, d->d_emat);
     t.stop();
   }
   {
@@ -4139,7 +4264,7 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
       else if (k == 1) {
         if (use_direct(s)) break;  // no separate tangent launch on the fused path: out[1] = 0
         TRY(ensure_kbuf(s));
-        launch_tangent_blocks(s->stream, d->view(), d->mat, p.time_step, s->d_Kbuf);
+        launch_tangent_blocks(s->stream, d->view(), d->mat, p.time_step, s->d_Kbuf, d->d_emat);
       } else if (k == 2 && use_direct(s))  // out[2] = the fused tangent + assembly launch
         launch_fused(s);
       else if (k == 2)
@@ -4843,7 +4968,7 @@ static void vbd_enqueue_sweep(tlfea_vbd_t a, hipStream_t st) {
       launch_vbd_color(st, a->color_lanes[k], d->view(), d->mat, d->inc(), a->d_color_nodes + c.color_offsets[k],
                        c.color_offsets[k + 1] - c.color_offsets[k], d->d_mval, d->d_fext, pinned ? d->d_fixed_slot : nullptr,
                        d->d_xt, d->d_yt, d->d_zt, s->d_lam, p.time_step, p.rho, p.omega, p.hess_eps, s->d_vprev, s->d_xp,
-                       s->d_yp, s->d_zp, s->d_v, d->d_x, d->d_y, d->d_z, a->d_conn_rm, a->d_xyz);
+                       s->d_yp, s->d_zp, s->d_v, d->d_x, d->d_y, d->d_z, a->d_conn_rm, a->d_xyz, d->d_emat, d->emat_damp);
     }
 }
 

@@ -35,6 +35,28 @@ struct Material {
   double rho0;
 };
 
+// Per-element materials (tlfea_t10_set_element_materials): one 64-byte record per element, expanded on the host from the
+// material table and the element ids.  Slot kEmRhoM is the density the mass matrix was assembled with (the snapshot
+// CalcMassMatrix takes), not the table's current one.  Only the kernels' per-element instantiations read it; the
+// uniform ones keep taking Material by value.
+constexpr int kEmRec = 8;
+enum : int { kEmLambda = 0, kEmMu = 1, kEmEta = 2, kEmLamd = 3, kEmMu10 = 4, kEmMu01 = 5, kEmKappa = 6, kEmRhoM = 7 };
+constexpr int kMaxMaterials = 256;  // table entries per object (tlfea_c.h)
+struct MaterialPE {
+  Material base;      // model; the scalars are unused
+  const double* rec;  // [E][kEmRec]
+};
+__device__ __forceinline__ Material mat_at(const Material& m, int) { return m; }
+__device__ __forceinline__ Material mat_at(const MaterialPE& m, int e) {
+  const double2* r = reinterpret_cast<const double2*>(m.rec + (size_t)e * kEmRec);
+  const double2 a = r[0], b = r[1], c = r[2], d = r[3];
+  Material o;
+  o.model = m.base.model;
+  o.lambda = a.x; o.mu = a.y; o.eta = b.x; o.lamd = b.y;
+  o.mu10 = c.x; o.mu01 = c.y; o.kappa = d.x; o.rho0 = d.y;
+  return o;
+}
+
 // Device view of one mesh + state (all pointers are device pointers).  "N" counts coefficient vectors: nodes
 // for T10, 4 per node (r, r_u, r_v, r_w) for the ANCF types.
 struct ElemView {
@@ -114,7 +136,8 @@ void launch_residual(hipStream_t s, const ElemView& m, const Material& mat, cons
                      double* Fq = nullptr /*[E][Q][9] row-major F per point, for the fused assembly*/,
                      const MassTerm* mt = nullptr /*T10: also write the per-element inertia rows*/,
                      double fq_h = 0.0 /*> 0: affine form, Fq holds [E][5][10] = F per point (centroid point first)*/,
-                     int fq_slots = 0x43210 /*record slot of point q in bits 4q..4q+3 (the affine assembly's order)*/);
+                     int fq_slots = 0x43210 /*record slot of point q in bits 4q..4q+3 (the affine assembly's order)*/,
+                     const double* emat = nullptr /*[E][kEmRec] per-element materials (T10), null = uniform mat*/);
 // grad L without the mass CSR product (T10, inertia rows from the residual launch): 8 lanes per node
 void launch_grad_light(hipStream_t s, int N, int Epad, const Incidence& inc, const double* fbuf, const double* mbuf,
                        const double* f_ext, const double* x, const double* y, const double* z, const double* xt,
@@ -123,7 +146,7 @@ void launch_grad_light(hipStream_t s, int N, int Epad, const Incidence& inc, con
 // fused tangent + row assembly (T10, SVK): H rows straight from grad N and the F of the last residual launch
 void launch_assemble_direct(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups& rg,
                             const double* Fq, const double* mval, const int* fixed_slot, const double* nw,
-                            double penalty, double* Hval);
+                            double penalty, double* Hval, const double* emat = nullptr);
 // affine-element set-up: gvec from grad N / det J, and the largest relative deviation of the stored grad N / det J from
 // the affine form (dev_max: one double on the device, zeroed by the caller)
 void launch_affine_pre(hipStream_t s, const ElemView& m, const AffineView& av, double* gvec, double* dev_max);
@@ -131,10 +154,11 @@ void launch_affine_pre(hipStream_t s, const ElemView& m, const AffineView& av, d
 void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups4& rg,
                             const AffineView& av, const double* Fq16,
                             const double* cmass /*[10][16] sum_q w_q N_i N_j per (row node, vertex n, p); mid-edge columns halved*/,
-                            double rho0 /*density of the assembled mass matrix, 0 = none*/, const int* fixed_slot,
-                            const double* nw, double penalty, double* Hval);
+                            double rho0 /*density of the assembled mass matrix, 0 = none (per-element: 1 = the
+                                           records' kEmRhoM)*/, const int* fixed_slot,
+                            const double* nw, double penalty, double* Hval, const double* emat = nullptr);
 void launch_tangent_blocks(hipStream_t s, const ElemView& m, const Material& mat, double h,
-                           double* Kbuf /*[E][55][9]*/);
+                           double* Kbuf /*[E][55][9]*/, const double* emat = nullptr);
 void launch_assemble_rows(hipStream_t s, int N, int S, int maxdeg, const Incidence& inc, const double* Kbuf,
                           const double* mval, double inv_h, const int* fixed_slot, const double* nw,
                           double penalty, double* Hval);
@@ -142,10 +166,12 @@ void launch_vbd_color(hipStream_t s, int lanes /*16|32|64 per node*/, const Elem
                       const Incidence& inc, const int* nodes, int count, const double* mval, const double* f_ext, const int* fixed_slot, const double* xt,
                       const double* yt, const double* zt, const double* lam, double h, double rho, double omega,
                       double hess_eps, const double* v_prev, const double* xp, const double* yp, const double* zp,
-                      double* v, double* x, double* y, double* z, const int* conn_rm /*[E][S]*/, double* xyz /*[N][3]*/);
+                      double* v, double* x, double* y, double* z, const int* conn_rm /*[E][S]*/, double* xyz /*[N][3]*/,
+                      const double* emat = nullptr, bool emat_damp = false /*some entry has eta or lamd != 0*/);
 void launch_interleave_xyz(hipStream_t s, int N, const double* x, const double* y, const double* z, double* xyz);
 void launch_mass_values(hipStream_t s, const ElemView& m, const Incidence& inc, const double* qx,
-                        const double* qy, const double* qz, double rho0, double* mval);
+                        const double* qy, const double* qz, double rho0, double* mval,
+                        const double* emat = nullptr /*per-element: density of slot kEmRhoM, rho0 unused*/);
 void launch_grad(hipStream_t s, int N, const Incidence& inc, const double* fbuf, const double* mval,
                  const double* v, const double* vprev, const double* f_ext, const double* x,
                  const double* y, const double* z, const double* xt, const double* yt, const double* zt,

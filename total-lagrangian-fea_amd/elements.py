@@ -2,10 +2,28 @@
 C-ABI.  Method names, argument order and call-order contract follow the reference; Eigen vectors become
 NumPy arrays, Eigen::MatrixXi connectivity is an (E,10) int array (sent column-major as the reference does)."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
-from .binding import check, dp, ip, load_library
+from .binding import MaterialEntryC, check, dp, ip, load_library
+
+MAX_MATERIALS = 256  # table entries per object (include/tlfea_c.h)
+_MODELS = {"svk": 0, "mooney_rivlin": 1, "mr": 1}
+
+
+@dataclasses.dataclass
+class ElementMaterial:
+    """One entry of a per-element material table: E, nu (SVK) or mu10, mu01, kappa (Mooney-Rivlin), the density rho0
+    and the Kelvin-Voigt damping eta, lamd.  Fields of the other model are ignored."""
+    E: float = 0.0
+    nu: float = 0.0
+    mu10: float = 0.0
+    mu01: float = 0.0
+    kappa: float = 0.0
+    rho0: float = 0.0
+    eta: float = 0.0
+    lamd: float = 0.0
 
 
 def _f64(a):
@@ -56,6 +74,39 @@ class GPU_FEAT10_Data:
 
     def SetMooneyRivlin(self, mu10, mu01, kappa):
         check(self._lib.tlfea_t10_set_mooney_rivlin(self._h, C.c_double(mu10), C.c_double(mu01), C.c_double(kappa)))
+
+    def SetElementMaterials(self, ids, materials, model="svk"):
+        """Per-element materials: ids[e] indexes `materials` (ElementMaterial or dicts of its fields); `model` ("svk" or
+        "mooney_rivlin") applies to every entry.  Densities take effect at the next CalcMassMatrix.  While a table is
+        set, SetSVK / SetMooneyRivlin / SetDensity / SetDamping fail; ClearElementMaterials returns to them."""
+        if model not in _MODELS:
+            raise ValueError(f"SetElementMaterials: unknown model {model!r} (one of {sorted(_MODELS)})")
+        mats = [m if isinstance(m, ElementMaterial) else ElementMaterial(**m) for m in materials]
+        if not 1 <= len(mats) <= MAX_MATERIALS:
+            raise ValueError(f"SetElementMaterials: the table needs 1..{MAX_MATERIALS} entries, got {len(mats)}")
+        eid = np.asarray(ids)
+        if eid.ndim != 1 or eid.size != self.n_elem:
+            raise ValueError(f"SetElementMaterials: {eid.size} ids for {self.n_elem} elements")
+        if eid.size and not np.issubdtype(eid.dtype, np.integer):
+            raise ValueError("SetElementMaterials: ids must be integers")
+        if eid.size and (eid.min() < 0 or eid.max() >= len(mats)):
+            raise ValueError(f"SetElementMaterials: ids must lie in 0..{len(mats) - 1}")
+        eid = np.ascontiguousarray(eid, dtype=np.int32)
+        table = (MaterialEntryC * len(mats))(*[MaterialEntryC(*dataclasses.astuple(m)) for m in mats])
+        check(self._lib.tlfea_t10_set_element_materials(self._h, _MODELS[model], len(mats), table, ip(eid), int(eid.size)))
+
+    def ClearElementMaterials(self):
+        check(self._lib.tlfea_t10_clear_element_materials(self._h))
+
+    def GetElementMaterialIds(self):
+        """The element ids of the table set, or None in uniform mode."""
+        n = C.c_int()
+        check(self._lib.tlfea_t10_get_element_materials(self._h, C.byref(n), None))
+        if n.value == 0:
+            return None
+        ids = np.zeros(self.n_elem, dtype=np.int32)
+        check(self._lib.tlfea_t10_get_element_materials(self._h, C.byref(n), ip(ids)))
+        return ids
 
     def SetExternalForce(self, h_f_ext):
         f = _f64(h_f_ext)

@@ -719,6 +719,21 @@ struct GPU_FEAT10_Data : public ElementBase {
   void SetMooneyRivlin(double mu10, double mu01, double kappa) {
     TLFEA_SOFT(tlfea_t10_set_mooney_rivlin(h, mu10, mu01, kappa));
   }
+  // per-element materials (no reference counterpart): ids[e] indexes `materials`; model 0 SVK, 1 Mooney-Rivlin.
+  // Returns the C-ABI's status (0 = accepted; tlfea_last_error() explains a refusal).
+  int SetElementMaterials(const std::vector<int>& ids, const std::vector<tlfea_material_entry>& materials, int model = 0) {
+    return tlfea_t10_set_element_materials(h, model, static_cast<int>(materials.size()), materials.data(), ids.data(),
+                                           static_cast<int>(ids.size()));
+  }
+  int ClearElementMaterials() { return tlfea_t10_clear_element_materials(h); }
+  // the element ids of the table set; empty in uniform mode
+  std::vector<int> GetElementMaterialIds() const {
+    int n = 0;
+    (void)tlfea_t10_get_element_materials(h, &n, nullptr);
+    std::vector<int> ids(n > 0 ? n_elem : 0);
+    if (n > 0) (void)tlfea_t10_get_element_materials(h, &n, ids.data());
+    return ids;
+  }
   void SetExternalForce(const tlfea::VectorXd& h_f_ext) {
     TLFEA_SOFT(tlfea_t10_set_external_force(h, h_f_ext.data(), h_f_ext.size()));
   }

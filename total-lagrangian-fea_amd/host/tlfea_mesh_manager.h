@@ -330,6 +330,13 @@ class MeshManager {
         return k;
     return -1;
   }
+  // mesh instance of every element of GetAllElements() (the id table of GPU_FEAT10_Data::SetElementMaterials)
+  std::vector<int> GetAllElementMeshIds() const {
+    std::vector<int> ids;
+    ids.reserve(GetTotalElements());
+    for (int k = 0; k < GetNumMeshes(); k++) ids.insert(ids.end(), inst_[k].num_elements, k);
+    return ids;
+  }
   int GetMeshIdFromNode(int global_node_idx) const {
     for (int k = 0; k < GetNumMeshes(); k++)
       if (global_node_idx >= inst_[k].node_offset && global_node_idx < inst_[k].node_offset + inst_[k].num_nodes) return k;
