@@ -99,6 +99,33 @@ int tlfea_t10_set_element_materials(tlfea_t10_t h, int model, int n_mat, const t
                                     const int *elem_material, int n_elem);
 int tlfea_t10_clear_element_materials(tlfea_t10_t h);
 int tlfea_t10_get_element_materials(tlfea_t10_t h, int *n_mat, int *elem_material);
+
+/* Rigid analytic obstacles (no reference counterpart).  Up to 16 half-spaces (kind 0: point p, outward unit
+ * normal n) and solid spheres (kind 1: centre p, radius) per T10 object, in implicit penalty contact with the surface
+ * nodes: every solver that evaluates the gradient (Newton, direct Newton, AdamW, Nesterov) adds the contact gradient, and
+ * Newton its 3x3 Hessian blocks.  stiffness: kappa in Pa/m (per unit surface area and penetration); friction: mu
+ * (regularised Coulomb with the normal force of the start of the step); eps_v: friction regularisation velocity; vel:
+ * obstacle velocity (friction only).  After Setup only.  While obstacles are set, tlfea_vbd_solve, tlfea_newton_set_halo
+ * and tlfea_newton_set_interface fail.  update moves obstacle k between steps; clear removes all.
+ * get_obstacle_forces: the contact force on every node (3N, the layout of f_ext) of the last gradient evaluation;
+ * get_obstacle_resultant: obstacle k's total force on the mesh (out[0..2]) and its nodes in contact (out[3]);
+ * get_surface_weights: the area share of every node (N, 0 inside the mesh). */
+typedef struct {
+  int kind;         /* 0 half-space, 1 sphere */
+  double p[3];      /* point on the plane | centre */
+  double n[3];      /* outward unit normal (half-space) */
+  double radius;    /* sphere */
+  double vel[3];    /* obstacle velocity (friction only) */
+  double stiffness; /* kappa, Pa/m */
+  double friction;  /* mu >= 0 */
+  double eps_v;     /* friction regularisation velocity, m/s */
+} tlfea_obstacle;
+int tlfea_t10_set_obstacles(tlfea_t10_t h, const tlfea_obstacle *list, int n);
+int tlfea_t10_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle *o);
+int tlfea_t10_clear_obstacles(tlfea_t10_t h);
+int tlfea_t10_get_obstacle_forces(tlfea_t10_t h, double *f);
+int tlfea_t10_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]);
+int tlfea_t10_get_surface_weights(tlfea_t10_t h, double *w);
 int tlfea_t10_set_external_force(tlfea_t10_t h, const double *f_ext, int n);   /* :636-646 (n must be 3N) */
 int tlfea_t10_set_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed);    /* FEAT10Data.cu:728-749 */
 int tlfea_t10_update_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed); /* FEAT10Data.cu:751-832 */

@@ -66,6 +66,23 @@ class MaterialEntryC(C.Structure):  # tlfea_material_entry
     _fields_ = [(n, C.c_double) for n in ("E", "nu", "mu10", "mu01", "kappa", "rho0", "eta", "lamd")]
 
 
+class ObstacleC(C.Structure):  # tlfea_obstacle
+    _fields_ = [("kind", C.c_int), ("p", C.c_double * 3), ("n", C.c_double * 3), ("radius", C.c_double),
+                ("vel", C.c_double * 3), ("stiffness", C.c_double), ("friction", C.c_double), ("eps_v", C.c_double)]
+
+
+def _obstacle_signatures(lib):
+    """ctypes signatures of the rigid-obstacle entry points."""
+    vp, i = C.c_void_p, C.c_int
+    sig = {"tlfea_t10_set_obstacles": [vp, C.POINTER(ObstacleC), i],
+           "tlfea_t10_update_obstacle": [vp, i, C.POINTER(ObstacleC)], "tlfea_t10_clear_obstacles": [vp],
+           "tlfea_t10_get_obstacle_forces": [vp, c_dp], "tlfea_t10_get_obstacle_resultant": [vp, i, c_dp],
+           "tlfea_t10_get_surface_weights": [vp, c_dp]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+
+
 def _material_signatures(lib):
     """ctypes signatures of the per-element material entry points."""
     vp, i = C.c_void_p, C.c_int
@@ -140,6 +157,7 @@ def load_library():
         getattr(lib, name).argtypes = [C.c_void_p]
     _contact_signatures(lib)
     _material_signatures(lib)
+    _obstacle_signatures(lib)
     _LIB = lib
     return lib
 

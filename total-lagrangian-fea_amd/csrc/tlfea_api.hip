@@ -25,6 +25,7 @@
 #include "rowgroup_host.h"
 #include "direct_host.h"
 #include "vbd_host.h"
+#include "obstacle_host.h"
 
 using namespace tlfea;
 
@@ -91,6 +92,13 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   std::vector<double> h_rho_mass;   // [E] density each element's share of the mass matrix was assembled with
   bool mass_pe = false;             // the mass matrix was assembled from h_rho_mass under a table
   Material mat_saved{kSVK, 0, 0, 0, 0, 0, 0, 0, 0};
+  // rigid obstacles (tlfea_t10_set_obstacles): obs.n == 0 = none -- nothing allocated, nothing launched
+  ObstacleList obs{};
+  std::vector<double> h_surf_w;     // [N] surface weight of every node (built once per mesh, on first use)
+  std::vector<int> h_surf;          // the nodes of weight > 0, ascending: the obstacle kernels' work list
+  int* d_ob_node = nullptr;
+  double *d_ob_w = nullptr, *d_ob_f = nullptr, *d_ob_blk = nullptr, *d_ob_fk = nullptr, *d_ob_res = nullptr;
+  int ob_fk_cap = 0;                // obstacles d_ob_fk has room for
   // constraints
   double* d_cons = nullptr;
   int *d_fixed = nullptr, *d_fixed_slot = nullptr;
@@ -199,7 +207,8 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_gradN, h->d_gradN_t, h->d_detJ, h->d_F, h->d_P, h->d_Fdot, h->d_Pvis, h->d_fbuf, h->d_fint,
                   h->d_fext, h->d_cons, h->d_fixed, h->d_fixed_slot, h->d_off, h->d_cols, h->d_n2e_off, h->d_n2e,
                   h->d_n2e_pos, h->d_diagpos, h->d_mval, h->d_joff, h->d_jcol, h->d_jtoff, h->d_jtcol, h->d_jval,
-                  h->d_jtval, h->d_rhs, h->d_emat};
+                  h->d_jtval, h->d_rhs, h->d_emat, h->d_ob_node, h->d_ob_w, h->d_ob_f, h->d_ob_blk, h->d_ob_fk,
+                  h->d_ob_res};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -384,6 +393,117 @@ extern "C" int tlfea_t10_get_element_materials(tlfea_t10_t h, int* n_mat, int* e
   if (!h) return fail("null handle");
   if (n_mat) *n_mat = h->n_mat;
   if (elem_material && h->d_emat) std::copy(h->h_eid.begin(), h->h_eid.end(), elem_material);
+  return 0;
+}
+
+// ---- rigid obstacles ---------------------------------------------------------------------------------------------------
+static void surface_build(tlfea_t10_t h) {
+  if (!h->h_surf_w.empty()) return;
+  h->h_surf_w = t10_surface_weights(h->E, h->N, h->h_conn, h->h_X0);
+  h->h_surf.clear();
+  for (int i = 0; i < h->N; i++)
+    if (h->h_surf_w[i] > 0.0) h->h_surf.push_back(i);
+}
+static void obstacles_free(tlfea_t10_t h) {
+  for (double** p : {&h->d_ob_w, &h->d_ob_f, &h->d_ob_blk, &h->d_ob_fk, &h->d_ob_res}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  if (h->d_ob_node) (void)hipFree(h->d_ob_node);
+  h->d_ob_node = nullptr;
+  h->ob_fk_cap = 0;
+  h->obs.n = 0;
+}
+extern "C" int tlfea_t10_clear_obstacles(tlfea_t10_t h) {
+  NEED_SETUP(h, "clearing obstacles.");
+  if (h->obs.n == 0) return 0;
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
+  obstacles_free(h);
+  return 0;
+}
+extern "C" int tlfea_t10_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
+  if (h && h->kind != kT10) return fail("tlfea_t10_set_obstacles: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "setting obstacles.");
+  if (n < 0 || n > kMaxObstacles)
+    return fail("tlfea_t10_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
+  if (n > 0 && !list) return fail("tlfea_t10_set_obstacles: null list");
+  for (int k = 0; k < n; k++) {
+    const std::string why = obstacle_check(list[k]);
+    if (!why.empty()) return fail("tlfea_t10_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
+  }
+  if (n == 0) return tlfea_t10_clear_obstacles(h);
+  surface_build(h);
+  HIP_TRY(hipDeviceSynchronize());
+  const int ns = (int)h->h_surf.size();
+  if (!h->d_ob_node) {
+    std::vector<double> w(ns);
+    for (int k = 0; k < ns; k++) w[k] = h->h_surf_w[h->h_surf[k]];
+    TRY(dmalloc(&h->d_ob_node, (size_t)ns));
+    TRY(dmalloc(&h->d_ob_w, (size_t)ns));
+    TRY(dmalloc(&h->d_ob_f, (size_t)3 * ns));
+    TRY(dmalloc(&h->d_ob_blk, (size_t)6 * ns));
+    TRY(dmalloc(&h->d_ob_res, (size_t)4 * kMaxObstacles));
+    if (ns) {
+      HIP_TRY(hipMemcpy(h->d_ob_node, h->h_surf.data(), (size_t)ns * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(h->d_ob_w, w.data(), (size_t)ns * sizeof(double), hipMemcpyHostToDevice));
+    }
+  }
+  if (h->ob_fk_cap < n) {
+    if (h->d_ob_fk) (void)hipFree(h->d_ob_fk);
+    h->d_ob_fk = nullptr;
+    TRY(dmalloc(&h->d_ob_fk, (size_t)4 * n * ns));
+    h->ob_fk_cap = n;
+  }
+  // no forces before the first gradient evaluation
+  HIP_TRY(hipMemset(h->d_ob_f, 0, (size_t)std::max(1, 3 * ns) * sizeof(double)));
+  HIP_TRY(hipMemset(h->d_ob_blk, 0, (size_t)std::max(1, 6 * ns) * sizeof(double)));
+  HIP_TRY(hipMemset(h->d_ob_fk, 0, (size_t)std::max(1, 4 * n * ns) * sizeof(double)));
+  h->obs.n = n;
+  for (int k = 0; k < n; k++) h->obs.o[k] = obstacle_dev(list[k]);
+  return 0;
+}
+extern "C" int tlfea_t10_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle* o) {
+  NEED_SETUP(h, "updating an obstacle.");
+  if (k < 0 || k >= h->obs.n)
+    return fail("tlfea_t10_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->obs.n) +
+                " obstacles set");
+  if (!o) return fail("tlfea_t10_update_obstacle: null obstacle");
+  const std::string why = obstacle_check(*o);
+  if (!why.empty()) return fail("tlfea_t10_update_obstacle: obstacle " + std::to_string(k) + ": " + why);
+  h->obs.o[k] = obstacle_dev(*o);  // a kernel argument: launches already queued keep the old value
+  return 0;
+}
+extern "C" int tlfea_t10_get_obstacle_forces(tlfea_t10_t h, double* f) {
+  NEED_SETUP(h, "reading obstacle forces.");
+  if (!f) return fail("tlfea_t10_get_obstacle_forces: null output");
+  std::fill(f, f + 3 * (size_t)h->N, 0.0);
+  if (h->obs.n == 0) return 0;
+  const size_t ns = h->h_surf.size();
+  std::vector<double> fs(3 * ns);
+  HIP_TRY(hipDeviceSynchronize());
+  if (ns) HIP_TRY(hipMemcpy(fs.data(), h->d_ob_f, 3 * ns * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < ns; k++)
+    for (int c = 0; c < 3; c++) f[3 * (size_t)h->h_surf[k] + c] = fs[3 * k + c];
+  return 0;
+}
+extern "C" int tlfea_t10_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
+  NEED_SETUP(h, "reading an obstacle resultant.");
+  if (!out) return fail("tlfea_t10_get_obstacle_resultant: null output");
+  if (k < 0 || k >= h->obs.n)
+    return fail("tlfea_t10_get_obstacle_resultant: index " + std::to_string(k) + " outside the " +
+                std::to_string(h->obs.n) + " obstacles set");
+  HIP_TRY(hipDeviceSynchronize());
+  launch_obstacle_resultant(h->stream, (int)h->h_surf.size(), h->obs.n, h->d_ob_fk, h->d_ob_res);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, h->d_ob_res + 4 * k, 4 * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+extern "C" int tlfea_t10_get_surface_weights(tlfea_t10_t h, double* w) {
+  if (h && h->kind != kT10) return fail("tlfea_t10_get_surface_weights: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "reading surface weights.");
+  if (!w) return fail("tlfea_t10_get_surface_weights: null output");
+  surface_build(h);
+  std::copy(h->h_surf_w.begin(), h->h_surf_w.end(), w);
   return 0;
 }
 
@@ -1551,6 +1671,8 @@ extern "C" int tlfea_newton_set_interface(tlfea_newton_t s, const int* iface_nod
   if (!s) return fail("tlfea_newton_set_interface: null solver");
   if (s->d->d_emat)
     return fail("tlfea_newton_set_interface: per-element materials are not supported on the partitioned path");
+  if (s->d->obs.n > 0)
+    return fail("tlfea_newton_set_interface: rigid obstacles are not supported on the partitioned path (clear them first)");
   if (s->pmg.tried)
     return fail("tlfea_newton_set_interface: set the interface before the first linear solve (the p-multigrid hierarchy "
                 "is partitioned with it)");
@@ -1906,6 +2028,8 @@ extern "C" int tlfea_newton_set_halo(tlfea_newton_t s, const int* node_layer, in
                                      int sync_before_callback) {
   if (!s || !node_layer || !lists || !allreduce || !exchange) return fail("tlfea_newton_set_halo: null argument");
   if (s->d->d_emat) return fail("tlfea_newton_set_halo: per-element materials are not supported on the partitioned path");
+  if (s->d->obs.n > 0)
+    return fail("tlfea_newton_set_halo: rigid obstacles are not supported on the partitioned path (clear them first)");
   if (s->pmg.tried || s->ar)
     return fail("tlfea_newton_set_halo: set the halo on a fresh solver, before the first linear solve and instead of "
                 "tlfea_newton_set_interface");
@@ -2351,8 +2475,26 @@ static int fill_mass_term(tlfea_newton_t s, MassTerm& mt) {
   return 0;
 }
 
+// contact gradient of the rigid obstacles (g may be null: refresh of the per-node force / block buffers only)
+static void launch_obstacles_grad(tlfea_newton_t s, double* g) {
+  tlfea_t10_t d = s->d;
+  launch_obstacle_grad(s->stream, (int)d->h_surf.size(), d->d_ob_node, d->d_ob_w, d->obs, d->d_x, d->d_y, d->d_z, s->d_xp,
+                       s->d_yp, s->d_zp, s->prm.time_step, pinned_on(s) ? d->d_fixed_slot : nullptr, g, d->d_ob_f,
+                       d->d_ob_blk, d->d_ob_fk);
+}
+// + h x the contact blocks on the diagonal of H: after the assembly and the constraint term, before anything reads H
+static void launch_obstacles_hessian(tlfea_newton_t s, bool buffers_fresh) {
+  tlfea_t10_t d = s->d;
+  if (d->obs.n == 0) return;
+  if (!buffers_fresh) launch_obstacles_grad(s, nullptr);
+  launch_obstacle_hessian(s->stream, (int)d->h_surf.size(), d->d_ob_node, d->d_off, d->d_diagpos, d->d_ob_blk,
+                          s->prm.time_step, s->d_H);
+}
+
 static int eval_gradient(tlfea_newton_t s, double* norm_g) {
   tlfea_t10_t d = s->d;
+  if (d->obs.n > 0 && dist_on(s))  // before any collective
+    return fail("rigid obstacles are not supported on the partitioned path (clear them first)");
   TRY(refresh_geometry(s));
   TRY(ensure_form_for_material(s));
   const tlfea_newton_params& p = s->prm;
@@ -2383,6 +2525,7 @@ static int eval_gradient(tlfea_newton_t s, double* norm_g) {
       launch_lin_constraint_grad(s->stream, 3 * s->N, d->d_jtoff, d->d_jtcol, d->d_jtval, s->d_lam, d->d_cons,
                                  p.time_step, p.rho, s->d_g);
     }
+    if (d->obs.n > 0) launch_obstacles_grad(s, s->d_g);
     HIP_TRY(hipGetLastError());
     // each rank's g holds only its own elements' forces and its share of M, f_ext, constraints on
     // partition-boundary nodes: sum the boundary entries over ranks (nothing else is exchanged)
@@ -2397,6 +2540,7 @@ static int eval_gradient(tlfea_newton_t s, double* norm_g) {
 // how the Newton loop calls it); a stand-alone assembly refreshes it with a residual launch first
 static int assemble(tlfea_newton_t s, bool fq_fresh = true) {
   tlfea_t10_t d = s->d;
+  const bool after_grad = fq_fresh;  // the obstacle buffers hold the current coordinates' blocks
   {
     const long seen = s->geom_gen_seen;
     TRY(refresh_geometry(s));
@@ -2415,6 +2559,7 @@ static int assemble(tlfea_newton_t s, bool fq_fresh = true) {
     if (lincons_on(s))  // + h^2 rho J^T J  (SyncedNewton.cu:292-341)
       launch_lin_constraint_hessian(s->stream, 3 * s->N, d->d_jtoff, d->d_jtcol, d->d_jtval, d->d_joff, d->d_jcol,
                                     d->d_jval, d->d_off, d->d_cols, p.time_step * p.time_step * p.rho, s->d_H);
+    launch_obstacles_hessian(s, after_grad);
     HIP_TRY(hipGetLastError());
     t.stop();
     return 0;
@@ -2432,6 +2577,7 @@ static int assemble(tlfea_newton_t s, bool fq_fresh = true) {
     if (lincons_on(s))  // + h^2 rho J^T J  (SyncedNewton.cu:292-341)
       launch_lin_constraint_hessian(s->stream, 3 * s->N, d->d_jtoff, d->d_jtcol, d->d_jtval, d->d_joff, d->d_jcol,
                                     d->d_jval, d->d_off, d->d_cols, p.time_step * p.time_step * p.rho, s->d_H);
+    launch_obstacles_hessian(s, after_grad);
     HIP_TRY(hipGetLastError());
     t.stop();
   }
@@ -4413,12 +4559,21 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
   int n_outer = 0, n_newton = 0, pcg_total = 0;
   double norm_g = 0.0, norm_c = 0.0;
   const int fail_hook = std::getenv("TLFEA_TEST_FAIL_LINSOLVE") ? std::atoi(std::getenv("TLFEA_TEST_FAIL_LINSOLVE")) : -1;
+  // Rigid obstacles with friction: the regularised Coulomb term switches between a stiff stick branch and a sliding branch
+  // whose exact Hessian has no stiffness along the slip, so a full Newton step can jump across the stick window and back
+  // forever.  The step is then halved (up to kMaxHalvings times) until ||g|| decreases; the gradient of the
+  // accepted point is the next iteration's.  Without friction nothing of this runs.
+  bool friction_on = false;
+  for (int k = 0; k < d->obs.n; k++) friction_on = friction_on || d->obs.o[k].mu > 0.0;
+  const int kMaxHalvings = 8;
   auto run = [&]() -> int {
     for (int outer = 0; outer < p.max_outer; ++outer) {
       n_outer++;
       double norm_g0 = -1.0;
+      bool g_current = false;
       for (int it = 0; it < p.max_inner; ++it) {
-        TRY(eval_gradient(s, &norm_g));
+        if (!g_current) TRY(eval_gradient(s, &norm_g));
+        g_current = false;
         if (s->verbose) std::printf("  outer %d newton %d ||g|| = %.6e\n", outer, it, norm_g);
         if (norm_g0 < 0.0) norm_g0 = norm_g;
         if (norm_g < p.inner_atol || (p.inner_rtol > 0.0 && norm_g0 > 0.0 && norm_g <= p.inner_rtol * norm_g0)) break;
@@ -4433,6 +4588,16 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
         if (rc) return rc;
         n_newton++;
         TRY(newton_update(s));                                               // v += dv ; x = x_prev + h v (:1116-1119)
+        if (friction_on) {
+          const double ng_prev = norm_g;
+          for (int k = 0;; k++) {
+            TRY(eval_gradient(s, &norm_g));
+            if (norm_g <= ng_prev || k == kMaxHalvings) break;
+            launch_scale(s->stream, n, k == 0 ? -0.5 : 0.5, s->d_dv);  // v = v0 + dv0 / 2^(k+1)
+            TRY(newton_update(s));
+          }
+          g_current = true;
+        }
       }
       HIP_TRY(hipMemcpyAsync(s->d_vprev, s->d_v, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice,
                              s->stream));                                    // every OUTER iteration (:1122)
@@ -5002,6 +5167,9 @@ extern "C" int tlfea_vbd_solve(tlfea_vbd_t a) {
   tlfea_t10_t d = s->d;
   const tlfea_vbd_params& p = a->prm;
   if (dist_on(s)) return fail("SyncedVBDSolver: single-GPU path only");
+  if (d->obs.n > 0)
+    return fail("SyncedVBDSolver: rigid obstacles are set, and the VBD vertex solve has no contact term; use the Newton, "
+                "AdamW or Nesterov solver, or clear the obstacles");
   TRY(sync_constraints(s));
   if (!a->mass_ready && !d->is_csr_setup) TRY(tlfea_vbd_initialize_mass_diag_blocks(a));
   TRY(tlfea_vbd_initialize_coloring(a));

@@ -339,4 +339,30 @@ struct MfDev {
 void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const double* H);
 void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const double* b, double* x);
 
+// Rigid analytic obstacles (tlfea_t10_set_obstacles): the list travels by value in the kernel arguments
+// (16 x 120 bytes).  Every surface node owns its own entries of g, of its diagonal block of H and of the per-node
+// buffers, so the launches need no atomics and are bitwise reproducible.
+constexpr int kMaxObstacles = 16;
+enum ObstacleKind : int { kHalfSpace = 0, kSphere = 1 };
+struct ObstacleDev {
+  int kind;
+  double p[3], n[3], radius, vel[3], kappa, mu, eps_v;
+};
+struct ObstacleList {
+  int n;
+  ObstacleDev o[kMaxObstacles];
+};
+// Per surface node k (node[k]): force f = -grad Phi (3), symmetric 3x3 block of the Hessian of Phi (xx yy zz xy xz yz),
+// and per obstacle j the node's share {fx, fy, fz, in contact} at fk[(j * n_surf + k) * 4].  g (may be null: refresh of
+// the buffers only) gains grad Phi.  Pinned nodes (fixed_slot >= 0) take no part.  xp/yp/zp: start-of-step positions.
+void launch_obstacle_grad(hipStream_t s, int n_surf, const int* node, const double* w, const ObstacleList& L,
+                          const double* x, const double* y, const double* z, const double* xp, const double* yp,
+                          const double* zp, double h, const int* fixed_slot, double* g, double* f, double* blk,
+                          double* fk);
+// H's diagonal block of every surface node += h * block (H = M/h + h K: the same scaling as the element tangent)
+void launch_obstacle_hessian(hipStream_t s, int n_surf, const int* node, const int* off, const int* diagpos,
+                             const double* blk, double h, double* H);
+// out[j][4] = fixed-order sums of fk over the surface nodes, one block per obstacle
+void launch_obstacle_resultant(hipStream_t s, int n_surf, int n_obs, const double* fk, double* out);
+
 }  // namespace tlfea

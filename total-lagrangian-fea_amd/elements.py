@@ -6,7 +6,8 @@ import dataclasses
 
 import numpy as np
 
-from .binding import MaterialEntryC, check, dp, ip, load_library
+from .binding import MaterialEntryC, ObstacleC, check, dp, ip, load_library
+from .obstacles import MAX_OBSTACLES, as_c
 
 MAX_MATERIALS = 256  # table entries per object (include/tlfea_c.h)
 _MODELS = {"svk": 0, "mooney_rivlin": 1, "mr": 1}
@@ -107,6 +108,41 @@ class GPU_FEAT10_Data:
         ids = np.zeros(self.n_elem, dtype=np.int32)
         check(self._lib.tlfea_t10_get_element_materials(self._h, C.byref(n), ip(ids)))
         return ids
+
+    # -- rigid obstacles ----------------------------------------------------------------------
+    def SetRigidObstacles(self, obstacles):
+        """Replace the obstacle list (RigidPlane / RigidSphere, at most 16; an empty list clears it)."""
+        obstacles = list(obstacles)
+        if len(obstacles) > MAX_OBSTACLES:
+            raise ValueError(f"at most {MAX_OBSTACLES} obstacles per object, got {len(obstacles)}")
+        arr = (ObstacleC * max(1, len(obstacles)))(*[as_c(o) for o in obstacles])
+        check(self._lib.tlfea_t10_set_obstacles(self._h, arr, len(obstacles)))
+
+    def UpdateRigidObstacle(self, k, obstacle):
+        """Replace obstacle k (move it between steps)."""
+        o = as_c(obstacle)
+        check(self._lib.tlfea_t10_update_obstacle(self._h, int(k), C.byref(o)))
+
+    def ClearRigidObstacles(self):
+        check(self._lib.tlfea_t10_clear_obstacles(self._h))
+
+    def GetObstacleForces(self):
+        """Contact force on every node (3N, the layout of f_ext) at the last gradient evaluation."""
+        f = np.zeros(3 * self.n_coef)
+        check(self._lib.tlfea_t10_get_obstacle_forces(self._h, dp(f)))
+        return f
+
+    def GetObstacleResultant(self, k):
+        """(force of obstacle k on the mesh as a 3-vector, number of nodes in contact) at the last gradient evaluation."""
+        out = np.zeros(4)
+        check(self._lib.tlfea_t10_get_obstacle_resultant(self._h, int(k), dp(out)))
+        return out[:3].copy(), int(round(out[3]))
+
+    def GetSurfaceWeights(self):
+        """Surface area share of every node (N; 0 inside the mesh): the weights of the contact model."""
+        w = np.zeros(self.n_coef)
+        check(self._lib.tlfea_t10_get_surface_weights(self._h, dp(w)))
+        return w
 
     def SetExternalForce(self, h_f_ext):
         f = _f64(h_f_ext)

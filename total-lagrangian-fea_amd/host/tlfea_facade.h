@@ -734,6 +734,25 @@ struct GPU_FEAT10_Data : public ElementBase {
     if (n > 0) (void)tlfea_t10_get_element_materials(h, &n, ids.data());
     return ids;
   }
+  // rigid obstacles (no reference counterpart): half-spaces and spheres in implicit contact with the surface
+  // nodes.  The set / update calls return the C-ABI's status (0 = accepted; tlfea_last_error() explains a refusal).
+  int SetRigidObstacles(const std::vector<tlfea_obstacle>& list) {
+    return tlfea_t10_set_obstacles(h, list.data(), static_cast<int>(list.size()));
+  }
+  int UpdateRigidObstacle(int k, const tlfea_obstacle& o) { return tlfea_t10_update_obstacle(h, k, &o); }
+  int ClearRigidObstacles() { return tlfea_t10_clear_obstacles(h); }
+  // contact force on every node (3N, the layout of f_ext) at the last gradient evaluation
+  void GetObstacleForces(tlfea::VectorXd& f) {
+    f.resize(3 * n_coef);
+    TLFEA_HANDLE_ERROR(tlfea_t10_get_obstacle_forces(h, f.data()));
+  }
+  // out[0..2]: obstacle k's force on the mesh, out[3]: its nodes in contact
+  void GetObstacleResultant(int k, double out[4]) { TLFEA_HANDLE_ERROR(tlfea_t10_get_obstacle_resultant(h, k, out)); }
+  // area share of every node (0 inside the mesh)
+  void GetSurfaceWeights(tlfea::VectorXd& w) {
+    w.resize(n_coef);
+    TLFEA_HANDLE_ERROR(tlfea_t10_get_surface_weights(h, w.data()));
+  }
   void SetExternalForce(const tlfea::VectorXd& h_f_ext) {
     TLFEA_SOFT(tlfea_t10_set_external_force(h, h_f_ext.data(), h_f_ext.size()));
   }
@@ -1041,6 +1060,8 @@ class SyncedNewtonSolver : public SolverBase {
   void OneStepNewtonCuDSS() { TLFEA_HANDLE_ERROR(tlfea_newton_solve(s_)); }  // name kept for drop-in; solves with PCG
   void Solve() override { OneStepNewtonCuDSS(); }
   double* GetVelocityGuessDevicePtr() const { return tlfea_newton_velocity_guess_device_ptr(s_); }
+  // outer iterations, Newton iterations, ||g||, ||c||, CG iterations, ms of the last Solve (tlfea_newton_get_stats)
+  void GetStats(double st[6]) const { TLFEA_HANDLE_ERROR(tlfea_newton_get_stats(s_, st)); }
   double compute_l2_norm_cublas(double* d_vec, int n_dofs) {
     double out = 0.0;
     TLFEA_HANDLE_ERROR(tlfea_newton_l2_norm(s_, d_vec, n_dofs, &out));
