@@ -126,6 +126,26 @@ int tlfea_t10_clear_obstacles(tlfea_t10_t h);
 int tlfea_t10_get_obstacle_forces(tlfea_t10_t h, double *f);
 int tlfea_t10_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]);
 int tlfea_t10_get_surface_weights(tlfea_t10_t h, double *w);
+/* Stress and energy recovery of T10 objects (no reference counterpart).  Works from the current positions and
+ * the object's own data at any time after CalcDnDuPre; changes nothing a solver reads.  d_vel: DEVICE pointer to a
+ * velocity (3N interleaved: what tlfea_*_velocity_guess_device_ptr returns) or NULL; with it a damped material's
+ * Kelvin-Voigt stress is added (the P of the residual), and the kinetic energy and viscous power are formed (needs
+ * CalcMassMatrix).  calc_stress_host takes the velocity from the host.  want_points != 0 also keeps the stresses of the
+ * five Keast points.  Cauchy stresses are 6 doubles xx yy zz xy yz zx.  Element values are reference-volume-weighted means
+ * over the points (von Mises of the mean stress; psi = elastic strain-energy density per reference volume; J = det F);
+ * nodal stress is the element-volume-weighted mean of the incident elements' means, von Mises taken from that tensor.
+ * get_energies: strain energy, kinetic energy 1/2 v.Mv, viscous power, reference volume, current volume.  A retrieve
+ * before calc_stress is an error.  Every output is bitwise reproducible.  ANCF handles are refused. */
+int tlfea_t10_calc_stress(tlfea_t10_t h, const double *d_vel /* device, 3N, or NULL */, int want_points);
+int tlfea_t10_calc_stress_host(tlfea_t10_t h, const double *vel /* host, 3N, or NULL */, int want_points);
+int tlfea_t10_retrieve_point_stress(tlfea_t10_t h, double *sigma /*E*5*6*/);
+int tlfea_t10_retrieve_element_stress(tlfea_t10_t h, double *sigma /*E*6*/, double *von_mises /*E*/, double *psi /*E*/,
+                                      double *J /*E*/, double *vol /*E*/); /* any may be NULL */
+int tlfea_t10_retrieve_nodal_stress(tlfea_t10_t h, double *sigma /*N*6*/, double *von_mises /*N*/); /* either may be NULL */
+int tlfea_t10_get_energies(tlfea_t10_t h, double out[5]);
+double *tlfea_t10_nodal_stress_device_ptr(tlfea_t10_t h); /* N*7: sigma, von Mises per node; NULL before calc_stress */
+/* mean ms over reps launches of: the point and element kernel, the nodal gather, the totals (profiling hook) */
+int tlfea_t10_time_stress_kernels(tlfea_t10_t h, const double *d_vel, int want_points, int reps, double *out_ms3);
 int tlfea_t10_set_external_force(tlfea_t10_t h, const double *f_ext, int n);   /* :636-646 (n must be 3N) */
 int tlfea_t10_set_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed);    /* FEAT10Data.cu:728-749 */
 int tlfea_t10_update_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed); /* FEAT10Data.cu:751-832 */

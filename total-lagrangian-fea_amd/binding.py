@@ -83,6 +83,21 @@ def _obstacle_signatures(lib):
         getattr(lib, name).restype = C.c_int
 
 
+def _stress_signatures(lib):
+    """ctypes signatures of the stress-recovery entry points."""
+    vp, i = C.c_void_p, C.c_int
+    sig = {"tlfea_t10_calc_stress": [vp, vp, i], "tlfea_t10_calc_stress_host": [vp, c_dp, i],
+           "tlfea_t10_retrieve_point_stress": [vp, c_dp],
+           "tlfea_t10_retrieve_element_stress": [vp, c_dp, c_dp, c_dp, c_dp, c_dp],
+           "tlfea_t10_retrieve_nodal_stress": [vp, c_dp, c_dp], "tlfea_t10_get_energies": [vp, c_dp],
+           "tlfea_t10_time_stress_kernels": [vp, vp, i, i, c_dp]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+    lib.tlfea_t10_nodal_stress_device_ptr.argtypes = [vp]
+    lib.tlfea_t10_nodal_stress_device_ptr.restype = vp
+
+
 def _material_signatures(lib):
     """ctypes signatures of the per-element material entry points."""
     vp, i = C.c_void_p, C.c_int
@@ -158,6 +173,7 @@ def load_library():
     _contact_signatures(lib)
     _material_signatures(lib)
     _obstacle_signatures(lib)
+    _stress_signatures(lib)
     _LIB = lib
     return lib
 

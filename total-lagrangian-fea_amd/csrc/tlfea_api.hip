@@ -99,6 +99,11 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   int* d_ob_node = nullptr;
   double *d_ob_w = nullptr, *d_ob_f = nullptr, *d_ob_blk = nullptr, *d_ob_fk = nullptr, *d_ob_res = nullptr;
   int ob_fk_cap = 0;                // obstacles d_ob_fk has room for
+  // stress recovery (tlfea_t10_calc_stress): allocated on first use, read by no solver
+  double *d_st_pts = nullptr, *d_st_erec = nullptr, *d_st_contrib = nullptr, *d_st_nodal = nullptr,
+         *d_st_part = nullptr, *d_st_tot = nullptr, *d_st_vel = nullptr;
+  double st_tot[5] = {0, 0, 0, 0, 0};
+  bool st_valid = false, st_pts_valid = false;  // a calc_stress has run | its point stresses were asked for
   // constraints
   double* d_cons = nullptr;
   int *d_fixed = nullptr, *d_fixed_slot = nullptr;
@@ -208,7 +213,8 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_fext, h->d_cons, h->d_fixed, h->d_fixed_slot, h->d_off, h->d_cols, h->d_n2e_off, h->d_n2e,
                   h->d_n2e_pos, h->d_diagpos, h->d_mval, h->d_joff, h->d_jcol, h->d_jtoff, h->d_jtcol, h->d_jval,
                   h->d_jtval, h->d_rhs, h->d_emat, h->d_ob_node, h->d_ob_w, h->d_ob_f, h->d_ob_blk, h->d_ob_fk,
-                  h->d_ob_res};
+                  h->d_ob_res, h->d_st_pts, h->d_st_erec, h->d_st_contrib, h->d_st_nodal, h->d_st_part, h->d_st_tot,
+                  h->d_st_vel};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -1062,6 +1068,124 @@ extern "C" int tlfea_t10_retrieve_p_from_f(tlfea_t10_t h, double* P) {
 extern "C" int tlfea_t10_retrieve_deformation_gradient(tlfea_t10_t h, double* F) {
   if (!h->d_F) return fail("CalcP has not been called");
   D2H(F, h->d_F, (size_t)h->E * h->Q * 9);
+  return 0;
+}
+// ---- stress and energy recovery -----------------------------------------------------------------------------
+static int stress_prepare(tlfea_t10_t h, const double* d_vel, int want_points) {
+  if (h && h->kind != kT10) return fail("tlfea_t10_calc_stress: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "CalcStress.");
+  if (!h->have_dndu) return fail("tlfea_t10_calc_stress: CalcDnDuPre must be called first");
+  if (d_vel && h->mass_rho0 < 0.0)
+    return fail("tlfea_t10_calc_stress: a velocity was given but the mass matrix is not assembled (the kinetic energy "
+                "needs CalcMassMatrix)");
+  if (!h->is_csr_setup) TRY(tlfea_t10_build_mass_csr_pattern(h));  // the node -> element incidence of the nodal gather
+  if (!h->d_st_erec) {
+    TRY(dmalloc(&h->d_st_erec, (size_t)h->E * 10));
+    TRY(dmalloc(&h->d_st_contrib, (size_t)h->Epad * 4));
+    TRY(dmalloc(&h->d_st_nodal, (size_t)h->N * 7));
+    TRY(dmalloc(&h->d_st_part, (size_t)kStressMaxPart * 5));
+    TRY(dmalloc(&h->d_st_tot, (size_t)5));
+  }
+  if (want_points && !h->d_st_pts) TRY(dmalloc(&h->d_st_pts, (size_t)h->E * kNQ * 6));
+  return 0;
+}
+extern "C" int tlfea_t10_calc_stress(tlfea_t10_t h, const double* d_vel, int want_points) {
+  TRY(stress_prepare(h, d_vel, want_points));
+  h->st_valid = h->st_pts_valid = false;
+  launch_stress_points(h->stream, h->view(), h->mat, h->d_emat, d_vel, want_points ? h->d_st_pts : nullptr, h->d_st_erec,
+                       h->d_st_contrib);
+  launch_stress_nodal(h->stream, h->N, h->inc(), h->d_st_erec, h->d_st_nodal);
+  launch_stress_totals(h->stream, h->E, h->Epad, h->d_st_contrib, h->N, h->inc(), h->d_mval, d_vel, h->d_st_part,
+                       h->d_st_tot);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
+  h->st_valid = true;
+  h->st_pts_valid = want_points != 0;
+  return 0;
+}
+// the same with a velocity on the host (3N interleaved, or null), uploaded to a buffer of the object
+extern "C" int tlfea_t10_calc_stress_host(tlfea_t10_t h, const double* vel, int want_points) {
+  if (!vel) return tlfea_t10_calc_stress(h, nullptr, want_points);
+  if (h && h->kind != kT10) return fail("tlfea_t10_calc_stress: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "CalcStress.");
+  if (!h->d_st_vel) TRY(dmalloc(&h->d_st_vel, (size_t)3 * h->N));
+  HIP_TRY(hipMemcpy(h->d_st_vel, vel, (size_t)3 * h->N * sizeof(double), hipMemcpyHostToDevice));
+  return tlfea_t10_calc_stress(h, h->d_st_vel, want_points);
+}
+#define NEED_STRESS(h, what)                                                                            \
+  if ((h) && (h)->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)"); \
+  if (!(h) || !(h)->st_valid) return fail(std::string(what) + ": tlfea_t10_calc_stress has not been called")
+extern "C" int tlfea_t10_retrieve_point_stress(tlfea_t10_t h, double* sigma) {
+  NEED_STRESS(h, "tlfea_t10_retrieve_point_stress");
+  if (!h->st_pts_valid)
+    return fail("tlfea_t10_retrieve_point_stress: the last tlfea_t10_calc_stress did not ask for point stresses (want_points = 0)");
+  if (!sigma) return fail("tlfea_t10_retrieve_point_stress: null output");
+  D2H(sigma, h->d_st_pts, (size_t)h->E * kNQ * 6);
+  return 0;
+}
+extern "C" int tlfea_t10_retrieve_element_stress(tlfea_t10_t h, double* sigma, double* von_mises, double* psi, double* J,
+                                                 double* vol) {
+  NEED_STRESS(h, "tlfea_t10_retrieve_element_stress");
+  std::vector<double> rec((size_t)h->E * 10);
+  D2H(rec.data(), h->d_st_erec, rec.size());
+  for (int e = 0; e < h->E; e++) {
+    const double* r = &rec[(size_t)e * 10];
+    if (sigma) std::copy_n(r, 6, sigma + (size_t)e * 6);
+    if (von_mises) von_mises[e] = r[6];
+    if (psi) psi[e] = r[7];
+    if (J) J[e] = r[8];
+    if (vol) vol[e] = r[9];
+  }
+  return 0;
+}
+extern "C" int tlfea_t10_retrieve_nodal_stress(tlfea_t10_t h, double* sigma, double* von_mises) {
+  NEED_STRESS(h, "tlfea_t10_retrieve_nodal_stress");
+  std::vector<double> rec((size_t)h->N * 7);
+  D2H(rec.data(), h->d_st_nodal, rec.size());
+  for (int i = 0; i < h->N; i++) {
+    if (sigma) std::copy_n(&rec[(size_t)i * 7], 6, sigma + (size_t)i * 6);
+    if (von_mises) von_mises[i] = rec[(size_t)i * 7 + 6];
+  }
+  return 0;
+}
+extern "C" int tlfea_t10_get_energies(tlfea_t10_t h, double out[5]) {
+  NEED_STRESS(h, "tlfea_t10_get_energies");
+  if (!out) return fail("tlfea_t10_get_energies: null output");
+  std::copy_n(h->st_tot, 5, out);
+  return 0;
+}
+extern "C" double* tlfea_t10_nodal_stress_device_ptr(tlfea_t10_t h) { return h && h->st_valid ? h->d_st_nodal : nullptr; }
+// Mean duration (ms) over `reps` back-to-back launches of out[0] the point and element kernel, [1] the nodal gather,
+// [2] the two totals launches, each bracketed by one hipEvent pair (as tlfea_newton_time_kernels).
+extern "C" int tlfea_t10_time_stress_kernels(tlfea_t10_t h, const double* d_vel, int want_points, int reps, double* out_ms3) {
+  TRY(stress_prepare(h, d_vel, want_points));
+  if (!out_ms3) return fail("tlfea_t10_time_stress_kernels: null output");
+  if (reps < 1) reps = 1;
+  hipEvent_t ev[2];
+  HIP_TRY(hipEventCreate(&ev[0]));
+  HIP_TRY(hipEventCreate(&ev[1]));
+  for (int k = 0; k < 3; k++) {
+    HIP_TRY(hipEventRecord(ev[0], h->stream));
+    for (int r = 0; r < reps; r++) {
+      if (k == 0)
+        launch_stress_points(h->stream, h->view(), h->mat, h->d_emat, d_vel, want_points ? h->d_st_pts : nullptr,
+                             h->d_st_erec, h->d_st_contrib);
+      else if (k == 1) launch_stress_nodal(h->stream, h->N, h->inc(), h->d_st_erec, h->d_st_nodal);
+      else
+        launch_stress_totals(h->stream, h->E, h->Epad, h->d_st_contrib, h->N, h->inc(), h->d_mval, d_vel, h->d_st_part,
+                             h->d_st_tot);
+    }
+    HIP_TRY(hipEventRecord(ev[1], h->stream));
+    HIP_TRY(hipEventSynchronize(ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    out_ms3[k] = ms / reps;
+  }
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
+  h->st_valid = true;
+  h->st_pts_valid = want_points != 0;
   return 0;
 }
 extern "C" int tlfea_t10_retrieve_dndu_pre(tlfea_t10_t h, double* g) { D2H(g, h->d_gradN, (size_t)h->E * h->Q * 3 * h->S); return 0; }

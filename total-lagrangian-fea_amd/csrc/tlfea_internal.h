@@ -365,4 +365,18 @@ void launch_obstacle_hessian(hipStream_t s, int n_surf, const int* node, const i
 // out[j][4] = fixed-order sums of fk over the surface nodes, one block per obstacle
 void launch_obstacle_resultant(hipStream_t s, int n_surf, int n_obs, const double* fk, double* out);
 
+// Stress and energy recovery of T10 objects (tlfea_t10_calc_stress; stress_kernels.hip).  No atomics.
+// pts (null: not wanted) [E][5][6] Cauchy stress per Keast point, xx yy zz xy yz zx; erec [E][10] = volume-weighted mean
+// stress (6) | its von Mises | mean strain-energy density | mean J | reference volume V_e; contrib [4][Epad] the element's
+// integrals of {psi, P_vis:Fdot, 1, J}.  v (3N interleaved, may be null) adds the Kelvin-Voigt stress of a damped material.
+void launch_stress_points(hipStream_t s, const ElemView& m, const Material& mat, const double* emat, const double* v,
+                          double* pts, double* erec, double* contrib);
+// nodal [N][7]: V_e-weighted mean of the incident elements' mean stresses (ascending element order) | its von Mises
+void launch_stress_nodal(hipStream_t s, int N, const Incidence& inc, const double* erec, double* nodal);
+// out5 = {strain energy, 1/2 v.Mv (0 without v), viscous power, reference volume, current volume}: fixed-order partial
+// sums (partial: kStressMaxPart x 5 doubles), then one block with a fixed tree
+constexpr int kStressMaxPart = 1024;
+void launch_stress_totals(hipStream_t s, int E, int Epad, const double* contrib, int N, const Incidence& inc,
+                          const double* mval, const double* v, double* partial, double* out5);
+
 }  // namespace tlfea

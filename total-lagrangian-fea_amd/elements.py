@@ -1,6 +1,7 @@
 """GPU_FEAT10_Data -- host mirror of the reference class (lib_src/elements/FEAT10Data.cuh:19-852) on the
 C-ABI.  Method names, argument order and call-order contract follow the reference; Eigen vectors become
 NumPy arrays, Eigen::MatrixXi connectivity is an (E,10) int array (sent column-major as the reference does)."""
+import collections
 import ctypes as C
 import dataclasses
 
@@ -25,6 +26,11 @@ class ElementMaterial:
     rho0: float = 0.0
     eta: float = 0.0
     lamd: float = 0.0
+
+
+ElementStress = collections.namedtuple("ElementStress", "sigma von_mises psi J volume")
+NodalStress = collections.namedtuple("NodalStress", "sigma von_mises")
+Energies = collections.namedtuple("Energies", "strain kinetic viscous_power reference_volume current_volume")
 
 
 def _f64(a):
@@ -214,6 +220,64 @@ class GPU_FEAT10_Data:
 
     def CalcInternalForce(self):
         check(self._lib.tlfea_t10_calc_internal_force(self._h))
+
+    # -- stress and energy recovery --------------------------------------------------------------
+    def _stress_velocity(self, velocity):
+        """(device pointer, host array) of CalcStress's velocity: a solver object gives its device pointer."""
+        if velocity is None:
+            return None, None
+        if hasattr(velocity, "GetVelocityGuessDevicePtr"):
+            return velocity.GetVelocityGuessDevicePtr(), None
+        v = _f64(velocity).reshape(-1)
+        if v.size != 3 * self.n_coef:
+            raise ValueError(f"CalcStress: the velocity needs {3 * self.n_coef} entries, got {v.size}")
+        return None, v
+
+    def CalcStress(self, velocity=None, points=False):
+        """Cauchy stress, strain-energy density and energies at the current positions.  `velocity`: None, a solver (its
+        device velocity is used) or a host array of 3N; it adds a damped material's viscous stress and gives the kinetic
+        energy and the viscous power.  `points` also keeps the stresses of the five quadrature points."""
+        ptr, host = self._stress_velocity(velocity)
+        if host is not None:
+            check(self._lib.tlfea_t10_calc_stress_host(self._h, dp(host), int(bool(points))))
+        else:
+            check(self._lib.tlfea_t10_calc_stress(self._h, C.c_void_p(ptr), int(bool(points))))
+
+    def RetrievePointStressToCPU(self):
+        """[E][5][6]: xx yy zz xy yz zx per quadrature point (CalcStress(points=True))."""
+        s = np.zeros((self.n_elem, 5, 6))
+        check(self._lib.tlfea_t10_retrieve_point_stress(self._h, dp(s)))
+        return s
+
+    def RetrieveElementStressToCPU(self):
+        """Reference-volume-weighted element means: sigma [E][6], von Mises of it, psi, J, and the element volume."""
+        E = self.n_elem
+        s, vm, psi, J, vol = np.zeros((E, 6)), np.zeros(E), np.zeros(E), np.zeros(E), np.zeros(E)
+        check(self._lib.tlfea_t10_retrieve_element_stress(self._h, dp(s), dp(vm), dp(psi), dp(J), dp(vol)))
+        return ElementStress(s, vm, psi, J, vol)
+
+    def RetrieveNodalStressToCPU(self):
+        """Element-volume-weighted nodal stress [N][6] and the von Mises stress of that tensor [N]."""
+        s, vm = np.zeros((self.n_coef, 6)), np.zeros(self.n_coef)
+        check(self._lib.tlfea_t10_retrieve_nodal_stress(self._h, dp(s), dp(vm)))
+        return NodalStress(s, vm)
+
+    def GetEnergies(self):
+        out = np.zeros(5)
+        check(self._lib.tlfea_t10_get_energies(self._h, dp(out)))
+        return Energies(*out.tolist())
+
+    def GetNodalStressDevicePtr(self):
+        return self._lib.tlfea_t10_nodal_stress_device_ptr(self._h)
+
+    def TimeStressKernels(self, velocity=None, points=False, reps=20):
+        """-> mean ms of (point and element kernel, nodal gather, totals) over `reps` back-to-back launches each."""
+        ptr, host = self._stress_velocity(velocity)
+        if host is not None:
+            raise ValueError("TimeStressKernels: pass a solver or None")
+        out = np.zeros(3)
+        check(self._lib.tlfea_t10_time_stress_kernels(self._h, C.c_void_p(ptr), int(bool(points)), int(reps), dp(out)))
+        return out
 
     # -- getters ----------------------------------------------------------------------------------
     def get_n_elem(self):

@@ -753,6 +753,54 @@ struct GPU_FEAT10_Data : public ElementBase {
     w.resize(n_coef);
     TLFEA_HANDLE_ERROR(tlfea_t10_get_surface_weights(h, w.data()));
   }
+  // stress and energy recovery (no reference counterpart).  velocity: a solver's GetVelocityGuessDevicePtr()
+  // (device) or null; CalcStressFromHost takes 3N host values.  Status 0 = done (tlfea_last_error() explains a refusal).
+  int CalcStress(const double* d_velocity = nullptr, bool points = false) {
+    return tlfea_t10_calc_stress(h, d_velocity, points ? 1 : 0);
+  }
+  int CalcStressFromHost(const tlfea::VectorXd& velocity, bool points = false) {
+    if (velocity.size() != 3 * n_coef) return tlfea_t10_calc_stress_host(h, nullptr, points ? 1 : 0);
+    return tlfea_t10_calc_stress_host(h, velocity.data(), points ? 1 : 0);
+  }
+  // sigma[e][q]: 6 x 1 (xx yy zz xy yz zx) per quadrature point
+  void RetrievePointStressToCPU(std::vector<std::vector<tlfea::VectorXd>>& sigma) {
+    std::vector<double> flat(static_cast<size_t>(n_elem) * 30);
+    TLFEA_HANDLE_ERROR(tlfea_t10_retrieve_point_stress(h, flat.data()));
+    sigma.assign(n_elem, std::vector<tlfea::VectorXd>(5, tlfea::VectorXd(6)));
+    for (int e = 0; e < n_elem; e++)
+      for (int q = 0; q < 5; q++) std::copy_n(flat.data() + (static_cast<size_t>(e) * 5 + q) * 6, 6, sigma[e][q].data());
+  }
+  // sigma: E x 6 element means; von Mises of the mean, mean strain-energy density, mean J, element volume: E each
+  void RetrieveElementStressToCPU(tlfea::MatrixXd& sigma, tlfea::VectorXd& von_mises, tlfea::VectorXd& psi,
+                                  tlfea::VectorXd& J, tlfea::VectorXd& volume) {
+    std::vector<double> flat(static_cast<size_t>(n_elem) * 6);
+    von_mises.resize(n_elem);
+    psi.resize(n_elem);
+    J.resize(n_elem);
+    volume.resize(n_elem);
+    TLFEA_HANDLE_ERROR(tlfea_t10_retrieve_element_stress(h, flat.data(), von_mises.data(), psi.data(), J.data(), volume.data()));
+    sigma.resize(n_elem, 6);
+    for (int e = 0; e < n_elem; e++)
+      for (int c = 0; c < 6; c++) sigma(e, c) = flat[static_cast<size_t>(e) * 6 + c];
+  }
+  // sigma: N x 6 nodal stress, von_mises: N (of the nodal tensor)
+  void RetrieveNodalStressToCPU(tlfea::MatrixXd& sigma, tlfea::VectorXd& von_mises) {
+    std::vector<double> flat(static_cast<size_t>(n_coef) * 6);
+    von_mises.resize(n_coef);
+    TLFEA_HANDLE_ERROR(tlfea_t10_retrieve_nodal_stress(h, flat.data(), von_mises.data()));
+    sigma.resize(n_coef, 6);
+    for (int i = 0; i < n_coef; i++)
+      for (int c = 0; c < 6; c++) sigma(i, c) = flat[static_cast<size_t>(i) * 6 + c];
+  }
+  struct Energies {
+    double strain, kinetic, viscous_power, reference_volume, current_volume;
+  };
+  Energies GetEnergies() {
+    double o[5];
+    TLFEA_HANDLE_ERROR(tlfea_t10_get_energies(h, o));
+    return Energies{o[0], o[1], o[2], o[3], o[4]};
+  }
+  double* GetNodalStressDevicePtr() { return tlfea_t10_nodal_stress_device_ptr(h); }
   void SetExternalForce(const tlfea::VectorXd& h_f_ext) {
     TLFEA_SOFT(tlfea_t10_set_external_force(h, h_f_ext.data(), h_f_ext.size()));
   }

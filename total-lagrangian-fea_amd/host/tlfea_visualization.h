@@ -120,6 +120,26 @@ struct VisualizationUtils {
     return WriteVTU(filename, pts, corner_tets(elements), 4, 10, {m, d});
   }
 
+  // T10 mesh at `nodes` + nodal "displacement" (3), Cauchy "stress" (6: xx yy zz xy yz zx, N x 6) and "von_mises" (1),
+  // as GPU_FEAT10_Data::RetrieveNodalStressToCPU returns them (no reference counterpart)
+  static bool ExportMeshWithStress(const tlfea::MatrixXd& nodes, const tlfea::MatrixXi& elements,
+                                   const tlfea::VectorXd& displacement, const tlfea::MatrixXd& nodal_sigma6,
+                                   const tlfea::VectorXd& nodal_von_mises, const std::string& filename) {
+    const int n = nodes.rows();
+    std::vector<P3> pts(n);
+    PointField d{"displacement", 3, std::vector<double>(3 * (size_t)n, 0.0)}, s{"stress", 6, std::vector<double>(6 * (size_t)n, 0.0)},
+        m{"von_mises", 1, std::vector<double>(n, 0.0)};
+    for (int i = 0; i < n; i++) {
+      pts[i] = {nodes(i, 0), nodes(i, 1), nodes(i, 2)};
+      for (int c = 0; c < 3; c++)
+        if (3 * i + c < displacement.size()) d.values[3 * (size_t)i + c] = displacement(3 * i + c);
+      if (i < nodal_sigma6.rows() && nodal_sigma6.cols() == 6)
+        for (int c = 0; c < 6; c++) s.values[6 * (size_t)i + c] = nodal_sigma6(i, c);
+      if (i < nodal_von_mises.size()) m.values[i] = nodal_von_mises(i);
+    }
+    return WriteVTU(filename, pts, corner_tets(elements), 4, 10, {m, d, s});
+  }
+
   // One hexahedron per shell: the four corner positions (coefficient slot 0 of each node) pushed -/+ thickness/2 along
   // the element normal (p1-p0) x (p3-p0); bottom face first (visualization_utils.h:848-955)
   static bool ExportANCF3443ToVTU(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
