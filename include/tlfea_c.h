@@ -280,6 +280,14 @@ int tlfea_newton_linear_solve(tlfea_newton_t s, const double *b, double *x, int 
 int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double *out_ms7);
 /* y = H x with the current H, host vectors of 3N (partition-boundary rows summed over ranks). */
 int tlfea_newton_apply_hessian(tlfea_newton_t s, const double *x, double *y);
+/* The same product from the matrix-free pair of the CG iteration (element records instead of the CSR values),
+ * with the records of the last assembly.  Returns an error where that product is not eligible: anything but straight-sided
+ * T10 elements with one St.Venant-Kirchhoff material on one GPU, general linear constraints, rigid obstacles, per-element
+ * materials, or a residual evaluation since the last assembly. */
+int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double *x, double *y);
+/* which product the CG iterations of the last linear solve used: 0 = CSR kernel, 1 = matrix-free pair
+ * (TLFEA_SPMV_MATFREE=0|1 forces it off / on where eligible; default: eligible and at least 150 000 nodes) */
+int tlfea_newton_get_spmv_mode(tlfea_newton_t s);
 /* One full Newton iteration without the convergence test (gradient, assembly, solve, update):
  * the unit bench.py times.  iters = PCG iterations used. */
 int tlfea_newton_iteration(tlfea_newton_t s, double *norm_g, int *iters);

@@ -2118,6 +2118,279 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
 }
 
 // ------------------------------------------------------------------------------------------------
+// matrix-free product q = H p on affine elements (T10, SVK + Kelvin-Voigt, one material): the linear map that
+// assemble_affine_kernel assembles, applied element by element from the records the engine keeps anyway -- 128 bytes of
+// vertex gradients + det J, 400 bytes of F at the five points, 40 bytes of connectivity -- instead of the 2 950 bytes
+// of CSR stream per element.  Two launches in the shape of residual_kernel + grad_light_kernel:
+//   tangent_apply_affine_kernel  thread per element: dF(q) = sum_n U_n(q) (x) g_n, dP = dF S_h + F dS, one 24-byte row
+//                                per (element, local node) into ybuf [a][Epad][3]
+//   matfree_gather_kernel        8 lanes per node sum the node's rows in ascending element order (fixed-order butterfly),
+//                                add h^2 rho p on pinned rows, store q and the p.q partial slots
+// With L the barycentric coordinates of a point, grad N of vertex n is (4 L_n - 1) g_n and of mid-edge (n, m)
+// 4 (L_m g_n + L_n g_m); the rule has L = 1/4 at the centroid point and L_v = 1/2, others 1/6 at outer point v.  Hence
+//   dF(centroid) = sum_n S_n (x) g_n                         S_n = sum of p over the three mid-edge nodes at vertex n
+//   dF(point v)  = sum_n (2/3 S_n - 1/3 p_n) (x) g_n + 4/3 (p_v (x) g_v + sum_{n != v} p_{nv} (x) g_n)
+// and on the way out, with P_q = w_q det J dP(q), SP = P_1 + .. + P_4:
+//   y_vertex n   = (4/3 P_n - 1/3 SP) g_n
+//   y_edge (a,b) = (P_0 + 2/3 SP) (g_a + g_b) + 4/3 (P_b g_a + P_a g_b)
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kMfG = 18;            // doubles per staged g record (16 + pad: 144 bytes, own-record reads spread over the banks)
+constexpr int kMfLds = 64 * kMfG;   // doubles of wave-private LDS (g records, then 64 x 10 of F per point, then 64 x 3 rows)
+}  // namespace
+
+__global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int Epad, const int* __restrict__ conn,
+                                                                  const double* __restrict__ gvec,
+                                                                  const double* __restrict__ Fq16, MatfreeCoef mc,
+                                                                  const double* __restrict__ p,
+                                                                  double* __restrict__ ybuf) {
+  __shared__ __attribute__((aligned(16))) double st_all[2 * kMfLds];
+  double* st = st_all + (threadIdx.x >> 6) * kMfLds;  // this wavefront's slice
+  double2* st2 = reinterpret_cast<double2*>(st);
+  const int lane = threadIdx.x & 63;
+  const int e0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);  // first element of this wavefront
+  const int last = E - 1;
+  // lanes past the end stay for the transposes (every read is clamped to the last element, the stores stay inside Epad)
+  const int e = min(blockIdx.x * blockDim.x + threadIdx.x, last);
+
+  // ---- g records: 64 x 128 contiguous bytes, whole-line loads, each lane takes its own record from LDS ---------------
+  {
+    const double2* src = reinterpret_cast<const double2*>(gvec);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int idx = lane + 64 * j, el = idx >> 3, c = idx & 7;
+      st2[el * (kMfG / 2) + c] = src[(size_t)min(e0 + el, last) * 8 + c];
+    }
+  }
+  // F records of the first point in flight: 64 x 80 bytes, 16 per lane and instruction
+  double2 nx[5];
+  auto fetch = [&](const int sdx) __attribute__((always_inline)) {
+    const double2* src = reinterpret_cast<const double2*>(Fq16);
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      const int idx = lane + 64 * j, el = idx / 5, c = idx - 5 * el;
+      nx[j] = src[(size_t)min(e0 + el, last) * 25 + sdx * 5 + c];
+    }
+  };
+  fetch(0);
+  wave_sync();
+  double g[4][3], detJ;
+  {
+    const double* gr = st + lane * kMfG;
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+      const double2 a = *reinterpret_cast<const double2*>(gr + 4 * n);
+      g[n][0] = a.x;
+      g[n][1] = a.y;
+      g[n][2] = gr[4 * n + 2];
+    }
+    detJ = gr[3];
+  }
+
+  // ---- dF at the five points (slot order: centroid, then the point of vertex 0..3), one component of p at a time -------
+  double D[5][9], Wm[kNQ][3];
+  {
+    int gn[kNN];
+#pragma unroll
+    for (int a = 0; a < kNN; a++) gn[a] = conn[(size_t)a * E + e];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      double pc[kNN];
+#pragma unroll
+      for (int a = 0; a < kNN; a++) pc[a] = p[3 * (size_t)gn[a] + i];
+      // mid-edge nodes 4..9 = (0,1) (1,2) (0,2) (0,3) (1,3) (2,3)   (FEAT10Data.cu:143)
+      const double S[4] = {pc[4] + pc[6] + pc[7], pc[4] + pc[5] + pc[8], pc[5] + pc[6] + pc[9], pc[7] + pc[8] + pc[9]};
+      // column v: p of vertex v and of the mid-edge nodes (n, v)
+      const double Cv[4][4] = {{pc[0], pc[4], pc[6], pc[7]}, {pc[4], pc[1], pc[5], pc[8]}, {pc[6], pc[5], pc[2], pc[9]},
+                               {pc[7], pc[8], pc[9], pc[3]}};
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        double c0 = 0.0, w = 0.0;
+#pragma unroll
+        for (int n = 0; n < 4; n++) {
+          c0 += S[n] * g[n][d];
+          w += ((2.0 / 3.0) * S[n] - (1.0 / 3.0) * pc[n]) * g[n][d];
+        }
+        D[0][3 * i + d] = c0;
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+          double t = 0.0;
+#pragma unroll
+          for (int n = 0; n < 4; n++) t += Cv[v][n] * g[n][d];
+          D[1 + v][3 * i + d] = w + (4.0 / 3.0) * t;
+        }
+      }
+      // mass: sum_j N_j(q) p_j at the rule's points (rule order)
+#pragma unroll
+      for (int q = 0; q < kNQ; q++) {
+        double w = 0.0;
+#pragma unroll
+        for (int a = 0; a < kNN; a++) w += mc.Nq[q][a] * pc[a];
+        Wm[q][i] = w;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kNQ; q++) {
+    const double cq = mc.rho_inv_h * detJ * mc.mw[q];
+#pragma unroll
+    for (int i = 0; i < 3; i++) Wm[q][i] *= cq;
+  }
+
+  // ---- P_q = w_q det J (dF S_h + F dS) in place of dF(q); the next point's records are in flight meanwhile ------------
+#pragma unroll
+  for (int sdx = 0; sdx < 5; sdx++) {
+    wave_sync();  // the g records / the previous point have been read
+#pragma unroll
+    for (int j = 0; j < 5; j++) st2[lane + 64 * j] = nx[j];
+    if (sdx < 4) fetch(sdx + 1);
+    wave_sync();
+    const double2* R2 = reinterpret_cast<const double2*>(st + lane * 10);
+    const double2 r0 = R2[0], r1 = R2[1], r2 = R2[2], r3 = R2[3], r4 = R2[4];
+    const double F[3][3] = {{r0.x, r0.y, r1.x}, {r1.y, r2.x, r2.y}, {r3.x, r3.y, r4.x}};
+    double(&dF)[9] = D[sdx];
+    double C[3][3], G[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        C[i][j] = F[0][i] * F[0][j] + F[1][i] * F[1][j] + F[2][i] * F[2][j];
+        G[i][j] = F[0][i] * dF[j] + F[1][i] * dF[3 + j] + F[2][i] * dF[6 + j];
+      }
+    const double trE = 0.5 * (C[0][0] + C[1][1] + C[2][2] - 3.0);
+    const double trG = G[0][0] + G[1][1] + G[2][2];
+    const double k0 = mc.cl * trE - mc.c1;  // h (lambda tr E - mu)   (SVK.cuh:35-55)
+    double M1[3][3], M2[3][3];              // S_h = k0 I + h mu F^T F ; dS = a tr(dE) I + b (G + G^T)
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        M1[i][j] = mc.c1 * C[i][j] + (i == j ? k0 : 0.0);
+        M2[i][j] = mc.b * (G[i][j] + G[j][i]) + (i == j ? mc.a * trG : 0.0);
+      }
+    const double dV = detJ * (sdx == 0 ? mc.w0 : mc.w1);
+    double Pn[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++)
+        Pn[3 * i + j] = dV * (dF[3 * i] * M1[0][j] + dF[3 * i + 1] * M1[1][j] + dF[3 * i + 2] * M1[2][j] +
+                              F[i][0] * M2[0][j] + F[i][1] * M2[1][j] + F[i][2] * M2[2][j]);
+#pragma unroll
+    for (int t = 0; t < 9; t++) dF[t] = Pn[t];
+  }
+
+  // ---- rows out: [a][Epad][3], a wavefront's 64 rows of local node a are 1 536 contiguous bytes -----------------------
+  double SPg[4][3], Bg[4][3];  // SP g_n and (P_0 + 2/3 SP) g_n
+  {
+    double SP[9];
+#pragma unroll
+    for (int t = 0; t < 9; t++) SP[t] = (D[1][t] + D[2][t]) + (D[3][t] + D[4][t]);
+#pragma unroll
+    for (int n = 0; n < 4; n++)
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        SPg[n][i] = SP[3 * i] * g[n][0] + SP[3 * i + 1] * g[n][1] + SP[3 * i + 2] * g[n][2];
+        Bg[n][i] = D[0][3 * i] * g[n][0] + D[0][3 * i + 1] * g[n][1] + D[0][3 * i + 2] * g[n][2] + (2.0 / 3.0) * SPg[n][i];
+      }
+  }
+#pragma unroll
+  for (int a = 0; a < kNN; a++) {
+    const int A = (0x904e4 >> (2 * a)) & 3;  // {0,1,2,3,0,1,0,0,1,2}: vertex a, or the ends (A, B) of mid-edge a
+    const int B = (0xfe9e4 >> (2 * a)) & 3;  // {0,1,2,3,1,2,2,3,3,3}
+    double y[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      if (a < 4) {
+        const double* P = D[1 + a];
+        y[i] = (4.0 / 3.0) * (P[3 * i] * g[a][0] + P[3 * i + 1] * g[a][1] + P[3 * i + 2] * g[a][2]) - (1.0 / 3.0) * SPg[a][i];
+      } else {
+        const double *PA = D[1 + A], *PB = D[1 + B];
+        y[i] = Bg[A][i] + Bg[B][i] +
+               (4.0 / 3.0) * (PB[3 * i] * g[A][0] + PB[3 * i + 1] * g[A][1] + PB[3 * i + 2] * g[A][2] + PA[3 * i] * g[B][0] +
+                              PA[3 * i + 1] * g[B][1] + PA[3 * i + 2] * g[B][2]);
+      }
+      double mr = 0.0;  // (M_e p)_a / h
+#pragma unroll
+      for (int q = 0; q < kNQ; q++) mr += mc.Nq[q][a] * Wm[q][i];
+      y[i] += mr;
+    }
+    wave_sync();
+    st[3 * lane] = y[0];
+    st[3 * lane + 1] = y[1];
+    st[3 * lane + 2] = y[2];
+    wave_sync();
+    if (e0 < E) {  // rows past E: padding
+      double2* out = reinterpret_cast<double2*>(ybuf + ((size_t)a * Epad + e0) * 3);
+      out[lane] = st2[lane];
+      if (lane < 32) out[64 + lane] = st2[64 + lane];
+    }
+  }
+}
+
+void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineView& av, const double* Fq16,
+                                 const MatfreeCoef& mc, const double* p, double* ybuf) {
+  hipLaunchKernelGGL(tangent_apply_affine_kernel, dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn, av.gvec, Fq16,
+                     mc, p, ybuf);
+}
+
+// q = sum of the node's element rows (+ h^2 rho p on pinned rows, as the "rows out" phase of assemble_affine_kernel adds
+// it), and the p.q partial slots.  Workgroups own contiguous chunks of nodes and there are at most kNPart of them.
+__global__ __launch_bounds__(1024) void matfree_gather_kernel(int N, int Epad, Incidence inc, const double* __restrict__ ybuf,
+                                                             const double* __restrict__ p, const int* __restrict__ fixed_slot,
+                                                             const double* __restrict__ nw, double penalty,
+                                                             double* __restrict__ q, double* __restrict__ pq_part) {
+  __shared__ double sh[16];
+  const int l8 = threadIdx.x & 7, grp = threadIdx.x >> 3;
+  const int per = ((N + gridDim.x - 1) / gridDim.x + 127) / 128 * 128;  // whole tiles of 128 nodes
+  const int r0 = blockIdx.x * per, r1 = min(N, r0 + per);
+  double pq = 0.0;
+  for (int i = r0 + grp; i < r1; i += 128) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int k = inc.n2e_off[i] + l8; k < inc.n2e_off[i + 1]; k += 8) {
+      const int code = inc.n2e[k], e = code / kNN, la = code - kNN * e;
+      const double* r = ybuf + ((size_t)la * Epad + e) * 3;
+      a0 += r[0];
+      a1 += r[1];
+      a2 += r[2];
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+      a0 += __shfl_xor(a0, o);
+      a1 += __shfl_xor(a1, o);
+      a2 += __shfl_xor(a2, o);
+    }
+    if (l8 < 3) {
+      const int c = 3 * i + l8;
+      const double pv = p[c];
+      double sv = (l8 == 0) ? a0 : ((l8 == 1) ? a1 : a2);
+      if (fixed_slot && fixed_slot[i] >= 0) sv += (nw ? nw[i] : 1.0) * penalty * pv;
+      q[c] = sv;
+      pq += pv * sv;
+    }
+  }
+  // fixed order: wave butterfly, then the waves in ascending order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) pq += __shfl_xor(pq, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = pq;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = 0.0;
+    for (int k = 0; k < (int)(blockDim.x >> 6); k++) r += sh[k];
+    pq_part[blockIdx.x] = r;
+  }
+  if (blockIdx.x == 0)  // slots without a workgroup read 0
+    for (int k = gridDim.x + threadIdx.x; k < kNPart; k += blockDim.x) pq_part[k] = 0.0;
+}
+
+void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc, const double* ybuf, const double* p,
+                           const int* fixed_slot, const double* nw, double penalty, double* q, double* pq_part) {
+  const int grid = std::max(1, std::min(kNPart, (N + 127) / 128));
+  hipLaunchKernelGGL(matfree_gather_kernel, dim3(grid), dim3(1024), 0, s, N, Epad, inc, ybuf, p, fixed_slot, nw, penalty, q,
+                     pq_part);
+}
+
+// ------------------------------------------------------------------------------------------------
 // consistent mass (FEAT10Data.cu:206-278), row-owner form: thread per node row, fixed order
 // ------------------------------------------------------------------------------------------------
 template <bool PE>  // PE: per-element densities (slot kEmRhoM of emat), rho0 unused

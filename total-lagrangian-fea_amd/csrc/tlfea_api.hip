@@ -1356,6 +1356,18 @@ struct tlfea_newton_s {
   bool affine_ok = false;
   long geom_gen_seen = -1;   // data->geom_gen the affine cache (gvec, affine_ok) was built from
   double affine_dev = -1.0;  // largest relative deviation from the affine form found at set-up (-1: not checked)
+  // Matrix-free product of the CG iteration: q = H p from gvec and the F records in d_Fq instead of the CSR
+  // stream.  `valid`: d_Fq, gvec and the scalars below are those H was assembled from -- set by the affine assembly,
+  // cleared by every residual launch that rewrites d_Fq (the next assembly sets it again) and by a new affine set-up.
+  struct Matfree {
+    bool valid = false;
+    MatfreeCoef mc{};
+    const int* fixed = nullptr;  // pinned rows of the assembled H (null: none)
+    double penalty = 0.0;
+    double* d_ybuf = nullptr;    // [10][Epad][3] element rows, allocated on first use
+    bool now = false;            // the running / last solve takes the matrix-free product
+    int last_mode = 0;           // tlfea_newton_get_spmv_mode
+  } mf;
   // sparse direct solve (lin.method == 1): rocSOLVER re-factorisation on a host-computed ordering + factor pattern
   struct Direct {
     bool tried = false, ok = false;
@@ -1522,6 +1534,7 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
   if (s->d_cmass) (void)hipFree(s->d_cmass);
   if (s->d_Fq) (void)hipFree(s->d_Fq);
   if (s->d_mbuf) (void)hipFree(s->d_mbuf);
+  if (s->mf.d_ybuf) (void)hipFree(s->mf.d_ybuf);
   direct_destroy(s);
   for (auto& e : s->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1630,6 +1643,7 @@ static int setup_affine_form(tlfea_newton_t s, bool* affine_out) {
   const int N = s->N;
   *affine_out = false;
   s->affine_ok = false;
+  s->mf.valid = false;
   if (!(s->asm_mode == 0 && d->have_dndu)) return 0;
   AffineView av{nullptr, -1, {-1, -1, -1, -1}};
   bool rule_ok = true;
@@ -2549,6 +2563,7 @@ static int fq_slots(tlfea_newton_t s);
 // residual launch of the Newton path (the point records it leaves for the fused assembly follow the assembly's form)
 static void launch_residual_newton(tlfea_newton_t s, double* Fq, const MassTerm* mt) {
   tlfea_t10_t d = s->d;
+  if (Fq) s->mf.valid = false;  // the records no longer belong to the assembled H (the next assembly claims them)
   launch_residual(s->stream, d->view(), d->mat, s->d_v, d->d_fbuf, nullptr, nullptr, nullptr, nullptr, Fq, mt, fq_h(s),
                   fq_slots(s), d->d_emat);
 }
@@ -2561,15 +2576,38 @@ static int fq_slots(tlfea_newton_t s) {
   }
   return w;
 }
+static void fill_mass_shape(tlfea_newton_t s, MassTerm& mt);
 static void launch_fused(tlfea_newton_t s) {
   tlfea_t10_t d = s->d;
   const tlfea_newton_params& p = s->prm;
   const int* fixed = pinned_on(s) ? d->d_fixed_slot : nullptr;
-  if (affine_now(s))
+  s->mf.valid = false;
+  if (affine_now(s)) {
     launch_assemble_affine(s->stream, d->view(), d->mat, p.time_step, s->rg4, s->av, s->d_Fq, s->d_cmass,
                            d->d_emat ? 1.0 : (d->mass_rho0 > 0.0 ? d->mass_rho0 : 0.0), fixed, s->d_nw,
                            p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
-  else
+    // The matrix-free product applies THIS H: the same records and the same scalars, kept as they are now.  Terms that
+    // the callers add to H after this launch (general linear constraints, obstacle blocks) and per-element materials
+    // are not reproduced by the element map: such an H is served by the CSR kernel only.
+    auto& f = s->mf;
+    const double h = p.time_step;
+    f.mc.a = h * d->mat.lambda + d->mat.lamd;
+    f.mc.b = h * d->mat.mu + d->mat.eta;
+    f.mc.c1 = h * d->mat.mu;
+    f.mc.cl = h * d->mat.lambda;
+    f.mc.w0 = d->h_qw[s->av.q0];
+    f.mc.w1 = d->h_qw[s->av.qv[0]];
+    f.mc.rho_inv_h = (d->mass_rho0 > 0.0 ? d->mass_rho0 : 0.0) / h;
+    MassTerm mt{};
+    fill_mass_shape(s, mt);
+    for (int q = 0; q < kNQ; q++) {
+      f.mc.mw[q] = d->h_qw[q];
+      for (int k = 0; k < kNN; k++) f.mc.Nq[q][k] = mt.Nq[q][k];
+    }
+    f.fixed = fixed;
+    f.penalty = p.time_step * p.time_step * p.rho;
+    f.valid = !d->d_emat && !lincons_on(s) && d->obs.n == 0;
+  } else
     launch_assemble_direct(s->stream, d->view(), d->mat, p.time_step, s->rg, s->d_Fq, d->d_mval, fixed, s->d_nw,
                            p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
 }
@@ -2590,12 +2628,48 @@ static int fill_mass_term(tlfea_newton_t s, MassTerm& mt) {
   mt.vprev = s->d_vprev;
   mt.mbuf = s->d_mbuf;
   mt.rho_inv_h = (d->d_emat ? 1.0 : d->mass_rho0) / s->prm.time_step;  // per-element: x the record's density
+  fill_mass_shape(s, mt);
+  return 0;
+}
+// shape functions at the rule's points (the rule of the mass matrix, FEAT10Data.cu:206-278)
+static void fill_mass_shape(tlfea_newton_t s, MassTerm& mt) {
+  tlfea_t10_t d = s->d;
   const int edges[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};  // FEAT10Data.cu:143
   for (int q = 0; q < kNQ; q++) {
     const double L[4] = {1.0 - d->h_q[0][q] - d->h_q[1][q] - d->h_q[2][q], d->h_q[0][q], d->h_q[1][q], d->h_q[2][q]};
     for (int k = 0; k < 4; k++) mt.Nq[q][k] = L[k] * (2.0 * L[k] - 1.0);
     for (int k = 0; k < 6; k++) mt.Nq[q][k + 4] = 4.0 * L[edges[k][0]] * L[edges[k][1]];
   }
+}
+
+// ---- matrix-free product of the CG iteration --------------------------------------------------------------
+// TLFEA_SPMV_MATFREE: 0 never, 1 wherever eligible, unset = eligible and at least kMatfreeMinRows node rows
+static int matfree_env() {
+  static const int m = std::getenv("TLFEA_SPMV_MATFREE") ? (std::atoi(std::getenv("TLFEA_SPMV_MATFREE")) != 0 ? 1 : 0) : -1;
+  return m;
+}
+// Two launches (plus the direction kernel on meshes that would run the fused SpMV) replace one.  Measured on the SVK bars
+// (DESIGN 3g): a tie at 30 k nodes, -12 % per Newton iteration at 172 k, -10 % at 402 k, -13 % at 1.34 M; between 30 k and
+// 172 k nothing was measured, so the pick starts just below the smallest size measured to win.
+constexpr int kMatfreeMinRows = 150000;
+static bool matfree_eligible(tlfea_newton_t s) {
+  return affine_now(s) && s->mf.valid && !dist_on(s) && !lincons_on(s) && s->d->obs.n == 0 && !s->d->d_emat && !s->spmv32_now;
+}
+static bool matfree_chosen(tlfea_newton_t s) {
+  if (matfree_env() == 0 || !matfree_eligible(s)) return false;
+  return matfree_env() == 1 || s->N >= kMatfreeMinRows;
+}
+// the element rows' buffer (233 MB at config C): on first use, and outside any stream capture
+static int matfree_ensure_buffer(tlfea_newton_t s) {
+  if (s->mf.d_ybuf) return 0;
+  return dmalloc(&s->mf.d_ybuf, (size_t)s->d->Epad * 3 * kNN);
+}
+// q = H p and the p.q slots from the element records (p as pcg_direction_kernel left it)
+static int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part) {
+  tlfea_t10_t d = s->d;
+  auto& f = s->mf;
+  launch_tangent_apply_affine(s->stream, d->view(), s->av, s->d_Fq, f.mc, p, f.d_ybuf);
+  launch_matfree_gather(s->stream, s->N, d->Epad, d->inc(), f.d_ybuf, p, f.fixed, s->d_nw, f.penalty, q, pq_part);
   return 0;
 }
 
@@ -3787,7 +3861,9 @@ static int enqueue_cg_iteration_impl(tlfea_newton_t s, double* d_x, bool first, 
                           s->d_q, pq_part, true, s->spmv_nt);
   } else {
     launch_pcg_direction(s->stream, 3 * Np, s->d_zv, first, part(s, 1 - cur), part(s, cur), p_old);
-    if (s->spmv32_now)
+    if (s->mf.now)
+      TRY(launch_matfree_product(s, p_old, s->d_q, pq_part));
+    else if (s->spmv32_now)
       launch_spmv_dir_dot_f32(s->stream, Nr, d->inc(), s->d_H32, s->d_zv, p_old, first, part(s, 1 - cur), part(s, cur), p_old,
                               s->d_q, pq_part, false, wown);
     else
@@ -3863,7 +3939,8 @@ static void cg_graphs_destroy(tlfea_newton_t s) {
 // path calls back into the host between kernels).
 static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg, int bits) {
   const long key[6] = {deg + 1000 * precond_eff(s) + 100000L * (s->pmg.ok ? pmg_coarse_degree_eff(s) : 0),
-                       bits + (s->spmv32_now ? 100000L : 0), (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
+                       bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0),
+                       (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
                        (long)(size_t)s->d_B8, (long)(size_t)s->pmg.d_B8c};
   if (s->cg_graph[0] && std::equal(key, key + 6, s->cg_graph_key)) return 0;
   cg_graphs_destroy(s);
@@ -4159,6 +4236,8 @@ static int direct_solve(tlfea_newton_t s, const double* d_b, double* d_x, int* i
 
 // Solve H x = b on the device (b, x device vectors of 3N).  Standard PCG, block-Jacobi.
 static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out) {
+  s->mf.now = false;
+  s->mf.last_mode = 0;
   if (s->lin.method == 1) return direct_solve(s, d_b, d_x, iters_out, rel_out);
   tlfea_t10_t d = s->d;
   const int N = s->N;
@@ -4200,8 +4279,15 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
   double rr = bb;
   if (bb > 0.0) {
     const double target = s->lin.rel_tol * s->lin.rel_tol * bb;
-    const bool fused = s->pcg_fused < 0 ? (N <= 200000) : (s->pcg_fused != 0);
+    const bool fused_csr = s->pcg_fused < 0 ? (N <= 200000) : (s->pcg_fused != 0);
     const int deg = cheb_degree_eff(s);
+    // matrix-free product (serves the un-fused form: p from the direction kernel); everything before the iteration -- the
+    // diagonal, the low-precision copy, the lambda_max estimate, the Galerkin operators -- stays on the CSR H
+    s->spmv32_now = s->spmv32_every >= 2 && deg > 1 && lp && !s->ar;
+    s->mf.now = matfree_chosen(s);
+    s->mf.last_mode = s->mf.now ? 1 : 0;
+    if (s->mf.now) TRY(matfree_ensure_buffer(s));
+    const bool fused = fused_csr && !s->mf.now;
     // an outer iteration costs `deg` SpMV launches: test convergence proportionally more often
     int check_every = std::max(1, s->lin.check_every / deg);
     // Every convergence test drains the launch queue (tens of microseconds: as much as an iteration on a small
@@ -4613,6 +4699,23 @@ extern "C" int tlfea_newton_apply_hessian(tlfea_newton_t s, const double* x, dou
   D2H(y, s->d_q, n);
   return 0;
 }
+
+// y = H x from the matrix-free pair with the current records (tests); an error where the product is not eligible
+extern "C" int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double* x, double* y) {
+  if (!s || !x || !y) return fail("null argument");
+  if (!s->sparsity_done || !matfree_eligible(s))
+    return fail("matrix-free Hessian product: not eligible (needs an assembled H of straight-sided T10 elements with one "
+                "St.Venant-Kirchhoff material, one GPU, no linear constraints, no obstacles, and no residual evaluation "
+                "since the assembly)");
+  const size_t n = 3 * (size_t)s->N;
+  HIP_TRY(hipMemcpy(s->d_zv, x, n * sizeof(double), hipMemcpyHostToDevice));
+  TRY(matfree_ensure_buffer(s));
+  TRY(launch_matfree_product(s, s->d_zv, s->d_q, part(s, 2)));
+  HIP_TRY(hipGetLastError());
+  D2H(y, s->d_q, n);
+  return 0;
+}
+extern "C" int tlfea_newton_get_spmv_mode(tlfea_newton_t s) { return s ? s->mf.last_mode : -1; }
 
 static int newton_update(tlfea_newton_t s) {
   tlfea_t10_t d = s->d;

@@ -157,6 +157,20 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
                             double rho0 /*density of the assembled mass matrix, 0 = none (per-element: 1 = the
                                            records' kEmRhoM)*/, const int* fixed_slot,
                             const double* nw, double penalty, double* Hval, const double* emat = nullptr);
+// Matrix-free product q = H p on affine elements (one material): the scalars of the assembled H, as
+// launch_assemble_affine forms them, and the mass rule (N_j at the rule's points in the rule's order, its weights).
+struct MatfreeCoef {
+  double a, b, c1, cl;      // h lambda + lamd | h mu + eta | h mu | h lambda
+  double w0, w1;            // weight of the centroid point | of the four outer points
+  double rho_inv_h;         // density of the assembled mass matrix / h (0: none)
+  double Nq[kNQ][kNN], mw[kNQ];
+};
+// element rows of H p: ybuf [10][Epad][3]; Fq16 = the [E][5][10] records H was assembled from
+void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineView& av, const double* Fq16,
+                                 const MatfreeCoef& mc, const double* p, double* ybuf);
+// q = node-owner sum of the element rows (+ penalty x nw x p on pinned rows), p.q partials into the kNPart slots
+void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc, const double* ybuf, const double* p,
+                           const int* fixed_slot, const double* nw, double penalty, double* q, double* pq_part);
 void launch_tangent_blocks(hipStream_t s, const ElemView& m, const Material& mat, double h,
                            double* Kbuf /*[E][55][9]*/, const double* emat = nullptr);
 void launch_assemble_rows(hipStream_t s, int N, int S, int maxdeg, const Incidence& inc, const double* Kbuf,

@@ -178,6 +178,17 @@ class SyncedNewtonSolver:
         check(self._lib.tlfea_newton_apply_hessian(self._h, dp(x), dp(y)))
         return y
 
+    def ApplyHessianMatfree(self, x):
+        """y = H x from the matrix-free pair of the CG iteration (raises where it is not eligible)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.zeros_like(x)
+        check(self._lib.tlfea_newton_apply_hessian_matfree(self._h, dp(x), dp(y)))
+        return y
+
+    def GetSpmvMode(self):
+        """product of the last solve's CG iterations: 0 CSR kernel, 1 matrix-free pair"""
+        return int(self._lib.tlfea_newton_get_spmv_mode(self._h))
+
     def NewtonIteration(self):
         ng, it = C.c_double(), C.c_int()
         check(self._lib.tlfea_newton_iteration(self._h, C.byref(ng), C.byref(it)))
