@@ -226,6 +226,24 @@ int tlfea_t10_get_constraint_mode(tlfea_t10_t h);
 int tlfea_t10_constraint_jac_nnz(tlfea_t10_t h); /* CalcDsDuPre  ANCF3243Data.cu:290-300, ANCF3443Data.cu:256-266 */
 int tlfea_elem_dims(tlfea_t10_t h, int *S /*shape functions*/, int *Q /*force quadrature points*/);
 
+/* Stress and energy recovery of ANCF beam and shell meshes (no reference counterpart; DESIGN 3f').  The semantics are those
+ * of tlfea_t10_calc_stress above with these differences: the handle is an ANCF one (a T10 handle is refused); d_vel / vel
+ * have 3 * n_coef entries; point stresses are E * Q * 6 over the force-quadrature points (Q = 12 | 48, tlfea_elem_dims);
+ * element values are means weighted by the reference volume (weights x det J of the element's L, W, H); "nodal" means per
+ * MESH node (n_nodes = n_coef / 4), the V_e-weighted mean of the incident elements' means in ascending element order, von
+ * Mises of that tensor; the kinetic energy 1/2 v.Mv runs over all coefficient DOFs (needs CalcMassMatrix).  Callable any
+ * time after CalcDsDuPre; changes nothing a solver reads; every output is bitwise reproducible. */
+int tlfea_ancf_calc_stress(tlfea_t10_t h, const double *d_vel /* device, 3*n_coef, or NULL */, int want_points);
+int tlfea_ancf_calc_stress_host(tlfea_t10_t h, const double *vel /* host, 3*n_coef, or NULL */, int want_points);
+int tlfea_ancf_retrieve_point_stress(tlfea_t10_t h, double *sigma /*E*Q*6*/);
+int tlfea_ancf_retrieve_element_stress(tlfea_t10_t h, double *sigma /*E*6*/, double *von_mises /*E*/, double *psi /*E*/,
+                                       double *J /*E*/, double *vol /*E*/); /* any may be NULL */
+int tlfea_ancf_retrieve_nodal_stress(tlfea_t10_t h, double *sigma /*n_nodes*6*/, double *von_mises /*n_nodes*/); /* either may be NULL */
+int tlfea_ancf_get_energies(tlfea_t10_t h, double out[5]);
+double *tlfea_ancf_nodal_stress_device_ptr(tlfea_t10_t h); /* n_nodes*7: sigma, von Mises per mesh node; NULL before calc_stress */
+/* mean ms over reps launches of: the point and element kernel, the mesh-node gather, the totals (profiling hook) */
+int tlfea_ancf_time_stress_kernels(tlfea_t10_t h, const double *d_vel, int want_points, int reps, double *out_ms3);
+
 /* ---- SyncedNewtonSolver --------------------------------------------------------------------- */
 int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_newton_t *out); /* SyncedNewton.cuh:37-149 */
 int tlfea_newton_destroy(tlfea_newton_t s);                                        /* dtor :151-204 */

@@ -94,8 +94,12 @@ def _stress_signatures(lib):
     for name, args in sig.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
-    lib.tlfea_t10_nodal_stress_device_ptr.argtypes = [vp]
-    lib.tlfea_t10_nodal_stress_device_ptr.restype = vp
+    for name, args in sig.items():  # the ANCF entry points (DESIGN 3f') take the same arguments
+        getattr(lib, name.replace("tlfea_t10_", "tlfea_ancf_")).argtypes = args
+        getattr(lib, name.replace("tlfea_t10_", "tlfea_ancf_")).restype = C.c_int
+    for name in ("tlfea_t10_nodal_stress_device_ptr", "tlfea_ancf_nodal_stress_device_ptr"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = vp
 
 
 def _material_signatures(lib):

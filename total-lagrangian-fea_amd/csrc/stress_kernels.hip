@@ -11,6 +11,14 @@
 //   stress_partial_kernel / stress_final_kernel
 //                         fixed-order two-stage sums of the element integrals and of the rows of 1/2 v.Mv
 //                         (obstacle_resultant_kernel's scheme): strided per-thread sums in index order, then a fixed tree
+//   ancf_stress_point_kernel
+//                         the ANCF kinds (DESIGN 3f'): lanes own quadrature points.  A wavefront takes G elements of Q
+//                         lanes each (shell <16,48>: 1 x 48, beam <8,12>: 5 x 12); the elements' coefficient vectors sit in
+//                         the wavefront's LDS slice, every lane streams its own contiguous 3 x S gradient run into F (and
+//                         Fdot) and forms P, sigma, psi and P_vis:Fdot of its point; the element sums are a fixed halving
+//                         tree over the element's lanes (Q = 3 * 2^k: Q/2, Q/4, ..., 3, then lanes 0 + 1 + 2)
+//   stress_node_gather_kernel
+//                         thread per mesh node over a node -> element list (ascending elements): the ANCF nodal stress
 // No atomics: every launch is bitwise reproducible.
 #include <type_traits>
 
@@ -218,6 +226,192 @@ __global__ __launch_bounds__(128) void stress_point_kernel(ElemView m, MT mat_in
   }
 }
 
+// ---- ANCF beams and shells: lanes own quadrature points ---------------------------------------------------------------------
+// sum of `val` over the Q lanes of an element, valid in the element's lane 0 (p = lane within the element).  Every lane
+// of the wavefront takes part in every shuffle; the shape depends on Q alone, so a launch is bitwise reproducible.
+template <int Q>
+__device__ __forceinline__ double elem_lane_sum(double val, int lane, int p) {
+  static_assert(Q % 3 == 0 && ((Q / 3) & (Q / 3 - 1)) == 0, "Q = 3 * 2^k");
+#pragma unroll
+  for (int off = Q / 2; off >= 3; off >>= 1) {
+    const double t = __shfl(val, (lane + off) & 63);
+    if (p < off) val += t;
+  }
+  const double t1 = __shfl(val, (lane + 1) & 63), t2 = __shfl(val, (lane + 2) & 63);
+  return (val + t1) + t2;
+}
+
+constexpr int kAncfWaves = 4;  // wavefronts of a block; each works on its own elements through its own LDS slice
+constexpr int kAncfPtRow = 7;  // LDS doubles per lane behind its 6 point-stress doubles (odd: no bank pile-up)
+
+// pts [E][Q][6], erec [E][10], contrib [4][Epad] as stress_point_kernel.  gradN [E][Q][3][S]: lane (g, q) reads the run of (e0 + g, q).
+template <int S, int Q, bool POINTS>
+__global__ __launch_bounds__(64 * kAncfWaves) void ancf_stress_point_kernel(ElemView m, Material mat,
+                                                                           const double* __restrict__ v,
+                                                                           double* __restrict__ pts,
+                                                                           double* __restrict__ erec,
+                                                                           double* __restrict__ contrib) {
+  constexpr int G = 64 / Q;            // elements of a wavefront
+  constexpr int kRow = 3 * S + 1;      // LDS doubles of an element's coefficient vectors (+1: the G rows start on different banks)
+  __shared__ double xs_all[kAncfWaves][G * kRow], vs_all[kAncfWaves][G * kRow];
+  __shared__ double tr_all[kAncfWaves][POINTS ? 64 * kAncfPtRow : G * 10];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int e0 = (blockIdx.x * kAncfWaves + w) * G;  // first element of this wavefront
+  if (e0 >= m.E) return;                             // the whole wavefront: nothing below synchronises across wavefronts
+  double *xs = xs_all[w], *vs = vs_all[w], *tr = tr_all[w];
+  const int n_el = min(G, m.E - e0);                 // elements of this wavefront
+  const bool damp = (v != nullptr) && (mat.eta != 0.0 || mat.lamd != 0.0);  // residual_kernel's condition
+  // the elements' coefficient vectors (and velocities), once per element
+  for (int idx = lane; idx < n_el * S; idx += 64) {
+    const int el = idx / S, a = idx - el * S;
+    const int c = m.conn[(size_t)a * m.E + e0 + el];
+    double* xo = xs + el * kRow + 3 * a;
+    xo[0] = m.x[c];
+    xo[1] = m.y[c];
+    xo[2] = m.z[c];
+    if (damp) {
+      double* vo = vs + el * kRow + 3 * a;
+      vo[0] = v[3 * c];
+      vo[1] = v[3 * c + 1];
+      vo[2] = v[3 * c + 2];
+    }
+  }
+  wave_sync();
+  const int g_raw = lane / Q, p = lane - g_raw * Q;
+  const bool active = g_raw < n_el;       // lanes past the wavefront's elements recompute element e0 and contribute zeros
+  const int g = active ? g_raw : 0, e = e0 + g;
+  const double2* gr = reinterpret_cast<const double2*>(m.gradN + ((size_t)e * Q + p) * (3 * S));  // 3 S doubles: 16-byte aligned
+  const double* xe = xs + g * kRow;
+  const double* ve = vs + g * kRow;
+  double F[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Fd[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+  for (int d = 0; d < 3; d++)
+#pragma unroll
+    for (int a = 0; a < S; a += 2) {
+      const double2 h = gr[(d * S + a) >> 1];
+#pragma unroll
+      for (int i = 0; i < 3; i++) F[i][d] += xe[3 * a + i] * h.x + xe[3 * a + 3 + i] * h.y;
+      if (damp) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) Fd[i][d] += ve[3 * a + i] * h.x + ve[3 * a + 3 + i] * h.y;
+      }
+    }
+  double P[3][3];
+  elastic_P(F, mat, P);
+  double pvis = 0.0;
+  if (damp) {
+    // Edot = sym(Fdot^T F) ; S = 2 eta Edot + lamd tr(Edot) I ; P_vis = F S (residual_kernel)
+    double Ed[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double a1 = 0.0, a2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          a1 += Fd[k][i] * F[k][j];
+          a2 += F[k][i] * Fd[k][j];
+        }
+        Ed[i][j] = 0.5 * (a1 + a2);
+      }
+    const double trEd = Ed[0][0] + Ed[1][1] + Ed[2][2];
+    double Sv[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) Sv[i][j] = 2.0 * mat.eta * Ed[i][j] + (i == j ? mat.lamd * trEd : 0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) s += F[i][k] * Sv[k][j];
+        P[i][j] += s;
+        pvis += s * Fd[i][j];
+      }
+  }
+  const double J = det3(F);
+  const double iJ = 1.0 / J;
+  const int si[6] = {0, 1, 2, 0, 1, 2}, sj[6] = {0, 1, 2, 1, 2, 0};  // sigma = P F^T / J, stored xx yy zz xy yz zx
+  double sig[6];
+#pragma unroll
+  for (int c = 0; c < 6; c++)
+    sig[c] = (P[si[c]][0] * F[sj[c]][0] + P[si[c]][1] * F[sj[c]][1] + P[si[c]][2] * F[sj[c]][2]) * iJ;
+  const double psi = elastic_psi(F, mat);
+  const double dV = active ? m.detJ[(size_t)e * Q + p] * m.qw[p] : 0.0;
+  if (POINTS) {
+    // the wavefront's n_el x Q x 6 point-stress doubles are contiguous (lane = g Q + q): whole-line stores
+#pragma unroll
+    for (int c = 0; c < 6; c++) tr[lane * kAncfPtRow + c] = sig[c];
+    wave_sync();
+    double* out = pts + (size_t)e0 * Q * 6;
+    const int n_out = n_el * Q * 6;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      const int idx = lane + 64 * j, l = idx / 6, c = idx - 6 * l;
+      if (idx < n_out) out[idx] = tr[l * kAncfPtRow + c];
+    }
+    wave_sync();
+  }
+  double rec[10];
+#pragma unroll
+  for (int c = 0; c < 6; c++) rec[c] = elem_lane_sum<Q>(sig[c] * dV, lane, p);
+  const double W = elem_lane_sum<Q>(psi * dV, lane, p);
+  const double D = elem_lane_sum<Q>(pvis * dV, lane, p);
+  const double V = elem_lane_sum<Q>(dV, lane, p);
+  const double Vc = elem_lane_sum<Q>(J * dV, lane, p);
+  if (active && p == 0) {
+    const double iV = 1.0 / V;
+#pragma unroll
+    for (int c = 0; c < 6; c++) rec[c] *= iV;
+    rec[6] = von_mises6(rec);
+    rec[7] = W * iV;
+    rec[8] = Vc * iV;
+    rec[9] = V;
+#pragma unroll
+    for (int c = 0; c < 10; c++) tr[g * 10 + c] = rec[c];
+    contrib[(size_t)0 * m.Epad + e] = W;
+    contrib[(size_t)1 * m.Epad + e] = D;
+    contrib[(size_t)2 * m.Epad + e] = V;
+    contrib[(size_t)3 * m.Epad + e] = Vc;
+  }
+  wave_sync();
+  if (lane < n_el * 10) erec[(size_t)e0 * 10 + lane] = tr[lane];  // the wavefront's records are contiguous
+}
+
+// nodal [n_nodes][7] of the ANCF kinds: node -> element list (off [n_nodes + 1], el ascending per node) instead of the
+// coefficient-level Incidence; otherwise stress_nodal_kernel
+__global__ __launch_bounds__(kRed) void stress_node_gather_kernel(int n_nodes, const int* __restrict__ off,
+                                                                 const int* __restrict__ el,
+                                                                 const double* __restrict__ erec,
+                                                                 double* __restrict__ nodal) {
+  __shared__ double st[kRed * 7];
+  const int t = threadIdx.x;
+  const int i0 = blockIdx.x * kRed, i = i0 + t;
+  double a[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, w = 0.0;
+  if (i < n_nodes) {
+    for (int k = off[i]; k < off[i + 1]; k++) {
+      const double* r = erec + (size_t)el[k] * 10;
+      const double Ve = r[9];
+#pragma unroll
+      for (int c = 0; c < 6; c++) a[c] += Ve * r[c];
+      w += Ve;
+    }
+    if (w > 0.0) {  // a node of no element keeps zeros
+      const double iw = 1.0 / w;
+#pragma unroll
+      for (int c = 0; c < 6; c++) a[c] *= iw;
+    }
+    a[6] = von_mises6(a);
+  }
+#pragma unroll
+  for (int c = 0; c < 7; c++) st[t * 7 + c] = a[c];
+  __syncthreads();
+  const int n_here = min(kRed, n_nodes - i0) * 7;
+  for (int k = t; k < n_here; k += kRed) nodal[(size_t)i0 * 7 + k] = st[k];
+}
+
 // nodal [N][7] = sigma_i (6) | von Mises of sigma_i; a block's 256 x 7 doubles are contiguous and leave through LDS
 __global__ __launch_bounds__(kRed) void stress_nodal_kernel(int N, Incidence inc, const double* __restrict__ erec,
                                                            double* __restrict__ nodal) {
@@ -330,6 +524,27 @@ void launch_stress_points(hipStream_t s, const ElemView& m, const Material& mat,
                           double* pts, double* erec, double* contrib) {
   if (emat) launch_points_t(s, m, MaterialPE{mat, emat}, v, pts, erec, contrib);
   else launch_points_t(s, m, mat, v, pts, erec, contrib);
+}
+
+template <int S, int Q>
+static void launch_ancf_points_t(hipStream_t s, const ElemView& m, const Material& mat, const double* v, double* pts,
+                                 double* erec, double* contrib) {
+  const int per_block = kAncfWaves * (64 / Q);
+  const dim3 grid((m.E + per_block - 1) / per_block), block(64 * kAncfWaves);
+  if (pts) hipLaunchKernelGGL((ancf_stress_point_kernel<S, Q, true>), grid, block, 0, s, m, mat, v, pts, erec, contrib);
+  else hipLaunchKernelGGL((ancf_stress_point_kernel<S, Q, false>), grid, block, 0, s, m, mat, v, pts, erec, contrib);
+}
+
+void launch_ancf_stress_points(hipStream_t s, const ElemView& m, const Material& mat, const double* v, double* pts,
+                               double* erec, double* contrib) {
+  if (m.S == 8) launch_ancf_points_t<8, 12>(s, m, mat, v, pts, erec, contrib);
+  else launch_ancf_points_t<16, 48>(s, m, mat, v, pts, erec, contrib);
+}
+
+void launch_stress_node_gather(hipStream_t s, int n_nodes, const int* off, const int* el, const double* erec,
+                               double* nodal) {
+  hipLaunchKernelGGL(stress_node_gather_kernel, dim3((n_nodes + kRed - 1) / kRed), dim3(kRed), 0, s, n_nodes, off, el, erec,
+                     nodal);
 }
 
 void launch_stress_nodal(hipStream_t s, int N, const Incidence& inc, const double* erec, double* nodal) {

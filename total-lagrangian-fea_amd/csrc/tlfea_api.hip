@@ -104,6 +104,8 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
          *d_st_part = nullptr, *d_st_tot = nullptr, *d_st_vel = nullptr;
   double st_tot[5] = {0, 0, 0, 0, 0};
   bool st_valid = false, st_pts_valid = false;  // a calc_stress has run | its point stresses were asked for
+  int *d_st_noff = nullptr, *d_st_nel = nullptr;  // ANCF (DESIGN 3f'): elements of every MESH node, ascending (n_nodes + 1 | E nn)
+  bool ancf_mass = false;                         // ANCF: d_mval holds an assembled mass matrix (the kinetic energy's condition)
   // constraints
   double* d_cons = nullptr;
   int *d_fixed = nullptr, *d_fixed_slot = nullptr;
@@ -214,7 +216,7 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_n2e_pos, h->d_diagpos, h->d_mval, h->d_joff, h->d_jcol, h->d_jtoff, h->d_jtcol, h->d_jval,
                   h->d_jtval, h->d_rhs, h->d_emat, h->d_ob_node, h->d_ob_w, h->d_ob_f, h->d_ob_blk, h->d_ob_fk,
                   h->d_ob_res, h->d_st_pts, h->d_st_erec, h->d_st_contrib, h->d_st_nodal, h->d_st_part, h->d_st_tot,
-                  h->d_st_vel};
+                  h->d_st_vel, h->d_st_noff, h->d_st_nel};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -943,6 +945,7 @@ static int ancf_mass_host(tlfea_t10_t h) {
     }
   }
   HIP_TRY(hipMemcpy(h->d_mval, mval.data(), mval.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->ancf_mass = true;
   return 0;
 }
 
@@ -1175,6 +1178,137 @@ extern "C" int tlfea_t10_time_stress_kernels(tlfea_t10_t h, const double* d_vel,
         launch_stress_totals(h->stream, h->E, h->Epad, h->d_st_contrib, h->N, h->inc(), h->d_mval, d_vel, h->d_st_part,
                              h->d_st_tot);
     }
+    HIP_TRY(hipEventRecord(ev[1], h->stream));
+    HIP_TRY(hipEventSynchronize(ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    out_ms3[k] = ms / reps;
+  }
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
+  h->st_valid = true;
+  h->st_pts_valid = want_points != 0;
+  return 0;
+}
+// ---- stress and energy recovery of the ANCF kinds (DESIGN 3f') ----------------------------------------------------------
+// Own entry points: the tlfea_t10_* ones above keep refusing ANCF handles.  The buffers are the d_st_* of the handle.
+#define NEED_ANCF(h, what) \
+  if ((h) && (h)->kind == kT10) return fail(std::string(what) + ": ANCF handles only (not a T10 handle)")
+static int ancf_stress_prepare(tlfea_t10_t h, const double* d_vel, int want_points) {
+  NEED_ANCF(h, "tlfea_ancf_calc_stress");
+  NEED_SETUP(h, "CalcElementStress.");
+  if (!h->have_dndu) return fail("tlfea_ancf_calc_stress: CalcDsDuPre must be called first");
+  if (d_vel && !h->ancf_mass)
+    return fail("tlfea_ancf_calc_stress: a velocity was given but the mass matrix is not assembled (the kinetic energy "
+                "needs CalcMassMatrix)");
+  if (!h->d_st_erec) {
+    // elements of every mesh node in ascending order: node = coefficient / 4, slot 0 of local node k is row 4 k of conn
+    const int E = h->E, nn = h->nn, n_nodes = h->n_nodes;
+    std::vector<int> off(n_nodes + 1, 0), el((size_t)E * nn);
+    for (int k = 0; k < nn; k++)
+      for (int e = 0; e < E; e++) off[h->h_conn[(size_t)(4 * k) * E + e] / 4 + 1]++;
+    for (int i = 0; i < n_nodes; i++) off[i + 1] += off[i];
+    std::vector<int> cur(off.begin(), off.end() - 1);
+    for (int e = 0; e < E; e++)
+      for (int k = 0; k < nn; k++) el[cur[h->h_conn[(size_t)(4 * k) * E + e] / 4]++] = e;
+    TRY(dmalloc(&h->d_st_noff, off.size()));
+    TRY(dmalloc(&h->d_st_nel, el.size()));
+    HIP_TRY(hipMemcpy(h->d_st_noff, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_st_nel, el.data(), el.size() * sizeof(int), hipMemcpyHostToDevice));
+    TRY(dmalloc(&h->d_st_contrib, (size_t)h->Epad * 4));
+    TRY(dmalloc(&h->d_st_nodal, (size_t)n_nodes * 7));
+    TRY(dmalloc(&h->d_st_part, (size_t)kStressMaxPart * 5));
+    TRY(dmalloc(&h->d_st_tot, (size_t)5));
+    TRY(dmalloc(&h->d_st_erec, (size_t)E * 10));
+  }
+  if (want_points && !h->d_st_pts) TRY(dmalloc(&h->d_st_pts, (size_t)h->E * h->Q * 6));
+  return 0;
+}
+static void ancf_stress_launch(tlfea_t10_t h, const double* d_vel, int want_points, int stage) {
+  if (stage == 0)
+    launch_ancf_stress_points(h->stream, h->view(), h->mat, d_vel, want_points ? h->d_st_pts : nullptr, h->d_st_erec,
+                              h->d_st_contrib);
+  else if (stage == 1)
+    launch_stress_node_gather(h->stream, h->n_nodes, h->d_st_noff, h->d_st_nel, h->d_st_erec, h->d_st_nodal);
+  else  // the kinetic energy runs over the n_coef rows of the mass matrix
+    launch_stress_totals(h->stream, h->E, h->Epad, h->d_st_contrib, h->N, h->inc(), h->d_mval, d_vel, h->d_st_part,
+                         h->d_st_tot);
+}
+extern "C" int tlfea_ancf_calc_stress(tlfea_t10_t h, const double* d_vel, int want_points) {
+  TRY(ancf_stress_prepare(h, d_vel, want_points));
+  h->st_valid = h->st_pts_valid = false;
+  for (int stage = 0; stage < 3; stage++) ancf_stress_launch(h, d_vel, want_points, stage);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
+  h->st_valid = true;
+  h->st_pts_valid = want_points != 0;
+  return 0;
+}
+extern "C" int tlfea_ancf_calc_stress_host(tlfea_t10_t h, const double* vel, int want_points) {
+  if (!vel) return tlfea_ancf_calc_stress(h, nullptr, want_points);
+  NEED_ANCF(h, "tlfea_ancf_calc_stress");
+  NEED_SETUP(h, "CalcElementStress.");
+  if (!h->d_st_vel) TRY(dmalloc(&h->d_st_vel, (size_t)3 * h->N));
+  HIP_TRY(hipMemcpy(h->d_st_vel, vel, (size_t)3 * h->N * sizeof(double), hipMemcpyHostToDevice));
+  return tlfea_ancf_calc_stress(h, h->d_st_vel, want_points);
+}
+#define NEED_ANCF_STRESS(h, what) \
+  NEED_ANCF(h, what);             \
+  if (!(h) || !(h)->st_valid) return fail(std::string(what) + ": tlfea_ancf_calc_stress has not been called")
+extern "C" int tlfea_ancf_retrieve_point_stress(tlfea_t10_t h, double* sigma) {
+  NEED_ANCF_STRESS(h, "tlfea_ancf_retrieve_point_stress");
+  if (!h->st_pts_valid)
+    return fail("tlfea_ancf_retrieve_point_stress: the last tlfea_ancf_calc_stress did not ask for point stresses (want_points = 0)");
+  if (!sigma) return fail("tlfea_ancf_retrieve_point_stress: null output");
+  D2H(sigma, h->d_st_pts, (size_t)h->E * h->Q * 6);
+  return 0;
+}
+extern "C" int tlfea_ancf_retrieve_element_stress(tlfea_t10_t h, double* sigma, double* von_mises, double* psi, double* J,
+                                                  double* vol) {
+  NEED_ANCF_STRESS(h, "tlfea_ancf_retrieve_element_stress");
+  std::vector<double> rec((size_t)h->E * 10);
+  D2H(rec.data(), h->d_st_erec, rec.size());
+  for (int e = 0; e < h->E; e++) {
+    const double* r = &rec[(size_t)e * 10];
+    if (sigma) std::copy_n(r, 6, sigma + (size_t)e * 6);
+    if (von_mises) von_mises[e] = r[6];
+    if (psi) psi[e] = r[7];
+    if (J) J[e] = r[8];
+    if (vol) vol[e] = r[9];
+  }
+  return 0;
+}
+extern "C" int tlfea_ancf_retrieve_nodal_stress(tlfea_t10_t h, double* sigma, double* von_mises) {
+  NEED_ANCF_STRESS(h, "tlfea_ancf_retrieve_nodal_stress");
+  std::vector<double> rec((size_t)h->n_nodes * 7);
+  D2H(rec.data(), h->d_st_nodal, rec.size());
+  for (int i = 0; i < h->n_nodes; i++) {
+    if (sigma) std::copy_n(&rec[(size_t)i * 7], 6, sigma + (size_t)i * 6);
+    if (von_mises) von_mises[i] = rec[(size_t)i * 7 + 6];
+  }
+  return 0;
+}
+extern "C" int tlfea_ancf_get_energies(tlfea_t10_t h, double out[5]) {
+  NEED_ANCF_STRESS(h, "tlfea_ancf_get_energies");
+  if (!out) return fail("tlfea_ancf_get_energies: null output");
+  std::copy_n(h->st_tot, 5, out);
+  return 0;
+}
+extern "C" double* tlfea_ancf_nodal_stress_device_ptr(tlfea_t10_t h) {
+  return h && h->kind != kT10 && h->st_valid ? h->d_st_nodal : nullptr;
+}
+// as tlfea_t10_time_stress_kernels: [0] the point kernel, [1] the mesh-node gather, [2] the two totals launches
+extern "C" int tlfea_ancf_time_stress_kernels(tlfea_t10_t h, const double* d_vel, int want_points, int reps, double* out_ms3) {
+  TRY(ancf_stress_prepare(h, d_vel, want_points));
+  if (!out_ms3) return fail("tlfea_ancf_time_stress_kernels: null output");
+  if (reps < 1) reps = 1;
+  hipEvent_t ev[2];
+  HIP_TRY(hipEventCreate(&ev[0]));
+  HIP_TRY(hipEventCreate(&ev[1]));
+  for (int k = 0; k < 3; k++) {
+    HIP_TRY(hipEventRecord(ev[0], h->stream));
+    for (int r = 0; r < reps; r++) ancf_stress_launch(h, d_vel, want_points, k);
     HIP_TRY(hipEventRecord(ev[1], h->stream));
     HIP_TRY(hipEventSynchronize(ev[1]));
     float ms = 0.f;

@@ -387,6 +387,12 @@ void launch_stress_points(hipStream_t s, const ElemView& m, const Material& mat,
                           double* pts, double* erec, double* contrib);
 // nodal [N][7]: V_e-weighted mean of the incident elements' mean stresses (ascending element order) | its von Mises
 void launch_stress_nodal(hipStream_t s, int N, const Incidence& inc, const double* erec, double* nodal);
+// The same for the ANCF kinds (tlfea_ancf_calc_stress, DESIGN 3f'): lanes own quadrature points, pts [E][Q][6]; one material
+void launch_ancf_stress_points(hipStream_t s, const ElemView& m, const Material& mat, const double* v, double* pts,
+                               double* erec, double* contrib);
+// nodal [n_nodes][7] over MESH nodes: off [n_nodes + 1] / el = the elements of every node, ascending
+void launch_stress_node_gather(hipStream_t s, int n_nodes, const int* off, const int* el, const double* erec,
+                               double* nodal);
 // out5 = {strain energy, 1/2 v.Mv (0 without v), viscous power, reference volume, current volume}: fixed-order partial
 // sums (partial: kStressMaxPart x 5 doubles), then one block with a fixed tree
 constexpr int kStressMaxPart = 1024;

@@ -436,6 +436,58 @@ class _GPU_ANCF_Data(GPU_FEAT10_Data):
     def get_n_beam(self):
         return self.n_elem
 
+    # -- stress and energy recovery (DESIGN 3f'); CalcStress / Retrieve*StressToCPU stay T10-only and keep refusing -------
+    def _ancf_stress_velocity(self, vel):
+        if vel is not None and not hasattr(vel, "GetVelocityGuessDevicePtr") and np.size(vel) != 3 * self.n_coef:
+            raise ValueError(f"CalcElementStress: the velocity needs {3 * self.n_coef} entries, got {np.size(vel)}")
+        return self._stress_velocity(vel)
+
+    def CalcElementStress(self, vel=None, want_points=False):
+        """Cauchy stress, strain-energy density and energies at the current coefficients.  `vel`: None, a solver (its
+        device velocity is used) or a host array of 3 n_coef; it adds a damped material's viscous stress and gives the
+        kinetic energy and the viscous power.  `want_points` also keeps the stresses of the Q force-quadrature points."""
+        ptr, host = self._ancf_stress_velocity(vel)
+        if host is not None:
+            check(self._lib.tlfea_ancf_calc_stress_host(self._h, dp(host), int(bool(want_points))))
+        else:
+            check(self._lib.tlfea_ancf_calc_stress(self._h, C.c_void_p(ptr), int(bool(want_points))))
+
+    def RetrieveANCFPointStressToCPU(self):
+        """[E][Q][6]: xx yy zz xy yz zx per force-quadrature point (CalcElementStress(want_points=True))."""
+        s = np.zeros((self.n_elem, self.Q, 6))
+        check(self._lib.tlfea_ancf_retrieve_point_stress(self._h, dp(s)))
+        return s
+
+    def RetrieveANCFElementStressToCPU(self):
+        """Reference-volume-weighted element means: sigma [E][6], von Mises of it, psi, J, and the element volume."""
+        E = self.n_elem
+        s, vm, psi, J, vol = np.zeros((E, 6)), np.zeros(E), np.zeros(E), np.zeros(E), np.zeros(E)
+        check(self._lib.tlfea_ancf_retrieve_element_stress(self._h, dp(s), dp(vm), dp(psi), dp(J), dp(vol)))
+        return ElementStress(s, vm, psi, J, vol)
+
+    def RetrieveANCFNodalStressToCPU(self):
+        """Element-volume-weighted stress of every MESH node [n_nodes][6] and the von Mises stress of that tensor."""
+        s, vm = np.zeros((self.n_nodes, 6)), np.zeros(self.n_nodes)
+        check(self._lib.tlfea_ancf_retrieve_nodal_stress(self._h, dp(s), dp(vm)))
+        return NodalStress(s, vm)
+
+    def GetANCFEnergies(self):
+        out = np.zeros(5)
+        check(self._lib.tlfea_ancf_get_energies(self._h, dp(out)))
+        return Energies(*out.tolist())
+
+    def GetANCFNodalStressDevicePtr(self):
+        return self._lib.tlfea_ancf_nodal_stress_device_ptr(self._h)
+
+    def TimeANCFStressKernels(self, vel=None, want_points=False, reps=20):
+        """-> mean ms of (point and element kernel, mesh-node gather, totals) over `reps` back-to-back launches each."""
+        ptr, host = self._ancf_stress_velocity(vel)
+        if host is not None:
+            raise ValueError("TimeANCFStressKernels: pass a solver or None")
+        out = np.zeros(3)
+        check(self._lib.tlfea_ancf_time_stress_kernels(self._h, C.c_void_p(ptr), int(bool(want_points)), int(reps), dp(out)))
+        return out
+
 
 class GPU_ANCF3243_Data(_GPU_ANCF_Data):
     TYPE, KIND, NN, S, Q = "TYPE_3243", 3243, 2, 8, 12

@@ -6,6 +6,9 @@
 // Same constants (:36-46), options (--mesh --steps --dt --vtu --apply_load_below_z --load_below_z --load_fz
 // --contact_fz_max) and solver parameters ({1e-4,0,1e-6,1e12,10,10,dt}, :329); thickness scaled by 0.25 (:243).
 // --csv_path=FILE additionally records, per step, the hub angle and the lowest ring position (for the tests).
+// --stress (off by default; nothing changes without it): stress recovery after every step -- the VTU frames carry the
+// nodal "stress" and "von_mises", and <vtu dir>/stress.csv (or --stress_csv=FILE) one line per step with the strain energy,
+// the kinetic energy, the viscous power and the largest nodal von Mises stress.
 #include <algorithm>
 #include <cmath>
 #include <filesystem>
@@ -22,10 +25,10 @@ constexpr double kThicknessScale = 0.25;
 constexpr double kOmegaTarget = 1.5 * 3.14159265358979323846, kOmegaRampTime = 0.05;
 
 struct Options {
-  std::string mesh, csv_path, vtu_dir = "output/ancf3443_mesh";
+  std::string mesh, csv_path, stress_csv, vtu_dir = "output/ancf3443_mesh";
   int steps = 10;
   double dt = 1e-3, ground_z = -0.2, contact_k = 5e4, contact_fz_max = 2e4;
-  bool write_vtu = false, contact = true;
+  bool write_vtu = false, contact = true, stress = false;
 };
 
 bool starts_with(const std::string& s, const std::string& p) { return s.rfind(p, 0) == 0; }
@@ -46,6 +49,8 @@ bool parse_args(int argc, char** argv, Options& o) {
       else if (starts_with(a, "--load_fz=")) o.contact_k = std::stod(val("--load_fz="));
       else if (starts_with(a, "--contact_fz_max=")) o.contact_fz_max = std::stod(val("--contact_fz_max="));
       else if (starts_with(a, "--csv_path=")) o.csv_path = val("--csv_path=");
+      else if (a == "--stress") o.stress = true;
+      else if (starts_with(a, "--stress_csv=")) { o.stress = true; o.stress_csv = val("--stress_csv="); }
       else if (starts_with(a, "--load_per_node=") || starts_with(a, "--load_fx=") || starts_with(a, "--load_fy=")) {
       }  // legacy options of the reference: accepted and ignored there too (:182-186)
       else {
@@ -183,9 +188,42 @@ int main(int argc, char** argv) {
     if (!opt.write_vtu || step % kVtuEvery != 0) return;
     std::ostringstream name;
     name << opt.vtu_dir << "/ancf3443_mesh_" << std::setw(6) << std::setfill('0') << step << ".vtu";
+    if (opt.stress) {  // of the last CalcElementStress
+      tlfea::MatrixXd sigma;
+      tlfea::VectorXd vm;
+      data.RetrieveANCFNodalStressToCPU(sigma, vm);
+      ANCFCPUUtils::VisualizationUtils::ExportANCFMeshWithStress(x, y, z, mesh.element_connectivity, 0.0, thickness, sigma, vm,
+                                                                 name.str());
+      return;
+    }
     ANCFCPUUtils::VisualizationUtils::ExportANCF3443ToVTU(x, y, z, mesh.element_connectivity, thickness, name.str());
   };
   if (opt.write_vtu) std::filesystem::create_directories(opt.vtu_dir);
+  std::ofstream stress_csv;
+  // stress recovery at the current state (velocity: the solver's, null before the first step) and its CSV line
+  auto recover_stress = [&](int step, const double* d_velocity) {
+    if (!opt.stress) return;
+    if (data.CalcElementStress(d_velocity) != 0) {
+      std::cerr << tlfea_last_error() << std::endl;
+      std::exit(1);
+    }
+    if (step < 0) return;
+    tlfea::MatrixXd sigma;
+    tlfea::VectorXd vm;
+    data.RetrieveANCFNodalStressToCPU(sigma, vm);
+    double vm_max = 0.0;
+    for (int i = 0; i < vm.size(); i++) vm_max = std::max(vm_max, vm(i));
+    const auto en = data.GetANCFEnergies();
+    stress_csv << step << "," << en.strain << "," << en.kinetic << "," << en.viscous_power << "," << vm_max << "\n";
+  };
+  if (opt.stress) {
+    if (opt.stress_csv.empty()) {
+      std::filesystem::create_directories(opt.vtu_dir);
+      opt.stress_csv = opt.vtu_dir + "/stress.csv";
+    }
+    stress_csv.open(opt.stress_csv);
+    stress_csv << std::setprecision(17) << "step,strain_energy,kinetic_energy,viscous_power,von_mises_max\n";
+  }
 
   SyncedNewtonParams params = {1e-4, 0.0, 1e-6, 1e12, 10, 10, opt.dt};
   SyncedNewtonSolver solver(&data, data.get_n_constraint());
@@ -199,6 +237,7 @@ int main(int argc, char** argv) {
   }
   tlfea::VectorXd x12, y12, z12;
   data.RetrievePositionToCPU(x12, y12, z12);
+  recover_stress(-1, nullptr);
   write_vtu(0, x12, y12, z12);
   tlfea::VectorXd rhs = all.rhs;
   double theta = 0.0;
@@ -223,6 +262,7 @@ int main(int argc, char** argv) {
     }
     solver.Solve();
     data.RetrievePositionToCPU(x12, y12, z12);
+    recover_stress(step, solver.GetVelocityGuessDevicePtr());
     write_vtu(step + 1, x12, y12, z12);
     if (csv.is_open()) {
       double ring_min = std::numeric_limits<double>::infinity();

@@ -953,6 +953,60 @@ struct GPU_ANCF_DataBase : public GPU_FEAT10_Data {
     if (tlfea_t10_update_linear_constraint_rhs(h, rhs.data(), rhs.size()) != 0) std::cerr << tlfea_last_error() << std::endl;
   }
   int GetConstraintMode() const { return tlfea_t10_get_constraint_mode(h); }
+  // stress and energy recovery of the ANCF kinds (DESIGN 3f'; no reference counterpart): the members of GPU_FEAT10_Data's
+  // CalcStress family under their own names (those keep refusing an ANCF object).  d_velocity: a solver's
+  // GetVelocityGuessDevicePtr() or null; "nodal" = per MESH node.  Status 0 = done (tlfea_last_error() explains a refusal).
+  int CalcElementStress(const double* d_velocity = nullptr, bool want_points = false) {
+    return tlfea_ancf_calc_stress(h, d_velocity, want_points ? 1 : 0);
+  }
+  int CalcElementStressFromHost(const tlfea::VectorXd& velocity, bool want_points = false) {
+    if (velocity.size() != 3 * n_coef) {
+      std::cerr << "CalcElementStressFromHost: the velocity needs " << 3 * n_coef << " entries, got " << velocity.size() << std::endl;
+      return 1;
+    }
+    return tlfea_ancf_calc_stress_host(h, velocity.data(), want_points ? 1 : 0);
+  }
+  // sigma[e][q]: 6 x 1 (xx yy zz xy yz zx) per force-quadrature point
+  void RetrieveANCFPointStressToCPU(std::vector<std::vector<tlfea::VectorXd>>& sigma) {
+    int S = 0, Q = 0;
+    TLFEA_HANDLE_ERROR(tlfea_elem_dims(h, &S, &Q));
+    std::vector<double> flat(static_cast<size_t>(n_elem) * Q * 6);
+    TLFEA_HANDLE_ERROR(tlfea_ancf_retrieve_point_stress(h, flat.data()));
+    sigma.assign(n_elem, std::vector<tlfea::VectorXd>(Q, tlfea::VectorXd(6)));
+    for (int e = 0; e < n_elem; e++)
+      for (int q = 0; q < Q; q++) std::copy_n(flat.data() + (static_cast<size_t>(e) * Q + q) * 6, 6, sigma[e][q].data());
+  }
+  void RetrieveANCFElementStressToCPU(tlfea::MatrixXd& sigma, tlfea::VectorXd& von_mises, tlfea::VectorXd& psi,
+                                      tlfea::VectorXd& J, tlfea::VectorXd& volume) {
+    std::vector<double> flat(static_cast<size_t>(n_elem) * 6);
+    von_mises.resize(n_elem);
+    psi.resize(n_elem);
+    J.resize(n_elem);
+    volume.resize(n_elem);
+    TLFEA_HANDLE_ERROR(tlfea_ancf_retrieve_element_stress(h, flat.data(), von_mises.data(), psi.data(), J.data(), volume.data()));
+    sigma.resize(n_elem, 6);
+    for (int e = 0; e < n_elem; e++)
+      for (int c = 0; c < 6; c++) sigma(e, c) = flat[static_cast<size_t>(e) * 6 + c];
+  }
+  // sigma: n_nodes x 6, von_mises: n_nodes (of the nodal tensor)
+  void RetrieveANCFNodalStressToCPU(tlfea::MatrixXd& sigma, tlfea::VectorXd& von_mises) {
+    std::vector<double> flat(static_cast<size_t>(n_nodes_) * 6);
+    von_mises.resize(n_nodes_);
+    TLFEA_HANDLE_ERROR(tlfea_ancf_retrieve_nodal_stress(h, flat.data(), von_mises.data()));
+    sigma.resize(n_nodes_, 6);
+    for (int i = 0; i < n_nodes_; i++)
+      for (int c = 0; c < 6; c++) sigma(i, c) = flat[static_cast<size_t>(i) * 6 + c];
+  }
+  Energies GetANCFEnergies() {
+    double o[5];
+    TLFEA_HANDLE_ERROR(tlfea_ancf_get_energies(h, o));
+    return Energies{o[0], o[1], o[2], o[3], o[4]};
+  }
+  double* GetANCFNodalStressDevicePtr() { return tlfea_ancf_nodal_stress_device_ptr(h); }
+  // mean ms of (point kernel, mesh-node gather, totals) over `reps` launches each
+  void TimeANCFStressKernels(const double* d_velocity, bool want_points, int reps, double out_ms3[3]) {
+    TLFEA_HANDLE_ERROR(tlfea_ancf_time_stress_kernels(h, d_velocity, want_points ? 1 : 0, reps, out_ms3));
+  }
   // element connectivity in NODE ids, n_beam x (2 | 4) (ANCF3243Data.cu:630-642, ANCF3443Data.cu:597-603); the handle
   // keeps coefficient ids [S][E] (slot 0 of node n of the element = 4 * node)
   void RetrieveConnectivityToCPU(tlfea::MatrixXi& connectivity) {

@@ -24,20 +24,36 @@ struct VisualizationUtils {
     std::vector<double> values;  // n_points * components
   };
 
-  // points, cells of `arity` point ids each (ids relative to `points`), VTK cell type (10 tetra, 12 hexahedron)
+  // points, cells of `arity` point ids each (ids relative to `points`), VTK cell type (1 vertex, 10 tetra, 12 hexahedron)
+  struct Piece {
+    std::vector<P3> points;
+    std::vector<int> cells;
+    int arity, vtk_type;
+    std::vector<PointField> fields;
+  };
   static bool WriteVTU(const std::string& filename, const std::vector<P3>& points, const std::vector<int>& cells,
                        int arity, int vtk_type, const std::vector<PointField>& fields = {}) {
+    return WriteVTU(filename, std::vector<Piece>{Piece{points, cells, arity, vtk_type, fields}});
+  }
+  // one <Piece> per entry, in order
+  static bool WriteVTU(const std::string& filename, const std::vector<Piece>& pieces) {
     std::ofstream file(filename);
     if (!file.is_open()) {
       std::cerr << "Error: Cannot open file " << filename << " for writing" << std::endl;
       return false;
     }
-    const size_t n_cells = arity ? cells.size() / arity : 0;
     file << std::setprecision(15) << std::scientific;
     file << "<?xml version=\"1.0\"?>\n"
          << "<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\">\n"
-         << "  <UnstructuredGrid>\n"
-         << "    <Piece NumberOfPoints=\"" << points.size() << "\" NumberOfCells=\"" << n_cells << "\">\n"
+         << "  <UnstructuredGrid>\n";
+    for (const Piece& p : pieces) write_piece(file, p.points, p.cells, p.arity, p.vtk_type, p.fields);
+    file << "  </UnstructuredGrid>\n</VTKFile>\n";
+    return static_cast<bool>(file);
+  }
+  static void write_piece(std::ofstream& file, const std::vector<P3>& points, const std::vector<int>& cells, int arity,
+                          int vtk_type, const std::vector<PointField>& fields) {
+    const size_t n_cells = arity ? cells.size() / arity : 0;
+    file << "    <Piece NumberOfPoints=\"" << points.size() << "\" NumberOfCells=\"" << n_cells << "\">\n"
          << "      <Points>\n"
          << "        <DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
     for (const P3& p : points) file << "          " << p[0] << " " << p[1] << " " << p[2] << "\n";
@@ -81,8 +97,7 @@ struct VisualizationUtils {
     for (size_t c = 0; c < n_cells; c++) file << "          " << (c + 1) * arity << "\n";
     file << "        </DataArray>\n        <DataArray type=\"UInt8\" Name=\"types\" format=\"ascii\">\n";
     for (size_t c = 0; c < n_cells; c++) file << "          " << vtk_type << "\n";
-    file << "        </DataArray>\n      </Cells>\n    </Piece>\n  </UnstructuredGrid>\n</VTKFile>\n";
-    return static_cast<bool>(file);
+    file << "        </DataArray>\n      </Cells>\n    </Piece>\n";
   }
 
   // T10 mesh as linear tets on the four corner nodes + nodal scalar "pressure" (visualization_utils.h:491-589)
@@ -146,6 +161,58 @@ struct VisualizationUtils {
                                   const tlfea::MatrixXi& element_connectivity, double thickness,
                                   const std::string& filename) {
     const int E = element_connectivity.rows();
+    return WriteVTU(filename, shell_points(x12, y12, z12, element_connectivity, thickness), iota_cells(E, 8), 8, 12);
+  }
+
+  // One hexahedron per beam: a width x height rectangle at each end node, in the frame built from the chord tangent t,
+  // n = t x ref (ref = z, or y when t is within ~26 degrees of z) and b = t x n (visualization_utils.h:974-1097)
+  static bool ExportANCF3243ToVTU(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
+                                  const tlfea::MatrixXi& element_connectivity, double width, double height,
+                                  const std::string& filename) {
+    const int E = element_connectivity.rows();
+    return WriteVTU(filename, beam_points(x12, y12, z12, element_connectivity, width, height), iota_cells(E, 8), 8, 12);
+  }
+
+  // What ExportANCF3443ToVTU (connectivity of 4 columns; `width` unused) or ExportANCF3243ToVTU (2 columns) writes, with
+  // point data "von_mises" (1) and "stress" (6: xx yy zz xy yz zx) as GPU_ANCF*_Data::RetrieveANCFNodalStressToCPU returns
+  // them: the hexahedra's corners carry the values of their mesh node, and a second piece holds the mesh nodes themselves
+  // (slot-0 positions, one vertex cell each) with the n_nodes tuples (no reference counterpart)
+  static bool ExportANCFMeshWithStress(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
+                                       const tlfea::MatrixXi& element_connectivity, double width, double height,
+                                       const tlfea::MatrixXd& nodal_sigma6, const tlfea::VectorXd& nodal_von_mises,
+                                       const std::string& filename) {
+    const int E = element_connectivity.rows(), nn = element_connectivity.cols(), n_nodes = x12.size() / 4;
+    if ((nn != 2 && nn != 4) || nodal_sigma6.rows() != n_nodes || nodal_sigma6.cols() != 6 || nodal_von_mises.size() != n_nodes) {
+      std::cerr << "ExportANCFMeshWithStress: connectivity of 2 or 4 columns and n_nodes x 6 / n_nodes stresses expected" << std::endl;
+      return false;
+    }
+    auto fields = [&](size_t n_points, auto node_of) {
+      PointField m{"von_mises", 1, std::vector<double>(n_points)}, s{"stress", 6, std::vector<double>(6 * n_points)};
+      for (size_t i = 0; i < n_points; i++) {
+        const int n = node_of(i);
+        m.values[i] = nodal_von_mises(n);
+        for (int c = 0; c < 6; c++) s.values[6 * i + c] = nodal_sigma6(n, c);
+      }
+      return std::vector<PointField>{m, s};
+    };
+    Piece hexa{nn == 4 ? shell_points(x12, y12, z12, element_connectivity, height)
+                       : beam_points(x12, y12, z12, element_connectivity, width, height),
+               iota_cells(E, 8), 8, 12, {}};
+    // corner i of element e: shells bottom face then top face over the 4 nodes, beams 4 corners per end node
+    hexa.fields = fields(hexa.points.size(), [&](size_t i) {
+      const int e = static_cast<int>(i / 8), k = static_cast<int>(i % 8);
+      return element_connectivity(e, nn == 4 ? k % 4 : k / 4);
+    });
+    Piece nodes{std::vector<P3>(n_nodes), iota_cells(n_nodes, 1), 1, 1, {}};
+    for (int n = 0; n < n_nodes; n++) nodes.points[n] = position(x12, y12, z12, n);
+    nodes.fields = fields(n_nodes, [](size_t i) { return static_cast<int>(i); });
+    return WriteVTU(filename, {hexa, nodes});
+  }
+
+ private:
+  static std::vector<P3> shell_points(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
+                                      const tlfea::MatrixXi& element_connectivity, double thickness) {
+    const int E = element_connectivity.rows();
     std::vector<P3> pts;
     pts.reserve(8 * (size_t)E);
     for (int e = 0; e < E; e++) {
@@ -156,14 +223,10 @@ struct VisualizationUtils {
       for (double side : {-0.5, 0.5})
         for (int k = 0; k < 4; k++) pts.push_back(axpy(side * thickness, nrm, p[k]));
     }
-    return WriteVTU(filename, pts, iota_cells(E, 8), 8, 12);
+    return pts;
   }
-
-  // One hexahedron per beam: a width x height rectangle at each end node, in the frame built from the chord tangent t,
-  // n = t x ref (ref = z, or y when t is within ~26 degrees of z) and b = t x n (visualization_utils.h:974-1097)
-  static bool ExportANCF3243ToVTU(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
-                                  const tlfea::MatrixXi& element_connectivity, double width, double height,
-                                  const std::string& filename) {
+  static std::vector<P3> beam_points(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
+                                     const tlfea::MatrixXi& element_connectivity, double width, double height) {
     const int E = element_connectivity.rows();
     std::vector<P3> pts;
     pts.reserve(8 * (size_t)E);
@@ -181,10 +244,8 @@ struct VisualizationUtils {
       for (int s = 0; s < 2; s++)
         for (int k = 0; k < 4; k++) pts.push_back(axpy(sv[k] * height, b, axpy(su[k] * width, n, end[s])));
     }
-    return WriteVTU(filename, pts, iota_cells(E, 8), 8, 12);
+    return pts;
   }
-
- private:
   static P3 position(const tlfea::VectorXd& x, const tlfea::VectorXd& y, const tlfea::VectorXd& z, int node) {
     return {x(4 * node), y(4 * node), z(4 * node)};
   }
