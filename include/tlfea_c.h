@@ -126,6 +126,24 @@ int tlfea_t10_clear_obstacles(tlfea_t10_t h);
 int tlfea_t10_get_obstacle_forces(tlfea_t10_t h, double *f);
 int tlfea_t10_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]);
 int tlfea_t10_get_surface_weights(tlfea_t10_t h, double *w);
+/* The same obstacles on ANCF-3243 / ANCF-3443 objects (DESIGN 3e'): contact is evaluated at 32 sample points on the
+ * faces of every element (shell: the faces zeta = -1, +1 with the 4 x 4 Gauss rule; beam: the four side faces with
+ * 4 x 2 Gauss points; no points on a shell's edge faces or a beam's end caps) and spread to the element's coefficients
+ * through the shape functions.  After Setup and CalcDsDuPre only; the limits, checks and refusals of the T10 entry points
+ * apply (which keep refusing ANCF handles, as these refuse T10 handles).
+ * get_obstacle_forces: the contact force on every coefficient (3 n_coef, the layout of f_ext) of the last gradient
+ * evaluation; get_obstacle_resultant: obstacle k's force on the mesh (out[0..2]) and its sample points in contact
+ * (out[3]); get_surface_points: the weight of every sample point (E * 32: quadrature weight x reference surface
+ * Jacobian, summing to the sampled area); retrieve_contact_points: E * 32 * 5 doubles, per point x y z, the smallest
+ * gap over the obstacles and the normal pressure sum_k kappa_k <-d_k> at the current coordinates (computed by this call:
+ * the same as at the last gradient evaluation unless the positions were changed since). */
+int tlfea_ancf_set_obstacles(tlfea_t10_t h, const tlfea_obstacle *list, int n);
+int tlfea_ancf_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle *o);
+int tlfea_ancf_clear_obstacles(tlfea_t10_t h);
+int tlfea_ancf_get_obstacle_forces(tlfea_t10_t h, double *f);
+int tlfea_ancf_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]);
+int tlfea_ancf_get_surface_points(tlfea_t10_t h, double *w);
+int tlfea_ancf_retrieve_contact_points(tlfea_t10_t h, double *out);
 /* Stress and energy recovery of T10 objects (no reference counterpart).  Works from the current positions and
  * the object's own data at any time after CalcDnDuPre; changes nothing a solver reads.  d_vel: DEVICE pointer to a
  * velocity (3N interleaved: what tlfea_*_velocity_guess_device_ptr returns) or NULL; with it a damped material's

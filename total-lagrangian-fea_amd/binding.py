@@ -78,6 +78,10 @@ def _obstacle_signatures(lib):
            "tlfea_t10_update_obstacle": [vp, i, C.POINTER(ObstacleC)], "tlfea_t10_clear_obstacles": [vp],
            "tlfea_t10_get_obstacle_forces": [vp, c_dp], "tlfea_t10_get_obstacle_resultant": [vp, i, c_dp],
            "tlfea_t10_get_surface_weights": [vp, c_dp]}
+    for name in list(sig)[:5]:  # the ANCF entry points (DESIGN 3e') take the same arguments
+        sig[name.replace("tlfea_t10_", "tlfea_ancf_")] = sig[name]
+    sig["tlfea_ancf_get_surface_points"] = [vp, c_dp]
+    sig["tlfea_ancf_retrieve_contact_points"] = [vp, c_dp]
     for name, args in sig.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int

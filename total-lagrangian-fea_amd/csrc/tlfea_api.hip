@@ -26,6 +26,7 @@
 #include "direct_host.h"
 #include "vbd_host.h"
 #include "obstacle_host.h"
+#include "ancf_obstacle_host.h"
 
 using namespace tlfea;
 
@@ -99,6 +100,14 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   int* d_ob_node = nullptr;
   double *d_ob_w = nullptr, *d_ob_f = nullptr, *d_ob_blk = nullptr, *d_ob_fk = nullptr, *d_ob_res = nullptr;
   int ob_fk_cap = 0;                // obstacles d_ob_fk has room for
+  // the same list on an ANCF object (tlfea_ancf_set_obstacles, DESIGN 3e'): sample-point tables and element-owned buffers
+  // (AncfObsView, tlfea_internal.h); d_ao_fc [N][3] the contact force per coefficient, d_ao_pts [E][32][5] the footprint
+  int *d_ao_cls = nullptr, *d_ao_touched = nullptr;
+  double *d_ao_sval = nullptr, *d_ao_w = nullptr, *d_ao_cbuf = nullptr, *d_ao_blk = nullptr, *d_ao_fk = nullptr,
+         *d_ao_fc = nullptr, *d_ao_pts = nullptr;
+  std::vector<double> h_ao_w;       // [E][32] sample-point weights (built once per mesh, on first use)
+  std::vector<int> h_ao_cls;
+  std::vector<double> h_ao_sval;
   // stress recovery (tlfea_t10_calc_stress): allocated on first use, read by no solver
   double *d_st_pts = nullptr, *d_st_erec = nullptr, *d_st_contrib = nullptr, *d_st_nodal = nullptr,
          *d_st_part = nullptr, *d_st_tot = nullptr, *d_st_vel = nullptr;
@@ -216,7 +225,8 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_n2e_pos, h->d_diagpos, h->d_mval, h->d_joff, h->d_jcol, h->d_jtoff, h->d_jtcol, h->d_jval,
                   h->d_jtval, h->d_rhs, h->d_emat, h->d_ob_node, h->d_ob_w, h->d_ob_f, h->d_ob_blk, h->d_ob_fk,
                   h->d_ob_res, h->d_st_pts, h->d_st_erec, h->d_st_contrib, h->d_st_nodal, h->d_st_part, h->d_st_tot,
-                  h->d_st_vel, h->d_st_noff, h->d_st_nel};
+                  h->d_st_vel, h->d_st_noff, h->d_st_nel, h->d_ao_cls, h->d_ao_touched, h->d_ao_sval, h->d_ao_w,
+                  h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -423,6 +433,8 @@ static void obstacles_free(tlfea_t10_t h) {
   h->obs.n = 0;
 }
 extern "C" int tlfea_t10_clear_obstacles(tlfea_t10_t h) {
+  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
+    return fail("tlfea_t10_clear_obstacles: T10 handles only (not an ANCF handle)");
   NEED_SETUP(h, "clearing obstacles.");
   if (h->obs.n == 0) return 0;
   HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
@@ -471,6 +483,8 @@ extern "C" int tlfea_t10_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list
   return 0;
 }
 extern "C" int tlfea_t10_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle* o) {
+  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
+    return fail("tlfea_t10_update_obstacle: T10 handles only (not an ANCF handle)");
   NEED_SETUP(h, "updating an obstacle.");
   if (k < 0 || k >= h->obs.n)
     return fail("tlfea_t10_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->obs.n) +
@@ -482,6 +496,8 @@ extern "C" int tlfea_t10_update_obstacle(tlfea_t10_t h, int k, const tlfea_obsta
   return 0;
 }
 extern "C" int tlfea_t10_get_obstacle_forces(tlfea_t10_t h, double* f) {
+  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
+    return fail("tlfea_t10_get_obstacle_forces: T10 handles only (not an ANCF handle)");
   NEED_SETUP(h, "reading obstacle forces.");
   if (!f) return fail("tlfea_t10_get_obstacle_forces: null output");
   std::fill(f, f + 3 * (size_t)h->N, 0.0);
@@ -495,6 +511,8 @@ extern "C" int tlfea_t10_get_obstacle_forces(tlfea_t10_t h, double* f) {
   return 0;
 }
 extern "C" int tlfea_t10_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
+  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
+    return fail("tlfea_t10_get_obstacle_resultant: T10 handles only (not an ANCF handle)");
   NEED_SETUP(h, "reading an obstacle resultant.");
   if (!out) return fail("tlfea_t10_get_obstacle_resultant: null output");
   if (k < 0 || k >= h->obs.n)
@@ -512,6 +530,148 @@ extern "C" int tlfea_t10_get_surface_weights(tlfea_t10_t h, double* w) {
   if (!w) return fail("tlfea_t10_get_surface_weights: null output");
   surface_build(h);
   std::copy(h->h_surf_w.begin(), h->h_surf_w.end(), w);
+  return 0;
+}
+
+// ---- rigid obstacles on the ANCF kinds (DESIGN 3e') ------------------------------------------------------------------------
+#define NEED_ANCF_OBS(h, what)                                                                              \
+  if ((h) && (h)->kind == kT10) return fail(std::string(what) + ": ANCF handles only (not a T10 handle)"); \
+  NEED_SETUP(h, what ".");                                                                                  \
+  if (!(h)->have_dndu) return fail(std::string(what) + ": CalcDsDuPre must run first (the point weights use the reference geometry)")
+// Weights and shape tables from the reference coefficients (x12_jac = d_xt).  Built by the first SetRigidObstacles /
+// GetSurfacePointWeights after a CalcDsDuPre, which drops the cache.  d_xt is also the constraint target: targets moved
+// (UpdateConstraintTargets) between CalcDsDuPre and that first use would be taken for the reference, as they would by a
+// second CalcDsDuPre itself.
+static int ancf_points_build(tlfea_t10_t h) {
+  if (!h->h_ao_w.empty()) return 0;
+  const size_t N = h->N;
+  std::vector<double> xj(N), yj(N), zj(N);
+  HIP_TRY(hipMemcpy(xj.data(), h->d_xt, N * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(yj.data(), h->d_yt, N * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(zj.data(), h->d_zt, N * sizeof(double), hipMemcpyDeviceToHost));
+  ancf::ObstacleSetup su =
+      ancf::obstacle_setup(h->S, h->E, h->h_conn, h->Lv, h->Wv, h->Hv, h->Binv, xj.data(), yj.data(), zj.data());
+  h->h_ao_w.swap(su.w);
+  h->h_ao_cls.swap(su.cls);
+  h->h_ao_sval.swap(su.sval);
+  return 0;
+}
+static AncfObsView ancf_obs_view(tlfea_t10_t h) {
+  return AncfObsView{h->E, h->S, h->d_conn, h->d_ao_cls, h->d_ao_sval, h->d_ao_w, h->d_ao_cbuf, h->d_ao_blk,
+                     h->d_ao_fk, h->d_ao_touched};
+}
+static void ancf_obstacles_free(tlfea_t10_t h) {
+  for (double** p : {&h->d_ao_sval, &h->d_ao_w, &h->d_ao_cbuf, &h->d_ao_blk, &h->d_ao_fk, &h->d_ao_fc, &h->d_ao_pts,
+                     &h->d_ob_res}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  for (int** p : {&h->d_ao_cls, &h->d_ao_touched}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  h->ob_fk_cap = 0;
+  h->obs.n = 0;
+}
+extern "C" int tlfea_ancf_clear_obstacles(tlfea_t10_t h) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_clear_obstacles");
+  if (h->obs.n == 0) return 0;
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
+  ancf_obstacles_free(h);
+  return 0;
+}
+extern "C" int tlfea_ancf_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_set_obstacles");
+  if (n < 0 || n > kMaxObstacles)
+    return fail("tlfea_ancf_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
+  if (n > 0 && !list) return fail("tlfea_ancf_set_obstacles: null list");
+  for (int k = 0; k < n; k++) {
+    const std::string why = obstacle_check(list[k]);
+    if (!why.empty()) return fail("tlfea_ancf_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
+  }
+  if (n == 0) return tlfea_ancf_clear_obstacles(h);
+  TRY(ancf_points_build(h));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t E = h->E, S = h->S, P = kAncfObsPoints;
+  if (!h->d_ao_w) {
+    TRY(dmalloc(&h->d_ao_cls, E));
+    TRY(dmalloc(&h->d_ao_touched, E));
+    TRY(dmalloc(&h->d_ao_sval, h->h_ao_sval.size()));
+    TRY(dmalloc(&h->d_ao_w, E * P));
+    TRY(dmalloc(&h->d_ao_cbuf, E * S * 3));
+    TRY(dmalloc(&h->d_ao_blk, E * P * 6));
+    TRY(dmalloc(&h->d_ao_fc, (size_t)3 * h->N));
+    TRY(dmalloc(&h->d_ob_res, (size_t)4 * kMaxObstacles));
+    HIP_TRY(hipMemcpy(h->d_ao_cls, h->h_ao_cls.data(), E * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_ao_sval, h->h_ao_sval.data(), h->h_ao_sval.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_ao_w, h->h_ao_w.data(), E * P * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (h->ob_fk_cap < n) {
+    if (h->d_ao_fk) (void)hipFree(h->d_ao_fk);
+    h->d_ao_fk = nullptr;
+    TRY(dmalloc(&h->d_ao_fk, (size_t)4 * n * E));
+    h->ob_fk_cap = n;
+  }
+  // no forces and no touched element before the first gradient evaluation
+  HIP_TRY(hipMemset(h->d_ao_touched, 0, E * sizeof(int)));
+  HIP_TRY(hipMemset(h->d_ao_cbuf, 0, E * S * 3 * sizeof(double)));
+  HIP_TRY(hipMemset(h->d_ao_fc, 0, (size_t)3 * h->N * sizeof(double)));
+  HIP_TRY(hipMemset(h->d_ao_fk, 0, (size_t)4 * n * E * sizeof(double)));
+  h->obs.n = n;
+  for (int k = 0; k < n; k++) h->obs.o[k] = obstacle_dev(list[k]);
+  return 0;
+}
+extern "C" int tlfea_ancf_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle* o) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_update_obstacle");
+  if (k < 0 || k >= h->obs.n)
+    return fail("tlfea_ancf_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->obs.n) +
+                " obstacles set");
+  if (!o) return fail("tlfea_ancf_update_obstacle: null obstacle");
+  const std::string why = obstacle_check(*o);
+  if (!why.empty()) return fail("tlfea_ancf_update_obstacle: obstacle " + std::to_string(k) + ": " + why);
+  h->obs.o[k] = obstacle_dev(*o);  // a kernel argument: launches already queued keep the old value
+  return 0;
+}
+extern "C" int tlfea_ancf_get_obstacle_forces(tlfea_t10_t h, double* f) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_get_obstacle_forces");
+  if (!f) return fail("tlfea_ancf_get_obstacle_forces: null output");
+  if (h->obs.n == 0) {
+    std::fill(f, f + 3 * (size_t)h->N, 0.0);
+    return 0;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(f, h->d_ao_fc, 3 * (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+extern "C" int tlfea_ancf_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_get_obstacle_resultant");
+  if (!out) return fail("tlfea_ancf_get_obstacle_resultant: null output");
+  if (k < 0 || k >= h->obs.n)
+    return fail("tlfea_ancf_get_obstacle_resultant: index " + std::to_string(k) + " outside the " +
+                std::to_string(h->obs.n) + " obstacles set");
+  HIP_TRY(hipDeviceSynchronize());
+  launch_obstacle_resultant(h->stream, h->E, h->obs.n, h->d_ao_fk, h->d_ob_res);  // the elements' shares, element order
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, h->d_ob_res + 4 * k, 4 * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+extern "C" int tlfea_ancf_get_surface_points(tlfea_t10_t h, double* w) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_get_surface_points");
+  if (!w) return fail("tlfea_ancf_get_surface_points: null output");
+  TRY(ancf_points_build(h));
+  std::copy(h->h_ao_w.begin(), h->h_ao_w.end(), w);
+  return 0;
+}
+extern "C" int tlfea_ancf_retrieve_contact_points(tlfea_t10_t h, double* out) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_retrieve_contact_points");
+  if (!out) return fail("tlfea_ancf_retrieve_contact_points: null output");
+  if (h->obs.n == 0) return fail("tlfea_ancf_retrieve_contact_points: no obstacles are set");
+  const size_t n = (size_t)h->E * kAncfObsPoints * 5;
+  HIP_TRY(hipDeviceSynchronize());
+  if (!h->d_ao_pts) TRY(dmalloc(&h->d_ao_pts, n));
+  launch_ancf_obstacle_footprint(h->stream, ancf_obs_view(h), h->obs, h->d_x, h->d_y, h->d_z, h->d_ao_pts);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, h->d_ao_pts, n * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -894,6 +1054,13 @@ extern "C" int tlfea_ancf_calc_dsdu_pre(tlfea_t10_t h) {
   HIP_TRY(hipMemcpy(h->d_gradN_t, gNt.data(), gNt.size() * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->d_detJ, dJ.data(), dJ.size() * sizeof(double), hipMemcpyHostToDevice));
   h->have_dndu = true;
+  // the sample-point weights of the obstacles (DESIGN 3e') belong to the reference this call has just used
+  h->h_ao_w.clear();
+  if (h->d_ao_w) {
+    TRY(ancf_points_build(h));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(h->d_ao_w, h->h_ao_w.data(), h->h_ao_w.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
   return 0;
 }
 
@@ -2810,6 +2977,12 @@ static int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, 
 // contact gradient of the rigid obstacles (g may be null: refresh of the per-node force / block buffers only)
 static void launch_obstacles_grad(tlfea_newton_t s, double* g) {
   tlfea_t10_t d = s->d;
+  if (d->kind != kT10) {  // DESIGN 3e': sample points per element, then the coefficient-owner gather
+    launch_ancf_obstacle_points(s->stream, ancf_obs_view(d), d->obs, d->d_x, d->d_y, d->d_z, s->d_xp, s->d_yp, s->d_zp,
+                                s->prm.time_step);
+    launch_ancf_obstacle_gather(s->stream, s->N, d->inc(), d->d_ao_cbuf, d->d_ao_fc, g);
+    return;
+  }
   launch_obstacle_grad(s->stream, (int)d->h_surf.size(), d->d_ob_node, d->d_ob_w, d->obs, d->d_x, d->d_y, d->d_z, s->d_xp,
                        s->d_yp, s->d_zp, s->prm.time_step, pinned_on(s) ? d->d_fixed_slot : nullptr, g, d->d_ob_f,
                        d->d_ob_blk, d->d_ob_fk);
@@ -2817,10 +2990,18 @@ static void launch_obstacles_grad(tlfea_newton_t s, double* g) {
 // + h x the contact blocks on the diagonal of H: after the assembly and the constraint term, before anything reads H
 static void launch_obstacles_hessian(tlfea_newton_t s, bool buffers_fresh) {
   tlfea_t10_t d = s->d;
-  if (d->obs.n == 0) return;
+  if (d->obs.n == 0 || d->kind != kT10) return;  // ANCF: in Kbuf before the row assembly (launch_ancf_obstacles_tangent)
   if (!buffers_fresh) launch_obstacles_grad(s, nullptr);
   launch_obstacle_hessian(s->stream, (int)d->h_surf.size(), d->d_ob_node, d->d_off, d->d_diagpos, d->d_ob_blk,
                           s->prm.time_step, s->d_H);
+}
+
+// ANCF: + h sum_p S_i S_j C_p on the element blocks of every touched element, between the element tangent and the rows
+static void launch_ancf_obstacles_tangent(tlfea_newton_t s, bool buffers_fresh) {
+  tlfea_t10_t d = s->d;
+  if (d->obs.n == 0 || d->kind == kT10) return;
+  if (!buffers_fresh) launch_obstacles_grad(s, nullptr);
+  launch_ancf_obstacle_tangent(s->stream, ancf_obs_view(d), s->prm.time_step, s->d_Kbuf);
 }
 
 static int eval_gradient(tlfea_newton_t s, double* norm_g) {
@@ -2904,6 +3085,7 @@ static int assemble(tlfea_newton_t s, bool fq_fresh = true) {
   }
   {
     StageTimer t(s, 3);
+    launch_ancf_obstacles_tangent(s, after_grad);
     launch_assemble_rows(s->stream, s->N, d->S, d->maxdeg, d->inc(), s->d_Kbuf, d->d_mval, 1.0 / p.time_step,
                          pinned ? d->d_fixed_slot : nullptr, s->d_nw, p.time_step * p.time_step * p.rho, s->d_H);
     if (lincons_on(s))  // + h^2 rho J^T J  (SyncedNewton.cu:292-341)

@@ -379,6 +379,32 @@ void launch_obstacle_hessian(hipStream_t s, int n_surf, const int* node, const i
 // out[j][4] = fixed-order sums of fk over the surface nodes, one block per obstacle
 void launch_obstacle_resultant(hipStream_t s, int n_surf, int n_obs, const double* fk, double* out);
 
+// The same obstacles on the ANCF kinds (tlfea_ancf_set_obstacles, DESIGN 3e'; ancf_obstacle_kernels.hip): contact at
+// kAncfObsPoints sample points per element, spread to the element's coefficients through the shape functions.
+constexpr int kAncfObsPoints = 32;
+struct AncfObsView {
+  int E, S;
+  const int* conn;      // [S][E] coefficient ids (ElemView::conn)
+  const int* cls;       // [E] the element's (L, W, H) class
+  const double* sval;   // [n_class][32][S] shape values S_a(p)
+  const double* w;      // [E][32] quadrature weight x reference surface Jacobian
+  double* cbuf;         // [E][S][3] contact force rows (the layout of fbuf)
+  double* blk;          // [E][32][6] C_p (xx yy zz xy xz yz), written for touched elements only
+  double* fk;           // [n_obs][E][4] per obstacle: the element's force share | its points in contact
+  int* touched;         // [E] some point has d < 0 or an active friction term
+};
+// points kernel: fills cbuf, blk, fk and touched from the current (x) and start-of-step (xp) coordinates
+void launch_ancf_obstacle_points(hipStream_t s, const AncfObsView& v, const ObstacleList& L, const double* x,
+                                 const double* y, const double* z, const double* xp, const double* yp, const double* zp,
+                                 double h);
+// Kbuf's (i <= j) blocks of every touched element += h sum_p S_i S_j C_p
+void launch_ancf_obstacle_tangent(hipStream_t s, const AncfObsView& v, double h, double* Kbuf);
+// fc [N][3] = ascending-element sum of the coefficient's cbuf rows; g (may be null) -= fc
+void launch_ancf_obstacle_gather(hipStream_t s, int N, const Incidence& inc, const double* cbuf, double* fc, double* g);
+// pts [E][32][5] = position | smallest gap | normal pressure sum_j kappa_j <-d_j> of every sample point
+void launch_ancf_obstacle_footprint(hipStream_t s, const AncfObsView& v, const ObstacleList& L, const double* x,
+                                    const double* y, const double* z, double* pts);
+
 // Stress and energy recovery of T10 objects (tlfea_t10_calc_stress; stress_kernels.hip).  No atomics.
 // pts (null: not wanted) [E][5][6] Cauchy stress per Keast point, xx yy zz xy yz zx; erec [E][10] = volume-weighted mean
 // stress (6) | its von Mises | mean strain-energy density | mean J | reference volume V_e; contrib [4][Epad] the element's

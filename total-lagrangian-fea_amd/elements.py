@@ -488,6 +488,53 @@ class _GPU_ANCF_Data(GPU_FEAT10_Data):
         check(self._lib.tlfea_ancf_time_stress_kernels(self._h, C.c_void_p(ptr), int(bool(want_points)), int(reps), dp(out)))
         return out
 
+    # -- rigid obstacles (DESIGN 3e'): contact at 32 sample points per element ------------------------------------------
+    POINTS = 32
+
+    def SetRigidObstacles(self, obstacles):
+        """Replace the obstacle list (RigidPlane / RigidSphere, at most 16; an empty list clears it).  After Setup and
+        CalcDsDuPre."""
+        obstacles = list(obstacles)
+        if len(obstacles) > MAX_OBSTACLES:
+            raise ValueError(f"at most {MAX_OBSTACLES} obstacles per object, got {len(obstacles)}")
+        arr = (ObstacleC * max(1, len(obstacles)))(*[as_c(o) for o in obstacles])
+        check(self._lib.tlfea_ancf_set_obstacles(self._h, arr, len(obstacles)))
+
+    def UpdateRigidObstacle(self, k, obstacle):
+        """Replace obstacle k (move it between steps)."""
+        o = as_c(obstacle)
+        check(self._lib.tlfea_ancf_update_obstacle(self._h, int(k), C.byref(o)))
+
+    def ClearRigidObstacles(self):
+        check(self._lib.tlfea_ancf_clear_obstacles(self._h))
+
+    def GetObstacleForces(self):
+        """Contact force on every coefficient (3 n_coef, the layout of f_ext) at the last gradient evaluation."""
+        f = np.zeros(3 * self.n_coef)
+        check(self._lib.tlfea_ancf_get_obstacle_forces(self._h, dp(f)))
+        return f
+
+    def GetObstacleResultant(self, k):
+        """(force of obstacle k on the mesh as a 3-vector, sample points in contact) at the last gradient evaluation."""
+        out = np.zeros(4)
+        check(self._lib.tlfea_ancf_get_obstacle_resultant(self._h, int(k), dp(out)))
+        return out[:3].copy(), int(round(out[3]))
+
+    def GetSurfacePointWeights(self):
+        """[E][32]: quadrature weight x reference surface Jacobian of every sample point; the sum is the sampled area."""
+        w = np.zeros((self.n_elem, self.POINTS))
+        check(self._lib.tlfea_ancf_get_surface_points(self._h, dp(w)))
+        return w
+
+    def GetSurfaceWeights(self):
+        raise TypeError("GetSurfaceWeights is nodal (T10); an ANCF object has GetSurfacePointWeights")
+
+    def RetrieveContactPointsToCPU(self):
+        """[E][32][5]: x, y, z, smallest gap and normal pressure of every sample point at the current coefficients."""
+        p = np.zeros((self.n_elem, self.POINTS, 5))
+        check(self._lib.tlfea_ancf_retrieve_contact_points(self._h, dp(p)))
+        return p
+
 
 class GPU_ANCF3243_Data(_GPU_ANCF_Data):
     TYPE, KIND, NN, S, Q = "TYPE_3243", 3243, 2, 8, 12

@@ -953,6 +953,33 @@ struct GPU_ANCF_DataBase : public GPU_FEAT10_Data {
     if (tlfea_t10_update_linear_constraint_rhs(h, rhs.data(), rhs.size()) != 0) std::cerr << tlfea_last_error() << std::endl;
   }
   int GetConstraintMode() const { return tlfea_t10_get_constraint_mode(h); }
+  // rigid obstacles on the ANCF kinds (DESIGN 3e'; no reference counterpart): contact at 32 sample points on the faces of
+  // every element.  After Setup and CalcDsDuPre.  The set / update calls return the C-ABI's status (0 = accepted).
+  int SetRigidObstacles(const std::vector<tlfea_obstacle>& list) {
+    return tlfea_ancf_set_obstacles(h, list.data(), static_cast<int>(list.size()));
+  }
+  int UpdateRigidObstacle(int k, const tlfea_obstacle& o) { return tlfea_ancf_update_obstacle(h, k, &o); }
+  int ClearRigidObstacles() { return tlfea_ancf_clear_obstacles(h); }
+  // contact force on every coefficient (3 n_coef, the layout of f_ext) at the last gradient evaluation
+  void GetObstacleForces(tlfea::VectorXd& f) {
+    f.resize(3 * n_coef);
+    TLFEA_HANDLE_ERROR(tlfea_ancf_get_obstacle_forces(h, f.data()));
+  }
+  // out[0..2]: obstacle k's force on the mesh, out[3]: its sample points in contact
+  void GetObstacleResultant(int k, double out[4]) { TLFEA_HANDLE_ERROR(tlfea_ancf_get_obstacle_resultant(h, k, out)); }
+  // weight of every sample point (n_elem * 32); the sum is the sampled area
+  void GetSurfacePointWeights(tlfea::VectorXd& w) {
+    w.resize(n_elem * 32);
+    TLFEA_HANDLE_ERROR(tlfea_ancf_get_surface_points(h, w.data()));
+  }
+  // n_elem * 32 rows of x, y, z, smallest gap, normal pressure at the current coefficients
+  void RetrieveContactPointsToCPU(tlfea::MatrixXd& pts) {
+    std::vector<double> flat(static_cast<size_t>(n_elem) * 32 * 5);
+    TLFEA_HANDLE_ERROR(tlfea_ancf_retrieve_contact_points(h, flat.data()));
+    pts.resize(n_elem * 32, 5);
+    for (int i = 0; i < n_elem * 32; i++)
+      for (int c = 0; c < 5; c++) pts(i, c) = flat[static_cast<size_t>(i) * 5 + c];
+  }
   // stress and energy recovery of the ANCF kinds (DESIGN 3f'; no reference counterpart): the members of GPU_FEAT10_Data's
   // CalcStress family under their own names (those keep refusing an ANCF object).  d_velocity: a solver's
   // GetVelocityGuessDevicePtr() or null; "nodal" = per MESH node.  Status 0 = done (tlfea_last_error() explains a refusal).

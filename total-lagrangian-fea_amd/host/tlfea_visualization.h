@@ -209,6 +209,26 @@ struct VisualizationUtils {
     return WriteVTU(filename, {hexa, nodes});
   }
 
+  // The sample points of GPU_ANCF*_Data::RetrieveContactPointsToCPU (rows of x, y, z, gap, pressure) as vertex cells with
+  // point data "gap" and "pressure"; in_contact_only keeps the rows of pressure > 0 (the footprint)
+  static bool ExportContactPointsToVTU(const tlfea::MatrixXd& pts, const std::string& filename, bool in_contact_only = false) {
+    if (pts.cols() != 5) {
+      std::cerr << "ExportContactPointsToVTU: rows of x, y, z, gap, pressure expected" << std::endl;
+      return false;
+    }
+    Piece piece{{}, {}, 1, 1, {}};
+    PointField gap{"gap", 1, {}}, pressure{"pressure", 1, {}};
+    for (int i = 0; i < pts.rows(); i++) {
+      if (in_contact_only && !(pts(i, 4) > 0.0)) continue;
+      piece.points.push_back({pts(i, 0), pts(i, 1), pts(i, 2)});
+      gap.values.push_back(pts(i, 3));
+      pressure.values.push_back(pts(i, 4));
+    }
+    piece.cells = iota_cells(static_cast<int>(piece.points.size()), 1);
+    piece.fields = {gap, pressure};
+    return WriteVTU(filename, {piece});
+  }
+
  private:
   static std::vector<P3> shell_points(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
                                       const tlfea::MatrixXi& element_connectivity, double thickness) {
