@@ -144,6 +144,39 @@ int tlfea_ancf_get_obstacle_forces(tlfea_t10_t h, double *f);
 int tlfea_ancf_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]);
 int tlfea_ancf_get_surface_points(tlfea_t10_t h, double *w);
 int tlfea_ancf_retrieve_contact_points(tlfea_t10_t h, double *out);
+/* Distributed loads (no reference counterpart).  They live beside f_ext, not in it: every gradient evaluation
+ * (Newton, direct Newton, AdamW, Nesterov) does g -= f_load(x), and tlfea_t10_set_external_force / retrieve_external_force
+ * keep their meaning.  Nothing is allocated or launched while no load is set.
+ * Body acceleration a (gravity), any handle: f_i = sum_j M_ij a_j with a_j = a on position coefficients (every
+ * coefficient of a T10 mesh, coefficient 4 n of ANCF node n) and 0 on gradient coefficients, from the mass matrix on the
+ * device; after CalcMassMatrix only, and rebuilt after a later CalcMassMatrix.
+ * Surface loads, ANCF handles only, after Setup and CalcDsDuPre, at most 16: each applies to one face of a list of
+ * elements (shell: zeta = -1, +1 -> face 0, 1; beam: eta = -1, +1, zeta = -1, +1 -> face 0..3, as the obstacle sample
+ * points number them).  kind 0, dead traction value[0..2] (force per reference area, fixed direction), integrated with
+ * the obstacle sample points of the face; kind 1, follower pressure value[0] (positive pushes against the outward normal
+ * of the deformed face), integrated at the current coefficients with a 5 x 5 (shell) or 5 x 2 (beam) Gauss rule.  scale
+ * multiplies the value; update_load_scale changes it between steps (ramps) without sending the list again.  An element
+ * index outside 0..E-1, a face outside the kind's range and the same element twice in one load are refused.  The pressure
+ * load stiffness is left out of the Hessian (it is unsymmetric; H stays SPD), so Newton converges linearly in that term.
+ * set_surface_loads replaces the list (n = 0 removes it); clear_loads removes the list and the body acceleration.
+ * While loads are set, tlfea_vbd_solve, tlfea_newton_set_halo and tlfea_newton_set_interface fail.
+ * get_load_forces: the load on every coefficient (3 n_coef, the layout of f_ext) of the last gradient evaluation;
+ * get_load_resultant: its sum over the position coefficients. */
+#define TLFEA_MAX_LOADS 16
+typedef struct {
+  int kind;          /* 0 dead traction, 1 follower pressure */
+  int face;          /* shell 0..1, beam 0..3 */
+  double value[3];   /* traction vector | pressure in value[0] */
+  double scale;      /* multiplies value */
+  const int *elems;  /* element indices */
+  int n_elems;
+} tlfea_surface_load;
+int tlfea_set_body_acceleration(tlfea_t10_t h, const double a[3]);
+int tlfea_ancf_set_surface_loads(tlfea_t10_t h, const tlfea_surface_load *list, int n);
+int tlfea_ancf_update_load_scale(tlfea_t10_t h, int k, double scale);
+int tlfea_clear_loads(tlfea_t10_t h);
+int tlfea_get_load_forces(tlfea_t10_t h, double *f);
+int tlfea_get_load_resultant(tlfea_t10_t h, double out[3]);
 /* Stress and energy recovery of T10 objects (no reference counterpart).  Works from the current positions and
  * the object's own data at any time after CalcDnDuPre; changes nothing a solver reads.  d_vel: DEVICE pointer to a
  * velocity (3N interleaved: what tlfea_*_velocity_guess_device_ptr returns) or NULL; with it a damped material's

@@ -71,6 +71,22 @@ class ObstacleC(C.Structure):  # tlfea_obstacle
                 ("vel", C.c_double * 3), ("stiffness", C.c_double), ("friction", C.c_double), ("eps_v", C.c_double)]
 
 
+class SurfaceLoadC(C.Structure):  # tlfea_surface_load
+    _fields_ = [("kind", C.c_int), ("face", C.c_int), ("value", C.c_double * 3), ("scale", C.c_double),
+                ("elems", c_ip), ("n_elems", C.c_int)]
+
+
+def _load_signatures(lib):
+    """ctypes signatures of the distributed-load entry points."""
+    vp, i = C.c_void_p, C.c_int
+    sig = {"tlfea_set_body_acceleration": [vp, c_dp], "tlfea_ancf_set_surface_loads": [vp, C.POINTER(SurfaceLoadC), i],
+           "tlfea_ancf_update_load_scale": [vp, i, C.c_double], "tlfea_clear_loads": [vp],
+           "tlfea_get_load_forces": [vp, c_dp], "tlfea_get_load_resultant": [vp, c_dp]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+
+
 def _obstacle_signatures(lib):
     """ctypes signatures of the rigid-obstacle entry points."""
     vp, i = C.c_void_p, C.c_int
@@ -182,6 +198,7 @@ def load_library():
     _material_signatures(lib)
     _obstacle_signatures(lib)
     _stress_signatures(lib)
+    _load_signatures(lib)
     _LIB = lib
     return lib
 

@@ -27,6 +27,7 @@
 #include "vbd_host.h"
 #include "obstacle_host.h"
 #include "ancf_obstacle_host.h"
+#include "ancf_load_host.h"
 
 using namespace tlfea;
 
@@ -108,6 +109,22 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   std::vector<double> h_ao_w;       // [E][32] sample-point weights (built once per mesh, on first use)
   std::vector<int> h_ao_cls;
   std::vector<double> h_ao_sval;
+  // distributed loads: none set = nothing allocated, nothing launched.  d_ld_fc [N][3] the constant part
+  // (M a + the traction vector d_ld_tr), rebuilt by the next gradient evaluation while ld_const_dirty; d_ld_f [N][3] the
+  // total load of the last gradient evaluation; the rest is AncfLoadView's (tlfea_internal.h)
+  struct SurfaceLoad {
+    int kind, face;
+    double value[3], scale;
+    std::vector<int> elems;
+  };
+  bool ld_have_a = false, ld_const_dirty = false;
+  double ld_a[3] = {0, 0, 0};
+  std::vector<SurfaceLoad> ld_list;
+  int ld_n_trac = 0, ld_n_press = 0;
+  double *d_ld_fc = nullptr, *d_ld_tr = nullptr, *d_ld_f = nullptr, *d_ld_lbuf = nullptr, *d_ld_tab = nullptr,
+         *d_ld_qw = nullptr, *d_ld_pe = nullptr;
+  int *d_ld_cls = nullptr, *d_ld_mask = nullptr;
+  bool loads_on() const { return ld_have_a || !ld_list.empty(); }
   // stress recovery (tlfea_t10_calc_stress): allocated on first use, read by no solver
   double *d_st_pts = nullptr, *d_st_erec = nullptr, *d_st_contrib = nullptr, *d_st_nodal = nullptr,
          *d_st_part = nullptr, *d_st_tot = nullptr, *d_st_vel = nullptr;
@@ -226,7 +243,8 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_jtval, h->d_rhs, h->d_emat, h->d_ob_node, h->d_ob_w, h->d_ob_f, h->d_ob_blk, h->d_ob_fk,
                   h->d_ob_res, h->d_st_pts, h->d_st_erec, h->d_st_contrib, h->d_st_nodal, h->d_st_part, h->d_st_tot,
                   h->d_st_vel, h->d_st_noff, h->d_st_nel, h->d_ao_cls, h->d_ao_touched, h->d_ao_sval, h->d_ao_w,
-                  h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts};
+                  h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts, h->d_ld_fc, h->d_ld_tr, h->d_ld_f,
+                  h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -675,6 +693,213 @@ extern "C" int tlfea_ancf_retrieve_contact_points(tlfea_t10_t h, double* out) {
   return 0;
 }
 
+// ---- distributed loads -------------------------------------------------------------------------------------------
+static bool mass_assembled(tlfea_t10_t h) { return h->kind == kT10 ? h->mass_rho0 >= 0.0 : h->ancf_mass; }
+static AncfLoadView ancf_load_view(tlfea_t10_t h) {
+  return AncfLoadView{h->E, h->S, h->d_conn, h->d_ld_cls, h->d_ld_tab, h->d_ld_qw, h->d_ld_mask, h->d_ld_pe, h->d_ld_lbuf};
+}
+static void surface_loads_free(tlfea_t10_t h) {
+  for (double** p : {&h->d_ld_tr, &h->d_ld_lbuf, &h->d_ld_tab, &h->d_ld_qw, &h->d_ld_pe}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  for (int** p : {&h->d_ld_cls, &h->d_ld_mask}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  h->ld_list.clear();
+  h->ld_n_trac = h->ld_n_press = 0;
+}
+static void loads_free(tlfea_t10_t h) {
+  surface_loads_free(h);
+  for (double** p : {&h->d_ld_fc, &h->d_ld_f}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  h->ld_have_a = h->ld_const_dirty = false;
+  h->ld_a[0] = h->ld_a[1] = h->ld_a[2] = 0.0;
+}
+// the two [N][3] vectors every load needs; the total starts at zero (no gradient evaluation yet)
+static int loads_alloc_common(tlfea_t10_t h) {
+  if (h->d_ld_f) return 0;
+  TRY(dmalloc(&h->d_ld_fc, (size_t)3 * h->N));
+  TRY(dmalloc(&h->d_ld_f, (size_t)3 * h->N));
+  HIP_TRY(hipMemset(h->d_ld_fc, 0, (size_t)3 * h->N * sizeof(double)));
+  HIP_TRY(hipMemset(h->d_ld_f, 0, (size_t)3 * h->N * sizeof(double)));
+  return 0;
+}
+// Traction vector [N][3] = sum over the traction loads (list order), their elements (list order), the element's
+// coefficients and the face's sample points (point order) of scale t w_p S_a(p): on the host, once per change.
+static int loads_build_traction(tlfea_t10_t h) {
+  if (h->ld_n_trac == 0) return 0;
+  TRY(ancf_points_build(h));
+  const int S = h->S, E = h->E, ppf = kAncfObsPoints / ancf::load_faces(S);
+  std::vector<double> tr((size_t)3 * h->N, 0.0);
+  for (const auto& L : h->ld_list) {
+    if (L.kind != 0) continue;
+    for (int e : L.elems) {
+      const double* sv = &h->h_ao_sval[(size_t)h->h_ao_cls[e] * kAncfObsPoints * S];
+      const double* w = &h->h_ao_w[(size_t)e * kAncfObsPoints];
+      for (int a = 0; a < S; a++) {
+        double ws = 0.0;
+        for (int p = L.face * ppf; p < (L.face + 1) * ppf; p++) ws += w[p] * sv[(size_t)p * S + a];
+        const int id = h->h_conn[(size_t)a * E + e];
+        for (int c = 0; c < 3; c++) tr[3 * (size_t)id + c] += L.scale * L.value[c] * ws;
+      }
+    }
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h->d_ld_tr, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->ld_const_dirty = true;
+  return 0;
+}
+// pe [E][faces] = -(orientation sign) x sum over the pressure loads (list order) of scale x pressure
+static int loads_build_pressure_scale(tlfea_t10_t h) {
+  if (h->ld_n_press == 0) return 0;
+  const int NF = ancf::load_faces(h->S);
+  std::vector<double> pe((size_t)h->E * NF, 0.0);
+  for (const auto& L : h->ld_list)
+    if (L.kind == 1)
+      for (int e : L.elems) pe[(size_t)e * NF + L.face] += L.scale * L.value[0];
+  for (size_t k = 0; k < pe.size(); k++) pe[k] *= -ancf::load_face_sign(h->S, (int)(k % NF));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h->d_ld_pe, pe.data(), pe.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int tlfea_clear_loads(tlfea_t10_t h) {
+  NEED_SETUP(h, "clearing loads.");
+  if (!h->loads_on()) return 0;
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
+  loads_free(h);
+  return 0;
+}
+extern "C" int tlfea_set_body_acceleration(tlfea_t10_t h, const double a[3]) {
+  NEED_SETUP(h, "setting a body acceleration.");
+  if (h->kind != kT10 && !h->have_dndu) return fail("tlfea_set_body_acceleration: CalcDsDuPre must run first");
+  if (!a) return fail("tlfea_set_body_acceleration: null acceleration");
+  if (!(std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2])))
+    return fail("tlfea_set_body_acceleration: the acceleration must be finite");
+  if (!mass_assembled(h))
+    return fail("tlfea_set_body_acceleration: CalcMassMatrix must run first (the load is the mass matrix times the acceleration)");
+  HIP_TRY(hipDeviceSynchronize());
+  if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0) {  // no body force: as if never set
+    h->ld_have_a = false;
+    h->ld_a[0] = h->ld_a[1] = h->ld_a[2] = 0.0;
+    if (!h->loads_on()) loads_free(h);
+    h->ld_const_dirty = true;
+    return 0;
+  }
+  TRY(loads_alloc_common(h));
+  h->ld_have_a = true;
+  std::copy(a, a + 3, h->ld_a);
+  h->ld_const_dirty = true;
+  return 0;
+}
+extern "C" int tlfea_ancf_set_surface_loads(tlfea_t10_t h, const tlfea_surface_load* list, int n) {
+  if (h && h->kind == kT10)
+    return fail("tlfea_ancf_set_surface_loads: ANCF handles only (a T10 handle takes the body acceleration alone)");
+  NEED_SETUP(h, "setting surface loads.");
+  if (!h->have_dndu)
+    return fail("tlfea_ancf_set_surface_loads: CalcDsDuPre must run first (the traction weights use the reference geometry)");
+  if (n < 0 || n > kMaxLoads)
+    return fail("tlfea_ancf_set_surface_loads: n must be in 0.." + std::to_string(kMaxLoads) + ", got " + std::to_string(n));
+  if (n > 0 && !list) return fail("tlfea_ancf_set_surface_loads: null list");
+  const int NF = ancf::load_faces(h->S), P = ancf::load_points(h->S), E = h->E, S = h->S;
+  std::vector<tlfea_t10_s::SurfaceLoad> fresh((size_t)n);
+  std::vector<char> seen;
+  for (int k = 0; k < n; k++) {
+    const tlfea_surface_load& L = list[k];
+    const std::string who = "tlfea_ancf_set_surface_loads: load " + std::to_string(k) + ": ";
+    if (L.kind != 0 && L.kind != 1) return fail(who + "kind must be 0 (traction) or 1 (pressure), got " + std::to_string(L.kind));
+    if (L.face < 0 || L.face >= NF)
+      return fail(who + "face " + std::to_string(L.face) + " outside 0.." + std::to_string(NF - 1));
+    for (int c = 0; c < (L.kind == 0 ? 3 : 1); c++)
+      if (!std::isfinite(L.value[c])) return fail(who + "the value must be finite");
+    if (!std::isfinite(L.scale)) return fail(who + "the scale must be finite");
+    if (L.n_elems <= 0 || !L.elems) return fail(who + "empty element list");
+    seen.assign((size_t)E, 0);
+    for (int i = 0; i < L.n_elems; i++) {
+      const int e = L.elems[i];
+      if (e < 0 || e >= E) return fail(who + "element " + std::to_string(e) + " outside 0.." + std::to_string(E - 1));
+      if (seen[e]) return fail(who + "element " + std::to_string(e) + " is listed twice for face " + std::to_string(L.face));
+      seen[e] = 1;
+    }
+    fresh[k].kind = L.kind;
+    fresh[k].face = L.face;
+    fresh[k].scale = L.scale;
+    for (int c = 0; c < 3; c++) fresh[k].value[c] = L.kind == 0 || c == 0 ? L.value[c] : 0.0;
+    fresh[k].elems.assign(L.elems, L.elems + L.n_elems);
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  surface_loads_free(h);
+  h->ld_const_dirty = true;
+  if (n == 0) {
+    if (!h->loads_on()) loads_free(h);
+    return 0;
+  }
+  TRY(loads_alloc_common(h));
+  h->ld_list.swap(fresh);
+  for (const auto& L : h->ld_list) (L.kind == 0 ? h->ld_n_trac : h->ld_n_press)++;
+  if (h->ld_n_trac > 0) {
+    TRY(dmalloc(&h->d_ld_tr, (size_t)3 * h->N));
+    TRY(loads_build_traction(h));
+  }
+  if (h->ld_n_press > 0) {
+    const ancf::PressureSetup su = ancf::pressure_setup(S, E, h->Lv, h->Wv, h->Hv, h->Binv);
+    std::vector<int> mask((size_t)E, 0);
+    for (const auto& L : h->ld_list)
+      if (L.kind == 1)
+        for (int e : L.elems) mask[e] |= 1 << L.face;
+    TRY(dmalloc(&h->d_ld_cls, (size_t)E));
+    TRY(dmalloc(&h->d_ld_mask, (size_t)E));
+    TRY(dmalloc(&h->d_ld_tab, su.tab.size()));
+    TRY(dmalloc(&h->d_ld_qw, (size_t)P));
+    TRY(dmalloc(&h->d_ld_pe, (size_t)E * NF));
+    TRY(dmalloc(&h->d_ld_lbuf, (size_t)E * S * 3));
+    HIP_TRY(hipMemcpy(h->d_ld_cls, su.cls.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_ld_mask, mask.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_ld_tab, su.tab.data(), su.tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_ld_qw, su.qw.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice));
+    // zeroed once: only the rows of loaded elements are ever rewritten
+    HIP_TRY(hipMemset(h->d_ld_lbuf, 0, (size_t)E * S * 3 * sizeof(double)));
+    TRY(loads_build_pressure_scale(h));
+  }
+  return 0;
+}
+extern "C" int tlfea_ancf_update_load_scale(tlfea_t10_t h, int k, double scale) {
+  if (h && h->kind == kT10) return fail("tlfea_ancf_update_load_scale: ANCF handles only (not a T10 handle)");
+  NEED_SETUP(h, "updating a load scale.");
+  if (k < 0 || k >= (int)h->ld_list.size())
+    return fail("tlfea_ancf_update_load_scale: index " + std::to_string(k) + " outside the " +
+                std::to_string(h->ld_list.size()) + " surface loads set");
+  if (!std::isfinite(scale)) return fail("tlfea_ancf_update_load_scale: the scale must be finite");
+  h->ld_list[k].scale = scale;
+  return h->ld_list[k].kind == 0 ? loads_build_traction(h) : loads_build_pressure_scale(h);
+}
+extern "C" int tlfea_get_load_forces(tlfea_t10_t h, double* f) {
+  NEED_SETUP(h, "reading load forces.");
+  if (!f) return fail("tlfea_get_load_forces: null output");
+  if (!h->loads_on()) {
+    std::fill(f, f + 3 * (size_t)h->N, 0.0);
+    return 0;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(f, h->d_ld_f, 3 * (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+extern "C" int tlfea_get_load_resultant(tlfea_t10_t h, double out[3]) {
+  NEED_SETUP(h, "reading the load resultant.");
+  if (!out) return fail("tlfea_get_load_resultant: null output");
+  std::vector<double> f((size_t)3 * h->N);
+  TRY(tlfea_get_load_forces(h, f.data()));
+  const int stride = h->kind == kT10 ? 1 : 4;  // the position coefficients, ascending
+  out[0] = out[1] = out[2] = 0.0;
+  for (int i = 0; i < h->N; i += stride)
+    for (int c = 0; c < 3; c++) out[c] += f[3 * (size_t)i + c];
+  return 0;
+}
+
 extern "C" int tlfea_t10_set_external_force(tlfea_t10_t h, const double* f, int n) {
   if (!h) return fail("null handle");
   if (n != 3 * h->N) return fail("External force vector size mismatch.");
@@ -963,6 +1188,7 @@ extern "C" int tlfea_t10_calc_mass_matrix(tlfea_t10_t h) {
   // per-element: 1 flags an assembled mass (the solvers scale by 1/h and take each element's density from its record)
   h->mass_rho0 = h->d_emat ? 1.0 : h->mat.rho0;
   h->mass_pe = h->d_emat != nullptr;
+  h->ld_const_dirty = true;  // the body force follows the mass matrix
   return 0;
 }
 
@@ -1061,6 +1287,7 @@ extern "C" int tlfea_ancf_calc_dsdu_pre(tlfea_t10_t h) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->d_ao_w, h->h_ao_w.data(), h->h_ao_w.size() * sizeof(double), hipMemcpyHostToDevice));
   }
+  TRY(loads_build_traction(h));  // the traction vector is made of the same weights
   return 0;
 }
 
@@ -1113,6 +1340,7 @@ static int ancf_mass_host(tlfea_t10_t h) {
   }
   HIP_TRY(hipMemcpy(h->d_mval, mval.data(), mval.size() * sizeof(double), hipMemcpyHostToDevice));
   h->ancf_mass = true;
+  h->ld_const_dirty = true;  // the body force follows the mass matrix
   return 0;
 }
 
@@ -2112,6 +2340,8 @@ extern "C" int tlfea_newton_set_interface(tlfea_newton_t s, const int* iface_nod
     return fail("tlfea_newton_set_interface: per-element materials are not supported on the partitioned path");
   if (s->d->obs.n > 0)
     return fail("tlfea_newton_set_interface: rigid obstacles are not supported on the partitioned path (clear them first)");
+  if (s->d->loads_on())
+    return fail("tlfea_newton_set_interface: distributed loads are not supported on the partitioned path (clear them first)");
   if (s->pmg.tried)
     return fail("tlfea_newton_set_interface: set the interface before the first linear solve (the p-multigrid hierarchy "
                 "is partitioned with it)");
@@ -2469,6 +2699,8 @@ extern "C" int tlfea_newton_set_halo(tlfea_newton_t s, const int* node_layer, in
   if (s->d->d_emat) return fail("tlfea_newton_set_halo: per-element materials are not supported on the partitioned path");
   if (s->d->obs.n > 0)
     return fail("tlfea_newton_set_halo: rigid obstacles are not supported on the partitioned path (clear them first)");
+  if (s->d->loads_on())
+    return fail("tlfea_newton_set_halo: distributed loads are not supported on the partitioned path (clear them first)");
   if (s->pmg.tried || s->ar)
     return fail("tlfea_newton_set_halo: set the halo on a fresh solver, before the first linear solve and instead of "
                 "tlfea_newton_set_interface");
@@ -3004,10 +3236,30 @@ static void launch_ancf_obstacles_tangent(tlfea_newton_t s, bool buffers_fresh) 
   launch_ancf_obstacle_tangent(s->stream, ancf_obs_view(d), s->prm.time_step, s->d_Kbuf);
 }
 
+// g -= f_load(x): the constant part is rebuilt when the mass matrix, the acceleration or a traction changed;
+// the pressure rows follow the current coefficients
+static int launch_loads_grad(tlfea_newton_t s) {
+  tlfea_t10_t d = s->d;
+  const bool has_const = d->ld_have_a || d->ld_n_trac > 0;
+  if (has_const && d->ld_const_dirty) {
+    if (d->ld_have_a && !mass_assembled(d))
+      return fail("a body acceleration is set but the mass matrix was dropped: CalcMassMatrix must run again");
+    launch_body_force(s->stream, s->N, d->inc(), d->ld_have_a ? d->d_mval : nullptr, d->kind == kT10 ? 1 : 4, d->ld_a,
+                      d->ld_n_trac > 0 ? d->d_ld_tr : nullptr, d->d_ld_fc);
+    d->ld_const_dirty = false;
+  }
+  if (d->ld_n_press > 0) launch_ancf_pressure(s->stream, ancf_load_view(d), d->d_x, d->d_y, d->d_z);
+  launch_load_gather(s->stream, s->N, d->inc(), has_const ? d->d_ld_fc : nullptr,
+                     d->ld_n_press > 0 ? d->d_ld_lbuf : nullptr, d->d_ld_f, s->d_g);
+  return 0;
+}
+
 static int eval_gradient(tlfea_newton_t s, double* norm_g) {
   tlfea_t10_t d = s->d;
   if (d->obs.n > 0 && dist_on(s))  // before any collective
     return fail("rigid obstacles are not supported on the partitioned path (clear them first)");
+  if (d->loads_on() && dist_on(s))
+    return fail("distributed loads are not supported on the partitioned path (clear them first)");
   TRY(refresh_geometry(s));
   TRY(ensure_form_for_material(s));
   const tlfea_newton_params& p = s->prm;
@@ -3039,6 +3291,7 @@ static int eval_gradient(tlfea_newton_t s, double* norm_g) {
                                  p.time_step, p.rho, s->d_g);
     }
     if (d->obs.n > 0) launch_obstacles_grad(s, s->d_g);
+    if (d->loads_on()) TRY(launch_loads_grad(s));
     HIP_TRY(hipGetLastError());
     // each rank's g holds only its own elements' forces and its share of M, f_ext, constraints on
     // partition-boundary nodes: sum the boundary entries over ranks (nothing else is exchanged)
@@ -5713,6 +5966,9 @@ extern "C" int tlfea_vbd_solve(tlfea_vbd_t a) {
   if (d->obs.n > 0)
     return fail("SyncedVBDSolver: rigid obstacles are set, and the VBD vertex solve has no contact term; use the Newton, "
                 "AdamW or Nesterov solver, or clear the obstacles");
+  if (d->loads_on())
+    return fail("SyncedVBDSolver: distributed loads are set, and the VBD vertex solve has no load term; use the Newton, "
+                "AdamW or Nesterov solver, or clear the loads");
   TRY(sync_constraints(s));
   if (!a->mass_ready && !d->is_csr_setup) TRY(tlfea_vbd_initialize_mass_diag_blocks(a));
   TRY(tlfea_vbd_initialize_coloring(a));

@@ -405,6 +405,28 @@ void launch_ancf_obstacle_gather(hipStream_t s, int N, const Incidence& inc, con
 void launch_ancf_obstacle_footprint(hipStream_t s, const AncfObsView& v, const ObstacleList& L, const double* x,
                                     const double* y, const double* z, double* pts);
 
+// Distributed loads (tlfea_set_body_acceleration, tlfea_ancf_set_surface_loads; load_kernels.hip).  No atomics.
+constexpr int kMaxLoads = 16;
+// Faces per element: shell 2, beam 4; pressure points per face P: shell 5 x 5, beam 5 x 2.
+struct AncfLoadView {
+  int E, S;
+  const int* conn;      // [S][E] coefficient ids (ElemView::conn)
+  const int* cls;       // [E] the element's (L, W, H) class
+  const double* tab;    // [n_class][faces][P][3][S]: S_a(q), dS_a/d(first face direction), dS_a/d(second)
+  const double* qw;     // [P] quadrature weight of point q
+  const int* mask;      // [E] bit f: some pressure load lists face f of the element
+  const double* pe;     // [E][faces] -(sum of scale x pressure over the loads of the face) x the face's orientation sign
+  double* lbuf;         // [E][S][3] pressure force rows (the layout of fbuf); written for elements with mask != 0 only
+};
+// fc [N][3] = sum_j M_ij a_j (+ add, may be null), a_j = a where j % stride == 0 (T10: 1, ANCF: 4); mval null: fc = add
+void launch_body_force(hipStream_t s, int N, const Incidence& inc, const double* mval, int stride, const double a[3],
+                       const double* add, double* fc);
+// lbuf rows of every element with a pressure load, from the current coefficients
+void launch_ancf_pressure(hipStream_t s, const AncfLoadView& v, const double* x, const double* y, const double* z);
+// f [N][3] = fc (may be null) + ascending-element sum of the coefficient's lbuf rows (lbuf may be null); g -= f
+void launch_load_gather(hipStream_t s, int N, const Incidence& inc, const double* fc, const double* lbuf, double* f,
+                        double* g);
+
 // Stress and energy recovery of T10 objects (tlfea_t10_calc_stress; stress_kernels.hip).  No atomics.
 // pts (null: not wanted) [E][5][6] Cauchy stress per Keast point, xx yy zz xy yz zx; erec [E][10] = volume-weighted mean
 // stress (6) | its von Mises | mean strain-energy density | mean J | reference volume V_e; contrib [4][Epad] the element's

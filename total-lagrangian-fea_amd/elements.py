@@ -7,7 +7,8 @@ import dataclasses
 
 import numpy as np
 
-from .binding import MaterialEntryC, ObstacleC, check, dp, ip, load_library
+from .binding import MaterialEntryC, ObstacleC, SurfaceLoadC, check, dp, ip, load_library
+from .loads import MAX_LOADS, FollowerPressure, SurfaceTraction, _SurfaceLoad
 from .obstacles import MAX_OBSTACLES, as_c
 
 MAX_MATERIALS = 256  # table entries per object (include/tlfea_c.h)
@@ -149,6 +150,31 @@ class GPU_FEAT10_Data:
         w = np.zeros(self.n_coef)
         check(self._lib.tlfea_t10_get_surface_weights(self._h, dp(w)))
         return w
+
+    # -- distributed loads: beside f_ext, not in it --------------------------------------------------
+    def SetGravity(self, acceleration):
+        """Body acceleration (3-vector): the load M a on the position coefficients, from the mass matrix on the device.
+        After CalcMassMatrix; follows a later CalcMassMatrix.  A zero vector removes it."""
+        a = _f64(acceleration)
+        if a.shape != (3,) or not np.all(np.isfinite(a)):
+            raise ValueError("SetGravity: the acceleration must be a finite 3-vector")
+        check(self._lib.tlfea_set_body_acceleration(self._h, dp(a)))
+
+    def ClearLoads(self):
+        """Remove the body acceleration (and, on an ANCF object, every surface load)."""
+        check(self._lib.tlfea_clear_loads(self._h))
+
+    def GetLoadForces(self):
+        """The distributed load on every coefficient (3 n_coef, the layout of f_ext) at the last gradient evaluation."""
+        f = np.zeros(3 * self.n_coef)
+        check(self._lib.tlfea_get_load_forces(self._h, dp(f)))
+        return f
+
+    def GetLoadResultant(self):
+        """Sum of the load over the position coefficients (3-vector) at the last gradient evaluation."""
+        out = np.zeros(3)
+        check(self._lib.tlfea_get_load_resultant(self._h, dp(out)))
+        return out
 
     def SetExternalForce(self, h_f_ext):
         f = _f64(h_f_ext)
@@ -487,6 +513,57 @@ class _GPU_ANCF_Data(GPU_FEAT10_Data):
         out = np.zeros(3)
         check(self._lib.tlfea_ancf_time_stress_kernels(self._h, C.c_void_p(ptr), int(bool(want_points)), int(reps), dp(out)))
         return out
+
+    # -- surface loads: dead traction and follower pressure on element faces -------------------------------
+    def _send_loads(self, loads):
+        pairs = [ld.to_c() for ld in loads]                       # the index arrays stay alive in `pairs` during the call
+        arr = (SurfaceLoadC * max(1, len(pairs)))(*[p[0] for p in pairs])
+        check(self._lib.tlfea_ancf_set_surface_loads(self._h, arr, len(pairs)))
+
+    def AddSurfaceLoad(self, load):
+        """Append a SurfaceTraction / FollowerPressure to the object's list (at most 16); returns its index.  After Setup
+        and CalcDsDuPre."""
+        if not isinstance(load, _SurfaceLoad):
+            raise ValueError(f"expected a SurfaceTraction or FollowerPressure, got {type(load).__name__}")
+        loads = getattr(self, "_loads", [])
+        if len(loads) + 1 > MAX_LOADS:
+            raise ValueError(f"at most {MAX_LOADS} surface loads per object")
+        load.check_against(self.S, self.n_elem)
+        self._send_loads(loads + [load])
+        self._loads = loads + [load]
+        return len(self._loads) - 1
+
+    def AddSurfaceTraction(self, face, elements, traction, scale=1.0):
+        """Dead traction (force per reference area, fixed direction) on one face of `elements`; returns the load's index."""
+        return self.AddSurfaceLoad(SurfaceTraction(face, elements, traction, scale))
+
+    def AddFollowerPressure(self, face, elements, pressure, scale=1.0):
+        """Pressure that follows the deformed face (positive pushes against its outward normal); returns the load's index.
+        Its load stiffness is left out of the Hessian, so Newton converges linearly in it: allow more inner iterations."""
+        return self.AddSurfaceLoad(FollowerPressure(face, elements, pressure, scale))
+
+    def SetLoadScale(self, k, scale):
+        """Change the scale factor of surface load k (ramps) without sending the load again."""
+        loads = getattr(self, "_loads", [])
+        if not 0 <= int(k) < len(loads):
+            raise ValueError(f"SetLoadScale: index {k} outside the {len(loads)} surface loads set")
+        if not np.isfinite(scale):
+            raise ValueError("SetLoadScale: the scale must be finite")
+        check(self._lib.tlfea_ancf_update_load_scale(self._h, int(k), C.c_double(scale)))
+        loads[int(k)].scale = float(scale)
+
+    def ClearLoads(self):
+        """Remove every surface load and the body acceleration."""
+        check(self._lib.tlfea_clear_loads(self._h))
+        self._loads = []
+
+    def GetLoadForces(self):
+        """The distributed load on every coefficient (3 n_coef, the layout of f_ext) at the last gradient evaluation."""
+        return super().GetLoadForces()
+
+    def GetLoadResultant(self):
+        """Sum of the load over the position coefficients 4 n (3-vector) at the last gradient evaluation."""
+        return super().GetLoadResultant()
 
     # -- rigid obstacles (DESIGN 3e'): contact at 32 sample points per element ------------------------------------------
     POINTS = 32

@@ -801,6 +801,12 @@ struct GPU_FEAT10_Data : public ElementBase {
     return Energies{o[0], o[1], o[2], o[3], o[4]};
   }
   double* GetNodalStressDevicePtr() { return tlfea_t10_nodal_stress_device_ptr(h); }
+  // distributed loads (no reference counterpart): beside f_ext, not in it.  SetGravity: the load M a on the
+  // position coefficients, from the mass matrix on the device (after CalcMassMatrix).  Status 0 = accepted.
+  int SetGravity(double ax, double ay, double az) {
+    const double a[3] = {ax, ay, az};
+    return tlfea_set_body_acceleration(h, a);
+  }
   void SetExternalForce(const tlfea::VectorXd& h_f_ext) {
     TLFEA_SOFT(tlfea_t10_set_external_force(h, h_f_ext.data(), h_f_ext.size()));
   }
@@ -953,6 +959,51 @@ struct GPU_ANCF_DataBase : public GPU_FEAT10_Data {
     if (tlfea_t10_update_linear_constraint_rhs(h, rhs.data(), rhs.size()) != 0) std::cerr << tlfea_last_error() << std::endl;
   }
   int GetConstraintMode() const { return tlfea_t10_get_constraint_mode(h); }
+  // surface loads on the ANCF kinds: a dead traction (force per reference area, fixed direction) or a
+  // follower pressure (positive pushes against the outward normal of the deformed face) on one face of a list of elements
+  // (shell: zeta = -1, +1 -> 0, 1; beam: eta = -1, +1, zeta = -1, +1 -> 0..3).  After Setup and CalcDsDuPre, at most 16.
+  // The Add calls return the load's index, or -1 when refused (tlfea_last_error() explains; the list is unchanged).
+  struct SurfaceLoadRec {
+    int kind, face;
+    double value[3], scale;
+    std::vector<int> elems;
+  };
+  std::vector<SurfaceLoadRec> loads_;  // what the object holds: the C-ABI takes the whole list
+  int AddSurfaceLoad(const SurfaceLoadRec& rec) {
+    std::vector<SurfaceLoadRec> next = loads_;
+    next.push_back(rec);
+    std::vector<tlfea_surface_load> c(next.size());
+    for (size_t k = 0; k < next.size(); k++)
+      c[k] = tlfea_surface_load{next[k].kind, next[k].face, {next[k].value[0], next[k].value[1], next[k].value[2]},
+                                next[k].scale, next[k].elems.data(), static_cast<int>(next[k].elems.size())};
+    if (tlfea_ancf_set_surface_loads(h, c.data(), static_cast<int>(c.size())) != 0) return -1;
+    loads_.swap(next);
+    return static_cast<int>(loads_.size()) - 1;
+  }
+  int AddSurfaceTraction(int face, const std::vector<int>& elements, double tx, double ty, double tz, double scale = 1.0) {
+    return AddSurfaceLoad(SurfaceLoadRec{0, face, {tx, ty, tz}, scale, elements});
+  }
+  int AddFollowerPressure(int face, const std::vector<int>& elements, double pressure, double scale = 1.0) {
+    return AddSurfaceLoad(SurfaceLoadRec{1, face, {pressure, 0.0, 0.0}, scale, elements});
+  }
+  // changes the scale factor of load k between steps (ramps) without sending the load again
+  int SetLoadScale(int k, double scale) {
+    const int rc = tlfea_ancf_update_load_scale(h, k, scale);
+    if (rc == 0) loads_[k].scale = scale;
+    return rc;
+  }
+  // removes every surface load and the body acceleration
+  int ClearLoads() {
+    loads_.clear();
+    return tlfea_clear_loads(h);
+  }
+  // the load on every coefficient (3 n_coef, the layout of f_ext) at the last gradient evaluation
+  void GetLoadForces(tlfea::VectorXd& f) {
+    f.resize(3 * n_coef);
+    TLFEA_HANDLE_ERROR(tlfea_get_load_forces(h, f.data()));
+  }
+  // its sum over the position coefficients
+  void GetLoadResultant(double out[3]) { TLFEA_HANDLE_ERROR(tlfea_get_load_resultant(h, out)); }
   // rigid obstacles on the ANCF kinds (DESIGN 3e'; no reference counterpart): contact at 32 sample points on the faces of
   // every element.  After Setup and CalcDsDuPre.  The set / update calls return the C-ABI's status (0 = accepted).
   int SetRigidObstacles(const std::vector<tlfea_obstacle>& list) {
