@@ -177,6 +177,30 @@ int tlfea_ancf_update_load_scale(tlfea_t10_t h, int k, double scale);
 int tlfea_clear_loads(tlfea_t10_t h);
 int tlfea_get_load_forces(tlfea_t10_t h, double *f);
 int tlfea_get_load_resultant(tlfea_t10_t h, double out[3]);
+/* Surface loads on the boundary faces of a T10 mesh (DESIGN 3h'), T10 handles only, after Setup.  A boundary face is a
+ * 6-node triangle that belongs to exactly one tet; the faces are numbered in ascending (element, local face) order, and
+ * this numbering is part of the interface.  get_boundary_faces: the count (null arrays: the count alone), per face its
+ * element, its local face (0..3: the face of nodes 012, 013, 023, 123) and its six node ids (nodes: 6 * n_faces; corners,
+ * then the mid-edge nodes 01 12 02), ordered so that the normal X_xi x X_eta points out of the mesh.
+ * A load applies to a list of boundary faces: kind 0, dead traction value[0..2] (force per reference area, fixed
+ * direction); kind 1, follower pressure value[0] (positive pushes against the outward normal of the deformed face),
+ * integrated at the current positions.  Both use the 6-point triangle rule of degree 4, which is exact for the pressure
+ * and for the traction on a straight-sided face.  scale multiplies the value; update_load_scale changes it between steps.
+ * At most 16 loads; several pressures on one face add.  A face outside 0..n_faces-1, the same face twice in one load, an
+ * unknown kind and a non-finite value or scale are refused.  set_surface_loads replaces the list (n = 0 removes it);
+ * tlfea_clear_loads removes it and the body acceleration; get_load_forces and get_load_resultant include these loads.
+ * The pressure load stiffness is left out of the Hessian, and tlfea_vbd_solve, tlfea_newton_set_halo and
+ * tlfea_newton_set_interface fail while loads are set, as above. */
+typedef struct {
+  int kind;          /* 0 dead traction, 1 follower pressure */
+  double value[3];   /* traction vector | pressure in value[0] */
+  double scale;      /* multiplies value */
+  const int *faces;  /* boundary-face indices */
+  int n_faces;
+} tlfea_t10_surface_load;
+int tlfea_t10_get_boundary_faces(tlfea_t10_t h, int *n_faces, int *elem, int *local_face, int *nodes);
+int tlfea_t10_set_surface_loads(tlfea_t10_t h, const tlfea_t10_surface_load *list, int n);
+int tlfea_t10_update_load_scale(tlfea_t10_t h, int k, double scale);
 /* Stress and energy recovery of T10 objects (no reference counterpart).  Works from the current positions and
  * the object's own data at any time after CalcDnDuPre; changes nothing a solver reads.  d_vel: DEVICE pointer to a
  * velocity (3N interleaved: what tlfea_*_velocity_guess_device_ptr returns) or NULL; with it a damped material's

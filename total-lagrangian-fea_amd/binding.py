@@ -76,12 +76,20 @@ class SurfaceLoadC(C.Structure):  # tlfea_surface_load
                 ("elems", c_ip), ("n_elems", C.c_int)]
 
 
+class T10SurfaceLoadC(C.Structure):  # tlfea_t10_surface_load
+    _fields_ = [("kind", C.c_int), ("value", C.c_double * 3), ("scale", C.c_double), ("faces", c_ip),
+                ("n_faces", C.c_int)]
+
+
 def _load_signatures(lib):
     """ctypes signatures of the distributed-load entry points."""
     vp, i = C.c_void_p, C.c_int
     sig = {"tlfea_set_body_acceleration": [vp, c_dp], "tlfea_ancf_set_surface_loads": [vp, C.POINTER(SurfaceLoadC), i],
            "tlfea_ancf_update_load_scale": [vp, i, C.c_double], "tlfea_clear_loads": [vp],
-           "tlfea_get_load_forces": [vp, c_dp], "tlfea_get_load_resultant": [vp, c_dp]}
+           "tlfea_get_load_forces": [vp, c_dp], "tlfea_get_load_resultant": [vp, c_dp],
+           "tlfea_t10_get_boundary_faces": [vp, c_ip, c_ip, c_ip, c_ip],
+           "tlfea_t10_set_surface_loads": [vp, C.POINTER(T10SurfaceLoadC), i],
+           "tlfea_t10_update_load_scale": [vp, i, C.c_double]}
     for name, args in sig.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int

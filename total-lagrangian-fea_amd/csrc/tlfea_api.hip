@@ -28,6 +28,7 @@
 #include "obstacle_host.h"
 #include "ancf_obstacle_host.h"
 #include "ancf_load_host.h"
+#include "t10_load_host.h"
 
 using namespace tlfea;
 
@@ -124,6 +125,13 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   double *d_ld_fc = nullptr, *d_ld_tr = nullptr, *d_ld_f = nullptr, *d_ld_lbuf = nullptr, *d_ld_tab = nullptr,
          *d_ld_qw = nullptr, *d_ld_pe = nullptr;
   int *d_ld_cls = nullptr, *d_ld_mask = nullptr;
+  // surface loads on a T10 object (DESIGN 3h'): ld_list holds boundary-face indices in `elems`; the pressure's loaded faces
+  // (ascending) own the rows of d_ld_lbuf [n][6][3], d_ld_pe [n] their effective pressure, d_ld_fnodes [n][6] their nodes,
+  // d_ld_foff / d_ld_fslot the node-to-row CSR of the gather
+  t10load::BoundaryFaces bf;
+  bool bf_built = false;
+  std::vector<int> h_ld_lf;         // the loaded faces, ascending
+  int *d_ld_fnodes = nullptr, *d_ld_foff = nullptr, *d_ld_fslot = nullptr;
   bool loads_on() const { return ld_have_a || !ld_list.empty(); }
   // stress recovery (tlfea_t10_calc_stress): allocated on first use, read by no solver
   double *d_st_pts = nullptr, *d_st_erec = nullptr, *d_st_contrib = nullptr, *d_st_nodal = nullptr,
@@ -244,7 +252,8 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_ob_res, h->d_st_pts, h->d_st_erec, h->d_st_contrib, h->d_st_nodal, h->d_st_part, h->d_st_tot,
                   h->d_st_vel, h->d_st_noff, h->d_st_nel, h->d_ao_cls, h->d_ao_touched, h->d_ao_sval, h->d_ao_w,
                   h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts, h->d_ld_fc, h->d_ld_tr, h->d_ld_f,
-                  h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask};
+                  h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask, h->d_ld_fnodes, h->d_ld_foff,
+                  h->d_ld_fslot};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -703,10 +712,11 @@ static void surface_loads_free(tlfea_t10_t h) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  for (int** p : {&h->d_ld_cls, &h->d_ld_mask}) {
+  for (int** p : {&h->d_ld_cls, &h->d_ld_mask, &h->d_ld_fnodes, &h->d_ld_foff, &h->d_ld_fslot}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
+  h->h_ld_lf.clear();
   h->ld_list.clear();
   h->ld_n_trac = h->ld_n_press = 0;
 }
@@ -728,10 +738,13 @@ static int loads_alloc_common(tlfea_t10_t h) {
   HIP_TRY(hipMemset(h->d_ld_f, 0, (size_t)3 * h->N * sizeof(double)));
   return 0;
 }
+static int t10_loads_build_traction(tlfea_t10_t h);  // the same two on the boundary faces of a T10 mesh (DESIGN 3h')
+static int t10_loads_build_pressure_scale(tlfea_t10_t h);
 // Traction vector [N][3] = sum over the traction loads (list order), their elements (list order), the element's
 // coefficients and the face's sample points (point order) of scale t w_p S_a(p): on the host, once per change.
 static int loads_build_traction(tlfea_t10_t h) {
   if (h->ld_n_trac == 0) return 0;
+  if (h->kind == kT10) return t10_loads_build_traction(h);
   TRY(ancf_points_build(h));
   const int S = h->S, E = h->E, ppf = kAncfObsPoints / ancf::load_faces(S);
   std::vector<double> tr((size_t)3 * h->N, 0.0);
@@ -756,6 +769,7 @@ static int loads_build_traction(tlfea_t10_t h) {
 // pe [E][faces] = -(orientation sign) x sum over the pressure loads (list order) of scale x pressure
 static int loads_build_pressure_scale(tlfea_t10_t h) {
   if (h->ld_n_press == 0) return 0;
+  if (h->kind == kT10) return t10_loads_build_pressure_scale(h);
   const int NF = ancf::load_faces(h->S);
   std::vector<double> pe((size_t)h->E * NF, 0.0);
   for (const auto& L : h->ld_list)
@@ -877,6 +891,148 @@ extern "C" int tlfea_ancf_update_load_scale(tlfea_t10_t h, int k, double scale) 
   h->ld_list[k].scale = scale;
   return h->ld_list[k].kind == 0 ? loads_build_traction(h) : loads_build_pressure_scale(h);
 }
+
+// ---- surface loads on the boundary faces of a T10 mesh (DESIGN 3h') ---------------------------------------------------------
+#define NEED_T10_LOADS(h, what) \
+  if ((h) && (h)->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)")
+static void boundary_faces_build(tlfea_t10_t h) {
+  if (h->bf_built) return;
+  h->bf = t10load::boundary_faces(h->E, h->N, h->h_conn, h->h_X0);
+  h->bf_built = true;
+}
+// Traction vector [N][3] = sum over the traction loads (list order), their faces (list order), the face's nodes and the
+// points of the rule (point order) of scale t w_q N_a(q) |X_xi x X_eta|(q): on the host, once per change.
+static int t10_loads_build_traction(tlfea_t10_t h) {
+  std::vector<double> tr((size_t)3 * h->N, 0.0);
+  for (const auto& L : h->ld_list) {
+    if (L.kind != 0) continue;
+    for (int k : L.elems) {
+      const int* nd = &h->bf.nodes[(size_t)k * 6];
+      double w[6];
+      t10load::traction_weights(nd, h->N, h->h_X0, w);
+      for (int a = 0; a < 6; a++)
+        for (int c = 0; c < 3; c++) tr[3 * (size_t)nd[a] + c] += L.scale * L.value[c] * w[a];
+    }
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h->d_ld_tr, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->ld_const_dirty = true;
+  return 0;
+}
+// pe [loaded faces] = -(sum over the pressure loads (list order) of scale x pressure): the nodes are ordered outward
+static int t10_loads_build_pressure_scale(tlfea_t10_t h) {
+  std::vector<double> pf((size_t)h->bf.count(), 0.0);
+  for (const auto& L : h->ld_list)
+    if (L.kind == 1)
+      for (int k : L.elems) pf[k] += L.scale * L.value[0];
+  std::vector<double> pe(h->h_ld_lf.size());
+  for (size_t i = 0; i < pe.size(); i++) pe[i] = -pf[h->h_ld_lf[i]];
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h->d_ld_pe, pe.data(), pe.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+static T10LoadView t10_load_view(tlfea_t10_t h) {
+  return T10LoadView{(int)h->h_ld_lf.size(), h->d_ld_fnodes, h->d_ld_pe, h->d_ld_lbuf};
+}
+
+extern "C" int tlfea_t10_get_boundary_faces(tlfea_t10_t h, int* n_faces, int* elem, int* local_face, int* nodes) {
+  NEED_T10_LOADS(h, "tlfea_t10_get_boundary_faces");
+  NEED_SETUP(h, "reading boundary faces.");
+  if (!n_faces) return fail("tlfea_t10_get_boundary_faces: null count");
+  boundary_faces_build(h);
+  *n_faces = h->bf.count();
+  if (elem) std::copy(h->bf.elem.begin(), h->bf.elem.end(), elem);
+  if (local_face) std::copy(h->bf.local_face.begin(), h->bf.local_face.end(), local_face);
+  if (nodes) std::copy(h->bf.nodes.begin(), h->bf.nodes.end(), nodes);
+  return 0;
+}
+extern "C" int tlfea_t10_set_surface_loads(tlfea_t10_t h, const tlfea_t10_surface_load* list, int n) {
+  NEED_T10_LOADS(h, "tlfea_t10_set_surface_loads");
+  NEED_SETUP(h, "setting surface loads.");
+  if (n < 0 || n > kMaxLoads)
+    return fail("tlfea_t10_set_surface_loads: n must be in 0.." + std::to_string(kMaxLoads) + ", got " + std::to_string(n));
+  if (n > 0 && !list) return fail("tlfea_t10_set_surface_loads: null list");
+  boundary_faces_build(h);
+  const int F = h->bf.count();
+  std::vector<tlfea_t10_s::SurfaceLoad> fresh((size_t)n);
+  std::vector<char> seen;
+  for (int k = 0; k < n; k++) {
+    const tlfea_t10_surface_load& L = list[k];
+    const std::string who = "tlfea_t10_set_surface_loads: load " + std::to_string(k) + ": ";
+    if (L.kind != 0 && L.kind != 1) return fail(who + "kind must be 0 (traction) or 1 (pressure), got " + std::to_string(L.kind));
+    for (int c = 0; c < (L.kind == 0 ? 3 : 1); c++)
+      if (!std::isfinite(L.value[c])) return fail(who + "the value must be finite");
+    if (!std::isfinite(L.scale)) return fail(who + "the scale must be finite");
+    if (L.n_faces <= 0 || !L.faces) return fail(who + "empty face list");
+    seen.assign((size_t)F, 0);
+    for (int i = 0; i < L.n_faces; i++) {
+      const int f = L.faces[i];
+      if (f < 0 || f >= F) return fail(who + "face " + std::to_string(f) + " outside 0.." + std::to_string(F - 1));
+      if (seen[f]) return fail(who + "face " + std::to_string(f) + " is listed twice");
+      seen[f] = 1;
+    }
+    fresh[k].kind = L.kind;
+    fresh[k].face = -1;
+    fresh[k].scale = L.scale;
+    for (int c = 0; c < 3; c++) fresh[k].value[c] = L.kind == 0 || c == 0 ? L.value[c] : 0.0;
+    fresh[k].elems.assign(L.faces, L.faces + L.n_faces);
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  surface_loads_free(h);
+  h->ld_const_dirty = true;
+  if (n == 0) {
+    if (!h->loads_on()) loads_free(h);
+    return 0;
+  }
+  TRY(loads_alloc_common(h));
+  h->ld_list.swap(fresh);
+  for (const auto& L : h->ld_list) (L.kind == 0 ? h->ld_n_trac : h->ld_n_press)++;
+  if (h->ld_n_trac > 0) {
+    TRY(dmalloc(&h->d_ld_tr, (size_t)3 * h->N));
+    TRY(loads_build_traction(h));
+  }
+  if (h->ld_n_press > 0) {
+    // the loaded faces, ascending; the rows of a node in ascending (loaded face, local node) order
+    std::vector<char> loaded((size_t)F, 0);
+    for (const auto& L : h->ld_list)
+      if (L.kind == 1)
+        for (int f : L.elems) loaded[f] = 1;
+    for (int f = 0; f < F; f++)
+      if (loaded[f]) h->h_ld_lf.push_back(f);
+    const size_t nlf = h->h_ld_lf.size();
+    std::vector<int> fnodes(nlf * 6), off((size_t)h->N + 1, 0), slot(nlf * 6);
+    for (size_t i = 0; i < nlf; i++)
+      for (int a = 0; a < 6; a++) {
+        fnodes[i * 6 + a] = h->bf.nodes[(size_t)h->h_ld_lf[i] * 6 + a];
+        off[fnodes[i * 6 + a] + 1]++;
+      }
+    for (int i = 0; i < h->N; i++) off[i + 1] += off[i];
+    std::vector<int> fill(off.begin(), off.end() - 1);
+    for (size_t r = 0; r < nlf * 6; r++) slot[fill[fnodes[r]]++] = (int)r;
+    TRY(dmalloc(&h->d_ld_fnodes, nlf * 6));
+    TRY(dmalloc(&h->d_ld_foff, (size_t)h->N + 1));
+    TRY(dmalloc(&h->d_ld_fslot, nlf * 6));
+    TRY(dmalloc(&h->d_ld_pe, nlf));
+    TRY(dmalloc(&h->d_ld_lbuf, nlf * 18));
+    HIP_TRY(hipMemcpy(h->d_ld_fnodes, fnodes.data(), fnodes.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_ld_foff, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_ld_fslot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(h->d_ld_lbuf, 0, nlf * 18 * sizeof(double)));
+    TRY(loads_build_pressure_scale(h));
+  }
+  return 0;
+}
+extern "C" int tlfea_t10_update_load_scale(tlfea_t10_t h, int k, double scale) {
+  NEED_T10_LOADS(h, "tlfea_t10_update_load_scale");
+  NEED_SETUP(h, "updating a load scale.");
+  if (k < 0 || k >= (int)h->ld_list.size())
+    return fail("tlfea_t10_update_load_scale: index " + std::to_string(k) + " outside the " +
+                std::to_string(h->ld_list.size()) + " surface loads set");
+  if (!std::isfinite(scale)) return fail("tlfea_t10_update_load_scale: the scale must be finite");
+  h->ld_list[k].scale = scale;
+  return h->ld_list[k].kind == 0 ? loads_build_traction(h) : loads_build_pressure_scale(h);
+}
+
 extern "C" int tlfea_get_load_forces(tlfea_t10_t h, double* f) {
   NEED_SETUP(h, "reading load forces.");
   if (!f) return fail("tlfea_get_load_forces: null output");
@@ -3248,8 +3404,15 @@ static int launch_loads_grad(tlfea_newton_t s) {
                       d->ld_n_trac > 0 ? d->d_ld_tr : nullptr, d->d_ld_fc);
     d->ld_const_dirty = false;
   }
-  if (d->ld_n_press > 0) launch_ancf_pressure(s->stream, ancf_load_view(d), d->d_x, d->d_y, d->d_z);
-  launch_load_gather(s->stream, s->N, d->inc(), has_const ? d->d_ld_fc : nullptr,
+  Incidence inc = d->inc();
+  if (d->ld_n_press > 0 && d->kind == kT10) {  // rows of the loaded boundary faces, through their own node-to-row CSR
+    launch_t10_pressure(s->stream, t10_load_view(d), d->d_x, d->d_y, d->d_z);
+    inc.n2e_off = d->d_ld_foff;
+    inc.n2e = d->d_ld_fslot;
+  } else if (d->ld_n_press > 0) {
+    launch_ancf_pressure(s->stream, ancf_load_view(d), d->d_x, d->d_y, d->d_z);
+  }
+  launch_load_gather(s->stream, s->N, inc, has_const ? d->d_ld_fc : nullptr,
                      d->ld_n_press > 0 ? d->d_ld_lbuf : nullptr, d->d_ld_f, s->d_g);
   return 0;
 }

@@ -423,6 +423,16 @@ void launch_body_force(hipStream_t s, int N, const Incidence& inc, const double*
                        const double* add, double* fc);
 // lbuf rows of every element with a pressure load, from the current coefficients
 void launch_ancf_pressure(hipStream_t s, const AncfLoadView& v, const double* x, const double* y, const double* z);
+// Follower pressure on the boundary faces of a T10 mesh (tlfea_t10_set_surface_loads, DESIGN 3h'): the LOADED faces only,
+// in ascending face order.  The gather is launch_load_gather with an Incidence whose n2e_off / n2e are the node-to-slot
+// CSR of fbuf (slot = loaded face * 6 + local node, ascending per node).
+struct T10LoadView {
+  int n_faces;          // loaded faces
+  const int* nodes;     // [n_faces][6] node ids, ordered outward (corners, then the mid-edge nodes 01 12 02)
+  const double* pe;     // [n_faces] -(sum of scale x pressure over the loads of the face)
+  double* fbuf;         // [n_faces][6][3] pressure force rows
+};
+void launch_t10_pressure(hipStream_t s, const T10LoadView& v, const double* x, const double* y, const double* z);
 // f [N][3] = fc (may be null) + ascending-element sum of the coefficient's lbuf rows (lbuf may be null); g -= f
 void launch_load_gather(hipStream_t s, int N, const Incidence& inc, const double* fc, const double* lbuf, double* f,
                         double* g);

@@ -7,8 +7,8 @@ import dataclasses
 
 import numpy as np
 
-from .binding import MaterialEntryC, ObstacleC, SurfaceLoadC, check, dp, ip, load_library
-from .loads import MAX_LOADS, FollowerPressure, SurfaceTraction, _SurfaceLoad
+from .binding import MaterialEntryC, ObstacleC, SurfaceLoadC, T10SurfaceLoadC, check, dp, ip, load_library
+from .loads import MAX_LOADS, BoundaryFaces, FaceLoad, FollowerPressure, SurfaceTraction, _SurfaceLoad
 from .obstacles import MAX_OBSTACLES, as_c
 
 MAX_MATERIALS = 256  # table entries per object (include/tlfea_c.h)
@@ -66,6 +66,7 @@ class GPU_FEAT10_Data:
         x, y, z = _f64(h_x12), _f64(h_y12), _f64(h_z12)
         assert x.size == y.size == z.size == self.n_coef
         check(self._lib.tlfea_t10_setup(self._h, dp(qx), dp(qy), dp(qz), dp(qw), dp(x), dp(y), dp(z), ip(conn_cm)))
+        self._X0 = np.stack([x, y, z], axis=1)                    # reference geometry of GetBoundaryFaces
 
     # -- setters --------------------------------------------------------------------------------
     def SetDensity(self, rho0):
@@ -161,8 +162,70 @@ class GPU_FEAT10_Data:
         check(self._lib.tlfea_set_body_acceleration(self._h, dp(a)))
 
     def ClearLoads(self):
-        """Remove the body acceleration (and, on an ANCF object, every surface load)."""
+        """Remove the body acceleration and every surface load."""
         check(self._lib.tlfea_clear_loads(self._h))
+        self._face_loads = []
+
+    # -- surface loads on the boundary faces of a T10 mesh (DESIGN 3h') ------------------------------------------------
+    def _t10_only(self, what):
+        if self.S != 10:
+            raise ValueError(f"{what}: T10 objects only (an ANCF object takes AddSurfaceTraction / AddFollowerPressure)")
+
+    def GetBoundaryFaces(self):
+        """The faces that belong to one tet only, in ascending (element, local face) order: elem (F), local_face (F),
+        nodes (F, 6: corners, then the mid-edge nodes 01 12 02, ordered so that the normal points out of the mesh), and of
+        the corner triangle in the reference configuration centroid (F, 3), outward unit normal (F, 3) and area (F).
+        Select faces with numpy, e.g. np.nonzero(bf.normal[:, 2] > 0.99)[0]."""
+        self._t10_only("GetBoundaryFaces")
+        n = C.c_int()
+        check(self._lib.tlfea_t10_get_boundary_faces(self._h, C.byref(n), None, None, None))
+        elem, lf = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        nodes = np.zeros((n.value, 6), dtype=np.int32)
+        check(self._lib.tlfea_t10_get_boundary_faces(self._h, C.byref(n), ip(elem), ip(lf), ip(nodes)))
+        X = self._X0                                              # the coordinates handed to Setup
+        a, b, c = X[nodes[:, 0]], X[nodes[:, 1]], X[nodes[:, 2]]
+        nrm = np.cross(b - a, c - a)
+        ln = np.linalg.norm(nrm, axis=1)
+        self._n_boundary_faces = int(n.value)
+        return BoundaryFaces(elem, lf, nodes, (a + b + c) / 3.0, nrm / ln[:, None], 0.5 * ln)
+
+    def _add_face_load(self, load):
+        self._t10_only("a face load")
+        loads = getattr(self, "_face_loads", [])
+        if len(loads) + 1 > MAX_LOADS:
+            raise ValueError(f"at most {MAX_LOADS} surface loads per object")
+        if getattr(self, "_n_boundary_faces", None) is None:
+            n = C.c_int()
+            check(self._lib.tlfea_t10_get_boundary_faces(self._h, C.byref(n), None, None, None))
+            self._n_boundary_faces = int(n.value)
+        load.check_against(self._n_boundary_faces)
+        pairs = [ld.to_c() for ld in loads + [load]]              # the index arrays stay alive in `pairs` during the call
+        arr = (T10SurfaceLoadC * len(pairs))(*[p[0] for p in pairs])
+        check(self._lib.tlfea_t10_set_surface_loads(self._h, arr, len(pairs)))
+        self._face_loads = loads + [load]
+        return len(self._face_loads) - 1
+
+    def AddFaceTraction(self, faces, traction, scale=1.0):
+        """Dead traction (3-vector, force per reference area, fixed direction) on the boundary faces `faces` (indices into
+        GetBoundaryFaces); returns the load's index."""
+        return self._add_face_load(FaceLoad(0, faces, traction, scale))
+
+    def AddFacePressure(self, faces, pressure, scale=1.0):
+        """Pressure that follows the deformed boundary faces `faces` (positive pushes against the outward normal);
+        returns the load's index.  Its load stiffness is left out of the Hessian, so Newton converges linearly in it:
+        allow more inner iterations."""
+        return self._add_face_load(FaceLoad(1, faces, pressure, scale))
+
+    def SetFaceLoadScale(self, k, scale):
+        """Change the scale factor of face load k (ramps) without sending the load again."""
+        self._t10_only("SetFaceLoadScale")
+        loads = getattr(self, "_face_loads", [])
+        if not 0 <= int(k) < len(loads):
+            raise ValueError(f"SetFaceLoadScale: index {k} outside the {len(loads)} face loads set")
+        if not np.isfinite(scale):
+            raise ValueError("SetFaceLoadScale: the scale must be finite")
+        check(self._lib.tlfea_t10_update_load_scale(self._h, int(k), C.c_double(scale)))
+        loads[int(k)].scale = float(scale)
 
     def GetLoadForces(self):
         """The distributed load on every coefficient (3 n_coef, the layout of f_ext) at the last gradient evaluation."""

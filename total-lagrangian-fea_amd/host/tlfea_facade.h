@@ -807,6 +807,80 @@ struct GPU_FEAT10_Data : public ElementBase {
     const double a[3] = {ax, ay, az};
     return tlfea_set_body_acceleration(h, a);
   }
+  // surface loads on the boundary faces of a T10 mesh (DESIGN 3h'): the faces that belong to one tet only, in ascending
+  // (element, local face) order, their six nodes ordered outward; of the corner triangle in the reference configuration
+  // the centroid, the outward unit normal and the area.  x0, y0, z0: the coordinates handed to Setup.
+  struct BoundaryFaces {
+    std::vector<int> elem, local_face, nodes;       // [F], [F], [F][6]
+    std::vector<double> centroid, normal, area;     // [F][3], [F][3], [F]
+    int count() const { return static_cast<int>(elem.size()); }
+  };
+  BoundaryFaces GetBoundaryFaces(const tlfea::VectorXd& x0, const tlfea::VectorXd& y0, const tlfea::VectorXd& z0) {
+    BoundaryFaces b;
+    int n = 0;
+    TLFEA_HANDLE_ERROR(tlfea_t10_get_boundary_faces(h, &n, nullptr, nullptr, nullptr));
+    b.elem.resize(n), b.local_face.resize(n), b.nodes.resize(6 * static_cast<size_t>(n));
+    TLFEA_HANDLE_ERROR(tlfea_t10_get_boundary_faces(h, &n, b.elem.data(), b.local_face.data(), b.nodes.data()));
+    b.centroid.resize(3 * static_cast<size_t>(n)), b.normal.resize(3 * static_cast<size_t>(n)), b.area.resize(n);
+    for (int k = 0; k < n; k++) {
+      double p[3][3];
+      for (int c = 0; c < 3; c++) {
+        const int i = b.nodes[6 * static_cast<size_t>(k) + c];
+        p[c][0] = x0(i), p[c][1] = y0(i), p[c][2] = z0(i);
+      }
+      const double u[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
+      const double v[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
+      const double cr[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+      const double len = std::sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
+      for (int d = 0; d < 3; d++) {
+        b.centroid[3 * static_cast<size_t>(k) + d] = (p[0][d] + p[1][d] + p[2][d]) / 3.0;
+        b.normal[3 * static_cast<size_t>(k) + d] = cr[d] / len;
+      }
+      b.area[k] = 0.5 * len;
+    }
+    return b;
+  }
+  // The Add calls return the load's index, or -1 when refused (tlfea_last_error() explains; the list is unchanged).
+  struct FaceLoadRec {
+    int kind;
+    double value[3], scale;
+    std::vector<int> faces;
+  };
+  std::vector<FaceLoadRec> face_loads_;  // what the object holds: the C-ABI takes the whole list
+  int AddFaceLoad(const FaceLoadRec& rec) {
+    std::vector<FaceLoadRec> next = face_loads_;
+    next.push_back(rec);
+    std::vector<tlfea_t10_surface_load> c(next.size());
+    for (size_t k = 0; k < next.size(); k++)
+      c[k] = tlfea_t10_surface_load{next[k].kind, {next[k].value[0], next[k].value[1], next[k].value[2]}, next[k].scale,
+                                    next[k].faces.data(), static_cast<int>(next[k].faces.size())};
+    if (tlfea_t10_set_surface_loads(h, c.data(), static_cast<int>(c.size())) != 0) return -1;
+    face_loads_.swap(next);
+    return static_cast<int>(face_loads_.size()) - 1;
+  }
+  int AddFaceTraction(const std::vector<int>& faces, double tx, double ty, double tz, double scale = 1.0) {
+    return AddFaceLoad(FaceLoadRec{0, {tx, ty, tz}, scale, faces});
+  }
+  int AddFacePressure(const std::vector<int>& faces, double pressure, double scale = 1.0) {
+    return AddFaceLoad(FaceLoadRec{1, {pressure, 0.0, 0.0}, scale, faces});
+  }
+  // changes the scale factor of face load k between steps (ramps) without sending the load again
+  int SetFaceLoadScale(int k, double scale) {
+    const int rc = tlfea_t10_update_load_scale(h, k, scale);
+    if (rc == 0) face_loads_[k].scale = scale;
+    return rc;
+  }
+  // removes every face load and the body acceleration
+  int ClearLoads() {
+    face_loads_.clear();
+    return tlfea_clear_loads(h);
+  }
+  // the load on every node (3 n_coef, the layout of f_ext) at the last gradient evaluation, and its sum
+  void GetLoadForces(tlfea::VectorXd& f) {
+    f.resize(3 * n_coef);
+    TLFEA_HANDLE_ERROR(tlfea_get_load_forces(h, f.data()));
+  }
+  void GetLoadResultant(double out[3]) { TLFEA_HANDLE_ERROR(tlfea_get_load_resultant(h, out)); }
   void SetExternalForce(const tlfea::VectorXd& h_f_ext) {
     TLFEA_SOFT(tlfea_t10_set_external_force(h, h_f_ext.data(), h_f_ext.size()));
   }

@@ -2,12 +2,15 @@
 direction) and a follower pressure (normal to the deformed face), each on one face of a list of elements.  Hand them to
 GPU_ANCF3243_Data / GPU_ANCF3443_Data.AddSurfaceTraction / AddFollowerPressure, or build the objects here and pass them
 to AddSurfaceLoad; SetLoadScale ramps one between steps.  Faces: shell zeta = -1, +1 -> 0, 1; beam eta = -1, +1,
-zeta = -1, +1 -> 0..3.  Every value is checked here, before the C-ABI (which checks them again)."""
+zeta = -1, +1 -> 0..3.  A T10 mesh takes the same two loads on a list of its boundary faces (DESIGN 3h',
+GPU_FEAT10_Data.GetBoundaryFaces / AddFaceTraction / AddFacePressure): FaceLoad below.  Every value is checked here, before
+the C-ABI (which checks them again)."""
+import collections
 import math
 
 import numpy as np
 
-from .binding import SurfaceLoadC, ip
+from .binding import SurfaceLoadC, T10SurfaceLoadC, ip
 
 MAX_LOADS = 16  # surface loads per element object (include/tlfea_c.h)
 FACES = {8: 4, 16: 2}  # faces that can carry a load, by shape functions per element (beam, shell)
@@ -85,3 +88,40 @@ class FollowerPressure(_SurfaceLoad):
 
     def value3(self):
         return (self.pressure, 0.0, 0.0)
+
+
+BoundaryFaces = collections.namedtuple("BoundaryFaces", "elem local_face nodes centroid normal area")
+
+
+class FaceLoad:
+    """A dead traction (kind 0, 3-vector) or a follower pressure (kind 1, scalar) on boundary faces of a T10 mesh."""
+
+    def __init__(self, kind, faces, value, scale=1.0):
+        f = np.asarray(faces)
+        if f.ndim != 1 or f.size == 0:
+            raise ValueError("a face load needs a non-empty 1-D list of boundary-face indices")
+        if not np.issubdtype(f.dtype, np.integer):
+            raise ValueError("boundary-face indices must be integers")
+        if f.min() < 0:
+            raise ValueError(f"boundary-face index {int(f.min())} is negative")
+        if np.unique(f).size != f.size:
+            raise ValueError("the same boundary face is listed twice in one load")
+        self.kind, self.faces = int(kind), np.ascontiguousarray(f, dtype=np.int32)
+        if self.kind == 0:
+            t = np.asarray(value, dtype=np.float64)
+            if t.shape != (3,) or not np.all(np.isfinite(t)):
+                raise ValueError("traction must be a finite 3-vector")
+            self.value = tuple(float(c) for c in t)
+        elif self.kind == 1:
+            self.value = (_finite(value, "pressure"), 0.0, 0.0)
+        else:
+            raise ValueError(f"kind must be 0 (traction) or 1 (pressure), got {kind!r}")
+        self.scale = _finite(scale, "scale")
+
+    def check_against(self, n_faces):
+        if self.faces.max() >= n_faces:
+            raise ValueError(f"boundary-face index {int(self.faces.max())} outside 0..{n_faces - 1}")
+
+    def to_c(self):
+        """(struct, the array it points into: keep it alive as long as the struct)"""
+        return T10SurfaceLoadC(self.kind, self.value, self.scale, ip(self.faces), int(self.faces.size)), self.faces
