@@ -144,6 +144,41 @@ int tlfea_ancf_get_obstacle_forces(tlfea_t10_t h, double *f);
 int tlfea_ancf_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]);
 int tlfea_ancf_get_surface_points(tlfea_t10_t h, double *w);
 int tlfea_ancf_retrieve_contact_points(tlfea_t10_t h, double *out);
+/* Field obstacles (no reference counterpart; DESIGN 3e''), any handle: a rigid obstacle given as a regular grid of
+ * signed-distance samples (negative inside the body) with a rigid pose, in implicit contact with T10 surface nodes and
+ * ANCF sample points through the model of the analytic obstacles, the interpolated gap phi in the place of the distance
+ * and its gradient G in the place of the normal: force kappa w <-phi> G, Hessian block kappa w G G^T, friction from
+ * G / |G| and kappa w <-phi> |G| at the start of the step.  values[k]: nx * ny * nz doubles, V[(iz * ny + iy) * nx + ix]
+ * at origin + spacing * (ix, iy, iz) in the obstacle's frame; pos and rot (row-major, frame -> world) place the frame.
+ * Interpolation is the uniform quadratic B-spline (C1); a point is covered iff 0.5 <= (s_a - origin_a) / spacing <=
+ * n_a - 1.5 on every axis, s = rot^T (x - pos), and an obstacle contributes exactly nothing to a point it does not cover.
+ * Accepted only if every sample is finite and every sample of the two outermost layers of each axis is > 0 (a closed body
+ * well inside its grid: n_a >= 5; at most 2^27 samples), rot is orthonormal to 1e-12 with determinant +1, spacing > 0.
+ * The samples are copied to the device; a call that fails leaves the previous field list as it was.
+ * Analytic and field obstacles together number at most 16; each list keeps its own
+ * index space, setting or clearing one leaves the other in place, and tlfea_*_get_obstacle_forces returns the total of
+ * both.  After Setup (ANCF: and CalcDsDuPre).  The refusals of the analytic obstacles apply (VBD, halo, interface).
+ * update: pose, vel, stiffness, friction, eps_v of field k; the grid must be the stored one and the samples are kept.
+ * get_field_obstacle_resultant: field k's force on the mesh (out[0..2]) and its nodes / sample points in contact (out[3]).
+ * tlfea_sdf_from_triangles (no handle): the signed distance of the closed, consistently oriented triangle surface
+ * (verts [n_verts][3], tris [n_tris][3]) at the nx * ny * nz grid points, computed on the device into `values`; negative
+ * inside, for either orientation.  At most 2^24 triangles.  Refuses indices out of range, a triangle of zero area and a surface some directed edge
+ * of which does not occur exactly once with its reverse exactly once. */
+typedef struct {
+  int nx, ny, nz;
+  double origin[3];
+  double spacing;
+  double pos[3];
+  double rot[9];
+  double vel[3];
+  double stiffness, friction, eps_v;
+} tlfea_field_obstacle;
+int tlfea_set_field_obstacles(tlfea_t10_t h, const tlfea_field_obstacle *list, const double *const *values, int n);
+int tlfea_update_field_obstacle(tlfea_t10_t h, int k, const tlfea_field_obstacle *o);
+int tlfea_clear_field_obstacles(tlfea_t10_t h);
+int tlfea_get_field_obstacle_resultant(tlfea_t10_t h, int k, double out[4]);
+int tlfea_sdf_from_triangles(const double *verts, int n_verts, const int *tris, int n_tris, int nx, int ny, int nz,
+                             const double origin[3], double spacing, double *values);
 /* Distributed loads (no reference counterpart).  They live beside f_ext, not in it: every gradient evaluation
  * (Newton, direct Newton, AdamW, Nesterov) does g -= f_load(x), and tlfea_t10_set_external_force / retrieve_external_force
  * keep their meaning.  Nothing is allocated or launched while no load is set.

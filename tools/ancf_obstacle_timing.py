@@ -6,6 +6,8 @@ contact kernels run inside two stages -- the points and gather kernels in "grad"
 -- so their cost is the difference of those stages between the two runs.  The tangent kernel is reported against the
 bytes it moves (136 pairs x 72 bytes each way plus 1.5 kB of C_p per touched shell).  The sequence fixes three Newton
 iterations per step in both runs; touched elements are counted after the warm-up and at the end.
+A third run adds a field obstacle far above the plate beside the floor (DESIGN 3e''): it covers no point, so the floor's
+work is the same, and the difference to the second run is the cost of the kernels' field instantiations.
 
     python tools/ancf_obstacle_timing.py [--steps 20] [--configs D] | tee profiles/r10_ancf_obstacle_timing.txt"""
 import argparse
@@ -25,7 +27,7 @@ ELEM = ("residual", "grad", "tangent_blocks", "assemble_rows")
 HBM = 6.29e12  # bytes/s: the measured float4-copy rate of one MI355X
 
 
-def run(w, with_floor, steps):
+def run(w, with_floor, steps, with_field=False):
     d, _ = wl.make_engine(tl, w, with_solver=False)
     touched = 0
     if with_floor:
@@ -33,6 +35,12 @@ def run(w, with_floor, steps):
         xc = 0.5 * w["X"][0::4, 0].max()
         n = np.array([-2e-4, 0.0, 1.0])
         d.SetRigidObstacles([tl.RigidPlane([xc, 0.0, -H / 2], n / np.linalg.norm(n), 1e3)])
+    if with_field:
+        # a field far above the plate beside the floor (DESIGN 3e''): it touches nothing, so the floor's work is the same,
+        # but the list holds a field and the launches take the kernels' field instantiations
+        zc = w["X"][0::4, 2].max() + 100.0
+        d.SetFieldObstacles([tl.RigidField.from_function(lambda p: np.linalg.norm(p - [xc, 0.0, zc], axis=-1) - 1.0,
+                                                         [xc - 3.0, -3.0, zc - 3.0], [xc + 3.0, 3.0, zc + 3.0], 0.5, 1e3)])
     s = tl.SyncedNewtonSolver(d, d.get_n_constraint())
     s.Setup()
     s.SetParameters(tl.SyncedNewtonParams(*w["params"]))
@@ -94,8 +102,9 @@ if __name__ == "__main__":
         E = w["conn"].shape[0]
         S = 16 if w["kind"] == 3443 else 8
         res = {}
-        for mode in ("none", "floor"):
-            r = res[mode] = run(w, mode == "floor", a.steps)
+        modes = ("none", "floor") + (("floor+field",) if hasattr(tl, "RigidField") else ())
+        for mode in modes:
+            r = res[mode] = run(w, mode != "none", a.steps, mode == "floor+field")
             print(f"{mode}: config={cfg} elements={E} touched_elements={r['touched0']}..{r['touched']} "
                   f"(after warm-up..at the end) points_in_contact={r['active']} "
                   f"grad_stage_ms={r['grad_ms']:.3f} assembly_stage_ms={r['asm_ms']:.3f} element_stage_ms={r['elem_ms']:.3f} "
@@ -112,3 +121,8 @@ if __name__ == "__main__":
               f"kernels/newton_iteration={(d_grad + d_asm) / n['newton_ms']:.4f} "
               f"newton_iteration {p['newton_ms'] / n['newton_ms']:.3f}x cg_iterations {n['cg']:.0f} -> {p['cg']:.0f}",
               flush=True)
+        if "floor+field" in res:
+            f = res["floor+field"]
+            print(f"floor+field - floor: config={cfg} grad_stage_ms {f['grad_ms'] - p['grad_ms']:+.3f} (the points kernel's field "
+                  f"instantiation, 3 waves per SIMD instead of 4) assembly_stage_ms {f['asm_ms'] - p['asm_ms']:+.3f} "
+                  f"newton_iteration {f['newton_ms'] / p['newton_ms']:.4f}x", flush=True)

@@ -13,13 +13,13 @@ from .elements import ElementMaterial, GPU_ANCF3243_Data, GPU_ANCF3443_Data, GPU
 from .solvers import (SyncedNewtonParams, SyncedNewtonSolver, LinSolveOpts, SyncedAdamWNocoopParams,  # noqa: F401
                       SyncedAdamWNocoopSolver, SyncedAdamWSolver, SyncedAdamWParams, SyncedNesterovParams, SyncedNesterovSolver, SyncedVBDParams,
                       SyncedVBDSolver)
-from .obstacles import RigidPlane, RigidSphere  # noqa: F401
+from .obstacles import RigidField, RigidPlane, RigidSphere  # noqa: F401
 from .loads import FollowerPressure, SurfaceTraction  # noqa: F401
 from . import mesh_utils, quadrature  # noqa: F401
 from .mesh_manager import MeshManager  # noqa: F401
 from .contact import (CollisionSystemInput, CollisionSystemParams, ContactPatch,  # noqa: F401
                       HydroelasticPatchCollisionSystem)
 
-__all__ = ["GPU_FEAT10_Data", "ElementMaterial", "RigidPlane", "RigidSphere", "SurfaceTraction", "FollowerPressure", "GPU_ANCF3243_Data", "GPU_ANCF3443_Data", "SyncedNewtonSolver", "SyncedNewtonParams", "LinSolveOpts", "SyncedAdamWNocoopSolver", "SyncedAdamWNocoopParams", "SyncedAdamWSolver", "SyncedAdamWParams", "SyncedNesterovSolver", "SyncedNesterovParams", "SyncedVBDSolver", "SyncedVBDParams", "mesh_utils", "MeshManager", "HydroelasticPatchCollisionSystem",
+__all__ = ["GPU_FEAT10_Data", "ElementMaterial", "RigidPlane", "RigidSphere", "RigidField", "SurfaceTraction", "FollowerPressure", "GPU_ANCF3243_Data", "GPU_ANCF3443_Data", "SyncedNewtonSolver", "SyncedNewtonParams", "LinSolveOpts", "SyncedAdamWNocoopSolver", "SyncedAdamWNocoopParams", "SyncedAdamWSolver", "SyncedAdamWParams", "SyncedNesterovSolver", "SyncedNesterovParams", "SyncedVBDSolver", "SyncedVBDParams", "mesh_utils", "MeshManager", "HydroelasticPatchCollisionSystem",
            "CollisionSystemInput", "CollisionSystemParams", "ContactPatch",
            "quadrature", "load_library", "device_count", "TlfeaError", "LIB_PATH", "exported_symbols"]

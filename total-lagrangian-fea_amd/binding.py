@@ -71,6 +71,12 @@ class ObstacleC(C.Structure):  # tlfea_obstacle
                 ("vel", C.c_double * 3), ("stiffness", C.c_double), ("friction", C.c_double), ("eps_v", C.c_double)]
 
 
+class FieldObstacleC(C.Structure):  # tlfea_field_obstacle
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("origin", C.c_double * 3), ("spacing", C.c_double),
+                ("pos", C.c_double * 3), ("rot", C.c_double * 9), ("vel", C.c_double * 3), ("stiffness", C.c_double),
+                ("friction", C.c_double), ("eps_v", C.c_double)]
+
+
 class SurfaceLoadC(C.Structure):  # tlfea_surface_load
     _fields_ = [("kind", C.c_int), ("face", C.c_int), ("value", C.c_double * 3), ("scale", C.c_double),
                 ("elems", c_ip), ("n_elems", C.c_int)]
@@ -106,6 +112,12 @@ def _obstacle_signatures(lib):
         sig[name.replace("tlfea_t10_", "tlfea_ancf_")] = sig[name]
     sig["tlfea_ancf_get_surface_points"] = [vp, c_dp]
     sig["tlfea_ancf_retrieve_contact_points"] = [vp, c_dp]
+    # field obstacles (DESIGN 3e''), any handle
+    sig["tlfea_set_field_obstacles"] = [vp, C.POINTER(FieldObstacleC), C.POINTER(c_dp), i]
+    sig["tlfea_update_field_obstacle"] = [vp, i, C.POINTER(FieldObstacleC)]
+    sig["tlfea_clear_field_obstacles"] = [vp]
+    sig["tlfea_get_field_obstacle_resultant"] = [vp, i, c_dp]
+    sig["tlfea_sdf_from_triangles"] = [c_dp, i, c_ip, i, i, i, i, c_dp, C.c_double, c_dp]
     for name, args in sig.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int

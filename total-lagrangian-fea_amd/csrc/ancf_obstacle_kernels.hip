@@ -1,8 +1,8 @@
-// ancf_obstacle_kernels.hip -- implicit contact of ANCF-3243 beams and ANCF-3443 shells with rigid half-spaces and
-// spheres (DESIGN 3e').  Contact is evaluated at 32 sample points on the faces of every element and spread to the
+// ancf_obstacle_kernels.hip -- implicit contact of ANCF-3243 beams and ANCF-3443 shells with rigid half-spaces,
+// spheres and signed-distance fields (DESIGN 3e', 3e'').  Contact is evaluated at 32 sample points on the faces of every element and spread to the
 // element's S coefficient vectors through the shape functions; the per-point physics is obstacle_point.h's.
 //
-//   ancf_obstacle_points_kernel<S>   one wavefront per element: lanes 0..31 own the points at the current coordinates,
+//   ancf_obstacle_points_kernel<S, F> (F: the list holds field obstacles; so for the footprint kernel) one wavefront per element: lanes 0..31 own the points at the current coordinates,
 //                                    lanes 32..63 evaluate the same points at the start-of-step coordinates; writes
 //                                    the element's rows of the contact force buffer cbuf [E][S][3], its touched flag,
 //                                    the blocks C_p of a touched element and the per-obstacle shares of the element
@@ -52,7 +52,7 @@ __device__ __forceinline__ void point_position(const double* __restrict__ sv, co
   }
 }
 
-template <int S>
+template <int S, bool kFields>
 __global__ __launch_bounds__(64) void ancf_obstacle_points_kernel(AncfObsView v, ObstacleList L,
                                                                   const double* __restrict__ x,
                                                                   const double* __restrict__ y,
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(64) void ancf_obstacle_points_kernel(AncfObsView v,
     double fj[4] = {0.0, 0.0, 0.0, 0.0};
     if (now) {
       bool fric;
-      const double d = obstacle_point_terms(L.o[j], wk, r, q0, h, fj, B, fj[3], fric);
+      const double d = obstacle_point_terms<kFields>(L.o[j], wk, r, q0, h, fj, B, fj[3], fric);
       hit = hit || d < 0.0 || fric;
       f[0] += fj[0];
       f[1] += fj[1];
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void ancf_obstacle_gather_kernel(int N, Incide
   }
 }
 
-template <int S>
+template <int S, bool kFields>
 __global__ __launch_bounds__(64) void ancf_obstacle_footprint_kernel(AncfObsView v, ObstacleList L,
                                                                      const double* __restrict__ x,
                                                                      const double* __restrict__ y,
@@ -185,6 +185,13 @@ __global__ __launch_bounds__(64) void ancf_obstacle_footprint_kernel(AncfObsView
   double gap = INFINITY, press = 0.0;
   for (int j = 0; j < L.n; j++) {
     double nrm[3];
+    if (kFields && L.o[j].kind == kField) {  // takes part only where it covers the point; pressure kappa <-phi> |G|
+      double phi;
+      if (!field_eval(L.o[j], r, phi, nrm)) continue;
+      gap = phi < gap ? phi : gap;
+      if (phi < 0.0) press += L.o[j].kappa * (-phi) * sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+      continue;
+    }
     const double d = obstacle_distance(L.o[j], r, nrm);
     gap = d < gap ? d : gap;
     if (d < 0.0) press += L.o[j].kappa * (-d);
@@ -202,10 +209,15 @@ __global__ __launch_bounds__(64) void ancf_obstacle_footprint_kernel(AncfObsView
 void launch_ancf_obstacle_points(hipStream_t s, const AncfObsView& v, const ObstacleList& L, const double* x,
                                  const double* y, const double* z, const double* xp, const double* yp, const double* zp,
                                  double h) {
-  if (v.S == 8)
-    hipLaunchKernelGGL((ancf_obstacle_points_kernel<8>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, xp, yp, zp, h);
+  const bool f = L.has_fields();
+  if (v.S == 8 && !f)
+    hipLaunchKernelGGL((ancf_obstacle_points_kernel<8, false>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, xp, yp, zp, h);
+  else if (v.S == 8)
+    hipLaunchKernelGGL((ancf_obstacle_points_kernel<8, true>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, xp, yp, zp, h);
+  else if (!f)
+    hipLaunchKernelGGL((ancf_obstacle_points_kernel<16, false>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, xp, yp, zp, h);
   else
-    hipLaunchKernelGGL((ancf_obstacle_points_kernel<16>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, xp, yp, zp, h);
+    hipLaunchKernelGGL((ancf_obstacle_points_kernel<16, true>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, xp, yp, zp, h);
 }
 
 void launch_ancf_obstacle_tangent(hipStream_t s, const AncfObsView& v, double h, double* Kbuf) {
@@ -221,10 +233,15 @@ void launch_ancf_obstacle_gather(hipStream_t s, int N, const Incidence& inc, con
 
 void launch_ancf_obstacle_footprint(hipStream_t s, const AncfObsView& v, const ObstacleList& L, const double* x,
                                     const double* y, const double* z, double* pts) {
-  if (v.S == 8)
-    hipLaunchKernelGGL((ancf_obstacle_footprint_kernel<8>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, pts);
+  const bool f = L.has_fields();
+  if (v.S == 8 && !f)
+    hipLaunchKernelGGL((ancf_obstacle_footprint_kernel<8, false>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, pts);
+  else if (v.S == 8)
+    hipLaunchKernelGGL((ancf_obstacle_footprint_kernel<8, true>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, pts);
+  else if (!f)
+    hipLaunchKernelGGL((ancf_obstacle_footprint_kernel<16, false>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, pts);
   else
-    hipLaunchKernelGGL((ancf_obstacle_footprint_kernel<16>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, pts);
+    hipLaunchKernelGGL((ancf_obstacle_footprint_kernel<16, true>), dim3(v.E), dim3(64), 0, s, v, L, x, y, z, pts);
 }
 
 }  // namespace tlfea

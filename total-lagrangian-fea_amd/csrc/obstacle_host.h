@@ -96,6 +96,7 @@ inline ObstacleDev obstacle_dev(const tlfea_obstacle& o) {
   d.kappa = o.stiffness;
   d.mu = o.friction;
   d.eps_v = o.eps_v;
+  d.fld = nullptr;
   return d;
 }
 

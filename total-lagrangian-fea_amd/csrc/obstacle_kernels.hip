@@ -1,6 +1,7 @@
-// obstacle_kernels.hip -- implicit contact of T10 surface nodes with rigid half-spaces and spheres.
+// obstacle_kernels.hip -- implicit contact of T10 surface nodes with rigid half-spaces, spheres and signed-distance
+// fields (DESIGN 3e, 3e'').
 //
-//   obstacle_grad_kernel       one thread per surface node: evaluates every obstacle of the list (kernel argument),
+//   obstacle_grad_kernel<F>    (F: the list holds field obstacles) one thread per surface node: evaluates every obstacle of the list (kernel argument),
 //                              adds grad Phi to g and keeps the node's force, its 3x3 Hessian block and its per-obstacle
 //                              share for the Hessian launch and the resultants
 //   obstacle_hessian_kernel    one thread per surface node: h x the block into the node's own diagonal block of H
@@ -20,6 +21,7 @@ namespace {
 
 constexpr int kBlock = 256;
 
+template <bool kFields>
 __global__ __launch_bounds__(kBlock) void obstacle_grad_kernel(int n_surf, const int* __restrict__ node,
                                                                const double* __restrict__ w, ObstacleList L,
                                                                const double* __restrict__ x, const double* __restrict__ y,
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(kBlock) void obstacle_grad_kernel(int n_surf, const
     double fj[3] = {0.0, 0.0, 0.0}, act = 0.0;
     if (!pinned) {
       bool fric;
-      obstacle_point_terms(o, wk, q, q0, h, fj, B, act, fric);
+      obstacle_point_terms<kFields>(o, wk, q, q0, h, fj, B, act, fric);
     }
     double* r = fk + ((size_t)j * n_surf + k) * 4;
     r[0] = fj[0];
@@ -106,8 +108,12 @@ void launch_obstacle_grad(hipStream_t s, int n_surf, const int* node, const doub
                           const double* zp, double h, const int* fixed_slot, double* g, double* f, double* blk,
                           double* fk) {
   if (n_surf <= 0) return;
-  hipLaunchKernelGGL(obstacle_grad_kernel, dim3(blocks(n_surf)), dim3(kBlock), 0, s, n_surf, node, w, L, x, y, z, xp, yp,
-                     zp, h, fixed_slot, g, f, blk, fk);
+  if (L.has_fields())
+    hipLaunchKernelGGL(obstacle_grad_kernel<true>, dim3(blocks(n_surf)), dim3(kBlock), 0, s, n_surf, node, w, L, x, y, z,
+                       xp, yp, zp, h, fixed_slot, g, f, blk, fk);
+  else
+    hipLaunchKernelGGL(obstacle_grad_kernel<false>, dim3(blocks(n_surf)), dim3(kBlock), 0, s, n_surf, node, w, L, x, y, z,
+                       xp, yp, zp, h, fixed_slot, g, f, blk, fk);
 }
 
 void launch_obstacle_hessian(hipStream_t s, int n_surf, const int* node, const int* off, const int* diagpos,

@@ -27,6 +27,7 @@
 #include "vbd_host.h"
 #include "obstacle_host.h"
 #include "ancf_obstacle_host.h"
+#include "field_obstacle_host.h"
 #include "ancf_load_host.h"
 #include "t10_load_host.h"
 
@@ -102,6 +103,14 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   int* d_ob_node = nullptr;
   double *d_ob_w = nullptr, *d_ob_f = nullptr, *d_ob_blk = nullptr, *d_ob_fk = nullptr, *d_ob_res = nullptr;
   int ob_fk_cap = 0;                // obstacles d_ob_fk has room for
+  // field obstacles (tlfea_set_field_obstacles, DESIGN 3e''): obs.o[0 .. ob_na) are the analytic obstacles and
+  // obs.o[ob_na .. obs.n) the fields, each list with its own index space; the samples (d_fld_V) and the descriptors
+  // (d_fld [kMaxObstacles], host copy h_fld) live in device memory
+  int ob_na = 0;
+  std::vector<tlfea_field_obstacle> fld;
+  std::vector<double*> d_fld_V;
+  FieldDev* d_fld = nullptr;
+  FieldDev h_fld[kMaxObstacles] = {};
   // the same list on an ANCF object (tlfea_ancf_set_obstacles, DESIGN 3e'): sample-point tables and element-owned buffers
   // (AncfObsView, tlfea_internal.h); d_ao_fc [N][3] the contact force per coefficient, d_ao_pts [E][32][5] the footprint
   int *d_ao_cls = nullptr, *d_ao_touched = nullptr;
@@ -253,8 +262,10 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_st_vel, h->d_st_noff, h->d_st_nel, h->d_ao_cls, h->d_ao_touched, h->d_ao_sval, h->d_ao_w,
                   h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts, h->d_ld_fc, h->d_ld_tr, h->d_ld_f,
                   h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask, h->d_ld_fnodes, h->d_ld_foff,
-                  h->d_ld_fslot};
+                  h->d_ld_fslot, h->d_fld};
   for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  for (double* p : h->d_fld_V)
     if (p) (void)hipFree(p);
   delete h;
   return 0;
@@ -457,30 +468,12 @@ static void obstacles_free(tlfea_t10_t h) {
   if (h->d_ob_node) (void)hipFree(h->d_ob_node);
   h->d_ob_node = nullptr;
   h->ob_fk_cap = 0;
-  h->obs.n = 0;
+  h->obs.n = h->ob_na = 0;
 }
-extern "C" int tlfea_t10_clear_obstacles(tlfea_t10_t h) {
-  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
-    return fail("tlfea_t10_clear_obstacles: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "clearing obstacles.");
-  if (h->obs.n == 0) return 0;
-  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
-  obstacles_free(h);
-  return 0;
-}
-extern "C" int tlfea_t10_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
-  if (h && h->kind != kT10) return fail("tlfea_t10_set_obstacles: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "setting obstacles.");
-  if (n < 0 || n > kMaxObstacles)
-    return fail("tlfea_t10_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
-  if (n > 0 && !list) return fail("tlfea_t10_set_obstacles: null list");
-  for (int k = 0; k < n; k++) {
-    const std::string why = obstacle_check(list[k]);
-    if (!why.empty()) return fail("tlfea_t10_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
-  }
-  if (n == 0) return tlfea_t10_clear_obstacles(h);
+// The node-owned buffers for a list of n obstacles (analytic and field together): allocated on first use, fk grown, all
+// zeroed -- no forces before the first gradient evaluation.
+static int obstacle_buffers(tlfea_t10_t h, int n) {
   surface_build(h);
-  HIP_TRY(hipDeviceSynchronize());
   const int ns = (int)h->h_surf.size();
   if (!h->d_ob_node) {
     std::vector<double> w(ns);
@@ -501,20 +494,65 @@ extern "C" int tlfea_t10_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list
     TRY(dmalloc(&h->d_ob_fk, (size_t)4 * n * ns));
     h->ob_fk_cap = n;
   }
-  // no forces before the first gradient evaluation
   HIP_TRY(hipMemset(h->d_ob_f, 0, (size_t)std::max(1, 3 * ns) * sizeof(double)));
   HIP_TRY(hipMemset(h->d_ob_blk, 0, (size_t)std::max(1, 6 * ns) * sizeof(double)));
   HIP_TRY(hipMemset(h->d_ob_fk, 0, (size_t)std::max(1, 4 * n * ns) * sizeof(double)));
-  h->obs.n = n;
-  for (int k = 0; k < n; k++) h->obs.o[k] = obstacle_dev(list[k]);
+  return 0;
+}
+// The list the kernels see: the analytic obstacles `a`, then the fields of h->fld in their order.
+static void obstacle_list_set(tlfea_t10_t h, const std::vector<ObstacleDev>& a) {
+  h->ob_na = (int)a.size();
+  for (int k = 0; k < h->ob_na; k++) h->obs.o[k] = a[k];
+  for (size_t k = 0; k < h->fld.size(); k++) h->obs.o[h->ob_na + k] = field_obstacle_dev(h->fld[k], h->d_fld + k);
+  h->obs.n = h->ob_na + (int)h->fld.size();
+}
+static std::vector<ObstacleDev> obstacle_list_analytic(tlfea_t10_t h) {
+  return std::vector<ObstacleDev>(h->obs.o, h->obs.o + h->ob_na);
+}
+static std::string obstacle_overflow(int n_analytic, int n_field) {
+  return std::to_string(n_analytic) + " analytic and " + std::to_string(n_field) + " field obstacles exceed the " +
+         std::to_string(kMaxObstacles) + " an object can hold";
+}
+extern "C" int tlfea_t10_clear_obstacles(tlfea_t10_t h) {
+  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
+    return fail("tlfea_t10_clear_obstacles: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "clearing obstacles.");
+  if (h->ob_na == 0) return 0;
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
+  if (h->fld.empty()) {
+    obstacles_free(h);
+  } else {  // the field list stays (DESIGN 3e'')
+    TRY(obstacle_buffers(h, (int)h->fld.size()));
+    obstacle_list_set(h, {});
+  }
+  return 0;
+}
+extern "C" int tlfea_t10_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
+  if (h && h->kind != kT10) return fail("tlfea_t10_set_obstacles: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "setting obstacles.");
+  if (n < 0 || n > kMaxObstacles)
+    return fail("tlfea_t10_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
+  if (n > 0 && !list) return fail("tlfea_t10_set_obstacles: null list");
+  for (int k = 0; k < n; k++) {
+    const std::string why = obstacle_check(list[k]);
+    if (!why.empty()) return fail("tlfea_t10_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
+  }
+  if (n + (int)h->fld.size() > kMaxObstacles)
+    return fail("tlfea_t10_set_obstacles: " + obstacle_overflow(n, (int)h->fld.size()));
+  if (n == 0) return tlfea_t10_clear_obstacles(h);
+  HIP_TRY(hipDeviceSynchronize());
+  TRY(obstacle_buffers(h, n + (int)h->fld.size()));
+  std::vector<ObstacleDev> a(n);
+  for (int k = 0; k < n; k++) a[k] = obstacle_dev(list[k]);
+  obstacle_list_set(h, a);
   return 0;
 }
 extern "C" int tlfea_t10_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle* o) {
   if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
     return fail("tlfea_t10_update_obstacle: T10 handles only (not an ANCF handle)");
   NEED_SETUP(h, "updating an obstacle.");
-  if (k < 0 || k >= h->obs.n)
-    return fail("tlfea_t10_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->obs.n) +
+  if (k < 0 || k >= h->ob_na)
+    return fail("tlfea_t10_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->ob_na) +
                 " obstacles set");
   if (!o) return fail("tlfea_t10_update_obstacle: null obstacle");
   const std::string why = obstacle_check(*o);
@@ -542,9 +580,9 @@ extern "C" int tlfea_t10_get_obstacle_resultant(tlfea_t10_t h, int k, double out
     return fail("tlfea_t10_get_obstacle_resultant: T10 handles only (not an ANCF handle)");
   NEED_SETUP(h, "reading an obstacle resultant.");
   if (!out) return fail("tlfea_t10_get_obstacle_resultant: null output");
-  if (k < 0 || k >= h->obs.n)
+  if (k < 0 || k >= h->ob_na)
     return fail("tlfea_t10_get_obstacle_resultant: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->obs.n) + " obstacles set");
+                std::to_string(h->ob_na) + " obstacles set");
   HIP_TRY(hipDeviceSynchronize());
   launch_obstacle_resultant(h->stream, (int)h->h_surf.size(), h->obs.n, h->d_ob_fk, h->d_ob_res);
   HIP_TRY(hipGetLastError());
@@ -598,27 +636,12 @@ static void ancf_obstacles_free(tlfea_t10_t h) {
     *p = nullptr;
   }
   h->ob_fk_cap = 0;
-  h->obs.n = 0;
+  h->obs.n = h->ob_na = 0;
 }
-extern "C" int tlfea_ancf_clear_obstacles(tlfea_t10_t h) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_clear_obstacles");
-  if (h->obs.n == 0) return 0;
-  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
-  ancf_obstacles_free(h);
-  return 0;
-}
-extern "C" int tlfea_ancf_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_set_obstacles");
-  if (n < 0 || n > kMaxObstacles)
-    return fail("tlfea_ancf_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
-  if (n > 0 && !list) return fail("tlfea_ancf_set_obstacles: null list");
-  for (int k = 0; k < n; k++) {
-    const std::string why = obstacle_check(list[k]);
-    if (!why.empty()) return fail("tlfea_ancf_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
-  }
-  if (n == 0) return tlfea_ancf_clear_obstacles(h);
+// The element-owned buffers for a list of n obstacles (analytic and field together): allocated on first use, fk grown,
+// zeroed -- no forces and no touched element before the first gradient evaluation.
+static int ancf_obstacle_buffers(tlfea_t10_t h, int n) {
   TRY(ancf_points_build(h));
-  HIP_TRY(hipDeviceSynchronize());
   const size_t E = h->E, S = h->S, P = kAncfObsPoints;
   if (!h->d_ao_w) {
     TRY(dmalloc(&h->d_ao_cls, E));
@@ -639,19 +662,47 @@ extern "C" int tlfea_ancf_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* lis
     TRY(dmalloc(&h->d_ao_fk, (size_t)4 * n * E));
     h->ob_fk_cap = n;
   }
-  // no forces and no touched element before the first gradient evaluation
   HIP_TRY(hipMemset(h->d_ao_touched, 0, E * sizeof(int)));
   HIP_TRY(hipMemset(h->d_ao_cbuf, 0, E * S * 3 * sizeof(double)));
   HIP_TRY(hipMemset(h->d_ao_fc, 0, (size_t)3 * h->N * sizeof(double)));
   HIP_TRY(hipMemset(h->d_ao_fk, 0, (size_t)4 * n * E * sizeof(double)));
-  h->obs.n = n;
-  for (int k = 0; k < n; k++) h->obs.o[k] = obstacle_dev(list[k]);
+  return 0;
+}
+extern "C" int tlfea_ancf_clear_obstacles(tlfea_t10_t h) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_clear_obstacles");
+  if (h->ob_na == 0) return 0;
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
+  if (h->fld.empty()) {
+    ancf_obstacles_free(h);
+  } else {  // the field list stays (DESIGN 3e'')
+    TRY(ancf_obstacle_buffers(h, (int)h->fld.size()));
+    obstacle_list_set(h, {});
+  }
+  return 0;
+}
+extern "C" int tlfea_ancf_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
+  NEED_ANCF_OBS(h, "tlfea_ancf_set_obstacles");
+  if (n < 0 || n > kMaxObstacles)
+    return fail("tlfea_ancf_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
+  if (n > 0 && !list) return fail("tlfea_ancf_set_obstacles: null list");
+  for (int k = 0; k < n; k++) {
+    const std::string why = obstacle_check(list[k]);
+    if (!why.empty()) return fail("tlfea_ancf_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
+  }
+  if (n + (int)h->fld.size() > kMaxObstacles)
+    return fail("tlfea_ancf_set_obstacles: " + obstacle_overflow(n, (int)h->fld.size()));
+  if (n == 0) return tlfea_ancf_clear_obstacles(h);
+  HIP_TRY(hipDeviceSynchronize());
+  TRY(ancf_obstacle_buffers(h, n + (int)h->fld.size()));
+  std::vector<ObstacleDev> a(n);
+  for (int k = 0; k < n; k++) a[k] = obstacle_dev(list[k]);
+  obstacle_list_set(h, a);
   return 0;
 }
 extern "C" int tlfea_ancf_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle* o) {
   NEED_ANCF_OBS(h, "tlfea_ancf_update_obstacle");
-  if (k < 0 || k >= h->obs.n)
-    return fail("tlfea_ancf_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->obs.n) +
+  if (k < 0 || k >= h->ob_na)
+    return fail("tlfea_ancf_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->ob_na) +
                 " obstacles set");
   if (!o) return fail("tlfea_ancf_update_obstacle: null obstacle");
   const std::string why = obstacle_check(*o);
@@ -673,9 +724,9 @@ extern "C" int tlfea_ancf_get_obstacle_forces(tlfea_t10_t h, double* f) {
 extern "C" int tlfea_ancf_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
   NEED_ANCF_OBS(h, "tlfea_ancf_get_obstacle_resultant");
   if (!out) return fail("tlfea_ancf_get_obstacle_resultant: null output");
-  if (k < 0 || k >= h->obs.n)
+  if (k < 0 || k >= h->ob_na)
     return fail("tlfea_ancf_get_obstacle_resultant: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->obs.n) + " obstacles set");
+                std::to_string(h->ob_na) + " obstacles set");
   HIP_TRY(hipDeviceSynchronize());
   launch_obstacle_resultant(h->stream, h->E, h->obs.n, h->d_ao_fk, h->d_ob_res);  // the elements' shares, element order
   HIP_TRY(hipGetLastError());
@@ -699,6 +750,167 @@ extern "C" int tlfea_ancf_retrieve_contact_points(tlfea_t10_t h, double* out) {
   launch_ancf_obstacle_footprint(h->stream, ancf_obs_view(h), h->obs, h->d_x, h->d_y, h->d_z, h->d_ao_pts);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, h->d_ao_pts, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- field obstacles (DESIGN 3e''), any handle ---------------------------------------------------------------------------
+#define NEED_FIELD_OBS(h, what)                                                                              \
+  NEED_SETUP(h, what ".");                                                                                   \
+  if ((h)->kind != kT10 && !(h)->have_dndu)                                                                  \
+  return fail(std::string(what) + ": CalcDsDuPre must run first (the point weights use the reference geometry)")
+static void field_storage_free(tlfea_t10_t h) {
+  for (double* p : h->d_fld_V)
+    if (p) (void)hipFree(p);
+  h->d_fld_V.clear();
+  h->fld.clear();
+}
+extern "C" int tlfea_clear_field_obstacles(tlfea_t10_t h) {
+  NEED_FIELD_OBS(h, "tlfea_clear_field_obstacles");
+  if (h->fld.empty()) return 0;
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the samples
+  field_storage_free(h);
+  if (h->ob_na == 0) {
+    if (h->kind == kT10)
+      obstacles_free(h);
+    else
+      ancf_obstacles_free(h);
+    if (h->d_fld) (void)hipFree(h->d_fld);
+    h->d_fld = nullptr;
+  } else {  // the analytic list stays
+    TRY(h->kind == kT10 ? obstacle_buffers(h, h->ob_na) : ancf_obstacle_buffers(h, h->ob_na));
+    obstacle_list_set(h, obstacle_list_analytic(h));
+  }
+  return 0;
+}
+extern "C" int tlfea_set_field_obstacles(tlfea_t10_t h, const tlfea_field_obstacle* list, const double* const* values,
+                                         int n) {
+  NEED_FIELD_OBS(h, "tlfea_set_field_obstacles");
+  if (n < 0 || n > kMaxObstacles)
+    return fail("tlfea_set_field_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
+  if (n > 0 && !list) return fail("tlfea_set_field_obstacles: null list");
+  if (n > 0 && !values) return fail("tlfea_set_field_obstacles: null sample pointer");
+  for (int k = 0; k < n; k++) {
+    if (!values[k]) return fail("tlfea_set_field_obstacles: field " + std::to_string(k) + ": null sample pointer");
+    std::string why = field_params_check(list[k]);
+    if (why.empty()) why = field_values_check(list[k], values[k]);
+    if (!why.empty()) return fail("tlfea_set_field_obstacles: field " + std::to_string(k) + ": " + why);
+  }
+  if (n + h->ob_na > kMaxObstacles) return fail("tlfea_set_field_obstacles: " + obstacle_overflow(h->ob_na, n));
+  if (n == 0) return tlfea_clear_field_obstacles(h);
+  HIP_TRY(hipDeviceSynchronize());
+  // the new samples are allocated and copied first and swapped in only when all of that has succeeded: a failure leaves
+  // the previous list as it was
+  std::vector<double*> fresh;
+  auto drop = [&](int r) {
+    for (double* p : fresh) (void)hipFree(p);
+    return r;
+  };
+  FieldDev desc[kMaxObstacles] = {};
+  for (int k = 0; k < n; k++) {
+    const size_t ns = (size_t)list[k].nx * list[k].ny * list[k].nz;
+    double* d_V = nullptr;
+    if (int r = dmalloc(&d_V, ns)) return drop(r);
+    fresh.push_back(d_V);
+    if (hipMemcpy(d_V, values[k], ns * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      return drop(fail("tlfea_set_field_obstacles: copying the samples of field " + std::to_string(k) + " failed"));
+    desc[k] = field_dev(list[k], d_V);
+  }
+  // the descriptors go to a fresh device array: the one in use, which the list entries point into, is untouched until
+  // every allocation and copy has succeeded
+  FieldDev* d_fld_new = nullptr;
+  if (int r = dmalloc(&d_fld_new, (size_t)kMaxObstacles)) return drop(r);
+  if (hipMemcpy(d_fld_new, desc, (size_t)n * sizeof(FieldDev), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d_fld_new);
+    return drop(fail("tlfea_set_field_obstacles: copying the descriptors failed"));
+  }
+  if (int r = h->kind == kT10 ? obstacle_buffers(h, h->ob_na + n) : ancf_obstacle_buffers(h, h->ob_na + n)) {
+    (void)hipFree(d_fld_new);  // the shared buffers may have been re-zeroed: no forces until the next evaluation
+    return drop(r);
+  }
+  if (h->d_fld) (void)hipFree(h->d_fld);
+  h->d_fld = d_fld_new;
+  const std::vector<ObstacleDev> analytic = obstacle_list_analytic(h);
+  field_storage_free(h);
+  h->d_fld_V.swap(fresh);
+  std::copy(desc, desc + n, h->h_fld);
+  h->fld.assign(list, list + n);
+  obstacle_list_set(h, analytic);
+  return 0;
+}
+extern "C" int tlfea_update_field_obstacle(tlfea_t10_t h, int k, const tlfea_field_obstacle* o) {
+  NEED_FIELD_OBS(h, "tlfea_update_field_obstacle");
+  if (k < 0 || k >= (int)h->fld.size())
+    return fail("tlfea_update_field_obstacle: index " + std::to_string(k) + " outside the " +
+                std::to_string(h->fld.size()) + " field obstacles set");
+  if (!o) return fail("tlfea_update_field_obstacle: null obstacle");
+  const std::string why = field_params_check(*o);
+  if (!why.empty()) return fail("tlfea_update_field_obstacle: field " + std::to_string(k) + ": " + why);
+  const tlfea_field_obstacle& old = h->fld[k];
+  if (o->nx != old.nx || o->ny != old.ny || o->nz != old.nz)
+    return fail("tlfea_update_field_obstacle: field " + std::to_string(k) + ": the grid is " + std::to_string(o->nx) +
+                " x " + std::to_string(o->ny) + " x " + std::to_string(o->nz) + ", the stored one " +
+                std::to_string(old.nx) + " x " + std::to_string(old.ny) + " x " + std::to_string(old.nz));
+  // the descriptor: a small copy ordered on the object's stream (the solvers' streams synchronise with it); position,
+  // velocity and the contact parameters are kernel arguments: launches already queued keep the old values
+  h->h_fld[k] = field_dev(*o, h->d_fld_V[k]);
+  HIP_TRY(hipMemcpyAsync(h->d_fld + k, &h->h_fld[k], sizeof(FieldDev), hipMemcpyHostToDevice, h->stream));
+  h->fld[k] = *o;
+  h->obs.o[h->ob_na + k] = field_obstacle_dev(*o, h->d_fld + k);
+  return 0;
+}
+extern "C" int tlfea_get_field_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
+  NEED_FIELD_OBS(h, "tlfea_get_field_obstacle_resultant");
+  if (!out) return fail("tlfea_get_field_obstacle_resultant: null output");
+  if (k < 0 || k >= (int)h->fld.size())
+    return fail("tlfea_get_field_obstacle_resultant: index " + std::to_string(k) + " outside the " +
+                std::to_string(h->fld.size()) + " field obstacles set");
+  HIP_TRY(hipDeviceSynchronize());
+  if (h->kind == kT10)
+    launch_obstacle_resultant(h->stream, (int)h->h_surf.size(), h->obs.n, h->d_ob_fk, h->d_ob_res);
+  else
+    launch_obstacle_resultant(h->stream, h->E, h->obs.n, h->d_ao_fk, h->d_ob_res);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, h->d_ob_res + 4 * (h->ob_na + k), 4 * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+// Launches of at most kSdfPairsPerLaunch (sample, triangle) pairs each, so that none is long-running (DESIGN 3e'').
+constexpr long long kSdfPairsPerLaunch = 1ll << 32;
+constexpr int kSdfMaxTriangles = 1 << 24;  // 256 samples x 2^24 triangles = the bound: every launch holds a whole block
+extern "C" int tlfea_sdf_from_triangles(const double* verts, int n_verts, const int* tris, int n_tris, int nx, int ny,
+                                        int nz, const double origin[3], double spacing, double* values) {
+  if (!verts || !tris || !origin || !values) return fail("tlfea_sdf_from_triangles: null argument");
+  if (nx < 1 || ny < 1 || nz < 1) return fail("tlfea_sdf_from_triangles: the grid needs at least one sample per axis");
+  if ((long long)nx * ny * nz > kMaxFieldSamples) return fail("tlfea_sdf_from_triangles: more than 2^27 samples");
+  if (!(spacing > 0.0) || !std::isfinite(spacing)) return fail("tlfea_sdf_from_triangles: spacing must be > 0");
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(origin[c])) return fail("tlfea_sdf_from_triangles: non-finite origin");
+  if (n_verts < 0 || n_tris < 0) return fail("tlfea_sdf_from_triangles: negative count");
+  if (n_tris > kSdfMaxTriangles)  // a launch of one block of samples would exceed the pair bound
+    return fail("tlfea_sdf_from_triangles: more than 2^24 triangles");
+  const std::string why = surface_check(verts, n_verts, tris, n_tris);
+  if (!why.empty()) return fail("tlfea_sdf_from_triangles: " + why);
+  std::vector<double> tri((size_t)9 * n_tris);
+  for (int t = 0; t < n_tris; t++)
+    for (int c = 0; c < 3; c++)
+      for (int a = 0; a < 3; a++) tri[(size_t)9 * t + 3 * c + a] = verts[3 * (size_t)tris[3 * t + c] + a];
+  const long long ns = (long long)nx * ny * nz;
+  double *d_tri = nullptr, *d_out = nullptr;
+  TRY(dmalloc(&d_tri, tri.size()));
+  if (int r = dmalloc(&d_out, (size_t)ns)) {
+    (void)hipFree(d_tri);
+    return r;
+  }
+  hipError_t e = hipMemcpy(d_tri, tri.data(), tri.size() * sizeof(double), hipMemcpyHostToDevice);
+  const long long per = std::max(256ll, kSdfPairsPerLaunch / n_tris / 256 * 256);
+  for (long long first = 0; first < ns && e == hipSuccess; first += per) {
+    launch_sdf_from_triangles(nullptr, d_tri, n_tris, nx, ny, origin, spacing, first, std::min(per, ns - first), d_out);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  }
+  if (e == hipSuccess) e = hipMemcpy(values, d_out, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(d_tri);
+  (void)hipFree(d_out);
+  HIP_TRY(e);
   return 0;
 }
 

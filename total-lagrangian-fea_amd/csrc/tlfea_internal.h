@@ -357,14 +357,29 @@ void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const doubl
 // (16 x 120 bytes).  Every surface node owns its own entries of g, of its diagonal block of H and of the per-node
 // buffers, so the launches need no atomics and are bitwise reproducible.
 constexpr int kMaxObstacles = 16;
-enum ObstacleKind : int { kHalfSpace = 0, kSphere = 1 };
+enum ObstacleKind : int { kHalfSpace = 0, kSphere = 1, kField = 2 };
+// A field obstacle (tlfea_set_field_obstacles, DESIGN 3e''): nx x ny x nz signed-distance samples V[(iz ny + iy) nx + ix]
+// at origin + spacing (ix, iy, iz) in the obstacle's frame, rot (row-major) frame -> world.  The descriptors and the
+// samples live in device memory; the list entry carries the descriptor's address, its position in p and the rest of
+// the contact parameters as an analytic obstacle does.
+struct FieldDev {
+  int nx, ny, nz;
+  double origin[3], spacing, rot[9];
+  const double* V;
+};
 struct ObstacleDev {
   int kind;
   double p[3], n[3], radius, vel[3], kappa, mu, eps_v;
+  const FieldDev* fld;  // kField only
 };
 struct ObstacleList {
   int n;
   ObstacleDev o[kMaxObstacles];
+  bool has_fields() const {  // host: which instantiation of the obstacle kernels a launch takes
+    for (int j = 0; j < n; j++)
+      if (o[j].kind == kField) return true;
+    return false;
+  }
 };
 // Per surface node k (node[k]): force f = -grad Phi (3), symmetric 3x3 block of the Hessian of Phi (xx yy zz xy xz yz),
 // and per obstacle j the node's share {fx, fy, fz, in contact} at fk[(j * n_surf + k) * 4].  g (may be null: refresh of
@@ -401,9 +416,17 @@ void launch_ancf_obstacle_points(hipStream_t s, const AncfObsView& v, const Obst
 void launch_ancf_obstacle_tangent(hipStream_t s, const AncfObsView& v, double h, double* Kbuf);
 // fc [N][3] = ascending-element sum of the coefficient's cbuf rows; g (may be null) -= fc
 void launch_ancf_obstacle_gather(hipStream_t s, int N, const Incidence& inc, const double* cbuf, double* fc, double* g);
-// pts [E][32][5] = position | smallest gap | normal pressure sum_j kappa_j <-d_j> of every sample point
+// pts [E][32][5] = position | smallest gap | normal pressure sum_j kappa_j <-d_j> of every sample point (a field takes
+// part where it covers the point, with kappa <-phi> |G|; a point that nothing covers reports a gap of +inf)
 void launch_ancf_obstacle_footprint(hipStream_t s, const AncfObsView& v, const ObstacleList& L, const double* x,
                                     const double* y, const double* z, double* pts);
+
+// Signed distance of a closed triangle surface on a regular grid (tlfea_sdf_from_triangles, DESIGN 3e''; sdf_kernels.hip):
+// tri [n_tris][9] vertex coordinates, out the samples first .. first + count - 1 of the nx x ny x nz grid (x fastest).
+// One thread per sample, every triangle in ascending order: bitwise reproducible.
+constexpr int kSdfTile = 128;  // triangles staged through LDS per tile
+void launch_sdf_from_triangles(hipStream_t s, const double* tri, int n_tris, int nx, int ny, const double origin[3],
+                               double spacing, long long first, long long count, double* out);
 
 // Distributed loads (tlfea_set_body_acceleration, tlfea_ancf_set_surface_loads; load_kernels.hip).  No atomics.
 constexpr int kMaxLoads = 16;

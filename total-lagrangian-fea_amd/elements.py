@@ -9,7 +9,7 @@ import numpy as np
 
 from .binding import MaterialEntryC, ObstacleC, SurfaceLoadC, T10SurfaceLoadC, check, dp, ip, load_library
 from .loads import MAX_LOADS, BoundaryFaces, FaceLoad, FollowerPressure, SurfaceTraction, _SurfaceLoad
-from .obstacles import MAX_OBSTACLES, as_c
+from .obstacles import MAX_OBSTACLES, RigidField, as_c, fields_as_c
 
 MAX_MATERIALS = 256  # table entries per object (include/tlfea_c.h)
 _MODELS = {"svk": 0, "mooney_rivlin": 1, "mr": 1}
@@ -145,6 +145,41 @@ class GPU_FEAT10_Data:
         out = np.zeros(4)
         check(self._lib.tlfea_t10_get_obstacle_resultant(self._h, int(k), dp(out)))
         return out[:3].copy(), int(round(out[3]))
+
+    # -- field obstacles (DESIGN 3e''): any data class, beside the analytic list ----------------------------------------
+    def SetFieldObstacles(self, fields):
+        """Replace the list of field obstacles (RigidField; an empty list clears it).  Analytic and field obstacles
+        together number at most 16; the analytic list stays as it is.  ANCF: after CalcDsDuPre."""
+        arr, ptrs, n = fields_as_c(fields)
+        check(self._lib.tlfea_set_field_obstacles(self._h, arr, ptrs, n))
+
+    def UpdateFieldObstacle(self, k, field):
+        """Move field k between steps: pose, velocity, stiffness, friction and eps_v of `field` (RigidField.moved); its grid
+        must be the stored one, and the samples on the device are kept."""
+        if not isinstance(field, RigidField):
+            raise ValueError(f"expected a RigidField, got {type(field).__name__}")
+        o = field.to_c()
+        check(self._lib.tlfea_update_field_obstacle(self._h, int(k), C.byref(o)))
+
+    def ClearFieldObstacles(self):
+        check(self._lib.tlfea_clear_field_obstacles(self._h))
+
+    def GetFieldObstacleResultant(self, k):
+        """(force of field k on the mesh as a 3-vector, nodes or sample points in contact) at the last gradient evaluation."""
+        out = np.zeros(4)
+        check(self._lib.tlfea_get_field_obstacle_resultant(self._h, int(k), dp(out)))
+        return out[:3].copy(), int(round(out[3]))
+
+    def GetBoundaryTriangles(self, current=False):
+        """The boundary of the mesh as a closed triangle surface: every 6-node face of GetBoundaryFaces split into four
+        triangles over its corner and mid-edge nodes.  Returns (V (n, 3), T (m, 3)) with compact vertex numbering, outward
+        orientation; the coordinates are the ones handed to Setup, or the current ones."""
+        bf = self.GetBoundaryFaces()
+        X = np.stack(self.RetrievePositionToCPU(), axis=1) if current else self._X0
+        f = bf.nodes                                              # corners 0 1 2, mid-edge nodes 01 12 02
+        tri = np.concatenate([f[:, [0, 3, 5]], f[:, [3, 1, 4]], f[:, [5, 4, 2]], f[:, [3, 4, 5]]], axis=1).reshape(-1, 3)
+        used, inv = np.unique(tri, return_inverse=True)
+        return np.ascontiguousarray(X[used]), inv.reshape(-1, 3).astype(np.int32)
 
     def GetSurfaceWeights(self):
         """Surface area share of every node (N; 0 inside the mesh): the weights of the contact model."""

@@ -696,6 +696,69 @@ class ElementBase {  // ElementBase.h:22-50 (host-side virtuals only)
   virtual void RetrievePositionToCPU(tlfea::VectorXd& x12, tlfea::VectorXd& y12, tlfea::VectorXd& z12) = 0;
 };
 
+// A rigid obstacle of any closed shape (DESIGN 3e''; no reference counterpart): signed-distance samples (negative inside)
+// values[(iz * ny + iy) * nx + ix] at origin + spacing * (ix, iy, iz) in the obstacle's frame, placed in the world by pos
+// and rot (row-major, frame -> world).  Goes to SetFieldObstacles / UpdateFieldObstacle of the three data classes.
+struct RigidField {
+  int nx = 0, ny = 0, nz = 0;
+  double origin[3] = {0, 0, 0}, spacing = 0;
+  double pos[3] = {0, 0, 0}, rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, vel[3] = {0, 0, 0};
+  double stiffness = 0, friction = 0, eps_v = 1e-3;
+  std::vector<double> values;
+  bool ok = true;  // false: FromTriangles was refused (tlfea_last_error() explains)
+
+  tlfea_field_obstacle ToC() const {
+    tlfea_field_obstacle o{};
+    o.nx = nx, o.ny = ny, o.nz = nz, o.spacing = spacing;
+    o.stiffness = stiffness, o.friction = friction, o.eps_v = eps_v;
+    for (int c = 0; c < 3; c++) o.origin[c] = origin[c], o.pos[c] = pos[c], o.vel[c] = vel[c];
+    for (int c = 0; c < 9; c++) o.rot[c] = rot[c];
+    return o;
+  }
+  // the grid lo, lo + spacing, ... that reaches hi on every axis
+  static RigidField Grid(const double lo[3], const double hi[3], double spacing, double stiffness, double friction) {
+    RigidField f;
+    f.spacing = spacing, f.stiffness = stiffness, f.friction = friction;
+    int* n[3] = {&f.nx, &f.ny, &f.nz};
+    for (int c = 0; c < 3; c++) {
+      f.origin[c] = lo[c];
+      *n[c] = static_cast<int>(std::ceil((hi[c] - lo[c]) / spacing - 1e-9)) + 1;
+    }
+    f.values.resize(static_cast<size_t>(f.nx) * f.ny * f.nz);
+    return f;
+  }
+  // samples sd(x, y, z) (signed distance, negative inside)
+  template <class F>
+  static RigidField FromFunction(F sd, const double lo[3], const double hi[3], double spacing, double stiffness,
+                                 double friction = 0.0) {
+    RigidField f = Grid(lo, hi, spacing, stiffness, friction);
+    for (int iz = 0; iz < f.nz; iz++)
+      for (int iy = 0; iy < f.ny; iy++)
+        for (int ix = 0; ix < f.nx; ix++)
+          f.values[(static_cast<size_t>(iz) * f.ny + iy) * f.nx + ix] =
+              sd(lo[0] + spacing * ix, lo[1] + spacing * iy, lo[2] + spacing * iz);
+    return f;
+  }
+  // the signed distance of the closed triangle surface (verts [n][3], tris [m][3]), built on the device, on a grid that
+  // extends `margin` spacings (at least 2.5) beyond the surface's bounding box
+  static RigidField FromTriangles(const std::vector<double>& verts, const std::vector<int>& tris, double spacing,
+                                  double stiffness, double friction = 0.0, double margin = 3.0) {
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    const size_t nv = verts.size() / 3;
+    for (size_t i = 0; i < nv; i++)
+      for (int c = 0; c < 3; c++) {
+        lo[c] = i ? std::min(lo[c], verts[3 * i + c]) : verts[c];
+        hi[c] = i ? std::max(hi[c], verts[3 * i + c]) : verts[c];
+      }
+    margin = std::max(margin, 2.5);
+    for (int c = 0; c < 3; c++) lo[c] -= margin * spacing, hi[c] += margin * spacing;
+    RigidField f = Grid(lo, hi, spacing, stiffness, friction);
+    f.ok = tlfea_sdf_from_triangles(verts.data(), static_cast<int>(nv), tris.data(), static_cast<int>(tris.size() / 3), f.nx,
+                                    f.ny, f.nz, f.origin, spacing, f.values.data()) == 0;
+    return f;
+  }
+};
+
 struct GPU_FEAT10_Data : public ElementBase {
   GPU_FEAT10_Data(int num_elements, int num_nodes) : n_elem(num_elements), n_coef(num_nodes) { type = TYPE_T10; }
 
@@ -753,6 +816,21 @@ struct GPU_FEAT10_Data : public ElementBase {
     w.resize(n_coef);
     TLFEA_HANDLE_ERROR(tlfea_t10_get_surface_weights(h, w.data()));
   }
+  // field obstacles (DESIGN 3e''), any data class, beside the analytic list (together at most 16).  The set / update calls
+  // return the C-ABI's status; UpdateFieldObstacle takes pose, velocity and contact parameters of `f` and keeps the samples.
+  int SetFieldObstacles(const std::vector<RigidField>& list) {
+    std::vector<tlfea_field_obstacle> c;
+    std::vector<const double*> v;
+    for (const RigidField& f : list) c.push_back(f.ToC()), v.push_back(f.values.data());
+    return tlfea_set_field_obstacles(h, c.data(), v.data(), static_cast<int>(list.size()));
+  }
+  int UpdateFieldObstacle(int k, const RigidField& f) {
+    const tlfea_field_obstacle o = f.ToC();
+    return tlfea_update_field_obstacle(h, k, &o);
+  }
+  int ClearFieldObstacles() { return tlfea_clear_field_obstacles(h); }
+  // out[0..2]: field k's force on the mesh, out[3]: its nodes (ANCF: sample points) in contact
+  void GetFieldObstacleResultant(int k, double out[4]) { TLFEA_HANDLE_ERROR(tlfea_get_field_obstacle_resultant(h, k, out)); }
   // stress and energy recovery (no reference counterpart).  velocity: a solver's GetVelocityGuessDevicePtr()
   // (device) or null; CalcStressFromHost takes 3N host values.  Status 0 = done (tlfea_last_error() explains a refusal).
   int CalcStress(const double* d_velocity = nullptr, bool points = false) {
@@ -839,6 +917,25 @@ struct GPU_FEAT10_Data : public ElementBase {
       b.area[k] = 0.5 * len;
     }
     return b;
+  }
+  // The boundary as a closed triangle surface: every 6-node boundary face split into four triangles over its corner and
+  // mid-edge nodes, compact vertex numbering, outward orientation.  x, y, z: the coordinates to take (reference or current).
+  void GetBoundaryTriangles(const tlfea::VectorXd& x, const tlfea::VectorXd& y, const tlfea::VectorXd& z,
+                            std::vector<double>& verts, std::vector<int>& tris) {
+    const BoundaryFaces b = GetBoundaryFaces(x, y, z);
+    static const int split[4][3] = {{0, 3, 5}, {3, 1, 4}, {5, 4, 2}, {3, 4, 5}};
+    std::vector<int> id(n_coef, -1);
+    verts.clear(), tris.clear();
+    std::vector<int> used(b.nodes);
+    std::sort(used.begin(), used.end());
+    used.erase(std::unique(used.begin(), used.end()), used.end());
+    for (size_t k = 0; k < used.size(); k++) {
+      id[used[k]] = static_cast<int>(k);
+      verts.push_back(x(used[k])), verts.push_back(y(used[k])), verts.push_back(z(used[k]));
+    }
+    for (int f = 0; f < b.count(); f++)
+      for (const auto& t : split)
+        for (int c = 0; c < 3; c++) tris.push_back(id[b.nodes[6 * static_cast<size_t>(f) + t[c]]]);
   }
   // The Add calls return the load's index, or -1 when refused (tlfea_last_error() explains; the list is unchanged).
   struct FaceLoadRec {

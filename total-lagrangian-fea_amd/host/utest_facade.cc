@@ -426,6 +426,57 @@ void two_bodies_one_system(const std::string& d) {
             std::to_string(diff / moved) + " rel)");
   data.Destroy();
 }
+
+// Field obstacles through the facade (DESIGN 3e''): the boundary of the 3 x 2 x 1 bar as a triangle surface is closed (the
+// builder refuses an open or inconsistently oriented one), the grid built from it equals the box distance sampled with
+// FromFunction on the same grid, and the data class takes, moves and clears the field.
+void field_obstacle_known_answers(const std::string& d) {
+  ANCFCPUUtils::MeshManager mm;
+  mm.LoadMesh(d + "/beam_3x2x1.1.node", d + "/beam_3x2x1.1.ele", "bar");
+  const tlfea::MatrixXd& nodes = mm.GetAllNodes();
+  const int N = mm.GetTotalNodes(), E = mm.GetTotalElements();
+  GPU_FEAT10_Data data(E, N);
+  data.Initialize();
+  tlfea::VectorXd x(N), y(N), z(N);
+  for (int i = 0; i < N; i++) x(i) = nodes(i, 0), y(i) = nodes(i, 1), z(i) = nodes(i, 2);
+  data.Setup(Quadrature::tet5pt_x, Quadrature::tet5pt_y, Quadrature::tet5pt_z, Quadrature::tet5pt_weights, x, y, z,
+             mm.GetAllElements());
+  std::vector<double> verts;
+  std::vector<int> tris;
+  data.GetBoundaryTriangles(x, y, z, verts, tris);
+  const int n_faces = data.GetBoundaryFaces(x, y, z).count();
+  check(static_cast<int>(tris.size()) == 12 * n_faces && !verts.empty(), "boundary triangles: four per boundary face");
+  const RigidField built = RigidField::FromTriangles(verts, tris, 0.23, 1e8);
+  check(built.ok, "FromTriangles accepts the boundary of the bar (closed, consistently oriented)");
+  std::vector<int> open_tris(tris.begin(), tris.end() - 3);
+  check(!RigidField::FromTriangles(verts, open_tris, 0.23, 1e8).ok, "FromTriangles refuses the surface with a triangle removed");
+  auto box = [](double px, double py, double pz) {
+    const double q[3] = {std::fabs(px - 1.5) - 1.5, std::fabs(py - 1.0) - 1.0, std::fabs(pz - 0.5) - 0.5};
+    double out2 = 0.0;
+    for (double v : q) out2 += v > 0.0 ? v * v : 0.0;
+    return std::sqrt(out2) + std::min(std::max(q[0], std::max(q[1], q[2])), 0.0);
+  };
+  const double hi[3] = {built.origin[0] + built.spacing * (built.nx - 1), built.origin[1] + built.spacing * (built.ny - 1),
+                        built.origin[2] + built.spacing * (built.nz - 1)};
+  RigidField sampled = RigidField::FromFunction(box, built.origin, hi, built.spacing, 1e8);
+  bool same_grid = sampled.nx == built.nx && sampled.ny == built.ny && sampled.nz == built.nz && built.ok;
+  double err = 0.0;
+  int inside = 0;
+  if (same_grid)
+    for (size_t i = 0; i < built.values.size(); i++) {
+      err = std::max(err, std::fabs(built.values[i] - sampled.values[i]));
+      inside += built.values[i] < 0.0;
+    }
+  check(same_grid && inside > 0 && err <= 1e-12, "FromTriangles == FromFunction(box distance) on the same grid (max diff " +
+                                                     std::to_string(err * 1e12) + "e-12)");
+  sampled.pos[2] = -1.5;  // under the bar
+  check(data.SetFieldObstacles({sampled}) == 0, "SetFieldObstacles accepts the sampled box");
+  sampled.pos[2] = -1.25;
+  check(data.UpdateFieldObstacle(0, sampled) == 0 && data.UpdateFieldObstacle(1, sampled) != 0,
+        "UpdateFieldObstacle moves field 0 and refuses index 1");
+  check(data.ClearFieldObstacles() == 0, "ClearFieldObstacles");
+  data.Destroy();
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -453,6 +504,7 @@ int main(int argc, char** argv) {
   mass_known_answer(3, data_dir);
   strip_3443();
   two_bodies_one_system(data_dir);
+  field_obstacle_known_answers(data_dir);
   if (print) {  // PrintDsDuPre text of one beam (ANCF3243Data.cu:326-360)
     ANCFCPUUtils::GridMeshGenerator gg(2.0, 0.0, 2.0, true, false);
     gg.generate_mesh();
