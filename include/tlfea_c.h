@@ -408,6 +408,32 @@ int tlfea_newton_linear_solve(tlfea_newton_t s, const double *b, double *x, int 
 int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double *out_ms7);
 /* y = H x with the current H, host vectors of 3N (partition-boundary rows summed over ranks). */
 int tlfea_newton_apply_hessian(tlfea_newton_t s, const double *x, double *y);
+/* ---- modal analysis (no reference counterpart) ---------------------------------------
+ * The n_modes lowest pairs of  K phi = omega^2 M phi  on the free DOFs, K the tangent stiffness at the positions the data
+ * object holds now (contact stiffness of rigid / field obstacles and the penalty of general linear constraints included;
+ * pinned coefficients eliminated exactly), by LOBPCG on the shifted pencil A = K + shift M with the Newton solver's own
+ * preconditioner.  shift (rad^2/s^2) must be positive -- it makes a free body's pencil definite -- and should be at or
+ * below the lowest omega^2 of interest: any value gives the same modes, only the iteration count changes.
+ * block_extra < 0 = auto (half of n_modes, at least 2).  Refused (tlfea_last_error says why): damping set, an obstacle with friction, a partitioned
+ * mesh, lin.method = 1, n_modes < 1, n_modes + block_extra > 32, 3 x that above the free DOFs, no mass matrix.  The solver
+ * is left as it was: time step, positions, velocities, multipliers, warm-start state; H is re-assembled. */
+typedef struct {
+  int n_modes, block_extra;
+  double shift, tol; /* column i converged: ||K phi - omega^2 M phi|| <= tol (omega^2 + shift) ||M phi|| */
+  int max_iter;
+  unsigned seed;     /* of the deterministic start block */
+} tlfea_modal_opts;
+/* omega2 [n_modes] ascending; modes [n_modes][3N] M-normalised (may be NULL); resid [n_modes] the relative residuals of
+ * the test above; info [4]: iterations, converged modes, block size, preconditioner (0 block-Jacobi, 1 polynomial,
+ * 2 p-multigrid).  Returns an error, the outputs filled with what it has, when fewer than n_modes converge in max_iter. */
+int tlfea_newton_modal_solve(tlfea_newton_t s, const tlfea_modal_opts *opts, double *omega2, double *modes, double *resid,
+                             int *info);
+/* test hooks: Y = H X (which 0) or (M (x) I3) X (which 1) with the current H for a host block [3N][m], m <= 32, pinned
+ * rows zeroed when apply_mask; G [p][q] = X^T Y for host blocks [3N][p], [3N][q], p, q <= 96 */
+int tlfea_newton_modal_apply_block(tlfea_newton_t s, int which, int m, const double *X, double *Y, int apply_mask);
+int tlfea_newton_modal_gram(tlfea_newton_t s, int p, int q, const double *X, const double *Y, double *G);
+/* mean ms of one block product Y = H X with m columns over `reps` launches (hipEvents; tools/modal_timing.py) */
+int tlfea_newton_modal_time_spmm(tlfea_newton_t s, int m, int reps, double *ms_out);
 /* The same product from the matrix-free pair of the CG iteration (element records instead of the CSR values),
  * with the records of the last assembly.  Returns an error where that product is not eligible: anything but straight-sided
  * T10 elements with one St.Venant-Kirchhoff material on one GPU, general linear constraints, rigid obstacles, per-element

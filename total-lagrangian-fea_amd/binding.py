@@ -152,6 +152,23 @@ def _material_signatures(lib):
         getattr(lib, name).restype = C.c_int
 
 
+class ModalOptsC(C.Structure):  # tlfea_modal_opts
+    _fields_ = [("n_modes", C.c_int), ("block_extra", C.c_int), ("shift", C.c_double), ("tol", C.c_double),
+                ("max_iter", C.c_int), ("seed", C.c_uint)]
+
+
+def _modal_signatures(lib):
+    """ctypes signatures of the modal-analysis entry points."""
+    vp, i = C.c_void_p, C.c_int
+    sig = {"tlfea_newton_modal_solve": [vp, C.POINTER(ModalOptsC), c_dp, c_dp, c_dp, c_ip],
+           "tlfea_newton_modal_apply_block": [vp, i, i, c_dp, c_dp, i],
+           "tlfea_newton_modal_gram": [vp, i, i, c_dp, c_dp, c_dp],
+           "tlfea_newton_modal_time_spmm": [vp, i, i, c_dp]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+
+
 def _contact_signatures(lib):
     """ctypes signatures of the tlfea_contact_* entry points (pointer arguments are c_void_p: device pointers pass as
     integers, host arrays through dp / ip)."""
@@ -219,6 +236,7 @@ def load_library():
     _obstacle_signatures(lib)
     _stress_signatures(lib)
     _load_signatures(lib)
+    _modal_signatures(lib)
     _LIB = lib
     return lib
 

@@ -307,6 +307,22 @@ void launch_pcg_update_noz(hipStream_t s, int N, const double* w, const double* 
                            const double* rz_part_old, const double* pq_part, double* x, double* r, double* rr_part,
                            double* indefinite);
 void launch_apply_dinv(hipStream_t s, int N, const double* Dinv, const double* q, double* v);
+// block-vector kernels of the modal solve (modal_kernels.hip): a block holds ld doubles per DOF row, the m
+// columns of a DOF contiguous; fixed_slot (or null) zeroes the rows of pinned nodes at write-out
+void launch_spmm_block(hipStream_t s, int N, int m, const int* off, const int* cols, const double* Hval, const double* X,
+                       int ldx, double* Y, int ldy, const int* fixed_slot);
+void launch_massmm_block(hipStream_t s, int N, int m, const int* off, const int* cols, const double* mval, const double* X,
+                         int ldx, double* Y, int ldy, const int* fixed_slot);
+size_t gram_slot_doubles(int n, int p, int q);  // doubles of the slot buffer a launch_gram of p x q over n rows needs
+void launch_gram(hipStream_t s, int n, int p, int q, const double* X, int ldx, const double* Y, int ldy, double* slots,
+                 double* G /*[p][q] = X^T Y*/);
+void launch_block_combine(hipStream_t s, int n, int k, double* S, int ld, const double* C /*[k][nz]*/, int nz, int nz0,
+                          int z0, int z1);
+void launch_block_residual(hipStream_t s, int n, int m, const double* AX, const double* MX, int ld, const double* mu,
+                           double* R, int ldr, double* slots, double* norms2 /*[m] |r|^2, [m] |Mx|^2*/);
+void launch_block_get_col(hipStream_t s, int n, const double* B, int ld, int j, double* v);
+void launch_block_set_col(hipStream_t s, int n, const double* v, const int* fixed_slot, double* B, int ld, int j);
+void launch_block_hash(hipStream_t s, int n, int m, unsigned seed, const int* fixed_slot, double* B, int ld);
 void launch_scale(hipStream_t s, int n, double a, double* v);
 void launch_scale_inv_sqrt(hipStream_t s, int n, const double* sumsq, double* v);
 void launch_newton_update(hipStream_t s, int N, const double* dv, double* v, const double* xp, const double* yp,

@@ -1398,6 +1398,7 @@ class SyncedNewtonSolver : public SolverBase {
   SyncedNewtonSolver(ElementBase* data, int n_constraints) {
     // SyncedNewton.cuh:52-85: the three element types share one device path here
     TLFEA_HANDLE_ERROR(tlfea_newton_create(static_cast<GPU_FEAT10_Data*>(data)->h, n_constraints, &s_));
+    n_coef_ = data->get_n_coef();
   }
   ~SyncedNewtonSolver() override { tlfea_newton_destroy(s_); }
   void Setup() { TLFEA_HANDLE_ERROR(tlfea_newton_setup(s_)); }
@@ -1421,8 +1422,39 @@ class SyncedNewtonSolver : public SolverBase {
   void SetVerbose(int v) { tlfea_newton_set_verbose(s_, v); }
   tlfea_newton_t handle() { return s_; }
 
+  // Modal analysis (no reference counterpart): the n_modes lowest K phi = omega^2 M phi at the current
+  // positions.  shift (rad^2/s^2) is passed to the engine as given -- zero, negative or non-finite values are refused
+  // there; the default is (2 pi 1 Hz)^2: keep it at or below the lowest omega^2 of interest.  block_extra < 0 = auto.
+  // modes[i] holds mode i as [3 n_coef], M-normalised.  Fails like every call here when the engine refuses (damping, a
+  // partitioned mesh, ...) or fewer than n_modes converge; the solver's state is unchanged either way.
+  struct ModalResult {
+    std::vector<double> omega2, freq_hz, residuals;
+    std::vector<std::vector<double>> modes;
+    int iterations = 0, converged = 0, block = 0, precond = 0;
+  };
+  static constexpr double kModalDefaultShift = 6.283185307179586 * 6.283185307179586;
+  ModalResult ModalAnalysis(int n_modes, double shift = kModalDefaultShift, double tol = 1e-8, int max_iter = 500,
+                            int block_extra = -1, unsigned seed = 0) {
+    const double two_pi = 6.283185307179586;
+    tlfea_modal_opts o{n_modes, block_extra, shift, tol, max_iter, seed};
+    const size_t k = (size_t)std::max(n_modes, 1), n = 3 * (size_t)n_coef_;
+    ModalResult r;
+    r.omega2.assign(k, 0.0);
+    r.residuals.assign(k, 0.0);
+    std::vector<double> flat(k * n, 0.0);
+    int info[4] = {0, 0, 0, 0};
+    TLFEA_HANDLE_ERROR(tlfea_newton_modal_solve(s_, &o, r.omega2.data(), flat.data(), r.residuals.data(), info));
+    for (size_t i = 0; i < k; i++) {
+      r.freq_hz.push_back(std::sqrt(std::max(r.omega2[i], 0.0)) / two_pi);
+      r.modes.emplace_back(flat.begin() + i * n, flat.begin() + (i + 1) * n);
+    }
+    r.iterations = info[0]; r.converged = info[1]; r.block = info[2]; r.precond = info[3];
+    return r;
+  }
+
  private:
   tlfea_newton_t s_ = nullptr;
+  int n_coef_ = 0;
 };
 
 // SyncedNesterovSolver (SyncedNesterov.cuh:26-260)

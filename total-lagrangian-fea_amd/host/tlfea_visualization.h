@@ -35,8 +35,9 @@ struct VisualizationUtils {
                        int arity, int vtk_type, const std::vector<PointField>& fields = {}) {
     return WriteVTU(filename, std::vector<Piece>{Piece{points, cells, arity, vtk_type, fields}});
   }
-  // one <Piece> per entry, in order
-  static bool WriteVTU(const std::string& filename, const std::vector<Piece>& pieces) {
+  // one <Piece> per entry, in order; field_data: arrays that belong to the whole file (<FieldData>, one tuple per value)
+  static bool WriteVTU(const std::string& filename, const std::vector<Piece>& pieces,
+                       const std::vector<PointField>& field_data = {}) {
     std::ofstream file(filename);
     if (!file.is_open()) {
       std::cerr << "Error: Cannot open file " << filename << " for writing" << std::endl;
@@ -46,6 +47,16 @@ struct VisualizationUtils {
     file << "<?xml version=\"1.0\"?>\n"
          << "<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\">\n"
          << "  <UnstructuredGrid>\n";
+    if (!field_data.empty()) {
+      file << "    <FieldData>\n";
+      for (const PointField& f : field_data) {
+        file << "      <DataArray type=\"Float64\" Name=\"" << f.name << "\" NumberOfTuples=\"" << f.values.size()
+             << "\" format=\"ascii\">\n         ";
+        for (double v : f.values) file << " " << v;
+        file << "\n      </DataArray>\n";
+      }
+      file << "    </FieldData>\n";
+    }
     for (const Piece& p : pieces) write_piece(file, p.points, p.cells, p.arity, p.vtk_type, p.fields);
     file << "  </UnstructuredGrid>\n</VTKFile>\n";
     return static_cast<bool>(file);
@@ -207,6 +218,69 @@ struct VisualizationUtils {
     for (int n = 0; n < n_nodes; n++) nodes.points[n] = position(x12, y12, z12, n);
     nodes.fields = fields(n_nodes, [](size_t i) { return static_cast<int>(i); });
     return WriteVTU(filename, {hexa, nodes});
+  }
+
+  // Mode shapes of SyncedNewtonSolver::ModalAnalysis (no reference counterpart).  T10: the mesh at `nodes` with
+  // one vector point field "mode_k" per mode (modes[k] = [3 n_nodes], M-normalised as returned) and the field data
+  // "frequency_hz" [n_modes].
+  static bool ExportModeShapesToVTU(const tlfea::MatrixXd& nodes, const tlfea::MatrixXi& elements,
+                                    const std::vector<std::vector<double>>& modes, const std::vector<double>& freq_hz,
+                                    const std::string& filename) {
+    const int n = nodes.rows();
+    if (modes.size() != freq_hz.size()) {
+      std::cerr << "ExportModeShapesToVTU: one frequency per mode expected" << std::endl;
+      return false;
+    }
+    Piece piece{std::vector<P3>(n), corner_tets(elements), 4, 10, {}};
+    for (int i = 0; i < n; i++) piece.points[i] = {nodes(i, 0), nodes(i, 1), nodes(i, 2)};
+    for (size_t k = 0; k < modes.size(); k++) {
+      if (modes[k].size() != 3 * (size_t)n) {
+        std::cerr << "ExportModeShapesToVTU: mode " << k << " does not hold 3 values per node" << std::endl;
+        return false;
+      }
+      piece.fields.push_back(PointField{"mode_" + std::to_string(k), 3, modes[k]});
+    }
+    return WriteVTU(filename, {piece}, {PointField{"frequency_hz", 1, freq_hz}});
+  }
+  // ANCF kinds (connectivity of 2 columns: ANCF-3243 beams, 4: ANCF-3443 shells; `width` unused for shells): the hexahedra
+  // of ExportANCF3243ToVTU / ExportANCF3443ToVTU, every corner carrying the position-coefficient part of its mesh node's
+  // mode vector (modes[k] = [3 n_coef], coefficient 4 node), a second piece with the mesh nodes themselves, and the same
+  // field data
+  static bool ExportModeShapesToVTU(const tlfea::VectorXd& x12, const tlfea::VectorXd& y12, const tlfea::VectorXd& z12,
+                                    const tlfea::MatrixXi& element_connectivity, double width, double height,
+                                    const std::vector<std::vector<double>>& modes, const std::vector<double>& freq_hz,
+                                    const std::string& filename) {
+    const int E = element_connectivity.rows(), nn = element_connectivity.cols(), n_nodes = x12.size() / 4;
+    if ((nn != 2 && nn != 4) || modes.size() != freq_hz.size()) {
+      std::cerr << "ExportModeShapesToVTU: connectivity of 2 or 4 columns and one frequency per mode expected" << std::endl;
+      return false;
+    }
+    for (const auto& m : modes)
+      if (m.size() != 12 * (size_t)n_nodes) {
+        std::cerr << "ExportModeShapesToVTU: a mode does not hold 3 values per coefficient" << std::endl;
+        return false;
+      }
+    auto fields = [&](size_t n_points, auto node_of) {
+      std::vector<PointField> out;
+      for (size_t k = 0; k < modes.size(); k++) {
+        PointField f{"mode_" + std::to_string(k), 3, std::vector<double>(3 * n_points)};
+        for (size_t i = 0; i < n_points; i++)
+          for (int c = 0; c < 3; c++) f.values[3 * i + c] = modes[k][12 * (size_t)node_of(i) + c];
+        out.push_back(f);
+      }
+      return out;
+    };
+    Piece hexa{nn == 4 ? shell_points(x12, y12, z12, element_connectivity, height)
+                       : beam_points(x12, y12, z12, element_connectivity, width, height),
+               iota_cells(E, 8), 8, 12, {}};
+    hexa.fields = fields(hexa.points.size(), [&](size_t i) {
+      const int e = static_cast<int>(i / 8), k = static_cast<int>(i % 8);
+      return element_connectivity(e, nn == 4 ? k % 4 : k / 4);
+    });
+    Piece pts{std::vector<P3>(n_nodes), iota_cells(n_nodes, 1), 1, 1, {}};
+    for (int n = 0; n < n_nodes; n++) pts.points[n] = position(x12, y12, z12, n);
+    pts.fields = fields(n_nodes, [](size_t i) { return static_cast<int>(i); });
+    return WriteVTU(filename, {hexa, pts}, {PointField{"frequency_hz", 1, freq_hz}});
   }
 
   // The sample points of GPU_ANCF*_Data::RetrieveContactPointsToCPU (rows of x, y, z, gap, pressure) as vertex cells with

@@ -4,8 +4,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .binding import (ALLREDUCE_FN, AdamWParamsC, LinSolveOptsC, NesterovParamsC, NewtonParams, VbdParamsC, check, dp, ip,
-                      load_library)
+from .binding import (ALLREDUCE_FN, AdamWParamsC, LinSolveOptsC, ModalOptsC, NesterovParamsC, NewtonParams, TlfeaError,
+                      VbdParamsC, check, dp, ip, load_library)
 
 
 @dataclass
@@ -30,6 +30,25 @@ class LinSolveOpts:
     precond: int = 0          # 0 auto | 1 Chebyshev polynomial | 2 two-level p-multigrid (T10, one GPU)
     method: int = 0           # 0 preconditioned CG | 1 sparse direct (where built)
     on_unconverged: int = 0   # 0: a solve that misses rel_tol fails the call (nothing applied) | 1: accept the iterate
+
+
+@dataclass
+class ModalResult:
+    """What ModalAnalysis returns: omega2 [n_modes] (rad^2/s^2, ascending), freq_hz = sqrt(max(omega2, 0)) / 2 pi,
+    modes [n_modes, N, 3] M-normalised, residuals [n_modes] = ||K phi - omega2 M phi|| / ((omega2 + shift) ||M phi||),
+    iterations, converged (modes that met tol), block (columns iterated), precond (0 block-Jacobi, 1 polynomial,
+    2 p-multigrid)."""
+    omega2: np.ndarray
+    freq_hz: np.ndarray
+    modes: np.ndarray
+    residuals: np.ndarray
+    iterations: int
+    converged: int
+    block: int
+    precond: int
+
+
+MODAL_DEFAULT_SHIFT = (2.0 * np.pi * 1.0) ** 2   # (2 pi 1 Hz)^2
 
 
 class SyncedNewtonSolver:
@@ -177,6 +196,51 @@ class SyncedNewtonSolver:
         y = np.zeros_like(x)
         check(self._lib.tlfea_newton_apply_hessian(self._h, dp(x), dp(y)))
         return y
+
+    def ModalAnalysis(self, n_modes, shift=None, tol=1e-8, max_iter=500, block_extra=None, seed=0):
+        """The n_modes lowest natural frequencies and mode shapes K phi = omega^2 M phi at the current positions (K the
+        tangent stiffness, contact and constraint-penalty stiffness included; pinned coefficients eliminated), by LOBPCG on
+        the device with the Newton solver's preconditioner.  shift (rad^2/s^2, default (2 pi 1 Hz)^2) makes a
+        free body's pencil definite; keep it at or below the lowest omega^2 of interest -- any positive value gives the
+        same modes, only the iteration count changes.  General linear constraints stay as the penalty H carries.  Raises
+        TlfeaError (with the modes found so far attached as .partial) when fewer than n_modes converge in max_iter; the
+        solver's state is unchanged either way."""
+        n_modes = int(n_modes)
+        o = ModalOptsC(n_modes, -1 if block_extra is None else int(block_extra),
+                       MODAL_DEFAULT_SHIFT if shift is None else float(shift), float(tol), int(max_iter), int(seed))
+        k = max(n_modes, 1)
+        w2, modes, res = np.zeros(k), np.zeros((k, 3 * self.n_coef)), np.zeros(k)
+        info = np.zeros(4, dtype=np.int32)
+        rc = self._lib.tlfea_newton_modal_solve(self._h, C.byref(o), dp(w2), dp(modes), dp(res), ip(info))
+        out = ModalResult(w2, np.sqrt(np.maximum(w2, 0.0)) / (2.0 * np.pi), modes.reshape(k, self.n_coef, 3), res,
+                          int(info[0]), int(info[1]), int(info[2]), int(info[3]))
+        if rc != 0:
+            err = TlfeaError(self._lib.tlfea_last_error().decode())
+            err.partial = out
+            raise err
+        return out
+
+    def ModalApplyBlock(self, X, which=0, apply_mask=False):
+        """Y = H X (which 0) or (M (x) I3) X (which 1) for a block X [3N, m], m <= 32, with the current H (test hook)"""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        assert X.ndim == 2 and X.shape[0] == 3 * self.n_coef
+        Y = np.zeros_like(X)
+        check(self._lib.tlfea_newton_modal_apply_block(self._h, int(which), X.shape[1], dp(X), dp(Y), int(bool(apply_mask))))
+        return Y
+
+    def ModalGram(self, X, Y):
+        """G = X^T Y for blocks [3N, p], [3N, q], p, q <= 96, by the modal solve's deterministic Gram kernels (test hook)"""
+        X, Y = np.ascontiguousarray(X, dtype=np.float64), np.ascontiguousarray(Y, dtype=np.float64)
+        assert X.ndim == 2 and Y.ndim == 2 and X.shape[0] == Y.shape[0] == 3 * self.n_coef
+        G = np.zeros((X.shape[1], Y.shape[1]))
+        check(self._lib.tlfea_newton_modal_gram(self._h, X.shape[1], Y.shape[1], dp(X), dp(Y), dp(G)))
+        return G
+
+    def ModalTimeSpmm(self, m, reps=20):
+        """mean ms of one block product Y = H X with m columns over `reps` back-to-back launches (hipEvents)"""
+        out = C.c_double()
+        check(self._lib.tlfea_newton_modal_time_spmm(self._h, int(m), int(reps), C.byref(out)))
+        return out.value
 
     def ApplyHessianMatfree(self, x):
         """y = H x from the matrix-free pair of the CG iteration (raises where it is not eligible)"""
