@@ -557,6 +557,23 @@ int tlfea_newton_pmg_cycle_info(tlfea_newton_t s, int *out6);
  * kappa (rounded), block size of the diagonal scaling of its operator -- 3 (per coefficient vector / node) or 12 (ANCF:
  * the four coefficient vectors of a node together, as a change of variables L^-1 H L^-T). */
 int tlfea_newton_polynomial_info(tlfea_newton_t s, int *out3);
+/* Test hooks: the CG preconditioner as an operator.  z = M^-1 r for host vectors of 3N with the current assembled H: the
+ * warm state of the lambda_max estimates is reset, the preconditioner is set up as a solve sets it up (its cold lambda_max
+ * estimate started from r; from a vector of ones when r is zero) and the function a CG iteration calls is applied once.
+ * The _block form sets the operator up once, from the first vector, and applies it to m vectors R [m][3N] -> Z [m][3N]
+ * (what a symmetry check needs: the operator depends on the start vector through lambda_max).  The warm state of the
+ * linear solver is restored on return.  Refused on a partitioned mesh and with method = 1 (sparse direct). */
+int tlfea_newton_apply_preconditioner(tlfea_newton_t s, const double *r, double *z);
+int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, const double *R, double *Z);
+/* What the last set-up (a solve or the hook above) left on the device.  iout16: [0] preconditioner (0 block-Jacobi,
+ * 1 polynomial, 2 p-multigrid), [1] levels (0, 2, 3), [2] polynomial degree, [3] fine smoother terms ks, [4..8] offsets of
+ * the residual pair, the restart pair, the ks smoother weights, the vertex-level table and the level-3 polynomial in the
+ * coefficient table, [9] vertex-level smoother terms ks2, [10] vertex-level polynomial degree kc, [11] level-3 degree k3,
+ * [12] smoother kind (1 first-kind Chebyshev, 3 / 4 fourth kind), [13] doubles written to coef, [14] block size of the
+ * polynomial's scaling (3 or 12), [15] matrix bits.  dout8: [0..2] lambda_max estimates (fine, vertex level, level 3) as
+ * they stand now, [3] lam_safety, [4..6] the estimates of the last tlfea_newton_apply_preconditioner set-up.  coef: the
+ * uploaded coefficient table copied back (pairs (c1, c2) per step), at most coef_cap doubles. */
+int tlfea_newton_preconditioner_state(tlfea_newton_t s, int *iout16, double *dout8, double *coef, int coef_cap);
 
 /* ---- SyncedAdamWNocoopSolver (SyncedAdamWNocoop.cuh:22-198, SyncedAdamWNocoop.cu:262-500) ------------------------
  * First-order ALM solver on the same velocity unknowns: per inner iteration one AdamW moment update, x = x_prev + dt v,

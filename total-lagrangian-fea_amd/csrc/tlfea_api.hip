@@ -2327,6 +2327,7 @@ struct tlfea_newton_s {
   int* d_own = nullptr;
   double* d_sc_mask = nullptr;
   double lam_max_loc = 0.0;
+  double hook_lam[3] = {0.0, 0.0, 0.0};  // lambda_max estimates of the last tlfea_newton_apply_preconditioner set-up
   bool sync_before_cb = true;
   tlfea_allreduce_fn ar = nullptr;
   void* ar_user = nullptr;
@@ -4654,7 +4655,18 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
   };
   if (!init_done) launch_cheb32_init(s->stream, Nf, Dinv_f, d_r, s->d_sc, cf, f_d, f_z, f_r);
   for (int k = 1; k < ks; k++) fine(cf + 2 * k, false, betas + k);
-  fine(cf + o_res, false, nullptr);
+  if (weighted) {
+    // Weighted z^ updates: the residual the recurrence carries is the UNWEIGHTED iterate's, not that of z^ -- restricting it
+    // made the cycle unsymmetric (defect 3e-4 on res2; tests/test_gpu_precond_operator.py, configuration 11).  Form
+    // res^ = S r - Hs z^ itself: start vectors into the spare buffers (res^ := S r), then one pass with z^ as the direction
+    // and the pair (0, 0), which leaves z^ as it is.
+    launch_cheb32_init(s->stream, Nf, Dinv_f, d_r, s->d_sc, cf, f_d2, f_z2, f_r2);
+    C32Bnd bnd = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
+    launch_cheb32(s->stream, Nf, d->nnz_coef, inc_f, s->d_B8, s->d_B1, fine_bits(s), Dinv_f, s->d_sc, f_z, cf + o_res, f_d2, f_z, f_z2,
+                  f_r2, f_r, d_r, d_z, rz_part, false, bnd);
+    std::swap(f_z, f_z2);
+  } else
+    fine(cf + o_res, false, nullptr);
   // coarse correction
   launch_pmg_restrict_init(s->stream, Nc, m.d_child_off, m.d_child, m.d_child_w, f_r, s->d_sc, m.d_sc_c, Dinv_fc, cf + o_c,
                            c_d, c_z, c_r);
@@ -4737,6 +4749,26 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
   return 0;
 }
 
+// z = M^-1 r with the preconditioner precond_setup() prepared: the p-multigrid cycle, the Chebyshev polynomial (12 x 12
+// node blocks on the ANCF kinds: z = L^-T p(L^-1 H L^-T) L^-1 r, the polynomial's r.z slots are r^.z^ = r.z) or the inverse
+// 3 x 3 diagonal blocks.  The one function behind a CG iteration of pcg(), the modal solve and the test hook
+// tlfea_newton_apply_preconditioner; the last fine step leaves the r.z slots in rz_part.  init_done: the previous CG
+// iteration's update kernel already wrote the fp32 start vectors.
+static int precond_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* rz_part, bool init_done) {
+  if (cheb_degree_eff(s) <= 1) {
+    launch_apply_dinv(s->stream, s->N, s->d_Dinv, d_r, d_z);
+    return 0;
+  }
+  if (precond_eff(s) == 2) return pmg_apply(s, d_r, d_z, rz_part, init_done);
+  if (blk12_now(s)) {
+    launch_blk12_apply(s->stream, s->N / 4, s->d_L12inv_f, false, d_r, s->d_cd);
+    TRY(cheb_apply(s, s->d_cd, s->d_cd2, rz_part, false));
+    launch_blk12_apply(s->stream, s->N / 4, s->d_L12inv_f, true, s->d_cd2, d_z);
+    return 0;
+  }
+  return cheb_apply(s, d_r, d_z, rz_part, init_done);
+}
+
 // Enqueue CG iteration `it` (parity cur = it & 1 selects the r.z slot pair and, in the fused variant, which of the
 // two direction buffers is read).  Everything an iteration needs from the previous one (alpha, beta, Chebyshev
 // coefficients) is read from device memory, so iterations >= 1 of either parity are the SAME launch sequence.
@@ -4784,14 +4816,7 @@ static int enqueue_cg_iteration_impl(tlfea_newton_t s, double* d_x, bool first, 
   const double* wown = hal ? s->d_w : nullptr;
   if (deg > 1) {
     // polynomial preconditioner: z = Cheb(r), r.z slots -> part(cur)   (deg-1 SpMV launches, no reductions)
-    if (precond_eff(s) == 2)
-      TRY(pmg_apply(s, s->d_r, s->d_zv, part(s, cur), fuse_init && !first));
-    else if (b12) {  // z = L^-T p(L^-1 H L^-T) L^-1 r; the polynomial's r.z slots are r^.z^ = r.z
-      launch_blk12_apply(s->stream, N / 4, s->d_L12inv_f, false, s->d_r, s->d_cd);
-      TRY(cheb_apply(s, s->d_cd, s->d_cd2, part(s, cur), false));
-      launch_blk12_apply(s->stream, N / 4, s->d_L12inv_f, true, s->d_cd2, s->d_zv);
-    } else
-      TRY(cheb_apply(s, s->d_r, s->d_zv, part(s, cur), fuse_init && !first));
+    TRY(precond_apply(s, s->d_r, s->d_zv, part(s, cur), fuse_init && !first));
     if ((s->ar && !(s->d_own && cheb_bits_eff(s) != 64)) || hal) TRY(parts_sum(s, part(s, cur)));
     if (hal) TRY(halo_refresh_f64(s, 0, 1, 3, s->d_zv));
   }
@@ -5706,22 +5731,6 @@ static void modal_product(tlfea_newton_t s, int which, int m, const double* X, i
   if (which == 0) launch_spmm_block(s->stream, s->N, m, d->d_off, d->d_cols, s->d_H, X, ldx, Y, ldy, mask);
   else launch_massmm_block(s->stream, s->N, m, d->d_off, d->d_cols, d->d_mval, X, ldx, Y, ldy, mask);
 }
-// z = T r with the preconditioner precond_setup() prepared: the p-multigrid cycle, the Chebyshev polynomial (12 x 12 node
-// blocks on the ANCF kinds) or the inverse 3 x 3 diagonal blocks -- what a CG iteration of pcg() applies
-static int modal_precond(tlfea_newton_t s, const double* d_r, double* d_z) {
-  if (cheb_degree_eff(s) <= 1) {
-    launch_apply_dinv(s->stream, s->N, s->d_Dinv, d_r, d_z);
-    return 0;
-  }
-  if (precond_eff(s) == 2) return pmg_apply(s, d_r, d_z, part(s, 0), false);
-  if (blk12_now(s)) {
-    launch_blk12_apply(s->stream, s->N / 4, s->d_L12inv_f, false, d_r, s->d_cd);
-    TRY(cheb_apply(s, s->d_cd, s->d_cd2, part(s, 0), false));
-    launch_blk12_apply(s->stream, s->N / 4, s->d_L12inv_f, true, s->d_cd2, d_z);
-    return 0;
-  }
-  return cheb_apply(s, d_r, d_z, part(s, 0), false);
-}
 
 static int modal_iterate(tlfea_newton_t s, const tlfea_modal_opts& o, int m, double* omega2, double* modes, double* resid,
                          int* info) {
@@ -5827,7 +5836,7 @@ static int modal_iterate(tlfea_newton_t s, const tlfea_modal_opts& o, int m, dou
         continue;
       }
       launch_block_get_col(s->stream, n, R, m, j, s->d_r);
-      TRY(modal_precond(s, s->d_r, s->d_zv));
+      TRY(precond_apply(s, s->d_r, s->d_zv, part(s, 0), false));
       launch_block_set_col(s->stream, n, s->d_zv, mask, S, ld, m + j);
       idx.push_back(m + j);
     }
@@ -5980,6 +5989,104 @@ extern "C" int tlfea_newton_modal_apply_block(tlfea_newton_t s, int which, int m
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s->stream));
   HIP_TRY(hipMemcpy(Y, dY, cnt * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+// Test hooks: the preconditioner as an operator (tests/test_gpu_precond_operator.py).  The set-up is the one of a solve
+// (precond_setup stages 0 and 1 back to back, as the modal solve runs them) from cold lambda_max estimates; the warm state
+// of the linear solver is put back afterwards, as tlfea_newton_modal_solve does.
+extern "C" int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, const double* R, double* Z) {
+  if (!s || !R || !Z) return fail("tlfea_newton_apply_preconditioner: null argument");
+  if (m < 1) return fail("tlfea_newton_apply_preconditioner: needs at least one vector");
+  if (!s->d_H) return fail("tlfea_newton_apply_preconditioner: no assembled H");
+  if (dist_on(s)) return fail("tlfea_newton_apply_preconditioner: not available on a partitioned mesh (set_interface / set_halo is active)");
+  if (s->lin.method == 1) return fail("tlfea_newton_apply_preconditioner: method = 1 (sparse direct) has no preconditioner");
+  const size_t n = 3 * (size_t)s->N;
+  const size_t nc = s->pmg.d_eigv_c ? 3 * (size_t)s->pmg.Nc : 0, n3 = s->pmg.agg.d_eigv3 ? 3 * (size_t)s->pmg.agg.N3 : 0;
+  ModalWork wk;
+  double *d_save = nullptr, *dR = nullptr, *dZ = nullptr;
+  TRY(wk.alloc(&d_save, n + nc + n3));
+  TRY(wk.alloc(&dR, (size_t)m * n));
+  TRY(wk.alloc(&dZ, (size_t)m * n));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpy(d_save, s->d_eigv, n * sizeof(double), hipMemcpyDeviceToDevice));
+  if (nc) HIP_TRY(hipMemcpy(d_save + n, s->pmg.d_eigv_c, nc * sizeof(double), hipMemcpyDeviceToDevice));
+  if (n3) HIP_TRY(hipMemcpy(d_save + n + nc, s->pmg.agg.d_eigv3, n3 * sizeof(double), hipMemcpyDeviceToDevice));
+  HIP_TRY(hipMemcpy(dR, R, (size_t)m * n * sizeof(double), hipMemcpyHostToDevice));
+  const double lam_max0 = s->lam_max, lam_loc0 = s->lam_max_loc, lam_c0 = s->pmg.lam_c, lam30 = s->pmg.agg.lam3;
+  s->lam_max = s->lam_max_loc = s->pmg.lam_c = s->pmg.agg.lam3 = 0.0;  // cold estimates: the result depends on no earlier solve
+  auto run = [&]() -> int {
+    // start vector of the fine lambda_max estimate: the first vector, ones where that is zero (no estimate from nothing)
+    bool zero = true;
+    for (size_t k = 0; k < n && zero; k++) zero = R[k] == 0.0;
+    if (zero) {
+      std::vector<double> ones(n, 1.0);
+      HIP_TRY(hipMemcpy(s->d_b, ones.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+      HIP_TRY(hipMemcpy(s->d_b, dR, n * sizeof(double), hipMemcpyDeviceToDevice));
+    }
+    TRY(precond_setup(s, s->d_b, 0));
+    TRY(precond_setup(s, s->d_b, 1));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (cheb_bits_eff(s) != 64 && blk12_now(s)) {
+      int bad = 0;
+      HIP_TRY(hipMemcpy(&bad, s->d_blk12_err, sizeof(int), hipMemcpyDeviceToHost));
+      if (bad) return fail("tlfea_newton_apply_preconditioner: a 12 x 12 node block of H is not positive definite (H is not SPD)");
+    }
+    for (int k = 0; k < m; k++) TRY(precond_apply(s, dR + k * n, dZ + k * n, part(s, 0), false));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(Z, dZ, (size_t)m * n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  const std::string why = rc ? g_err : std::string();
+  (void)hipStreamSynchronize(s->stream);
+  s->hook_lam[0] = s->lam_max; s->hook_lam[1] = s->pmg.lam_c; s->hook_lam[2] = s->pmg.agg.lam3;
+  s->lam_max = lam_max0; s->lam_max_loc = lam_loc0; s->pmg.lam_c = lam_c0; s->pmg.agg.lam3 = lam30;
+  // the set-up may have built the p-multigrid levels for the first time: their kept vectors did not exist at the save
+  (void)hipMemcpy(s->d_eigv, d_save, n * sizeof(double), hipMemcpyDeviceToDevice);
+  if (nc) (void)hipMemcpy(s->pmg.d_eigv_c, d_save + n, nc * sizeof(double), hipMemcpyDeviceToDevice);
+  if (n3) (void)hipMemcpy(s->pmg.agg.d_eigv3, d_save + n + nc, n3 * sizeof(double), hipMemcpyDeviceToDevice);
+  if (rc) g_err = why;
+  return rc;
+}
+extern "C" int tlfea_newton_apply_preconditioner(tlfea_newton_t s, const double* r, double* z) {
+  return tlfea_newton_apply_preconditioner_block(s, 1, r, z);
+}
+extern "C" int tlfea_newton_preconditioner_state(tlfea_newton_t s, int* iout16, double* dout8, double* coef, int coef_cap) {
+  if (!s || !iout16 || !dout8 || !coef) return fail("tlfea_newton_preconditioner_state: null argument");
+  for (int k = 0; k < 16; k++) iout16[k] = 0;
+  for (int k = 0; k < 8; k++) dout8[k] = 0.0;
+  const int deg = cheb_degree_eff(s);
+  const bool pmg = deg > 1 && precond_eff(s) == 2 && s->pmg.ok && s->pmg.d_coef;
+  const bool l3 = pmg && s->pmg.agg.ok;
+  iout16[0] = deg > 1 ? (pmg ? 2 : 1) : 0;
+  iout16[1] = pmg ? (l3 ? 3 : 2) : 0;
+  iout16[2] = deg;
+  iout16[12] = pmg_smoother_kind();
+  iout16[14] = blk12_now(s) ? 12 : 3;
+  iout16[15] = cheb_bits_eff(s);
+  int n_coef = 0;
+  const double* src = nullptr;
+  if (pmg) {
+    iout16[3] = pmg_ks(s);
+    iout16[4] = pmg_cf_resid(s); iout16[5] = pmg_cf_restart(s); iout16[6] = pmg_cf_beta(s); iout16[7] = pmg_cf_coarse(s);
+    iout16[8] = l3 ? pmg_cf_level3(s) : 0;
+    iout16[9] = l3 ? pmg_ks2(s) : 0;
+    iout16[10] = l3 ? 0 : pmg_coarse_degree_eff(s);
+    iout16[11] = l3 ? pmg_level3_degree(s->pmg.agg.N3) : 0;
+    n_coef = l3 ? pmg_cf_level3(s) + 2 * iout16[11] : pmg_cf_coarse(s) + 2 * iout16[10];
+    src = s->pmg.d_coef;
+  } else if (deg > 1) {
+    n_coef = 2 * deg;
+    src = s->d_coef;
+  }
+  if (n_coef > coef_cap) return fail("tlfea_newton_preconditioner_state: the coefficient table has " + std::to_string(n_coef) + " doubles, coef_cap is smaller");
+  iout16[13] = n_coef;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (n_coef) HIP_TRY(hipMemcpy(coef, src, (size_t)n_coef * sizeof(double), hipMemcpyDeviceToHost));
+  dout8[0] = s->lam_max; dout8[1] = s->pmg.lam_c; dout8[2] = s->pmg.agg.lam3; dout8[3] = s->lam_safety;
+  dout8[4] = s->hook_lam[0]; dout8[5] = s->hook_lam[1]; dout8[6] = s->hook_lam[2];
   return 0;
 }
 // Mean milliseconds of one spmm_block launch (Y = H X, m columns, masked) over `reps` back-to-back launches between one

@@ -125,6 +125,32 @@ class SyncedNewtonSolver:
         check(self._lib.tlfea_newton_polynomial_info(self._h, out))
         return dict(zip(("degree", "kappa", "block"), list(out)))
 
+    def ApplyPreconditioner(self, r):
+        """z = M^-1 r with the CG preconditioner of the current assembled H, set up from cold lambda_max estimates started
+        at r (test hook).  r [3N], or a block [m, 3N]: the operator is then set up once, from r[0], and applied to every
+        row -- one fixed operator for all of them.  The solver's warm state is left as it was."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.shape[-1] == 3 * self.n_coef and r.ndim in (1, 2)
+        z = np.zeros_like(r)
+        if r.ndim == 1:
+            check(self._lib.tlfea_newton_apply_preconditioner(self._h, dp(r), dp(z)))
+        else:
+            check(self._lib.tlfea_newton_apply_preconditioner_block(self._h, r.shape[0], dp(r), dp(z)))
+        return z
+
+    def GetPreconditionerState(self):
+        """dict of what the last set-up (a solve or ApplyPreconditioner) left on the device: the coefficient table `coef`
+        (pairs (c1, c2) per step), its layout (ks, cf_resid, cf_restart, cf_beta, cf_coarse, cf_level3, ks2, kc, k3),
+        precond / levels / degree / smoother / block / bits, the lambda_max estimates and lam_safety (test hook)."""
+        io, do, coef = (C.c_int * 16)(), (C.c_double * 8)(), np.zeros(512)
+        check(self._lib.tlfea_newton_preconditioner_state(self._h, io, do, dp(coef), coef.size))
+        names = ("precond", "levels", "degree", "ks", "cf_resid", "cf_restart", "cf_beta", "cf_coarse", "cf_level3", "ks2",
+                 "kc", "k3", "smoother", "n_coef", "block", "bits")
+        out = dict(zip(names, list(io)))
+        out.update(coef=coef[:out["n_coef"]].copy(), lam_max=do[0], lam_c=do[1], lam3=do[2], lam_safety=do[3],
+                   hook_lam=(do[4], do[5], do[6]))
+        return out
+
     def GetPmgLevel3Info(self):
         """(aggregates, 3x3 blocks, polynomial degree) of the third level, (0, 0, 0) when the cycle has two levels"""
         na, nnz, deg = C.c_int(), C.c_int(), C.c_int()
