@@ -389,6 +389,17 @@ int tlfea_newton_pmg_coarse_degree(tlfea_newton_t s);
  * (9 nnz values in the DOF-level layout of H: node row -> [d][k][e]) */
 int tlfea_newton_pmg_sizes(tlfea_newton_t s, int *n_coarse, int *nnz_coarse_blocks);
 int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int *par0, int *par1, int *c_off, int *c_cols, double *Hc);
+/* Test hooks of the restricted fine operator R = S_c P^T S_f^-1 Hs, through which the V-cycle restricts the fine residual
+ * (one GPU, first-kind smoother, 16- or 32-bit fine copy; TLFEA_PMG_RESTRICT_OP=0 keeps the fine residual pass).  They
+ * copy back what the LAST preconditioner set-up (a solve or tlfea_newton_apply_preconditioner) left on the device and
+ * rebuild nothing.  sizes: out6 = [0] 1 when that set-up built R, [1] vertex nodes Nc (rows of R), [2] 3x3 blocks of R,
+ * [3] (child, fine block) contributions, [4] 3x3 blocks of H, [5] bits of the fine copy.  restrict_op_retrieve: R as it
+ * is stored, node-level CSR off [Nc+1] / cols (ascending) and vals [blocks][9], each block row-major, fp32 widened to
+ * double.  fine_copy_retrieve: the fine level's stored copy Hs = S_f H S_f in the node-block CSR of H (off [N+1], cols,
+ * vals [blocks][9], fp16 / fp32 widened to double) and the scalings sc_f [3N], sc_c [3 Nc]. */
+int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int *out6);
+int tlfea_newton_pmg_restrict_op_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals);
+int tlfea_newton_pmg_fine_copy_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals, double *sc_f, double *sc_c);
 int tlfea_newton_hessian_nnz(tlfea_newton_t s, int *nnz);
 /* H in the reference's DOF-level CSR (SyncedNewton.cu:163-205): rows 3N, sorted columns */
 int tlfea_newton_retrieve_hessian_csr(tlfea_newton_t s, int *row_offsets, int *col_indices, double *values);

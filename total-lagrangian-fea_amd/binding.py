@@ -169,6 +169,19 @@ def _modal_signatures(lib):
         getattr(lib, name).restype = C.c_int
 
 
+def _pmg_signatures(lib):
+    """ctypes signatures of the p-multigrid test hooks (the handle must not travel as a C int)."""
+    vp = C.c_void_p
+    sig = {"tlfea_newton_pmg_sizes": [vp, c_ip, c_ip],
+           "tlfea_newton_pmg_retrieve": [vp, c_ip, c_ip, c_ip, c_ip, c_dp],
+           "tlfea_newton_pmg_restrict_op_sizes": [vp, c_ip],
+           "tlfea_newton_pmg_restrict_op_retrieve": [vp, c_ip, c_ip, c_dp],
+           "tlfea_newton_pmg_fine_copy_retrieve": [vp, c_ip, c_ip, c_dp, c_dp, c_dp]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+
+
 def _contact_signatures(lib):
     """ctypes signatures of the tlfea_contact_* entry points (pointer arguments are c_void_p: device pointers pass as
     integers, host arrays through dp / ip)."""
@@ -237,6 +250,7 @@ def load_library():
     _stress_signatures(lib)
     _load_signatures(lib)
     _modal_signatures(lib)
+    _pmg_signatures(lib)
     _LIB = lib
     return lib
 

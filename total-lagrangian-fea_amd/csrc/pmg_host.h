@@ -11,7 +11,9 @@
 #ifndef TLFEA_PMG_HOST_H_
 #define TLFEA_PMG_HOST_H_
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace tlfea {
@@ -225,6 +227,120 @@ inline bool pmg_build_ancf(int N, const int* off, const int* cols, PmgHost& o) {
   o.child_w.assign((size_t)Nc, 1.f);
   for (int I = 0; I <= Nc; I++) o.child_off[I] = I;
   for (int I = 0; I < Nc; I++) o.child[I] = 4 * I;
+  return true;
+}
+
+// ---- restricted fine operator  R = S_c P^T S_f^-1 Hs  (one node row per coarse node) ---------------------------------
+// The V-cycle restricts the residual of the smoothed iterate, res_B = res_A - Hs d_last.  The residual is linear in the
+// direction, so the pass that forms res_B only to restrict it can be replaced by  r^_c = S_c P^T S_f^-1 res_A - R d_last
+// with R stored: 0.29 x the blocks of H on a structured T10 bar.  Here the integer part, built once per mesh:
+//   row I of R  = union of the fine rows of I's children (the vertex itself, weight 1; its mid-edge nodes, weight 1/2),
+//                 columns ascending;
+//   per R block = the list of (child, fine block) pairs that feed it, children in ascending fine id -- the build kernel
+//                 gathers them in that order (fixed summation order, no atomics).
+struct RopHost {
+  int Nc = 0, nnz = 0, n_con = 0;
+  std::vector<int> off, cols;       // [Nc+1], [nnz] node-level CSR of R, columns ascending
+  std::vector<int> ch_off, ch;      // children of every coarse node in ASCENDING fine id (PmgHost keeps the vertex first)
+  std::vector<float> ch_w;          // 1 or 1/2
+  std::vector<int> con_off;         // [nnz+1] contributions to each R block
+  std::vector<int> con_blk;         // fine block index off[i] + k
+  std::vector<unsigned char> con_ord;  // position of the child i in ch[ch_off[I] ..]
+};
+
+// off/cols: fine node adjacency (sorted).  Returns false when R does not fit the 32-bit / 8-bit index types.
+inline bool pmg_restrict_op_build(int N, const int* off, const int* cols, const PmgHost& h, RopHost& o) {
+  o = RopHost();
+  const int Nc = h.Nc;
+  o.Nc = Nc;
+  o.ch_off = h.child_off;
+  o.ch.resize(h.child.size());
+  o.ch_w.resize(h.child.size());
+  bool fits = true;
+  for (int I = 0; I < Nc; I++) {
+    const int c0 = h.child_off[I], nch = h.child_off[I + 1] - c0;
+    if (nch > 256) fits = false;
+    std::vector<std::pair<int, float>> cw((size_t)nch);
+    for (int t = 0; t < nch; t++) cw[t] = {h.child[c0 + t], h.child_w[c0 + t]};
+    std::sort(cw.begin(), cw.end());
+    for (int t = 0; t < nch; t++) {
+      o.ch[c0 + t] = cw[t].first;
+      o.ch_w[c0 + t] = cw[t].second;
+    }
+  }
+  if (!fits) return false;
+  // pass 1: row lengths
+  std::vector<long long> roff((size_t)Nc + 1, 0);
+#pragma omp parallel
+  {
+    std::vector<int> row;
+#pragma omp for schedule(dynamic, 1024)
+    for (int I = 0; I < Nc; I++) {
+      row.clear();
+      for (int t = o.ch_off[I]; t < o.ch_off[I + 1]; t++) {
+        const int i = o.ch[t];
+        row.insert(row.end(), cols + off[i], cols + off[i + 1]);
+      }
+      std::sort(row.begin(), row.end());
+      roff[I + 1] = (long long)(std::unique(row.begin(), row.end()) - row.begin());
+    }
+  }
+  long long n_con = 0;
+  for (int I = 0; I < Nc; I++) {
+    roff[I + 1] += roff[I];
+    for (int t = o.ch_off[I]; t < o.ch_off[I + 1]; t++) n_con += off[o.ch[t] + 1] - off[o.ch[t]];
+  }
+  if (roff[Nc] > 2000000000LL || n_con > 2000000000LL) return false;
+  o.nnz = (int)roff[Nc];
+  o.n_con = (int)n_con;
+  o.off.assign(roff.begin(), roff.end());
+  o.cols.resize((size_t)o.nnz);
+  o.con_off.assign((size_t)o.nnz + 1, 0);
+  // pass 2: columns and the number of contributions per block
+#pragma omp parallel
+  {
+    std::vector<int> row;
+#pragma omp for schedule(dynamic, 1024)
+    for (int I = 0; I < Nc; I++) {
+      row.clear();
+      for (int t = o.ch_off[I]; t < o.ch_off[I + 1]; t++) {
+        const int i = o.ch[t];
+        row.insert(row.end(), cols + off[i], cols + off[i + 1]);
+      }
+      std::sort(row.begin(), row.end());
+      row.erase(std::unique(row.begin(), row.end()), row.end());
+      std::copy(row.begin(), row.end(), o.cols.begin() + o.off[I]);
+      for (int t = o.ch_off[I]; t < o.ch_off[I + 1]; t++) {
+        const int i = o.ch[t];
+        for (int g = off[i]; g < off[i + 1]; g++) {
+          const int p = (int)(std::lower_bound(row.begin(), row.end(), cols[g]) - row.begin());
+          o.con_off[(size_t)o.off[I] + p + 1]++;  // rows are disjoint ranges of con_off: no race
+        }
+      }
+    }
+  }
+  for (int b = 0; b < o.nnz; b++) o.con_off[b + 1] += o.con_off[b];
+  o.con_blk.assign((size_t)o.n_con, 0);
+  o.con_ord.assign((size_t)o.n_con, 0);
+  // pass 3: fill, children ascending (so every block's list is in ascending child order)
+#pragma omp parallel
+  {
+    std::vector<int> cur;
+#pragma omp for schedule(dynamic, 1024)
+    for (int I = 0; I < Nc; I++) {
+      const int r0 = o.off[I], len = o.off[I + 1] - r0;
+      cur.assign(o.con_off.begin() + r0, o.con_off.begin() + r0 + len);
+      const int* row = o.cols.data() + r0;
+      for (int t = o.ch_off[I]; t < o.ch_off[I + 1]; t++) {
+        const int i = o.ch[t];
+        for (int g = off[i]; g < off[i + 1]; g++) {
+          const int p = (int)(std::lower_bound(row, row + len, cols[g]) - row);
+          o.con_blk[cur[p]] = g;
+          o.con_ord[cur[p]++] = (unsigned char)(t - o.ch_off[I]);
+        }
+      }
+    }
+  }
   return true;
 }
 

@@ -1467,12 +1467,12 @@ __global__ __launch_bounds__(256) void pmg_prolong_kernel(int N, const int* __re
                                                          const float* __restrict__ z_c,
                                                          const double* __restrict__ sc_c,
                                                          const double* __restrict__ sc_f, float* __restrict__ z_f,
-                                                         float* __restrict__ d_f) {
+                                                         float* __restrict__ d_f, int add) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const int a = par0[i], b = par1[i];
   if (a < 0) {  // no coarse parent (ANCF gradient coefficients): the correction is zero here
-    d_f[3 * i] = d_f[3 * i + 1] = d_f[3 * i + 2] = 0.f;
+    if (!add) d_f[3 * i] = d_f[3 * i + 1] = d_f[3 * i + 2] = 0.f;
     return;
   }
 #pragma unroll
@@ -1480,13 +1480,163 @@ __global__ __launch_bounds__(256) void pmg_prolong_kernel(int N, const int* __re
     const double ea = sc_c[3 * a + c] * (double)z_c[3 * a + c];
     const double e = (a == b) ? ea : 0.5 * (ea + sc_c[3 * b + c] * (double)z_c[3 * b + c]);
     const float corr = (float)(e / sc_f[3 * i + c]);
-    d_f[3 * i + c] = corr;
+    d_f[3 * i + c] = add ? d_f[3 * i + c] + corr : corr;
     z_f[3 * i + c] += corr;
   }
 }
+// add_to_d: d := d + corr^ (the restricted-operator cycle: the restart pass then subtracts Hs (d_last + corr^) at once)
 void launch_pmg_prolong(hipStream_t s, int N, const int* par0, const int* par1, const float* z_c, const double* sc_c,
-                        const double* sc_f, float* z_f, float* d_f) {
-  hipLaunchKernelGGL(pmg_prolong_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, par0, par1, z_c, sc_c, sc_f, z_f, d_f);
+                        const double* sc_f, float* z_f, float* d_f, bool add_to_d) {
+  hipLaunchKernelGGL(pmg_prolong_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, par0, par1, z_c, sc_c, sc_f, z_f, d_f,
+                     add_to_d ? 1 : 0);
+}
+
+// ---- restricted fine operator R = S_c P^T S_f^-1 Hs (pmg_host.h pmg_restrict_op_build) ------------------------------
+// Build, once per solve:  R[I,j]_de = sc_c[I,d] * sum_{i in children(I)} w_i Hs[i,j]_de / sc_f[i,d]  with Hs AS STORED
+// (fp16 or fp32, widened): the cycle with R is then the same operator as the cycle with the extra pass, up to the fp32
+// work vectors.  The sum runs in fp64 over the block's contribution list (ascending child), rounded once to fp32 -- R
+// itself must not be 16-bit: fp16(P^T Hs) != P^T fp16(Hs) breaks the symmetry of the cycle.  32 lanes per coarse row,
+// a lane per R block; R is stored like the streamed copies (8 + 1 entries per block) so that cheb32's row product
+// reads it.
+template <typename HT>
+__global__ __launch_bounds__(256) void pmg_rop_build_kernel(
+    int Nc, const int* __restrict__ r_off, const int* __restrict__ con_off, const int* __restrict__ con_blk,
+    const unsigned char* __restrict__ con_ord, const int* __restrict__ ch_off, const int* __restrict__ ch,
+    const float* __restrict__ ch_w, const Blk8<HT>* __restrict__ B8, const HT* __restrict__ B1,
+    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8,
+    float* __restrict__ R1) {
+  const int lane = threadIdx.x & 31;
+  const int I = blockIdx.x * 8 + (threadIdx.x >> 5);
+  if (I >= Nc) return;
+  const double sI[3] = {sc_c[3 * I], sc_c[3 * I + 1], sc_c[3 * I + 2]};
+  const int c0 = ch_off[I], b1 = r_off[I + 1];
+  for (int b = r_off[I] + lane; b < b1; b += 32) {
+    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int t1 = con_off[b + 1];
+    for (int t = con_off[b]; t < t1; t++) {
+      const int g = con_blk[t], ct = c0 + (int)con_ord[t], i = ch[ct];
+      const double w = (double)ch_w[ct];
+      const Blk8<HT> v = B8[g];
+      const HT v8 = B1[g];
+      const double f[3] = {w / sc_f[3 * i], w / sc_f[3 * i + 1], w / sc_f[3 * i + 2]};
+#pragma unroll
+      for (int k = 0; k < 8; k++) acc[k] += f[k / 3] * (double)(float)v.v[k];
+      acc[8] += f[2] * (double)(float)v8;
+    }
+    Blk8<float> out;
+#pragma unroll
+    for (int k = 0; k < 8; k++) out.v[k] = (float)(sI[k / 3] * acc[k]);
+    R8[b] = out;
+    R1[b] = (float)(sI[2] * acc[8]);
+  }
+}
+void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
+                          const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,
+                          const void* B1, int bits, const double* sc_f, const double* sc_c, void* R8, float* R1) {
+  const dim3 g((Nc + 7) / 8), b(256);
+  if (bits == 16)
+    hipLaunchKernelGGL((pmg_rop_build_kernel<_Float16>), g, b, 0, s, Nc, r_off, con_off, con_blk, con_ord, ch_off, ch, ch_w,
+                       (const Blk8<_Float16>*)B8, (const _Float16*)B1, sc_f, sc_c, (Blk8<float>*)R8, R1);
+  else
+    hipLaunchKernelGGL((pmg_rop_build_kernel<float>), g, b, 0, s, Nc, r_off, con_off, con_blk, con_ord, ch_off, ch, ch_w,
+                       (const Blk8<float>*)B8, (const float*)B1, sc_f, sc_c, (Blk8<float>*)R8, R1);
+}
+
+// Restriction with the stored operator, fused with the coarse start vectors: everything pmg_restrict_init_kernel does
+// with res_f = res_A (the residual BEFORE the last pre-smoothing direction was applied), and the coarse right-hand side
+// has R d_last subtracted:  r^_c = S_c P^T S_f^-1 res_A - R d_last.  L lanes per coarse row; the row product is laid out
+// like cheb32_kernel's (two blocks per lane and round, branch-free first round, fixed-order butterfly, fp32 sums).
+template <int L>
+__global__ __launch_bounds__(256) void pmg_restrict_op_init_kernel(
+    int Nc, const int* __restrict__ child_off, const int* __restrict__ child, const float* __restrict__ child_w,
+    const float* __restrict__ res_f, const float* __restrict__ d_f, const double* __restrict__ sc_f,
+    const double* __restrict__ sc_c, Incidence rinc, const Blk8<float>* __restrict__ R8, const float* __restrict__ R1,
+    const float* __restrict__ Dinv_c, const double* __restrict__ coef_c, float* __restrict__ d_c, float* __restrict__ z_c,
+    float* __restrict__ res_c) {
+  const int lane = threadIdx.x & (L - 1);
+  const int I = blockIdx.x * (256 / L) + threadIdx.x / L;
+  if (I >= Nc) return;
+  // row product first: its loads are the long ones
+  const int base = rinc.off[I], deg = rinc.off[I + 1] - base;
+  const int t0 = child_off[I], t1 = child_off[I + 1];
+  C32Round<float, L> R;
+  R.load(rinc, R8, R1, base, deg, lane);
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  {
+    const float* pa = d_f + 3 * (size_t)R.ca;
+    const float* pb = d_f + 3 * (size_t)R.cb;
+    const float x[3] = {pa[0], pa[1], pa[2]}, y[3] = {pb[0], pb[1], pb[2]};
+    c32_fma<float, L>(R, x, y, s0, s1, s2);
+  }
+  for (int k = lane + 2 * L; k < deg; k += 2 * L) {
+    C32Round<float, L> T;
+    T.load(rinc, R8, R1, base, deg, k);
+    const float* pa = d_f + 3 * (size_t)T.ca;
+    const float* pb = d_f + 3 * (size_t)T.cb;
+    const float x[3] = {pa[0], pa[1], pa[2]}, y[3] = {pb[0], pb[1], pb[2]};
+    c32_fma<float, L>(T, x, y, s0, s1, s2);
+  }
+  double r[3] = {0.0, 0.0, 0.0};
+  for (int t = t0 + lane; t < t1; t += L) {
+    const int n = child[t];
+    const double w = (double)child_w[t];
+#pragma unroll
+    for (int c = 0; c < 3; c++) r[c] += w * (double)res_f[3 * n + c] / sc_f[3 * n + c];
+  }
+#pragma unroll
+  for (int o = L / 2; o > 0; o >>= 1) {
+    s0 += __shfl_xor(s0, o);
+    s1 += __shfl_xor(s1, o);
+    s2 += __shfl_xor(s2, o);
+    r[0] += __shfl_xor(r[0], o);
+    r[1] += __shfl_xor(r[1], o);
+    r[2] += __shfl_xor(r[2], o);
+  }
+  if (lane >= 3) return;
+  const int c = lane;
+  const float inv_theta = (float)coef_c[0];
+  const float rs0 = (float)(r[0] * sc_c[3 * I]) - s0, rs1 = (float)(r[1] * sc_c[3 * I + 1]) - s1,
+              rs2 = (float)(r[2] * sc_c[3 * I + 2]) - s2;
+  const float* D = Dinv_c + (size_t)9 * I + 3 * c;
+  const float v = (D[0] * rs0 + D[1] * rs1 + D[2] * rs2) * inv_theta;
+  d_c[3 * I + c] = v;
+  z_c[3 * I + c] = v;
+  res_c[3 * I + c] = (c == 0) ? rs0 : ((c == 1) ? rs1 : rs2);
+}
+void launch_pmg_restrict_op_init(hipStream_t s, int Nc, int nnz_r, const int* child_off, const int* child,
+                                 const float* child_w, const float* res_f, const float* d_f, const double* sc_f,
+                                 const double* sc_c, const int* r_off, const int* r_cols, const void* R8, const float* R1,
+                                 const float* Dinv_c, const double* coef_c, float* d_c, float* z_c, float* res_c) {
+  // lanes per row: two blocks per lane and round (T10: ~62 blocks per row of R at config C -> 32 lanes, one round for most rows)
+  const double avg = (double)nnz_r / std::max(1, Nc);
+  const Incidence rinc{nullptr, nullptr, nullptr, r_off, r_cols, nullptr};
+#define TLFEA_ROP(LL)                                                                                                    \
+  hipLaunchKernelGGL((pmg_restrict_op_init_kernel<LL>), dim3((Nc + 256 / LL - 1) / (256 / LL)), dim3(256), 0, s, Nc,     \
+                     child_off, child, child_w, res_f, d_f, sc_f, sc_c, rinc, (const Blk8<float>*)R8, R1, Dinv_c, coef_c, \
+                     d_c, z_c, res_c)
+  if (avg > 36.0) TLFEA_ROP(32);
+  else if (avg > 18.0) TLFEA_ROP(16);
+  else TLFEA_ROP(8);
+#undef TLFEA_ROP
+}
+
+// test hooks: a streamed copy (8 + 1 entries per block, 16 or 32 bits) widened to doubles, [nnz][9] row-major
+template <typename HT>
+__global__ void lp_widen_kernel(size_t nnz, const Blk8<HT>* __restrict__ B8, const HT* __restrict__ B1,
+                                double* __restrict__ out) {
+  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < nnz; g += (size_t)gridDim.x * blockDim.x) {
+    const Blk8<HT> v = B8[g];
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[9 * g + k] = (double)(float)v.v[k];
+    out[9 * g + 8] = (double)(float)B1[g];
+  }
+}
+void launch_lp_widen(hipStream_t s, size_t nnz, const void* B8, const void* B1, int bits, double* out) {
+  const dim3 g((unsigned)std::max<size_t>(1, std::min<size_t>(4096, (nnz + 255) / 256))), b(256);
+  if (bits == 16)
+    hipLaunchKernelGGL((lp_widen_kernel<_Float16>), g, b, 0, s, nnz, (const Blk8<_Float16>*)B8, (const _Float16*)B1, out);
+  else
+    hipLaunchKernelGGL((lp_widen_kernel<float>), g, b, 0, s, nnz, (const Blk8<float>*)B8, (const float*)B1, out);
 }
 
 // ---- third level (pmg_host.h agg_build): rigid-body-mode aggregation of the vertex level ---------------------------

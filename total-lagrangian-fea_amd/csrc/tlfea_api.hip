@@ -2200,6 +2200,17 @@ struct tlfea_newton_s {
     // vertex-level operator is worse conditioned than the guess covers (a 5 x 3.3 x 1.7 bar of 4.5 M elements needs
     // degree ~50 where the guess says 39), the solver raises it for this and all later solves
     double kc_boost = 1.0;
+    // restricted fine operator R = S_c P^T S_f^-1 Hs (pmg_host.h pmg_restrict_op_build; one GPU, first-kind smoother):
+    // pattern and contribution lists with the hierarchy, values (fp32, 8 + 1 per block) rebuilt by pmg_build_level
+    struct Rop {
+      bool ok = false, built = false;
+      int nnz = 0, n_con = 0;
+      int *d_off = nullptr, *d_cols = nullptr, *d_ch_off = nullptr, *d_ch = nullptr, *d_con_off = nullptr,
+          *d_con_blk = nullptr;
+      unsigned char* d_con_ord = nullptr;
+      float *d_ch_w = nullptr, *d_R1 = nullptr;
+      void* d_R8 = nullptr;
+    } rop;
     Incidence inc() const { return Incidence{nullptr, nullptr, nullptr, d_c_off, d_c_cols, d_c_diagpos}; }
     // third level: rigid-body-mode aggregates of the vertex level (pmg_host.h agg_build); N3 = 2 Na nodes
     struct Agg {
@@ -2448,6 +2459,11 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
                   m.d_con_off, m.d_con_base, m.d_con_deg, m.d_child_w, m.d_con_w, m.d_Hc, m.d_Dc, m.d_Dinv_c, m.d_sc_c,
                   m.d_Dinv_s_c, m.d_eigv_c, m.d_q_c, m.d_p_c, m.d_B8c, m.d_B1c, m.d_f32c, m.d_coef};
     for (void* q : pp)
+      if (q) (void)hipFree(q);
+    auto& ro = m.rop;
+    void* rr[] = {ro.d_off, ro.d_cols, ro.d_ch_off, ro.d_ch, ro.d_con_off, ro.d_con_blk, ro.d_con_ord, ro.d_ch_w, ro.d_R1,
+                  ro.d_R8};
+    for (void* q : rr)
       if (q) (void)hipFree(q);
     auto& g = m.agg;
     void* gg[] = {g.d_agg, g.d_active, g.d_mem_off, g.d_mem, g.d_off3, g.d_cols3, g.d_diag3, g.d_pair_A, g.d_pair_pos,
@@ -4072,6 +4088,24 @@ static int pmg_smoother_kind() {
   static const int k = std::getenv("TLFEA_PMG_SMOOTHER") ? std::atoi(std::getenv("TLFEA_PMG_SMOOTHER")) : 1;
   return (k == 3 || k == 4) ? k : 1;
 }
+// Restriction through the stored operator R = S_c P^T S_f^-1 Hs instead of the fine (0, 0) residual pass (pmg_apply):
+// one GPU, first-kind smoother, fine copy in 16 or 32 bits, T10 hierarchy with R built.  TLFEA_PMG_RESTRICT_OP=0 keeps
+// the residual pass (A/B runs, and the sequence every other configuration runs).
+static bool pmg_rop_wanted() {
+  static const bool on = !(std::getenv("TLFEA_PMG_RESTRICT_OP") && std::atoi(std::getenv("TLFEA_PMG_RESTRICT_OP")) == 0);
+  return on;
+}
+// The one statement of eligibility, in three stages: what the mesh and the process allow (pmg_prepare builds the lists
+// on it), what a set-up builds R for (pmg_build_level), what a cycle or a captured graph runs now (pmg_apply, the key).
+static bool pmg_rop_possible(tlfea_newton_t s) {
+  return pmg_rop_wanted() && s->d->kind == kT10 && !dist_on(s) && pmg_smoother_kind() == 1;
+}
+static bool pmg_rop_on(tlfea_newton_t s) {
+  if (!pmg_rop_possible(s) || !s->pmg.rop.ok) return false;
+  const int fb = fine_bits(s);
+  return fb == 16 || fb == 32;
+}
+static bool pmg_rop_now(tlfea_newton_t s) { return pmg_rop_on(s) && s->pmg.rop.built; }
 // Third level (rigid-body-mode aggregates below the vertex level): opt-in with TLFEA_PMG_LEVELS=3.  Measured at config C
 // it makes a CG iteration 10-12 % cheaper (4 vertex-level steps + a degree-20..32 polynomial on ~20 000 level-3 nodes
 // instead of 31 vertex-level steps) and costs 10-17 % more iterations (33-35 instead of 30, whatever the accuracy of
@@ -4150,6 +4184,25 @@ static int pmg_prepare(tlfea_newton_t s) {
   TRY(dmalloc(&m.d_coef, (size_t)5 * kPmgMaxKs + 8 + 2 * kPmgMaxCoarseDeg));
   m.ok = true;
   if (s->verbose) std::printf("p-multigrid: %d fine nodes -> %d vertex nodes, %d coarse blocks\n", d->N, m.Nc, m.nnz_c);
+  if (pmg_rop_possible(s)) {
+    RopHost ro;
+    if (pmg_restrict_op_build(d->N, d->h_off.data(), d->h_cols.data(), h, ro)) {
+      auto& r = m.rop;
+      r.nnz = ro.nnz;
+      r.n_con = ro.n_con;
+      TRY(upload_vec(&r.d_off, ro.off)); TRY(upload_vec(&r.d_cols, ro.cols));
+      TRY(upload_vec(&r.d_ch_off, ro.ch_off)); TRY(upload_vec(&r.d_ch, ro.ch)); TRY(upload_vec(&r.d_ch_w, ro.ch_w));
+      TRY(upload_vec(&r.d_con_off, ro.con_off)); TRY(upload_vec(&r.d_con_blk, ro.con_blk));
+      TRY(upload_vec(&r.d_con_ord, ro.con_ord));
+      HIP_TRY(hipMalloc(&r.d_R8, ((size_t)r.nnz + 1) * 8 * sizeof(float)));
+      TRY(dmalloc(&r.d_R1, (size_t)r.nnz + 1));
+      r.ok = true;
+      if (s->verbose)
+        std::printf("p-multigrid: restricted fine operator, %d blocks (%.3f of H), %d contributions, %.1f MB\n", r.nnz,
+                    (double)r.nnz / std::max(1, d->nnz_coef), r.n_con,
+                    (44.0 * r.nnz + 5.0 * r.n_con + 8.0 * ro.ch.size() + 4.0 * m.Nc) / 1048576.0);
+    }
+  }
   if (s->ar) {
     // Multi-GPU: the coarse level inherits the partition.  A vertex node on the partition boundary is a coarse node
     // replicated on the same ranks; every rank flags the exchange slots of ITS boundary vertices, the flags are summed
@@ -4407,6 +4460,13 @@ static int pmg_build_level(tlfea_newton_t s) {
   launch_lp_scale(s->stream, m.Nc, m.d_Dc, m.d_Dinv_c, m.d_sc_c, m.d_Dinv_s_c);
   launch_lp_convert(s->stream, m.Nc, ic, m.d_Hc, m.d_sc_c, nullptr, m.d_Dc, m.d_B8c, m.d_B1c, bits);
   launch_to_float(s->stream, (size_t)9 * m.Nc, m.d_Dinv_s_c, m.d_f32c + (size_t)18 * m.Nc);
+  m.rop.built = false;
+  if (pmg_rop_on(s)) {  // R = S_c P^T S_f^-1 Hs from the fine copy as stored (lp_build ran before) and both scalings
+    auto& r = m.rop;
+    launch_pmg_rop_build(s->stream, m.Nc, r.d_off, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch, r.d_ch_w,
+                         s->d_B8, s->d_B1, fine_bits(s), s->d_sc, m.d_sc_c, r.d_R8, r.d_R1);
+    r.built = true;
+  }
   if (m.agg.ok) {  // third level: H3 = P2^T Hc P2, its scaling and low-precision copy
     auto& g = m.agg;
     launch_agg_galerkin(s->stream, g.n_pairs, g.d_pair_A, g.d_pair_pos, g.d_pair_B, g.d_pcon_off, g.d_pcon_base,
@@ -4655,7 +4715,15 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
   };
   if (!init_done) launch_cheb32_init(s->stream, Nf, Dinv_f, d_r, s->d_sc, cf, f_d, f_z, f_r);
   for (int k = 1; k < ks; k++) fine(cf + 2 * k, false, betas + k);
-  if (weighted) {
+  // Restriction through the stored operator (pmg_rop_on): the residual pass is dropped.  f_r is res_A = r^ - Hs (z^ - d_last)
+  // and f_d the last direction; the residual is linear in the direction, so the coarse right-hand side is
+  // S_c P^T S_f^-1 res_A - R d_last, the prolongation writes d := d_last + corr, and the restart pass below forms
+  // res_A - Hs (d_last + corr) -- what the residual pass and the restart pass formed together.
+  const bool rop = pmg_rop_now(s);
+  if (rop) {
+    launch_pmg_restrict_op_init(s->stream, Nc, m.rop.nnz, m.d_child_off, m.d_child, m.d_child_w, f_r, f_d, s->d_sc, m.d_sc_c,
+                                m.rop.d_off, m.rop.d_cols, m.rop.d_R8, m.rop.d_R1, Dinv_fc, cf + o_c, c_d, c_z, c_r);
+  } else if (weighted) {
     // Weighted z^ updates: the residual the recurrence carries is the UNWEIGHTED iterate's, not that of z^ -- restricting it
     // made the cycle unsymmetric (defect 3e-4 on res2; tests/test_gpu_precond_operator.py, configuration 11).  Form
     // res^ = S r - Hs z^ itself: start vectors into the spare buffers (res^ := S r), then one pass with z^ as the direction
@@ -4668,8 +4736,9 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
   } else
     fine(cf + o_res, false, nullptr);
   // coarse correction
-  launch_pmg_restrict_init(s->stream, Nc, m.d_child_off, m.d_child, m.d_child_w, f_r, s->d_sc, m.d_sc_c, Dinv_fc, cf + o_c,
-                           c_d, c_z, c_r);
+  if (!rop)
+    launch_pmg_restrict_init(s->stream, Nc, m.d_child_off, m.d_child, m.d_child_w, f_r, s->d_sc, m.d_sc_c, Dinv_fc, cf + o_c,
+                             c_d, c_z, c_r);
   if (m.agg.ok) {
     // vertex level as a smoothing level: the fine level's sequence once more, with the level-3 polynomial inside
     auto& g = m.agg;
@@ -4741,7 +4810,8 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
     }
     if (hal && valid < need_end) TRY(halo_refresh_f32(s, 1, need_end, 3, c_z));  // the last chunk ended too shallow
   }
-  launch_pmg_prolong(s->stream, Nf, m.d_par0, m.d_par1, c_z, m.d_sc_c, s->d_sc, f_z, f_d);  // z^ += corr ; d := corr
+  // z^ += corr ; d := corr (restricted operator: d := d_last + corr)
+  launch_pmg_prolong(s->stream, Nf, m.d_par0, m.d_par1, c_z, m.d_sc_c, s->d_sc, f_z, f_d, rop);
   // post-smooth: res^ -= Hs corr ; d0' = (SDS)^-1 res^/theta ; z^ += d0'   == one step with coefficients (0, 1/theta),
   // then the ks - 1 Chebyshev steps that complete the polynomial; the last pass returns z = S z^ (fp64) and the r.z slots
   fine(cf + o_rst, ks == 1, betas);
@@ -4909,7 +4979,8 @@ static void cg_graphs_destroy(tlfea_newton_t s) {
 // path calls back into the host between kernels).
 static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg, int bits) {
   const long key[6] = {deg + 1000 * precond_eff(s) + 100000L * (s->pmg.ok ? pmg_coarse_degree_eff(s) : 0),
-                       bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0),
+                       bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0) +
+                           (pmg_rop_now(s) ? 400000L : 0),
                        (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
                        (long)(size_t)s->d_B8, (long)(size_t)s->pmg.d_B8c};
   if (s->cg_graph[0] && std::equal(key, key + 6, s->cg_graph_key)) return 0;
@@ -5485,6 +5556,59 @@ extern "C" int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int* par0, int* par1,
   D2H(c_cols, m.d_c_cols, (size_t)nnz);
   D2H(Hc, m.d_Hc, (size_t)9 * nnz);
   return 0;
+}
+
+// Test hooks of the restricted fine operator: what the LAST preconditioner set-up (a solve or
+// tlfea_newton_apply_preconditioner) left on the device, nothing is rebuilt.  Sizes; R as stored (values widened to
+// double, [nnz][9] row-major per block); the fine level's stored copy in the node-block CSR of H, widened likewise,
+// with both scalings.
+extern "C" int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int* out6) {
+  if (!s || !out6) return fail("tlfea_newton_pmg_restrict_op_sizes: null argument");
+  const auto& m = s->pmg;
+  const bool have = m.ok && m.rop.ok && m.rop.built;
+  out6[0] = have ? 1 : 0;
+  out6[1] = m.ok ? m.Nc : 0;
+  out6[2] = have ? m.rop.nnz : 0;
+  out6[3] = have ? m.rop.n_con : 0;
+  out6[4] = s->d->nnz_coef;
+  out6[5] = s->d_B8 ? s->lp_bits_alloc : 0;
+  return 0;
+}
+static int widen_to_host(tlfea_newton_t s, size_t nnz, const void* B8, const void* B1, int bits, double* out) {
+  double* d_tmp = nullptr;
+  TRY(dmalloc(&d_tmp, 9 * nnz));
+  launch_lp_widen(s->stream, nnz, B8, B1, bits, d_tmp);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e == hipSuccess) e = hipMemcpy(out, d_tmp, 9 * nnz * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(d_tmp);
+  HIP_TRY(e);
+  return 0;
+}
+extern "C" int tlfea_newton_pmg_restrict_op_retrieve(tlfea_newton_t s, int* off, int* cols, double* vals) {
+  if (!s || !off || !cols || !vals) return fail("tlfea_newton_pmg_restrict_op_retrieve: null argument");
+  const auto& m = s->pmg;
+  if (!(m.ok && m.rop.ok && m.rop.built))
+    return fail("tlfea_newton_pmg_restrict_op_retrieve: the last preconditioner set-up built no restricted operator");
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  D2H(off, m.rop.d_off, (size_t)m.Nc + 1);
+  D2H(cols, m.rop.d_cols, (size_t)m.rop.nnz);
+  return widen_to_host(s, (size_t)m.rop.nnz, m.rop.d_R8, m.rop.d_R1, 32, vals);
+}
+extern "C" int tlfea_newton_pmg_fine_copy_retrieve(tlfea_newton_t s, int* off, int* cols, double* vals, double* sc_f,
+                                                   double* sc_c) {
+  if (!s || !off || !cols || !vals || !sc_f || !sc_c) return fail("tlfea_newton_pmg_fine_copy_retrieve: null argument");
+  const auto& m = s->pmg;
+  const int bits = s->d_B8 ? s->lp_bits_alloc : 0;
+  if (!m.ok || !m.d_sc_c || !s->d_sc || (bits != 16 && bits != 32))
+    return fail("tlfea_newton_pmg_fine_copy_retrieve: no p-multigrid set-up with a 16- or 32-bit fine copy on the device");
+  tlfea_t10_t d = s->d;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  std::copy(d->h_off.begin(), d->h_off.begin() + d->N + 1, off);
+  std::copy(d->h_cols.begin(), d->h_cols.begin() + d->nnz_coef, cols);
+  D2H(sc_f, s->d_sc, 3 * (size_t)s->N);
+  D2H(sc_c, m.d_sc_c, 3 * (size_t)m.Nc);
+  return widen_to_host(s, (size_t)d->nnz_coef, s->d_B8, s->d_B1, bits, vals);
 }
 
 // third level (opt-in, TLFEA_PMG_LEVELS=3): sizes, and everything

@@ -293,7 +293,18 @@ void launch_agg_init3(hipStream_t s, int N3, const double* r3, const double* sc3
 void launch_agg_prolong(hipStream_t s, int Nc, const int* agg, const double* rvec, const float* z3, const double* sc3,
                         const double* sc2, float* z2, float* d2);
 void launch_pmg_prolong(hipStream_t s, int N, const int* par0, const int* par1, const float* z_c, const double* sc_c,
-                        const double* sc_f, float* z_f, float* d_f);
+                        const double* sc_f, float* z_f, float* d_f, bool add_to_d = false);
+// restricted fine operator R = S_c P^T S_f^-1 Hs (pmg_host.h pmg_restrict_op_build): build from the stored fine copy (once
+// per solve), and the restriction  r^_c = S_c P^T S_f^-1 res_f - R d_f  fused with the coarse start vectors
+void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
+                          const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,
+                          const void* B1, int bits, const double* sc_f, const double* sc_c, void* R8, float* R1);
+void launch_pmg_restrict_op_init(hipStream_t s, int Nc, int nnz_r, const int* child_off, const int* child,
+                                 const float* child_w, const float* res_f, const float* d_f, const double* sc_f,
+                                 const double* sc_c, const int* r_off, const int* r_cols, const void* R8, const float* R1,
+                                 const float* Dinv_c, const double* coef_c, float* d_c, float* z_c, float* res_c);
+// test hooks: a streamed copy (bits 16 or 32) widened to doubles, [nnz][9]
+void launch_lp_widen(hipStream_t s, size_t nnz, const void* B8, const void* B1, int bits, double* out);
 // mode 0: Chebyshev step, 1: last step (z back in the unscaled space + r.z slots in out), 2: out = Hs d_old
 void launch_cheb_lp(hipStream_t s, int N, int nnz_coef, const Incidence& inc, const void* B8, const void* B1, int bits,
                     const double* Dinv_s, const double* sc, const double* d_old, const double* coef, double* d_new,

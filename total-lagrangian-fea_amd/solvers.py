@@ -112,6 +112,30 @@ class SyncedNewtonSolver:
         check(self._lib.tlfea_newton_pmg_retrieve(self._h, ip(par0), ip(par1), ip(c_off), ip(c_cols), dp(Hc)))
         return par0, par1, c_off, c_cols, Hc
 
+    def GetRestrictOpInfo(self):
+        """dict(active, n_coarse, blocks, contributions, fine_blocks, fine_bits) of the restricted fine operator
+        R = S_c P^T S_f^-1 Hs as the last preconditioner set-up left it (active 0: the cycle runs the fine residual pass)"""
+        out = (C.c_int * 6)()
+        check(self._lib.tlfea_newton_pmg_restrict_op_sizes(self._h, out))
+        return dict(zip(("active", "n_coarse", "blocks", "contributions", "fine_blocks", "fine_bits"), list(out)))
+
+    def RetrieveRestrictOp(self):
+        """(off, cols, vals[blocks, 3, 3]): R as stored after the last set-up, fp32 widened to double (test hook)"""
+        info = self.GetRestrictOpInfo()
+        off, cols = np.zeros(info["n_coarse"] + 1, dtype=np.int32), np.zeros(max(1, info["blocks"]), dtype=np.int32)
+        vals = np.zeros(9 * max(1, info["blocks"]))
+        check(self._lib.tlfea_newton_pmg_restrict_op_retrieve(self._h, ip(off), ip(cols), dp(vals)))
+        return off, cols[:info["blocks"]], vals[:9 * info["blocks"]].reshape(-1, 3, 3)
+
+    def RetrieveFineCopy(self):
+        """(off, cols, vals[blocks, 3, 3], sc_f[3N], sc_c[3Nc]): the fine level's stored copy S_f H S_f in the node-block
+        CSR of H, fp16 / fp32 widened to double, and the scalings of both levels (test hook)"""
+        info = self.GetRestrictOpInfo()
+        off, cols = np.zeros(self.n_coef + 1, dtype=np.int32), np.zeros(info["fine_blocks"], dtype=np.int32)
+        vals, sc_f, sc_c = np.zeros(9 * info["fine_blocks"]), np.zeros(3 * self.n_coef), np.zeros(3 * max(1, info["n_coarse"]))
+        check(self._lib.tlfea_newton_pmg_fine_copy_retrieve(self._h, ip(off), ip(cols), dp(vals), dp(sc_f), dp(sc_c)))
+        return off, cols, vals.reshape(-1, 3, 3), sc_f, sc_c[:3 * info["n_coarse"]]
+
     def GetPmgCycleInfo(self):
         """dict(levels, fine_terms, vertex_terms, vertex_degree, level3_degree, level3_nodes) of the cycle in use (levels 0:
         polynomial preconditioner)"""
