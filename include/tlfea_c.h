@@ -398,6 +398,14 @@ int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int *par0, int *par1, int *c_off
  * double.  fine_copy_retrieve: the fine level's stored copy Hs = S_f H S_f in the node-block CSR of H (off [N+1], cols,
  * vals [blocks][9], fp16 / fp32 widened to double) and the scalings sc_f [3N], sc_c [3 Nc]. */
 int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int *out6);
+/* Test hook: launch geometry of the last NON-FINAL single-precision polynomial step on level 0 (fine), 1 (vertex) or 2
+ * (third level): out7 = regime (0 last, 1 bandwidth, 2 latency, 3 one-round; -1 none yet), lanes per row, threads per
+ * workgroup, blocks per lane issued up front, rows per group, grid, and the resident workgroups the occupancy query
+ * answered for the instantiation launched (0 in the slot-capped regimes).  It is written where the host issues the launch:
+ * when the CG iteration runs as a captured graph, that is at capture, and replays of the graph leave it as it is.
+ * TLFEA_C32_REGIME=1|2|3|4 forces a regime (4: one-round with half the lanes); a forced one-round regime that does not
+ * fit the device falls back to the automatic choice. */
+int tlfea_newton_get_c32_geometry(tlfea_newton_t s, int level, int *out7);
 int tlfea_newton_pmg_restrict_op_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals);
 int tlfea_newton_pmg_fine_copy_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals, double *sc_f, double *sc_c);
 int tlfea_newton_hessian_nnz(tlfea_newton_t s, int *nnz);

@@ -960,9 +960,7 @@ bool row_map_tiled() {
 
 int lp_lanes(int N, int nnz_coef) {
   static const int forced = std::getenv("TLFEA_LP_LANES") ? std::atoi(std::getenv("TLFEA_LP_LANES")) : 0;
-  if (forced == 8 || forced == 16 || forced == 32) return forced;
-  const double avg = (double)nnz_coef / std::max(1, N);
-  return avg > 48.0 ? 32 : 16;
+  return c32_lp_lanes(N, nnz_coef, forced);
 }
 
 void launch_cheb_lp(hipStream_t s, int N, int nnz_coef, const Incidence& inc, const void* B8, const void* B1, int bits,
@@ -1229,6 +1227,89 @@ __global__ __launch_bounds__(TPB) void cheb32_kernel(int N, Incidence inc, const
   }
 }
 
+// ONE ROUND: a non-final step of a level small enough that every row has its own lane group resident at once
+// (c32_geometry.h).  One row per group, no sweep: the grid is ceil(N / G), the three dependent memory phases of a row are
+// the whole kernel and all rows are in them together.  With the rule's lanes that is cheb32_kernel itself in 256-thread
+// workgroups (its sweep makes one trip; same code, same bits as the latency regime).  This kernel is the form with HALF
+// the lanes, each holding FOUR blocks, for a level whose rows x lanes does not fit but whose rows x lanes / 2 does: the
+// loads of all four go out branch-free before the first use.
+// The groups past the last row of the last workgroup shadow row N - 1 with their stores masked.  No multi-GPU boundary
+// rows (the launcher does not pick this regime when they are in use).
+template <typename HT, int L, int TPB>
+__global__ __launch_bounds__(TPB) void cheb32_one_kernel(int N, Incidence inc, const Blk8<HT>* __restrict__ B8,
+                                                         const HT* __restrict__ B1, const float* __restrict__ Dinv_f,
+                                                         const float* __restrict__ d_old, const double* __restrict__ coef,
+                                                         float* __restrict__ d_new, const float* __restrict__ z,
+                                                         float* __restrict__ z_new, const float* __restrict__ res,
+                                                         float* __restrict__ res_new, const double* __restrict__ zw) {
+  const float c1 = (float)coef[0], c2 = (float)coef[1];
+  const float zwf = zw ? (float)zw[0] : 1.f;
+  constexpr int G = TPB / L;
+  const int lane = threadIdx.x & (L - 1), grp = threadIdx.x / L;
+  const int c = lane < 3 ? lane : 0;
+  const int row = blockIdx.x * G + grp;
+  const bool live = row < N;
+  const int i = live ? row : N - 1;
+  // phase 1: offsets and the operands of the epilogue (every lane loads, the group's addresses coincide)
+  const int base = inc.off[i], deg = inc.off[i + 1] - base;
+  const float e0r = res[3 * i], e1r = res[3 * i + 1], e2r = res[3 * i + 2];
+  const float* D = Dinv_f + (size_t)9 * i + 3 * c;
+  const float D0 = D[0], D1 = D[1], D2 = D[2];
+  const float dc = d_old[3 * i + c], zc = z[3 * i + c];
+  // phase 2: the lane's four blocks (k, k + L and k + 2 L, k + 3 L)
+  C32Round<HT, L> RA, RB;
+  RA.load(inc, B8, B1, base, deg, lane);
+  RB.load(inc, B8, B1, base, deg, lane + 2 * L);
+  // phase 3: gathers
+  float xA[3], yA[3], xB[3], yB[3];
+  {
+    const float* pa = d_old + 3 * (size_t)RA.ca;
+    const float* pb = d_old + 3 * (size_t)RA.cb;
+    const float* qa = d_old + 3 * (size_t)RB.ca;
+    const float* qb = d_old + 3 * (size_t)RB.cb;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      xA[j] = pa[j];
+      yA[j] = pb[j];
+      xB[j] = qa[j];
+      yB[j] = qb[j];
+    }
+  }
+  // The two pairs of blocks are summed apart and then joined.  Either order is as good an fp32 row sum as the other
+  // (operator error against the fp64 restatement 4.5e-7 against 4.3e-7 on plate3443).  This one was taken because the
+  // single chain, at 62 instead of 71 VGPRs (fp16, 16 lanes: 8 instead of 7 workgroups per CU), gave 288 CG iterations on
+  // plate3443 where tests/test_gpu_c32_geometry.py allows 286 -- a count that rounding alone moves between 163 and 284 on
+  // the CPU; this form gives 278.  The third level of config C fits at either residency.
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, t0 = 0.f, t1 = 0.f, t2 = 0.f;
+  c32_fma<HT, L>(RA, xA, yA, s0, s1, s2);
+  c32_fma<HT, L>(RB, xB, yB, t0, t1, t2);
+  s0 += t0;
+  s1 += t1;
+  s2 += t2;
+  // further rounds of rows longer than the up-front slots
+  for (int k = lane + 4 * L; k < deg; k += 2 * L) {
+    C32Round<HT, L> T;
+    T.load(inc, B8, B1, base, deg, k);
+    const float* pa = d_old + 3 * (size_t)T.ca;
+    const float* pb = d_old + 3 * (size_t)T.cb;
+    const float x[3] = {pa[0], pa[1], pa[2]}, y[3] = {pb[0], pb[1], pb[2]};
+    c32_fma<HT, L>(T, x, y, s0, s1, s2);
+  }
+#pragma unroll
+  for (int o = L / 2; o > 0; o >>= 1) {
+    s0 += __shfl_xor(s0, o);
+    s1 += __shfl_xor(s1, o);
+    s2 += __shfl_xor(s2, o);
+  }
+  if (lane < 3 && live) {
+    const float e0 = e0r - s0, e1 = e1r - s1, e2 = e2r - s2;
+    const float dn = c1 * dc + c2 * (D0 * e0 + D1 * e1 + D2 * e2);
+    d_new[3 * i + c] = dn;
+    z_new[3 * i + c] = zc + zwf * dn;
+    res_new[3 * i + c] = (c == 0) ? e0 : ((c == 1) ? e1 : e2);
+  }
+}
+
 template <typename K>
 static int resident_blocks(K kernel, int tpb) {  // workgroups of this kernel resident on the device at once
   int per_cu = 0, dev = 0, cus = 0;
@@ -1238,47 +1319,66 @@ static int resident_blocks(K kernel, int tpb) {  // workgroups of this kernel re
   return per_cu * cus;
 }
 
-static int c32_bandwidth_rows() {
-  static const int n = std::getenv("TLFEA_C32_BW_N") ? std::atoi(std::getenv("TLFEA_C32_BW_N")) : 100000;
-  return n;
+static int env_int(const char* name, int dflt) { return std::getenv(name) ? std::atoi(std::getenv(name)) : dflt; }
+static const C32Switches& c32_switches() {  // the process's switches, read once
+  static const C32Switches sw = [] {
+    C32Switches w;
+    w.bw_rows = env_int("TLFEA_C32_BW_N", 100000);
+    w.forced_lanes = env_int("TLFEA_C32_LANES", 0);
+    w.regime = env_int("TLFEA_C32_REGIME", -1);
+    w.slots = kNPart;
+    return w;
+  }();
+  return sw;
 }
 
 template <typename T, int LL>
 static void launch_cheb32_t(hipStream_t s, int N, const Incidence& inc, const void* B8, const void* B1,
                             const float* Dinv_f, const double* sc, const float* d_old, const double* coef,
                             float* d_new, const float* z, float* z_new, const float* res, float* res_new,
-                            const double* r, double* z_out, double* rz_part, bool last, C32Bnd bnd) {
+                            const double* r, double* z_out, double* rz_part, bool last, C32Bnd bnd,
+                            C32Geometry* chosen) {
   bnd.xcd = xcd_rows_mode();
+  // the candidates' resident workgroups, asked once per instantiation; the geometry itself is c32_geometry.h's
+  static const C32Resident resident = [] {
+    C32Resident r;
+    r.two_row = resident_blocks(cheb32_kernel<T, LL, false, 256, true>, 256);
+    r.one_full = resident_blocks(cheb32_kernel<T, LL, false, 256, false>, 256);
+    if constexpr (LL >= 16) r.one_half = resident_blocks(cheb32_one_kernel<T, LL / 2, 256>, 256);
+    return r;
+  }();
+  C32Switches sw = c32_switches();
+  sw.boundary = bnd.bslot != nullptr;
+  const C32Geometry geo = c32_geometry(N, LL, last, resident, sw);
+  if (chosen) *chosen = geo;
+  const dim3 g(geo.grid), b(geo.threads);
 #define TLFEA_C32_ARGS N, inc, (const Blk8<T>*)B8, (const T*)B1, Dinv_f, sc, d_old, coef, d_new, z, z_new, res, res_new, r, z_out, rz_part, bnd
-  if (last) {
-    constexpr int TPB = 1024, G = TPB / LL;
-    const dim3 g(std::max(1, std::min(kNPart, (N + G - 1) / G))), b(TPB);
-    hipLaunchKernelGGL((cheb32_kernel<T, LL, true, TPB, false>), g, b, 0, s, TLFEA_C32_ARGS);
-  } else if (N > c32_bandwidth_rows()) {  // bandwidth regime: two rows per lane group, 256-thread workgroups, resident grid
-    constexpr int TPB = 256, G = TPB / LL;
-    static const int resident = resident_blocks(cheb32_kernel<T, LL, false, TPB, true>, TPB);
-    const dim3 g(std::max(1, std::min(resident, (N + 2 * G - 1) / (2 * G)))), b(TPB);
-    hipLaunchKernelGGL((cheb32_kernel<T, LL, false, TPB, true>), g, b, 0, s, TLFEA_C32_ARGS);
-  } else {  // latency regime: as many independent groups as there are rows
-    constexpr int TPB = 1024, G = TPB / LL;
-    const dim3 g(std::max(1, std::min(kNPart, (N + G - 1) / G))), b(TPB);
-    hipLaunchKernelGGL((cheb32_kernel<T, LL, false, TPB, false>), g, b, 0, s, TLFEA_C32_ARGS);
+#define TLFEA_C32_ONE_ARGS N, inc, (const Blk8<T>*)B8, (const T*)B1, Dinv_f, d_old, coef, d_new, z, z_new, res, res_new, bnd.zw
+  if (geo.regime == kC32Last) {
+    hipLaunchKernelGGL((cheb32_kernel<T, LL, true, 1024, false>), g, b, 0, s, TLFEA_C32_ARGS);
+  } else if (geo.regime == kC32Bandwidth) {  // two rows per lane group, 256-thread workgroups, resident grid
+    hipLaunchKernelGGL((cheb32_kernel<T, LL, false, 256, true>), g, b, 0, s, TLFEA_C32_ARGS);
+  } else if (geo.regime == kC32OneRound && geo.lanes == LL) {
+    bnd.xcd = 0;  // no sweep: workgroup b holds rows b G .. b G + G - 1
+    hipLaunchKernelGGL((cheb32_kernel<T, LL, false, 256, false>), g, b, 0, s, TLFEA_C32_ARGS);
+  } else if (geo.regime == kC32OneRound) {
+    if constexpr (LL >= 16) hipLaunchKernelGGL((cheb32_one_kernel<T, LL / 2, 256>), g, b, 0, s, TLFEA_C32_ONE_ARGS);
+  } else {  // latency regime: as many independent groups as the reduction slots allow
+    hipLaunchKernelGGL((cheb32_kernel<T, LL, false, 1024, false>), g, b, 0, s, TLFEA_C32_ARGS);
   }
+#undef TLFEA_C32_ONE_ARGS
 #undef TLFEA_C32_ARGS
 }
 
 void launch_cheb32(hipStream_t s, int N, int nnz_coef, const Incidence& inc, const void* B8, const void* B1, int bits,
                    const float* Dinv_f, const double* sc, const float* d_old, const double* coef, float* d_new,
                    const float* z, float* z_new, const float* res, float* res_new, const double* r, double* z_out,
-                   double* rz_part, bool last, C32Bnd bnd) {
-  // lanes per row: two blocks per lane and round; the vertex level of the p-multigrid cycle has ~15 blocks per row
-  // (8 lanes hold them in one round with every lane busy), quadratic tets ~30 (16 lanes), the ANCF shells 100+ (32)
-  static const int forced = std::getenv("TLFEA_C32_LANES") ? std::atoi(std::getenv("TLFEA_C32_LANES")) : 0;
-  const double avg = (double)nnz_coef / std::max(1, N);
-  int L = lp_lanes(N, nnz_coef) >= 32 ? 32 : (avg <= 18.0 ? 8 : 16);
-  if (forced == 8 || forced == 16 || forced == 32) L = forced;
+                   double* rz_part, bool last, C32Bnd bnd, C32Geometry* chosen) {
+  // lanes per row (c32_geometry.h): the vertex level of the p-multigrid cycle has ~15 blocks per row (8 lanes hold them
+  // in one round with every lane busy), quadratic tets ~30 (16 lanes), the ANCF shells 100+ (32)
+  const int L = c32_rule_lanes(N, nnz_coef, lp_lanes(N, nnz_coef), c32_switches().forced_lanes);
 #define TLFEA_C32(T, LL) \
-  launch_cheb32_t<T, LL>(s, N, inc, B8, B1, Dinv_f, sc, d_old, coef, d_new, z, z_new, res, res_new, r, z_out, rz_part, last, bnd)
+  launch_cheb32_t<T, LL>(s, N, inc, B8, B1, Dinv_f, sc, d_old, coef, d_new, z, z_new, res, res_new, r, z_out, rz_part, last, bnd, chosen)
   if (bits == 8) {
     TLFEA_C32(Fp8, 16);   // fine level of T10 meshes only (the experiment's scope)
   } else if (bits == 16) {
@@ -1468,27 +1568,33 @@ __global__ __launch_bounds__(256) void pmg_prolong_kernel(int N, const int* __re
                                                          const double* __restrict__ sc_c,
                                                          const double* __restrict__ sc_f, float* __restrict__ z_f,
                                                          float* __restrict__ d_f, int add) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
+  // a lane per DOF: the three fine streams (sc_f, z_f, d_f) are read and written as whole contiguous lines, the parent
+  // pair of a node is one address for its three lanes, and the parents' entries are fetched without a branch (a == b
+  // re-reads the same address)
+  const size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (j >= 3 * (size_t)N) return;
+  const int i = (int)(j / 3), c = (int)(j - 3 * (size_t)i);
   const int a = par0[i], b = par1[i];
   if (a < 0) {  // no coarse parent (ANCF gradient coefficients): the correction is zero here
-    if (!add) d_f[3 * i] = d_f[3 * i + 1] = d_f[3 * i + 2] = 0.f;
+    if (!add) d_f[j] = 0.f;
     return;
   }
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const double ea = sc_c[3 * a + c] * (double)z_c[3 * a + c];
-    const double e = (a == b) ? ea : 0.5 * (ea + sc_c[3 * b + c] * (double)z_c[3 * b + c]);
-    const float corr = (float)(e / sc_f[3 * i + c]);
-    d_f[3 * i + c] = add ? d_f[3 * i + c] + corr : corr;
-    z_f[3 * i + c] += corr;
-  }
+  const double sa = sc_c[3 * a + c], sb = sc_c[3 * b + c], sf = sc_f[j];
+  const float za = z_c[3 * a + c], zb = z_c[3 * b + c];
+  const float d0 = add ? d_f[j] : 0.f, z0 = z_f[j];
+  const double ea = sa * (double)za;
+  const double e = (a == b) ? ea : 0.5 * (ea + sb * (double)zb);
+  const float corr = (float)(e / sf);
+  d_f[j] = add ? d0 + corr : corr;
+  z_f[j] = z0 + corr;
 }
 // add_to_d: d := d + corr^ (the restricted-operator cycle: the restart pass then subtracts Hs (d_last + corr^) at once)
 void launch_pmg_prolong(hipStream_t s, int N, const int* par0, const int* par1, const float* z_c, const double* sc_c,
                         const double* sc_f, float* z_f, float* d_f, bool add_to_d) {
-  hipLaunchKernelGGL(pmg_prolong_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, par0, par1, z_c, sc_c, sc_f, z_f, d_f,
-                     add_to_d ? 1 : 0);
+  if (N <= 0) return;
+  const size_t n = 3 * (size_t)N;
+  hipLaunchKernelGGL(pmg_prolong_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, N, par0, par1, z_c, sc_c, sc_f,
+                     z_f, d_f, add_to_d ? 1 : 0);
 }
 
 // ---- restricted fine operator R = S_c P^T S_f^-1 Hs (pmg_host.h pmg_restrict_op_build) ------------------------------

@@ -2294,6 +2294,10 @@ struct tlfea_newton_s {
   int mass_mode = 0;          // TLFEA_MASS=csr: always the mass CSR product in grad_kernel
   double *d_p = nullptr, *d_p2 = nullptr, *d_q = nullptr, *d_zv = nullptr;
   double* d_parts = nullptr;  // 6 x kNPart: rz[2], pq, rr, bb, norm
+  // read-back hook (tlfea_newton_get_c32_geometry): the last NON-FINAL polynomial step launched on the fine level [0],
+  // the vertex level [1] and the third level [2]; regime -1 = none yet
+  C32Geometry c32_geo[3] = {{-1}, {-1}, {-1}};
+  C32Geometry* geo_out(int level, bool last) { return last ? nullptr : &c32_geo[level]; }
   double* d_scal = nullptr;   // 4 scalars
   double* h_pin = nullptr;    // pinned host words: [0..7] scalars read back, [8..] Chebyshev coefficients to upload
   double* d_coef = nullptr;   // Chebyshev coefficients on the device (2 per step)
@@ -3965,7 +3969,7 @@ static int cheb_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* 
       const bool last = (k == deg - 1);
       if (hal) TRY(halo_refresh_f32(s, 0, 1, 3, f_d));
       launch_cheb32(s->stream, Nr, d->nnz_coef, d->inc(), s->d_B8, s->d_B1, fine_bits(s), Dinv_f, sc, f_d, s->d_coef + 2 * k, f_d2,
-                    f_z, f_z2, f_r, f_r2, d_r, d_z, rz_part, last, bnd);
+                    f_z, f_z2, f_r, f_r2, d_r, d_z, rz_part, last, bnd, s->geo_out(0, last));
       std::swap(f_d, f_d2);
       std::swap(f_z, f_z2);
       std::swap(f_r, f_r2);
@@ -4649,7 +4653,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
       launch_spmv32_rows(s->stream, s->n_if_loc, s->d_if_node, s->d_if_slot, inc_f, s->d_B8, s->d_B1, bits, din, s->d_ibuf);
       if (nb) TRY(call_allreduce(s, s->d_ibuf, nb));
       launch_cheb32(s->stream, N, d->nnz_coef, inc_f, s->d_B8, s->d_B1, bits, Dinv_f, s->d_sc, din, co, dout, zin, zout, rin,
-                    rout, d_r, d_z, rz_part, last, C32Bnd{s->d_bslot_f, s->d_ibuf, s->d_w});
+                    rout, d_r, d_z, rz_part, last, C32Bnd{s->d_bslot_f, s->d_ibuf, s->d_w}, s->geo_out(0, last));
       return 0;
     };
     auto coarse_step = [&](const float* din, const double* co, float* dout, const float* zin, float* zout,
@@ -4659,7 +4663,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
       launch_spmv32_rows(s->stream, m.n_ifc_loc, m.d_ifc_node, m.d_ifc_slot, inc_c, m.d_B8c, m.d_B1c, bits, din, s->d_ibuf);
       if (nb) TRY(call_allreduce(s, s->d_ibuf, nb));
       launch_cheb32(s->stream, Nc, m.nnz_c, inc_c, m.d_B8c, m.d_B1c, bits, Dinv_fc, m.d_sc_c, din, co, dout, zin, zout, rin,
-                    rout, d_r, d_z, rz_part, false, C32Bnd{m.d_bslot_c, s->d_ibuf, nullptr});
+                    rout, d_r, d_z, rz_part, false, C32Bnd{m.d_bslot_c, s->d_ibuf, nullptr}, s->geo_out(1, false));
       return 0;
     };
     const int ks = pmg_ks(s), o_res = pmg_cf_resid(s), o_rst = pmg_cf_restart(s), o_c = pmg_cf_coarse(s);
@@ -4708,7 +4712,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
     C32Bnd bnd = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
     bnd.zw = weighted ? zw : nullptr;
     launch_cheb32(s->stream, Nf, d->nnz_coef, inc_f, s->d_B8, s->d_B1, fine_bits(s), Dinv_f, s->d_sc, f_d, co, f_d2, f_z, f_z2, f_r,
-                  f_r2, d_r, d_z, rz_part, last, bnd);
+                  f_r2, d_r, d_z, rz_part, last, bnd, s->geo_out(0, last));
     std::swap(f_d, f_d2);
     std::swap(f_z, f_z2);
     std::swap(f_r, f_r2);
@@ -4731,7 +4735,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
     launch_cheb32_init(s->stream, Nf, Dinv_f, d_r, s->d_sc, cf, f_d2, f_z2, f_r2);
     C32Bnd bnd = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
     launch_cheb32(s->stream, Nf, d->nnz_coef, inc_f, s->d_B8, s->d_B1, fine_bits(s), Dinv_f, s->d_sc, f_z, cf + o_res, f_d2, f_z, f_z2,
-                  f_r2, f_r, d_r, d_z, rz_part, false, bnd);
+                  f_r2, f_r, d_r, d_z, rz_part, false, bnd, s->geo_out(0, false));
     std::swap(f_z, f_z2);
   } else
     fine(cf + o_res, false, nullptr);
@@ -4759,7 +4763,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
         valid = G - 1;
       }
       launch_cheb32(s->stream, Nc, m.nnz_c, inc_c, m.d_B8c, m.d_B1c, bits, Dinv_fc, m.d_sc_c, c_d, co, c_d2, c_z, c_z2, c_r, c_r2,
-                    d_r, d_z, rz_part, false);
+                    d_r, d_z, rz_part, false, C32Bnd(), s->geo_out(1, false));
       valid--;
       std::swap(c_d, c_d2);
       std::swap(c_z, c_z2);
@@ -4778,7 +4782,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
     const int k3 = pmg_level3_degree(g.N3);
     for (int k = 1; k < k3; k++) {
       launch_cheb32(s->stream, g.N3, g.nnz3, inc_3, g.d_B8, g.d_B1, bits, Dinv_f3, g.d_sc3, a_d, cf + o3 + 2 * k, a_d2, a_z,
-                    a_z2, a_r, a_r2, d_r, d_z, rz_part, false);
+                    a_z2, a_r, a_r2, d_r, d_z, rz_part, false, C32Bnd(), s->geo_out(2, false));
       std::swap(a_d, a_d2);
       std::swap(a_z, a_z2);
       std::swap(a_r, a_r2);
@@ -4802,7 +4806,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
         valid = G - 1;
       }
       launch_cheb32(s->stream, Nc, m.nnz_c, inc_c, m.d_B8c, m.d_B1c, bits, Dinv_fc, m.d_sc_c, c_d, cf + o_c + 2 * k, c_d2, c_z,
-                    c_z2, c_r, c_r2, d_r, d_z, rz_part, false);
+                    c_z2, c_r, c_r2, d_r, d_z, rz_part, false, C32Bnd(), s->geo_out(1, false));
       valid--;
       std::swap(c_d, c_d2);
       std::swap(c_z, c_z2);
@@ -5562,6 +5566,24 @@ extern "C" int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int* par0, int* par1,
 // tlfea_newton_apply_preconditioner) left on the device, nothing is rebuilt.  Sizes; R as stored (values widened to
 // double, [nnz][9] row-major per block); the fine level's stored copy in the node-block CSR of H, widened likewise,
 // with both scalings.
+// Read-back of the polynomial step's launch geometry (c32_geometry.h): regime (0 last, 1 bandwidth, 2 latency, 3 one-round;
+// -1: no such launch yet), lanes per row, threads per workgroup, blocks per lane issued up front, rows per group, grid of
+// the last NON-FINAL step launched on level 0 (fine), 1 (vertex) or 2 (third level) by a solve or the preconditioner hook,
+// and the occupancy query's answer for the instantiation launched.  Recorded where the host issues the launch: a captured
+// CG graph records it at capture, its replays do not touch it.
+extern "C" int tlfea_newton_get_c32_geometry(tlfea_newton_t s, int level, int* out7) {
+  if (!s || !out7) return fail("tlfea_newton_get_c32_geometry: null argument");
+  if (level < 0 || level > 2) return fail("tlfea_newton_get_c32_geometry: level must be 0, 1 or 2");
+  const C32Geometry& g = s->c32_geo[level];
+  out7[0] = g.regime;
+  out7[1] = g.lanes;
+  out7[2] = g.threads;
+  out7[3] = g.upfront;
+  out7[4] = g.rows_per_group;
+  out7[5] = g.grid;
+  out7[6] = g.resident;
+  return 0;
+}
 extern "C" int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int* out6) {
   if (!s || !out6) return fail("tlfea_newton_pmg_restrict_op_sizes: null argument");
   const auto& m = s->pmg;

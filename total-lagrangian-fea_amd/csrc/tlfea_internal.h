@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <string>
 
+#include "c32_geometry.h"
 #include "mf_host.h"
 
 namespace tlfea {
@@ -264,7 +265,7 @@ struct C32Bnd {
 void launch_cheb32(hipStream_t s, int N, int nnz_coef, const Incidence& inc, const void* B8, const void* B1, int bits,
                    const float* Dinv_f, const double* sc, const float* d_old, const double* coef, float* d_new,
                    const float* z, float* z_new, const float* res, float* res_new, const double* r, double* z_out,
-                   double* rz_part, bool last, C32Bnd bnd = C32Bnd());
+                   double* rz_part, bool last, C32Bnd bnd = C32Bnd(), C32Geometry* chosen = nullptr /*out: the geometry launched*/);
 // out[3 slot[k] + c] = (Hs d)_{rows[k], c} for a list of rows (this rank's part of the partition-boundary rows)
 void launch_spmv32_rows(hipStream_t s, int n_rows, const int* rows, const int* slots, const Incidence& inc, const void* B8,
                         const void* B1, int bits, const float* d, double* out);

@@ -119,6 +119,14 @@ class SyncedNewtonSolver:
         check(self._lib.tlfea_newton_pmg_restrict_op_sizes(self._h, out))
         return dict(zip(("active", "n_coarse", "blocks", "contributions", "fine_blocks", "fine_bits"), list(out)))
 
+    def GetC32Geometry(self, level):
+        """dict(regime, lanes, threads, upfront, rows_per_group, grid, resident) of the last non-final polynomial step launched
+        on level 0 (fine), 1 (vertex) or 2 (third level); regime 1 bandwidth, 2 latency, 3 one-round, -1 none yet; resident:
+        the occupancy query's answer for the instantiation launched, in workgroups (test hook)"""
+        out = (C.c_int * 7)()
+        check(self._lib.tlfea_newton_get_c32_geometry(self._h, int(level), out))
+        return dict(zip(("regime", "lanes", "threads", "upfront", "rows_per_group", "grid", "resident"), list(out)))
+
     def RetrieveRestrictOp(self):
         """(off, cols, vals[blocks, 3, 3]): R as stored after the last set-up, fp32 widened to double (test hook)"""
         info = self.GetRestrictOpInfo()
