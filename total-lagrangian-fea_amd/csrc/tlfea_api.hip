@@ -22,6 +22,7 @@
 #include "ancf_host.h"
 #include "tlfea_internal.h"
 #include "pmg_host.h"
+#include "pmg_coef.h"
 #include "rowgroup_host.h"
 #include "direct_host.h"
 #include "vbd_host.h"
@@ -2155,6 +2156,70 @@ extern "C" double* tlfea_t10_external_force_device_ptr(tlfea_t10_t h) { return h
 extern "C" double* tlfea_t10_constraint_device_ptr(tlfea_t10_t h) { return h->d_cons; }
 
 // =================================================================================================
+// One single-precision polynomial step (launch_cheb32) takes its operands from three places: the level (C32Level), the
+// level's ping-pong vectors (C32Vecs) and the call (rows, coefficient pair, outputs of the last step); c32_step() below.
+struct C32Level {
+  int nnz;
+  Incidence inc;
+  const void *B8, *B1;  // the level's low-precision scaled copy, 8 + 1 entries per block
+  int bits;
+  const double* sc;
+  int geo;  // slot of tlfea_newton_s::c32_geo the launch geometry is recorded in; -1: not recorded
+};
+struct C32Vecs {  // d, z^, res^ and their ping-pong partners (6 x n floats), then (S D S)^-1 (3 n)
+  float *d, *d2, *z, *z2, *r, *r2;
+  const float* Dinv_f;
+  C32Vecs(float* base, size_t n)
+      : d(base), d2(base + n), z(base + 2 * n), z2(base + 3 * n), r(base + 4 * n), r2(base + 5 * n), Dinv_f(base + 6 * n) {}
+  void swap() { std::swap(d, d2); std::swap(z, z2); std::swap(r, r2); }
+};
+// partition-boundary nodes of a level (tlfea_newton_set_interface): their rows are summed over ranks
+struct LevelIface {
+  int n_loc, n_glob;  // boundary nodes on this rank / slots of the exchange buffer
+  const int *d_node, *d_slot;
+  const int* d_bslot;  // [N] exchange slot of a boundary node, -1 inside
+};
+
+// A coarse level of the p-multigrid cycle (vertex level, third level): pattern, operator, block-Jacobi scaling, the
+// low-precision copy its polynomial streams, and the work vectors.  The fine level keeps its members in tlfea_newton_s.
+struct PolyLevel {
+  int N = 0, nnz = 0;  // nodes, 3 x 3 blocks
+  int *d_off = nullptr, *d_cols = nullptr, *d_diagpos = nullptr;
+  double *d_H = nullptr, *d_D = nullptr, *d_Dinv = nullptr, *d_sc = nullptr, *d_Dinv_s = nullptr;
+  double *d_eigv = nullptr, *d_q = nullptr, *d_p = nullptr;  // power iteration: the kept vector and two work vectors
+  void *d_B8 = nullptr, *d_B1 = nullptr;
+  int bits_alloc = 0;
+  float* d_f32 = nullptr;  // C32Vecs(d_f32, 3 N)
+  double lam = 0.0;        // lambda_max(D^-1 H) estimate, warm-started across solves
+  Incidence inc() const { return Incidence{nullptr, nullptr, nullptr, d_off, d_cols, d_diagpos}; }
+  C32Level c32(int bits, int geo) const { return C32Level{nnz, inc(), d_B8, d_B1, bits, d_sc, geo}; }
+  int alloc_work() {  // once N and nnz are known
+    const size_t n = 3 * (size_t)N;
+    TRY(dmalloc(&d_H, (size_t)9 * nnz));
+    TRY(dmalloc(&d_D, (size_t)9 * N)); TRY(dmalloc(&d_Dinv, (size_t)9 * N));
+    TRY(dmalloc(&d_sc, n)); TRY(dmalloc(&d_Dinv_s, (size_t)9 * N));
+    TRY(dmalloc(&d_eigv, n)); TRY(dmalloc(&d_q, n)); TRY(dmalloc(&d_p, n));
+    TRY(dmalloc(&d_f32, 6 * n + (size_t)9 * N));
+    return 0;
+  }
+  int ensure_copy(int bits) {  // storage of the low-precision copy at `bits` per entry
+    if (bits_alloc == bits) return 0;
+    if (d_B8) (void)hipFree(d_B8);
+    if (d_B1) (void)hipFree(d_B1);
+    d_B8 = d_B1 = nullptr;
+    HIP_TRY(hipMalloc(&d_B8, (size_t)nnz * 8 * (bits / 8)));
+    HIP_TRY(hipMalloc(&d_B1, (size_t)nnz * (bits / 8)));
+    bits_alloc = bits;
+    return 0;
+  }
+  void release() {
+    void* p[] = {d_off, d_cols, d_diagpos, d_H, d_D, d_Dinv, d_sc, d_Dinv_s, d_eigv, d_q, d_p, d_B8, d_B1, d_f32};
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+    *this = PolyLevel();
+  }
+};
+
 struct tlfea_newton_s {
   tlfea_t10_t d = nullptr;
   int N = 0, n_constraints = 0;
@@ -2176,18 +2241,11 @@ struct tlfea_newton_s {
   // two-level p-multigrid preconditioner (T10, single GPU): see pmg_host.h / pmg_apply()
   struct Pmg {
     bool tried = false, ok = false;
-    int Nc = 0, nnz_c = 0;
-    int *d_par0 = nullptr, *d_par1 = nullptr, *d_c_off = nullptr, *d_c_cols = nullptr, *d_c_diagpos = nullptr,
-        *d_cblk_row = nullptr, *d_child_off = nullptr, *d_child = nullptr, *d_con_off = nullptr, *d_con_base = nullptr,
-        *d_con_deg = nullptr;
+    PolyLevel vertex;  // the vertex level: Hc = P^T H P
+    int *d_par0 = nullptr, *d_par1 = nullptr, *d_cblk_row = nullptr, *d_child_off = nullptr, *d_child = nullptr,
+        *d_con_off = nullptr, *d_con_base = nullptr, *d_con_deg = nullptr;
     float *d_child_w = nullptr, *d_con_w = nullptr;
-    double *d_Hc = nullptr, *d_Dc = nullptr, *d_Dinv_c = nullptr, *d_sc_c = nullptr, *d_Dinv_s_c = nullptr,
-           *d_eigv_c = nullptr, *d_q_c = nullptr, *d_p_c = nullptr;
-    void *d_B8c = nullptr, *d_B1c = nullptr;
-    int bits_alloc = 0;
-    float* d_f32c = nullptr;   // coarse d, z^, res^ ping-pong pairs (6 x 3Nc) + (S D S)^-1 (9 Nc)
-    double* d_coef = nullptr;  // [0..7] fine smoother, [8..] coarse polynomial
-    double lam_c = 0.0;
+    double* d_coef = nullptr;  // the cycle's coefficient table (pmg_coef.h, PmgTable), kPmgTableCap doubles
     // multi-GPU: the coarse level is partitioned like the fine one (vertex nodes of the partition boundary are
     // replicated); slots of the coarse exchange buffer are agreed once (pmg_prepare), child weights carry 1/multiplicity
     int n_ifc_loc = 0, n_ifc_glob = 0;
@@ -2211,25 +2269,21 @@ struct tlfea_newton_s {
       float *d_ch_w = nullptr, *d_R1 = nullptr;
       void* d_R8 = nullptr;
     } rop;
-    Incidence inc() const { return Incidence{nullptr, nullptr, nullptr, d_c_off, d_c_cols, d_c_diagpos}; }
-    // third level: rigid-body-mode aggregates of the vertex level (pmg_host.h agg_build); N3 = 2 Na nodes
+    LevelIface iface() const { return LevelIface{n_ifc_loc, n_ifc_glob, d_ifc_node, d_ifc_slot, d_bslot_c}; }
+    // third level: rigid-body-mode aggregates of the vertex level (pmg_host.h agg_build); lvl.N = 2 Na nodes
     struct Agg {
       bool ok = false, bins = false;
       double size_ratio = 0.0;  // bins: cell size in mean vertex edges (0: greedy aggregates, ~2.2)
       double* d_r3 = nullptr;  // overlapping partition: this rank's share of the level-3 residual (summed over ranks)
-      int Na = 0, N3 = 0, nnz3 = 0, n_pairs = 0;
-      int *d_agg = nullptr, *d_active = nullptr, *d_mem_off = nullptr, *d_mem = nullptr, *d_off3 = nullptr,
-          *d_cols3 = nullptr, *d_diag3 = nullptr, *d_pair_A = nullptr, *d_pair_pos = nullptr, *d_pair_B = nullptr,
-          *d_pcon_off = nullptr, *d_pcon_base = nullptr, *d_pcon_deg = nullptr, *d_pcon_i = nullptr, *d_pcon_j = nullptr;
-      double *d_rvec = nullptr, *d_H3 = nullptr, *d_D3 = nullptr, *d_Dinv3 = nullptr, *d_sc3 = nullptr,
-             *d_Dinv_s3 = nullptr, *d_eigv3 = nullptr, *d_q3 = nullptr, *d_p3 = nullptr;
-      void *d_B8 = nullptr, *d_B1 = nullptr;
-      int bits_alloc = 0;
-      float* d_f32 = nullptr;  // level-3 d, z^, res^ ping-pong pairs (6 x 3 N3) + (S D S)^-1 (9 N3)
-      double lam3 = 0.0;
-      Incidence inc() const { return Incidence{nullptr, nullptr, nullptr, d_off3, d_cols3, d_diag3}; }
+      int Na = 0, n_pairs = 0;
+      PolyLevel lvl;           // H3 = P2^T Hc P2
+      int *d_agg = nullptr, *d_active = nullptr, *d_mem_off = nullptr, *d_mem = nullptr, *d_pair_A = nullptr,
+          *d_pair_pos = nullptr, *d_pair_B = nullptr, *d_pcon_off = nullptr, *d_pcon_base = nullptr, *d_pcon_deg = nullptr,
+          *d_pcon_i = nullptr, *d_pcon_j = nullptr;
+      double* d_rvec = nullptr;
     } agg;
   } pmg;
+  LevelIface iface() const { return LevelIface{n_if_loc, n_if_glob, d_if_node, d_if_slot, d_bslot_f}; }
   float* d_f32 = nullptr;  // single-precision polynomial (single GPU): d, z, res ping-pong pairs (6 x 3N) + (SDS)^-1 (9N)
   bool fixed_pattern = false, sparsity_done = false;
   int verbose = 0;
@@ -2242,9 +2296,9 @@ struct tlfea_newton_s {
          *d_b = nullptr;
   double *d_step0 = nullptr, *d_lam0 = nullptr;  // v | v_prev and lambda at the start of the running step (roll-back)
   int lam0_cap = 0;
-  bool profiling = false;
+  bool profiling = false;  // per-stage hipEvent timing (adds a host sync per stage)
   int pcg_fused = -1;  // -1 auto (fused direction update below 200k nodes), 0/1 forced (TLFEA_PCG_FUSED)
-  bool spmv_nt = false; // non-temporal loads of H in the SpMV (TLFEA_SPMV_NT): measured slower at config C  // per-stage hipEvent timing (adds a host sync per stage)
+  bool spmv_nt = false; // non-temporal loads of H in the SpMV (TLFEA_SPMV_NT): measured slower at config C
   double *d_xp = nullptr, *d_yp = nullptr, *d_zp = nullptr;
   double *d_H = nullptr, *d_Kbuf = nullptr, *d_Dinv = nullptr;
   // fused tangent + assembly (T10, SVK): row groups (rowgroup_host.h) and the per-point F of the last residual launch.
@@ -2404,8 +2458,8 @@ extern "C" int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_ne
   TRY(dmalloc(&s->d_xp, (size_t)s->N)); TRY(dmalloc(&s->d_yp, (size_t)s->N)); TRY(dmalloc(&s->d_zp, (size_t)s->N));
   TRY(dmalloc(&s->d_parts, (size_t)6 * kNPart));
   TRY(dmalloc(&s->d_scal, (size_t)4));
-  HIP_TRY(hipHostMalloc((void**)&s->h_pin, (8 + 128 + 2 * 64) * sizeof(double)));
-  TRY(dmalloc(&s->d_coef, (size_t)2 * 64));
+  HIP_TRY(hipHostMalloc((void**)&s->h_pin, (8 + kPmgTableCap) * sizeof(double)));
+  TRY(dmalloc(&s->d_coef, (size_t)2 * kChebMaxDeg));
   if (const char* e = std::getenv("TLFEA_GRAPH")) s->use_graphs = std::atoi(e) != 0;
   TRY(dmalloc(&s->d_Dinv, (size_t)9 * s->N));
   TRY(dmalloc(&s->d_D, (size_t)9 * s->N));
@@ -2417,7 +2471,7 @@ extern "C" int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_ne
   s->stream = s->stream_own;
   if (const char* e = std::getenv("TLFEA_PCG_FUSED")) s->pcg_fused = std::atoi(e);
   if (const char* e = std::getenv("TLFEA_SPMV32")) s->spmv32_every = std::max(0, std::atoi(e)) & ~1;  // even: odd parity
-  if (const char* e = std::getenv("TLFEA_CHEB_DEG")) s->lin.cheb_degree = std::min(64, std::max(0, std::atoi(e)));
+  if (const char* e = std::getenv("TLFEA_CHEB_DEG")) s->lin.cheb_degree = std::min(kChebMaxDeg, std::max(0, std::atoi(e)));
   if (const char* e = std::getenv("TLFEA_SPMV_NT")) s->spmv_nt = std::atoi(e) != 0;
   if (const char* e = std::getenv("TLFEA_CHEB_BITS")) s->lin.cheb_bits = std::atoi(e);
   if (const char* e = std::getenv("TLFEA_PRECOND")) s->lin.precond = std::atoi(e);
@@ -2459,22 +2513,22 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
     void* pd[] = {m.d_ifc_node, m.d_ifc_slot, m.d_bslot_c, m.d_wc3, m.d_child_w_dist, s->d_bslot_f};
     for (void* q : pd)
       if (q) (void)hipFree(q);
-    void* pp[] = {m.d_par0, m.d_par1, m.d_c_off, m.d_c_cols, m.d_c_diagpos, m.d_cblk_row, m.d_child_off, m.d_child,
-                  m.d_con_off, m.d_con_base, m.d_con_deg, m.d_child_w, m.d_con_w, m.d_Hc, m.d_Dc, m.d_Dinv_c, m.d_sc_c,
-                  m.d_Dinv_s_c, m.d_eigv_c, m.d_q_c, m.d_p_c, m.d_B8c, m.d_B1c, m.d_f32c, m.d_coef};
+    void* pp[] = {m.d_par0, m.d_par1, m.d_cblk_row, m.d_child_off, m.d_child, m.d_con_off, m.d_con_base, m.d_con_deg,
+                  m.d_child_w, m.d_con_w, m.d_coef};
     for (void* q : pp)
       if (q) (void)hipFree(q);
+    m.vertex.release();
     auto& ro = m.rop;
     void* rr[] = {ro.d_off, ro.d_cols, ro.d_ch_off, ro.d_ch, ro.d_con_off, ro.d_con_blk, ro.d_con_ord, ro.d_ch_w, ro.d_R1,
                   ro.d_R8};
     for (void* q : rr)
       if (q) (void)hipFree(q);
     auto& g = m.agg;
-    void* gg[] = {g.d_agg, g.d_active, g.d_mem_off, g.d_mem, g.d_off3, g.d_cols3, g.d_diag3, g.d_pair_A, g.d_pair_pos,
-                  g.d_pair_B, g.d_pcon_off, g.d_pcon_base, g.d_pcon_deg, g.d_pcon_i, g.d_pcon_j, g.d_rvec, g.d_H3, g.d_D3,
-                  g.d_Dinv3, g.d_sc3, g.d_Dinv_s3, g.d_eigv3, g.d_q3, g.d_p3, g.d_B8, g.d_B1, g.d_f32, g.d_r3};
+    void* gg[] = {g.d_agg, g.d_active, g.d_mem_off, g.d_mem, g.d_pair_A, g.d_pair_pos, g.d_pair_B, g.d_pcon_off,
+                  g.d_pcon_base, g.d_pcon_deg, g.d_pcon_i, g.d_pcon_j, g.d_rvec, g.d_r3};
     for (void* q : gg)
       if (q) (void)hipFree(q);
+    g.lvl.release();
   }
   if (s->d_coef) (void)hipFree(s->d_coef);
   {
@@ -2514,7 +2568,7 @@ extern "C" int tlfea_newton_set_linsolve_opts(tlfea_newton_t s, const tlfea_lins
   s->lin = *o;
   if (s->lin.check_every < 1) s->lin.check_every = 1;
   if (s->lin.cheb_degree < 0) s->lin.cheb_degree = 0;
-  if (s->lin.cheb_degree > 64) s->lin.cheb_degree = 64;
+  if (s->lin.cheb_degree > kChebMaxDeg) s->lin.cheb_degree = kChebMaxDeg;
   if (!(s->lin.cheb_kappa > 1.0)) s->lin.cheb_kappa = 0.0;  // auto
   if (s->lin.cheb_bits != 16 && s->lin.cheb_bits != 32 && s->lin.cheb_bits != 64) s->lin.cheb_bits = 0;
   if (s->lin.precond < 0 || s->lin.precond > 2) s->lin.precond = 0;
@@ -3320,21 +3374,29 @@ static int call_allreduce(tlfea_newton_t s, double* d_buf, int n) {
   return 0;
 }
 
+// host doubles summed over ranks through a device buffer (set-up only: synchronises)
+static int allreduce_host(tlfea_newton_t s, double* d_buf, double* h, size_t n) {
+  HIP_TRY(hipMemcpy(d_buf, h, n * sizeof(double), hipMemcpyHostToDevice));
+  TRY(call_allreduce(s, d_buf, (int)n));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpy(h, d_buf, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
 // Sum over ranks of the partition-boundary entries of a nodal field with `dim` values per node (3 for
 // vectors, 9 for diagonal blocks), optionally fused with `n_extra` reduction slots (one collective).
-static int iface_sum_lvl(tlfea_newton_t s, int n_loc, int n_glob, const int* d_node, const int* d_slot, double* d_vec,
-                         int dim, double* d_extra = nullptr, int n_extra = 0, double* d_extra2 = nullptr);
+static int iface_sum_lvl(tlfea_newton_t s, const LevelIface& I, double* d_vec, int dim, double* d_extra = nullptr,
+                         int n_extra = 0, double* d_extra2 = nullptr);
 static int iface_sum(tlfea_newton_t s, double* d_vec, int dim, double* d_extra = nullptr, int n_extra = 0,
                      double* d_extra2 = nullptr) {
-  return iface_sum_lvl(s, s->n_if_loc, s->n_if_glob, s->d_if_node, s->d_if_slot, d_vec, dim, d_extra, n_extra, d_extra2);
+  return iface_sum_lvl(s, s->iface(), d_vec, dim, d_extra, n_extra, d_extra2);
 }
 // the same for any level of the multigrid hierarchy (its own boundary node / slot lists)
-static int iface_sum_lvl(tlfea_newton_t s, int n_if_loc, int n_if_glob, const int* d_if_node, const int* d_if_slot,
-                         double* d_vec, int dim, double* d_extra, int n_extra, double* d_extra2) {
+static int iface_sum_lvl(tlfea_newton_t s, const LevelIface& I, double* d_vec, int dim, double* d_extra, int n_extra,
+                         double* d_extra2) {
   if (!s->ar) return 0;
-  const int nb = dim * n_if_glob;
+  const int nb = dim * I.n_glob;
   if (nb) HIP_TRY(hipMemsetAsync(s->d_ibuf, 0, (size_t)nb * sizeof(double), s->stream));
-  launch_pack(s->stream, n_if_loc, dim, d_if_node, d_if_slot, d_vec, s->d_ibuf);
+  launch_pack(s->stream, I.n_loc, dim, I.d_node, I.d_slot, d_vec, s->d_ibuf);
   int total = nb;
   if (d_extra) {
     HIP_TRY(hipMemcpyAsync(s->d_ibuf + total, d_extra, (size_t)n_extra * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
@@ -3346,7 +3408,7 @@ static int iface_sum_lvl(tlfea_newton_t s, int n_if_loc, int n_if_glob, const in
   }
   if (total == 0) return 0;
   TRY(call_allreduce(s, s->d_ibuf, total));
-  launch_unpack(s->stream, n_if_loc, dim, d_if_node, d_if_slot, s->d_ibuf, d_vec);
+  launch_unpack(s->stream, I.n_loc, dim, I.d_node, I.d_slot, s->d_ibuf, d_vec);
   int o = nb;
   if (d_extra) {
     HIP_TRY(hipMemcpyAsync(d_extra, s->d_ibuf + o, (size_t)n_extra * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
@@ -3448,11 +3510,7 @@ static int sync_constraints(tlfea_newton_t s) {
   }
   double cnt = 0.0;   // boundary sums: every holder counts its rows; overlapping partition: owners only
   for (int k = 0; k < d->n_constraint; k++) cnt += s->halo.on ? s->h_nw[d->h_fixed[k / 3]] : 1.0;
-  double* buf = s->halo.on ? s->halo.d_red : s->d_ibuf;
-  HIP_TRY(hipMemcpy(buf, &cnt, sizeof(double), hipMemcpyHostToDevice));
-  TRY(call_allreduce(s, buf, 1));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(&cnt, buf, sizeof(double), hipMemcpyDeviceToHost));
+  TRY(allreduce_host(s, s->halo.on ? s->halo.d_red : s->d_ibuf, &cnt, 1));
   s->n_constraints_global = (int)(cnt + 0.5);
   return 0;
 }
@@ -3782,6 +3840,16 @@ static int fine_bits(tlfea_newton_t s) {
   const int bits = cheb_bits_eff(s);
   return (forced == 8 && bits == 16 && precond_eff(s) == 2 && !s->ar) ? 8 : bits;
 }
+static C32Level fine_c32(tlfea_newton_t s) {
+  return C32Level{s->d->nnz_coef, s->d->inc(), s->d_B8, s->d_B1, fine_bits(s), s->d_sc, 0};
+}
+// One step of a level's single-precision polynomial on its first `rows` rows; the ping-pong partners swap roles.
+static void c32_step(tlfea_newton_t s, const C32Level& L, C32Vecs& v, int rows, const double* coef, const double* d_r,
+                     double* d_z, double* rz_part, bool last, C32Bnd bnd = C32Bnd()) {
+  launch_cheb32(s->stream, rows, L.nnz, L.inc, L.B8, L.B1, L.bits, v.Dinv_f, L.sc, v.d, coef, v.d2, v.z, v.z2, v.r, v.r2, d_r,
+                d_z, rz_part, last, bnd, L.geo < 0 ? nullptr : s->geo_out(L.geo, last));
+  v.swap();
+}
 // ANCF kinds, one GPU, polynomial preconditioner on the low-precision copy: the copy is that of L^-1 H L^-T with the 12 x 12
 // node blocks D12 = L L^T (TLFEA_ANCF_BLOCK12=0 keeps the 3 x 3 scaling).  Needs the pattern to come in complete 4 x 4
 // groups of blocks (constraint rows that couple single coefficient vectors break that: then the 3 x 3 form stays).
@@ -3924,18 +3992,8 @@ static int estimate_lam_max(tlfea_newton_t s, const double* d_b) {
 // in device memory (not kernel arguments) so that the captured launch sequence stays valid when lambda_max moves.
 static int cheb_upload_coefficients(tlfea_newton_t s) {
   const int deg = cheb_degree_eff(s);
-  const double b = s->lam_safety * s->lam_max, a = b / cheb_kappa_eff(s);
-  const double theta = 0.5 * (b + a), delta = 0.5 * (b - a), sigma = theta / delta;
-  double rho = 1.0 / sigma;
   double* h = s->h_pin + 8;
-  h[0] = 1.0 / theta;
-  h[1] = 0.0;
-  for (int k = 1; k < deg; k++) {
-    const double rho_new = 1.0 / (2.0 * sigma - rho);
-    h[2 * k] = rho_new * rho;
-    h[2 * k + 1] = 2.0 * rho_new / delta;
-    rho = rho_new;
-  }
+  cheb_pairs(s->lam_safety * s->lam_max, cheb_kappa_eff(s), deg, h);
   HIP_TRY(hipMemcpyAsync(s->d_coef, h, (size_t)2 * deg * sizeof(double), hipMemcpyHostToDevice, s->stream));
   return 0;
 }
@@ -3954,25 +4012,19 @@ static int cheb_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* 
     // single GPU, or rank-local on the owned nodes: the whole polynomial in single precision (cheb32_kernel); d, z,
     // res ping-pong so that a row's stores never order against loads of other rows; the last step returns
     // z = S z^ in fp64 and the r.z slots.  Rank-local: the masked scaling zeroes r and z on nodes another rank owns.
-    if (local) sc = s->d_sc_mask;
-    const size_t n = 3 * (size_t)N;
-    float *f_d = s->d_f32, *f_d2 = f_d + n, *f_z = f_d2 + n, *f_z2 = f_z + n, *f_r = f_z2 + n, *f_r2 = f_r + n;
-    const float* Dinv_f = f_r2 + n;
+    C32Level L = fine_c32(s);
+    if (local) L.sc = s->d_sc_mask;
+    C32Vecs f(s->d_f32, 3 * (size_t)N);
     // init_done: the previous iteration's update kernel already wrote the start vectors (pcg_update_init32_kernel)
     // overlapping partition (meshes without a p-multigrid hierarchy): owned rows only, the direction's first ghost layer
     // is refreshed before every step
     const bool hal = s->halo.on;
     const int Nr = hal ? s->halo.rows(0) : N;
     const C32Bnd bnd = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
-    if (!init_done) launch_cheb32_init(s->stream, Nr, Dinv_f, d_r, sc, s->d_coef, f_d, f_z, f_r);
+    if (!init_done) launch_cheb32_init(s->stream, Nr, f.Dinv_f, d_r, L.sc, s->d_coef, f.d, f.z, f.r);
     for (int k = 1; k < deg; k++) {
-      const bool last = (k == deg - 1);
-      if (hal) TRY(halo_refresh_f32(s, 0, 1, 3, f_d));
-      launch_cheb32(s->stream, Nr, d->nnz_coef, d->inc(), s->d_B8, s->d_B1, fine_bits(s), Dinv_f, sc, f_d, s->d_coef + 2 * k, f_d2,
-                    f_z, f_z2, f_r, f_r2, d_r, d_z, rz_part, last, bnd, s->geo_out(0, last));
-      std::swap(f_d, f_d2);
-      std::swap(f_z, f_z2);
-      std::swap(f_r, f_r2);
+      if (hal) TRY(halo_refresh_f32(s, 0, 1, 3, f.d));
+      c32_step(s, L, f, Nr, s->d_coef + 2 * k, d_r, d_z, rz_part, k == deg - 1, bnd);
     }
     // every node's z comes from its owner (zero elsewhere), r.z = sum over owners: one collective for both
     if (local) TRY(iface_sum(s, d_z, 3, rz_part, kNPart));
@@ -4027,19 +4079,14 @@ static int cheb_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* 
 // (kc, kappa_c) = (12, 200) at 2 197 coarse nodes (config B: 3.9 ms), (32, 1600) at 172 081 (config C: 98 ms; 16/400
 // gives 159 ms, 48/3200 108 ms) -- about 3.2 per doubling of the node count, with kappa_c = 1.5 kc^2.  The fine
 // smoother stays the 2-term polynomial on [lmax/8, lmax] (kappa_s 5 / 8 / 12: 103 / 98 / 158 ms at config C).
-static const int kPmgMaxCoarseDeg = 64;
-static int pmg_coarse_degree(int n_coarse) {
-  static const int forced = std::getenv("TLFEA_PMG_KC") ? std::atoi(std::getenv("TLFEA_PMG_KC")) : 0;
-  if (forced > 1) return std::min(forced, kPmgMaxCoarseDeg);
-  const double kc = 12.0 + 3.2 * (std::log2((double)std::max(2, n_coarse)) - 11.1);
-  return std::max(8, std::min(kPmgMaxCoarseDeg, (int)std::lround(kc)));
-}
 static double pmg_kappa_coarse(int kc) {
   static const double forced = std::getenv("TLFEA_PMG_KAPPA_C") ? std::atof(std::getenv("TLFEA_PMG_KAPPA_C")) : 0.0;
   return forced > 1.0 ? forced : 1.5 * kc * kc;
 }
 static int pmg_coarse_degree_eff(tlfea_newton_t s) {
-  const int base = pmg_coarse_degree((dist_on(s) && s->pmg.Nc_glob > 0) ? s->pmg.Nc_glob : s->pmg.Nc);
+  static const int forced = std::getenv("TLFEA_PMG_KC") ? std::atoi(std::getenv("TLFEA_PMG_KC")) : 0;
+  const int n_vertex = (dist_on(s) && s->pmg.Nc_glob > 0) ? s->pmg.Nc_glob : s->pmg.vertex.N;
+  const int base = pmg_poly_degree(n_vertex, forced, kPmgMaxCoarseDeg);
   return std::min(kPmgMaxCoarseDeg, (int)std::lround(base * s->pmg.kc_boost));
 }
 // terms of the fine smoother's Chebyshev polynomial (TLFEA_PMG_KS): pre- and post-smoothing cost ks fine passes each
@@ -4048,7 +4095,6 @@ static int pmg_coarse_degree_eff(tlfea_newton_t s) {
 // few microseconds and the vertex-level polynomial's 10-60 launches dominate (meshes up to ~100 k nodes, the reference's
 // real meshes: 4 terms cut res16 from 7.9 to 6.4 ms and the badly graded teapot from 35.7 to 24.6 ms per Newton iteration,
 // profiles/r03_real_mesh_timing.txt).  The partitioned solve keeps 2 (the ghost depth it needs grows with ks).
-static const int kPmgMaxKs = 12;
 static int pmg_ks(tlfea_newton_t s) {
   static const int forced = std::getenv("TLFEA_PMG_KS") ? std::atoi(std::getenv("TLFEA_PMG_KS")) : 0;
   if (forced >= 1) return std::min(forced, kPmgMaxKs);
@@ -4062,14 +4108,8 @@ static double pmg_kappa_s(tlfea_newton_t s) {
   const int ks = pmg_ks(s);
   return ks <= 2 ? 8.0 : 1.5 * ks * ks;
 }
-// coefficient table of the cycle (device doubles): [0 .. 2 ks) init + steps of the fine smoother, then the residual pass
-// (0, 0), the post-smoothing restart (0, 1/theta), then the coarse polynomial
-static int pmg_cf_resid(tlfea_newton_t s) { return 2 * pmg_ks(s); }
-static int pmg_cf_restart(tlfea_newton_t s) { return 2 * pmg_ks(s) + 2; }
-static int pmg_cf_beta(tlfea_newton_t s) { return 2 * pmg_ks(s) + 4; }                 // ks weights of z^ += beta_k d
-static int pmg_cf_coarse(tlfea_newton_t s) { return 2 * pmg_ks(s) + 4 + kPmgMaxKs; }
-// three levels: the vertex level smooths with ks2 terms (TLFEA_PMG_KS2, default 2) -- its table [steps | residual pass |
-// restart] sits where the two-level cycle keeps the vertex-level polynomial; the level-3 polynomial follows
+// three levels: the vertex level smooths with ks2 terms (TLFEA_PMG_KS2) -- its table [steps | residual pass | restart]
+// sits where the two-level cycle keeps the vertex-level polynomial; the level-3 polynomial follows (pmg_coef.h, PmgTable)
 static int pmg_ks2(tlfea_newton_t s) {
   static const int forced = std::getenv("TLFEA_PMG_KS2") ? std::atoi(std::getenv("TLFEA_PMG_KS2")) : 0;
   if (forced >= 1) return std::min(forced, kPmgMaxKs);
@@ -4084,7 +4124,6 @@ static double pmg_kappa_s2(tlfea_newton_t s) {
   const int k = pmg_ks2(s);
   return forced > 1.0 ? forced : 2.5 * k * k;  // 90 at 6 terms (measured optimum 60-100)
 }
-static int pmg_cf_level3(tlfea_newton_t s) { return pmg_cf_coarse(s) + 2 * pmg_ks2(s) + 4; }
 // Smoother polynomial (TLFEA_PMG_SMOOTHER): 1 = first-kind Chebyshev on [lmax / kappa_s, lmax] (the default),
 // 3 = fourth-kind Chebyshev (needs lmax only), 4 = fourth kind with the optimised weights of Lottes (2022),
 // "Optimal polynomial smoothers for multigrid V-cycles": the z^ update is weighted, z^_k = z^_{k-1} + beta_k d_{k-1}.
@@ -4128,13 +4167,16 @@ static int pmg_levels_wanted(int n_vertex) {
 }
 static int pmg_level3_degree(int n3) {
   static const int forced = std::getenv("TLFEA_PMG_KC3") ? std::atoi(std::getenv("TLFEA_PMG_KC3")) : 0;
-  if (forced > 1) return std::min(forced, kPmgMaxCoarseDeg - 4);
-  const double kc = 12.0 + 3.2 * (std::log2((double)std::max(2, n3)) - 11.1);
-  return std::max(8, std::min(kPmgMaxCoarseDeg - 4, (int)std::lround(kc)));
+  return pmg_poly_degree(n3, forced, kPmgMaxLevel3Deg);
 }
 static double pmg_kappa_level3(int kc) {
   static const double forced = std::getenv("TLFEA_PMG_KAPPA_C3") ? std::atof(std::getenv("TLFEA_PMG_KAPPA_C3")) : 0.0;
   return forced > 1.0 ? forced : 1.5 * kc * kc;
+}
+// shape of the cycle a solve would run now, hence where its coefficients sit in pmg.d_coef
+static PmgTable pmg_table(tlfea_newton_t s) {
+  if (s->pmg.agg.ok) return PmgTable{pmg_ks(s), pmg_ks2(s), 0, pmg_level3_degree(s->pmg.agg.lvl.N), 3};
+  return PmgTable{pmg_ks(s), 0, pmg_coarse_degree_eff(s), 0, 2};
 }
 
 template <typename T>
@@ -4171,23 +4213,19 @@ static int pmg_prepare(tlfea_newton_t s) {
     if (s->verbose) std::printf("p-multigrid: the mesh is not a conforming T10 mesh, using the polynomial preconditioner\n");
     return 0;
   }
-  m.Nc = h.Nc;
-  m.nnz_c = h.nnz_c;
+  m.vertex.N = h.Nc;
+  m.vertex.nnz = h.nnz_c;
   TRY(upload_vec(&m.d_par0, h.par0)); TRY(upload_vec(&m.d_par1, h.par1));
-  TRY(upload_vec(&m.d_c_off, h.c_off)); TRY(upload_vec(&m.d_c_cols, h.c_cols)); TRY(upload_vec(&m.d_c_diagpos, h.c_diagpos));
+  TRY(upload_vec(&m.vertex.d_off, h.c_off)); TRY(upload_vec(&m.vertex.d_cols, h.c_cols)); TRY(upload_vec(&m.vertex.d_diagpos, h.c_diagpos));
   TRY(upload_vec(&m.d_cblk_row, h.cblk_row));
   TRY(upload_vec(&m.d_child_off, h.child_off)); TRY(upload_vec(&m.d_child, h.child)); TRY(upload_vec(&m.d_child_w, h.child_w));
   TRY(upload_vec(&m.d_con_off, h.con_off)); TRY(upload_vec(&m.d_con_base, h.con_base)); TRY(upload_vec(&m.d_con_deg, h.con_deg));
   TRY(upload_vec(&m.d_con_w, h.con_w));
-  const size_t nc = 3 * (size_t)m.Nc;
-  TRY(dmalloc(&m.d_Hc, (size_t)9 * m.nnz_c));
-  TRY(dmalloc(&m.d_Dc, (size_t)9 * m.Nc)); TRY(dmalloc(&m.d_Dinv_c, (size_t)9 * m.Nc));
-  TRY(dmalloc(&m.d_sc_c, nc)); TRY(dmalloc(&m.d_Dinv_s_c, (size_t)9 * m.Nc));
-  TRY(dmalloc(&m.d_eigv_c, nc)); TRY(dmalloc(&m.d_q_c, nc)); TRY(dmalloc(&m.d_p_c, nc));
-  TRY(dmalloc(&m.d_f32c, 6 * nc + (size_t)9 * m.Nc));
-  TRY(dmalloc(&m.d_coef, (size_t)5 * kPmgMaxKs + 8 + 2 * kPmgMaxCoarseDeg));
+  const size_t nc = 3 * (size_t)m.vertex.N;
+  TRY(m.vertex.alloc_work());
+  TRY(dmalloc(&m.d_coef, (size_t)kPmgTableCap));
   m.ok = true;
-  if (s->verbose) std::printf("p-multigrid: %d fine nodes -> %d vertex nodes, %d coarse blocks\n", d->N, m.Nc, m.nnz_c);
+  if (s->verbose) std::printf("p-multigrid: %d fine nodes -> %d vertex nodes, %d coarse blocks\n", d->N, m.vertex.N, m.vertex.nnz);
   if (pmg_rop_possible(s)) {
     RopHost ro;
     if (pmg_restrict_op_build(d->N, d->h_off.data(), d->h_cols.data(), h, ro)) {
@@ -4204,7 +4242,7 @@ static int pmg_prepare(tlfea_newton_t s) {
       if (s->verbose)
         std::printf("p-multigrid: restricted fine operator, %d blocks (%.3f of H), %d contributions, %.1f MB\n", r.nnz,
                     (double)r.nnz / std::max(1, d->nnz_coef), r.n_con,
-                    (44.0 * r.nnz + 5.0 * r.n_con + 8.0 * ro.ch.size() + 4.0 * m.Nc) / 1048576.0);
+                    (44.0 * r.nnz + 5.0 * r.n_con + 8.0 * ro.ch.size() + 4.0 * m.vertex.N) / 1048576.0);
     }
   }
   if (s->ar) {
@@ -4227,7 +4265,7 @@ static int pmg_prepare(tlfea_newton_t s) {
     int nc_glob = 0;
     for (int t = 0; t < ng; t++)
       if (flag[t] > 0.5) cslot[t] = nc_glob++;
-    std::vector<int> cn, cs, bs((size_t)m.Nc, -1);
+    std::vector<int> cn, cs, bs((size_t)m.vertex.N, -1);
     for (int k = 0; k < nl; k++) {
       const int n = s->h_if_node[k];
       if (h.par0[n] != h.par1[n]) continue;
@@ -4241,18 +4279,15 @@ static int pmg_prepare(tlfea_newton_t s) {
     if (cn.empty()) { cn.push_back(0); cs.push_back(0); }
     TRY(upload_vec(&m.d_ifc_node, cn)); TRY(upload_vec(&m.d_ifc_slot, cs)); TRY(upload_vec(&m.d_bslot_c, bs));
     std::vector<double> wc3(nc);
-    for (int I = 0; I < m.Nc; I++) {
+    for (int I = 0; I < m.vertex.N; I++) {
       const double w = s->h_nw[h.child[h.child_off[I]]];  // the vertex itself is its first child
       wc3[3 * (size_t)I] = wc3[3 * (size_t)I + 1] = wc3[3 * (size_t)I + 2] = w;
     }
     TRY(upload_vec(&m.d_wc3, wc3));
     {
       double cnt = 0.0;
-      for (int I = 0; I < m.Nc; I++) cnt += wc3[3 * (size_t)I];
-      HIP_TRY(hipMemcpy(s->d_ibuf, &cnt, sizeof(double), hipMemcpyHostToDevice));
-      TRY(call_allreduce(s, s->d_ibuf, 1));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      HIP_TRY(hipMemcpy(&cnt, s->d_ibuf, sizeof(double), hipMemcpyDeviceToHost));
+      for (int I = 0; I < m.vertex.N; I++) cnt += wc3[3 * (size_t)I];
+      TRY(allreduce_host(s, s->d_ibuf, &cnt, 1));
       m.Nc_glob = (int)std::lround(cnt);
     }
     std::vector<float> cw(h.child_w);
@@ -4290,8 +4325,8 @@ static int pmg_prepare(tlfea_newton_t s) {
     // owner weights and layer counts of the coarse nodes (coarse ids ascend with the fine ids of their vertices, so the
     // coarse numbering is ordered by layer as well -- checked)
     std::vector<double> wc3(nc);
-    std::vector<int> lay_c((size_t)m.Nc);
-    for (int I = 0; I < m.Nc; I++) {
+    std::vector<int> lay_c((size_t)m.vertex.N);
+    for (int I = 0; I < m.vertex.N; I++) {
       const int nf = h.child[h.child_off[I]];  // the vertex itself is its first child
       lay_c[I] = hl.layer[nf];
       wc3[3 * (size_t)I] = wc3[3 * (size_t)I + 1] = wc3[3 * (size_t)I + 2] = lay_c[I] == 0 ? 1.0 : 0.0;
@@ -4301,27 +4336,24 @@ static int pmg_prepare(tlfea_newton_t s) {
     for (int k = 0; k <= hl.depth; k++) hl.n_upto_c[k] = (int)(std::upper_bound(lay_c.begin(), lay_c.end(), k) - lay_c.begin());
     TRY(upload_vec(&m.d_wc3, wc3));
     double cnt = hl.n_upto_c[0];
-    HIP_TRY(hipMemcpy(hl.d_red, &cnt, sizeof(double), hipMemcpyHostToDevice));
-    TRY(call_allreduce(s, hl.d_red, 1));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(&cnt, hl.d_red, sizeof(double), hipMemcpyDeviceToHost));
+    TRY(allreduce_host(s, hl.d_red, &cnt, 1));
     m.Nc_glob = (int)std::lround(cnt);
     if (s->verbose)
       std::printf("p-multigrid: overlapped coarse level, %d owned of %d local vertices (%d over all ranks)\n", hl.n_upto_c[0],
-                  m.Nc, m.Nc_glob);
+                  m.vertex.N, m.Nc_glob);
   }
   // third level: single GPU (greedy aggregates, or the grid of bins with TLFEA_PMG_AGG=bins) and the overlapping
   // partition (bins: the level is replicated on every rank, see pmg_host.h)
   const bool l3_halo = s->halo.on && s->halo.world > 0;
-  if ((!dist_on(s) || l3_halo) && pmg_levels_wanted(s->halo.on ? m.Nc_glob : m.Nc) == 3) {
+  if ((!dist_on(s) || l3_halo) && pmg_levels_wanted(s->halo.on ? m.Nc_glob : m.vertex.N) == 3) {
     // reference coordinates of the vertex nodes (slot 0 of a coarse node's children is the vertex itself)
-    std::vector<double> xf((size_t)3 * d->N), Xv((size_t)3 * m.Nc);
+    std::vector<double> xf((size_t)3 * d->N), Xv((size_t)3 * m.vertex.N);
     D2H(xf.data(), d->d_xt, (size_t)d->N);
     D2H(xf.data() + d->N, d->d_yt, (size_t)d->N);
     D2H(xf.data() + 2 * (size_t)d->N, d->d_zt, (size_t)d->N);
-    for (int I = 0; I < m.Nc; I++) {
+    for (int I = 0; I < m.vertex.N; I++) {
       const int n = h.child[h.child_off[I]];
-      for (int c = 0; c < 3; c++) Xv[(size_t)c * m.Nc + I] = xf[(size_t)c * d->N + n];
+      for (int c = 0; c < 3; c++) Xv[(size_t)c * m.vertex.N + I] = xf[(size_t)c * d->N + n];
     }
     AggHost a;
     auto& g = m.agg;
@@ -4333,27 +4365,27 @@ static int pmg_prepare(tlfea_newton_t s) {
       // --- grid of bins.  Agreed numbers: bounding box, mean / longest vertex edge (over owned rows), then the moments ---
       std::vector<char> owned;
       if (s->halo.on) {
-        owned.resize((size_t)m.Nc);
-        for (int I = 0; I < m.Nc; I++) owned[I] = s->halo.layer[h.child[h.child_off[I]]] == 0;
+        owned.resize((size_t)m.vertex.N);
+        for (int I = 0; I < m.vertex.N; I++) owned[I] = s->halo.layer[h.child[h.child_off[I]]] == 0;
       }
       const char* own = s->halo.on ? owned.data() : nullptr;
       double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, sum_len = 0.0, n_len = 0.0, max_len = 0.0;
-      for (int I = 0; I < m.Nc; I++) {
+      for (int I = 0; I < m.vertex.N; I++) {
         if (own && !own[I]) continue;
         for (int c = 0; c < 3; c++) {
-          lo[c] = std::min(lo[c], Xv[(size_t)c * m.Nc + I]);
-          hi[c] = std::max(hi[c], Xv[(size_t)c * m.Nc + I]);
+          lo[c] = std::min(lo[c], Xv[(size_t)c * m.vertex.N + I]);
+          hi[c] = std::max(hi[c], Xv[(size_t)c * m.vertex.N + I]);
         }
         for (int k = h.c_off[I]; k < h.c_off[I + 1]; k++) {
           const int J = h.c_cols[k];
           if (J == I) continue;
           double l2 = 0.0;
-          for (int c = 0; c < 3; c++) l2 += (Xv[(size_t)c * m.Nc + I] - Xv[(size_t)c * m.Nc + J]) * (Xv[(size_t)c * m.Nc + I] - Xv[(size_t)c * m.Nc + J]);
+          for (int c = 0; c < 3; c++) l2 += (Xv[(size_t)c * m.vertex.N + I] - Xv[(size_t)c * m.vertex.N + J]) * (Xv[(size_t)c * m.vertex.N + I] - Xv[(size_t)c * m.vertex.N + J]);
           const double l = std::sqrt(l2);
           sum_len += l; n_len += 1.0; max_len = std::max(max_len, l);
         }
       }
-      double n_own_glob = s->halo.on ? 0.0 : (double)m.Nc;
+      double n_own_glob = s->halo.on ? 0.0 : (double)m.vertex.N;
       if (s->halo.on) {
         // gather-by-sum: rank r fills slots [9 r, 9 r + 9) of a zero vector, the all-reduce hands every rank all of them
         const int W = s->halo.world, R = s->halo.rank;
@@ -4361,10 +4393,7 @@ static int pmg_prepare(tlfea_newton_t s) {
         std::vector<double> v((size_t)9 * W, 0.0);
         const double mine[9] = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], sum_len, n_len, max_len};
         std::copy(mine, mine + 9, v.begin() + (size_t)9 * R);
-        HIP_TRY(hipMemcpy(s->halo.d_red, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
-        TRY(call_allreduce(s, s->halo.d_red, 9 * W));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMemcpy(v.data(), s->halo.d_red, v.size() * sizeof(double), hipMemcpyDeviceToHost));
+        TRY(allreduce_host(s, s->halo.d_red, v.data(), v.size()));
         sum_len = n_len = max_len = 0.0;
         for (int r = 0; r < W; r++) {
           for (int c = 0; c < 3; c++) {
@@ -4385,7 +4414,7 @@ static int pmg_prepare(tlfea_newton_t s) {
       while ((double)grid.cells() > max_bins) grid = bin_grid(lo, hi, mean_len, max_len, (grid.size / mean_len) * 1.1);
       std::vector<int> agg;
       std::vector<double> mom;
-      bin_moments(m.Nc, Xv.data(), grid, own, agg, mom);
+      bin_moments(m.vertex.N, Xv.data(), grid, own, agg, mom);
       if (s->halo.on) {
         double* d_m = nullptr;
         TRY(dmalloc(&d_m, mom.size()));
@@ -4395,7 +4424,7 @@ static int pmg_prepare(tlfea_newton_t s) {
         HIP_TRY(hipMemcpy(mom.data(), d_m, mom.size() * sizeof(double), hipMemcpyDeviceToHost));
         (void)hipFree(d_m);
       }
-      built = agg_build_bins(m.Nc, h.c_off.data(), h.c_cols.data(), Xv.data(), grid, agg, mom, own, a);
+      built = agg_build_bins(m.vertex.N, h.c_off.data(), h.c_cols.data(), Xv.data(), grid, agg, mom, own, a);
       g.bins = built;
       g.size_ratio = built ? grid.size / mean_len : 0.0;
       if (s->verbose)
@@ -4405,225 +4434,150 @@ static int pmg_prepare(tlfea_newton_t s) {
       if (s->halo.on) {
         // every rank must take the same branch: agree that ALL built the level
         double okv = built ? 0.0 : 1.0;
-        HIP_TRY(hipMemcpy(s->halo.d_red, &okv, sizeof(double), hipMemcpyHostToDevice));
-        TRY(call_allreduce(s, s->halo.d_red, 1));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMemcpy(&okv, s->halo.d_red, sizeof(double), hipMemcpyDeviceToHost));
+        TRY(allreduce_host(s, s->halo.d_red, &okv, 1));
         built = built && okv < 0.5;
       }
     } else {
-      built = agg_build(m.Nc, h.c_off.data(), h.c_cols.data(), Xv.data(), a);
+      built = agg_build(m.vertex.N, h.c_off.data(), h.c_cols.data(), Xv.data(), a);
     }
     if (built) {
-      g.Na = a.Na; g.N3 = a.N3; g.nnz3 = a.nnz3; g.n_pairs = a.n_pairs;
+      g.Na = a.Na; g.lvl.N = a.N3; g.lvl.nnz = a.nnz3; g.n_pairs = a.n_pairs;
       TRY(upload_vec(&g.d_agg, a.agg)); TRY(upload_vec(&g.d_active, a.active)); TRY(upload_vec(&g.d_rvec, a.rvec));
       TRY(upload_vec(&g.d_mem_off, a.mem_off));
       if (a.mem.empty()) a.mem.push_back(0);
       TRY(upload_vec(&g.d_mem, a.mem));
-      TRY(upload_vec(&g.d_off3, a.off3)); TRY(upload_vec(&g.d_cols3, a.cols3)); TRY(upload_vec(&g.d_diag3, a.diag3));
+      TRY(upload_vec(&g.lvl.d_off, a.off3)); TRY(upload_vec(&g.lvl.d_cols, a.cols3)); TRY(upload_vec(&g.lvl.d_diagpos, a.diag3));
       TRY(upload_vec(&g.d_pair_A, a.pair_A)); TRY(upload_vec(&g.d_pair_pos, a.pair_pos)); TRY(upload_vec(&g.d_pair_B, a.pair_B));
       TRY(upload_vec(&g.d_pcon_off, a.pcon_off)); TRY(upload_vec(&g.d_pcon_base, a.pcon_base));
       TRY(upload_vec(&g.d_pcon_deg, a.pcon_deg)); TRY(upload_vec(&g.d_pcon_i, a.pcon_i)); TRY(upload_vec(&g.d_pcon_j, a.pcon_j));
-      const size_t n3 = 3 * (size_t)g.N3;
-      TRY(dmalloc(&g.d_H3, (size_t)9 * g.nnz3));
-      TRY(dmalloc(&g.d_D3, (size_t)9 * g.N3)); TRY(dmalloc(&g.d_Dinv3, (size_t)9 * g.N3));
-      TRY(dmalloc(&g.d_sc3, n3)); TRY(dmalloc(&g.d_Dinv_s3, (size_t)9 * g.N3));
-      TRY(dmalloc(&g.d_eigv3, n3)); TRY(dmalloc(&g.d_q3, n3)); TRY(dmalloc(&g.d_p3, n3));
-      TRY(dmalloc(&g.d_f32, 6 * n3 + (size_t)9 * g.N3));
-      if (s->halo.on) TRY(dmalloc(&g.d_r3, n3));
+      TRY(g.lvl.alloc_work());
+      if (s->halo.on) TRY(dmalloc(&g.d_r3, 3 * (size_t)g.lvl.N));
       g.ok = true;
       if (s->verbose)
-        std::printf("p-multigrid: third level, %d aggregates with rigid-body modes (%d nodes, %d blocks)\n", g.Na, g.N3, g.nnz3);
+        std::printf("p-multigrid: third level, %d aggregates with rigid-body modes (%d nodes, %d blocks)\n", g.Na, g.lvl.N,
+                    g.lvl.nnz);
     }
   }
   return 0;
+}
+
+// Galerkin operators of the current H: Hc = P^T H P, H3 = P2^T Hc P2
+static void vertex_galerkin(tlfea_newton_t s) {
+  auto& m = s->pmg;
+  launch_pmg_galerkin(s->stream, m.vertex.nnz, m.vertex.d_off, m.d_cblk_row, m.d_con_off, m.d_con_base, m.d_con_deg, m.d_con_w,
+                      s->d_H, m.vertex.d_H);
+}
+static void level3_galerkin(tlfea_newton_t s) {
+  auto& g = s->pmg.agg;
+  launch_agg_galerkin(s->stream, g.n_pairs, g.d_pair_A, g.d_pair_pos, g.d_pair_B, g.d_pcon_off, g.d_pcon_base, g.d_pcon_deg,
+                      g.d_pcon_i, g.d_pcon_j, g.d_rvec, g.d_active, g.lvl.d_off, s->pmg.vertex.d_H, g.lvl.d_H);
+}
+
+// block-Jacobi scaling and low-precision copy of a coarse level whose d_H and d_D are current
+static void level_scale_convert(tlfea_newton_t s, PolyLevel& L, int bits) {
+  launch_invert_diag(s->stream, L.N, L.d_D, L.d_Dinv);
+  launch_lp_scale(s->stream, L.N, L.d_D, L.d_Dinv, L.d_sc, L.d_Dinv_s);
+  launch_lp_convert(s->stream, L.N, L.inc(), L.d_H, L.d_sc, nullptr, L.d_D, L.d_B8, L.d_B1, bits);
+  launch_to_float(s->stream, (size_t)9 * L.N, L.d_Dinv_s, L.d_f32 + (size_t)18 * L.N);
 }
 
 // per solve, after H and the fine block diagonal are current: Hc = P^T H P, its block-Jacobi scaling and fp16 copy
 static int pmg_build_level(tlfea_newton_t s) {
   auto& m = s->pmg;
+  PolyLevel& V = m.vertex;
   const int bits = cheb_bits_eff(s);
-  launch_pmg_galerkin(s->stream, m.nnz_c, m.d_c_off, m.d_cblk_row, m.d_con_off, m.d_con_base, m.d_con_deg, m.d_con_w,
-                      s->d_H, m.d_Hc);
-  if (m.bits_alloc != bits) {
-    if (m.d_B8c) (void)hipFree(m.d_B8c);
-    if (m.d_B1c) (void)hipFree(m.d_B1c);
-    m.d_B8c = m.d_B1c = nullptr;
-    HIP_TRY(hipMalloc(&m.d_B8c, (size_t)m.nnz_c * 8 * (bits / 8)));
-    HIP_TRY(hipMalloc(&m.d_B1c, (size_t)m.nnz_c * (bits / 8)));
-    m.bits_alloc = bits;
-  }
-  const Incidence ic = m.inc();
-  launch_extract_diag(s->stream, m.Nc, ic, m.d_Hc, m.d_Dc);
+  vertex_galerkin(s);
+  TRY(V.ensure_copy(bits));
+  launch_extract_diag(s->stream, V.N, V.inc(), V.d_H, V.d_D);
   // multi-GPU: Hc = sum over ranks of P^T H_r P -- the diagonal blocks of boundary vertices are partial per rank
-  if (s->ar) TRY(iface_sum_lvl(s, m.n_ifc_loc, m.n_ifc_glob, m.d_ifc_node, m.d_ifc_slot, m.d_Dc, 9));
+  if (s->ar) TRY(iface_sum_lvl(s, m.iface(), V.d_D, 9));
   // overlapping partition: rows of the outermost ghost layer are incomplete -- their diagonal blocks (hence the scaling of
   // their COLUMNS in every complete row) come from their owners
-  TRY(halo_refresh_f64(s, 1, s->halo.depth, 9, m.d_Dc));
-  launch_invert_diag(s->stream, m.Nc, m.d_Dc, m.d_Dinv_c);
-  launch_lp_scale(s->stream, m.Nc, m.d_Dc, m.d_Dinv_c, m.d_sc_c, m.d_Dinv_s_c);
-  launch_lp_convert(s->stream, m.Nc, ic, m.d_Hc, m.d_sc_c, nullptr, m.d_Dc, m.d_B8c, m.d_B1c, bits);
-  launch_to_float(s->stream, (size_t)9 * m.Nc, m.d_Dinv_s_c, m.d_f32c + (size_t)18 * m.Nc);
+  TRY(halo_refresh_f64(s, 1, s->halo.depth, 9, V.d_D));
+  level_scale_convert(s, V, bits);
   m.rop.built = false;
   if (pmg_rop_on(s)) {  // R = S_c P^T S_f^-1 Hs from the fine copy as stored (lp_build ran before) and both scalings
     auto& r = m.rop;
-    launch_pmg_rop_build(s->stream, m.Nc, r.d_off, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch, r.d_ch_w,
-                         s->d_B8, s->d_B1, fine_bits(s), s->d_sc, m.d_sc_c, r.d_R8, r.d_R1);
+    launch_pmg_rop_build(s->stream, V.N, r.d_off, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch, r.d_ch_w,
+                         s->d_B8, s->d_B1, fine_bits(s), s->d_sc, V.d_sc, r.d_R8, r.d_R1);
     r.built = true;
   }
   if (m.agg.ok) {  // third level: H3 = P2^T Hc P2, its scaling and low-precision copy
-    auto& g = m.agg;
-    launch_agg_galerkin(s->stream, g.n_pairs, g.d_pair_A, g.d_pair_pos, g.d_pair_B, g.d_pcon_off, g.d_pcon_base,
-                        g.d_pcon_deg, g.d_pcon_i, g.d_pcon_j, g.d_rvec, g.d_active, g.d_off3, m.d_Hc, g.d_H3);
+    PolyLevel& A = m.agg.lvl;
+    level3_galerkin(s);
     // overlapping partition: every rank summed the vertex-level rows it OWNS; the level is replicated, so the shares are
     // added once per Newton iteration (identical bits on every rank afterwards: the level-3 polynomial needs no exchange)
-    if (s->halo.on) TRY(call_allreduce(s, g.d_H3, 9 * g.nnz3));
-    if (g.bits_alloc != bits) {
-      if (g.d_B8) (void)hipFree(g.d_B8);
-      if (g.d_B1) (void)hipFree(g.d_B1);
-      g.d_B8 = g.d_B1 = nullptr;
-      HIP_TRY(hipMalloc(&g.d_B8, (size_t)g.nnz3 * 8 * (bits / 8)));
-      HIP_TRY(hipMalloc(&g.d_B1, (size_t)g.nnz3 * (bits / 8)));
-      g.bits_alloc = bits;
-    }
-    const Incidence i3 = g.inc();
-    launch_extract_diag(s->stream, g.N3, i3, g.d_H3, g.d_D3);
-    launch_invert_diag(s->stream, g.N3, g.d_D3, g.d_Dinv3);
-    launch_lp_scale(s->stream, g.N3, g.d_D3, g.d_Dinv3, g.d_sc3, g.d_Dinv_s3);
-    launch_lp_convert(s->stream, g.N3, i3, g.d_H3, g.d_sc3, nullptr, g.d_D3, g.d_B8, g.d_B1, bits);
-    launch_to_float(s->stream, (size_t)9 * g.N3, g.d_Dinv_s3, g.d_f32 + (size_t)18 * g.N3);
+    if (s->halo.on) TRY(call_allreduce(s, A.d_H, 9 * A.nnz));
+    TRY(A.ensure_copy(bits));
+    launch_extract_diag(s->stream, A.N, A.inc(), A.d_H, A.d_D);
+    level_scale_convert(s, A, bits);
   }
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-// lambda_max(Dc^-1 Hc) by power iteration (warm-started), then both coefficient tables to the device:
-//   d_coef[0..7]: fine smoother on [lmax/kappa_s, lmax]: (1/theta, 0), step 1 (c1, c2), residual pass (0, 0),
-//                 post-smoothing restart (0, 1/theta)
-//   d_coef[8..]:  coarse polynomial: (1/theta_c, 0), steps 1..kc-1
-static int pmg_coefficients(tlfea_newton_t s) {
-  auto& m = s->pmg;
-  const int Nc = m.Nc, nc = 3 * Nc;
-  const Incidence ic = m.inc();
-  const bool cold = !(m.lam_c > 0.0);
-  if (cold) {  // start vector: D^-1 applied to the restricted scaling vector (positive on every DOF)
-    HIP_TRY(hipMemcpyAsync(m.d_eigv_c, m.d_sc_c, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-  }
-  // multi-GPU: norms weigh replicated DOFs by 1/multiplicity and are summed over ranks, boundary rows of Hc v are
-  // summed like the fine level's -- every rank ends with the same estimate, hence the same polynomial
-  const int Ncr = s->halo.on ? s->halo.rows_c(0) : Nc, ncr = 3 * Ncr;  // overlapping partition: owned rows, layer-1 refresh
-  TRY(device_sumsq_async(s, m.d_eigv_c, dist_on(s) ? m.d_wc3 : nullptr, ncr));
-  launch_scale_inv_sqrt(s->stream, ncr, s->d_scal, m.d_eigv_c);
+// lambda_max(D^-1 H) of a coarse level by power iteration on its first `rows` rows, warm-started from the vector the level
+// keeps: 16 products from the scaling vector (positive on every DOF) when cold, 2 when warm.
+// iface given: the level follows the partition (vertex level).  Norms weigh replicated DOFs by w and are summed over ranks,
+//   ghost layer 1 of the vector is refreshed before and the boundary rows of H v are summed after every product: every
+//   rank ends with the same estimate.  iface null: the level is replicated (third level), no exchange of any kind.
+static int level_lam_max(tlfea_newton_t s, PolyLevel& L, int rows, const double* w, const LevelIface* iface,
+                         const char* name) {
+  const int n = 3 * rows;
+  const bool cold = !(L.lam > 0.0);
+  if (cold)
+    HIP_TRY(hipMemcpyAsync(L.d_eigv, L.d_sc, 3 * (size_t)L.N * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+  auto normalise = [&]() -> int {  // v <- v / ||v||, the norm stays on the device
+    if (iface)
+      TRY(device_sumsq_async(s, L.d_eigv, w, n));
+    else
+      launch_norm2(s->stream, L.d_eigv, nullptr, n, part(s, 5), s->d_scal);
+    launch_scale_inv_sqrt(s->stream, n, s->d_scal, L.d_eigv);
+    return 0;
+  };
+  TRY(normalise());
   for (int k = 0; k < (cold ? 16 : 2); k++) {
-    TRY(halo_refresh_f64(s, 1, 1, 3, m.d_eigv_c));
-    launch_spmv_dir_dot(s->stream, Ncr, ic, m.d_Hc, m.d_eigv_c, m.d_eigv_c, 1, part(s, 1), part(s, 0), m.d_p_c, m.d_q_c,
+    if (iface) TRY(halo_refresh_f64(s, 1, 1, 3, L.d_eigv));
+    launch_spmv_dir_dot(s->stream, rows, L.inc(), L.d_H, L.d_eigv, L.d_eigv, 1, part(s, 1), part(s, 0), L.d_p, L.d_q,
                         part(s, 2), false, false);
-    if (s->ar) TRY(iface_sum_lvl(s, m.n_ifc_loc, m.n_ifc_glob, m.d_ifc_node, m.d_ifc_slot, m.d_q_c, 3));
-    launch_apply_dinv(s->stream, Ncr, m.d_Dinv_c, m.d_q_c, m.d_eigv_c);
-    TRY(device_sumsq_async(s, m.d_eigv_c, dist_on(s) ? m.d_wc3 : nullptr, ncr));
-    launch_scale_inv_sqrt(s->stream, ncr, s->d_scal, m.d_eigv_c);
+    if (iface) TRY(iface_sum_lvl(s, *iface, L.d_q, 3));
+    launch_apply_dinv(s->stream, rows, L.d_Dinv, L.d_q, L.d_eigv);
+    TRY(normalise());
   }
   double ss = 0.0;
   TRY(fetch_scalar(s, s->d_scal, &ss));
-  if (!(ss > 0.0)) return fail("p-multigrid: coarse lambda_max estimate failed");
-  m.lam_c = std::sqrt(ss);
+  if (!(ss > 0.0)) return fail(std::string("p-multigrid: ") + name + " lambda_max estimate failed");
+  L.lam = std::sqrt(ss);
+  return 0;
+}
+
+// lambda_max of the coarse levels, then the cycle's coefficient table (pmg_coef.h) to the device
+static int pmg_coefficients(tlfea_newton_t s) {
+  auto& m = s->pmg;
+  const LevelIface ic = m.iface();
+  // overlapping partition: the vertex level's iteration lives on the owned rows
+  TRY(level_lam_max(s, m.vertex, s->halo.on ? s->halo.rows_c(0) : m.vertex.N, dist_on(s) ? m.d_wc3 : nullptr, &ic, "coarse"));
+  if (m.agg.ok) TRY(level_lam_max(s, m.agg.lvl, m.agg.lvl.N, nullptr, nullptr, "level-3"));
+  const PmgTable t = pmg_table(s);
+  const bool l3 = t.levels == 3;  // the vertex level smooths like the fine one, the polynomial solve moves to level 3
+  const PmgInterval fine{s->lam_safety * s->lam_max, pmg_kappa_s(s)};
+  const PmgInterval vertex{s->lam_safety * m.vertex.lam, l3 ? pmg_kappa_s2(s) : pmg_kappa_coarse(t.kc)};
+  const PmgInterval level3 = l3 ? PmgInterval{s->lam_safety * m.agg.lvl.lam, pmg_kappa_level3(t.k3)} : PmgInterval();
   double* h = s->h_pin + 8;
-  const int ks = pmg_ks(s);
-  {
-    const double b = s->lam_safety * s->lam_max, a = b / pmg_kappa_s(s);
-    const double theta = 0.5 * (b + a), delta = 0.5 * (b - a), sigma = theta / delta;
-    double rho = 1.0 / sigma;
-    h[0] = 1.0 / theta; h[1] = 0.0;
-    for (int k = 1; k < ks; k++) {
-      const double rho_new = 1.0 / (2.0 * sigma - rho);
-      h[2 * k] = rho_new * rho;
-      h[2 * k + 1] = 2.0 * rho_new / delta;
-      rho = rho_new;
-    }
-    h[2 * ks] = 0.0; h[2 * ks + 1] = 0.0;
-    h[2 * ks + 2] = 0.0; h[2 * ks + 3] = 1.0 / theta;
-    for (int k = 0; k < kPmgMaxKs; k++) h[2 * ks + 4 + k] = 1.0;
-    if (pmg_smoother_kind() != 1) {
-      // fourth kind: d0 = 4/(3 rho) D^-1 r ; d_k = (2k-1)/(2k+3) d_{k-1} + (8k+4)/((2k+3) rho) D^-1 r_k ; z_k = z_{k-1} + beta_k d_{k-1}
-      static const double kOpt[4][4] = {{1.12500000000000, 0, 0, 0},
-                                        {1.02387287570313, 1.26408905371085, 0, 0},
-                                        {1.00842544782028, 1.08867839208730, 1.33753125909618, 0},
-                                        {1.00391310427285, 1.04035811188593, 1.14863498546254, 1.38268869241000}};
-      const double rho_s = b;
-      for (int k = 0; k < ks; k++) h[2 * ks + 4 + k] = (pmg_smoother_kind() == 4 && ks <= 4) ? kOpt[ks - 1][k] : 1.0;
-      h[0] = 4.0 / (3.0 * rho_s);
-      h[1] = h[2 * ks + 4];                       // z^0 = beta_1 d0 (the init kernels read it: 0 would mean 1)
-      for (int k = 1; k < ks; k++) {
-        h[2 * k] = (2.0 * k - 1.0) / (2.0 * k + 3.0);
-        h[2 * k + 1] = (8.0 * k + 4.0) / ((2.0 * k + 3.0) * rho_s);
-      }
-      h[2 * ks + 3] = 4.0 / (3.0 * rho_s);        // post-smoothing restart: d0' = 4/(3 rho) D^-1 res
-    }
-  }
-  if (m.agg.ok) {
-    // three levels: the vertex level smooths like the fine one (d_coef[8..15], same four pairs), the polynomial
-    // solve moves to level 3 (d_coef[16..]); lambda_max(D3^-1 H3) by the same warm-started power iteration
-    auto& g = m.agg;
-    const int n3 = 3 * g.N3;
-    const Incidence i3 = g.inc();
-    const bool cold3 = !(g.lam3 > 0.0);
-    if (cold3) HIP_TRY(hipMemcpyAsync(g.d_eigv3, g.d_sc3, (size_t)n3 * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    launch_norm2(s->stream, g.d_eigv3, nullptr, n3, part(s, 5), s->d_scal);
-    launch_scale_inv_sqrt(s->stream, n3, s->d_scal, g.d_eigv3);
-    for (int k = 0; k < (cold3 ? 16 : 2); k++) {
-      launch_spmv_dir_dot(s->stream, g.N3, i3, g.d_H3, g.d_eigv3, g.d_eigv3, 1, part(s, 1), part(s, 0), g.d_p3, g.d_q3,
-                          part(s, 2), false, false);
-      launch_apply_dinv(s->stream, g.N3, g.d_Dinv3, g.d_q3, g.d_eigv3);
-      launch_norm2(s->stream, g.d_eigv3, nullptr, n3, part(s, 5), s->d_scal);
-      launch_scale_inv_sqrt(s->stream, n3, s->d_scal, g.d_eigv3);
-    }
-    double s3 = 0.0;
-    TRY(fetch_scalar(s, s->d_scal, &s3));
-    if (!(s3 > 0.0)) return fail("p-multigrid: level-3 lambda_max estimate failed");
-    g.lam3 = std::sqrt(s3);
-    const int ks2 = pmg_ks2(s), o2 = pmg_cf_coarse(s), o3 = pmg_cf_level3(s);
-    {
-      const double b = s->lam_safety * m.lam_c, a = b / pmg_kappa_s2(s);
-      const double theta = 0.5 * (b + a), delta = 0.5 * (b - a), sigma = theta / delta;
-      double rho = 1.0 / sigma;
-      h[o2] = 1.0 / theta; h[o2 + 1] = 0.0;
-      for (int k = 1; k < ks2; k++) {
-        const double rho_new = 1.0 / (2.0 * sigma - rho);
-        h[o2 + 2 * k] = rho_new * rho;
-        h[o2 + 2 * k + 1] = 2.0 * rho_new / delta;
-        rho = rho_new;
-      }
-      h[o2 + 2 * ks2] = 0.0; h[o2 + 2 * ks2 + 1] = 0.0;
-      h[o2 + 2 * ks2 + 2] = 0.0; h[o2 + 2 * ks2 + 3] = 1.0 / theta;
-    }
-    const int k3 = pmg_level3_degree(g.N3);
-    const double b = s->lam_safety * g.lam3, a = b / pmg_kappa_level3(k3);
-    const double theta = 0.5 * (b + a), delta = 0.5 * (b - a), sigma = theta / delta;
-    double rho = 1.0 / sigma;
-    h[o3] = 1.0 / theta; h[o3 + 1] = 0.0;
-    for (int k = 1; k < k3; k++) {
-      const double rho_new = 1.0 / (2.0 * sigma - rho);
-      h[o3 + 2 * k] = rho_new * rho;
-      h[o3 + 2 * k + 1] = 2.0 * rho_new / delta;
-      rho = rho_new;
-    }
-    HIP_TRY(hipMemcpyAsync(m.d_coef, h, (size_t)(o3 + 2 * k3) * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    return 0;
-  }
-  const int kc = pmg_coarse_degree_eff(s), oc = pmg_cf_coarse(s);
-  {
-    const double b = s->lam_safety * m.lam_c, a = b / pmg_kappa_coarse(kc);
-    const double theta = 0.5 * (b + a), delta = 0.5 * (b - a), sigma = theta / delta;
-    double rho = 1.0 / sigma;
-    h[oc] = 1.0 / theta; h[oc + 1] = 0.0;
-    for (int k = 1; k < kc; k++) {
-      const double rho_new = 1.0 / (2.0 * sigma - rho);
-      h[oc + 2 * k] = rho_new * rho;
-      h[oc + 2 * k + 1] = 2.0 * rho_new / delta;
-      rho = rho_new;
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(m.d_coef, h, (size_t)(oc + 2 * kc) * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  pmg_table_fill(t, pmg_smoother_kind(), fine, vertex, level3, h);
+  HIP_TRY(hipMemcpyAsync(m.d_coef, h, (size_t)t.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  return 0;
+}
+
+// One step of a partitioned level's polynomial (tlfea_newton_set_interface): this rank's partial boundary rows of Hs d ->
+// all-reduce -> the fused step reads the sums.  One collective per step.  w: weights of the r.z partials (last step).
+static int c32_step_iface(tlfea_newton_t s, const C32Level& L, const LevelIface& I, C32Vecs& v, int rows, const double* coef,
+                          const double* d_r, double* d_z, double* rz_part, bool last, const double* w) {
+  const int nb = 3 * I.n_glob;
+  if (nb) HIP_TRY(hipMemsetAsync(s->d_ibuf, 0, (size_t)nb * sizeof(double), s->stream));
+  launch_spmv32_rows(s->stream, I.n_loc, I.d_node, I.d_slot, L.inc, L.B8, L.B1, L.bits, v.d, s->d_ibuf);
+  if (nb) TRY(call_allreduce(s, s->d_ibuf, nb));
+  c32_step(s, L, v, rows, coef, d_r, d_z, rz_part, last, C32Bnd{I.d_bslot, s->d_ibuf, w});
   return 0;
 }
 
@@ -4631,75 +4585,40 @@ static int pmg_coefficients(tlfea_newton_t s) {
 // kernel already wrote the fine start vectors.
 static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* rz_part, bool init_done) {
   auto& m = s->pmg;
-  tlfea_t10_t d = s->d;
-  const int N = s->N, Nc = m.Nc, bits = cheb_bits_eff(s);
-  const size_t n = 3 * (size_t)N, nc = 3 * (size_t)Nc;
-  float *f_d = s->d_f32, *f_d2 = f_d + n, *f_z = f_d2 + n, *f_z2 = f_z + n, *f_r = f_z2 + n, *f_r2 = f_r + n;
-  const float* Dinv_f = f_r2 + n;
-  float *c_d = m.d_f32c, *c_d2 = c_d + nc, *c_z = c_d2 + nc, *c_z2 = c_z + nc, *c_r = c_z2 + nc, *c_r2 = c_r + nc;
-  const float* Dinv_fc = c_r2 + nc;
+  const PolyLevel& V = m.vertex;
+  const int N = s->N, Nc = V.N, bits = cheb_bits_eff(s);
+  const PmgTable t = pmg_table(s);
+  const int ks = t.ks;
   const double* cf = m.d_coef;
-  const Incidence inc_f = d->inc(), inc_c = m.inc();
+  const double* cc = cf + t.coarse();  // the vertex level's pairs
+  const C32Level Lf = fine_c32(s), Lc = V.c32(bits, 1);
+  C32Vecs f(s->d_f32, 3 * (size_t)N), c(V.d_f32, 3 * (size_t)Nc);
   if (s->ar) {
     // Multi-GPU V-cycle: the same sequence, every polynomial step on either level preceded by the exchange of the
-    // partition-boundary rows of Hs d (this rank's partial rows -> all-reduce -> the fused step reads the sums), the
-    // restriction by the exchange of the boundary vertices' restricted residuals.  One collective per step: 4 on the
-    // fine level, kc - 1 on the coarse level, 1 for the restriction.
+    // partition-boundary rows of Hs d, the restriction by the exchange of the boundary vertices' restricted residuals.
+    // One collective per step: 2 ks on the fine level, kc - 1 on the coarse level, 1 for the restriction.
     if (m.agg.ok) return fail("p-multigrid: the third level is single-GPU only");
-    auto fine_step = [&](const float* din, const double* co, float* dout, const float* zin, float* zout, const float* rin,
-                         float* rout, bool last) -> int {
-      const int nb = 3 * s->n_if_glob;
-      if (nb) HIP_TRY(hipMemsetAsync(s->d_ibuf, 0, (size_t)nb * sizeof(double), s->stream));
-      launch_spmv32_rows(s->stream, s->n_if_loc, s->d_if_node, s->d_if_slot, inc_f, s->d_B8, s->d_B1, bits, din, s->d_ibuf);
-      if (nb) TRY(call_allreduce(s, s->d_ibuf, nb));
-      launch_cheb32(s->stream, N, d->nnz_coef, inc_f, s->d_B8, s->d_B1, bits, Dinv_f, s->d_sc, din, co, dout, zin, zout, rin,
-                    rout, d_r, d_z, rz_part, last, C32Bnd{s->d_bslot_f, s->d_ibuf, s->d_w}, s->geo_out(0, last));
-      return 0;
+    const LevelIface If = s->iface(), Ic = m.iface();
+    auto fine = [&](const double* co, bool last) {
+      return c32_step_iface(s, Lf, If, f, N, co, d_r, d_z, rz_part, last, s->d_w);
     };
-    auto coarse_step = [&](const float* din, const double* co, float* dout, const float* zin, float* zout,
-                           const float* rin, float* rout) -> int {
-      const int nb = 3 * m.n_ifc_glob;
-      if (nb) HIP_TRY(hipMemsetAsync(s->d_ibuf, 0, (size_t)nb * sizeof(double), s->stream));
-      launch_spmv32_rows(s->stream, m.n_ifc_loc, m.d_ifc_node, m.d_ifc_slot, inc_c, m.d_B8c, m.d_B1c, bits, din, s->d_ibuf);
-      if (nb) TRY(call_allreduce(s, s->d_ibuf, nb));
-      launch_cheb32(s->stream, Nc, m.nnz_c, inc_c, m.d_B8c, m.d_B1c, bits, Dinv_fc, m.d_sc_c, din, co, dout, zin, zout, rin,
-                    rout, d_r, d_z, rz_part, false, C32Bnd{m.d_bslot_c, s->d_ibuf, nullptr}, s->geo_out(1, false));
-      return 0;
-    };
-    const int ks = pmg_ks(s), o_res = pmg_cf_resid(s), o_rst = pmg_cf_restart(s), o_c = pmg_cf_coarse(s);
-    auto fine = [&](const double* co, bool last) -> int {  // one fine pass; the ping-pong partners swap roles
-      TRY(fine_step(f_d, co, f_d2, f_z, f_z2, f_r, f_r2, last));
-      std::swap(f_d, f_d2);
-      std::swap(f_z, f_z2);
-      std::swap(f_r, f_r2);
-      return 0;
-    };
-    launch_cheb32_init(s->stream, N, Dinv_f, d_r, s->d_sc, cf, f_d, f_z, f_r);
+    launch_cheb32_init(s->stream, N, f.Dinv_f, d_r, s->d_sc, cf, f.d, f.z, f.r);
     for (int k = 1; k < ks; k++) TRY(fine(cf + 2 * k, false));
-    TRY(fine(cf + o_res, false));
-    {
-      const int nb = 3 * m.n_ifc_glob;
-      if (nb) HIP_TRY(hipMemsetAsync(s->d_ibuf, 0, (size_t)nb * sizeof(double), s->stream));
-      launch_pmg_restrict_rows(s->stream, m.n_ifc_loc, m.d_ifc_node, m.d_ifc_slot, m.d_child_off, m.d_child,
-                               m.d_child_w_dist, f_r, s->d_sc, s->d_ibuf);
-      if (nb) TRY(call_allreduce(s, s->d_ibuf, nb));
-      launch_pmg_restrict_init(s->stream, Nc, m.d_child_off, m.d_child, m.d_child_w, f_r, s->d_sc, m.d_sc_c, Dinv_fc, cf + o_c,
-                               c_d, c_z, c_r, m.d_bslot_c, s->d_ibuf);
-    }
-    const int kc = pmg_coarse_degree_eff(s);
-    for (int k = 1; k < kc; k++) {
-      TRY(coarse_step(c_d, cf + o_c + 2 * k, c_d2, c_z, c_z2, c_r, c_r2));
-      std::swap(c_d, c_d2);
-      std::swap(c_z, c_z2);
-      std::swap(c_r, c_r2);
-    }
-    launch_pmg_prolong(s->stream, N, m.d_par0, m.d_par1, c_z, m.d_sc_c, s->d_sc, f_z, f_d);
-    TRY(fine(cf + o_rst, ks == 1));
+    TRY(fine(cf + t.resid(), false));
+    const int nb = 3 * Ic.n_glob;
+    if (nb) HIP_TRY(hipMemsetAsync(s->d_ibuf, 0, (size_t)nb * sizeof(double), s->stream));
+    launch_pmg_restrict_rows(s->stream, Ic.n_loc, Ic.d_node, Ic.d_slot, m.d_child_off, m.d_child, m.d_child_w_dist, f.r,
+                             s->d_sc, s->d_ibuf);
+    if (nb) TRY(call_allreduce(s, s->d_ibuf, nb));
+    launch_pmg_restrict_init(s->stream, Nc, m.d_child_off, m.d_child, m.d_child_w, f.r, s->d_sc, V.d_sc, c.Dinv_f, cc, c.d, c.z,
+                             c.r, Ic.d_bslot, s->d_ibuf);
+    for (int k = 1; k < t.kc; k++) TRY(c32_step_iface(s, Lc, Ic, c, Nc, cc + 2 * k, d_r, d_z, rz_part, false, nullptr));
+    launch_pmg_prolong(s->stream, N, m.d_par0, m.d_par1, c.z, V.d_sc, s->d_sc, f.z, f.d);
+    TRY(fine(cf + t.restart(), ks == 1));
     for (int k = 1; k < ks; k++) TRY(fine(cf + 2 * k, k == ks - 1));
     return 0;
   }
   // pre-smooth: d0 = (SDS)^-1 r^/theta ; ks - 1 Chebyshev steps ; residual of the result (coefficients (0,0): res -= Hs d)
-  const int ks = pmg_ks(s), o_res = pmg_cf_resid(s), o_rst = pmg_cf_restart(s), o_c = pmg_cf_coarse(s);
   // Overlapping partition: r comes in exact on layers <= halo_dr(); every fine pass gives up one layer (the restriction
   // needs layer 1 after the ks pre-smoothing passes, the post-smoother's pointwise operands layer ks - 1), so the fine
   // launches stop at that row count -- deeper ghosts are never computed, they would only accumulate garbage -- and the
@@ -4707,118 +4626,85 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
   const bool hal = s->halo.on;
   const int Nf = hal ? s->halo.rows(halo_dr(s)) : N;
   const bool weighted = pmg_smoother_kind() != 1;  // fourth-kind smoother: z^ += beta_k d
-  const double* betas = cf + pmg_cf_beta(s);
-  auto fine = [&](const double* co, bool last, const double* zw) {  // one fine pass; the ping-pong partners swap roles
-    C32Bnd bnd = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
+  const double* betas = cf + t.beta();
+  const C32Bnd bnd_f = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
+  auto fine = [&](const double* co, bool last, const double* zw) {  // one fine pass
+    C32Bnd bnd = bnd_f;
     bnd.zw = weighted ? zw : nullptr;
-    launch_cheb32(s->stream, Nf, d->nnz_coef, inc_f, s->d_B8, s->d_B1, fine_bits(s), Dinv_f, s->d_sc, f_d, co, f_d2, f_z, f_z2, f_r,
-                  f_r2, d_r, d_z, rz_part, last, bnd, s->geo_out(0, last));
-    std::swap(f_d, f_d2);
-    std::swap(f_z, f_z2);
-    std::swap(f_r, f_r2);
+    c32_step(s, Lf, f, Nf, co, d_r, d_z, rz_part, last, bnd);
   };
-  if (!init_done) launch_cheb32_init(s->stream, Nf, Dinv_f, d_r, s->d_sc, cf, f_d, f_z, f_r);
+  if (!init_done) launch_cheb32_init(s->stream, Nf, f.Dinv_f, d_r, s->d_sc, cf, f.d, f.z, f.r);
   for (int k = 1; k < ks; k++) fine(cf + 2 * k, false, betas + k);
-  // Restriction through the stored operator (pmg_rop_on): the residual pass is dropped.  f_r is res_A = r^ - Hs (z^ - d_last)
-  // and f_d the last direction; the residual is linear in the direction, so the coarse right-hand side is
+  // Restriction through the stored operator (pmg_rop_on): the residual pass is dropped.  f.r is res_A = r^ - Hs (z^ - d_last)
+  // and f.d the last direction; the residual is linear in the direction, so the coarse right-hand side is
   // S_c P^T S_f^-1 res_A - R d_last, the prolongation writes d := d_last + corr, and the restart pass below forms
   // res_A - Hs (d_last + corr) -- what the residual pass and the restart pass formed together.
   const bool rop = pmg_rop_now(s);
   if (rop) {
-    launch_pmg_restrict_op_init(s->stream, Nc, m.rop.nnz, m.d_child_off, m.d_child, m.d_child_w, f_r, f_d, s->d_sc, m.d_sc_c,
-                                m.rop.d_off, m.rop.d_cols, m.rop.d_R8, m.rop.d_R1, Dinv_fc, cf + o_c, c_d, c_z, c_r);
+    launch_pmg_restrict_op_init(s->stream, Nc, m.rop.nnz, m.d_child_off, m.d_child, m.d_child_w, f.r, f.d, s->d_sc, V.d_sc,
+                                m.rop.d_off, m.rop.d_cols, m.rop.d_R8, m.rop.d_R1, c.Dinv_f, cc, c.d, c.z, c.r);
   } else if (weighted) {
     // Weighted z^ updates: the residual the recurrence carries is the UNWEIGHTED iterate's, not that of z^ -- restricting it
     // made the cycle unsymmetric (defect 3e-4 on res2; tests/test_gpu_precond_operator.py, configuration 11).  Form
     // res^ = S r - Hs z^ itself: start vectors into the spare buffers (res^ := S r), then one pass with z^ as the direction
-    // and the pair (0, 0), which leaves z^ as it is.
-    launch_cheb32_init(s->stream, Nf, Dinv_f, d_r, s->d_sc, cf, f_d2, f_z2, f_r2);
-    C32Bnd bnd = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
-    launch_cheb32(s->stream, Nf, d->nnz_coef, inc_f, s->d_B8, s->d_B1, fine_bits(s), Dinv_f, s->d_sc, f_z, cf + o_res, f_d2, f_z, f_z2,
-                  f_r2, f_r, d_r, d_z, rz_part, false, bnd, s->geo_out(0, false));
-    std::swap(f_z, f_z2);
+    // and the pair (0, 0), which leaves z^ as it is.  Not a c32_step: it reads z^ as the direction, writes into the spare
+    // buffers and swaps z^ only.
+    launch_cheb32_init(s->stream, Nf, f.Dinv_f, d_r, s->d_sc, cf, f.d2, f.z2, f.r2);
+    launch_cheb32(s->stream, Nf, Lf.nnz, Lf.inc, Lf.B8, Lf.B1, Lf.bits, f.Dinv_f, Lf.sc, f.z, cf + t.resid(), f.d2, f.z, f.z2,
+                  f.r2, f.r, d_r, d_z, rz_part, false, bnd_f, s->geo_out(0, false));
+    std::swap(f.z, f.z2);
   } else
-    fine(cf + o_res, false, nullptr);
+    fine(cf + t.resid(), false, nullptr);
   // coarse correction
   if (!rop)
-    launch_pmg_restrict_init(s->stream, Nc, m.d_child_off, m.d_child, m.d_child_w, f_r, s->d_sc, m.d_sc_c, Dinv_fc, cf + o_c,
-                             c_d, c_z, c_r);
+    launch_pmg_restrict_init(s->stream, Nc, m.d_child_off, m.d_child, m.d_child_w, f.r, s->d_sc, V.d_sc, c.Dinv_f, cc, c.d, c.z,
+                             c.r);
+  // Overlapping partition: the restricted residual is exact on the owned vertices only.  A refresh makes the three
+  // vectors exact on every ghost layer (G of them).  Rows of Hc are exact up to layer G - 2 (a vertex of layer G - 1 has
+  // mid-edge children in the outermost fine layer, whose rows of H are incomplete), so the first step after a refresh
+  // leaves layers <= G - 2 exact and every further step gives up one more; the prolongation needs ks + 1 layers at the
+  // end (ks fine passes follow).  One exchange buys up to G - 1 steps, computed redundantly on the overlap.
+  const int G = s->halo.depth, need_end = ks + 1;
+  int valid = 0;
+  auto mid = [&](const double* co) -> int {  // one vertex-level pass
+    if (hal && valid < 1) {
+      TRY(halo_refresh_f32(s, 1, G, 3, c.d, c.z, c.r));
+      valid = G - 1;
+    }
+    c32_step(s, Lc, c, Nc, co, d_r, d_z, rz_part, false);
+    valid--;
+    return 0;
+  };
   if (m.agg.ok) {
-    // vertex level as a smoothing level: the fine level's sequence once more, with the level-3 polynomial inside
+    // vertex level as a smoothing level: the fine level's sequence once more, with the level-3 polynomial inside.
+    // Overlapping partition: the third level is REPLICATED -- its residual is summed over the ranks' owned members (one
+    // small all-reduce), its polynomial runs redundantly with no exchange, and its correction is exact on every vertex a
+    // rank holds (so it does not touch the validity count).
     auto& g = m.agg;
-    const size_t n3 = 3 * (size_t)g.N3;
-    float *a_d = g.d_f32, *a_d2 = a_d + n3, *a_z = a_d2 + n3, *a_z2 = a_z + n3, *a_r = a_z2 + n3, *a_r2 = a_r + n3;
-    const float* Dinv_f3 = a_r2 + n3;
-    const Incidence inc_3 = g.inc();
-    const int ks2 = pmg_ks2(s), o3 = pmg_cf_level3(s);
-    // Overlapping partition: as in the two-level branch below -- a refresh makes the vertex-level vectors exact on every
-    // ghost layer, a product gives up one (the first after a refresh two) -- with the third level REPLICATED: its residual
-    // is summed over the ranks' owned members (one small all-reduce), its polynomial runs redundantly with no exchange,
-    // and its correction is exact on every vertex a rank holds (so it does not touch the validity count).
-    const int G = s->halo.depth;
-    int valid = 0;
-    auto mid = [&](const double* co) -> int {  // one vertex-level pass; the ping-pong partners swap roles
-      if (hal && valid < 1) {
-        TRY(halo_refresh_f32(s, 1, G, 3, c_d, c_z, c_r));
-        valid = G - 1;
-      }
-      launch_cheb32(s->stream, Nc, m.nnz_c, inc_c, m.d_B8c, m.d_B1c, bits, Dinv_fc, m.d_sc_c, c_d, co, c_d2, c_z, c_z2, c_r, c_r2,
-                    d_r, d_z, rz_part, false, C32Bnd(), s->geo_out(1, false));
-      valid--;
-      std::swap(c_d, c_d2);
-      std::swap(c_z, c_z2);
-      std::swap(c_r, c_r2);
-      return 0;
-    };
-    for (int k = 1; k < ks2; k++) TRY(mid(cf + o_c + 2 * k));   // Chebyshev steps of the pre-smoother
-    TRY(mid(cf + o_c + 2 * ks2));                               // (0,0): residual of the result
+    const PolyLevel& A = g.lvl;
+    const C32Level L3 = A.c32(bits, 2);
+    C32Vecs a(A.d_f32, 3 * (size_t)A.N);
+    const double* c3 = cf + t.level3();
+    for (int k = 1; k < t.ks2; k++) TRY(mid(cc + 2 * k));  // Chebyshev steps of the pre-smoother
+    TRY(mid(cf + t.coarse_resid()));                       // (0,0): residual of the result
     if (hal) {
-      launch_agg_restrict(s->stream, g.N3, g.d_mem_off, g.d_mem, g.d_rvec, c_r, m.d_sc_c, g.d_r3);
-      TRY(call_allreduce(s, g.d_r3, 3 * g.N3));
-      launch_agg_init3(s->stream, g.N3, g.d_r3, g.d_sc3, Dinv_f3, cf + o3, a_d, a_z, a_r);
+      launch_agg_restrict(s->stream, A.N, g.d_mem_off, g.d_mem, g.d_rvec, c.r, V.d_sc, g.d_r3);
+      TRY(call_allreduce(s, g.d_r3, 3 * A.N));
+      launch_agg_init3(s->stream, A.N, g.d_r3, A.d_sc, a.Dinv_f, c3, a.d, a.z, a.r);
     } else
-    launch_agg_restrict_init(s->stream, g.N3, g.d_mem_off, g.d_mem, g.d_rvec, c_r, m.d_sc_c, g.d_sc3, Dinv_f3, cf + o3, a_d, a_z,
-                             a_r);
-    const int k3 = pmg_level3_degree(g.N3);
-    for (int k = 1; k < k3; k++) {
-      launch_cheb32(s->stream, g.N3, g.nnz3, inc_3, g.d_B8, g.d_B1, bits, Dinv_f3, g.d_sc3, a_d, cf + o3 + 2 * k, a_d2, a_z,
-                    a_z2, a_r, a_r2, d_r, d_z, rz_part, false, C32Bnd(), s->geo_out(2, false));
-      std::swap(a_d, a_d2);
-      std::swap(a_z, a_z2);
-      std::swap(a_r, a_r2);
-    }
-    launch_agg_prolong(s->stream, Nc, g.d_agg, g.d_rvec, a_z, g.d_sc3, m.d_sc_c, c_z, c_d);  // z^ += corr ; d := corr
-    TRY(mid(cf + o_c + 2 * ks2 + 2));                           // (0, 1/theta): res^ -= Hs corr, restart
-    for (int k = 1; k < ks2; k++) TRY(mid(cf + o_c + 2 * k));   // the remaining terms; the vertex-level result is in c_z
-    if (hal && valid < ks + 1) TRY(halo_refresh_f32(s, 1, ks + 1, 3, c_z));  // the prolongation needs ks + 1 layers
-  } else {
-    const int kc = pmg_coarse_degree_eff(s);
-    // Overlapping partition: the restricted residual is exact on the owned vertices only.  A refresh makes the three
-    // vectors exact on every ghost layer (G of them).  Rows of Hc are exact up to layer G - 2 (a vertex of layer G - 1 has
-    // mid-edge children in the outermost fine layer, whose rows of H are incomplete), so the first step after a refresh
-    // leaves layers <= G - 2 exact and every further step gives up one more; the prolongation needs ks + 1 layers at the
-    // end (ks fine passes follow).  One exchange buys up to G - 1 steps, computed redundantly on the overlap.
-    const int G = s->halo.depth, need_end = ks + 1;
-    int valid = 0;
-    for (int k = 1; k < kc; k++) {
-      if (hal && valid < 1) {
-        TRY(halo_refresh_f32(s, 1, G, 3, c_d, c_z, c_r));
-        valid = G - 1;
-      }
-      launch_cheb32(s->stream, Nc, m.nnz_c, inc_c, m.d_B8c, m.d_B1c, bits, Dinv_fc, m.d_sc_c, c_d, cf + o_c + 2 * k, c_d2, c_z,
-                    c_z2, c_r, c_r2, d_r, d_z, rz_part, false, C32Bnd(), s->geo_out(1, false));
-      valid--;
-      std::swap(c_d, c_d2);
-      std::swap(c_z, c_z2);
-      std::swap(c_r, c_r2);
-    }
-    if (hal && valid < need_end) TRY(halo_refresh_f32(s, 1, need_end, 3, c_z));  // the last chunk ended too shallow
-  }
+      launch_agg_restrict_init(s->stream, A.N, g.d_mem_off, g.d_mem, g.d_rvec, c.r, V.d_sc, A.d_sc, a.Dinv_f, c3, a.d, a.z, a.r);
+    for (int k = 1; k < t.k3; k++) c32_step(s, L3, a, A.N, c3 + 2 * k, d_r, d_z, rz_part, false);
+    launch_agg_prolong(s->stream, Nc, g.d_agg, g.d_rvec, a.z, A.d_sc, V.d_sc, c.z, c.d);  // z^ += corr ; d := corr
+    TRY(mid(cf + t.coarse_restart()));                     // (0, 1/theta): res^ -= Hs corr, restart
+    for (int k = 1; k < t.ks2; k++) TRY(mid(cc + 2 * k));  // the remaining terms; the vertex-level result is in c.z
+  } else
+    for (int k = 1; k < t.kc; k++) TRY(mid(cc + 2 * k));
+  if (hal && valid < need_end) TRY(halo_refresh_f32(s, 1, need_end, 3, c.z));  // the last chunk ended too shallow
   // z^ += corr ; d := corr (restricted operator: d := d_last + corr)
-  launch_pmg_prolong(s->stream, Nf, m.d_par0, m.d_par1, c_z, m.d_sc_c, s->d_sc, f_z, f_d, rop);
+  launch_pmg_prolong(s->stream, Nf, m.d_par0, m.d_par1, c.z, V.d_sc, s->d_sc, f.z, f.d, rop);
   // post-smooth: res^ -= Hs corr ; d0' = (SDS)^-1 res^/theta ; z^ += d0'   == one step with coefficients (0, 1/theta),
   // then the ks - 1 Chebyshev steps that complete the polynomial; the last pass returns z = S z^ (fp64) and the r.z slots
-  fine(cf + o_rst, ks == 1, betas);
+  fine(cf + t.restart(), ks == 1, betas);
   for (int k = 1; k < ks; k++) fine(cf + 2 * k, k == ks - 1, betas + k);
   return 0;
 }
@@ -4986,7 +4872,7 @@ static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg,
                        bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0) +
                            (pmg_rop_now(s) ? 400000L : 0),
                        (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
-                       (long)(size_t)s->d_B8, (long)(size_t)s->pmg.d_B8c};
+                       (long)(size_t)s->d_B8, (long)(size_t)s->pmg.vertex.d_B8};
   if (s->cg_graph[0] && std::equal(key, key + 6, s->cg_graph_key)) return 0;
   cg_graphs_destroy(s);
   for (int k = 0; k < (s->spmv32_now ? 3 : 2); k++) {
@@ -5542,23 +5428,22 @@ extern "C" int tlfea_newton_pmg_sizes(tlfea_newton_t s, int* n_coarse, int* nnz_
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
   TRY(pmg_prepare(s));
   if (!s->pmg.ok) return fail("p-multigrid is not available for this mesh");
-  *n_coarse = s->pmg.Nc;
-  *nnz_coarse_blocks = s->pmg.nnz_c;
+  *n_coarse = s->pmg.vertex.N;
+  *nnz_coarse_blocks = s->pmg.vertex.nnz;
   return 0;
 }
 extern "C" int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int* par0, int* par1, int* c_off, int* c_cols, double* Hc) {
   int nc = 0, nnz = 0;
   TRY(tlfea_newton_pmg_sizes(s, &nc, &nnz));
   auto& m = s->pmg;
-  launch_pmg_galerkin(s->stream, m.nnz_c, m.d_c_off, m.d_cblk_row, m.d_con_off, m.d_con_base, m.d_con_deg, m.d_con_w,
-                      s->d_H, m.d_Hc);
+  vertex_galerkin(s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s->stream));
   D2H(par0, m.d_par0, (size_t)s->N);
   D2H(par1, m.d_par1, (size_t)s->N);
-  D2H(c_off, m.d_c_off, (size_t)nc + 1);
-  D2H(c_cols, m.d_c_cols, (size_t)nnz);
-  D2H(Hc, m.d_Hc, (size_t)9 * nnz);
+  D2H(c_off, m.vertex.d_off, (size_t)nc + 1);
+  D2H(c_cols, m.vertex.d_cols, (size_t)nnz);
+  D2H(Hc, m.vertex.d_H, (size_t)9 * nnz);
   return 0;
 }
 
@@ -5589,7 +5474,7 @@ extern "C" int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int* out6) {
   const auto& m = s->pmg;
   const bool have = m.ok && m.rop.ok && m.rop.built;
   out6[0] = have ? 1 : 0;
-  out6[1] = m.ok ? m.Nc : 0;
+  out6[1] = m.ok ? m.vertex.N : 0;
   out6[2] = have ? m.rop.nnz : 0;
   out6[3] = have ? m.rop.n_con : 0;
   out6[4] = s->d->nnz_coef;
@@ -5613,7 +5498,7 @@ extern "C" int tlfea_newton_pmg_restrict_op_retrieve(tlfea_newton_t s, int* off,
   if (!(m.ok && m.rop.ok && m.rop.built))
     return fail("tlfea_newton_pmg_restrict_op_retrieve: the last preconditioner set-up built no restricted operator");
   HIP_TRY(hipStreamSynchronize(s->stream));
-  D2H(off, m.rop.d_off, (size_t)m.Nc + 1);
+  D2H(off, m.rop.d_off, (size_t)m.vertex.N + 1);
   D2H(cols, m.rop.d_cols, (size_t)m.rop.nnz);
   return widen_to_host(s, (size_t)m.rop.nnz, m.rop.d_R8, m.rop.d_R1, 32, vals);
 }
@@ -5622,14 +5507,14 @@ extern "C" int tlfea_newton_pmg_fine_copy_retrieve(tlfea_newton_t s, int* off, i
   if (!s || !off || !cols || !vals || !sc_f || !sc_c) return fail("tlfea_newton_pmg_fine_copy_retrieve: null argument");
   const auto& m = s->pmg;
   const int bits = s->d_B8 ? s->lp_bits_alloc : 0;
-  if (!m.ok || !m.d_sc_c || !s->d_sc || (bits != 16 && bits != 32))
+  if (!m.ok || !m.vertex.d_sc || !s->d_sc || (bits != 16 && bits != 32))
     return fail("tlfea_newton_pmg_fine_copy_retrieve: no p-multigrid set-up with a 16- or 32-bit fine copy on the device");
   tlfea_t10_t d = s->d;
   HIP_TRY(hipStreamSynchronize(s->stream));
   std::copy(d->h_off.begin(), d->h_off.begin() + d->N + 1, off);
   std::copy(d->h_cols.begin(), d->h_cols.begin() + d->nnz_coef, cols);
   D2H(sc_f, s->d_sc, 3 * (size_t)s->N);
-  D2H(sc_c, m.d_sc_c, 3 * (size_t)m.Nc);
+  D2H(sc_c, m.vertex.d_sc, 3 * (size_t)m.vertex.N);
   return widen_to_host(s, (size_t)d->nnz_coef, s->d_B8, s->d_B1, bits, vals);
 }
 
@@ -5640,29 +5525,26 @@ extern "C" int tlfea_newton_pmg3_sizes(tlfea_newton_t s, int* n_aggregates, int*
   TRY(tlfea_newton_pmg_sizes(s, &nc, &nnz));
   const auto& g = s->pmg.agg;
   if (n_aggregates) *n_aggregates = g.ok ? g.Na : 0;
-  if (nnz_blocks) *nnz_blocks = g.ok ? g.nnz3 : 0;
-  if (degree) *degree = g.ok ? pmg_level3_degree(g.N3) : 0;
+  if (nnz_blocks) *nnz_blocks = g.ok ? g.lvl.nnz : 0;
+  if (degree) *degree = g.ok ? pmg_level3_degree(g.lvl.N) : 0;
   return 0;
 }
 extern "C" int tlfea_newton_pmg3_retrieve(tlfea_newton_t s, int* agg, double* rvec, int* active, int* off3, int* cols3,
                                           double* H3) {
   int nc = 0, nnz = 0;
   TRY(tlfea_newton_pmg_sizes(s, &nc, &nnz));
-  auto& m = s->pmg;
-  auto& g = m.agg;
+  auto& g = s->pmg.agg;
   if (!g.ok) return fail("p-multigrid: no third level on this mesh");
-  launch_pmg_galerkin(s->stream, m.nnz_c, m.d_c_off, m.d_cblk_row, m.d_con_off, m.d_con_base, m.d_con_deg, m.d_con_w,
-                      s->d_H, m.d_Hc);
-  launch_agg_galerkin(s->stream, g.n_pairs, g.d_pair_A, g.d_pair_pos, g.d_pair_B, g.d_pcon_off, g.d_pcon_base, g.d_pcon_deg,
-                      g.d_pcon_i, g.d_pcon_j, g.d_rvec, g.d_active, g.d_off3, m.d_Hc, g.d_H3);
+  vertex_galerkin(s);
+  level3_galerkin(s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s->stream));
   D2H(agg, g.d_agg, (size_t)nc);
   D2H(rvec, g.d_rvec, (size_t)3 * nc);
   D2H(active, g.d_active, (size_t)g.Na);
-  D2H(off3, g.d_off3, (size_t)g.N3 + 1);
-  D2H(cols3, g.d_cols3, (size_t)g.nnz3);
-  D2H(H3, g.d_H3, (size_t)9 * g.nnz3);
+  D2H(off3, g.lvl.d_off, (size_t)g.lvl.N + 1);
+  D2H(cols3, g.lvl.d_cols, (size_t)g.lvl.nnz);
+  D2H(H3, g.lvl.d_H, (size_t)9 * g.lvl.nnz);
   return 0;
 }
 
@@ -5672,13 +5554,13 @@ extern "C" int tlfea_newton_pmg_cycle_info(tlfea_newton_t s, int* out6) {
   if (!s || !out6) return fail("null argument");
   for (int k = 0; k < 6; k++) out6[k] = 0;
   if (precond_eff(s) != 2 || !s->pmg.ok) return 0;
-  const bool l3 = s->pmg.agg.ok;
-  out6[0] = l3 ? 3 : 2;
-  out6[1] = pmg_ks(s);
-  out6[2] = l3 ? pmg_ks2(s) : 0;
-  out6[3] = l3 ? 0 : pmg_coarse_degree_eff(s);
-  out6[4] = l3 ? pmg_level3_degree(s->pmg.agg.N3) : 0;
-  out6[5] = l3 ? s->pmg.agg.N3 : 0;
+  const PmgTable t = pmg_table(s);
+  out6[0] = t.levels;
+  out6[1] = t.ks;
+  out6[2] = t.ks2;
+  out6[3] = t.kc;
+  out6[4] = t.k3;
+  out6[5] = t.levels == 3 ? s->pmg.agg.lvl.N : 0;
   return 0;
 }
 extern "C" int tlfea_newton_polynomial_info(tlfea_newton_t s, int* out3) {
@@ -5739,8 +5621,13 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
   const int N = s->N;
   const bool fused = s->pcg_fused < 0 ? (N <= 200000) : (s->pcg_fused != 0);
   out_ms4[5] = out_ms4[6] = 0.0;
+  // geo -1: a measurement is no solve, the geometry read-back keeps the solver's last launch
+  C32Level Lf = fine_c32(s);
+  Lf.geo = -1;
+  const PolyLevel& V = s->pmg.vertex;
+  const C32Level Lc = V.c32(cheb_bits_eff(s), -1);
   for (int k = 0; k < 7; k++) {
-    if (k >= 5 && !(s->pmg.ok && s->pmg.d_B8c)) break;
+    if (k >= 5 && !(s->pmg.ok && s->pmg.vertex.d_B8)) break;
     HIP_TRY(hipEventRecord(s->ev[6], s->stream));
     for (int r = 0; r < reps; r++) {
       if (k == 0) {
@@ -5767,40 +5654,23 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
         // the polynomial-step kernel in the order of one V-cycle: fine, fine, kc-1 coarse, fine (the cycle's last fine
         // step is another instantiation).  Both levels run the SAME kernel, so this is the per-launch average that
         // rocprofv3 reports under the kernel's name (the levels evict each other's matrix from L2 between launches).
-        auto& m = s->pmg;
-        const size_t n = 3 * (size_t)N, nc = 3 * (size_t)m.Nc;
-        float *f = s->d_f32, *g = m.d_f32c;
-        const int kc = pmg_coarse_degree_eff(s), bits = cheb_bits_eff(s);
-        auto fine = [&](int a) {
-          const int b = 1 - a;
-          launch_cheb32(s->stream, N, d->nnz_coef, d->inc(), s->d_B8, s->d_B1, fine_bits(s), f + 6 * n, s->d_sc, f + a * n,
-                        m.d_coef + 2, f + b * n, f + (2 + a) * n, f + (2 + b) * n, f + (4 + a) * n, f + (4 + b) * n, s->d_r,
-                        s->d_zv, part(s, 0), false);
-        };
-        fine(0);
-        fine(1);
-        for (int c = 1; c < kc; c++) {
-          const int a = c & 1, b = 1 - a;
-          launch_cheb32(s->stream, m.Nc, m.nnz_c, m.inc(), m.d_B8c, m.d_B1c, bits, g + 6 * nc, m.d_sc_c, g + a * nc,
-                        m.d_coef + pmg_cf_coarse(s) + 2, g + b * nc, g + (2 + a) * nc, g + (2 + b) * nc, g + (4 + a) * nc, g + (4 + b) * nc,
-                        s->d_r, s->d_zv, part(s, 0), false);
-        }
-        fine(0);
+        C32Vecs f(s->d_f32, 3 * (size_t)N), c(V.d_f32, 3 * (size_t)V.N);
+        const int kc = pmg_coarse_degree_eff(s);
+        const double* cf = s->pmg.d_coef;
+        c32_step(s, Lf, f, N, cf + 2, s->d_r, s->d_zv, part(s, 0), false);
+        c32_step(s, Lf, f, N, cf + 2, s->d_r, s->d_zv, part(s, 0), false);
+        c.swap();  // as after the cycle's restriction: the first vertex-level step reads the second buffers
+        const double* cc = cf + pmg_table(s).coarse() + 2;
+        for (int j = 1; j < kc; j++) c32_step(s, Lc, c, V.N, cc, s->d_r, s->d_zv, part(s, 0), false);
+        c32_step(s, Lf, f, N, cf + 2, s->d_r, s->d_zv, part(s, 0), false);
       } else if (k == 5) {  // one step of the coarse-level polynomial of the p-multigrid cycle
-        auto& m = s->pmg;
-        const size_t nc = 3 * (size_t)m.Nc;
-        float* f = m.d_f32c;
-        const int a = r & 1, b = 1 - a;
-        launch_cheb32(s->stream, m.Nc, m.nnz_c, m.inc(), m.d_B8c, m.d_B1c, cheb_bits_eff(s), f + 6 * nc, m.d_sc_c,
-                      f + a * nc, m.d_coef + pmg_cf_coarse(s) + 2, f + b * nc, f + (2 + a) * nc, f + (2 + b) * nc, f + (4 + a) * nc,
-                      f + (4 + b) * nc, s->d_r, s->d_zv, part(s, 0), false);
+        C32Vecs c(V.d_f32, 3 * (size_t)V.N);
+        if (r & 1) c.swap();  // each step reads what the last one wrote
+        c32_step(s, Lc, c, V.N, s->pmg.d_coef + pmg_table(s).coarse() + 2, s->d_r, s->d_zv, part(s, 0), false);
       } else if (cheb_bits_eff(s) != 64 && s->d_B8 && !s->ar) {  // one step of the polynomial, buffers ping-pong as in
-        const size_t n = 3 * (size_t)N;                          // cheb_apply (each step reads what the last one wrote)
-        float* f = s->d_f32;
-        const int a = r & 1, b = 1 - a;
-        launch_cheb32(s->stream, N, d->nnz_coef, d->inc(), s->d_B8, s->d_B1, fine_bits(s), f + 6 * n, s->d_sc,
-                      f + a * n, s->d_coef + 2, f + b * n, f + (2 + a) * n, f + (2 + b) * n, f + (4 + a) * n,
-                      f + (4 + b) * n, s->d_r, s->d_zv, part(s, 0), false);
+        C32Vecs f(s->d_f32, 3 * (size_t)N);                      // cheb_apply (each step reads what the last one wrote)
+        if (r & 1) f.swap();
+        c32_step(s, Lf, f, N, s->d_coef + 2, s->d_r, s->d_zv, part(s, 0), false);
       } else if (cheb_bits_eff(s) != 64 && s->d_B8)
         launch_cheb_lp(s->stream, N, d->nnz_coef, d->inc(), s->d_B8, s->d_B1, cheb_bits_eff(s), s->d_Dinv_s, s->d_sc,
                        s->d_cd, s->d_coef + 2, s->d_cd2, s->d_cz, s->d_cz2, s->d_cres, s->d_cres2, s->d_r, s->d_w, part(s, 0), 0);
@@ -5864,6 +5734,43 @@ struct ModalWork {
     TRY(dmalloc(p, n));
     owned.push_back(*p);
     return 0;
+  }
+};
+// Warm-start state of the lambda_max estimates (fine level and the coarse levels that exist): save() keeps it and sets the
+// estimates cold, so that what follows depends on no earlier solve; restore() puts it back.  A level built in between did
+// not exist at the save: its vector stays, its estimate goes back to 0.
+struct LamKeep {
+  std::vector<std::pair<double*, size_t>> vecs;  // the kept vectors that exist at the save
+  std::vector<std::pair<double*, double>> lams;  // the estimates
+  double* d_save = nullptr;
+  int save(tlfea_newton_t s, ModalWork& wk) {
+    size_t total = 0;
+    for (PolyLevel* L : {&s->pmg.vertex, &s->pmg.agg.lvl})
+      if (L->d_eigv) vecs.push_back({L->d_eigv, 3 * (size_t)L->N});
+    vecs.push_back({s->d_eigv, 3 * (size_t)s->N});
+    for (auto& v : vecs) total += v.second;
+    TRY(wk.alloc(&d_save, total));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(copy(true));
+    for (double* p : {&s->lam_max, &s->lam_max_loc, &s->pmg.vertex.lam, &s->pmg.agg.lvl.lam}) {
+      lams.push_back({p, *p});
+      *p = 0.0;
+    }
+    return 0;
+  }
+  void restore() {
+    for (auto& l : lams) *l.first = l.second;
+    (void)copy(false);
+  }
+  hipError_t copy(bool out) {
+    hipError_t e = hipSuccess;
+    double* at = d_save;
+    for (auto& v : vecs) {
+      const hipError_t e1 = hipMemcpy(out ? at : v.first, out ? v.first : at, v.second * sizeof(double), hipMemcpyDeviceToDevice);
+      if (e == hipSuccess) e = e1;
+      at += v.second;
+    }
+    return e;
   }
 };
 }  // namespace
@@ -6083,34 +5990,24 @@ extern "C" int tlfea_newton_modal_solve(tlfea_newton_t s, const tlfea_modal_opts
                 std::to_string(3 * n_free) + " free DOFs");
   info[2] = m;
   // what the call must leave as it found it: the time step, the warm-start state of the linear solver
-  const size_t n = 3 * (size_t)s->N;
-  const size_t nc = s->pmg.d_eigv_c ? 3 * (size_t)s->pmg.Nc : 0, n3 = s->pmg.agg.d_eigv3 ? 3 * (size_t)s->pmg.agg.N3 : 0;
-  ModalWork keep;
-  double* d_save = nullptr;
-  TRY(keep.alloc(&d_save, n + nc + n3));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(d_save, s->d_eigv, n * sizeof(double), hipMemcpyDeviceToDevice));
-  if (nc) HIP_TRY(hipMemcpy(d_save + n, s->pmg.d_eigv_c, nc * sizeof(double), hipMemcpyDeviceToDevice));
-  if (n3) HIP_TRY(hipMemcpy(d_save + n + nc, s->pmg.agg.d_eigv3, n3 * sizeof(double), hipMemcpyDeviceToDevice));
-  const double h0 = s->prm.time_step, lam_max0 = s->lam_max, lam_loc0 = s->lam_max_loc, safety0 = s->lam_safety,
-               lam_c0 = s->pmg.lam_c, lam30 = s->pmg.agg.lam3, boost0 = s->pmg.kc_boost, last_rel0 = s->lin_last_rel,
+  ModalWork wk;
+  LamKeep keep;
+  const double h0 = s->prm.time_step, safety0 = s->lam_safety, boost0 = s->pmg.kc_boost, last_rel0 = s->lin_last_rel,
                worst_rel0 = s->lin_worst_rel;
   const int outer0 = s->last_outer_iters, deg0 = s->last_deg, bits0 = s->last_bits, mode0 = s->mf.last_mode;
   const bool last_ok0 = s->lin_last_ok, all_ok0 = s->lin_all_ok;
+  TRY(keep.save(s, wk));  // cold estimates: the result depends on no earlier solve
   s->prm.time_step = 1.0 / std::sqrt(o.shift);
-  s->lam_max = s->lam_max_loc = s->pmg.lam_c = s->pmg.agg.lam3 = 0.0;  // cold estimates: the result depends on no earlier solve
   int rc = assemble(s, /*fq_fresh=*/false);
   if (!rc) rc = modal_iterate(s, o, m, omega2, modes, resid, info);
   const std::string why = rc ? g_err : std::string();
   (void)hipStreamSynchronize(s->stream);
   s->prm.time_step = h0;
-  s->lam_max = lam_max0; s->lam_max_loc = lam_loc0; s->lam_safety = safety0;
-  s->pmg.lam_c = lam_c0; s->pmg.agg.lam3 = lam30; s->pmg.kc_boost = boost0;
+  s->lam_safety = safety0;
+  s->pmg.kc_boost = boost0;
   s->last_outer_iters = outer0; s->last_deg = deg0; s->last_bits = bits0; s->mf.last_mode = mode0;
   s->lin_last_rel = last_rel0; s->lin_worst_rel = worst_rel0; s->lin_last_ok = last_ok0; s->lin_all_ok = all_ok0;
-  (void)hipMemcpy(s->d_eigv, d_save, n * sizeof(double), hipMemcpyDeviceToDevice);
-  if (nc) (void)hipMemcpy(s->pmg.d_eigv_c, d_save + n, nc * sizeof(double), hipMemcpyDeviceToDevice);
-  if (n3) (void)hipMemcpy(s->pmg.agg.d_eigv3, d_save + n + nc, n3 * sizeof(double), hipMemcpyDeviceToDevice);
+  keep.restore();
   const int rc2 = assemble(s, /*fq_fresh=*/false);  // H of the caller's time step again
   (void)hipStreamSynchronize(s->stream);
   if (rc) {
@@ -6147,19 +6044,14 @@ extern "C" int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, 
   if (dist_on(s)) return fail("tlfea_newton_apply_preconditioner: not available on a partitioned mesh (set_interface / set_halo is active)");
   if (s->lin.method == 1) return fail("tlfea_newton_apply_preconditioner: method = 1 (sparse direct) has no preconditioner");
   const size_t n = 3 * (size_t)s->N;
-  const size_t nc = s->pmg.d_eigv_c ? 3 * (size_t)s->pmg.Nc : 0, n3 = s->pmg.agg.d_eigv3 ? 3 * (size_t)s->pmg.agg.N3 : 0;
   ModalWork wk;
-  double *d_save = nullptr, *dR = nullptr, *dZ = nullptr;
-  TRY(wk.alloc(&d_save, n + nc + n3));
+  LamKeep keep;
+  double *dR = nullptr, *dZ = nullptr;
   TRY(wk.alloc(&dR, (size_t)m * n));
   TRY(wk.alloc(&dZ, (size_t)m * n));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(d_save, s->d_eigv, n * sizeof(double), hipMemcpyDeviceToDevice));
-  if (nc) HIP_TRY(hipMemcpy(d_save + n, s->pmg.d_eigv_c, nc * sizeof(double), hipMemcpyDeviceToDevice));
-  if (n3) HIP_TRY(hipMemcpy(d_save + n + nc, s->pmg.agg.d_eigv3, n3 * sizeof(double), hipMemcpyDeviceToDevice));
   HIP_TRY(hipMemcpy(dR, R, (size_t)m * n * sizeof(double), hipMemcpyHostToDevice));
-  const double lam_max0 = s->lam_max, lam_loc0 = s->lam_max_loc, lam_c0 = s->pmg.lam_c, lam30 = s->pmg.agg.lam3;
-  s->lam_max = s->lam_max_loc = s->pmg.lam_c = s->pmg.agg.lam3 = 0.0;  // cold estimates: the result depends on no earlier solve
+  TRY(keep.save(s, wk));  // cold estimates: the result depends on no earlier solve
   auto run = [&]() -> int {
     // start vector of the fine lambda_max estimate: the first vector, ones where that is zero (no estimate from nothing)
     bool zero = true;
@@ -6187,12 +6079,8 @@ extern "C" int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, 
   const int rc = run();
   const std::string why = rc ? g_err : std::string();
   (void)hipStreamSynchronize(s->stream);
-  s->hook_lam[0] = s->lam_max; s->hook_lam[1] = s->pmg.lam_c; s->hook_lam[2] = s->pmg.agg.lam3;
-  s->lam_max = lam_max0; s->lam_max_loc = lam_loc0; s->pmg.lam_c = lam_c0; s->pmg.agg.lam3 = lam30;
-  // the set-up may have built the p-multigrid levels for the first time: their kept vectors did not exist at the save
-  (void)hipMemcpy(s->d_eigv, d_save, n * sizeof(double), hipMemcpyDeviceToDevice);
-  if (nc) (void)hipMemcpy(s->pmg.d_eigv_c, d_save + n, nc * sizeof(double), hipMemcpyDeviceToDevice);
-  if (n3) (void)hipMemcpy(s->pmg.agg.d_eigv3, d_save + n + nc, n3 * sizeof(double), hipMemcpyDeviceToDevice);
+  s->hook_lam[0] = s->lam_max; s->hook_lam[1] = s->pmg.vertex.lam; s->hook_lam[2] = s->pmg.agg.lvl.lam;
+  keep.restore();
   if (rc) g_err = why;
   return rc;
 }
@@ -6215,13 +6103,14 @@ extern "C" int tlfea_newton_preconditioner_state(tlfea_newton_t s, int* iout16, 
   int n_coef = 0;
   const double* src = nullptr;
   if (pmg) {
-    iout16[3] = pmg_ks(s);
-    iout16[4] = pmg_cf_resid(s); iout16[5] = pmg_cf_restart(s); iout16[6] = pmg_cf_beta(s); iout16[7] = pmg_cf_coarse(s);
-    iout16[8] = l3 ? pmg_cf_level3(s) : 0;
-    iout16[9] = l3 ? pmg_ks2(s) : 0;
-    iout16[10] = l3 ? 0 : pmg_coarse_degree_eff(s);
-    iout16[11] = l3 ? pmg_level3_degree(s->pmg.agg.N3) : 0;
-    n_coef = l3 ? pmg_cf_level3(s) + 2 * iout16[11] : pmg_cf_coarse(s) + 2 * iout16[10];
+    const PmgTable t = pmg_table(s);
+    iout16[3] = t.ks;
+    iout16[4] = t.resid(); iout16[5] = t.restart(); iout16[6] = t.beta(); iout16[7] = t.coarse();
+    iout16[8] = t.level3();
+    iout16[9] = t.ks2;
+    iout16[10] = t.kc;
+    iout16[11] = t.k3;
+    n_coef = t.size();
     src = s->pmg.d_coef;
   } else if (deg > 1) {
     n_coef = 2 * deg;
@@ -6231,7 +6120,7 @@ extern "C" int tlfea_newton_preconditioner_state(tlfea_newton_t s, int* iout16, 
   iout16[13] = n_coef;
   HIP_TRY(hipStreamSynchronize(s->stream));
   if (n_coef) HIP_TRY(hipMemcpy(coef, src, (size_t)n_coef * sizeof(double), hipMemcpyDeviceToHost));
-  dout8[0] = s->lam_max; dout8[1] = s->pmg.lam_c; dout8[2] = s->pmg.agg.lam3; dout8[3] = s->lam_safety;
+  dout8[0] = s->lam_max; dout8[1] = s->pmg.vertex.lam; dout8[2] = s->pmg.agg.lvl.lam; dout8[3] = s->lam_safety;
   dout8[4] = s->hook_lam[0]; dout8[5] = s->hook_lam[1]; dout8[6] = s->hook_lam[2];
   return 0;
 }
