@@ -406,6 +406,19 @@ int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int *out6);
  * TLFEA_C32_REGIME=1|2|3|4 forces a regime (4: one-round with half the lanes); a forced one-round regime that does not
  * fit the device falls back to the automatic choice. */
 int tlfea_newton_get_c32_geometry(tlfea_newton_t s, int level, int *out7);
+/* Test hooks of the engine's own sparse direct solve (lin.method = 1, native backend), valid once a direct solve has
+ * built its plan.  get_direct_info: out22 = plan facts [0] fronts, [1] levels, [2] top_depth (-1: every batch a whole
+ * level; >= 0: fronts down to that depth one by one with a stack of update matrices), [3] doubles of the factor,
+ * [4..7] doubles of the level buffers 0 / 1, the WORK buffer and the STACK, [8] largest front (DOF rows), [9] most own
+ * columns of a front, [10] fronts without own columns, [11] nodes; then the kernel launches of the LAST factorisation +
+ * solve, counted on the host next to each launch: [12] panel, [13] update inside a super-panel, [14] trailing update in
+ * 64-tiles, [15] trailing update in 128-tiles, [16] extend-add, [17] stack push, [18] levels solved one workgroup per
+ * front, [19] levels solved step by step, [20] forward steps, [21] backward steps.  get_direct_fronts: the elimination
+ * order (new -> old node, [nodes]) and per front (children before parents) c0, c1 (own nodes: new positions [c0, c1)),
+ * depth, parent, node rows, child 0, child 1 ([7 fronts]; -1: none).  The switches that steer the plan and the launches: TLFEA_DIRECT_LEAF,
+ * _TOP_DEPTH, _MAX_NNZ, _SUPER, _WIDE_TILES, _ONE_WG_ROWS (DESIGN, "Sparse direct solve"). */
+int tlfea_newton_get_direct_info(tlfea_newton_t s, long long *out22);
+int tlfea_newton_get_direct_fronts(tlfea_newton_t s, int *order, int *fronts7);
 int tlfea_newton_pmg_restrict_op_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals);
 int tlfea_newton_pmg_fine_copy_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals, double *sc_f, double *sc_c);
 int tlfea_newton_hessian_nnz(tlfea_newton_t s, int *nnz);

@@ -22,6 +22,49 @@ extern "C" int mf_build(int N, const int* off, const int* cols, const double* x,
   info[7] = (long long)g_p.h_src.size();
   return 0;
 }
+// what tlfea_newton_get_direct_info reports of a plan beyond mf_build's info: top_depth and the four workspaces
+extern "C" void mf_regime(long long* out5) {
+  out5[0] = g_p.top_depth;
+  for (int t = 0; t < 4; t++) out5[1 + t] = g_p.F_cap[t];
+}
+// the table tlfea_newton_get_direct_fronts returns: c0, c1, depth, parent, node rows, child 0, child 1 per front
+extern "C" void mf_fronts(int* fronts7) {
+  for (size_t f = 0; f < g_p.fronts.size(); f++) {
+    const tlfea::MfFront& F = g_p.fronts[f];
+    const int v[7] = {F.c0, F.c1, F.depth, F.parent, F.nrows, F.child[0], F.child[1]};
+    std::copy(v, v + 7, fronts7 + 7 * f);
+  }
+}
+// Everything the kernels address through the plan lies inside the buffers the plan sizes (the device allocates exactly
+// L_total, F_cap[0..3], v_total): 0 when it does, else the number of the first check that fails.
+extern "C" int mf_check_bounds() {
+  using namespace tlfea;
+  const MfPlan& P = g_p;
+  for (const MfBatch& B : P.batches) {
+    if (B.F_base < 0 || B.F_base + B.F_doubles > P.F_cap[B.wbuf]) return 1;
+    for (int t = B.hent_off; t < B.hent_off + B.hent_count; t++)
+      if (P.h_dst[t] < B.F_base || P.h_dst[t] + 2 + 2LL * P.h_dld[t] >= B.F_base + B.F_doubles) return 2;
+    for (int t = B.first; t < B.first + B.count; t++) {
+      const MfFront& F = P.fronts[P.batch_fronts[t]];
+      const long long m = 3LL * F.nrows, k = 3LL * (F.c1 - F.c0), mu = m - k;
+      if (F.F_off < B.F_base || F.F_off + m * m > B.F_base + B.F_doubles) return 3;
+      if (F.L_off < 0 || F.L_off + m * k > P.L_total) return 4;
+      if (F.v_off < 0 || F.v_off + m > P.v_total) return 5;
+      for (int c : F.child) {
+        if (c < 0) continue;
+        const MfFront& C = P.fronts[c];
+        const long long mc = 3LL * (C.nrows - (C.c1 - C.c0));
+        if (mc > 0 && (C.cF_off < 0 || C.cF_off + (C.c_k0 + mc - 1) + (C.c_k0 + mc - 1) * (long long)C.c_ld >= P.F_cap[B.cbuf]))
+          return 6;
+        for (long long i = 0; i < mc / 3; i++)
+          if (P.map[(size_t)C.map_off + i] < 0 || P.map[(size_t)C.map_off + i] >= F.nrows) return 7;
+      }
+      if (B.push && (B.count != 1 || F.c_k0 != 0 || F.c_ld != mu || F.cF_off < 0 || F.cF_off + mu * mu > P.F_cap[3])) return 8;
+      if (!B.push && F.parent >= 0 && (F.c_ld != m || F.c_k0 != k || F.cF_off != F.F_off)) return 9;
+    }
+  }
+  return 0;
+}
 extern "C" void mf_fetch(int* order, int* front_c0, int* front_c1, int* front_parent, int* front_depth, int* front_nrows) {
   std::copy(g_p.order.begin(), g_p.order.end(), order);
   for (size_t f = 0; f < g_p.fronts.size(); f++) {

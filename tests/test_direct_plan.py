@@ -98,6 +98,67 @@ def test_plan_factors_and_solves(shim, mesh, leaf):
         assert np.linalg.norm(x2 - xo) <= 1e-13 * np.linalg.norm(xo)
 
 
+def _regime_plan(shim, graph, env, monkeypatch):
+    """the plan the engine builds for a graph under the TLFEA_DIRECT_* switches in env: (fronts [n, 7], top_depth, info) or None"""
+    off, cols, x, y, z = graph
+    monkeypatch.delenv("TLFEA_DIRECT_TOP_DEPTH", raising=False)
+    if "TLFEA_DIRECT_TOP_DEPTH" in env:                     # read by mf_plan_build itself, per plan
+        monkeypatch.setenv("TLFEA_DIRECT_TOP_DEPTH", env["TLFEA_DIRECT_TOP_DEPTH"])
+    info = (C.c_longlong * 8)()
+    leaf, bound = int(env.get("TLFEA_DIRECT_LEAF", 32)), int(env.get("TLFEA_DIRECT_MAX_NNZ", 1 << 40))
+    if shim.mf_build(len(x), ip(off), ip(cols), dp(x), dp(y), dp(z), leaf, bound, info) != 0:
+        return None
+    assert shim.mf_check_bounds() == 0      # what the kernels will address lies inside the buffers the plan sizes
+    fronts, reg = np.zeros(7 * int(info[0]), dtype=np.int32), (C.c_longlong * 5)()
+    shim.mf_fronts(ip(fronts))
+    shim.mf_regime(reg)
+    return fronts.reshape(-1, 7), int(reg[0]), dict(L_total=int(info[2]), F_cap0=int(reg[1]), F_cap1=int(reg[2]),
+                                                    F_cap_work=int(reg[3]), F_cap_stack=int(reg[4]))
+
+
+def test_regime_configurations_reach_their_regimes(shim, monkeypatch):
+    """Every configuration of tests/test_gpu_direct_regimes.py (table and `expect` inequalities: tests/direct_worker.py),
+    evaluated on the plan this host builds for its mesh and switches: a mesh or a switch that stops reaching the kernel
+    regime it is there for is caught here, without a GPU.  The launches are those plan_facts predicts; on the GPU the
+    worker requires the launches the library counted to equal that prediction."""
+    from tests import direct_worker as dw
+    graphs, facts, spd = {}, {}, {}
+    for name, problem, env in dw.CONFIGS:
+        if problem not in graphs:
+            graphs[problem] = dw.plan_graph(problem)
+        assert 3 * len(graphs[problem][2]) <= 13000, (problem, "the matrix is to stay a small mesh")
+        if name == "stack_auto":
+            continue
+        fronts, top, info = _regime_plan(shim, graphs[problem], env, monkeypatch)
+        facts[name] = dict(dw.plan_facts(fronts, top, env), **info)
+        dw.check_expect(name, env, facts[name])
+        if name in ("stack_0", "stack_2", "stack_all", "levels_ref", "two_bodies_stack"):
+            # the forced cuts, executed: WORK buffer, stack pushes and pops give the solution of the whole-level plan
+            if problem not in spd:
+                N = len(graphs[problem][2])
+                vals, A = spd_in_engine_layout(N, graphs[problem][0], graphs[problem][1], 5)
+                b = np.random.default_rng(7).normal(size=3 * N)
+                spd[problem] = (vals, b, spla.spsolve(A, b))
+            vals, b, ref = spd[problem]
+            xo = np.zeros_like(b)
+            assert shim.mf_cpu_factor_solve(dp(vals), dp(b), dp(xo)) == 0
+            assert np.linalg.norm(xo - ref) <= 1e-12 * np.linalg.norm(ref), name
+    # the plan's own choice of the stack regime: the first memory bound of the list that it accepts
+    problem = dict((c[0], c[1]) for c in dw.CONFIGS)["stack_auto"]
+    for f in dw.STACK_AUTO_FRACTIONS:
+        env = dw.stack_auto_env(facts["levels_ref"], f)
+        got = _regime_plan(shim, graphs[problem], env, monkeypatch)
+        if got is not None:
+            dw.check_expect("stack_auto", env, dw.plan_facts(got[0], got[1], env))
+            break
+    else:
+        raise AssertionError("the plan accepts none of the memory bounds of stack_auto")
+    # the four configurations that are compared bit by bit share the ordering and the fronts
+    for name in ("stack_0", "stack_2", "stack_all"):
+        assert all(np.array_equal(facts[name][key], facts["levels_ref"][key]) for key in ("k", "m", "depth", "parent"))
+        assert facts[name]["L_total"] == facts["levels_ref"]["L_total"]
+
+
 def test_plan_refuses_what_does_not_fit(shim):
     X, conn = mu.structured_t10_box(4, 3, 3, 2.0, 1.5, 1.5)
     conn = np.ascontiguousarray(conn, dtype=np.int32)

@@ -40,6 +40,9 @@ def test_library_exports_every_declared_symbol():
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, missing
     assert lib.tlfea_version() >= 100
+    # the read-back hooks tests assert kernel regimes through are part of the declared surface
+    for hook in ("tlfea_newton_get_c32_geometry", "tlfea_newton_get_direct_info", "tlfea_newton_get_direct_fronts"):
+        assert hook in syms and hasattr(lib, hook), hook
 
 
 def test_no_cpu_fallback_without_gpu():

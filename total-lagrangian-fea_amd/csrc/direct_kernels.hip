@@ -511,9 +511,12 @@ __global__ void mf_unpermute_kernel(int N, const int* __restrict__ order, const 
 }  // namespace
 
 // numeric factorisation of the H whose values are at `H` (the engine's layout); err is set when a pivot is not positive
-void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const double* H) {
+void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const double* H, MfTally& tally) {
   // super-panel: the trailing matrix is updated once per KS columns (a multiple of the panel width)
   static const int KS = NB * std::max(1, std::getenv("TLFEA_DIRECT_SUPER") ? std::atoi(std::getenv("TLFEA_DIRECT_SUPER")) : 8);
+  // 128-tiles from this many of them on (the chip's 256 CUs twice over)
+  static const double wide_tiles = std::getenv("TLFEA_DIRECT_WIDE_TILES") ? std::atof(std::getenv("TLFEA_DIRECT_WIDE_TILES")) : 512.0;
+  tally.panel = tally.update_inner = tally.update_trailing = tally.update_wide = tally.extend_add = tally.push = 0;
   (void)hipMemsetAsync(D.err, 0, sizeof(int), s);
   for (const MfBatch& B : P.batches) {  // level batches, then (large problems) the top fronts one by one (mf_host.h)
     double* W = D.F[B.wbuf];
@@ -537,9 +540,11 @@ void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const doub
       }
       if (mu <= 0) continue;
       const unsigned g = (unsigned)((mu + 15) / 16);
-      for (int z0 = 0; z0 < nfl; z0 += 32768)
+      for (int z0 = 0; z0 < nfl; z0 += 32768) {
         hipLaunchKernelGGL(mf_extend_add_kernel, dim3(g, g, (unsigned)std::min(32768, nfl - z0)), dim3(256), 0, s, D.fr,
                            lvl + z0, slot, W, Wc, D.map);
+        tally.extend_add++;
+      }
     }
     for (int t = B.step_off; t < B.step_off + B.step_count; t++) {
       const MfLevelStep& st = P.bsteps[t];
@@ -549,9 +554,12 @@ void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const doub
       for (int z0 = 0; z0 < st.n_active; z0 += 32768) {
         const unsigned nz = (unsigned)std::min(32768, st.n_active - z0);
         hipLaunchKernelGGL(mf_panel_kernel, dim3(rt, nz), dim3(256), 0, s, D.fr, lvl + z0, st.j0, W, D.L, D.err);
-        if (ut > 0 && st.j0 + NB < s1)
+        tally.panel++;
+        if (ut > 0 && st.j0 + NB < s1) {
           hipLaunchKernelGGL(mf_update_kernel, dim3(ut, std::min(ut, ct), nz), dim3(256), 0, s, D.fr, lvl + z0, st.j0, s1, 0,
                              W, D.L);
+          tally.update_inner++;
+        }
       }
       if (st.j0 + NB >= s1 || t + 1 == B.step_off + B.step_count) {  // the super-panel is complete: take it out of the rest
         const MfLevelStep& s0 = P.bsteps[B.step_off + S0 / NB];
@@ -562,7 +570,7 @@ void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const doub
         }
         const unsigned wt = (unsigned)((below + WT - 1) / WT), wt64 = (unsigned)((below + 63) / 64);
         // 128-tiles when they fill the chip (the lower triangle of the largest front x the fronts), 64-tiles below that
-        const bool big = (double)wt * (wt + 1) / 2 * s0.n_active >= 2.0 * 256;
+        const bool big = (double)wt * (wt + 1) / 2 * s0.n_active >= wide_tiles;
         if (wt > 0)
           for (int z0 = 0; z0 < s0.n_active; z0 += 32768) {
             const unsigned nz = (unsigned)std::min(32768, s0.n_active - z0);
@@ -570,22 +578,26 @@ void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const doub
               hipLaunchKernelGGL(mf_update_wide_kernel, dim3(wt, wt, nz), dim3(256), 0, s, D.fr, lvl + z0, S0, KS, W, D.L);
             else
               hipLaunchKernelGGL(mf_update_kernel, dim3(wt64, wt64, nz), dim3(256), 0, s, D.fr, lvl + z0, S0, s1, 1, W, D.L);
+            (big ? tally.update_wide : tally.update_trailing)++;
           }
       }
     }
     if (B.push) {
       const MfFront& F = P.fronts[P.batch_fronts[(size_t)B.first]];
       const int mu = 3 * (F.nrows - (F.c1 - F.c0));
-      if (mu > 0)
+      if (mu > 0) {
         hipLaunchKernelGGL(mf_push_kernel, dim3((unsigned)((mu + 63) / 64), (unsigned)((mu + 63) / 64)), dim3(256), 0, s, D.fr,
                            P.batch_fronts[(size_t)B.first], W, D.F[3]);
+        tally.push++;
+      }
     }
   }
 }
 
 // x = H^-1 b with the factor of the last launch_mf_factor (b, x in the engine's DOF order; x may alias b)
-void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const double* b, double* x) {
+void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const double* b, double* x, MfTally& tally) {
   const int nl = P.n_levels();
+  tally.levels_one_wg = tally.levels_stepwise = tally.fwd_step = tally.bwd_step = 0;
   // a level whose largest front has at most this many DOF rows runs one workgroup per front; above, step by step
   static const int one_wg_rows = std::getenv("TLFEA_DIRECT_ONE_WG_ROWS") ? std::atoi(std::getenv("TLFEA_DIRECT_ONE_WG_ROWS")) : 768;
   std::vector<int> m_max((size_t)nl, 0), mu_max((size_t)nl, 0), k_max((size_t)nl, 0);
@@ -602,8 +614,10 @@ void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const doubl
     const int* lvl = D.lvl + P.level_off[l];
     if (m_max[l] <= one_wg_rows) {
       hipLaunchKernelGGL(mf_forward_kernel, dim3(nfl), dim3(512), 0, s, D.fr, lvl, D.L, D.map, D.order, b, D.v, D.y);
+      tally.levels_one_wg++;
       continue;
     }
+    tally.levels_stepwise++;
     hipLaunchKernelGGL(mf_fwd_init_kernel, dim3((unsigned)((m_max[l] + 255) / 256), nfl), dim3(256), 0, s, D.fr, lvl, D.order, b,
                        D.v);
     if (mu_max[l] > 0)
@@ -614,6 +628,7 @@ void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const doubl
       const MfLevelStep& st = P.steps[t];
       hipLaunchKernelGGL(mf_fwd_step_kernel, dim3((unsigned)std::max(1, (st.max_below + 255) / 256), (unsigned)st.n_active),
                          dim3(256), 0, s, D.fr, lvl, st.j0, D.L, D.v, D.y);
+      tally.fwd_step++;
     }
   }
   for (int l = nl - 1; l >= 0; l--) {
@@ -630,6 +645,7 @@ void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const doubl
       const MfLevelStep& st = P.steps[t];
       hipLaunchKernelGGL(mf_bwd_step_kernel, dim3((unsigned)std::max(1, (st.j0 + 255) / 256), (unsigned)st.n_active), dim3(256),
                          0, s, D.fr, lvl, st.j0, D.L, D.v, D.xp);
+      tally.bwd_step++;
     }
   }
   hipLaunchKernelGGL(mf_unpermute_kernel, dim3((unsigned)((P.N + 255) / 256)), dim3(256), 0, s, P.N, D.order, D.xp, x);

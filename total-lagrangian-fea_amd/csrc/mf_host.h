@@ -382,7 +382,8 @@ inline bool mf_plan_build(int N, const int* off, const int* cols, const double* 
         std::fprintf(stderr, "top depth %d: workspace %.4g (levels %.4g %.4g, work %.4g, stack %.4g)\n", c, (double)w, (double)cap[0],
                      (double)cap[1], (double)cap[2], (double)cap[3]);
       }
-    static const int forced = std::getenv("TLFEA_DIRECT_TOP_DEPTH") ? std::atoi(std::getenv("TLFEA_DIRECT_TOP_DEPTH")) : -2;
+    // (read per plan, not once per process: the CPU suite builds plans of several forced depths in one process)
+    const int forced = std::getenv("TLFEA_DIRECT_TOP_DEPTH") ? std::atoi(std::getenv("TLFEA_DIRECT_TOP_DEPTH")) : -2;
     if (forced >= -1) T = std::min(forced, maxd);
     else
       while (T < maxd && P.L_total + workspace(T, cap) > max_doubles) T++;

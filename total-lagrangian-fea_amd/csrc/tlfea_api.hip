@@ -2341,6 +2341,7 @@ struct tlfea_newton_s {
     double* d_valT = nullptr;
     MfPlan plan;      // host plan (levels, panel steps); the device copies below
     MfDev dev{};
+    MfTally tally;    // launches of the last native factorisation + solve (tlfea_newton_get_direct_info)
     std::vector<void*> owned;  // device allocations of the native backend
     double factor_ms = 0.0, solve_ms = 0.0;
   } direct;
@@ -5119,8 +5120,8 @@ static int direct_solve(tlfea_newton_t s, const double* d_b, double* d_x, int* i
   StageTimer t(s, 4);
   const size_t nb = (size_t)m.n * sizeof(double);
   if (m.backend == 0) {
-    launch_mf_factor(s->stream, m.plan, m.dev, s->d_H);
-    launch_mf_solve(s->stream, m.plan, m.dev, d_b, d_x);
+    launch_mf_factor(s->stream, m.plan, m.dev, s->d_H, m.tally);
+    launch_mf_solve(s->stream, m.plan, m.dev, d_b, d_x, m.tally);
     int bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, m.dev.err, sizeof(int), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -5467,6 +5468,40 @@ extern "C" int tlfea_newton_get_c32_geometry(tlfea_newton_t s, int level, int* o
   out7[4] = g.rows_per_group;
   out7[5] = g.grid;
   out7[6] = g.resident;
+  return 0;
+}
+// Test hooks of the native sparse direct solve: the plan the solver holds and the launches its last factorisation + solve
+// issued (host counters next to the launches, direct_kernels.hip), so that a test can assert which kernels a mesh and the
+// TLFEA_DIRECT_* switches reached.  Available once a direct solve has built the plan.
+extern "C" int tlfea_newton_get_direct_info(tlfea_newton_t s, long long* out22) {
+  if (!s || !out22) return fail("tlfea_newton_get_direct_info: null argument");
+  const auto& m = s->direct;
+  if (!m.ok || m.backend != 0) return fail("tlfea_newton_get_direct_info: no native direct solve has run on this solver");
+  const MfPlan& P = m.plan;
+  long long m_max = 0, k_max = 0, k_zero = 0;
+  for (const MfFront& F : P.fronts) {
+    m_max = std::max(m_max, 3LL * F.nrows);
+    k_max = std::max(k_max, 3LL * (F.c1 - F.c0));
+    k_zero += F.c1 == F.c0;
+  }
+  const MfTally& t = m.tally;
+  const long long v[22] = {(long long)P.fronts.size(), P.n_levels(), P.top_depth, P.L_total, P.F_cap[0], P.F_cap[1], P.F_cap[2],
+                           P.F_cap[3], m_max, k_max, k_zero, P.N, t.panel, t.update_inner, t.update_trailing, t.update_wide,
+                           t.extend_add, t.push, t.levels_one_wg, t.levels_stepwise, t.fwd_step, t.bwd_step};
+  std::copy(v, v + 22, out22);
+  return 0;
+}
+extern "C" int tlfea_newton_get_direct_fronts(tlfea_newton_t s, int* order, int* fronts7) {
+  if (!s || !order || !fronts7) return fail("tlfea_newton_get_direct_fronts: null argument");
+  const auto& m = s->direct;
+  if (!m.ok || m.backend != 0) return fail("tlfea_newton_get_direct_fronts: no native direct solve has run on this solver");
+  const MfPlan& P = m.plan;
+  std::copy(P.order.begin(), P.order.end(), order);
+  for (size_t f = 0; f < P.fronts.size(); f++) {
+    const MfFront& F = P.fronts[f];
+    const int v[7] = {F.c0, F.c1, F.depth, F.parent, F.nrows, F.child[0], F.child[1]};
+    std::copy(v, v + 7, fronts7 + 7 * f);
+  }
   return 0;
 }
 extern "C" int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int* out6) {

@@ -378,8 +378,14 @@ struct MfDev {
   double *v, *y, *xp;
   int* err;
 };
-void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const double* H);
-void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const double* b, double* x);
+// Launches issued by the last launch_mf_factor / launch_mf_solve, counted on the host next to each launch
+// (tlfea_newton_get_direct_info): which kernels a plan and the TLFEA_DIRECT_* switches actually reached.
+struct MfTally {
+  long long panel = 0, update_inner = 0, update_trailing = 0, update_wide = 0, extend_add = 0, push = 0;  // factorisation
+  long long levels_one_wg = 0, levels_stepwise = 0, fwd_step = 0, bwd_step = 0;                           // solve
+};
+void launch_mf_factor(hipStream_t s, const MfPlan& P, const MfDev& D, const double* H, MfTally& tally);
+void launch_mf_solve(hipStream_t s, const MfPlan& P, const MfDev& D, const double* b, double* x, MfTally& tally);
 
 // Rigid analytic obstacles (tlfea_t10_set_obstacles): the list travels by value in the kernel arguments
 // (16 x 120 bytes).  Every surface node owns its own entries of g, of its diagonal block of H and of the per-node

@@ -127,6 +127,25 @@ class SyncedNewtonSolver:
         check(self._lib.tlfea_newton_get_c32_geometry(self._h, int(level), out))
         return dict(zip(("regime", "lanes", "threads", "upfront", "rows_per_group", "grid", "resident"), list(out)))
 
+    DIRECT_INFO_KEYS = ("fronts", "levels", "top_depth", "L_total", "F_cap0", "F_cap1", "F_cap_work", "F_cap_stack", "m_max",
+                        "k_max", "k_zero", "nodes", "panel", "update_inner", "update_trailing", "update_wide", "extend_add",
+                        "push", "levels_one_wg", "levels_stepwise", "fwd_step", "bwd_step")
+
+    def GetDirectInfo(self):
+        """dict of the native sparse direct solve's plan facts (fronts, levels, top_depth, L_total, the four F_cap, m_max,
+        k_max, k_zero, nodes) and of the kernel launches its last factorisation + solve issued (test hook)"""
+        out = (C.c_longlong * 22)()
+        check(self._lib.tlfea_newton_get_direct_info(self._h, out))
+        return dict(zip(self.DIRECT_INFO_KEYS, (int(v) for v in out)))
+
+    def GetDirectFronts(self):
+        """(order[nodes], fronts[n, 7]): elimination order (new -> old node) and per front c0, c1, depth, parent, node rows,
+        child 0, child 1 of the native sparse direct solve's plan, children before parents (test hook)"""
+        info = self.GetDirectInfo()
+        order, fr = np.zeros(info["nodes"], dtype=np.int32), np.zeros(7 * info["fronts"], dtype=np.int32)
+        check(self._lib.tlfea_newton_get_direct_fronts(self._h, ip(order), ip(fr)))
+        return order, fr.reshape(-1, 7)
+
     def RetrieveRestrictOp(self):
         """(off, cols, vals[blocks, 3, 3]): R as stored after the last set-up, fp32 widened to double (test hook)"""
         info = self.GetRestrictOpInfo()
