@@ -606,6 +606,25 @@ int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, const doubl
  * they stand now, [3] lam_safety, [4..6] the estimates of the last tlfea_newton_apply_preconditioner set-up.  coef: the
  * uploaded coefficient table copied back (pairs (c1, c2) per step), at most coef_cap doubles. */
 int tlfea_newton_preconditioner_state(tlfea_newton_t s, int *iout16, double *dout8, double *coef, int coef_cap);
+/* Test hook: the iterative solve of H x = b (host vector b [3N]) for exactly k iterations, 1 <= k <= 8 -- the solver's own
+ * loop (set-up, start, first iteration launched eagerly, later ones replayed as graphs where graphs are on, residual
+ * replacements where the mixed-precision iteration places them) with no convergence test before the last iteration --
+ * and every iterate copied to the host on the way.  Record 0 is taken after the start (x = 0, r = b), record j after
+ * iteration j - 1.
+ *   vecs  [(k+1)][5][3N]: x, r, z, p, q.  p and q are those of the iteration just run, from the buffers that hold them (0 in
+ *         record 0); after an iteration that ended with a residual replacement q is the replacement's H x.  With the
+ *         block-Jacobi preconditioner z already belongs to the NEW r, with a polynomial one to the r the iteration
+ *         started from.
+ *   sums  [(k+1)][4]: the device's totals of the slot arrays r.z (even, odd iterations), p.q, r.r.
+ *   slots [(k+1)][5][512]: the raw slot arrays (r.z even, r.z odd, p.q, r.r, b.b).
+ *   form  [24], what ran: [0] fused direction update [1] lanes per row [2] non-temporal loads [3] tiled sweep [4] XCD
+ *         eighths taken for this N and grid [5] grid of the product [6] graphs replayed [7] mixed-precision iteration
+ *         [8] bit j: iteration j ended with a residual replacement [9] update kernel (0 block-Jacobi, 1 without z, 2 with
+ *         the next polynomial's fp32 start vectors) [10] matrix-free product [11] polynomial degree [12] preconditioner
+ *         (0 | 1 | 2) [13] matrix bits of the polynomial [14] 12 x 12 node blocks [15] grid of the update kernel [16..18]
+ *         lanes, grid and XCD eighths of a residual replacement's fp64 product [19] TLFEA_XCD_ROWS mode.
+ * The warm state is left as a solve of k iterations leaves it.  Refused on a partitioned mesh and with method = 1. */
+int tlfea_newton_cg_trace(tlfea_newton_t s, const double *b, int k, double *vecs, double *sums, double *slots, int *form);
 
 /* ---- SyncedAdamWNocoopSolver (SyncedAdamWNocoop.cuh:22-198, SyncedAdamWNocoop.cu:262-500) ------------------------
  * First-order ALM solver on the same velocity unknowns: per inner iteration one AdamW moment update, x = x_prev + dt v,

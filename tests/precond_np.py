@@ -337,6 +337,34 @@ def unpack_csr(prefix, d):
     return sp.csr_matrix((d[prefix + "_data"], d[prefix + "_indices"], d[prefix + "_indptr"]), shape=tuple(d[prefix + "_shape"]))
 
 
+LAYOUT_KEYS = ("precond", "levels", "degree", "ks", "cf_resid", "cf_restart", "cf_beta", "cf_coarse", "cf_level3", "ks2", "kc",
+               "k3", "smoother", "block")
+
+
+def layout_of(state):
+    """the integers of GetPreconditionerState() a restatement needs, in the order of LAYOUT_KEYS"""
+    return np.array([state[k] for k in LAYOUT_KEYS])
+
+
+def pack_device_state(s, H, store, state, info):
+    """what operator_from() needs from the device besides the coefficient table, as arrays an npz holds: H, the storage
+    bits and, for the cycles, the parent map and the coarse operators of the solver s (shared by the workers of
+    tests/test_gpu_precond_operator.py and tests/test_gpu_cg_trace.py).  Sizes of the coarse levels go into `info`."""
+    data = dict(store=store, **pack_csr("H", H))
+    if state["precond"] == 2:
+        par0, par1, c_off, c_cols, Hc = s.RetrievePmgLevel()
+        nc = len(c_off) - 1
+        vb = np.diff(c_off)
+        data.update(par0=par0, par1=par1, **pack_csr("Hc", node_csr_to_dof(c_off, c_cols, Hc, nc)))
+        info.update(n_vertex=int(nc), vertex_blocks_max=int(vb.max()), vertex_blocks=int(vb.sum()))
+        if state["levels"] == 3:
+            agg, rvec, active, off3, cols3, H3 = s.RetrievePmgLevel3()
+            na = len(active)
+            data.update(agg=agg, rvec=rvec, **pack_csr("H3", node_csr_to_dof(off3, cols3, H3, 2 * na)))
+            info.update(n_aggregates=int(na), inactive_rotations=int((active == 0).sum()), empty_cells=int((active < 0).sum()))
+    return data
+
+
 def operator_from(data, state, dtype=np.float64):
     """the restated M^-1 of a configuration: data holds H (pack_csr "H"), store, and for the cycles par0 / par1 and Hc
     ("Hc"), for three levels agg / rvec and H3 ("H3"); state is GetPreconditionerState() of the set-up to restate"""

@@ -32,7 +32,10 @@ def lanes_rule(n_rows, n_blocks):
 
 
 def build_t10(tag):
-    X, conn = load_mesh(tag)
+    return build_t10_mesh(*load_mesh(tag))
+
+
+def build_t10_mesh(X, conn):
     fixed = fixed_x0(X)
     d = make_gpu(X, conn, MATERIALS["svk"], fixed)
     x = X + np.random.default_rng(7).normal(0.0, 1e-4, X.shape)
@@ -111,18 +114,9 @@ def main(cfg, out_path):
     out.update(store=store, precond=state["precond"], levels=state["levels"], degree=state["degree"], ks=state["ks"],
                ks2=state["ks2"], kc=state["kc"], k3=state["k3"], block=state["block"], smoother=state["smoother"],
                lam=list(state["hook_lam"]), lam_safety=state["lam_safety"], lanes_fine=lanes_rule(N, int(blocks.sum())))
-    data = dict(store=store, R=R, **pn.pack_csr("H", H))
+    data = dict(R=R, **pn.pack_device_state(s, H, store, state, out))
     if state["precond"] == 2:
-        par0, par1, c_off, c_cols, Hc = s.RetrievePmgLevel()
-        nc = len(c_off) - 1
-        vb = np.diff(c_off)
-        data.update(par0=par0, par1=par1, **pn.pack_csr("Hc", pn.node_csr_to_dof(c_off, c_cols, Hc, nc)))
-        out.update(n_vertex=int(nc), vertex_blocks_max=int(vb.max()), lanes_vertex=lanes_rule(nc, int(vb.sum())))
-        if state["levels"] == 3:
-            agg, rvec, active, off3, cols3, H3 = s.RetrievePmgLevel3()
-            na = len(active)
-            data.update(agg=agg, rvec=rvec, **pn.pack_csr("H3", pn.node_csr_to_dof(off3, cols3, H3, 2 * na)))
-            out.update(n_aggregates=int(na), inactive_rotations=int((active == 0).sum()), empty_cells=int((active < 0).sum()))
+        out["lanes_vertex"] = lanes_rule(out["n_vertex"], out["vertex_blocks"])
 
     # ---- preconditions of the path this configuration pins -----------------------------------------------------------
     ex = cfg.get("expect", {})
@@ -169,11 +163,8 @@ def main(cfg, out_path):
     x_np, its_np, rel_np = pn.pcg(H, b, op_e, 1e-12)
     out.update(its_gpu=int(its_gpu), its_np=int(its_np), rel_gpu=float(rel), rel_np=float(rel_np),
                x_relerr=float(np.abs(x_gpu - x_np).max() / np.abs(x_np).max()), lam_safety_solve=st_e["lam_safety"])
-    keys = ("precond", "levels", "degree", "ks", "cf_resid", "cf_restart", "cf_beta", "cf_coarse", "cf_level3", "ks2", "kc",
-            "k3", "smoother", "block")
     data.update(b=b, names=np.array(names), coef=state["coef"], coef_solve=st_e["coef"],
-                layout=np.array([state[k] for k in keys]), layout_solve=np.array([st_e[k] for k in keys]),
-                layout_keys=np.array(keys))
+                layout=pn.layout_of(state), layout_solve=pn.layout_of(st_e), layout_keys=np.array(pn.LAYOUT_KEYS))
     np.savez(out_path, **data)
     print(json.dumps(out), flush=True)
     del s

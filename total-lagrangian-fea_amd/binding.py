@@ -178,6 +178,7 @@ def _pmg_signatures(lib):
            "tlfea_newton_get_c32_geometry": [vp, C.c_int, c_ip],
            "tlfea_newton_get_direct_info": [vp, C.POINTER(C.c_longlong)],
            "tlfea_newton_get_direct_fronts": [vp, c_ip, c_ip],
+           "tlfea_newton_cg_trace": [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_ip],
            "tlfea_newton_pmg_restrict_op_retrieve": [vp, c_ip, c_ip, c_dp],
            "tlfea_newton_pmg_fine_copy_retrieve": [vp, c_ip, c_ip, c_dp, c_dp, c_dp]}
     for name, args in sig.items():

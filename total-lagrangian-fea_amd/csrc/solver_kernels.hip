@@ -16,9 +16,7 @@ namespace tlfea {
 // wave64 butterfly + one LDS hop: 1-2 barriers per workgroup sum instead of a 9-barrier tree (these
 // kernels are latency-, not bandwidth-bound on small meshes).  Orders are fixed -> bitwise reproducible.
 bool row_map_tiled();
-// XCD-aware row sweep of the two streaming kernels (polynomial step, SpMV).  Workgroups are dealt round-robin over the 8
-// XCDs, so the workgroups b with the same b & 7 share one L2.  They take ONE contiguous eighth of the rows and sweep it in
-// tiles together, so that each XCD's gathers stay inside its own eighth of the vector (plus the neighbouring planes).
+// XCD-aware row sweep of the two streaming kernels (polynomial step, SpMV): row_sweep.h.
 // Measured at config C (round 3, A/B on one box): the cache-resident vertex level gains 8 % (15.6 -> 14.3 us per step); the
 // fine level and the fp64 SpMV do NOT (262 -> 266 us, 752 -> 771 us: their 1.4x traffic is not cross-XCD duplication of the
 // vector), so the eighths are used between 64 k and 600 k rows only.  TLFEA_XCD_ROWS=0 | 2: never | on every size.
@@ -26,24 +24,8 @@ static int xcd_rows_mode() {
   static const int m = std::getenv("TLFEA_XCD_ROWS") ? std::atoi(std::getenv("TLFEA_XCD_ROWS")) : 1;
   return m;
 }
-struct RowSweep {  // rows of this lane group: i = first, first + stride, ... < end
-  int first, end, stride;
-};
 __device__ __forceinline__ RowSweep row_sweep(int N, int G, int grp, int xcd) {
-  RowSweep r;
-  if (xcd && (gridDim.x & 7) == 0 && N >= 65536 && (xcd == 2 || N <= 600000)) {
-    const int nb = gridDim.x >> 3, lb = blockIdx.x >> 3, x = blockIdx.x & 7;
-    const int per = (((N + 7) >> 3) + G - 1) / G * G;  // an eighth, rounded to whole tiles
-    const int r0 = x * per;
-    r.end = min(N, r0 + per);
-    r.first = r0 + lb * G + grp;
-    r.stride = nb * G;
-  } else {
-    r.first = blockIdx.x * G + grp;
-    r.end = N;
-    r.stride = gridDim.x * G;
-  }
-  return r;
+  return row_sweep_of(N, G, grp, xcd, gridDim.x, blockIdx.x);
 }
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -297,23 +279,40 @@ __global__ __launch_bounds__(1024) void spmv_dir_dot_kernel(int N, Incidence inc
     for (int k = gridDim.x + threadIdx.x; k < kNPart; k += blockDim.x) pq_part[k] = 0.0;
 }
 
+// grid of the 256-thread vector kernels whose partial sums fill the reduction slots: one item per thread and trip
+int slot_grid_256(int n) { return std::max(1, std::min(kNPart, (n + 255) / 256)); }
 int spmv_grid(int N) { return std::max(1, std::min(kNPart, (N + 31) / 32)); }  // small meshes: one row per half-wave
+
+// The instantiation and geometry a launch of N rows takes: what the two launchers below dispatch on, and what the test
+// hook tlfea_newton_cg_trace reports.  The 16-lane and the single-precision instantiations exist without non-temporal loads.
+SpmvForm spmv_form(int N, bool fused, bool nt, bool f32) {
+  static const int lanes_env = std::getenv("TLFEA_SPMV_LANES") ? std::atoi(std::getenv("TLFEA_SPMV_LANES")) : 32;
+  SpmvForm f;
+  f.fused = fused ? 1 : 0;
+  f.lanes = (!f32 && lanes_env == 16) ? 16 : 32;
+  f.nt = (!f32 && f.lanes == 32 && nt) ? 1 : 0;
+  f.tiled = row_map_tiled() ? 1 : 0;
+  f.xcd_mode = xcd_rows_mode();
+  f.grid = spmv_grid(N);
+  f.xcd = (f.tiled && xcd_sweep_taken(N, f.grid, f.xcd_mode)) ? 1 : 0;
+  return f;
+}
 
 void launch_spmv_dir_dot(hipStream_t s, int N, const Incidence& inc, const double* Hval, const double* z,
                          const double* p_old, int first, const double* rz_part_old, const double* rz_part_new,
                          double* p_new, double* q, double* pq_part, bool fused, bool nt, const double* wown) {
-  const dim3 g(spmv_grid(N)), b(1024);
-  const int tiled = (row_map_tiled() ? 1 : 0) | (xcd_rows_mode() << 1);
-  static const int lanes = std::getenv("TLFEA_SPMV_LANES") ? std::atoi(std::getenv("TLFEA_SPMV_LANES")) : 32;
+  const SpmvForm f = spmv_form(N, fused, nt, false);
+  const dim3 g(f.grid), b(1024);
+  const int tiled = f.tiled | (f.xcd_mode << 1);
 #define TLFEA_SPMV(F, T, L)                                                                                       \
   hipLaunchKernelGGL((spmv_dir_dot_kernel<double, F, T, L>), g, b, 0, s, N, inc, Hval, z, p_old, first, rz_part_old,  \
                      rz_part_new, p_new, q, pq_part, tiled, wown)
-  if (lanes == 16) {
-    if (fused) TLFEA_SPMV(true, false, 16);
+  if (f.lanes == 16) {
+    if (f.fused) TLFEA_SPMV(true, false, 16);
     else TLFEA_SPMV(false, false, 16);
-  } else if (fused && nt) TLFEA_SPMV(true, true, 32);
-  else if (fused) TLFEA_SPMV(true, false, 32);
-  else if (nt) TLFEA_SPMV(false, true, 32);
+  } else if (f.fused && f.nt) TLFEA_SPMV(true, true, 32);
+  else if (f.fused) TLFEA_SPMV(true, false, 32);
+  else if (f.nt) TLFEA_SPMV(false, true, 32);
   else TLFEA_SPMV(false, false, 32);
 #undef TLFEA_SPMV
 }
@@ -322,8 +321,9 @@ void launch_spmv_dir_dot(hipStream_t s, int N, const Incidence& inc, const doubl
 void launch_spmv_dir_dot_f32(hipStream_t s, int N, const Incidence& inc, const float* Hval32, const double* z,
                              const double* p_old, int first, const double* rz_part_old, const double* rz_part_new,
                              double* p_new, double* q, double* pq_part, bool fused, const double* wown) {
-  const dim3 g(spmv_grid(N)), b(1024);
-  const int tiled = (row_map_tiled() ? 1 : 0) | (xcd_rows_mode() << 1);
+  const SpmvForm f = spmv_form(N, fused, false, true);
+  const dim3 g(f.grid), b(1024);
+  const int tiled = f.tiled | (f.xcd_mode << 1);
   if (fused)
     hipLaunchKernelGGL((spmv_dir_dot_kernel<float, true, false, 32>), g, b, 0, s, N, inc, Hval32, z, p_old, first,
                        rz_part_old, rz_part_new, p_new, q, pq_part, tiled, wown);
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256) void pcg_update_kernel(int N, const double* __
 void launch_pcg_update(hipStream_t s, int N, const double* Dinv, const double* w, const double* p, const double* q,
                        const double* rz_part_old, const double* pq_part, double* x, double* r, double* z,
                        double* rz_part_new, double* rr_part) {
-  const int n_blocks = std::max(1, std::min(kNPart, (N + 255) / 256));
+  const int n_blocks = slot_grid_256(N);
   hipLaunchKernelGGL(pcg_update_kernel, dim3(n_blocks), dim3(256), 0, s, N, Dinv, w, p, q, rz_part_old, pq_part, x, r,
                      z, rz_part_new, rr_part);
 }
@@ -2086,7 +2086,7 @@ void launch_pcg_update_init32(hipStream_t s, int N, const double* p, const doubl
                               const double* pq_part, double* x, double* r, double* rr_part, double* indefinite,
                               const float* Dinv_f, const double* sc, const double* coef, float* d, float* z,
                               float* res, const double* wown) {
-  const int n_blocks = std::max(1, std::min(kNPart, (N + 255) / 256));
+  const int n_blocks = slot_grid_256(N);
   hipLaunchKernelGGL(pcg_update_init32_kernel, dim3(n_blocks), dim3(256), 0, s, N, p, q, rz_part_old, pq_part, x, r,
                      rr_part, indefinite, Dinv_f, sc, coef, d, z, res, wown);
 }
@@ -2129,7 +2129,7 @@ __global__ __launch_bounds__(256) void residual_replace_init32_kernel(
 void launch_residual_replace_init32(hipStream_t s, int N, const double* b, const double* q, double* r, double* rr_part,
                                     const float* Dinv_f, const double* sc, const double* coef, float* d, float* z,
                                     float* res, const double* wown) {
-  const int n_blocks = std::max(1, std::min(kNPart, (N + 255) / 256));
+  const int n_blocks = slot_grid_256(N);
   hipLaunchKernelGGL(residual_replace_init32_kernel, dim3(n_blocks), dim3(256), 0, s, N, b, q, r, rr_part, Dinv_f, sc, coef,
                      d, z, res, wown);
 }
@@ -2137,7 +2137,7 @@ void launch_residual_replace_init32(hipStream_t s, int N, const double* b, const
 void launch_pcg_update_noz(hipStream_t s, int N, const double* w, const double* p, const double* q,
                            const double* rz_part_old, const double* pq_part, double* x, double* r, double* rr_part,
                            double* indefinite) {
-  const int n_blocks = std::max(1, std::min(kNPart, (3 * N + 255) / 256));
+  const int n_blocks = slot_grid_256(3 * N);
   hipLaunchKernelGGL(pcg_update_noz_kernel, dim3(n_blocks), dim3(256), 0, s, N, w, p, q, rz_part_old, pq_part, x, r,
                      rr_part, indefinite);
 }

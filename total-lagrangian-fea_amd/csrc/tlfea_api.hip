@@ -2370,6 +2370,14 @@ struct tlfea_newton_s {
   const double* cur_b = nullptr; // right-hand side of the running solve (residual replacement)
   long n_replacements = 0;
   long cg_graph_key[6] = {0, 0, 0, 0, 0, 0};
+  // test hook tlfea_newton_cg_trace: while set, pcg() runs exactly `k` iterations without convergence tests and copies the
+  // iterates to the host after its start and after every iteration (cg_trace_record)
+  struct CgTrace {
+    int k = 0;
+    double *vecs = nullptr, *sums = nullptr, *slots = nullptr;  // host: [(k+1)][5][3N], [(k+1)][4], [(k+1)][5][kNPart]
+    int* form = nullptr;                                        // host: kCgTraceForm ints
+  };
+  CgTrace* trace = nullptr;
   bool use_graphs = true;     // TLFEA_GRAPH=0 launches every kernel eagerly
   int last_outer_iters = 0;   // CG iterations of the previous solve: where the next one starts testing convergence
   // ANCF: 12 x 12 node-block scaling of the polynomial's operator (solver_kernels.hip, blk12_*): -1 not decided yet
@@ -5203,6 +5211,50 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
   return 0;
 }
 
+// Test hook tlfea_newton_cg_trace: record `rec` (0: after launch_pcg_init, j: after iteration j - 1) of the running solve.
+// Drains the stream and copies x, r, z, the direction of this iteration (d_p_now: whichever of d_p / d_p2 holds it; null
+// before the first iteration) and q, the device's own totals of the slot arrays r.z (both parities), p.q and r.r, and the
+// raw slot arrays (r.z even, r.z odd, p.q, r.r, b.b).
+constexpr int kCgTraceForm = 24;
+static int cg_trace_record(tlfea_newton_t s, int rec, const double* d_x, const double* d_p_now) {
+  auto& tr = *s->trace;
+  const size_t n = 3 * (size_t)s->N;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  double* v = tr.vecs + (size_t)rec * 5 * n;
+  const double* src[5] = {d_x, s->d_r, s->d_zv, d_p_now, d_p_now ? s->d_q : nullptr};
+  for (int k = 0; k < 5; k++) {
+    if (src[k]) D2H(v + k * n, src[k], n);
+    else std::fill(v + k * n, v + (k + 1) * n, 0.0);
+  }
+  for (int k = 0; k < 4; k++) {
+    launch_sum_parts(s->stream, part(s, k), s->d_scal);
+    TRY(fetch_scalar(s, s->d_scal, tr.sums + 4 * (size_t)rec + k));
+  }
+  D2H(tr.slots + (size_t)rec * 5 * kNPart, s->d_parts, (size_t)5 * kNPart);  // the five arrays pcg() zeroes; the sixth is scratch
+  return 0;
+}
+// ... and what the iterations of this solve launch, from the expressions the launchers themselves evaluate:
+// [0] fused [1] lanes [2] non-temporal [3] tiled [4] XCD eighths taken [5] grid of the product [6] graphs replayed
+// [7] mixed-precision iteration [8] bit j: iteration j ended with a residual replacement [9] update kernel (0 block-Jacobi
+// pcg_update, 1 pcg_update_noz, 2 pcg_update_init32) [10] matrix-free product [11] polynomial degree [12] preconditioner
+// [13] bits of the polynomial's matrix [14] 12 x 12 node blocks [15] grid of the update kernel [16] lanes, [17] grid and
+// [18] XCD eighths of the fp64 product of a residual replacement [19] TLFEA_XCD_ROWS mode
+static void cg_trace_form(tlfea_newton_t s, bool fused, int deg, bool graphs) {
+  int* f = s->trace->form;
+  const int N = s->N;
+  const SpmvForm sf = spmv_form(N, fused, s->spmv_nt, s->spmv32_now), rf = spmv_form(N, false, s->spmv_nt, false);
+  const bool fuse_init = deg > 1 && cheb_bits_eff(s) != 64 && !s->ar && !blk12_now(s);  // as enqueue_cg_iteration_impl
+  f[0] = sf.fused; f[1] = sf.lanes; f[2] = sf.nt; f[3] = sf.tiled; f[4] = sf.xcd; f[5] = sf.grid;
+  f[6] = graphs ? 1 : 0;
+  f[7] = s->spmv32_now ? 1 : 0;
+  f[9] = deg > 1 ? (fuse_init ? 2 : 1) : 0;
+  f[10] = s->mf.now ? 1 : 0;
+  f[11] = deg; f[12] = deg > 1 ? precond_eff(s) : 0; f[13] = cheb_bits_eff(s); f[14] = blk12_now(s) ? 1 : 0;
+  f[15] = slot_grid_256(f[9] == 1 ? 3 * N : N);
+  f[16] = rf.lanes; f[17] = rf.grid; f[18] = rf.xcd; f[19] = sf.xcd_mode;
+}
+
 // Solve H x = b on the device (b, x device vectors of 3N).  Standard PCG, block-Jacobi.
 static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out) {
   s->mf.now = false;
@@ -5228,6 +5280,7 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
   launch_sum_parts(s->stream, part(s, 4), s->d_scal + 1);
   double bb = 0.0;
   TRY(fetch_scalar(s, s->d_scal + 1, &bb));
+  if (s->trace) TRY(cg_trace_record(s, 0, d_x, nullptr));
   if (lp && blk12_now(s)) {  // the stream is drained: the flag of this solve's node-block factorisation is final
     int bad = 0;
     HIP_TRY(hipMemcpy(&bad, s->d_blk12_err, sizeof(int), hipMemcpyDeviceToHost));
@@ -5333,7 +5386,13 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
           s->n_replacements += replace ? 1 : 0;
         }
         it++;
-        if ((it >= first_check && (it - first_check) % check_every == 0) || it == s->lin.max_iter || it == stall_check) {
+        if (s->trace) {  // the hook's max_iter is its k: no test before the last iteration
+          if (it == 1) cg_trace_form(s, fused, deg, graphs);
+          if (replace) s->trace->form[8] |= 1 << (it - 1);
+          TRY(cg_trace_record(s, it, d_x, fused ? (((it - 1) & 1) ? s->d_p : s->d_p2) : s->d_p));
+        }
+        if ((!s->trace && it >= first_check && (it - first_check) % check_every == 0) || it == s->lin.max_iter ||
+            (!s->trace && it == stall_check)) {
           if (s->halo.on) TRY(parts_sum(s, part(s, 3)));  // the r.r slots are summed over ranks only when tested
           launch_sum_parts(s->stream, part(s, 3), s->d_scal + 2);
           TRY(fetch_scalar2(s, s->d_scal + 2, &rr, &indefinite));  // ||r||^2 and the r.z < 0 flag
@@ -5640,6 +5699,35 @@ extern "C" int tlfea_newton_linear_solve(tlfea_newton_t s, const double* b, doub
   HIP_TRY(hipMemcpy(s->d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
   TRY(pcg(s, s->d_b, s->d_dv, iters, rel_res));
   D2H(x, s->d_dv, n);
+  return 0;
+}
+
+// Test hook (tests/test_gpu_cg_trace.py): the solver's own iterative solve of H x = b for exactly k <= 8 iterations -- pcg()
+// itself with max_iter = k and no convergence test before the last iteration -- with every iterate copied out on the way
+// (cg_trace_record, cg_trace_form).  The warm state is left as that solve leaves it.
+extern "C" int tlfea_newton_cg_trace(tlfea_newton_t s, const double* b, int k, double* vecs, double* sums, double* slots,
+                                     int* form) {
+  if (!s || !b || !vecs || !sums || !slots || !form) return fail("tlfea_newton_cg_trace: null argument");
+  if (k < 1 || k > 8) return fail("tlfea_newton_cg_trace: k must be 1..8");
+  if (!s->d_H) return fail("tlfea_newton_cg_trace: no assembled H");
+  if (dist_on(s)) return fail("tlfea_newton_cg_trace: not available on a partitioned mesh (set_interface / set_halo is active)");
+  if (s->lin.method == 1) return fail("tlfea_newton_cg_trace: method = 1 (sparse direct) has no iteration");
+  const size_t n = 3 * (size_t)s->N;
+  HIP_TRY(hipMemcpy(s->d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
+  tlfea_newton_s::CgTrace tr;
+  tr.k = k; tr.vecs = vecs; tr.sums = sums; tr.slots = slots; tr.form = form;
+  std::fill(form, form + kCgTraceForm, 0);
+  const auto lin = s->lin;
+  s->lin.max_iter = k;
+  s->lin.on_unconverged = 1;  // k iterations are not meant to converge
+  s->trace = &tr;
+  int its = 0;
+  double rel = 0.0;
+  const int rc = pcg(s, s->d_b, s->d_dv, &its, &rel);
+  s->trace = nullptr;
+  s->lin = lin;
+  if (rc) return rc;
+  if (its != k) return fail("tlfea_newton_cg_trace: the solve ended after " + std::to_string(its) + " of " + std::to_string(k) + " iterations");
   return 0;
 }
 

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "c32_geometry.h"
+#include "row_sweep.h"
 #include "mf_host.h"
 
 namespace tlfea {
@@ -214,6 +215,13 @@ void launch_pcg_init(hipStream_t s, int N, const double* b, const double* Dinv, 
 void launch_spmv_dir_dot(hipStream_t s, int N, const Incidence& inc, const double* Hval, const double* z,
                          const double* p_old, int first, const double* rz_part_old, const double* rz_part_new,
                          double* p_new, double* q, double* pq_part, bool fused, bool nt, const double* wown = nullptr);
+// what a launch of the CG's product kernel on N rows is: instantiation (fused direction update, lanes per row,
+// non-temporal loads) and geometry (tiled sweep, TLFEA_XCD_ROWS mode, XCD eighths taken -- row_sweep.h -- and grid)
+struct SpmvForm {
+  int fused = 0, lanes = 32, nt = 0, tiled = 1, xcd_mode = 1, xcd = 0, grid = 1;
+};
+SpmvForm spmv_form(int N, bool fused, bool nt, bool f32);
+int slot_grid_256(int n);  // workgroups of the 256-thread update kernels over n items
 void launch_pcg_direction(hipStream_t s, int n, const double* z, int first, const double* rz_part_old,
                           const double* rz_part_new, double* p);
 void launch_pcg_update(hipStream_t s, int N, const double* Dinv, const double* w, const double* p, const double* q,

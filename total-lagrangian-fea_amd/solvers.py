@@ -202,6 +202,25 @@ class SyncedNewtonSolver:
                    hook_lam=(do[4], do[5], do[6]))
         return out
 
+    CG_TRACE_FORM = ("fused", "lanes", "nt", "tiled", "xcd", "grid", "graphs", "spmv32", "replaced_mask", "update", "matfree",
+                     "degree", "precond", "bits", "block12", "update_grid", "replace_lanes", "replace_grid", "replace_xcd",
+                     "xcd_mode")
+
+    def CGTrace(self, b, k):
+        """The solver's own iterative solve of H x = b for exactly k <= 8 iterations with every iterate copied out (test
+        hook).  Returns dict(x, r, z, p, q [k+1, 3N]; sums [k+1, 4] the device's totals of the slot arrays r.z (even / odd
+        iterations), p.q, r.r; slots [k+1, 5, 512] the raw slot arrays; form: what ran, see tlfea_newton_cg_trace).  Record
+        0 is the start, record j follows iteration j - 1; p and q are those of the iteration just run."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        n, k = 3 * self.n_coef, int(k)
+        assert b.shape == (n,) and 1 <= k <= 8
+        vecs, sums, slots = np.zeros((k + 1, 5, n)), np.zeros((k + 1, 4)), np.zeros((k + 1, 5, 512))
+        form = np.zeros(24, dtype=np.int32)
+        check(self._lib.tlfea_newton_cg_trace(self._h, dp(b), k, dp(vecs), dp(sums), dp(slots), ip(form)))
+        out = {nm: vecs[:, j, :].copy() for j, nm in enumerate(("x", "r", "z", "p", "q"))}
+        out.update(sums=sums, slots=slots, form=dict(zip(self.CG_TRACE_FORM, (int(v) for v in form))))
+        return out
+
     def GetPmgLevel3Info(self):
         """(aggregates, 3x3 blocks, polynomial degree) of the third level, (0, 0, 0) when the cycle has two levels"""
         na, nnz, deg = C.c_int(), C.c_int(), C.c_int()
