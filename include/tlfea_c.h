@@ -474,6 +474,10 @@ int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double *x, double
 /* which product the CG iterations of the last linear solve used: 0 = CSR kernel, 1 = matrix-free pair
  * (TLFEA_SPMV_MATFREE=0|1 forces it off / on where eligible; default: eligible and at least 150 000 nodes) */
 int tlfea_newton_get_spmv_mode(tlfea_newton_t s);
+/* row form of the matrix-free pair once it has run: returns 1 where a wavefront of 64 elements sums its rows per node
+ * before storing them (TLFEA_MATFREE_COMPACT, default 1), 0 for one row per (element, local node), -1 before the first
+ * product.  rows = rows of the buffer, ratio = 10 E / rows (1 for the element form); either may be null. */
+int tlfea_newton_get_matfree_rows(tlfea_newton_t s, long long *rows, double *ratio);
 /* One full Newton iteration without the convergence test (gradient, assembly, solve, update):
  * the unit bench.py times.  iters = PCG iterations used. */
 int tlfea_newton_iteration(tlfea_newton_t s, double *norm_g, int *iters);

@@ -2134,24 +2134,56 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
 //   y_vertex n   = (4/3 P_n - 1/3 SP) g_n
 //   y_edge (a,b) = (P_0 + 2/3 SP) (g_a + g_b) + 4/3 (P_b g_a + P_a g_b)
 // ------------------------------------------------------------------------------------------------
+// CP (compact rows, matfree_compact.h): instead of one row per (element, local node), the wavefront parks its 640 rows in
+// LDS, sums them per node in the list order of the host builder (ascending element) and stores one row per unique node:
+// ybuf [rows][3], rows of wavefront w from cp.row_off[w].  No atomics: the order is the list's.
 namespace {
 constexpr int kMfG = 18;            // doubles per staged g record (16 + pad: 144 bytes, own-record reads spread over the banks)
 constexpr int kMfLds = 64 * kMfG;   // doubles of wave-private LDS (g records, then 64 x 10 of F per point, then 64 x 3 rows)
+// compact form: [0, 1920) the 640 parked rows (over the g / F staging), [1920, 2112) 64 summed rows on their way out,
+// then 640 source entries and 640 descriptors of 16 bits: 19 456 bytes per wavefront, 4 workgroups in a CU's 160 KB
+constexpr int kMfcRows = 3 * kMfcSrc, kMfcOut = 3 * 64;
+constexpr int kMfLdsCp = kMfcRows + kMfcOut + 2 * kMfcSrc / 4;
+static_assert(4 * 2 * kMfLdsCp * 8 <= 160 * 1024, "four workgroups of tangent_apply_affine_kernel<true> per CU");
 }  // namespace
 
+template <bool CP>
 __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int Epad, const int* __restrict__ conn,
                                                                   const double* __restrict__ gvec,
                                                                   const double* __restrict__ Fq16, MatfreeCoef mc,
                                                                   const double* __restrict__ p,
-                                                                  double* __restrict__ ybuf) {
-  __shared__ __attribute__((aligned(16))) double st_all[2 * kMfLds];
-  double* st = st_all + (threadIdx.x >> 6) * kMfLds;  // this wavefront's slice
+                                                                  double* __restrict__ ybuf, MatfreeCompact cp) {
+  constexpr int kLds = CP ? kMfLdsCp : kMfLds;
+  __shared__ __attribute__((aligned(16))) double st_all[2 * kLds];
+  double* st = st_all + (threadIdx.x >> 6) * kLds;  // this wavefront's slice
   double2* st2 = reinterpret_cast<double2*>(st);
   const int lane = threadIdx.x & 63;
   const int e0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);  // first element of this wavefront
   const int last = E - 1;
   // lanes past the end stay for the transposes (every read is clamped to the last element, the stores stay inside Epad)
   const int e = min(blockIdx.x * blockDim.x + threadIdx.x, last);
+
+  // ---- compact form: this wavefront's source list and row descriptors into LDS, long before the reduction reads them ---
+  int row0 = 0, n_rows = 0;
+  if (CP && e0 < E) {
+    const int w = e0 >> 6;
+    row0 = cp.row_off[w];
+    n_rows = cp.row_off[w + 1] - row0;
+    unsigned* lst = reinterpret_cast<unsigned*>(st + kMfcRows + kMfcOut);  // 320 words of sources, 320 of descriptors
+    const unsigned* gs = reinterpret_cast<const unsigned*>(cp.src) + (size_t)w * (kMfcSrc / 2);
+    const unsigned* gd = reinterpret_cast<const unsigned*>(cp.desc) + (size_t)w * (kMfcSrc / 2);
+    unsigned vs[5], vd[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      vs[j] = gs[lane + 64 * j];
+      vd[j] = 2 * (lane + 64 * j) < n_rows ? gd[lane + 64 * j] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      lst[lane + 64 * j] = vs[j];
+      lst[kMfcSrc / 2 + lane + 64 * j] = vd[j];
+    }
+  }
 
   // ---- g records: 64 x 128 contiguous bytes, whole-line loads, each lane takes its own record from LDS ---------------
   {
@@ -2315,6 +2347,14 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
       for (int q = 0; q < kNQ; q++) mr += mc.Nq[q][a] * Wm[q][i];
       y[i] += mr;
     }
+    if (CP) {  // parked: row a * 64 + lane (the F records of the last point have been read: the barrier before a = 0)
+      if (a == 0) wave_sync();
+      double* r = st + 3 * (a * 64 + lane);
+      r[0] = y[0];
+      r[1] = y[1];
+      r[2] = y[2];
+      continue;
+    }
     wave_sync();
     st[3 * lane] = y[0];
     st[3 * lane + 1] = y[1];
@@ -2326,16 +2366,51 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
       if (lane < 32) out[64 + lane] = st2[64 + lane];
     }
   }
+  if (!CP) return;
+
+  // ---- compact rows out: lane s sums the sources of row s in list order, 64 rows leave as 1 536 contiguous bytes --------
+  wave_sync();
+  const unsigned short* lsrc = reinterpret_cast<const unsigned short*>(st + kMfcRows + kMfcOut);
+  const unsigned short* ldesc = lsrc + kMfcSrc;
+  double* outp = st + kMfcRows;
+  for (int s0 = 0; s0 < n_rows; s0 += 64) {
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+    if (s0 + lane < n_rows) {
+      const int dsc = ldesc[s0 + lane], k0 = dsc & ((1 << kMfcStartBits) - 1), k1 = k0 + (dsc >> kMfcStartBits) + 1;
+      for (int k = k0; k < k1; k++) {
+        const double* r = st + 3 * (int)lsrc[k];
+        r0 += r[0];
+        r1 += r[1];
+        r2 += r[2];
+      }
+    }
+    wave_sync();  // the previous 64 rows have left
+    outp[3 * lane] = r0;
+    outp[3 * lane + 1] = r1;
+    outp[3 * lane + 2] = r2;
+    wave_sync();
+    const int nd = 3 * min(64, n_rows - s0);
+    double* dst = ybuf + 3 * ((size_t)row0 + s0);
+#pragma unroll
+    for (int t = 0; t < 3; t++)
+      if (lane + 64 * t < nd) dst[lane + 64 * t] = outp[lane + 64 * t];
+  }
 }
 
 void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineView& av, const double* Fq16,
-                                 const MatfreeCoef& mc, const double* p, double* ybuf) {
-  hipLaunchKernelGGL(tangent_apply_affine_kernel, dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn, av.gvec, Fq16,
-                     mc, p, ybuf);
+                                 const MatfreeCoef& mc, const double* p, double* ybuf, const MatfreeCompact* cp) {
+  if (cp)
+    hipLaunchKernelGGL(tangent_apply_affine_kernel<true>, dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
+                       av.gvec, Fq16, mc, p, ybuf, *cp);
+  else
+    hipLaunchKernelGGL(tangent_apply_affine_kernel<false>, dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
+                       av.gvec, Fq16, mc, p, ybuf, MatfreeCompact{});
 }
 
 // q = sum of the node's element rows (+ h^2 rho p on pinned rows, as the "rows out" phase of assemble_affine_kernel adds
 // it), and the p.q partial slots.  Workgroups own contiguous chunks of nodes and there are at most kNPart of them.
+// CP: the node's rows are the compact rows inc.n2e lists (n2r of matfree_compact.h), ascending wavefront.
+template <bool CP>
 __global__ __launch_bounds__(1024) void matfree_gather_kernel(int N, int Epad, Incidence inc, const double* __restrict__ ybuf,
                                                              const double* __restrict__ p, const int* __restrict__ fixed_slot,
                                                              const double* __restrict__ nw, double penalty,
@@ -2349,7 +2424,7 @@ __global__ __launch_bounds__(1024) void matfree_gather_kernel(int N, int Epad, I
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
     for (int k = inc.n2e_off[i] + l8; k < inc.n2e_off[i + 1]; k += 8) {
       const int code = inc.n2e[k], e = code / kNN, la = code - kNN * e;
-      const double* r = ybuf + ((size_t)la * Epad + e) * 3;
+      const double* r = CP ? ybuf + (size_t)code * 3 : ybuf + ((size_t)la * Epad + e) * 3;
       a0 += r[0];
       a1 += r[1];
       a2 += r[2];
@@ -2384,10 +2459,18 @@ __global__ __launch_bounds__(1024) void matfree_gather_kernel(int N, int Epad, I
 }
 
 void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc, const double* ybuf, const double* p,
-                           const int* fixed_slot, const double* nw, double penalty, double* q, double* pq_part) {
+                           const int* fixed_slot, const double* nw, double penalty, double* q, double* pq_part,
+                           const MatfreeCompact* cp) {
   const int grid = std::max(1, std::min(kNPart, (N + 127) / 128));
-  hipLaunchKernelGGL(matfree_gather_kernel, dim3(grid), dim3(1024), 0, s, N, Epad, inc, ybuf, p, fixed_slot, nw, penalty, q,
-                     pq_part);
+  if (cp) {
+    Incidence rows = inc;
+    rows.n2e_off = cp->n2r_off;
+    rows.n2e = cp->n2r;
+    hipLaunchKernelGGL(matfree_gather_kernel<true>, dim3(grid), dim3(1024), 0, s, N, Epad, rows, ybuf, p, fixed_slot, nw,
+                       penalty, q, pq_part);
+  } else
+    hipLaunchKernelGGL(matfree_gather_kernel<false>, dim3(grid), dim3(1024), 0, s, N, Epad, inc, ybuf, p, fixed_slot, nw,
+                       penalty, q, pq_part);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -2327,8 +2327,14 @@ struct tlfea_newton_s {
     MatfreeCoef mc{};
     const int* fixed = nullptr;  // pinned rows of the assembled H (null: none)
     double penalty = 0.0;
-    double* d_ybuf = nullptr;    // [10][Epad][3] element rows, allocated on first use
-    bool now = false;            // the running / last solve takes the matrix-free product
+    double* d_ybuf = nullptr;    // [10][Epad][3] element rows, allocated on first use; compact form: [rows][3]
+    // compact form (matfree_compact.h, TLFEA_MATFREE_COMPACT): the lists, built and uploaded with d_ybuf
+    bool compact = false;
+    MatfreeCompact cp{nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* d_cp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    long cp_rows = 0;
+    double cp_ratio = 0.0;       // 10 E / rows
+    bool now = false;           // the running / last solve takes the matrix-free product
     int last_mode = 0;           // tlfea_newton_get_spmv_mode
   } mf;
   // sparse direct solve (lin.method == 1): rocSOLVER re-factorisation on a host-computed ordering + factor pattern
@@ -2512,6 +2518,8 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
   if (s->d_Fq) (void)hipFree(s->d_Fq);
   if (s->d_mbuf) (void)hipFree(s->d_mbuf);
   if (s->mf.d_ybuf) (void)hipFree(s->mf.d_ybuf);
+  for (void* p : s->mf.d_cp)
+    if (p) (void)hipFree(p);
   direct_destroy(s);
   for (auto& e : s->ev)
     if (e) (void)hipEventDestroy(e);
@@ -3649,17 +3657,51 @@ static bool matfree_chosen(tlfea_newton_t s) {
   if (matfree_env() == 0 || !matfree_eligible(s)) return false;
   return matfree_env() == 1 || s->N >= kMatfreeMinRows;
 }
-// the element rows' buffer (233 MB at config C): on first use, and outside any stream capture
+// TLFEA_MATFREE_COMPACT: 1 (default) = a wavefront sums its element rows per node before they are stored
+// (matfree_compact.h), 0 = one row per (element, local node) in [10][Epad][3].  Read once per process.
+static bool matfree_compact_env() {
+  static const bool on = !std::getenv("TLFEA_MATFREE_COMPACT") || std::atoi(std::getenv("TLFEA_MATFREE_COMPACT")) != 0;
+  return on;
+}
+// the element rows' buffer (233 MB at config C, 75 MB in the compact form) and the compact form's lists: on first use,
+// and outside any stream capture
 static int matfree_ensure_buffer(tlfea_newton_t s) {
-  if (s->mf.d_ybuf) return 0;
-  return dmalloc(&s->mf.d_ybuf, (size_t)s->d->Epad * 3 * kNN);
+  auto& f = s->mf;
+  if (f.d_ybuf) return 0;
+  tlfea_t10_t d = s->d;
+  if (!matfree_compact_env()) return dmalloc(&f.d_ybuf, (size_t)d->Epad * 3 * kNN);
+  MatfreeCompactHost h;
+  if (!build_matfree_compact(s->N, d->E, d->h_conn.data(), h)) return fail("matrix-free product: malformed connectivity");
+  int *d_row_off = nullptr, *d_n2r_off = nullptr, *d_n2r = nullptr;
+  unsigned short *d_src = nullptr, *d_desc = nullptr;
+  TRY(dmalloc(&d_row_off, h.row_off.size()));
+  f.d_cp[0] = d_row_off;
+  TRY(dmalloc(&d_src, h.src.size()));
+  f.d_cp[1] = d_src;
+  TRY(dmalloc(&d_desc, h.desc.size()));
+  f.d_cp[2] = d_desc;
+  TRY(dmalloc(&d_n2r_off, h.n2r_off.size()));
+  f.d_cp[3] = d_n2r_off;
+  TRY(dmalloc(&d_n2r, h.n2r.size()));
+  f.d_cp[4] = d_n2r;
+  HIP_TRY(hipMemcpy(d_row_off, h.row_off.data(), h.row_off.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_src, h.src.data(), h.src.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_desc, h.desc.data(), h.desc.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_n2r_off, h.n2r_off.data(), h.n2r_off.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_n2r, h.n2r.data(), h.n2r.size() * sizeof(int), hipMemcpyHostToDevice));
+  f.cp = MatfreeCompact{d_row_off, d_src, d_desc, d_n2r_off, d_n2r};
+  f.cp_rows = h.rows();
+  f.cp_ratio = h.ratio(d->E);
+  f.compact = true;
+  return dmalloc(&f.d_ybuf, (size_t)f.cp_rows * 3);
 }
 // q = H p and the p.q slots from the element records (p as pcg_direction_kernel left it)
 static int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part) {
   tlfea_t10_t d = s->d;
   auto& f = s->mf;
-  launch_tangent_apply_affine(s->stream, d->view(), s->av, s->d_Fq, f.mc, p, f.d_ybuf);
-  launch_matfree_gather(s->stream, s->N, d->Epad, d->inc(), f.d_ybuf, p, f.fixed, s->d_nw, f.penalty, q, pq_part);
+  const MatfreeCompact* cp = f.compact ? &f.cp : nullptr;
+  launch_tangent_apply_affine(s->stream, d->view(), s->av, s->d_Fq, f.mc, p, f.d_ybuf, cp);
+  launch_matfree_gather(s->stream, s->N, d->Epad, d->inc(), f.d_ybuf, p, f.fixed, s->d_nw, f.penalty, q, pq_part, cp);
   return 0;
 }
 
@@ -4878,7 +4920,7 @@ static void cg_graphs_destroy(tlfea_newton_t s) {
 // path calls back into the host between kernels).
 static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg, int bits) {
   const long key[6] = {deg + 1000 * precond_eff(s) + 100000L * (s->pmg.ok ? pmg_coarse_degree_eff(s) : 0),
-                       bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0) +
+                       bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0) + (s->mf.now && s->mf.compact ? 800000L : 0) +
                            (pmg_rop_now(s) ? 400000L : 0),
                        (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
                        (long)(size_t)s->d_B8, (long)(size_t)s->pmg.vertex.d_B8};
@@ -5841,6 +5883,12 @@ extern "C" int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double
   return 0;
 }
 extern "C" int tlfea_newton_get_spmv_mode(tlfea_newton_t s) { return s ? s->mf.last_mode : -1; }
+extern "C" int tlfea_newton_get_matfree_rows(tlfea_newton_t s, long long* rows, double* ratio) {
+  if (!s || !s->mf.d_ybuf) return -1;
+  if (rows) *rows = s->mf.compact ? s->mf.cp_rows : (long long)kNN * s->d->E;
+  if (ratio) *ratio = s->mf.compact ? s->mf.cp_ratio : 1.0;
+  return s->mf.compact ? 1 : 0;
+}
 
 // ---- modal analysis: the lowest pairs of K phi = omega^2 M phi by LOBPCG on the shifted pencil ------------
 // A = K + sigma M is H / h assembled with h = 1 / sqrt(sigma), so the iteration runs on the pencil (H, M) itself:

@@ -10,6 +10,7 @@
 #include "c32_geometry.h"
 #include "row_sweep.h"
 #include "mf_host.h"
+#include "matfree_compact.h"
 
 namespace tlfea {
 
@@ -167,12 +168,22 @@ struct MatfreeCoef {
   double rho_inv_h;         // density of the assembled mass matrix / h (0: none)
   double Nq[kNQ][kNN], mw[kNQ];
 };
-// element rows of H p: ybuf [10][Epad][3]; Fq16 = the [E][5][10] records H was assembled from
+// Device lists of the compact row form (matfree_compact.h): a wavefront of 64 elements sums its rows per node first
+struct MatfreeCompact {
+  const int* row_off;           // [W + 1] first compact row of wavefront w
+  const unsigned short* src;    // [W][640] LDS rows a * 64 + lane, grouped by compact row
+  const unsigned short* desc;   // [W][640] start | (count - 1) << 10 per compact row of the wavefront
+  const int* n2r_off;           // [N + 1]
+  const int* n2r;               // [rows] compact rows of a node, ascending
+};
+// element rows of H p: ybuf [10][Epad][3], or with cp one row per (wavefront, node): ybuf [rows][3]; Fq16 = the
+// [E][5][10] records H was assembled from
 void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineView& av, const double* Fq16,
-                                 const MatfreeCoef& mc, const double* p, double* ybuf);
+                                 const MatfreeCoef& mc, const double* p, double* ybuf, const MatfreeCompact* cp = nullptr);
 // q = node-owner sum of the element rows (+ penalty x nw x p on pinned rows), p.q partials into the kNPart slots
 void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc, const double* ybuf, const double* p,
-                           const int* fixed_slot, const double* nw, double penalty, double* q, double* pq_part);
+                           const int* fixed_slot, const double* nw, double penalty, double* q, double* pq_part,
+                           const MatfreeCompact* cp = nullptr);
 void launch_tangent_blocks(hipStream_t s, const ElemView& m, const Material& mat, double h,
                            double* Kbuf /*[E][55][9]*/, const double* emat = nullptr);
 void launch_assemble_rows(hipStream_t s, int N, int S, int maxdeg, const Incidence& inc, const double* Kbuf,

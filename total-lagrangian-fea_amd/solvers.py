@@ -349,6 +349,13 @@ class SyncedNewtonSolver:
         """product of the last solve's CG iterations: 0 CSR kernel, 1 matrix-free pair"""
         return int(self._lib.tlfea_newton_get_spmv_mode(self._h))
 
+    def GetMatfreeRows(self):
+        """(form, rows, ratio) of the matrix-free pair's row buffer: form 1 = summed per wavefront and node, 0 = one row per
+        (element, local node), -1 = the pair has not run; ratio = 10 E / rows"""
+        rows, ratio = C.c_longlong(), C.c_double()
+        form = int(self._lib.tlfea_newton_get_matfree_rows(self._h, C.byref(rows), C.byref(ratio)))
+        return form, int(rows.value), float(ratio.value)
+
     def NewtonIteration(self):
         ng, it = C.c_double(), C.c_int()
         check(self._lib.tlfea_newton_iteration(self._h, C.byref(ng), C.byref(it)))
