@@ -466,6 +466,43 @@ int tlfea_newton_modal_apply_block(tlfea_newton_t s, int which, int m, const dou
 int tlfea_newton_modal_gram(tlfea_newton_t s, int p, int q, const double *X, const double *Y, double *G);
 /* mean ms of one block product Y = H X with m columns over `reps` launches (hipEvents; tools/modal_timing.py) */
 int tlfea_newton_modal_time_spmm(tlfea_newton_t s, int m, int reps, double *ms_out);
+/* ---- adjoint sensitivities of the implicit step (no reference counterpart) ---------------
+ * One tlfea_newton_solve with max_outer = 1 finds v with g(v) = 0, x = x_prev + h v, then lambda_new = lambda + rho (J x - t)
+ * and v_prev_new = v.  Given the cotangents x_bar, v_bar [3N] and lam_bar [n_constraints] of the outputs x, v, lambda_new
+ * (NULL = zero), the adjoint step solves  H w = v_bar + h (x_bar + rho J^T lam_bar)  with the H of the current positions
+ * and the solver's own tlfea_linsolve_opts (iterative or method = 1) and returns the cotangents of the step's inputs:
+ *   f_ext_bar [3N] = w, v_prev_bar [3N] = M w / h, x_prev_bar [3N], lam_in_bar and t_bar [n_constraints] (t: the targets of
+ *   fixed nodes, in the order 3 slot + component, or the right-hand side of the CSR rows), a_bar [3] (body acceleration),
+ *   per_material [n_mat][P + 1] and per_element [E][P + 1]: the natural stiffness parameters of the model -- SVK
+ *   (lambda, mu), P = 2; Mooney-Rivlin (mu10, mu01, kappa), P = 3 -- then the density.  n_mat = 1 without a table.
+ * Any output may be NULL.  v_prev (NULL = the v_prev the last tlfea_newton_solve started from, which the solver keeps)
+ * enters the density slot only.  All pointers are host pointers in tlfea_newton_adjoint_step and device pointers in
+ * tlfea_newton_adjoint_step_device (a_bar and per_material included).  info[0] = iterations of the solve, rel_res its
+ * ||r|| / ||b||.  The state must be that of a step just solved: positions, v; the call leaves x, v, v_prev, lambda and
+ * the warm-start state of the linear solver as they were and re-assembles H.
+ * Refused (tlfea_last_error says why): an ANCF handle, damping set (uniform or in a table entry), an obstacle with
+ * friction, a follower pressure, a partitioned mesh, no mass matrix, and a last tlfea_newton_solve that ran more than one
+ * outer iteration, failed, or left its Newton loop without meeting inner_atol / inner_rtol. */
+typedef struct {
+  const double *x_bar, *v_bar, *lam_bar, *v_prev;
+} tlfea_adjoint_in;
+typedef struct {
+  double *f_ext_bar, *v_prev_bar, *x_prev_bar, *lam_in_bar, *t_bar, *a_bar, *per_material, *per_element;
+} tlfea_adjoint_out;
+int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_in *in, const tlfea_adjoint_out *out, int *info,
+                              double *rel_res);
+int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in *in, const tlfea_adjoint_out *out, int *info,
+                                     double *rel_res);
+/* 0 when tlfea_newton_adjoint_step would accept the solver's state now, else the refusal (tlfea_last_error) */
+int tlfea_newton_adjoint_ready(tlfea_newton_t s);
+/* The element kernel and its reduction alone, at the current positions: host vectors w, u [3N] (u NULL: density slot 0),
+ * per_element [E][P + 1] and per_material [n_mat][P + 1] as above (either may be NULL). */
+int tlfea_t10_material_sensitivity(tlfea_t10_t h, const double *w, const double *u, double *per_element,
+                                   double *per_material);
+/* n_mat (1 without a table) and P + 1 of the object's model as it is set now */
+int tlfea_t10_material_sensitivity_shape(tlfea_t10_t h, int *n_mat, int *slots);
+/* mean ms over `reps` launches of out[0] the element kernel, [1] its reduction (hipEvents; tools/adjoint_timing.py) */
+int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, double *out_ms2);
 /* The same product from the matrix-free pair of the CG iteration (element records instead of the CSR values),
  * with the records of the last assembly.  Returns an error where that product is not eligible: anything but straight-sided
  * T10 elements with one St.Venant-Kirchhoff material on one GPU, general linear constraints, rigid obstacles, per-element

@@ -169,6 +169,28 @@ def _modal_signatures(lib):
         getattr(lib, name).restype = C.c_int
 
 
+class AdjointInC(C.Structure):  # tlfea_adjoint_in (host or device pointers, by entry point)
+    _fields_ = [(n, C.c_void_p) for n in ("x_bar", "v_bar", "lam_bar", "v_prev")]
+
+
+class AdjointOutC(C.Structure):  # tlfea_adjoint_out
+    _fields_ = [(n, C.c_void_p) for n in ("f_ext_bar", "v_prev_bar", "x_prev_bar", "lam_in_bar", "t_bar", "a_bar",
+                                          "per_material", "per_element")]
+
+
+def _adjoint_signatures(lib):
+    """ctypes signatures of the adjoint-sensitivity entry points."""
+    vp, i = C.c_void_p, C.c_int
+    step = [vp, C.POINTER(AdjointInC), C.POINTER(AdjointOutC), c_ip, c_dp]
+    sig = {"tlfea_newton_adjoint_step": step, "tlfea_newton_adjoint_step_device": step,
+           "tlfea_newton_adjoint_ready": [vp], "tlfea_t10_material_sensitivity": [vp, c_dp, c_dp, c_dp, c_dp],
+           "tlfea_t10_material_sensitivity_shape": [vp, c_ip, c_ip],
+           "tlfea_t10_time_sensitivity_kernels": [vp, i, c_dp]}
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+
+
 def _pmg_signatures(lib):
     """ctypes signatures of the p-multigrid test hooks (the handle must not travel as a C int)."""
     vp = C.c_void_p
@@ -254,6 +276,7 @@ def load_library():
     _stress_signatures(lib)
     _load_signatures(lib)
     _modal_signatures(lib)
+    _adjoint_signatures(lib)
     _pmg_signatures(lib)
     _LIB = lib
     return lib

@@ -151,6 +151,15 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   bool st_valid = false, st_pts_valid = false;  // a calc_stress has run | its point stresses were asked for
   int *d_st_noff = nullptr, *d_st_nel = nullptr;  // ANCF (DESIGN 3f'): elements of every MESH node, ascending (n_nodes + 1 | E nn)
   bool ancf_mass = false;                         // ANCF: d_mval holds an assembled mass matrix (the kinetic energy's condition)
+  // material sensitivities (tlfea_t10_material_sensitivity): allocated on first use.  d_sn_sens [4][Epad],
+  // d_sn_out [n_mat][P + 1]; under a table the ascending element list of every material (d_sn_idx [E], concatenated),
+  // its chunks (d_sn_blk) and the first chunk of every material (d_sn_boff), rebuilt when `gen` has moved on
+  double *d_sn_sens = nullptr, *d_sn_part = nullptr, *d_sn_out = nullptr, *d_sn_w = nullptr, *d_sn_u = nullptr,
+         *d_sn_pe = nullptr;
+  int *d_sn_idx = nullptr, *d_sn_boff = nullptr;
+  int2* d_sn_blk = nullptr;
+  int sn_nb = 0, sn_part_cap = 0, sn_out_cap = 0;
+  long sn_gen = -1;
   // constraints
   double* d_cons = nullptr;
   int *d_fixed = nullptr, *d_fixed_slot = nullptr;
@@ -264,7 +273,8 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_st_vel, h->d_st_noff, h->d_st_nel, h->d_ao_cls, h->d_ao_touched, h->d_ao_sval, h->d_ao_w,
                   h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts, h->d_ld_fc, h->d_ld_tr, h->d_ld_f,
                   h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask, h->d_ld_fnodes, h->d_ld_foff,
-                  h->d_ld_fslot, h->d_fld};
+                  h->d_ld_fslot, h->d_fld, h->d_sn_sens, h->d_sn_part, h->d_sn_out, h->d_sn_w, h->d_sn_u, h->d_sn_pe,
+                  h->d_sn_idx, h->d_sn_boff, h->d_sn_blk};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (double* p : h->d_fld_V)
@@ -2296,6 +2306,9 @@ struct tlfea_newton_s {
          *d_b = nullptr;
   double *d_step0 = nullptr, *d_lam0 = nullptr;  // v | v_prev and lambda at the start of the running step (roll-back)
   int lam0_cap = 0;
+  // what the last Solve() left for tlfea_newton_adjoint_step: 0 no Solve yet, 1 one outer iteration whose Newton loop met
+  // its tolerance, 2 more than one outer iteration, 3 the step failed, 4 the Newton loop ran out of iterations
+  int adj_state = 0;
   bool profiling = false;  // per-stage hipEvent timing (adds a host sync per stage)
   int pcg_fused = -1;  // -1 auto (fused direction update below 200k nodes), 0/1 forced (TLFEA_PCG_FUSED)
   bool spmv_nt = false; // non-temporal loads of H in the SpMV (TLFEA_SPMV_NT): measured slower at config C
@@ -3630,15 +3643,15 @@ static int fill_mass_term(tlfea_newton_t s, MassTerm& mt) {
   return 0;
 }
 // shape functions at the rule's points (the rule of the mass matrix, FEAT10Data.cu:206-278)
-static void fill_mass_shape(tlfea_newton_t s, MassTerm& mt) {
-  tlfea_t10_t d = s->d;
+static void shape_at_rule_points(tlfea_t10_t d, double Nq[kNQ][kNN]) {
   const int edges[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};  // FEAT10Data.cu:143
   for (int q = 0; q < kNQ; q++) {
     const double L[4] = {1.0 - d->h_q[0][q] - d->h_q[1][q] - d->h_q[2][q], d->h_q[0][q], d->h_q[1][q], d->h_q[2][q]};
-    for (int k = 0; k < 4; k++) mt.Nq[q][k] = L[k] * (2.0 * L[k] - 1.0);
-    for (int k = 0; k < 6; k++) mt.Nq[q][k + 4] = 4.0 * L[edges[k][0]] * L[edges[k][1]];
+    for (int k = 0; k < 4; k++) Nq[q][k] = L[k] * (2.0 * L[k] - 1.0);
+    for (int k = 0; k < 6; k++) Nq[q][k + 4] = 4.0 * L[edges[k][0]] * L[edges[k][1]];
   }
 }
+static void fill_mass_shape(tlfea_newton_t s, MassTerm& mt) { shape_at_rule_points(s->d, mt.Nq); }
 
 // ---- matrix-free product of the CG iteration --------------------------------------------------------------
 // TLFEA_SPMV_MATFREE: 0 never, 1 wherever eligible, unset = eligible and at least kMatfreeMinRows node rows
@@ -6409,9 +6422,11 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
   bool friction_on = false;
   for (int k = 0; k < d->obs.n; k++) friction_on = friction_on || d->obs.o[k].mu > 0.0;
   const int kMaxHalvings = 8;
+  bool inner_met = false;  // the last outer iteration's Newton loop left through its tolerance test
   auto run = [&]() -> int {
     for (int outer = 0; outer < p.max_outer; ++outer) {
       n_outer++;
+      inner_met = false;
       double norm_g0 = -1.0;
       bool g_current = false;
       for (int it = 0; it < p.max_inner; ++it) {
@@ -6419,7 +6434,10 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
         g_current = false;
         if (s->verbose) std::printf("  outer %d newton %d ||g|| = %.6e\n", outer, it, norm_g);
         if (norm_g0 < 0.0) norm_g0 = norm_g;
-        if (norm_g < p.inner_atol || (p.inner_rtol > 0.0 && norm_g0 > 0.0 && norm_g <= p.inner_rtol * norm_g0)) break;
+        if (norm_g < p.inner_atol || (p.inner_rtol > 0.0 && norm_g0 > 0.0 && norm_g <= p.inner_rtol * norm_g0)) {
+          inner_met = true;
+          break;
+        }
         launch_axpy_neg(s->stream, n, s->d_g, s->d_b);                       // r = -g  (:494-502)
         TRY(assemble(s));                                                    // (:1080-1097)
         int iters = 0;
@@ -6474,6 +6492,7 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
     (void)hipStreamSynchronize(s->stream);
     s->stats[0] = n_outer; s->stats[1] = n_newton; s->stats[2] = norm_g; s->stats[3] = norm_c;
     s->stats[4] = pcg_total; s->stats[5] = 0.0;
+    s->adj_state = 3;
     g_err = why;
     return rc_step;
   }
@@ -6483,6 +6502,7 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
   HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
   s->stats[0] = n_outer; s->stats[1] = n_newton; s->stats[2] = norm_g; s->stats[3] = norm_c;
   s->stats[4] = pcg_total; s->stats[5] = ms;
+  s->adj_state = n_outer > 1 ? 2 : (inner_met ? 1 : 4);
   if (s->verbose) std::printf("OneStepNewton kernel time: %.3f ms\n", ms);
   return 0;
 }
@@ -6543,6 +6563,279 @@ extern "C" int tlfea_newton_get_stage_ms(tlfea_newton_t s, double* ms, double* c
 extern "C" int tlfea_newton_begin_step(tlfea_newton_t s) {
   TRY(begin_step(s));
   HIP_TRY(hipMemcpyAsync(s->d_vprev, s->d_v, 3 * (size_t)s->N * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+  return 0;
+}
+
+// =================================================================================================
+// Adjoint sensitivities of the implicit step (adjoint_kernels.hip)
+static int sens_slots(tlfea_t10_t h) { return (h->mat.model == kMooneyRivlin ? 3 : 2) + 1; }
+static int sens_n_mat(tlfea_t10_t h) { return h->d_emat ? h->n_mat : 1; }
+// buffers and, under a material table, the ascending element list of every material with its chunks of kAdjChunk
+static int sens_prepare(tlfea_t10_t h, const char* what) {
+  if (h && h->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, what);
+  if (!h->have_dndu) return fail(std::string(what) + ": CalcDnDuPre must be called first");
+  if (!h->d_sn_sens) TRY(dmalloc(&h->d_sn_sens, (size_t)4 * h->Epad));
+  const int n_mat = sens_n_mat(h);
+  if (n_mat > h->sn_out_cap) {
+    if (h->d_sn_out) (void)hipFree(h->d_sn_out);
+    TRY(dmalloc(&h->d_sn_out, (size_t)n_mat * 4));
+    h->sn_out_cap = n_mat;
+  }
+  int nb = (h->E + kAdjChunk - 1) / kAdjChunk;
+  if (h->d_emat && h->sn_gen != h->gen) {
+    std::vector<int> cnt(n_mat + 1, 0), idx(h->E), boff(n_mat + 1, 0);
+    for (int e = 0; e < h->E; e++) cnt[h->h_eid[e] + 1]++;
+    for (int k = 0; k < n_mat; k++) cnt[k + 1] += cnt[k];
+    std::vector<int> at(cnt.begin(), cnt.end() - 1);
+    for (int e = 0; e < h->E; e++) idx[at[h->h_eid[e]]++] = e;  // ascending inside every material
+    std::vector<int2> blk;
+    for (int k = 0; k < n_mat; k++) {
+      boff[k] = (int)blk.size();
+      for (int a = cnt[k]; a < cnt[k + 1]; a += kAdjChunk) blk.push_back(make_int2(a, std::min(cnt[k + 1], a + kAdjChunk)));
+    }
+    boff[n_mat] = (int)blk.size();
+    HIP_TRY(hipDeviceSynchronize());
+    for (void* p : {(void*)h->d_sn_idx, (void*)h->d_sn_boff, (void*)h->d_sn_blk})
+      if (p) (void)hipFree(p);
+    h->d_sn_idx = h->d_sn_boff = nullptr;
+    h->d_sn_blk = nullptr;
+    TRY(dmalloc(&h->d_sn_idx, idx.size()));
+    TRY(dmalloc(&h->d_sn_boff, boff.size()));
+    TRY(dmalloc(&h->d_sn_blk, blk.size()));
+    HIP_TRY(hipMemcpy(h->d_sn_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_sn_boff, boff.data(), boff.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!blk.empty()) HIP_TRY(hipMemcpy(h->d_sn_blk, blk.data(), blk.size() * sizeof(int2), hipMemcpyHostToDevice));
+    h->sn_nb = (int)blk.size();
+    h->sn_gen = h->gen;
+  }
+  if (h->d_emat) nb = h->sn_nb;
+  const int cap = std::max(nb, (h->N + kAdjChunk - 1) / kAdjChunk);  // the node sums of a_bar share the buffer
+  if (cap > h->sn_part_cap) {
+    if (h->d_sn_part) (void)hipFree(h->d_sn_part);
+    TRY(dmalloc(&h->d_sn_part, (size_t)cap * 4));
+    h->sn_part_cap = cap;
+  }
+  return 0;
+}
+// the two launches after sens_prepare: d_sn_sens from device vectors w, u, then d_sn_out [n_mat][slots]
+static void sens_launch_points(tlfea_t10_t h, hipStream_t st, const double* d_w, const double* d_u) {
+  SensShape sh;
+  shape_at_rule_points(h, sh.Nq);
+  launch_sens_points(st, h->view(), h->mat.model, sh, d_w, d_u, h->d_sn_sens);
+}
+static void sens_launch_sums(tlfea_t10_t h, hipStream_t st) {
+  if (h->d_emat)
+    launch_adj_sums(st, sens_slots(h), h->E, h->sn_nb, h->d_sn_blk, h->d_sn_idx, h->d_sn_sens, (size_t)h->Epad, 1, h->n_mat,
+                    h->d_sn_boff, h->d_sn_part, h->d_sn_out);
+  else
+    launch_adj_sums(st, sens_slots(h), h->E, (h->E + kAdjChunk - 1) / kAdjChunk, nullptr, nullptr, h->d_sn_sens,
+                    (size_t)h->Epad, 1, 1, nullptr, h->d_sn_part, h->d_sn_out);
+}
+
+extern "C" int tlfea_t10_material_sensitivity_shape(tlfea_t10_t h, int* n_mat, int* slots) {
+  if (h && h->kind != kT10) return fail("tlfea_t10_material_sensitivity_shape: T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "tlfea_t10_material_sensitivity_shape");
+  if (n_mat) *n_mat = sens_n_mat(h);
+  if (slots) *slots = sens_slots(h);
+  return 0;
+}
+
+extern "C" int tlfea_t10_material_sensitivity(tlfea_t10_t h, const double* w, const double* u, double* per_element,
+                                              double* per_material) {
+  TRY(sens_prepare(h, "tlfea_t10_material_sensitivity"));
+  if (!w) return fail("tlfea_t10_material_sensitivity: null w");
+  const size_t n = 3 * (size_t)h->N;
+  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
+  if (u && !h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
+  HIP_TRY(hipMemcpy(h->d_sn_w, w, n * sizeof(double), hipMemcpyHostToDevice));
+  if (u) HIP_TRY(hipMemcpy(h->d_sn_u, u, n * sizeof(double), hipMemcpyHostToDevice));
+  const int slots = sens_slots(h);
+  sens_launch_points(h, h->stream, h->d_sn_w, u ? h->d_sn_u : nullptr);
+  sens_launch_sums(h, h->stream);
+  HIP_TRY(hipGetLastError());
+  if (per_element) {
+    if (!h->d_sn_pe) TRY(dmalloc(&h->d_sn_pe, (size_t)h->E * 4));
+    launch_sens_transpose(h->stream, h->E, h->Epad, slots, h->d_sn_sens, h->d_sn_pe);
+    D2H(per_element, h->d_sn_pe, (size_t)h->E * slots);
+  }
+  if (per_material) D2H(per_material, h->d_sn_out, (size_t)sens_n_mat(h) * slots);
+  HIP_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, double* out_ms2) {
+  TRY(sens_prepare(h, "tlfea_t10_time_sensitivity_kernels"));
+  if (!out_ms2) return fail("tlfea_t10_time_sensitivity_kernels: null output");
+  if (reps < 1) reps = 1;
+  const size_t n = 3 * (size_t)h->N;
+  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
+  if (!h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
+  // any finite vectors serve a timing: the positions as w, zeros as u
+  HIP_TRY(hipMemset(h->d_sn_w, 0, n * sizeof(double)));
+  HIP_TRY(hipMemcpy(h->d_sn_w, h->d_x, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice));
+  HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
+  hipEvent_t ev[2];
+  HIP_TRY(hipEventCreate(&ev[0]));
+  HIP_TRY(hipEventCreate(&ev[1]));
+  for (int k = 0; k < 2; k++) {
+    HIP_TRY(hipEventRecord(ev[0], h->stream));
+    for (int r = 0; r < reps; r++) {
+      if (k == 0) sens_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u);
+      else sens_launch_sums(h, h->stream);
+    }
+    HIP_TRY(hipEventRecord(ev[1], h->stream));
+    HIP_TRY(hipEventSynchronize(ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    out_ms2[k] = ms / reps;
+  }
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  return 0;
+}
+
+// why the adjoint step cannot run on the solver's state now (0: it can)
+static int adjoint_refusal(tlfea_newton_t s) {
+  if (!s) return fail("tlfea_newton_adjoint_step: null handle");
+  tlfea_t10_t d = s->d;
+  const std::string w = "tlfea_newton_adjoint_step: ";
+  if (d->kind != kT10) return fail(w + "T10 handles only (not an ANCF handle)");
+  if (d->mat.eta != 0.0 || d->mat.lamd != 0.0 || d->emat_damp)
+    return fail(w + "damping is set (eta / lambda_damp != 0, uniform or in the material table): the viscous stress depends "
+                    "on v and x separately, which the adjoint of the undamped step does not carry");
+  for (int k = 0; k < d->obs.n; k++)
+    if (d->obs.o[k].mu > 0.0)
+      return fail(w + "obstacle " + std::to_string(k) + " has friction: its force depends on the start-of-step positions "
+                      "and its step is line-searched; frictionless obstacles only");
+  if (d->ld_n_press > 0)
+    return fail(w + "a follower pressure is set: its load stiffness is not in H, so H is not the Jacobian of the residual");
+  if (dist_on(s)) return fail(w + "not available on a partitioned mesh (set_interface / set_halo is active)");
+  if (!d->have_dndu || !d->is_csr_setup || !d->d_mval || d->mass_rho0 < 0.0)
+    return fail(w + "needs the mass matrix (CalcDnDuPre, CalcMassMatrix) first");
+  switch (s->adj_state) {
+    case 1: break;
+    case 0: return fail(w + "no Solve() has run: the state must be that of a step just solved");
+    case 2: return fail(w + "the last Solve() ran more than one outer iteration: one differentiated step is one outer "
+                            "iteration (max_outer = 1)");
+    case 3: return fail(w + "the last Solve() failed");
+    default: return fail(w + "the last Solve() left its Newton loop without meeting inner_atol / inner_rtol: H is the "
+                             "Jacobian of the residual at a converged step only");
+  }
+  return 0;
+}
+extern "C" int tlfea_newton_adjoint_ready(tlfea_newton_t s) { return adjoint_refusal(s); }
+
+extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                                                int* info, double* rel_res) {
+  TRY(adjoint_refusal(s));
+  if (!in || !out) return fail("tlfea_newton_adjoint_step: null argument");
+  tlfea_t10_t d = s->d;
+  TRY(sens_prepare(d, "tlfea_newton_adjoint_step"));
+  TRY(tlfea_newton_analyze_hessian_sparsity(s));
+  TRY(sync_constraints(s));
+  const int n = 3 * s->N, nc = s->n_constraints;
+  const double h = s->prm.time_step, rho = s->prm.rho;
+  const double* vprev = in->v_prev ? in->v_prev : (s->d_step0 ? s->d_step0 + n : nullptr);
+  if (!vprev) return fail("tlfea_newton_adjoint_step: no v_prev given and no Solve() has kept one");
+  AdjCons J{0, d->d_fixed, d->d_fixed_slot, d->d_joff, d->d_jcol, d->d_jtoff, d->d_jtcol, d->d_jval, d->d_jtval};
+  J.mode = pinned_on(s) ? 1 : (lincons_on(s) ? 2 : 0);
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  ModalWork wk;
+  double *xt, *vt, *u, *Mw;
+  TRY(wk.alloc(&xt, (size_t)n));
+  TRY(wk.alloc(&vt, (size_t)n));
+  TRY(wk.alloc(&u, (size_t)n));
+  TRY(wk.alloc(&Mw, (size_t)n));
+  // what the call must leave as it found it: the warm-start state of the linear solver (tlfea_newton_modal_solve)
+  LamKeep keep;
+  const double safety0 = s->lam_safety, boost0 = s->pmg.kc_boost, last_rel0 = s->lin_last_rel, worst_rel0 = s->lin_worst_rel;
+  const int outer0 = s->last_outer_iters, deg0 = s->last_deg, bits0 = s->last_bits, mode0 = s->mf.last_mode;
+  const bool last_ok0 = s->lin_last_ok, all_ok0 = s->lin_all_ok;
+  TRY(keep.save(s, wk));  // cold estimates: the result depends on no earlier solve
+  launch_adj_rhs(s->stream, n, J, in->x_bar, in->v_bar, J.mode ? in->lam_bar : nullptr, s->d_v, vprev,
+                 d->ld_have_a ? d->ld_a : zero3, h, rho, xt, vt, u);
+  int it = 0;
+  double rel = 0.0;
+  int rc = assemble(s, /*fq_fresh=*/false);
+  // the solve runs on the Newton iteration's own right-hand side and solution vectors (scratch between Solve() calls), so
+  // the captured CG graphs stay those of the forward step
+  if (!rc && hipMemcpyAsync(s->d_b, vt, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream) != hipSuccess)
+    rc = fail("tlfea_newton_adjoint_step: device copy failed");
+  if (!rc) rc = pcg(s, s->d_b, s->d_dv, &it, &rel);
+  const std::string why = rc ? g_err : std::string();
+  s->lam_safety = safety0;
+  s->pmg.kc_boost = boost0;
+  s->last_outer_iters = outer0; s->last_deg = deg0; s->last_bits = bits0; s->mf.last_mode = mode0;
+  s->lin_last_rel = last_rel0; s->lin_worst_rel = worst_rel0; s->lin_last_ok = last_ok0; s->lin_all_ok = all_ok0;
+  if (rc) {
+    (void)hipStreamSynchronize(s->stream);
+    keep.restore();
+    g_err = why;
+    return rc;
+  }
+  const double* w = s->d_dv;
+  launch_massmm_block(s->stream, s->N, 1, d->d_off, d->d_cols, d->d_mval, w, 1, Mw, 1, nullptr);
+  launch_adj_out(s->stream, n, nc, J, w, Mw, xt, vt, J.mode ? in->lam_bar : nullptr, h, rho, out->f_ext_bar,
+                 out->v_prev_bar, out->x_prev_bar, out->lam_in_bar, out->t_bar);
+  if (J.mode == 0 && nc > 0) {  // constraint terms off: the multipliers pass through
+    for (double* p : {out->lam_in_bar, out->t_bar})
+      if (p) (void)hipMemsetAsync(p, 0, (size_t)nc * sizeof(double), s->stream);
+  }
+  if (out->a_bar)
+    launch_adj_sums(s->stream, 3, s->N, (s->N + kAdjChunk - 1) / kAdjChunk, nullptr, nullptr, Mw, 1, 3, 1, nullptr,
+                    d->d_sn_part, out->a_bar);
+  if (out->per_material || out->per_element) {
+    const int slots = sens_slots(d);
+    sens_launch_points(d, s->stream, w, u);
+    if (out->per_material) {
+      sens_launch_sums(d, s->stream);
+      (void)hipMemcpyAsync(out->per_material, d->d_sn_out, (size_t)sens_n_mat(d) * slots * sizeof(double),
+                           hipMemcpyDeviceToDevice, s->stream);
+    }
+    if (out->per_element) launch_sens_transpose(s->stream, d->E, d->Epad, slots, d->d_sn_sens, out->per_element);
+  }
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s->stream);
+  keep.restore();
+  HIP_TRY(e1);
+  HIP_TRY(e2);
+  if (info) info[0] = it;
+  if (rel_res) *rel_res = rel;
+  return 0;
+}
+
+extern "C" int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                                         int* info, double* rel_res) {
+  TRY(adjoint_refusal(s));
+  if (!in || !out) return fail("tlfea_newton_adjoint_step: null argument");
+  tlfea_t10_t d = s->d;
+  const size_t n = 3 * (size_t)s->N, nc = (size_t)s->n_constraints;
+  const size_t n_pm = (size_t)sens_n_mat(d) * sens_slots(d), n_pe = (size_t)d->E * sens_slots(d);
+  ModalWork wk;
+  tlfea_adjoint_in din{nullptr, nullptr, nullptr, nullptr};
+  tlfea_adjoint_out dout{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto up = [&](const double* src, size_t cnt, const double** dst) -> int {
+    if (!src || cnt == 0) return 0;
+    double* p;
+    TRY(wk.alloc(&p, cnt));
+    HIP_TRY(hipMemcpy(p, src, cnt * sizeof(double), hipMemcpyHostToDevice));
+    *dst = p;
+    return 0;
+  };
+  TRY(up(in->x_bar, n, &din.x_bar));
+  TRY(up(in->v_bar, n, &din.v_bar));
+  TRY(up(in->lam_bar, nc, &din.lam_bar));
+  TRY(up(in->v_prev, n, &din.v_prev));
+  struct Ret { double* host; double** dev; size_t cnt; };
+  const Ret rets[] = {{out->f_ext_bar, &dout.f_ext_bar, n}, {out->v_prev_bar, &dout.v_prev_bar, n},
+                      {out->x_prev_bar, &dout.x_prev_bar, n}, {out->lam_in_bar, &dout.lam_in_bar, nc},
+                      {out->t_bar, &dout.t_bar, nc}, {out->a_bar, &dout.a_bar, 3},
+                      {out->per_material, &dout.per_material, n_pm}, {out->per_element, &dout.per_element, n_pe}};
+  for (const Ret& r : rets)
+    if (r.host && r.cnt > 0) TRY(wk.alloc(r.dev, r.cnt));
+  TRY(tlfea_newton_adjoint_step_device(s, &din, &dout, info, rel_res));
+  for (const Ret& r : rets)
+    if (r.host && r.cnt > 0) HIP_TRY(hipMemcpy(r.host, *r.dev, r.cnt * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -533,4 +533,39 @@ constexpr int kStressMaxPart = 1024;
 void launch_stress_totals(hipStream_t s, int E, int Epad, const double* contrib, int N, const Incidence& inc,
                           const double* mval, const double* v, double* partial, double* out5);
 
+// Adjoint sensitivities of the implicit Newton step of T10 objects (tlfea_newton_adjoint_step, DESIGN 3j;
+// adjoint_kernels.hip).  No atomics.
+struct SensShape {
+  double Nq[kNQ][kNN];  // shape functions at the rule's points (the mass matrix's rule)
+};
+// sens [P + 1][Epad] per element, P = 2 (SVK: lambda, mu) | 3 (Mooney-Rivlin: mu10, mu01, kappa):
+// -sum_q dV (dP/dtheta_p)(F) : grad w, then the density slot -sum_q dV (N w).(N u) (u null: zeros).  w, u [3N] interleaved.
+void launch_sens_points(hipStream_t s, const ElemView& m, int model, const SensShape& sh, const double* w, const double* u,
+                        double* sens);
+void launch_sens_transpose(hipStream_t s, int E, int Epad, int slots, const double* sens, double* out /*[E][slots]*/);
+// Fixed-order sums of `slots` (3 | 4) values per item over groups of items: value (c, k) = src[c slot_stride +
+// item item_stride], item = idx ? idx[k] : k.  Partial block b adds the items [blk[b].x, blk[b].y) (blk null: chunks of
+// kAdjChunk over [0, n)), then block g of the final launch adds the partial rows [boff[g], boff[g + 1]) (boff null: one
+// group of all nb rows) into out [groups][slots].  partial: nb x slots doubles.
+constexpr int kAdjChunk = 4096;
+void launch_adj_sums(hipStream_t s, int slots, int n, int nb, const int2* blk, const int* idx, const double* src,
+                     size_t slot_stride, int item_stride, int groups, const int* boff, double* partial, double* out);
+// the constraint Jacobian J as the vector kernels see it: mode 0 none, 1 the fixed-node selector (constraint
+// 3 slot + c = component c of node fixed[slot]), 2 CSR rows (and J^T in CSR over DOF rows)
+struct AdjCons {
+  int mode;
+  const int *fixed, *fixed_slot;            // mode 1: [n_fixed] nodes, [N] slot of a node or -1
+  const int *joff, *jcol, *jtoff, *jtcol;   // mode 2
+  const double *jval, *jtval;
+};
+// x_t = x_bar + rho J^T lam_bar, v_t = v_bar + h x_t, u = (v - v_prev) / h - a over the n = 3N DOFs (null cotangent = 0)
+void launch_adj_rhs(hipStream_t s, int n, const AdjCons& J, const double* xbar, const double* vbar, const double* lambar,
+                    const double* v, const double* vprev, const double a[3], double h, double rho, double* xt, double* vt,
+                    double* u);
+// f_ext_bar = w, v_prev_bar = M w / h, x_prev_bar = x_t - (v_t - M w / h) / h per DOF; lam_in_bar = lam_bar - h J w,
+// t_bar = h rho J w - rho lam_bar per constraint row (null output = not wanted)
+void launch_adj_out(hipStream_t s, int n, int nc, const AdjCons& J, const double* w, const double* Mw, const double* xt,
+                    const double* vt, const double* lambar, double h, double rho, double* fext_bar, double* vprev_bar,
+                    double* xprev_bar, double* lam_in_bar, double* t_bar);
+
 }  // namespace tlfea

@@ -1,0 +1,146 @@
+"""Differentiable implicit step of a T10 body: torch.autograd over SyncedNewtonSolver.Solve().
+
+One step with max_outer = 1 maps the state (x, v, lambda) and the inputs f_ext, constraint targets, body acceleration
+and material parameters to the next state.  ImplicitStep runs the engine's own forward step and, in backward, the
+adjoint step on the device (tlfea_newton_adjoint_step_device): one linear solve with the step's Hessian per step.
+
+Tensors are float64 on the CPU (the engine's setters take host arrays); backward moves the cotangents to the GPU and
+calls the device form.  The materials tensor is [n_mat, P + 1] in the model's natural parameters -- SVK (lambda, mu, rho0),
+Mooney-Rivlin (mu10, mu01, kappa, rho0); lame_from_E_nu / E_nu_from_lame are written in torch, so the chain rule to
+(E, nu) is autograd's.  Densities enter the mass matrix: a forward whose densities differ from the ones the mass matrix
+was assembled with runs CalcMassMatrix again (and so does a backward that has to go back to them).
+
+Not differentiated (refused by the adjoint step): ANCF kinds, damping, friction, follower pressure, a partitioned mesh,
+steps with more than one outer iteration.
+"""
+import numpy as np
+import torch
+
+from .binding import AdjointInC, AdjointOutC, TlfeaError
+from .elements import ElementMaterial
+
+
+def lame_from_E_nu(E, nu):
+    """(lambda, mu) from Young's modulus and Poisson's ratio (torch tensors or floats)"""
+    return E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu)), E / (2.0 * (1.0 + nu))
+
+
+def E_nu_from_lame(lam, mu):
+    """(E, nu) from the Lame parameters"""
+    return mu * (3.0 * lam + 2.0 * mu) / (lam + mu), lam / (2.0 * (lam + mu))
+
+
+def _np(t):
+    return None if t is None else t.detach().cpu().numpy().astype(np.float64)
+
+
+def _apply_inputs(solver, data, f_ext, targets, gravity, materials):
+    """Write one step's differentiable inputs into the objects (None = leave what is set)."""
+    if materials is not None:
+        m = _np(materials)
+        n_mat, slots = data.MaterialSensitivityShape()
+        if m.shape != (n_mat, slots):
+            raise ValueError(f"materials must be [{n_mat}, {slots}] for the model and table set, got {tuple(m.shape)}")
+        ids = data.GetElementMaterialIds()
+        if slots == 3:
+            En = [E_nu_from_lame(r[0], r[1]) for r in m]
+            mats = [ElementMaterial(E=e, nu=nu, rho0=r[2]) for (e, nu), r in zip(En, m)]
+        else:
+            mats = [ElementMaterial(mu10=r[0], mu01=r[1], kappa=r[2], rho0=r[3]) for r in m]
+        if ids is not None:
+            data.SetElementMaterials(ids, mats, model="svk" if slots == 3 else "mooney_rivlin")
+        elif slots == 3:
+            data.SetSVK(mats[0].E, mats[0].nu)
+            data.SetDensity(mats[0].rho0)
+        else:
+            data.SetMooneyRivlin(mats[0].mu10, mats[0].mu01, mats[0].kappa)
+            data.SetDensity(mats[0].rho0)
+        rho = m[:, -1].copy()
+        if getattr(data, "_mass_rho", None) is None or not np.array_equal(data._mass_rho, rho):
+            data.CalcMassMatrix()
+            data._mass_rho = rho
+    if gravity is not None:
+        data.SetGravity(_np(gravity).reshape(3))
+    if f_ext is not None:
+        data.SetExternalForce(_np(f_ext).reshape(-1))
+    if targets is not None:
+        t = _np(targets)
+        if data.GetConstraintMode() == 2:
+            data.UpdateLinearConstraintRHS(t.reshape(-1))
+        else:
+            full = np.array(data._X0, dtype=np.float64)  # targets of free nodes are never read
+            full[data.fixed_nodes] = t.reshape(-1, 3)
+            data.UpdateConstraintTargets(full[:, 0], full[:, 1], full[:, 2])
+
+
+class ImplicitStep(torch.autograd.Function):
+    """(x, v, lambda)_new = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials).
+
+    x, v [N, 3], lam [n_constraints]; f_ext [N, 3]; targets [n_fixed, 3] (positions of data.fixed_nodes, in their order)
+    or the right-hand side [n_constraints] of CSR constraints; gravity [3]; materials [n_mat, P + 1].  Any of the last four
+    may be None: the objects keep what is set and no gradient flows.  The solver's parameters must have max_outer = 1."""
+
+    @staticmethod
+    def forward(ctx, solver, data, x, v, lam, f_ext, targets, gravity, materials):
+        _apply_inputs(solver, data, f_ext, targets, gravity, materials)
+        xn, vn = _np(x).reshape(-1, 3), _np(v).reshape(-1)
+        data.UpdatePositions(xn[:, 0], xn[:, 1], xn[:, 2])
+        solver.SetVelocity(vn, vn)  # the step starts from v_prev = v: Solve() ends every step that way
+        if solver.n_constraints:
+            solver.SetLambda(_np(lam).reshape(-1))
+        solver.Solve()
+        solver.AdjointReady()  # a step the adjoint would refuse is refused here, where the cause is
+        x1 = np.stack(data.RetrievePositionToCPU(), axis=1)
+        v1 = solver.RetrieveVelocityToCPU().reshape(-1, 3)
+        lam1 = solver.RetrieveLambdaToCPU()
+        ctx.solver, ctx.data = solver, data
+        ctx.inputs = (f_ext, targets, gravity, materials)
+        ctx.state = (x1, v1, lam1, vn.copy())
+        ctx.shapes = (x.shape, v.shape, lam.shape)
+        return (torch.tensor(x1).reshape(x.shape), torch.tensor(v1).reshape(v.shape), torch.tensor(lam1).reshape(lam.shape))
+
+    @staticmethod
+    def backward(ctx, gx, gv, glam):
+        solver, data = ctx.solver, ctx.data
+        f_ext, targets, gravity, materials = ctx.inputs
+        x1, v1, lam1, v0 = ctx.state
+        # that step's converged state and inputs again (H depends on x, the materials and the time step alone)
+        _apply_inputs(solver, data, None, None, gravity, materials)
+        data.UpdatePositions(x1[:, 0], x1[:, 1], x1[:, 2])
+        solver.SetVelocity(v1.reshape(-1), v1.reshape(-1))
+        if solver.n_constraints:
+            solver.SetLambda(lam1)
+        dev = torch.device("cuda")
+        N, nc = data.n_coef, solver.n_constraints
+        n_mat, slots = data.MaterialSensitivityShape()
+
+        def up(t):
+            return None if t is None else t.detach().to(dev, torch.float64).contiguous().reshape(-1)
+        ins = [up(gx), up(gv), up(glam) if nc else None, torch.from_numpy(v0).to(dev)]
+        want = {"f_ext": f_ext is not None and ctx.needs_input_grad[5], "t": targets is not None and ctx.needs_input_grad[6],
+                "a": gravity is not None and ctx.needs_input_grad[7], "m": materials is not None and ctx.needs_input_grad[8]}
+        z = lambda k: torch.zeros(k, dtype=torch.float64, device=dev)  # noqa: E731
+        outs = [z(3 * N), z(3 * N), z(3 * N), z(nc) if nc else None, z(nc) if nc and want["t"] else None,
+                z(3) if want["a"] else None, z(n_mat * slots) if want["m"] else None, None]
+        torch.cuda.synchronize()
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        solver.AdjointStepDevice(AdjointInC(*[ptr(t) for t in ins]), AdjointOutC(*[ptr(t) for t in outs]))
+        sx, sv, sl = ctx.shapes
+        back = lambda t, shape: None if t is None else t.cpu().reshape(shape)  # noqa: E731
+        return (None, None, back(outs[2], sx), back(outs[1], sv), back(outs[3], sl) if nc else torch.zeros(sl, dtype=torch.float64),
+                back(outs[0], f_ext.shape) if want["f_ext"] else None,
+                back(outs[4], targets.shape) if want["t"] and nc else None,
+                back(outs[5], gravity.shape) if want["a"] else None,
+                back(outs[6], materials.shape) if want["m"] else None)
+
+
+def rollout(solver, data, state, n_steps, f_ext=None, targets=None, gravity=None, materials=None):
+    """n_steps chained ImplicitStep calls from state = (x, v, lam); the inputs are the same tensors in every step (their
+    gradients add up).  -> the final (x, v, lam)."""
+    x, v, lam = state
+    for _ in range(int(n_steps)):
+        x, v, lam = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials)
+    return x, v, lam
+
+
+__all__ = ["ImplicitStep", "rollout", "lame_from_E_nu", "E_nu_from_lame", "TlfeaError"]

@@ -281,6 +281,7 @@ class GPU_FEAT10_Data:
     def SetNodalFixed(self, fixed_nodes):
         fx = np.ascontiguousarray(fixed_nodes, dtype=np.int32)
         check(self._lib.tlfea_t10_set_nodal_fixed(self._h, ip(fx), int(fx.size)))
+        self.fixed_nodes = fx.copy()  # constraint 3 k + c is component c of node fixed_nodes[k]
 
     def SetLinearConstraintsCSR(self, j_offsets, j_columns, j_values, rhs):
         """General linear constraints c = J x - rhs (ANCF3243Data.cuh:810-940); columns = 3*coef + component."""
@@ -308,6 +309,7 @@ class GPU_FEAT10_Data:
     def UpdateNodalFixed(self, fixed_nodes):
         fx = np.ascontiguousarray(fixed_nodes, dtype=np.int32)
         check(self._lib.tlfea_t10_update_nodal_fixed(self._h, ip(fx), int(fx.size)))
+        self.fixed_nodes = fx.copy()
 
     def UpdatePositions(self, h_x12, h_y12, h_z12):
         x, y, z = _f64(h_x12), _f64(h_y12), _f64(h_z12)
@@ -393,6 +395,33 @@ class GPU_FEAT10_Data:
 
     def GetNodalStressDevicePtr(self):
         return self._lib.tlfea_t10_nodal_stress_device_ptr(self._h)
+
+    # -- material sensitivities ------------------------------------------------------------------
+    def MaterialSensitivityShape(self):
+        """(n_mat, P + 1): entries of the material table (1 without one) and the slots of the model set now -- SVK
+        (lambda, mu, rho0), Mooney-Rivlin (mu10, mu01, kappa, rho0)."""
+        n_mat, slots = C.c_int(), C.c_int()
+        check(self._lib.tlfea_t10_material_sensitivity_shape(self._h, C.byref(n_mat), C.byref(slots)))
+        return n_mat.value, slots.value
+
+    def MaterialSensitivity(self, w, u=None):
+        """The element kernel of the adjoint step and its reduction alone, at the current positions: for an adjoint field
+        w and an acceleration field u [3N or N x 3], per element -sum_q dV (dP/dtheta_p)(F) : grad w for every stiffness
+        parameter and -sum_q dV (N w).(N u) for the density.  -> (per_element [E, P + 1], per_material [n_mat, P + 1])."""
+        w = _f64(w).reshape(-1)
+        u = None if u is None else _f64(u).reshape(-1)
+        if w.size != 3 * self.n_coef or (u is not None and u.size != w.size):
+            raise ValueError(f"MaterialSensitivity: w and u need {3 * self.n_coef} entries")
+        n_mat, slots = self.MaterialSensitivityShape()
+        pe, pm = np.zeros((self.n_elem, slots)), np.zeros((n_mat, slots))
+        check(self._lib.tlfea_t10_material_sensitivity(self._h, dp(w), dp(u), dp(pe), dp(pm)))
+        return pe, pm
+
+    def TimeSensitivityKernels(self, reps=20):
+        """-> mean ms of (element kernel, reduction) over `reps` back-to-back launches each."""
+        out = np.zeros(2)
+        check(self._lib.tlfea_t10_time_sensitivity_kernels(self._h, int(reps), dp(out)))
+        return out
 
     def TimeStressKernels(self, velocity=None, points=False, reps=20):
         """-> mean ms of (point and element kernel, nodal gather, totals) over `reps` back-to-back launches each."""

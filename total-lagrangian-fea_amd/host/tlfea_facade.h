@@ -1397,7 +1397,8 @@ class SyncedNewtonSolver : public SolverBase {
  public:
   SyncedNewtonSolver(ElementBase* data, int n_constraints) {
     // SyncedNewton.cuh:52-85: the three element types share one device path here
-    TLFEA_HANDLE_ERROR(tlfea_newton_create(static_cast<GPU_FEAT10_Data*>(data)->h, n_constraints, &s_));
+    data_ = static_cast<GPU_FEAT10_Data*>(data)->h;
+    TLFEA_HANDLE_ERROR(tlfea_newton_create(data_, n_constraints, &s_));
     n_coef_ = data->get_n_coef();
   }
   ~SyncedNewtonSolver() override { tlfea_newton_destroy(s_); }
@@ -1452,7 +1453,38 @@ class SyncedNewtonSolver : public SolverBase {
     return r;
   }
 
+  // Adjoint of the implicit step just solved (no reference counterpart; Solve() with max_outer = 1): given the
+  // cotangents of the outputs x, v [3 n_coef] and lambda_new [n_constraints] (an empty vector = zero), the cotangents of
+  // the step's inputs.  per_material is [n_mat][P + 1]: SVK (lambda, mu), Mooney-Rivlin (mu10, mu01, kappa), then the
+  // density.  v_prev (the velocity the step started from; empty = the one the last Solve() started from) enters the
+  // density slot only.  The solver's state is unchanged.
+  struct AdjointResult {
+    std::vector<double> f_ext, v_prev, x_prev, lam_in, targets, per_material, per_element;
+    double gravity[3] = {0.0, 0.0, 0.0};
+    int n_mat = 0, slots = 0, iterations = 0;
+    double rel_res = 0.0;
+  };
+  AdjointResult AdjointStep(const std::vector<double>& xbar, const std::vector<double>& vbar,
+                            const std::vector<double>& lambar = {}, bool per_element = false,
+                            const std::vector<double>& v_prev = {}) {
+    const size_t n = 3 * (size_t)n_coef_, nc = (size_t)std::max(0, tlfea_newton_n_constraints(s_));
+    AdjointResult r;
+    TLFEA_HANDLE_ERROR(tlfea_t10_material_sensitivity_shape(data_, &r.n_mat, &r.slots));
+    auto in = [](const std::vector<double>& a, size_t want) { return a.size() == want && want ? a.data() : nullptr; };
+    r.f_ext.assign(n, 0.0); r.v_prev.assign(n, 0.0); r.x_prev.assign(n, 0.0);
+    r.lam_in.assign(nc, 0.0); r.targets.assign(nc, 0.0);
+    r.per_material.assign((size_t)r.n_mat * r.slots, 0.0);
+    if (per_element) r.per_element.assign((size_t)tlfea_t10_get_n_elem(data_) * r.slots, 0.0);
+    tlfea_adjoint_in ci{in(xbar, n), in(vbar, n), in(lambar, nc), in(v_prev, n)};
+    tlfea_adjoint_out co{r.f_ext.data(), r.v_prev.data(), r.x_prev.data(), nc ? r.lam_in.data() : nullptr,
+                         nc ? r.targets.data() : nullptr, r.gravity, r.per_material.data(),
+                         per_element ? r.per_element.data() : nullptr};
+    TLFEA_HANDLE_ERROR(tlfea_newton_adjoint_step(s_, &ci, &co, &r.iterations, &r.rel_res));
+    return r;
+  }
+
  private:
+  tlfea_t10_t data_ = nullptr;
   tlfea_newton_t s_ = nullptr;
   int n_coef_ = 0;
 };

@@ -4,7 +4,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .binding import (ALLREDUCE_FN, AdamWParamsC, LinSolveOptsC, ModalOptsC, NesterovParamsC, NewtonParams, TlfeaError,
+from .binding import (ALLREDUCE_FN, AdamWParamsC, AdjointInC, AdjointOutC, LinSolveOptsC, ModalOptsC, NesterovParamsC, NewtonParams, TlfeaError,
                       VbdParamsC, check, dp, ip, load_library)
 
 
@@ -46,6 +46,25 @@ class ModalResult:
     converged: int
     block: int
     precond: int
+
+
+@dataclass
+class AdjointResult:
+    """What AdjointStep returns: the cotangents of the inputs of the step just solved.  f_ext, v_prev, x_prev [N, 3];
+    lam_in, targets [n_constraints] (targets: of the fixed nodes in the order 3 slot + component, or the right-hand side
+    of the CSR rows); gravity [3]; per_material [n_mat, P + 1] in the model's natural parameters -- SVK (lambda, mu),
+    Mooney-Rivlin (mu10, mu01, kappa) -- then the density; per_element [E, P + 1] or None; iterations and rel_res of the
+    linear solve."""
+    f_ext: np.ndarray
+    v_prev: np.ndarray
+    x_prev: np.ndarray
+    lam_in: np.ndarray
+    targets: np.ndarray
+    gravity: np.ndarray
+    per_material: np.ndarray
+    per_element: object
+    iterations: int
+    rel_res: float
 
 
 MODAL_DEFAULT_SHIFT = (2.0 * np.pi * 1.0) ** 2   # (2 pi 1 Hz)^2
@@ -315,6 +334,45 @@ class SyncedNewtonSolver:
             err.partial = out
             raise err
         return out
+
+    def AdjointReady(self):
+        """Raises TlfeaError with the reason when AdjointStep would refuse the solver's state now."""
+        check(self._lib.tlfea_newton_adjoint_ready(self._h))
+
+    def AdjointStep(self, xbar=None, vbar=None, lambar=None, per_element=False, v_prev=None):
+        """Adjoint of the implicit step just solved (Solve() with max_outer = 1): given the cotangents of its
+        outputs x, v [3N or N x 3] and lambda_new [n_constraints] (None = zero), one solve with the step's Hessian gives
+        the cotangents of f_ext, v_prev, x_prev, lambda, the constraint targets, the body acceleration and the material
+        parameters.  v_prev: the velocity the step started from (default: the one the last Solve() started from); it
+        enters the density slot only.  The solver's state is left as it was."""
+        n, nc = 3 * self.n_coef, int(self._lib.tlfea_newton_n_constraints(self._h))
+        self.n_constraints = nc
+
+        def arr(a, size, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            if a.size != size:
+                raise ValueError(f"AdjointStep: {name} needs {size} entries, got {a.size}")
+            return a
+        ins = [arr(xbar, n, "xbar"), arr(vbar, n, "vbar"), arr(lambar, nc, "lambar"), arr(v_prev, n, "v_prev")]
+        n_mat, slots = self._data.MaterialSensitivityShape()
+        outs = [np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(nc), np.zeros(nc), np.zeros(3), np.zeros((n_mat, slots)),
+                np.zeros((self._data.n_elem, slots)) if per_element else None]
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
+        cin, cout = AdjointInC(*[ptr(a) for a in ins]), AdjointOutC(*[ptr(a) for a in outs])
+        it, rel = C.c_int(), C.c_double()
+        check(self._lib.tlfea_newton_adjoint_step(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
+        N = self.n_coef
+        return AdjointResult(outs[0].reshape(N, 3), outs[1].reshape(N, 3), outs[2].reshape(N, 3), outs[3], outs[4],
+                             outs[5], outs[6], outs[7], it.value, rel.value)
+
+    def AdjointStepDevice(self, cin, cout):
+        """The same on device pointers (binding.AdjointInC / AdjointOutC filled with device addresses, 0 / None = absent):
+        -> (iterations, rel_res).  differentiable.ImplicitStep calls this with torch tensors."""
+        it, rel = C.c_int(), C.c_double()
+        check(self._lib.tlfea_newton_adjoint_step_device(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
+        return it.value, rel.value
 
     def ModalApplyBlock(self, X, which=0, apply_mask=False):
         """Y = H X (which 0) or (M (x) I3) X (which 1) for a block X [3N, m], m <= 32, with the current H (test hook)"""
