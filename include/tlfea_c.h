@@ -511,6 +511,10 @@ int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double *x, double
 /* which product the CG iterations of the last linear solve used: 0 = CSR kernel, 1 = matrix-free pair
  * (TLFEA_SPMV_MATFREE=0|1 forces it off / on where eligible; default: eligible and at least 150 000 nodes) */
 int tlfea_newton_get_spmv_mode(tlfea_newton_t s);
+/* the last lambda_max estimates: out[0] fine level, out[1] vertex level, out[2] third level (0 where there is none);
+ * out[3] = 1 if the last fine estimate ran its products through the matrix-free pair (inside a solve whose CG iteration
+ * does; TLFEA_LMAX_MATFREE=0 keeps the CSR product), else 0 */
+int tlfea_newton_get_lambda_max(tlfea_newton_t s, double out[4]);
 /* row form of the matrix-free pair once it has run: returns 1 where a wavefront of 64 elements sums its rows per node
  * before storing them (TLFEA_MATFREE_COMPACT, default 1), 0 for one row per (element, local node), -1 before the first
  * product.  rows = rows of the buffer, ratio = 10 E / rows (1 for the element form); either may be null. */

@@ -206,6 +206,9 @@ def _pmg_signatures(lib):
     for name, args in sig.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "tlfea_newton_get_lambda_max"):  # an older build loaded through TLFEA_LIB_PATH (A/B runs) lacks it
+        lib.tlfea_newton_get_lambda_max.argtypes = [vp, c_dp]
+        lib.tlfea_newton_get_lambda_max.restype = C.c_int
 
 
 def _contact_signatures(lib):

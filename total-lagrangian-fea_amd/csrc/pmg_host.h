@@ -25,12 +25,37 @@ struct PmgHost {
   std::vector<int> cblk_row;                 // [nnz_c] coarse row of each coarse block
   std::vector<int> child_off, child;         // [Nc+1], fine ids: the vertex itself first, then its mid-edge nodes
   std::vector<float> child_w;                // 1 or 1/2
-  std::vector<int> con_off;                  // [nnz_c+1] contributions of fine blocks to each coarse block
+  // H is symmetric, so Hc[J,I] = Hc[I,J]^T: contribution lists exist only for the blocks with column >= row
+  std::vector<int> c_upper;                  // [n_upper] ids of those blocks, ascending
+  std::vector<int> c_mirror;                 // [nnz_c] position of block (J, I) for every block (I, J)
+  std::vector<int> con_off;                  // [n_upper+1] contributions of fine blocks to coarse block c_upper[u]
   std::vector<int> con_blk;                  // fine block index (off[i] + k), ascending within a coarse block
   std::vector<int> con_base, con_deg;        // of that fine block: 9 off[i] + 3 k (its place in H's layout) and deg(i)
   std::vector<float> con_w;                  // w_i * w_j
   std::vector<int> blk_row;                  // [nnz_f] fine row of each fine block
 };
+
+// c_upper and c_mirror from the coarse pattern; upos[cb] = position of block cb in c_upper, -1 for a block below the
+// diagonal.  False when some block (I, J) has no block (J, I): the pattern is not symmetric.
+inline bool pmg_mirror_build(PmgHost& o, std::vector<int>& upos) {
+  o.c_mirror.assign((size_t)o.nnz_c, -1);
+  o.c_upper.clear();
+  upos.assign((size_t)o.nnz_c, -1);
+  for (int cb = 0; cb < o.nnz_c; cb++) {
+    const int I = o.cblk_row[cb], J = o.c_cols[cb];
+    if (J < 0 || J >= o.Nc) return false;
+    const int* r = o.c_cols.data() + o.c_off[J];
+    const int deg = o.c_off[J + 1] - o.c_off[J];
+    const int* p = std::lower_bound(r, r + deg, I);
+    if (p == r + deg || *p != I) return false;
+    o.c_mirror[cb] = o.c_off[J] + (int)(p - r);
+    if (J >= I) {
+      upos[cb] = (int)o.c_upper.size();
+      o.c_upper.push_back(cb);
+    }
+  }
+  return true;
+}
 
 // T10 local edges of the mid-edge nodes 4..9 (FEAT10Data.cu:143, cpu_utils.cc:609-619)
 static const int kT10Edge[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};
@@ -147,14 +172,19 @@ inline bool pmg_build(int N, int E, const int* conn, const int* off, const int* 
     }
   }
   if (bad) return false;
-  o.con_off.assign((size_t)o.nnz_c + 1, 0);
+  std::vector<int> upos;
+  if (!pmg_mirror_build(o, upos)) return false;
+  const int n_upper = (int)o.c_upper.size();
+  for (size_t t = 0; t < tgt.size(); t++)  // lists for the upper triangle only: the kernel mirrors the rest
+    if (tgt[t] >= 0) tgt[t] = upos[tgt[t]];
+  o.con_off.assign((size_t)n_upper + 1, 0);
   for (size_t t = 0; t < tgt.size(); t++)
     if (tgt[t] >= 0) o.con_off[(size_t)tgt[t] + 1]++;
-  for (int k = 0; k < o.nnz_c; k++) o.con_off[k + 1] += o.con_off[k];
-  o.con_blk.assign((size_t)o.con_off[o.nnz_c], 0);
-  o.con_w.assign((size_t)o.con_off[o.nnz_c], 0.f);
-  o.con_base.assign((size_t)o.con_off[o.nnz_c], 0);
-  o.con_deg.assign((size_t)o.con_off[o.nnz_c], 0);
+  for (int k = 0; k < n_upper; k++) o.con_off[k + 1] += o.con_off[k];
+  o.con_blk.assign((size_t)o.con_off[n_upper], 0);
+  o.con_w.assign((size_t)o.con_off[n_upper], 0.f);
+  o.con_base.assign((size_t)o.con_off[n_upper], 0);
+  o.con_deg.assign((size_t)o.con_off[n_upper], 0);
   {
     std::vector<int> cur(o.con_off.begin(), o.con_off.end() - 1);
     for (int g = 0; g < nnz_f; g++) {  // ascending fine block index: fixed summation order
@@ -199,29 +229,37 @@ inline bool pmg_build_ancf(int N, const int* off, const int* cols, PmgHost& o) {
   o.c_cols.resize((size_t)o.nnz_c);
   o.c_diagpos.assign((size_t)Nc, -1);
   o.cblk_row.resize((size_t)o.nnz_c);
-  o.con_off.resize((size_t)o.nnz_c + 1);
-  o.con_blk.resize((size_t)o.nnz_c);
-  o.con_base.resize((size_t)o.nnz_c);
-  o.con_deg.resize((size_t)o.nnz_c);
-  o.con_w.assign((size_t)o.nnz_c, 1.f);
+  std::vector<int> src((size_t)o.nnz_c);  // the one fine block behind every coarse block
   for (int I = 0; I < Nc; I++) {
     int k = o.c_off[I];
-    const int i = 4 * I, deg = off[i + 1] - off[i];
+    const int i = 4 * I;
     for (int g = off[i]; g < off[i + 1]; g++) {
       if (cols[g] % 4) continue;
       const int J = cols[g] / 4;
       if (J == I) o.c_diagpos[I] = k - o.c_off[I];
       o.c_cols[k] = J;           // fine columns ascend, so do these
       o.cblk_row[k] = I;
-      o.con_off[k] = k;
-      o.con_blk[k] = g;
-      o.con_base[k] = 9 * off[i] + 3 * (g - off[i]);
-      o.con_deg[k] = deg;
+      src[k] = g;
       k++;
     }
     if (o.c_diagpos[I] < 0) return false;
   }
-  o.con_off[o.nnz_c] = o.nnz_c;
+  std::vector<int> upos;
+  if (!pmg_mirror_build(o, upos)) return false;
+  const int n_upper = (int)o.c_upper.size();  // one contribution per block with column >= row, mirrored by the kernel
+  o.con_off.resize((size_t)n_upper + 1);
+  o.con_blk.resize((size_t)n_upper);
+  o.con_base.resize((size_t)n_upper);
+  o.con_deg.resize((size_t)n_upper);
+  o.con_w.assign((size_t)n_upper, 1.f);
+  for (int u = 0; u < n_upper; u++) {
+    const int cb = o.c_upper[u], g = src[cb], i = 4 * o.cblk_row[cb];
+    o.con_off[u] = u;
+    o.con_blk[u] = g;
+    o.con_base[u] = 9 * off[i] + 3 * (g - off[i]);
+    o.con_deg[u] = off[i + 1] - off[i];
+  }
+  o.con_off[n_upper] = n_upper;
   o.child_off.resize((size_t)Nc + 1);
   o.child.resize((size_t)Nc);
   o.child_w.assign((size_t)Nc, 1.f);

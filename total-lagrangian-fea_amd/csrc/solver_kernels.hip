@@ -1439,7 +1439,12 @@ void launch_spmv32_rows(hipStream_t s, int n_rows, const int* rows, const int* s
 // Hc = P^T H P by gather: one thread owns one coarse 3x3 block and adds its contributing fine blocks in ascending
 // fine-block order with weights 1, 1/2, 1/4 (no atomics: bitwise reproducible).  H and Hc in the reference's
 // DOF-level layout (node row -> [d][k][e]).
-__global__ __launch_bounds__(256) void pmg_galerkin_kernel(int nnz_c, const int* __restrict__ c_off,
+// H is symmetric, so Hc[J,I] = Hc[I,J]^T: only the blocks with column >= row (c_upper, ascending) are summed, each from
+// its own list (con_off is indexed by the position in c_upper), and an off-diagonal block is stored a second time,
+// transposed, at c_mirror[cb] -- the lower triangle is the exact transpose of the upper one.
+__global__ __launch_bounds__(256) void pmg_galerkin_kernel(int n_upper, const int* __restrict__ c_upper,
+                                                          const int* __restrict__ c_mirror,
+                                                          const int* __restrict__ c_off,
                                                           const int* __restrict__ cblk_row,
                                                           const int* __restrict__ con_off,
                                                           const int* __restrict__ con_base,
@@ -1450,10 +1455,10 @@ __global__ __launch_bounds__(256) void pmg_galerkin_kernel(int nnz_c, const int*
   // butterfly; con_base = 9 off[i] + 3 k and con_deg = deg(i) of the contributing fine block are precomputed so that
   // a contribution is one independent round trip instead of a chain of four
   const int lane = threadIdx.x & 15;
-  const int cb = blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (cb >= nnz_c) return;
+  const int ub = blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (ub >= n_upper) return;
   double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int u = con_off[cb] + lane; u < con_off[cb + 1]; u += 16) {
+  for (int u = con_off[ub] + lane; u < con_off[ub + 1]; u += 16) {
     const double w = (double)con_w[u];
     const int deg3 = 3 * con_deg[u];
     const double* Hi = Hf + con_base[u];
@@ -1471,13 +1476,19 @@ __global__ __launch_bounds__(256) void pmg_galerkin_kernel(int nnz_c, const int*
   double v = acc[0];
 #pragma unroll
   for (int k = 1; k < 9; k++) v = (lane == k) ? acc[k] : v;
+  const int cb = c_upper[ub], cm = c_mirror[cb];
   const int I = cblk_row[cb], oc = c_off[I], degc = c_off[I + 1] - oc, pc = cb - oc;
   Hc[(size_t)9 * oc + (size_t)dd * 3 * degc + 3 * pc + ee] = v;
+  if (cm == cb) return;
+  const int J = cblk_row[cm], om = c_off[J], degm = c_off[J + 1] - om, pm = cm - om;
+  Hc[(size_t)9 * om + (size_t)ee * 3 * degm + 3 * pm + dd] = v;
 }
-void launch_pmg_galerkin(hipStream_t s, int nnz_c, const int* c_off, const int* cblk_row, const int* con_off,
-                         const int* con_base, const int* con_deg, const float* con_w, const double* Hf, double* Hc) {
-  hipLaunchKernelGGL(pmg_galerkin_kernel, dim3((nnz_c + 15) / 16), dim3(256), 0, s, nnz_c, c_off, cblk_row, con_off,
-                     con_base, con_deg, con_w, Hf, Hc);
+void launch_pmg_galerkin(hipStream_t s, int n_upper, const int* c_upper, const int* c_mirror, const int* c_off,
+                         const int* cblk_row, const int* con_off, const int* con_base, const int* con_deg,
+                         const float* con_w, const double* Hf, double* Hc) {
+  if (n_upper <= 0) return;
+  hipLaunchKernelGGL(pmg_galerkin_kernel, dim3((n_upper + 15) / 16), dim3(256), 0, s, n_upper, c_upper, c_mirror, c_off,
+                     cblk_row, con_off, con_base, con_deg, con_w, Hf, Hc);
 }
 
 // Restriction fused with the coarse polynomial's start vectors.  The fine residual lives in the fine scaled space
@@ -1604,6 +1615,7 @@ void launch_pmg_prolong(hipStream_t s, int N, const int* par0, const int* par1, 
 // itself must not be 16-bit: fp16(P^T Hs) != P^T fp16(Hs) breaks the symmetry of the cycle.  32 lanes per coarse row,
 // a lane per R block; R is stored like the streamed copies (8 + 1 entries per block) so that cheb32's row product
 // reads it.
+constexpr int kRopTab = 64;  // children per row whose factors the LDS table holds (8 rows x 64 x 3 doubles = 12 KB a block)
 template <typename HT>
 __global__ __launch_bounds__(256) void pmg_rop_build_kernel(
     int Nc, const int* __restrict__ r_off, const int* __restrict__ con_off, const int* __restrict__ con_blk,
@@ -1611,23 +1623,63 @@ __global__ __launch_bounds__(256) void pmg_rop_build_kernel(
     const float* __restrict__ ch_w, const Blk8<HT>* __restrict__ B8, const HT* __restrict__ B1,
     const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8,
     float* __restrict__ R1) {
-  const int lane = threadIdx.x & 31;
-  const int I = blockIdx.x * 8 + (threadIdx.x >> 5);
+  // The factors w_i / sc_f[i,d] belong to the row's children (~15), not to its contributions (~6 per block, ~62 blocks):
+  // the row's lanes divide once per child into a table in LDS that only this row's lanes touch (the first kRopTab
+  // children; a later one -- no T10 mesh seen so far has any -- divides in place, the same quotient).  The 32 lanes are
+  // half a wavefront: the table needs a wave-level fence, not a block barrier.
+  __shared__ double tab[8][kRopTab][3];
+  const int lane = threadIdx.x & 31, rw = threadIdx.x >> 5;
+  const int I = blockIdx.x * 8 + rw;
   if (I >= Nc) return;
   const double sI[3] = {sc_c[3 * I], sc_c[3 * I + 1], sc_c[3 * I + 2]};
   const int c0 = ch_off[I], b1 = r_off[I + 1];
+  const int n_tab = min(ch_off[I + 1] - c0, kRopTab);
+  for (int c = lane; c < n_tab; c += 32) {
+    const int i = ch[c0 + c];
+    const double w = (double)ch_w[c0 + c];
+    tab[rw][c][0] = w / sc_f[3 * i];
+    tab[rw][c][1] = w / sc_f[3 * i + 1];
+    tab[rw][c][2] = w / sc_f[3 * i + 2];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  auto factors = [&](int ord, double f[3]) {
+    if (ord < kRopTab) {
+      f[0] = tab[rw][ord][0];
+      f[1] = tab[rw][ord][1];
+      f[2] = tab[rw][ord][2];
+    } else {
+      const int i = ch[c0 + ord];
+      const double w = (double)ch_w[c0 + ord];
+      f[0] = w / sc_f[3 * i];
+      f[1] = w / sc_f[3 * i + 1];
+      f[2] = w / sc_f[3 * i + 2];
+    }
+  };
   for (int b = r_off[I] + lane; b < b1; b += 32) {
     double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int t1 = con_off[b + 1];
-    for (int t = con_off[b]; t < t1; t++) {
-      const int g = con_blk[t], ct = c0 + (int)con_ord[t], i = ch[ct];
-      const double w = (double)ch_w[ct];
-      const Blk8<HT> v = B8[g];
-      const HT v8 = B1[g];
-      const double f[3] = {w / sc_f[3 * i], w / sc_f[3 * i + 1], w / sc_f[3 * i + 2]};
+    // two contributions per round, both blocks requested before the first is used; a missing second one re-reads the
+    // first with factor zero (acc + 0 * finite = acc: the sums and their order are those of the one-by-one loop)
+    for (int t = con_off[b]; t < t1; t += 2) {
+      const bool two = t + 1 < t1;
+      const int tb = two ? t + 1 : t;
+      const int ga = con_blk[t], gb = con_blk[tb];
+      const int oa = (int)con_ord[t], ob = (int)con_ord[tb];
+      const Blk8<HT> va = B8[ga], vb = B8[gb];
+      const HT va8 = B1[ga], vb8 = B1[gb];
+      double fa[3], fb[3];
+      factors(oa, fa);
+      factors(ob, fb);
+      if (!two) fb[0] = fb[1] = fb[2] = 0.0;
 #pragma unroll
-      for (int k = 0; k < 8; k++) acc[k] += f[k / 3] * (double)(float)v.v[k];
-      acc[8] += f[2] * (double)(float)v8;
+      for (int k = 0; k < 8; k++) {
+        acc[k] += fa[k / 3] * (double)(float)va.v[k];
+        acc[k] += fb[k / 3] * (double)(float)vb.v[k];
+      }
+      acc[8] += fa[2] * (double)(float)va8;
+      acc[8] += fb[2] * (double)(float)vb8;
     }
     Blk8<float> out;
 #pragma unroll
@@ -1755,19 +1807,23 @@ __device__ __forceinline__ void cross3(const double a[3], const double b[3], dou
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// H3 = P2^T Hc P2 by gather: one thread owns one aggregate pair (A, B) = four 3x3 blocks and adds the vertex-level
-// blocks (i in A, j in B) in ascending order (no atomics).  Both matrices in the DOF-level layout [row][d][k][e].
-__global__ __launch_bounds__(128) void agg_galerkin_kernel(int n_pairs, const int* __restrict__ pair_A,
+// H3 = P2^T Hc P2 by gather: 16 lanes own one aggregate pair (A, B) = four 3x3 blocks; lane l adds the vertex-level
+// blocks (i in A, j in B) number l, l + 16, ... of the pair's ascending list, then a fixed-order butterfly sums the 36
+// accumulators over the lanes (no atomics: the same bits from build to build).  A diagonal pair has ~250 blocks, which
+// one thread used to walk one dependent load at a time while the launch waited for it.  Both matrices in the DOF-level
+// layout [row][d][k][e].
+__global__ __launch_bounds__(256) void agg_galerkin_kernel(int n_pairs, const int* __restrict__ pair_A,
                                                           const int* __restrict__ pair_pos, const int* __restrict__ pair_B,
                                                           const int* __restrict__ pcon_off, const int* __restrict__ pcon_base,
                                                           const int* __restrict__ pcon_deg, const int* __restrict__ pcon_i,
                                                           const int* __restrict__ pcon_j, const double* __restrict__ rvec,
                                                           const int* __restrict__ active, const int* __restrict__ off3,
                                                           const double* __restrict__ Hc, double* __restrict__ H3) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 15;
+  const int p = blockIdx.x * 16 + (threadIdx.x >> 4);
   if (p >= n_pairs) return;
   double tt[3][3] = {{0}}, tr[3][3] = {{0}}, rt[3][3] = {{0}}, rr[3][3] = {{0}};
-  for (int u = pcon_off[p]; u < pcon_off[p + 1]; u++) {
+  for (int u = pcon_off[p] + lane; u < pcon_off[p + 1]; u += 16) {
     const int deg3 = 3 * pcon_deg[u];
     const double* Hi = Hc + pcon_base[u];
     const double* ri = rvec + 3 * (size_t)pcon_i[u];
@@ -1800,6 +1856,18 @@ __global__ __launch_bounds__(128) void agg_galerkin_kernel(int n_pairs, const in
       }
     }
   }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+#pragma unroll
+      for (int e = 0; e < 3; e++) {
+        tt[d][e] += __shfl_xor(tt[d][e], o);
+        tr[d][e] += __shfl_xor(tr[d][e], o);
+        rt[d][e] += __shfl_xor(rt[d][e], o);
+        rr[d][e] += __shfl_xor(rr[d][e], o);
+      }
+  if (lane >= 4) return;  // every lane holds the sums: lane 2 s2 + t2 stores block (s2, t2)
   const int A = pair_A[p], B = pair_B[p], pos = pair_pos[p];
   if (A == B && active[A] <= 0) {  // unusable rotations (0) / empty grid cell (-1): identity keeps the level-3 matrix
 #pragma unroll                   // definite, the modes stay at zero (on several ranks the identities add up: harmless)
@@ -1810,25 +1878,21 @@ __global__ __launch_bounds__(128) void agg_galerkin_kernel(int n_pairs, const in
         if (active[A] < 0) tt[d][e] = (d == e) ? 1.0 : 0.0;
       }
   }
+  const int s2 = lane >> 1, t2 = lane & 1;
+  const int row = 2 * A + s2, o3 = off3[row], deg3 = 3 * (off3[row + 1] - o3);
+  double* out = H3 + (size_t)9 * o3 + 3 * (2 * pos + t2);
 #pragma unroll
-  for (int s2 = 0; s2 < 2; s2++) {
-    const int row = 2 * A + s2, o3 = off3[row], deg3 = 3 * (off3[row + 1] - o3);
+  for (int d = 0; d < 3; d++)
 #pragma unroll
-    for (int t2 = 0; t2 < 2; t2++) {
-      double* out = H3 + (size_t)9 * o3 + 3 * (2 * pos + t2);
-#pragma unroll
-      for (int d = 0; d < 3; d++)
-#pragma unroll
-        for (int e = 0; e < 3; e++)
-          out[(size_t)d * deg3 + e] = s2 == 0 ? (t2 == 0 ? tt[d][e] : tr[d][e]) : (t2 == 0 ? rt[d][e] : rr[d][e]);
-    }
-  }
+    for (int e = 0; e < 3; e++)
+      out[(size_t)d * deg3 + e] = s2 == 0 ? (t2 == 0 ? tt[d][e] : tr[d][e]) : (t2 == 0 ? rt[d][e] : rr[d][e]);
 }
 void launch_agg_galerkin(hipStream_t s, int n_pairs, const int* pair_A, const int* pair_pos, const int* pair_B,
                          const int* pcon_off, const int* pcon_base, const int* pcon_deg, const int* pcon_i,
                          const int* pcon_j, const double* rvec, const int* active, const int* off3, const double* Hc,
                          double* H3) {
-  hipLaunchKernelGGL(agg_galerkin_kernel, dim3((n_pairs + 127) / 128), dim3(128), 0, s, n_pairs, pair_A, pair_pos, pair_B,
+  if (n_pairs <= 0) return;
+  hipLaunchKernelGGL(agg_galerkin_kernel, dim3((n_pairs + 15) / 16), dim3(256), 0, s, n_pairs, pair_A, pair_pos, pair_B,
                      pcon_off, pcon_base, pcon_deg, pcon_i, pcon_j, rvec, active, off3, Hc, H3);
 }
 

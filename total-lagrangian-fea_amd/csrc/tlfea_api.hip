@@ -2254,6 +2254,8 @@ struct tlfea_newton_s {
     PolyLevel vertex;  // the vertex level: Hc = P^T H P
     int *d_par0 = nullptr, *d_par1 = nullptr, *d_cblk_row = nullptr, *d_child_off = nullptr, *d_child = nullptr,
         *d_con_off = nullptr, *d_con_base = nullptr, *d_con_deg = nullptr;
+    int n_upper = 0;  // Galerkin gather: blocks with column >= row (d_c_upper), the rest mirrored through d_c_mirror
+    int *d_c_upper = nullptr, *d_c_mirror = nullptr;
     float *d_child_w = nullptr, *d_con_w = nullptr;
     double* d_coef = nullptr;  // the cycle's coefficient table (pmg_coef.h, PmgTable), kPmgTableCap doubles
     // multi-GPU: the coarse level is partitioned like the fine one (vertex nodes of the partition boundary are
@@ -2424,6 +2426,8 @@ struct tlfea_newton_s {
   int* d_own = nullptr;
   double* d_sc_mask = nullptr;
   double lam_max_loc = 0.0;
+  bool lmax_mf_ok = false;    // set by pcg() around its own set-up call: the fine lambda_max product may be matrix-free
+  bool lmax_used_mf = false;  // the last fine estimate used the matrix-free product (tlfea_newton_get_lambda_max)
   double hook_lam[3] = {0.0, 0.0, 0.0};  // lambda_max estimates of the last tlfea_newton_apply_preconditioner set-up
   bool sync_before_cb = true;
   tlfea_allreduce_fn ar = nullptr;
@@ -2544,7 +2548,7 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
     for (void* q : pd)
       if (q) (void)hipFree(q);
     void* pp[] = {m.d_par0, m.d_par1, m.d_cblk_row, m.d_child_off, m.d_child, m.d_con_off, m.d_con_base, m.d_con_deg,
-                  m.d_child_w, m.d_con_w, m.d_coef};
+                  m.d_child_w, m.d_con_w, m.d_coef, m.d_c_upper, m.d_c_mirror};
     for (void* q : pp)
       if (q) (void)hipFree(q);
     m.vertex.release();
@@ -4009,7 +4013,15 @@ static int estimate_lam_max_local(tlfea_newton_t s) {
   return 0;
 }
 
+// TLFEA_LMAX_MATFREE: 1 (default) = the fine power iteration's product runs through the matrix-free pair in
+// the solves whose CG iteration does, 0 = always the CSR product.  Read once per process.
+static bool lmax_matfree_env() {
+  static const bool on = !std::getenv("TLFEA_LMAX_MATFREE") || std::atoi(std::getenv("TLFEA_LMAX_MATFREE")) != 0;
+  return on;
+}
+
 static int estimate_lam_max(tlfea_newton_t s, const double* d_b) {
+  s->lmax_used_mf = false;
   if (s->ar && s->d_own && cheb_bits_eff(s) != 64) return estimate_lam_max_local(s);
   tlfea_t10_t d = s->d;
   const int N = s->N;
@@ -4026,12 +4038,19 @@ static int estimate_lam_max(tlfea_newton_t s, const double* d_b) {
   TRY(device_sumsq_async(s, s->d_eigv, s->d_w, nr));
   launch_scale_inv_sqrt(s->stream, nr, s->d_scal, s->d_eigv);
   const bool b12 = blk12_now(s);  // lambda_max of L^-1 H L^-T: v <- L^-1 H L^-T v
+  // inside pcg(), in a solve whose iteration runs the matrix-free product: the same product here (0.30 against 0.78 ms
+  // at config C).  Every other caller, the partitioned paths and the 12 x 12 scaling keep the CSR product.
+  const bool mf = s->lmax_mf_ok && s->mf.now && s->mf.d_ybuf && lmax_matfree_env() && !b12 && !s->ar && !s->halo.on;
+  s->lmax_used_mf = mf;
   for (int k = 0; k < iters; k++) {
     TRY(halo_refresh_f64(s, 0, 1, 3, s->d_eigv));
     if (b12) launch_blk12_apply(s->stream, N / 4, s->d_L12inv_f, true, s->d_eigv, s->d_cd);
     const double* vv = b12 ? s->d_cd : s->d_eigv;
-    launch_spmv_dir_dot(s->stream, Nr, d->inc(), s->d_H, vv, vv, 1, part(s, 1), part(s, 0), s->d_p2, s->d_q,
-                        part(s, 2), false, s->spmv_nt);
+    if (mf)
+      TRY(launch_matfree_product(s, vv, s->d_q, part(s, 2)));
+    else
+      launch_spmv_dir_dot(s->stream, Nr, d->inc(), s->d_H, vv, vv, 1, part(s, 1), part(s, 0), s->d_p2, s->d_q,
+                          part(s, 2), false, s->spmv_nt);
     if (s->ar) TRY(iface_sum(s, s->d_q, 3));
     if (b12) launch_blk12_apply(s->stream, N / 4, s->d_L12inv_f, false, s->d_q, s->d_eigv);
     else launch_apply_dinv(s->stream, Nr, s->d_Dinv, s->d_q, s->d_eigv);
@@ -4285,11 +4304,15 @@ static int pmg_prepare(tlfea_newton_t s) {
   TRY(upload_vec(&m.d_child_off, h.child_off)); TRY(upload_vec(&m.d_child, h.child)); TRY(upload_vec(&m.d_child_w, h.child_w));
   TRY(upload_vec(&m.d_con_off, h.con_off)); TRY(upload_vec(&m.d_con_base, h.con_base)); TRY(upload_vec(&m.d_con_deg, h.con_deg));
   TRY(upload_vec(&m.d_con_w, h.con_w));
+  m.n_upper = (int)h.c_upper.size();
+  TRY(upload_vec(&m.d_c_upper, h.c_upper)); TRY(upload_vec(&m.d_c_mirror, h.c_mirror));
   const size_t nc = 3 * (size_t)m.vertex.N;
   TRY(m.vertex.alloc_work());
   TRY(dmalloc(&m.d_coef, (size_t)kPmgTableCap));
   m.ok = true;
-  if (s->verbose) std::printf("p-multigrid: %d fine nodes -> %d vertex nodes, %d coarse blocks\n", d->N, m.vertex.N, m.vertex.nnz);
+  if (s->verbose)
+    std::printf("p-multigrid: %d fine nodes -> %d vertex nodes, %d coarse blocks (%d gathered from %zu contributions, the rest "
+                "mirrored)\n", d->N, m.vertex.N, m.vertex.nnz, m.n_upper, h.con_w.size());
   if (pmg_rop_possible(s)) {
     RopHost ro;
     if (pmg_restrict_op_build(d->N, d->h_off.data(), d->h_cols.data(), h, ro)) {
@@ -4528,8 +4551,8 @@ static int pmg_prepare(tlfea_newton_t s) {
 // Galerkin operators of the current H: Hc = P^T H P, H3 = P2^T Hc P2
 static void vertex_galerkin(tlfea_newton_t s) {
   auto& m = s->pmg;
-  launch_pmg_galerkin(s->stream, m.vertex.nnz, m.vertex.d_off, m.d_cblk_row, m.d_con_off, m.d_con_base, m.d_con_deg, m.d_con_w,
-                      s->d_H, m.vertex.d_H);
+  launch_pmg_galerkin(s->stream, m.n_upper, m.d_c_upper, m.d_c_mirror, m.vertex.d_off, m.d_cblk_row, m.d_con_off,
+                      m.d_con_base, m.d_con_deg, m.d_con_w, s->d_H, m.vertex.d_H);
 }
 static void level3_galerkin(tlfea_newton_t s) {
   auto& g = s->pmg.agg;
@@ -5370,7 +5393,10 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
     }
     s->last_deg = deg;
     s->last_bits = bits;
-    TRY(precond_setup(s, d_b, 1));
+    s->lmax_mf_ok = true;  // only this call may take the matrix-free lambda_max product (estimate_lam_max)
+    const int rc_setup = precond_setup(s, d_b, 1);
+    s->lmax_mf_ok = false;
+    if (rc_setup) return rc_setup;
     // hipGraph replay: single GPU, and the overlapping partition when its exchange is the built-in RCCL one (enqueued
     // from C++ on this stream, so the neighbour exchanges and all-reduces are captured with the kernels)
     bool graphs = s->use_graphs && !s->ar && !s->profiling && (!s->halo.on || (s->halo.native && halo_graph_wanted()));
@@ -5896,6 +5922,16 @@ extern "C" int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double
   return 0;
 }
 extern "C" int tlfea_newton_get_spmv_mode(tlfea_newton_t s) { return s ? s->mf.last_mode : -1; }
+// the last lambda_max estimates of the fine, vertex and third level (0 where there is none); out[3] = 1 if the last fine
+// estimate ran its products through the matrix-free pair
+extern "C" int tlfea_newton_get_lambda_max(tlfea_newton_t s, double out[4]) {
+  if (!s || !out) return fail("null argument");
+  out[0] = s->lam_max;
+  out[1] = s->pmg.ok ? s->pmg.vertex.lam : 0.0;
+  out[2] = s->pmg.agg.ok ? s->pmg.agg.lvl.lam : 0.0;
+  out[3] = s->lmax_used_mf ? 1.0 : 0.0;
+  return 0;
+}
 extern "C" int tlfea_newton_get_matfree_rows(tlfea_newton_t s, long long* rows, double* ratio) {
   if (!s || !s->mf.d_ybuf) return -1;
   if (rows) *rows = s->mf.compact ? s->mf.cp_rows : (long long)kNN * s->d->E;

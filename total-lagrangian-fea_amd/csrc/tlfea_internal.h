@@ -292,8 +292,9 @@ void launch_spmv32_rows(hipStream_t s, int n_rows, const int* rows, const int* s
 void launch_pmg_restrict_rows(hipStream_t s, int n_rows, const int* rows, const int* slots, const int* child_off,
                               const int* child, const float* child_w, const float* res_f, const double* sc_f, double* out);
 // two-level p-multigrid (T10): Galerkin coarse operator and grid transfers (pmg_host.h holds the integer set-up)
-void launch_pmg_galerkin(hipStream_t s, int nnz_c, const int* c_off, const int* cblk_row, const int* con_off,
-                         const int* con_base, const int* con_deg, const float* con_w, const double* Hf, double* Hc);
+void launch_pmg_galerkin(hipStream_t s, int n_upper, const int* c_upper, const int* c_mirror, const int* c_off,
+                         const int* cblk_row, const int* con_off, const int* con_base, const int* con_deg,
+                         const float* con_w, const double* Hf, double* Hc);
 void launch_pmg_restrict_init(hipStream_t s, int Nc, const int* child_off, const int* child, const float* child_w,
                               const float* res_f, const double* sc_f, const double* sc_c, const float* Dinv_c,
                               const double* coef_c, float* d_c, float* z_c, float* res_c, const int* bslot = nullptr,

@@ -407,6 +407,13 @@ class SyncedNewtonSolver:
         """product of the last solve's CG iterations: 0 CSR kernel, 1 matrix-free pair"""
         return int(self._lib.tlfea_newton_get_spmv_mode(self._h))
 
+    def GetLambdaMax(self):
+        """(fine, vertex, level3, matfree): the last lambda_max estimates of the three levels (0 where a level does not
+        exist) and whether the last fine estimate ran its products through the matrix-free pair"""
+        out = np.zeros(4)
+        check(self._lib.tlfea_newton_get_lambda_max(self._h, dp(out)))
+        return float(out[0]), float(out[1]), float(out[2]), bool(out[3] != 0.0)
+
     def GetMatfreeRows(self):
         """(form, rows, ratio) of the matrix-free pair's row buffer: form 1 = summed per wavefront and node, 0 = one row per
         (element, local node), -1 = the pair has not run; ratio = 10 E / rows"""
