@@ -511,6 +511,17 @@ int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double *x, double
 /* which product the CG iterations of the last linear solve used: 0 = CSR kernel, 1 = matrix-free pair
  * (TLFEA_SPMV_MATFREE=0|1 forces it off / on where eligible; default: eligible and at least 150 000 nodes) */
 int tlfea_newton_get_spmv_mode(tlfea_newton_t s);
+/* fine smoother of the p-multigrid cycle the last preconditioner set-up chose: 0 = stream of the low-precision copy,
+ * 1 = single-precision passes from the element records (DESIGN 3g'; TLFEA_PMG_FINE_MATFREE=0|1 forces it off / on where
+ * eligible; default: eligible and at least 400 000 nodes) */
+int tlfea_newton_get_fine_smoother(tlfea_newton_t s);
+/* Test hook: one fine smoother pass of that form (res^ -= Hs d ; d' = c1 d + c2 (SDS)^-1 res^ ; z^ += zw d') with the
+ * set-up a preceding tlfea_newton_apply_preconditioner left.  d, res, z: float [3N]; r: double [3N]; coef2 = (c1, c2); zw 0 =
+ * no weight.  d_out always; last = 0: z_out, res_out (float [3N]); last = 1: z64_out = S z^' (double [3N]) and the 512 r.z
+ * slots.  An error where the last set-up did not choose the form. */
+int tlfea_newton_fine_smoother_pass(tlfea_newton_t s, const float *d, const float *res, const float *z, const double *r,
+                                    const double *coef2, double zw, int last, float *d_out, float *z_out, float *res_out,
+                                    double *z64_out, double *rz_slots);
 /* the last lambda_max estimates: out[0] fine level, out[1] vertex level, out[2] third level (0 where there is none);
  * out[3] = 1 if the last fine estimate ran its products through the matrix-free pair (inside a solve whose CG iteration
  * does; TLFEA_LMAX_MATFREE=0 keeps the CSR product), else 0 */

@@ -209,6 +209,13 @@ def _pmg_signatures(lib):
     if hasattr(lib, "tlfea_newton_get_lambda_max"):  # an older build loaded through TLFEA_LIB_PATH (A/B runs) lacks it
         lib.tlfea_newton_get_lambda_max.argtypes = [vp, c_dp]
         lib.tlfea_newton_get_lambda_max.restype = C.c_int
+    if hasattr(lib, "tlfea_newton_get_fine_smoother"):
+        lib.tlfea_newton_get_fine_smoother.argtypes = [vp]
+        lib.tlfea_newton_get_fine_smoother.restype = C.c_int
+        c_fp = C.POINTER(C.c_float)
+        lib.tlfea_newton_fine_smoother_pass.argtypes = [vp, c_fp, c_fp, c_fp, c_dp, c_dp, C.c_double, C.c_int, c_fp, c_fp, c_fp,
+                                                        c_dp, c_dp]
+        lib.tlfea_newton_fine_smoother_pass.restype = C.c_int
 
 
 def _contact_signatures(lib):

@@ -2145,18 +2145,26 @@ constexpr int kMfLds = 64 * kMfG;   // doubles of wave-private LDS (g records, t
 constexpr int kMfcRows = 3 * kMfcSrc, kMfcOut = 3 * 64;
 constexpr int kMfLdsCp = kMfcRows + kMfcOut + 2 * kMfcSrc / 4;
 static_assert(4 * 2 * kMfLdsCp * 8 <= 160 * 1024, "four workgroups of tangent_apply_affine_kernel<true> per CU");
+// single precision (the fine smoother, DESIGN 3g'): the same layout in floats, the lists take twice the slots
+constexpr int kMfLdsCpF = kMfcRows + kMfcOut + kMfcSrc;
+// three waves per SIMD: 162 VGPRs and no scratch; four would need 128 VGPRs, which the compiler reaches with 272 bytes of scratch
+static_assert(6 * 2 * kMfLdsCpF * 4 <= 160 * 1024, "six workgroups of tangent_apply_affine_kernel<true, float> per CU");
+template <typename R> struct MfPair;
+template <> struct MfPair<double> { using type = double2; };
+template <> struct MfPair<float> { using type = float2; };
 }  // namespace
 
-template <bool CP>
-__global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int Epad, const int* __restrict__ conn,
-                                                                  const double* __restrict__ gvec,
-                                                                  const double* __restrict__ Fq16, MatfreeCoef mc,
-                                                                  const double* __restrict__ p,
-                                                                  double* __restrict__ ybuf, MatfreeCompact cp) {
-  constexpr int kLds = CP ? kMfLdsCp : kMfLds;
-  __shared__ __attribute__((aligned(16))) double st_all[2 * kLds];
-  double* st = st_all + (threadIdx.x >> 6) * kLds;  // this wavefront's slice
-  double2* st2 = reinterpret_cast<double2*>(st);
+// R: the real type of the records, the direction and the rows.  float: the direction is scl[c] p[c], formed at the load.
+template <bool CP, typename R = double>
+__global__ __launch_bounds__(128, sizeof(R) == 8 ? 2 : 3) void tangent_apply_affine_kernel(
+    int E, int Epad, const int* __restrict__ conn, const R* __restrict__ gvec, const R* __restrict__ Fq16, MatfreeCoefT<R> mc,
+    const R* __restrict__ p, R* __restrict__ ybuf, MatfreeCompact cp, const R* __restrict__ scl) {
+  using R2 = typename MfPair<R>::type;
+  constexpr bool kF = sizeof(R) == 4;
+  constexpr int kLds = CP ? (kF ? kMfLdsCpF : kMfLdsCp) : kMfLds;
+  __shared__ __attribute__((aligned(16))) R st_all[2 * kLds];
+  R* st = st_all + (threadIdx.x >> 6) * kLds;  // this wavefront's slice
+  R2* st2 = reinterpret_cast<R2*>(st);
   const int lane = threadIdx.x & 63;
   const int e0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);  // first element of this wavefront
   const int last = E - 1;
@@ -2187,7 +2195,7 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
 
   // ---- g records: 64 x 128 contiguous bytes, whole-line loads, each lane takes its own record from LDS ---------------
   {
-    const double2* src = reinterpret_cast<const double2*>(gvec);
+    const R2* src = reinterpret_cast<const R2*>(gvec);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const int idx = lane + 64 * j, el = idx >> 3, c = idx & 7;
@@ -2195,9 +2203,9 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
     }
   }
   // F records of the first point in flight: 64 x 80 bytes, 16 per lane and instruction
-  double2 nx[5];
+  R2 nx[5];
   auto fetch = [&](const int sdx) __attribute__((always_inline)) {
-    const double2* src = reinterpret_cast<const double2*>(Fq16);
+    const R2* src = reinterpret_cast<const R2*>(Fq16);
 #pragma unroll
     for (int j = 0; j < 5; j++) {
       const int idx = lane + 64 * j, el = idx / 5, c = idx - 5 * el;
@@ -2206,12 +2214,12 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
   };
   fetch(0);
   wave_sync();
-  double g[4][3], detJ;
+  R g[4][3], detJ;
   {
-    const double* gr = st + lane * kMfG;
+    const R* gr = st + lane * kMfG;
 #pragma unroll
     for (int n = 0; n < 4; n++) {
-      const double2 a = *reinterpret_cast<const double2*>(gr + 4 * n);
+      const R2 a = *reinterpret_cast<const R2*>(gr + 4 * n);
       g[n][0] = a.x;
       g[n][1] = a.y;
       g[n][2] = gr[4 * n + 2];
@@ -2220,42 +2228,46 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
   }
 
   // ---- dF at the five points (slot order: centroid, then the point of vertex 0..3), one component of p at a time -------
-  double D[5][9], Wm[kNQ][3];
+  R D[5][9], Wm[kNQ][3];
   {
     int gn[kNN];
 #pragma unroll
     for (int a = 0; a < kNN; a++) gn[a] = conn[(size_t)a * E + e];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-      double pc[kNN];
+      R pc[kNN];
 #pragma unroll
-      for (int a = 0; a < kNN; a++) pc[a] = p[3 * (size_t)gn[a] + i];
+      for (int a = 0; a < kNN; a++) {
+        const size_t c = 3 * (size_t)gn[a] + i;
+        if constexpr (kF) pc[a] = scl[c] * p[c];
+        else pc[a] = p[c];
+      }
       // mid-edge nodes 4..9 = (0,1) (1,2) (0,2) (0,3) (1,3) (2,3)   (FEAT10Data.cu:143)
-      const double S[4] = {pc[4] + pc[6] + pc[7], pc[4] + pc[5] + pc[8], pc[5] + pc[6] + pc[9], pc[7] + pc[8] + pc[9]};
+      const R S[4] = {pc[4] + pc[6] + pc[7], pc[4] + pc[5] + pc[8], pc[5] + pc[6] + pc[9], pc[7] + pc[8] + pc[9]};
       // column v: p of vertex v and of the mid-edge nodes (n, v)
-      const double Cv[4][4] = {{pc[0], pc[4], pc[6], pc[7]}, {pc[4], pc[1], pc[5], pc[8]}, {pc[6], pc[5], pc[2], pc[9]},
+      const R Cv[4][4] = {{pc[0], pc[4], pc[6], pc[7]}, {pc[4], pc[1], pc[5], pc[8]}, {pc[6], pc[5], pc[2], pc[9]},
                                {pc[7], pc[8], pc[9], pc[3]}};
 #pragma unroll
       for (int d = 0; d < 3; d++) {
-        double c0 = 0.0, w = 0.0;
+        R c0 = R(0), w = R(0);
 #pragma unroll
         for (int n = 0; n < 4; n++) {
           c0 += S[n] * g[n][d];
-          w += ((2.0 / 3.0) * S[n] - (1.0 / 3.0) * pc[n]) * g[n][d];
+          w += (R(2.0 / 3.0) * S[n] - R(1.0 / 3.0) * pc[n]) * g[n][d];
         }
         D[0][3 * i + d] = c0;
 #pragma unroll
         for (int v = 0; v < 4; v++) {
-          double t = 0.0;
+          R t = R(0);
 #pragma unroll
           for (int n = 0; n < 4; n++) t += Cv[v][n] * g[n][d];
-          D[1 + v][3 * i + d] = w + (4.0 / 3.0) * t;
+          D[1 + v][3 * i + d] = w + R(4.0 / 3.0) * t;
         }
       }
       // mass: sum_j N_j(q) p_j at the rule's points (rule order)
 #pragma unroll
       for (int q = 0; q < kNQ; q++) {
-        double w = 0.0;
+        R w = R(0);
 #pragma unroll
         for (int a = 0; a < kNN; a++) w += mc.Nq[q][a] * pc[a];
         Wm[q][i] = w;
@@ -2264,7 +2276,7 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
   }
 #pragma unroll
   for (int q = 0; q < kNQ; q++) {
-    const double cq = mc.rho_inv_h * detJ * mc.mw[q];
+    const R cq = mc.rho_inv_h * detJ * mc.mw[q];
 #pragma unroll
     for (int i = 0; i < 3; i++) Wm[q][i] *= cq;
   }
@@ -2277,11 +2289,11 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
     for (int j = 0; j < 5; j++) st2[lane + 64 * j] = nx[j];
     if (sdx < 4) fetch(sdx + 1);
     wave_sync();
-    const double2* R2 = reinterpret_cast<const double2*>(st + lane * 10);
-    const double2 r0 = R2[0], r1 = R2[1], r2 = R2[2], r3 = R2[3], r4 = R2[4];
-    const double F[3][3] = {{r0.x, r0.y, r1.x}, {r1.y, r2.x, r2.y}, {r3.x, r3.y, r4.x}};
-    double(&dF)[9] = D[sdx];
-    double C[3][3], G[3][3];
+    const R2* Fr = reinterpret_cast<const R2*>(st + lane * 10);
+    const R2 r0 = Fr[0], r1 = Fr[1], r2 = Fr[2], r3 = Fr[3], r4 = Fr[4];
+    const R F[3][3] = {{r0.x, r0.y, r1.x}, {r1.y, r2.x, r2.y}, {r3.x, r3.y, r4.x}};
+    R(&dF)[9] = D[sdx];
+    R C[3][3], G[3][3];
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -2289,19 +2301,19 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
         C[i][j] = F[0][i] * F[0][j] + F[1][i] * F[1][j] + F[2][i] * F[2][j];
         G[i][j] = F[0][i] * dF[j] + F[1][i] * dF[3 + j] + F[2][i] * dF[6 + j];
       }
-    const double trE = 0.5 * (C[0][0] + C[1][1] + C[2][2] - 3.0);
-    const double trG = G[0][0] + G[1][1] + G[2][2];
-    const double k0 = mc.cl * trE - mc.c1;  // h (lambda tr E - mu)   (SVK.cuh:35-55)
-    double M1[3][3], M2[3][3];              // S_h = k0 I + h mu F^T F ; dS = a tr(dE) I + b (G + G^T)
+    const R trE = R(0.5) * (C[0][0] + C[1][1] + C[2][2] - R(3));
+    const R trG = G[0][0] + G[1][1] + G[2][2];
+    const R k0 = mc.cl * trE - mc.c1;  // h (lambda tr E - mu)   (SVK.cuh:35-55)
+    R M1[3][3], M2[3][3];              // S_h = k0 I + h mu F^T F ; dS = a tr(dE) I + b (G + G^T)
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int j = 0; j < 3; j++) {
-        M1[i][j] = mc.c1 * C[i][j] + (i == j ? k0 : 0.0);
-        M2[i][j] = mc.b * (G[i][j] + G[j][i]) + (i == j ? mc.a * trG : 0.0);
+        M1[i][j] = mc.c1 * C[i][j] + (i == j ? k0 : R(0));
+        M2[i][j] = mc.b * (G[i][j] + G[j][i]) + (i == j ? mc.a * trG : R(0));
       }
-    const double dV = detJ * (sdx == 0 ? mc.w0 : mc.w1);
-    double Pn[9];
+    const R dV = detJ * (sdx == 0 ? mc.w0 : mc.w1);
+    R Pn[9];
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -2313,9 +2325,9 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
   }
 
   // ---- rows out: [a][Epad][3], a wavefront's 64 rows of local node a are 1 536 contiguous bytes -----------------------
-  double SPg[4][3], Bg[4][3];  // SP g_n and (P_0 + 2/3 SP) g_n
+  R SPg[4][3], Bg[4][3];  // SP g_n and (P_0 + 2/3 SP) g_n
   {
-    double SP[9];
+    R SP[9];
 #pragma unroll
     for (int t = 0; t < 9; t++) SP[t] = (D[1][t] + D[2][t]) + (D[3][t] + D[4][t]);
 #pragma unroll
@@ -2323,33 +2335,33 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
 #pragma unroll
       for (int i = 0; i < 3; i++) {
         SPg[n][i] = SP[3 * i] * g[n][0] + SP[3 * i + 1] * g[n][1] + SP[3 * i + 2] * g[n][2];
-        Bg[n][i] = D[0][3 * i] * g[n][0] + D[0][3 * i + 1] * g[n][1] + D[0][3 * i + 2] * g[n][2] + (2.0 / 3.0) * SPg[n][i];
+        Bg[n][i] = D[0][3 * i] * g[n][0] + D[0][3 * i + 1] * g[n][1] + D[0][3 * i + 2] * g[n][2] + R(2.0 / 3.0) * SPg[n][i];
       }
   }
 #pragma unroll
   for (int a = 0; a < kNN; a++) {
     const int A = (0x904e4 >> (2 * a)) & 3;  // {0,1,2,3,0,1,0,0,1,2}: vertex a, or the ends (A, B) of mid-edge a
     const int B = (0xfe9e4 >> (2 * a)) & 3;  // {0,1,2,3,1,2,2,3,3,3}
-    double y[3];
+    R y[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
       if (a < 4) {
-        const double* P = D[1 + a];
-        y[i] = (4.0 / 3.0) * (P[3 * i] * g[a][0] + P[3 * i + 1] * g[a][1] + P[3 * i + 2] * g[a][2]) - (1.0 / 3.0) * SPg[a][i];
+        const R* P = D[1 + a];
+        y[i] = R(4.0 / 3.0) * (P[3 * i] * g[a][0] + P[3 * i + 1] * g[a][1] + P[3 * i + 2] * g[a][2]) - R(1.0 / 3.0) * SPg[a][i];
       } else {
-        const double *PA = D[1 + A], *PB = D[1 + B];
+        const R *PA = D[1 + A], *PB = D[1 + B];
         y[i] = Bg[A][i] + Bg[B][i] +
-               (4.0 / 3.0) * (PB[3 * i] * g[A][0] + PB[3 * i + 1] * g[A][1] + PB[3 * i + 2] * g[A][2] + PA[3 * i] * g[B][0] +
+               R(4.0 / 3.0) * (PB[3 * i] * g[A][0] + PB[3 * i + 1] * g[A][1] + PB[3 * i + 2] * g[A][2] + PA[3 * i] * g[B][0] +
                               PA[3 * i + 1] * g[B][1] + PA[3 * i + 2] * g[B][2]);
       }
-      double mr = 0.0;  // (M_e p)_a / h
+      R mr = R(0);  // (M_e p)_a / h
 #pragma unroll
       for (int q = 0; q < kNQ; q++) mr += mc.Nq[q][a] * Wm[q][i];
       y[i] += mr;
     }
     if (CP) {  // parked: row a * 64 + lane (the F records of the last point have been read: the barrier before a = 0)
       if (a == 0) wave_sync();
-      double* r = st + 3 * (a * 64 + lane);
+      R* r = st + 3 * (a * 64 + lane);
       r[0] = y[0];
       r[1] = y[1];
       r[2] = y[2];
@@ -2361,7 +2373,7 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
     st[3 * lane + 2] = y[2];
     wave_sync();
     if (e0 < E) {  // rows past E: padding
-      double2* out = reinterpret_cast<double2*>(ybuf + ((size_t)a * Epad + e0) * 3);
+      R2* out = reinterpret_cast<R2*>(ybuf + ((size_t)a * Epad + e0) * 3);
       out[lane] = st2[lane];
       if (lane < 32) out[64 + lane] = st2[64 + lane];
     }
@@ -2372,13 +2384,13 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
   wave_sync();
   const unsigned short* lsrc = reinterpret_cast<const unsigned short*>(st + kMfcRows + kMfcOut);
   const unsigned short* ldesc = lsrc + kMfcSrc;
-  double* outp = st + kMfcRows;
+  R* outp = st + kMfcRows;
   for (int s0 = 0; s0 < n_rows; s0 += 64) {
-    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+    R r0 = R(0), r1 = R(0), r2 = R(0);
     if (s0 + lane < n_rows) {
       const int dsc = ldesc[s0 + lane], k0 = dsc & ((1 << kMfcStartBits) - 1), k1 = k0 + (dsc >> kMfcStartBits) + 1;
       for (int k = k0; k < k1; k++) {
-        const double* r = st + 3 * (int)lsrc[k];
+        const R* r = st + 3 * (int)lsrc[k];
         r0 += r[0];
         r1 += r[1];
         r2 += r[2];
@@ -2390,7 +2402,7 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
     outp[3 * lane + 2] = r2;
     wave_sync();
     const int nd = 3 * min(64, n_rows - s0);
-    double* dst = ybuf + 3 * ((size_t)row0 + s0);
+    R* dst = ybuf + 3 * ((size_t)row0 + s0);
 #pragma unroll
     for (int t = 0; t < 3; t++)
       if (lane + 64 * t < nd) dst[lane + 64 * t] = outp[lane + 64 * t];
@@ -2400,11 +2412,16 @@ __global__ __launch_bounds__(128, 2) void tangent_apply_affine_kernel(int E, int
 void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineView& av, const double* Fq16,
                                  const MatfreeCoef& mc, const double* p, double* ybuf, const MatfreeCompact* cp) {
   if (cp)
-    hipLaunchKernelGGL(tangent_apply_affine_kernel<true>, dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
-                       av.gvec, Fq16, mc, p, ybuf, *cp);
+    hipLaunchKernelGGL((tangent_apply_affine_kernel<true, double>), dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
+                       av.gvec, Fq16, mc, p, ybuf, *cp, (const double*)nullptr);
   else
-    hipLaunchKernelGGL(tangent_apply_affine_kernel<false>, dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
-                       av.gvec, Fq16, mc, p, ybuf, MatfreeCompact{});
+    hipLaunchKernelGGL((tangent_apply_affine_kernel<false, double>), dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
+                       av.gvec, Fq16, mc, p, ybuf, MatfreeCompact{}, (const double*)nullptr);
+}
+
+void launch_fine_matfree_apply(hipStream_t s, const ElemView& m, const FineMatfree& f, const float* d, const MatfreeCompact& cp) {
+  hipLaunchKernelGGL((tangent_apply_affine_kernel<true, float>), dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
+                     f.gvec, f.Fq, f.mc, d, f.ybuf, cp, f.scn);
 }
 
 // q = sum of the node's element rows (+ h^2 rho p on pinned rows, as the "rows out" phase of assemble_affine_kernel adds
@@ -2471,6 +2488,105 @@ void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc,
   } else
     hipLaunchKernelGGL(matfree_gather_kernel<false>, dim3(grid), dim3(1024), 0, s, N, Epad, inc, ybuf, p, fixed_slot, nw,
                        penalty, q, pq_part);
+}
+
+// Second launch of a fine smoother pass from the element records (FineMatfree, DESIGN 3g'): matfree_gather_kernel<true> in
+// single precision -- 8 lanes per node, the node's compact rows in ascending order, fixed-order butterfly -- then
+//   (Hs d)_i = tau scn_i (sum + nw_i h^2 rho / m0 x_i [pinned rows])       x = scn d, tau = m0 sigma^2
+// and the epilogue of cheb32_kernel on lanes 0..2: res^ -= Hs d ; d' = c1 d + c2 (SDS)^-1 res^ ; z^ += zw d'.  LAST: z = S z^
+// in fp64 and the r.z slots (at most kNPart workgroups, slots without one read 0).  No atomics.
+template <bool LAST>
+__global__ __launch_bounds__(1024) void fine_matfree_step_kernel(
+    int N, const int* __restrict__ n2r_off, const int* __restrict__ n2r, const float* __restrict__ ybuf,
+    const float* __restrict__ scn, const double* __restrict__ ss, double inv_n, double m0, double pen_m0,
+    const int* __restrict__ fixed_slot, const double* __restrict__ nw, const float* __restrict__ Dinv_f,
+    const double* __restrict__ sc, const float* __restrict__ d_old, const double* __restrict__ coef,
+    const double* __restrict__ zw, float* __restrict__ d_new, const float* __restrict__ z, float* __restrict__ z_new,
+    const float* __restrict__ res, float* __restrict__ res_new, const double* __restrict__ r, double* __restrict__ z_out,
+    double* __restrict__ rz_part) {
+  __shared__ double sh[16];
+  const float c1 = (float)coef[0], c2 = (float)coef[1];
+  const float zwf = zw ? (float)zw[0] : 1.f;
+  const float tau = (float)(m0 * (ss[0] * inv_n));
+  const int l8 = threadIdx.x & 7, grp = threadIdx.x >> 3;
+  const int c = l8 < 3 ? l8 : 0;
+  const int per = ((N + gridDim.x - 1) / gridDim.x + 127) / 128 * 128;  // whole tiles of 128 nodes
+  const int r0 = blockIdx.x * per, r1 = min(N, r0 + per);
+  double rz = 0.0;
+  for (int i = r0 + grp; i < r1; i += 128) {
+    // the epilogue's operands first (every lane loads, the group's addresses coincide), the rows behind them
+    const int k0 = n2r_off[i], k1 = n2r_off[i + 1];
+    const float s0 = scn[3 * i], s1 = scn[3 * i + 1], s2 = scn[3 * i + 2];
+    const float x0 = s0 * d_old[3 * i], x1 = s1 * d_old[3 * i + 1], x2 = s2 * d_old[3 * i + 2];
+    const float q0 = res[3 * i], q1 = res[3 * i + 1], q2 = res[3 * i + 2];
+    const float* D = Dinv_f + (size_t)9 * i + 3 * c;
+    const float D0 = D[0], D1 = D[1], D2 = D[2];
+    const float dc = d_old[3 * i + c], zc = z[3 * i + c];
+    float pw = 0.f;
+    if (fixed_slot && fixed_slot[i] >= 0) pw = (float)((nw ? nw[i] : 1.0) * pen_m0);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int k = k0 + l8; k < k1; k += 8) {
+      const float* y = ybuf + (size_t)n2r[k] * 3;
+      a0 += y[0];
+      a1 += y[1];
+      a2 += y[2];
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+      a0 += __shfl_xor(a0, o);
+      a1 += __shfl_xor(a1, o);
+      a2 += __shfl_xor(a2, o);
+    }
+    if (l8 < 3) {
+      const float t0 = tau * s0 * (a0 + pw * x0), t1 = tau * s1 * (a1 + pw * x1), t2 = tau * s2 * (a2 + pw * x2);
+      const float e0 = q0 - t0, e1 = q1 - t1, e2 = q2 - t2;
+      const float dn = c1 * dc + c2 * (D0 * e0 + D1 * e1 + D2 * e2);
+      const float zn = zc + zwf * dn;
+      d_new[3 * i + c] = dn;
+      if (LAST) {
+        const double zt = sc[3 * i + c] * (double)zn;
+        z_out[3 * i + c] = zt;
+        rz += r[3 * i + c] * zt;
+      } else {
+        z_new[3 * i + c] = zn;
+        res_new[3 * i + c] = (c == 0) ? e0 : ((c == 1) ? e1 : e2);
+      }
+    }
+  }
+  if (!LAST) return;
+  // fixed order: wave butterfly, then the waves in ascending order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rz += __shfl_xor(rz, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = rz;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int k = 0; k < (int)(blockDim.x >> 6); k++) t += sh[k];
+    rz_part[blockIdx.x] = t;
+  }
+  if (blockIdx.x == 0)  // slots without a workgroup read 0
+    for (int k = gridDim.x + threadIdx.x; k < kNPart; k += blockDim.x) rz_part[k] = 0.0;
+}
+
+void launch_fine_matfree_step(hipStream_t s, int N, const FineMatfree& f, const MatfreeCompact& cp, const float* Dinv_f,
+                              const double* sc, const float* d_old, const double* coef, const double* zw, float* d_new,
+                              const float* z, float* z_new, const float* res, float* res_new, const double* r, double* z_out,
+                              double* rz_part, bool last) {
+  const dim3 g(std::max(1, std::min(kNPart, (N + 127) / 128))), b(1024);
+#define TLFEA_FMF_ARGS N, cp.n2r_off, cp.n2r, f.ybuf, f.scn, f.ss, f.inv_n, f.m0, f.pen_m0, f.fixed_slot, f.nw, Dinv_f, sc, d_old, coef, zw, d_new, z, z_new, res, res_new, r, z_out, rz_part
+  if (last) hipLaunchKernelGGL(fine_matfree_step_kernel<true>, g, b, 0, s, TLFEA_FMF_ARGS);
+  else hipLaunchKernelGGL(fine_matfree_step_kernel<false>, g, b, 0, s, TLFEA_FMF_ARGS);
+#undef TLFEA_FMF_ARGS
+}
+
+__global__ void fine_matfree_scale_kernel(int n, const double* __restrict__ sc, const double* __restrict__ ss, double inv_n,
+                                          float* __restrict__ scn) {
+  const double inv_sigma = 1.0 / sqrt(ss[0] * inv_n);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) scn[i] = (float)(sc[i] * inv_sigma);
+}
+void launch_fine_matfree_scale(hipStream_t s, int n, const double* sc, const double* ss, double inv_n, float* scn) {
+  hipLaunchKernelGGL(fine_matfree_scale_kernel, dim3(std::max(1, std::min(4096, (n + 255) / 256))), dim3(256), 0, s, n, sc, ss,
+                     inv_n, scn);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1688,6 +1688,73 @@ __global__ __launch_bounds__(256) void pmg_rop_build_kernel(
     R1[b] = (float)(sI[2] * acc[8]);
   }
 }
+// The same R from the fp64 rows of H itself, for the cycle whose fine smoother applies the exact operator (DESIGN 3g': the
+// smoother and the restriction must see one operator).  With Hs = S_f H S_f the quotient cancels:
+//   R[I,j]_de = sc_c[I,d] * (sum_{i in children(I)} w_i H[i,j]_de) * sc_f[j,e]
+// The same lists, the same order of the sum (ascending child), the table in LDS holds each child's weight and where its
+// row of H lies (H of row i: [d][block][e] from 9 off[i], the layout lp_convert_kernel reads).
+__global__ __launch_bounds__(256) void pmg_rop_build_h_kernel(
+    int Nc, const int* __restrict__ r_off, const int* __restrict__ r_cols, const int* __restrict__ con_off,
+    const int* __restrict__ con_blk, const unsigned char* __restrict__ con_ord, const int* __restrict__ ch_off,
+    const int* __restrict__ ch, const float* __restrict__ ch_w, const int* __restrict__ f_off, const double* __restrict__ Hval,
+    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8, float* __restrict__ R1) {
+  __shared__ double tabw[8][kRopTab];
+  __shared__ int tabo[8][kRopTab][2];
+  const int lane = threadIdx.x & 31, rw = threadIdx.x >> 5;
+  const int I = blockIdx.x * 8 + rw;
+  if (I >= Nc) return;
+  const double sI[3] = {sc_c[3 * I], sc_c[3 * I + 1], sc_c[3 * I + 2]};
+  const int c0 = ch_off[I], b1 = r_off[I + 1];
+  const int n_tab = min(ch_off[I + 1] - c0, kRopTab);
+  for (int c = lane; c < n_tab; c += 32) {
+    const int i = ch[c0 + c];
+    tabw[rw][c] = (double)ch_w[c0 + c];
+    tabo[rw][c][0] = f_off[i];
+    tabo[rw][c][1] = f_off[i + 1] - f_off[i];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int b = r_off[I] + lane; b < b1; b += 32) {
+    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int t1 = con_off[b + 1];
+    // unrolled so that the blocks of four contributions are requested together; the sum keeps the list's order
+#pragma unroll 4
+    for (int t = con_off[b]; t < t1; t++) {
+      const int g = con_blk[t], ord = (int)con_ord[t];
+      double w;
+      int o0, deg;
+      if (ord < kRopTab) {
+        w = tabw[rw][ord];
+        o0 = tabo[rw][ord][0];
+        deg = tabo[rw][ord][1];
+      } else {
+        const int i = ch[c0 + ord];
+        w = (double)ch_w[c0 + ord];
+        o0 = f_off[i];
+        deg = f_off[i + 1] - o0;
+      }
+      const double* Hb = Hval + (size_t)9 * o0 + 3 * (size_t)(g - o0);
+#pragma unroll
+      for (int d = 0; d < 3; d++)
+#pragma unroll
+        for (int e = 0; e < 3; e++) acc[3 * d + e] += w * Hb[(size_t)d * 3 * deg + e];
+    }
+    const int j = r_cols[b];
+    const double sj[3] = {sc_f[3 * j], sc_f[3 * j + 1], sc_f[3 * j + 2]};
+    Blk8<float> out;
+#pragma unroll
+    for (int k = 0; k < 8; k++) out.v[k] = (float)(sI[k / 3] * acc[k] * sj[k % 3]);
+    R8[b] = out;
+    R1[b] = (float)(sI[2] * acc[8] * sj[2]);
+  }
+}
+void launch_pmg_rop_build_h(hipStream_t s, int Nc, const int* r_off, const int* r_cols, const int* con_off, const int* con_blk,
+                            const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const int* f_off,
+                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1) {
+  hipLaunchKernelGGL(pmg_rop_build_h_kernel, dim3((Nc + 7) / 8), dim3(256), 0, s, Nc, r_off, r_cols, con_off, con_blk, con_ord,
+                     ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, (Blk8<float>*)R8, R1);
+}
 void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
                           const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,
                           const void* B1, int bits, const double* sc_f, const double* sc_c, void* R8, float* R1) {

@@ -2351,7 +2351,20 @@ struct tlfea_newton_s {
     double cp_ratio = 0.0;       // 10 E / rows
     bool now = false;           // the running / last solve takes the matrix-free product
     int last_mode = 0;           // tlfea_newton_get_spmv_mode
+    long gen = 0;                // counts the assemblies that claimed the records (fine smoother: whose records its copies are)
   } mf;
+  // Fine smoother of the p-multigrid cycle from the element records (DESIGN 3g'): float copies of gvec and d_Fq, the
+  // normalised scaling, and the choice the last preconditioner set-up took.  The copies belong to assembly `gen`; an
+  // application that finds mf.valid cleared or another assembly fails (pmg_apply).
+  struct FineMf {
+    bool now = false;            // the last preconditioner set-up chose it (taken once, before R is built)
+    int last = 0;                // tlfea_newton_get_fine_smoother
+    long gen = -1;               // mf.gen the float F records were converted at
+    bool g_ok = false;           // the float g records are those of the current affine set-up
+    float *d_g32 = nullptr, *d_F32 = nullptr, *d_scn = nullptr;
+    double* d_ss = nullptr;      // sum(sc^2)
+    FineMatfree v{};
+  } fmf;
   // sparse direct solve (lin.method == 1): rocSOLVER re-factorisation on a host-computed ordering + factor pattern
   struct Direct {
     bool tried = false, ok = false;
@@ -2535,6 +2548,10 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
   if (s->d_Fq) (void)hipFree(s->d_Fq);
   if (s->d_mbuf) (void)hipFree(s->d_mbuf);
   if (s->mf.d_ybuf) (void)hipFree(s->mf.d_ybuf);
+  if (s->fmf.d_g32) (void)hipFree(s->fmf.d_g32);
+  if (s->fmf.d_F32) (void)hipFree(s->fmf.d_F32);
+  if (s->fmf.d_scn) (void)hipFree(s->fmf.d_scn);
+  if (s->fmf.d_ss) (void)hipFree(s->fmf.d_ss);
   for (void* p : s->mf.d_cp)
     if (p) (void)hipFree(p);
   direct_destroy(s);
@@ -2675,6 +2692,7 @@ static int setup_affine_form(tlfea_newton_t s, bool* affine_out) {
   TRY(dmalloc(&d_dev, 1));
   HIP_TRY(hipMemsetAsync(d_dev, 0, sizeof(double), d->stream));
   av.gvec = s->d_gvec;
+  s->fmf.g_ok = false;
   launch_affine_pre(d->stream, d->view(), av, s->d_gvec, d_dev);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(d->stream));
@@ -3622,6 +3640,7 @@ static void launch_fused(tlfea_newton_t s) {
     f.fixed = fixed;
     f.penalty = p.time_step * p.time_step * p.rho;
     f.valid = !d->d_emat && !lincons_on(s) && d->obs.n == 0;
+    f.gen++;
   } else
     launch_assemble_direct(s->stream, d->view(), d->mat, p.time_step, s->rg, s->d_Fq, d->d_mval, fixed, s->d_nw,
                            p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
@@ -4232,6 +4251,99 @@ static bool pmg_rop_on(tlfea_newton_t s) {
   return fb == 16 || fb == 32;
 }
 static bool pmg_rop_now(tlfea_newton_t s) { return pmg_rop_on(s) && s->pmg.rop.built; }
+
+// ---- fine smoother from the element records (DESIGN 3g') ----------------------------------------------------------------
+// TLFEA_PMG_FINE_MATFREE: 0 never, 1 wherever eligible, unset = eligible and at least kFineMatfreeMinRows node rows.  Read once.
+static int fine_matfree_env() {
+  static const int m =
+      std::getenv("TLFEA_PMG_FINE_MATFREE") ? (std::atoi(std::getenv("TLFEA_PMG_FINE_MATFREE")) != 0 ? 1 : 0) : -1;
+  return m;
+}
+// Measured on the SVK bars (DESIGN 3g'): 172 k nodes lose 6 % (three smoother terms, and the fp16 copy of that size is
+// served from the last-level cache), 402 k gain 8 %, 1.34 M gain 10 %; between 172 k and 402 k nothing was measured, so the
+// pick starts just below the smallest size measured to win.
+constexpr int kFineMatfreeMinRows = 400000;
+// Eligible: where the CG's matrix-free product is (compact rows), inside the p-multigrid cycle with the restriction through
+// the stored operator and the first-kind smoother, on one GPU, with the fine storage left at auto.  TLFEA_SPMV_MATFREE does
+// not enter: forcing the CG's product on a small mesh leaves the smoother on the low-precision copy.
+static double fine_matfree_m0(tlfea_newton_t s) {  // the material scalars are divided by their largest
+  const MatfreeCoef& mc = s->mf.mc;
+  return std::max(std::max(std::fabs(mc.a), std::fabs(mc.b)), std::max(std::fabs(mc.c1), std::fabs(mc.cl)));
+}
+static bool fine_matfree_chosen(tlfea_newton_t s) {
+  if (fine_matfree_env() == 0 || !matfree_eligible(s) || !matfree_compact_env()) return false;
+  if (cheb_degree_eff(s) <= 1 || precond_eff(s) != 2 || !pmg_rop_now(s) || pmg_smoother_kind() != 1) return false;
+  if (!(fine_matfree_m0(s) > 0.0)) return false;
+  if (s->ar || s->halo.on || s->lin.cheb_bits != 0 || fine_bits(s) != 16) return false;
+  return fine_matfree_env() == 1 || s->N >= kFineMatfreeMinRows;
+}
+// The choice of a set-up is taken ONCE, by pmg_build_level before it builds R (rop.built already set), with the compact
+// lists in place; the build of R and fine_matfree_setup both follow fmf.now.
+static int fine_matfree_choose(tlfea_newton_t s) {
+  auto& f = s->fmf;
+  f.now = fine_matfree_chosen(s);
+  if (f.now) {
+    TRY(matfree_ensure_buffer(s));
+    f.now = s->mf.compact;
+  }
+  f.last = f.now ? 1 : 0;
+  return 0;
+}
+// The choice of this preconditioner set-up and, where taken, the float copies of the records H was assembled from, the
+// normalised scaling and the scalars (FineMatfree, tlfea_internal.h).  After lp_build (d_sc) and pmg_build_level (R).
+static int fine_matfree_setup(tlfea_newton_t s) {
+  auto& f = s->fmf;
+  tlfea_t10_t d = s->d;
+  const MatfreeCoef& mc = s->mf.mc;
+  const double m0 = fine_matfree_m0(s);
+  if (!f.now) return 0;
+  const size_t n = 3 * (size_t)s->N;
+  if (!f.d_g32) {
+    TRY(dmalloc(&f.d_g32, (size_t)d->E * 16));
+    TRY(dmalloc(&f.d_F32, (size_t)d->E * 50));
+    TRY(dmalloc(&f.d_scn, n));
+    TRY(dmalloc(&f.d_ss, 1));
+    f.g_ok = false;
+  }
+  if (!f.g_ok) launch_to_float(s->stream, (size_t)d->E * 16, s->d_gvec, f.d_g32);
+  f.g_ok = true;
+  launch_to_float(s->stream, (size_t)d->E * 50, s->d_Fq, f.d_F32);
+  f.gen = s->mf.gen;
+  launch_norm2(s->stream, s->d_sc, nullptr, (int)n, part(s, 5), f.d_ss);
+  launch_fine_matfree_scale(s->stream, (int)n, s->d_sc, f.d_ss, 1.0 / (double)n, f.d_scn);
+  FineMatfree& v = f.v;
+  v.mc.a = (float)(mc.a / m0); v.mc.b = (float)(mc.b / m0); v.mc.c1 = (float)(mc.c1 / m0); v.mc.cl = (float)(mc.cl / m0);
+  v.mc.w0 = (float)mc.w0; v.mc.w1 = (float)mc.w1;
+  v.mc.rho_inv_h = (float)(mc.rho_inv_h / m0);
+  for (int q = 0; q < kNQ; q++) {
+    v.mc.mw[q] = (float)mc.mw[q];
+    for (int k = 0; k < kNN; k++) v.mc.Nq[q][k] = (float)mc.Nq[q][k];
+  }
+  v.m0 = m0;
+  v.pen_m0 = s->mf.penalty / m0;
+  v.gvec = f.d_g32; v.Fq = f.d_F32; v.scn = f.d_scn; v.ss = f.d_ss;
+  v.inv_n = 1.0 / (double)n;
+  v.ybuf = reinterpret_cast<float*>(s->mf.d_ybuf);  // the CG's product and the smoother never overlap: one buffer
+  v.fixed_slot = s->mf.fixed; v.nw = s->d_nw;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// the scalars the pair's kernels take BY VALUE (a captured graph holds them): part of the CG graphs' key
+static long fine_matfree_key(tlfea_newton_t s) {
+  if (!s->fmf.now) return 0;
+  const FineMatfree& v = s->fmf.v;
+  const double dv[3] = {v.m0, v.pen_m0, v.inv_n};
+  const float fv[7] = {v.mc.a, v.mc.b, v.mc.c1, v.mc.cl, v.mc.w0, v.mc.w1, v.mc.rho_inv_h};
+  unsigned long long h = 1469598103934665603ULL;  // FNV-1a over the bytes
+  auto mix = [&](const void* p, size_t n) {
+    for (size_t k = 0; k < n; k++) h = (h ^ ((const unsigned char*)p)[k]) * 1099511628211ULL;
+  };
+  mix(dv, sizeof dv);
+  mix(fv, sizeof fv);
+  return (long)h;
+}
+// this pass may read the float records: chosen at the set-up, and the records are still those of that assembly
+static bool fine_matfree_live(tlfea_newton_t s) { return s->fmf.now && s->mf.valid && s->fmf.gen == s->mf.gen; }
 // Third level (rigid-body-mode aggregates below the vertex level): opt-in with TLFEA_PMG_LEVELS=3.  Measured at config C
 // it makes a CG iteration 10-12 % cheaper (4 vertex-level steps + a degree-20..32 polynomial on ~20 000 level-3 nodes
 // instead of 31 vertex-level steps) and costs 10-17 % more iterations (33-35 instead of 30, whatever the accuracy of
@@ -4585,9 +4697,15 @@ static int pmg_build_level(tlfea_newton_t s) {
   m.rop.built = false;
   if (pmg_rop_on(s)) {  // R = S_c P^T S_f^-1 Hs from the fine copy as stored (lp_build ran before) and both scalings
     auto& r = m.rop;
-    launch_pmg_rop_build(s->stream, V.N, r.d_off, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch, r.d_ch_w,
-                         s->d_B8, s->d_B1, fine_bits(s), s->d_sc, V.d_sc, r.d_R8, r.d_R1);
     r.built = true;
+    // the fine smoother will apply H itself (DESIGN 3g'): R from H's fp64 rows, so that both see one operator
+    TRY(fine_matfree_choose(s));
+    if (s->fmf.now)
+      launch_pmg_rop_build_h(s->stream, V.N, r.d_off, r.d_cols, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch,
+                             r.d_ch_w, s->d->d_off, s->d_H, s->d_sc, V.d_sc, r.d_R8, r.d_R1);
+    else
+      launch_pmg_rop_build(s->stream, V.N, r.d_off, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch, r.d_ch_w,
+                           s->d_B8, s->d_B1, fine_bits(s), s->d_sc, V.d_sc, r.d_R8, r.d_R1);
   }
   if (m.agg.ok) {  // third level: H3 = P2^T Hc P2, its scaling and low-precision copy
     PolyLevel& A = m.agg.lvl;
@@ -4715,7 +4833,21 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
   const bool weighted = pmg_smoother_kind() != 1;  // fourth-kind smoother: z^ += beta_k d
   const double* betas = cf + t.beta();
   const C32Bnd bnd_f = hal ? C32Bnd{nullptr, nullptr, s->d_w} : C32Bnd();
+  // from the element records where this set-up chose that form and the records still belong to the assembled H
+  // (DESIGN 3g': two launches, the ping-pong partners swap as in c32_step), else the stream of the low-precision copy
+  // R of this set-up came from H itself: streaming the fp16 copy now would smooth and restrict with two operators
+  if (s->fmf.now && !fine_matfree_live(s))
+    return fail("p-multigrid: the element records no longer belong to the H this preconditioner was set up for (a residual "
+                "evaluation or an assembly since the set-up); set the preconditioner up again");
+  const bool fmf = s->fmf.now;
   auto fine = [&](const double* co, bool last, const double* zw) {  // one fine pass
+    if (fmf) {
+      launch_fine_matfree_apply(s->stream, s->d->view(), s->fmf.v, f.d, s->mf.cp);
+      launch_fine_matfree_step(s->stream, N, s->fmf.v, s->mf.cp, f.Dinv_f, s->d_sc, f.d, co, weighted ? zw : nullptr, f.d2, f.z,
+                               f.z2, f.r, f.r2, d_r, d_z, rz_part, last);
+      f.swap();
+      return;
+    }
     C32Bnd bnd = bnd_f;
     bnd.zw = weighted ? zw : nullptr;
     c32_step(s, Lf, f, Nf, co, d_r, d_z, rz_part, last, bnd);
@@ -4957,9 +5089,9 @@ static void cg_graphs_destroy(tlfea_newton_t s) {
 static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg, int bits) {
   const long key[6] = {deg + 1000 * precond_eff(s) + 100000L * (s->pmg.ok ? pmg_coarse_degree_eff(s) : 0),
                        bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0) + (s->mf.now && s->mf.compact ? 800000L : 0) +
-                           (pmg_rop_now(s) ? 400000L : 0),
+                           (pmg_rop_now(s) ? 400000L : 0) + (fine_matfree_live(s) ? 1600000L : 0),
                        (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
-                       (long)(size_t)s->d_B8, (long)(size_t)s->pmg.vertex.d_B8};
+                       (long)(size_t)s->d_B8 ^ fine_matfree_key(s), (long)(size_t)s->pmg.vertex.d_B8};
   if (s->cg_graph[0] && std::equal(key, key + 6, s->cg_graph_key)) return 0;
   cg_graphs_destroy(s);
   for (int k = 0; k < (s->spmv32_now ? 3 : 2); k++) {
@@ -5275,6 +5407,8 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
     }
     return 0;
   }
+  s->fmf.now = false;
+  s->fmf.last = 0;
   if (cheb_degree_eff(s) > 1) {
     TRY(estimate_lam_max(s, d_b));
     TRY(cheb_upload_coefficients(s));
@@ -5283,6 +5417,7 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
       if (precond_eff(s) == 2) {  // still available after the set-up attempt
         TRY(pmg_build_level(s));
         TRY(pmg_coefficients(s));
+        TRY(fine_matfree_setup(s));  // the fine smoother's form for this set-up (DESIGN 3g')
       }
     }
   }
@@ -5337,6 +5472,8 @@ static void cg_trace_form(tlfea_newton_t s, bool fused, int deg, bool graphs) {
 static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out) {
   s->mf.now = false;
   s->mf.last_mode = 0;
+  s->fmf.now = false;
+  s->fmf.last = 0;
   if (s->lin.method == 1) return direct_solve(s, d_b, d_x, iters_out, rel_out);
   tlfea_t10_t d = s->d;
   const int N = s->N;
@@ -5922,6 +6059,50 @@ extern "C" int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double
   return 0;
 }
 extern "C" int tlfea_newton_get_spmv_mode(tlfea_newton_t s) { return s ? s->mf.last_mode : -1; }
+// Test hook: ONE fine pass of the form of DESIGN 3g' (apply + gather-and-step) with the set-up a preceding
+// tlfea_newton_apply_preconditioner left, on host vectors: d, res, z float [3N], r double [3N], the pair coef[2], zw (0:
+// none), last.  Out: d', and either z^', res^' (float) or z = S z^' (double) and the kNPart r.z slots.
+extern "C" int tlfea_newton_fine_smoother_pass(tlfea_newton_t s, const float* d, const float* res, const float* z, const double* r,
+                                               const double* coef2, double zw, int last, float* d_out, float* z_out,
+                                               float* res_out, double* z64_out, double* rz_slots) {
+  if (!s || !d || !res || !z || !r || !coef2 || !d_out) return fail("tlfea_newton_fine_smoother_pass: null argument");
+  if (!fine_matfree_live(s))
+    return fail("tlfea_newton_fine_smoother_pass: the last preconditioner set-up did not choose the fine smoother from the "
+                "element records, or the records have changed since");
+  const int N = s->N;
+  const size_t n = 3 * (size_t)N;
+  C32Vecs f(s->d_f32, n);
+  double* d_cf = nullptr;
+  TRY(dmalloc(&d_cf, 3));
+  const double cf[3] = {coef2[0], coef2[1], zw};
+  auto run = [&]() -> int {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(d_cf, cf, sizeof cf, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f.d, d, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f.r, res, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f.z, z, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_r, r, n * sizeof(double), hipMemcpyHostToDevice));
+    launch_fine_matfree_apply(s->stream, s->d->view(), s->fmf.v, f.d, s->mf.cp);
+    launch_fine_matfree_step(s->stream, N, s->fmf.v, s->mf.cp, f.Dinv_f, s->d_sc, f.d, d_cf, zw != 0.0 ? d_cf + 2 : nullptr, f.d2,
+                             f.z, f.z2, f.r, f.r2, s->d_r, s->d_zv, part(s, 0), last != 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(d_out, f.d2, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (last) {
+      if (z64_out) HIP_TRY(hipMemcpy(z64_out, s->d_zv, n * sizeof(double), hipMemcpyDeviceToHost));
+      if (rz_slots) HIP_TRY(hipMemcpy(rz_slots, part(s, 0), (size_t)kNPart * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+      if (z_out) HIP_TRY(hipMemcpy(z_out, f.z2, n * sizeof(float), hipMemcpyDeviceToHost));
+      if (res_out) HIP_TRY(hipMemcpy(res_out, f.r2, n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return 0;
+  };
+  const int rc = run();
+  (void)hipFree(d_cf);
+  return rc;
+}
+// fine smoother the last preconditioner set-up chose: 0 stream of the low-precision copy, 1 from the element records
+extern "C" int tlfea_newton_get_fine_smoother(tlfea_newton_t s) { return s ? s->fmf.last : -1; }
 // the last lambda_max estimates of the fine, vertex and third level (0 where there is none); out[3] = 1 if the last fine
 // estimate ran its products through the matrix-free pair
 extern "C" int tlfea_newton_get_lambda_max(tlfea_newton_t s, double out[4]) {

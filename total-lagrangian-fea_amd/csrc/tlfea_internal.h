@@ -162,12 +162,14 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
                             const double* nw, double penalty, double* Hval, const double* emat = nullptr);
 // Matrix-free product q = H p on affine elements (one material): the scalars of the assembled H, as
 // launch_assemble_affine forms them, and the mass rule (N_j at the rule's points in the rule's order, its weights).
-struct MatfreeCoef {
-  double a, b, c1, cl;      // h lambda + lamd | h mu + eta | h mu | h lambda
-  double w0, w1;            // weight of the centroid point | of the four outer points
-  double rho_inv_h;         // density of the assembled mass matrix / h (0: none)
-  double Nq[kNQ][kNN], mw[kNQ];
+template <typename R>
+struct MatfreeCoefT {
+  R a, b, c1, cl;      // h lambda + lamd | h mu + eta | h mu | h lambda
+  R w0, w1;            // weight of the centroid point | of the four outer points
+  R rho_inv_h;         // density of the assembled mass matrix / h (0: none)
+  R Nq[kNQ][kNN], mw[kNQ];
 };
+using MatfreeCoef = MatfreeCoefT<double>;
 // Device lists of the compact row form (matfree_compact.h): a wavefront of 64 elements sums its rows per node first
 struct MatfreeCompact {
   const int* row_off;           // [W + 1] first compact row of wavefront w
@@ -184,6 +186,32 @@ void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineV
 void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc, const double* ybuf, const double* p,
                            const int* fixed_slot, const double* nw, double penalty, double* q, double* pq_part,
                            const MatfreeCompact* cp = nullptr);
+// Fine smoother of the p-multigrid cycle from the element records, in single precision (DESIGN 3g').  One pass
+//   res^ -= Hs d ; d' = c1 d + c2 (SDS)^-1 res^ ; z^ += zw d'      Hs = S H S
+// is two launches.  The apply is tangent_apply_affine_kernel in float on float copies of the records (compact rows only),
+// with the material scalars divided by m0 = max(|a|, |b|, |c1|, |cl|) and the direction x = (sc / sigma) d formed at the
+// load (scn = float(sc / sigma), sigma^2 = mean(sc^2)): every factor is O(1) whatever the units.  The step sums a node's
+// rows as matfree_gather_kernel does, adds the pinned-row term, multiplies by tau scn (tau = m0 sigma^2, formed on the
+// device from ss = sum(sc^2): captured launch sequences stay valid when H moves; m0, the scalars and pen_m0 go to the
+// kernels by value and are part of the CG graphs' key) and ends like cheb32_kernel.
+struct FineMatfree {
+  MatfreeCoefT<float> mc;       // scalars / m0
+  double m0, pen_m0;            // m0 | h^2 rho / m0
+  const float *gvec, *Fq;       // float copies of the records
+  const float* scn;             // [3N] float(sc / sigma)
+  const double* ss;             // device scalar sum(sc^2)
+  double inv_n;                 // 1 / 3N
+  float* ybuf;                  // [rows][3]
+  const int* fixed_slot;
+  const double* nw;
+};
+void launch_fine_matfree_apply(hipStream_t s, const ElemView& m, const FineMatfree& f, const float* d, const MatfreeCompact& cp);
+void launch_fine_matfree_step(hipStream_t s, int N, const FineMatfree& f, const MatfreeCompact& cp, const float* Dinv_f,
+                              const double* sc, const float* d_old, const double* coef, const double* zw, float* d_new,
+                              const float* z, float* z_new, const float* res, float* res_new, const double* r, double* z_out,
+                              double* rz_part, bool last);
+// scn = float(sc / sigma) with sigma^2 = ss[0] * inv_n
+void launch_fine_matfree_scale(hipStream_t s, int n, const double* sc, const double* ss, double inv_n, float* scn);
 void launch_tangent_blocks(hipStream_t s, const ElemView& m, const Material& mat, double h,
                            double* Kbuf /*[E][55][9]*/, const double* emat = nullptr);
 void launch_assemble_rows(hipStream_t s, int N, int S, int maxdeg, const Incidence& inc, const double* Kbuf,
@@ -317,6 +345,9 @@ void launch_pmg_prolong(hipStream_t s, int N, const int* par0, const int* par1, 
                         const double* sc_f, float* z_f, float* d_f, bool add_to_d = false);
 // restricted fine operator R = S_c P^T S_f^-1 Hs (pmg_host.h pmg_restrict_op_build): build from the stored fine copy (once
 // per solve), and the restriction  r^_c = S_c P^T S_f^-1 res_f - R d_f  fused with the coarse start vectors
+void launch_pmg_rop_build_h(hipStream_t s, int Nc, const int* r_off, const int* r_cols, const int* con_off, const int* con_blk,
+                            const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const int* f_off,
+                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1);
 void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
                           const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,
                           const void* B1, int bits, const double* sc_f, const double* sc_c, void* R8, float* R1);

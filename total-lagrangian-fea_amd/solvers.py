@@ -407,6 +407,26 @@ class SyncedNewtonSolver:
         """product of the last solve's CG iterations: 0 CSR kernel, 1 matrix-free pair"""
         return int(self._lib.tlfea_newton_get_spmv_mode(self._h))
 
+    def GetFineSmoother(self):
+        """fine smoother the last preconditioner set-up chose: 0 stream of the low-precision copy, 1 passes from the
+        element records (DESIGN 3g')"""
+        return int(self._lib.tlfea_newton_get_fine_smoother(self._h))
+
+    def FineSmootherPass(self, d, res, z, r, coef, zw=0.0, last=False):
+        """one fine smoother pass from the element records with the set-up the last ApplyPreconditioner left (test hook):
+        (d', z^', res^') as float32, or with last (d', z = S z^' in float64, the 512 r.z slots)"""
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        n = 3 * self.n_coef
+        d, res, z = (np.ascontiguousarray(a, dtype=np.float32) for a in (d, res, z))
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        cf = np.ascontiguousarray(coef, dtype=np.float64)
+        assert d.shape == res.shape == z.shape == r.shape == (n,) and cf.shape == (2,)
+        d_o, z_o, r_o = (np.zeros(n, dtype=np.float32) for _ in range(3))
+        z64, slots = np.zeros(n), np.zeros(512)
+        check(self._lib.tlfea_newton_fine_smoother_pass(self._h, fp(d), fp(res), fp(z), dp(r), dp(cf), float(zw), int(bool(last)),
+                                                        fp(d_o), fp(z_o), fp(r_o), dp(z64), dp(slots)))
+        return (d_o, z64, slots) if last else (d_o, z_o, r_o)
+
     def GetLambdaMax(self):
         """(fine, vertex, level3, matfree): the last lambda_max estimates of the three levels (0 where a level does not
         exist) and whether the last fine estimate ran its products through the matrix-free pair"""
