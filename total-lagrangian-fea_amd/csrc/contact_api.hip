@@ -2,41 +2,10 @@
 // ownership and the launch sequence of one contact step (contact_kernels.hip).  The number of launches per step does
 // not depend on the mesh; the one device-to-host read per step is the candidate-pair count, which sizes the pair
 // buffers before they are filled (they grow, the list is never truncated).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "../../include/tlfea_c.h"
+#include "api_common.h"
 #include "contact_internal.h"
-#include "tlfea_internal.h"
 
 using namespace tlfea;
-
-namespace {
-
-#define CHECK_HIP(expr)                                                                                        \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess)                                                                                      \
-      return api_fail(std::string(hipGetErrorString(_e)) + " in " + __FILE__ + ":" + std::to_string(__LINE__)); \
-  } while (0)
-
-template <typename T>
-int dalloc(T** p, size_t n) {
-  *p = nullptr;
-  CHECK_HIP(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-  return 0;
-}
-
-template <typename T>
-void dfree(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-}  // namespace
 
 struct tlfea_contact_s {
   int N = 0, E = 0, npe = 0, self = 0;
@@ -85,8 +54,8 @@ struct tlfea_contact_s {
     if (cap * 8 > 0x7fffffffLL) return api_fail("tlfea_contact_step: " + std::to_string(need) + " candidate pairs exceed the capacity of the contact buffers");
     dfree(d_pairs), dfree(d_patches), dfree(d_contrib), dfree(d_slot_node), dfree(d_node_items);
     pair_cap = 0;
-    if (dalloc(&d_pairs, cap) || dalloc(&d_patches, cap) || dalloc(&d_contrib, cap * 24) ||
-        dalloc(&d_slot_node, cap * 8) || dalloc(&d_node_items, cap * 8))
+    if (dmalloc(&d_pairs, cap) || dmalloc(&d_patches, cap) || dmalloc(&d_contrib, cap * 24) ||
+        dmalloc(&d_slot_node, cap * 8) || dmalloc(&d_node_items, cap * 8))
       return 1;
     pair_cap = (int)cap;
     return 0;
@@ -120,12 +89,12 @@ extern "C" int tlfea_contact_create(int n_nodes, int n_elems, int nodes_per_elem
   c->N = n_nodes, c->E = n_elems, c->npe = nodes_per_elem, c->self = self_collision ? 1 : 0;
   c->cell_cap = std::max(1024, 2 * n_elems);
   const size_t N = n_nodes, E = n_elems;
-  int rc = dalloc(&c->d_conn, nc) || dalloc(&c->d_mesh, E) || dalloc(&c->d_press, N) || dalloc(&c->d_box, 6 * E) ||
-           dalloc(&c->d_grid, 1) || dalloc(&c->d_elem_cell, E) || dalloc(&c->d_cell_cnt, c->cell_cap) ||
-           dalloc(&c->d_cell_off, c->cell_cap + 1) || dalloc(&c->d_cell_cur, c->cell_cap) ||
-           dalloc(&c->d_cell_items, E) || dalloc(&c->d_row_cnt, E) || dalloc(&c->d_row_off, E + 1) ||
-           dalloc(&c->d_node_cnt, N) || dalloc(&c->d_node_off, N + 1) || dalloc(&c->d_node_cur, N) ||
-           dalloc(&c->d_n_valid, 1) || dalloc(&c->d_force, 3 * N) || dalloc(&c->d_base, 3 * N) ||
+  int rc = dmalloc(&c->d_conn, nc) || dmalloc(&c->d_mesh, E) || dmalloc(&c->d_press, N) || dmalloc(&c->d_box, 6 * E) ||
+           dmalloc(&c->d_grid, 1) || dmalloc(&c->d_elem_cell, E) || dmalloc(&c->d_cell_cnt, c->cell_cap) ||
+           dmalloc(&c->d_cell_off, c->cell_cap + 1) || dmalloc(&c->d_cell_cur, c->cell_cap) ||
+           dmalloc(&c->d_cell_items, E) || dmalloc(&c->d_row_cnt, E) || dmalloc(&c->d_row_off, E + 1) ||
+           dmalloc(&c->d_node_cnt, N) || dmalloc(&c->d_node_off, N + 1) || dmalloc(&c->d_node_cur, N) ||
+           dmalloc(&c->d_n_valid, 1) || dmalloc(&c->d_force, 3 * N) || dmalloc(&c->d_base, 3 * N) ||
            c->grow_pairs(std::max(1024, 4 * n_elems));
   if (!rc) {
     hipError_t e = hipMemcpy(c->d_conn, conn_colmajor, nc * sizeof(int), hipMemcpyHostToDevice);
@@ -188,8 +157,8 @@ extern "C" int tlfea_contact_step(tlfea_contact_t c, const double* d_vel, double
   // order of a cell's members, claimed with atomics, does not reach the output)
   launch_contact_boxes(s, m, p, c->d_box);
   launch_contact_grid(s, c->E, c->d_box, c->cell_cap, c->d_grid);
-  CHECK_HIP(hipMemsetAsync(c->d_cell_cnt, 0, c->cell_cap * sizeof(int), s));
-  CHECK_HIP(hipMemsetAsync(c->d_cell_cur, 0, c->cell_cap * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(c->d_cell_cnt, 0, c->cell_cap * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(c->d_cell_cur, 0, c->cell_cap * sizeof(int), s));
   launch_contact_cell_count(s, c->E, c->d_box, c->d_grid, c->d_elem_cell, c->d_cell_cnt);
   launch_contact_scan(s, c->d_cell_cnt, c->cell_cap, c->d_cell_off);
   launch_contact_cell_fill(s, c->E, c->d_elem_cell, c->d_cell_off, c->d_cell_cur, c->d_cell_items);
@@ -197,17 +166,17 @@ extern "C" int tlfea_contact_step(tlfea_contact_t c, const double* d_vel, double
                        nullptr, nullptr);
   launch_contact_scan(s, c->d_row_cnt, c->E, c->d_row_off);
   int total = 0;
-  CHECK_HIP(hipMemcpyAsync(&total, c->d_row_off + c->E, sizeof(int), hipMemcpyDeviceToHost, s));
-  CHECK_HIP(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(&total, c->d_row_off + c->E, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   if (total < 0) return api_fail("tlfea_contact_step: candidate-pair count overflowed");
   if (int rc = c->grow_pairs(total)) return rc;
   c->n_pairs = total;
   launch_contact_pairs(s, m, c->d_box, c->d_grid, c->d_elem_cell, c->d_cell_off, c->d_cell_items, true, c->d_row_cnt,
                        c->d_row_off, c->d_pairs);
   // narrowphase: one patch per pair
-  CHECK_HIP(hipMemsetAsync(c->d_n_valid, 0, sizeof(int), s));
-  CHECK_HIP(hipMemsetAsync(c->d_node_cnt, 0, c->N * sizeof(int), s));
-  CHECK_HIP(hipMemsetAsync(c->d_node_cur, 0, c->N * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(c->d_n_valid, 0, sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(c->d_node_cnt, 0, c->N * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(c->d_node_cur, 0, c->N * sizeof(int), s));
   launch_contact_narrowphase(s, m, p, total, c->d_pairs, c->d_patches, c->d_n_valid);
   // forces: 8 corner contributions per patch, node lists counted / scanned / filled, summed in patch order
   launch_contact_forces(s, m, p, total, c->d_patches, d_vel, damping, friction, c->d_contrib, c->d_slot_node,
@@ -215,14 +184,14 @@ extern "C" int tlfea_contact_step(tlfea_contact_t c, const double* d_vel, double
   launch_contact_scan(s, c->d_node_cnt, c->N, c->d_node_off);
   launch_contact_node_fill(s, 8 * total, c->d_slot_node, c->d_node_off, c->d_node_cur, c->d_node_items);
   launch_contact_node_sum(s, c->N, c->d_node_off, c->d_node_items, c->d_contrib, c->d_force);
-  CHECK_HIP(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
 extern "C" int tlfea_contact_set_base_force(tlfea_contact_t c, const double* f, int n) {
   if (!c || !f) return api_fail("tlfea_contact_set_base_force: NULL argument");
   if (n != 3 * c->N) return api_fail("tlfea_contact_set_base_force: n must be 3N = " + std::to_string(3 * c->N));
-  CHECK_HIP(hipMemcpy(c->d_base, f, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_base, f, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -232,8 +201,8 @@ extern "C" int tlfea_contact_apply_to_t10(tlfea_contact_t c) {
   double* f_ext = tlfea_t10_external_force_device_ptr(c->t10);
   if (!f_ext) return api_fail("tlfea_contact_apply_to_t10: the element object has no external-force buffer");
   launch_contact_add(c->stream, 3 * c->N, c->d_base, c->d_force, f_ext);
-  CHECK_HIP(hipGetLastError());
-  CHECK_HIP(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -249,27 +218,27 @@ extern "C" int tlfea_contact_num_pairs(tlfea_contact_t c, int* n) {
 
 extern "C" int tlfea_contact_num_patches(tlfea_contact_t c, int* n) {
   if (!c || !n) return api_fail("tlfea_contact_num_patches: NULL argument");
-  CHECK_HIP(hipMemcpy(n, c->d_n_valid, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n, c->d_n_valid, sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
 // RetrieveResults
 extern "C" int tlfea_contact_retrieve_pairs(tlfea_contact_t c, int* pairs) {
   if (!c || (!pairs && c->n_pairs)) return api_fail("tlfea_contact_retrieve_pairs: NULL argument");
-  if (c->n_pairs) CHECK_HIP(hipMemcpy(pairs, c->d_pairs, (size_t)c->n_pairs * sizeof(int2), hipMemcpyDeviceToHost));
+  if (c->n_pairs) HIP_TRY(hipMemcpy(pairs, c->d_pairs, (size_t)c->n_pairs * sizeof(int2), hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int tlfea_contact_retrieve_patches(tlfea_contact_t c, tlfea_contact_patch* patches) {
   if (!c || (!patches && c->n_pairs)) return api_fail("tlfea_contact_retrieve_patches: NULL argument");
   if (c->n_pairs)
-    CHECK_HIP(hipMemcpy(patches, c->d_patches, (size_t)c->n_pairs * sizeof(tlfea_contact_patch),
+    HIP_TRY(hipMemcpy(patches, c->d_patches, (size_t)c->n_pairs * sizeof(tlfea_contact_patch),
                         hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int tlfea_contact_retrieve_force(tlfea_contact_t c, double* f) {
   if (!c || !f) return api_fail("tlfea_contact_retrieve_force: NULL argument");
-  CHECK_HIP(hipMemcpy(f, c->d_force, 3 * (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(f, c->d_force, 3 * (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }

@@ -1,5 +1,5 @@
 // field_obstacle_host.h -- host side of the field obstacles (DESIGN 3e''): the argument checks of one field and of a
-// triangle surface handed to the builder.  Included by tlfea_api.hip only.
+// triangle surface handed to the builder.  Included by obstacle_api.hip only.
 #pragma once
 #include <algorithm>
 #include <cmath>

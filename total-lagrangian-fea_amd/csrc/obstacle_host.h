@@ -1,5 +1,5 @@
 // obstacle_host.h -- host side of the rigid obstacles: the surface weights of a T10 mesh and the argument
-// checks of one obstacle.  Included by tlfea_api.hip only.
+// checks of one obstacle.  Included by obstacle_api.hip and t10_load_host.h.
 #pragma once
 #include <algorithm>
 #include <array>

@@ -18,17 +18,13 @@
 #include <vector>
 #include <unistd.h>
 
-#include "../../include/tlfea_c.h"
 #include "ancf_host.h"
-#include "tlfea_internal.h"
+#include "data_handle.h"
 #include "pmg_host.h"
 #include "pmg_coef.h"
 #include "rowgroup_host.h"
 #include "direct_host.h"
 #include "vbd_host.h"
-#include "obstacle_host.h"
-#include "ancf_obstacle_host.h"
-#include "field_obstacle_host.h"
 #include "ancf_load_host.h"
 #include "t10_load_host.h"
 #include "modal_host.h"
@@ -39,175 +35,17 @@ struct RcclUniqueId {  // == ncclUniqueId (rccl.h): 128 opaque bytes, passed BY 
   char internal[128];
 };
 
-namespace {
-thread_local std::string g_err;
-
-int fail(const std::string& msg) {
-  g_err = msg;
+std::string& tlfea::api_error() {
+  thread_local std::string err;
+  return err;
+}
+extern "C" const char* tlfea_last_error(void) { return api_error().c_str(); }
+// every C-ABI translation unit reports through this one message
+int tlfea::api_fail(const std::string& msg) {
+  api_error() = msg;
   std::fprintf(stderr, "tlfea: %s\n", msg.c_str());
   return 1;
 }
-
-#define HIP_TRY(expr)                                                                                \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess)                                                                            \
-      return fail(std::string(hipGetErrorString(_e)) + " in " + __FILE__ + ":" + std::to_string(__LINE__)); \
-  } while (0)
-
-template <typename T>
-int dmalloc(T** p, size_t n) {
-  *p = nullptr;
-  if (n == 0) n = 1;
-  HIP_TRY(hipMalloc((void**)p, n * sizeof(T)));
-  return 0;
-}
-#define TRY(x)           \
-  do {                   \
-    if (int _r = (x)) return _r; \
-  } while (0)
-}  // namespace
-
-// =================================================================================================
-struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first element type
-  int kind = kT10, S = kNN, Q = kNQ, nn = kNN;  // shape functions, force QPs, nodes per element
-  int n_nodes = 0;                             // mesh nodes (== N for T10, N/4 for the ANCF types)
-  int E = 0, N = 0, Epad = 0;
-  // ANCF set-up data (host): per-element dimensions, (B^T)^-1 column-major, force and mass rules
-  std::vector<double> Lv, Wv, Hv, Binv;
-  std::vector<double> fr[6], mr[6];  // gauss xi/eta/zeta, weight xi/eta/zeta
-  int n_constraint = 0, n_fixed = 0;
-  hipStream_t stream = nullptr;  // default stream, as the reference
-  // mesh + state
-  int* d_conn = nullptr;
-  double *d_x = nullptr, *d_y = nullptr, *d_z = nullptr, *d_xt = nullptr, *d_yt = nullptr, *d_zt = nullptr;
-  double *d_qx = nullptr, *d_qy = nullptr, *d_qz = nullptr;
-  double h_qw[kMaxQ] = {0};
-  double *d_gradN = nullptr, *d_gradN_t = nullptr, *d_detJ = nullptr;
-  double *d_F = nullptr, *d_P = nullptr, *d_Fdot = nullptr, *d_Pvis = nullptr;  // lazily, CalcP only
-  double *d_fbuf = nullptr, *d_fint = nullptr, *d_fext = nullptr;
-  Material mat{kSVK, 0, 0, 0, 0, 0, 0, 0, 0};
-  double E_mod = 0, nu = 0;
-  // per-element materials (tlfea_t10_set_element_materials): null d_emat = one material (mat) for every element.  While
-  // a table is set, mat.model is the table's model and mat_saved the uniform material that ClearElementMaterials restores
-  double* d_emat = nullptr;         // [E][kEmRec], tlfea_internal.h
-  int n_mat = 0;
-  bool emat_damp = false;           // some entry has eta or lamd != 0
-  std::vector<double> h_table;      // [n_mat][kEmRec] (slot kEmRhoM: the entry's density)
-  std::vector<int> h_eid;           // [E]
-  std::vector<double> h_rho_mass;   // [E] density each element's share of the mass matrix was assembled with
-  bool mass_pe = false;             // the mass matrix was assembled from h_rho_mass under a table
-  Material mat_saved{kSVK, 0, 0, 0, 0, 0, 0, 0, 0};
-  // rigid obstacles (tlfea_t10_set_obstacles): obs.n == 0 = none -- nothing allocated, nothing launched
-  ObstacleList obs{};
-  std::vector<double> h_surf_w;     // [N] surface weight of every node (built once per mesh, on first use)
-  std::vector<int> h_surf;          // the nodes of weight > 0, ascending: the obstacle kernels' work list
-  int* d_ob_node = nullptr;
-  double *d_ob_w = nullptr, *d_ob_f = nullptr, *d_ob_blk = nullptr, *d_ob_fk = nullptr, *d_ob_res = nullptr;
-  int ob_fk_cap = 0;                // obstacles d_ob_fk has room for
-  // field obstacles (tlfea_set_field_obstacles, DESIGN 3e''): obs.o[0 .. ob_na) are the analytic obstacles and
-  // obs.o[ob_na .. obs.n) the fields, each list with its own index space; the samples (d_fld_V) and the descriptors
-  // (d_fld [kMaxObstacles], host copy h_fld) live in device memory
-  int ob_na = 0;
-  std::vector<tlfea_field_obstacle> fld;
-  std::vector<double*> d_fld_V;
-  FieldDev* d_fld = nullptr;
-  FieldDev h_fld[kMaxObstacles] = {};
-  // the same list on an ANCF object (tlfea_ancf_set_obstacles, DESIGN 3e'): sample-point tables and element-owned buffers
-  // (AncfObsView, tlfea_internal.h); d_ao_fc [N][3] the contact force per coefficient, d_ao_pts [E][32][5] the footprint
-  int *d_ao_cls = nullptr, *d_ao_touched = nullptr;
-  double *d_ao_sval = nullptr, *d_ao_w = nullptr, *d_ao_cbuf = nullptr, *d_ao_blk = nullptr, *d_ao_fk = nullptr,
-         *d_ao_fc = nullptr, *d_ao_pts = nullptr;
-  std::vector<double> h_ao_w;       // [E][32] sample-point weights (built once per mesh, on first use)
-  std::vector<int> h_ao_cls;
-  std::vector<double> h_ao_sval;
-  // distributed loads: none set = nothing allocated, nothing launched.  d_ld_fc [N][3] the constant part
-  // (M a + the traction vector d_ld_tr), rebuilt by the next gradient evaluation while ld_const_dirty; d_ld_f [N][3] the
-  // total load of the last gradient evaluation; the rest is AncfLoadView's (tlfea_internal.h)
-  struct SurfaceLoad {
-    int kind, face;
-    double value[3], scale;
-    std::vector<int> elems;
-  };
-  bool ld_have_a = false, ld_const_dirty = false;
-  double ld_a[3] = {0, 0, 0};
-  std::vector<SurfaceLoad> ld_list;
-  int ld_n_trac = 0, ld_n_press = 0;
-  double *d_ld_fc = nullptr, *d_ld_tr = nullptr, *d_ld_f = nullptr, *d_ld_lbuf = nullptr, *d_ld_tab = nullptr,
-         *d_ld_qw = nullptr, *d_ld_pe = nullptr;
-  int *d_ld_cls = nullptr, *d_ld_mask = nullptr;
-  // surface loads on a T10 object (DESIGN 3h'): ld_list holds boundary-face indices in `elems`; the pressure's loaded faces
-  // (ascending) own the rows of d_ld_lbuf [n][6][3], d_ld_pe [n] their effective pressure, d_ld_fnodes [n][6] their nodes,
-  // d_ld_foff / d_ld_fslot the node-to-row CSR of the gather
-  t10load::BoundaryFaces bf;
-  bool bf_built = false;
-  std::vector<int> h_ld_lf;         // the loaded faces, ascending
-  int *d_ld_fnodes = nullptr, *d_ld_foff = nullptr, *d_ld_fslot = nullptr;
-  bool loads_on() const { return ld_have_a || !ld_list.empty(); }
-  // stress recovery (tlfea_t10_calc_stress): allocated on first use, read by no solver
-  double *d_st_pts = nullptr, *d_st_erec = nullptr, *d_st_contrib = nullptr, *d_st_nodal = nullptr,
-         *d_st_part = nullptr, *d_st_tot = nullptr, *d_st_vel = nullptr;
-  double st_tot[5] = {0, 0, 0, 0, 0};
-  bool st_valid = false, st_pts_valid = false;  // a calc_stress has run | its point stresses were asked for
-  int *d_st_noff = nullptr, *d_st_nel = nullptr;  // ANCF (DESIGN 3f'): elements of every MESH node, ascending (n_nodes + 1 | E nn)
-  bool ancf_mass = false;                         // ANCF: d_mval holds an assembled mass matrix (the kinetic energy's condition)
-  // material sensitivities (tlfea_t10_material_sensitivity): allocated on first use.  d_sn_sens [4][Epad],
-  // d_sn_out [n_mat][P + 1]; under a table the ascending element list of every material (d_sn_idx [E], concatenated),
-  // its chunks (d_sn_blk) and the first chunk of every material (d_sn_boff), rebuilt when `gen` has moved on
-  double *d_sn_sens = nullptr, *d_sn_part = nullptr, *d_sn_out = nullptr, *d_sn_w = nullptr, *d_sn_u = nullptr,
-         *d_sn_pe = nullptr;
-  int *d_sn_idx = nullptr, *d_sn_boff = nullptr;
-  int2* d_sn_blk = nullptr;
-  int sn_nb = 0, sn_part_cap = 0, sn_out_cap = 0;
-  long sn_gen = -1;
-  // constraints
-  double* d_cons = nullptr;
-  int *d_fixed = nullptr, *d_fixed_slot = nullptr;
-  std::vector<int> h_fixed;
-  // constraint mode: 0 none, 1 fixed coefficients (SetNodalFixed), 2 general linear rows (SetLinearConstraintsCSR);
-  // mode 2 keeps J (rows = constraints) and J^T (rows = DOFs, entries in ascending constraint id) in CSR
-  int cons_mode = 0;
-  std::vector<int> h_joff, h_jcol, h_jtoff, h_jtcol;
-  std::vector<double> h_jval, h_jtval, h_rhs;
-  int *d_joff = nullptr, *d_jcol = nullptr, *d_jtoff = nullptr, *d_jtcol = nullptr;
-  double *d_jval = nullptr, *d_jtval = nullptr, *d_rhs = nullptr;
-  // entries of the coefficient adjacency that exist only through a constraint row (not part of the mass pattern)
-  std::vector<char> h_extra;
-  int nnz_mass = 0;
-  // sparsity (host copies are kept: the solver and the retrieve calls need them)
-  std::vector<int> h_conn, h_off, h_cols, h_n2e_off, h_n2e;
-  double h_q[3][kNQ] = {{0}};  // T10 quadrature points (host copy: shape-function table of the element-wise inertia term)
-  bool fbuf_valid = true;      // d_fbuf holds the force rows of the last residual evaluation (false after a solver
-                               // evaluation on the interleaved-row path: d_fint itself is then current)
-  double mass_rho0 = -1.0;     // density the mass matrix was assembled with (CalcMassMatrix); < 0: not assembled
-  std::vector<double> h_X0;  // coordinates handed to Setup (x | y | z): the Morton order of the fused assembly's row groups
-  int *d_off = nullptr, *d_cols = nullptr, *d_n2e_off = nullptr, *d_n2e = nullptr, *d_n2e_pos = nullptr,
-      *d_diagpos = nullptr;
-  double* d_mval = nullptr;
-  int nnz_coef = 0, maxdeg = 0;
-  // bumped by every setter that changes what a captured launch has baked in (material scalars travel by value, the
-  // fixed-node buffers are re-allocated by UpdateNodalFixed): cached hipGraphs carry the value they were captured at
-  long gen = 0;
-  // bumped by CalcDnDuPre: the solver's affine-form cache (vertex gradients, det J, the 'all elements straight-sided'
-  // decision) was derived from the grad N / det J of one call and must follow a re-referencing
-  long geom_gen = 0;
-  bool is_setup = false, is_constraints_setup = false, is_csr_setup = false, is_j_csr_setup = false,
-       is_cj_csr_setup = false, have_dndu = false;
-
-  ElemView view() const {
-    ElemView v;
-    v.E = E; v.N = N; v.Epad = Epad; v.S = S; v.Q = Q;
-    v.conn = d_conn; v.x = d_x; v.y = d_y; v.z = d_z;
-    v.gradN = d_gradN; v.gradN_t = d_gradN_t; v.detJ = d_detJ;
-    for (int q = 0; q < kMaxQ; q++) v.qw[q] = h_qw[q];
-    return v;
-  }
-  Incidence inc() const { return Incidence{d_n2e_off, d_n2e, d_n2e_pos, d_off, d_cols, d_diagpos}; }
-};
-
-extern "C" const char* tlfea_last_error(void) { return g_err.c_str(); }
-// the other C-ABI translation units (contact_api.hip) report through the same message
-int tlfea::api_fail(const std::string& msg) { return fail(msg); }
 extern "C" int tlfea_version(void) { return 100; }
 extern "C" int tlfea_device_count(void) {
   int n = 0;
@@ -322,8 +160,6 @@ extern "C" int tlfea_t10_setup(tlfea_t10_t h, const double* qx, const double* qy
   return 0;
 }
 
-#define NEED_SETUP(h, what) \
-  if (!(h) || !(h)->is_setup) return fail(std::string("GPU_FEAT10_Data must be set up before ") + what)
 #define NO_TABLE(h, what)                                                                                               \
   if ((h)->d_emat)                                                                                                    \
   return fail(std::string(what) + ": per-element materials are set (tlfea_t10_set_element_materials); clear them first " \
@@ -461,468 +297,6 @@ extern "C" int tlfea_t10_get_element_materials(tlfea_t10_t h, int* n_mat, int* e
   if (!h) return fail("null handle");
   if (n_mat) *n_mat = h->n_mat;
   if (elem_material && h->d_emat) std::copy(h->h_eid.begin(), h->h_eid.end(), elem_material);
-  return 0;
-}
-
-// ---- rigid obstacles ---------------------------------------------------------------------------------------------------
-static void surface_build(tlfea_t10_t h) {
-  if (!h->h_surf_w.empty()) return;
-  h->h_surf_w = t10_surface_weights(h->E, h->N, h->h_conn, h->h_X0);
-  h->h_surf.clear();
-  for (int i = 0; i < h->N; i++)
-    if (h->h_surf_w[i] > 0.0) h->h_surf.push_back(i);
-}
-static void obstacles_free(tlfea_t10_t h) {
-  for (double** p : {&h->d_ob_w, &h->d_ob_f, &h->d_ob_blk, &h->d_ob_fk, &h->d_ob_res}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (h->d_ob_node) (void)hipFree(h->d_ob_node);
-  h->d_ob_node = nullptr;
-  h->ob_fk_cap = 0;
-  h->obs.n = h->ob_na = 0;
-}
-// The node-owned buffers for a list of n obstacles (analytic and field together): allocated on first use, fk grown, all
-// zeroed -- no forces before the first gradient evaluation.
-static int obstacle_buffers(tlfea_t10_t h, int n) {
-  surface_build(h);
-  const int ns = (int)h->h_surf.size();
-  if (!h->d_ob_node) {
-    std::vector<double> w(ns);
-    for (int k = 0; k < ns; k++) w[k] = h->h_surf_w[h->h_surf[k]];
-    TRY(dmalloc(&h->d_ob_node, (size_t)ns));
-    TRY(dmalloc(&h->d_ob_w, (size_t)ns));
-    TRY(dmalloc(&h->d_ob_f, (size_t)3 * ns));
-    TRY(dmalloc(&h->d_ob_blk, (size_t)6 * ns));
-    TRY(dmalloc(&h->d_ob_res, (size_t)4 * kMaxObstacles));
-    if (ns) {
-      HIP_TRY(hipMemcpy(h->d_ob_node, h->h_surf.data(), (size_t)ns * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(h->d_ob_w, w.data(), (size_t)ns * sizeof(double), hipMemcpyHostToDevice));
-    }
-  }
-  if (h->ob_fk_cap < n) {
-    if (h->d_ob_fk) (void)hipFree(h->d_ob_fk);
-    h->d_ob_fk = nullptr;
-    TRY(dmalloc(&h->d_ob_fk, (size_t)4 * n * ns));
-    h->ob_fk_cap = n;
-  }
-  HIP_TRY(hipMemset(h->d_ob_f, 0, (size_t)std::max(1, 3 * ns) * sizeof(double)));
-  HIP_TRY(hipMemset(h->d_ob_blk, 0, (size_t)std::max(1, 6 * ns) * sizeof(double)));
-  HIP_TRY(hipMemset(h->d_ob_fk, 0, (size_t)std::max(1, 4 * n * ns) * sizeof(double)));
-  return 0;
-}
-// The list the kernels see: the analytic obstacles `a`, then the fields of h->fld in their order.
-static void obstacle_list_set(tlfea_t10_t h, const std::vector<ObstacleDev>& a) {
-  h->ob_na = (int)a.size();
-  for (int k = 0; k < h->ob_na; k++) h->obs.o[k] = a[k];
-  for (size_t k = 0; k < h->fld.size(); k++) h->obs.o[h->ob_na + k] = field_obstacle_dev(h->fld[k], h->d_fld + k);
-  h->obs.n = h->ob_na + (int)h->fld.size();
-}
-static std::vector<ObstacleDev> obstacle_list_analytic(tlfea_t10_t h) {
-  return std::vector<ObstacleDev>(h->obs.o, h->obs.o + h->ob_na);
-}
-static std::string obstacle_overflow(int n_analytic, int n_field) {
-  return std::to_string(n_analytic) + " analytic and " + std::to_string(n_field) + " field obstacles exceed the " +
-         std::to_string(kMaxObstacles) + " an object can hold";
-}
-extern "C" int tlfea_t10_clear_obstacles(tlfea_t10_t h) {
-  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
-    return fail("tlfea_t10_clear_obstacles: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "clearing obstacles.");
-  if (h->ob_na == 0) return 0;
-  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
-  if (h->fld.empty()) {
-    obstacles_free(h);
-  } else {  // the field list stays (DESIGN 3e'')
-    TRY(obstacle_buffers(h, (int)h->fld.size()));
-    obstacle_list_set(h, {});
-  }
-  return 0;
-}
-extern "C" int tlfea_t10_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
-  if (h && h->kind != kT10) return fail("tlfea_t10_set_obstacles: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "setting obstacles.");
-  if (n < 0 || n > kMaxObstacles)
-    return fail("tlfea_t10_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
-  if (n > 0 && !list) return fail("tlfea_t10_set_obstacles: null list");
-  for (int k = 0; k < n; k++) {
-    const std::string why = obstacle_check(list[k]);
-    if (!why.empty()) return fail("tlfea_t10_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
-  }
-  if (n + (int)h->fld.size() > kMaxObstacles)
-    return fail("tlfea_t10_set_obstacles: " + obstacle_overflow(n, (int)h->fld.size()));
-  if (n == 0) return tlfea_t10_clear_obstacles(h);
-  HIP_TRY(hipDeviceSynchronize());
-  TRY(obstacle_buffers(h, n + (int)h->fld.size()));
-  std::vector<ObstacleDev> a(n);
-  for (int k = 0; k < n; k++) a[k] = obstacle_dev(list[k]);
-  obstacle_list_set(h, a);
-  return 0;
-}
-extern "C" int tlfea_t10_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle* o) {
-  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
-    return fail("tlfea_t10_update_obstacle: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "updating an obstacle.");
-  if (k < 0 || k >= h->ob_na)
-    return fail("tlfea_t10_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->ob_na) +
-                " obstacles set");
-  if (!o) return fail("tlfea_t10_update_obstacle: null obstacle");
-  const std::string why = obstacle_check(*o);
-  if (!why.empty()) return fail("tlfea_t10_update_obstacle: obstacle " + std::to_string(k) + ": " + why);
-  h->obs.o[k] = obstacle_dev(*o);  // a kernel argument: launches already queued keep the old value
-  return 0;
-}
-extern "C" int tlfea_t10_get_obstacle_forces(tlfea_t10_t h, double* f) {
-  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
-    return fail("tlfea_t10_get_obstacle_forces: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "reading obstacle forces.");
-  if (!f) return fail("tlfea_t10_get_obstacle_forces: null output");
-  std::fill(f, f + 3 * (size_t)h->N, 0.0);
-  if (h->obs.n == 0) return 0;
-  const size_t ns = h->h_surf.size();
-  std::vector<double> fs(3 * ns);
-  HIP_TRY(hipDeviceSynchronize());
-  if (ns) HIP_TRY(hipMemcpy(fs.data(), h->d_ob_f, 3 * ns * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < ns; k++)
-    for (int c = 0; c < 3; c++) f[3 * (size_t)h->h_surf[k] + c] = fs[3 * k + c];
-  return 0;
-}
-extern "C" int tlfea_t10_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
-  if (h && h->kind != kT10 && h->obs.n > 0)  // an ANCF object's list belongs to the tlfea_ancf_* calls (DESIGN 3e')
-    return fail("tlfea_t10_get_obstacle_resultant: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "reading an obstacle resultant.");
-  if (!out) return fail("tlfea_t10_get_obstacle_resultant: null output");
-  if (k < 0 || k >= h->ob_na)
-    return fail("tlfea_t10_get_obstacle_resultant: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->ob_na) + " obstacles set");
-  HIP_TRY(hipDeviceSynchronize());
-  launch_obstacle_resultant(h->stream, (int)h->h_surf.size(), h->obs.n, h->d_ob_fk, h->d_ob_res);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, h->d_ob_res + 4 * k, 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-extern "C" int tlfea_t10_get_surface_weights(tlfea_t10_t h, double* w) {
-  if (h && h->kind != kT10) return fail("tlfea_t10_get_surface_weights: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "reading surface weights.");
-  if (!w) return fail("tlfea_t10_get_surface_weights: null output");
-  surface_build(h);
-  std::copy(h->h_surf_w.begin(), h->h_surf_w.end(), w);
-  return 0;
-}
-
-// ---- rigid obstacles on the ANCF kinds (DESIGN 3e') ------------------------------------------------------------------------
-#define NEED_ANCF_OBS(h, what)                                                                              \
-  if ((h) && (h)->kind == kT10) return fail(std::string(what) + ": ANCF handles only (not a T10 handle)"); \
-  NEED_SETUP(h, what ".");                                                                                  \
-  if (!(h)->have_dndu) return fail(std::string(what) + ": CalcDsDuPre must run first (the point weights use the reference geometry)")
-// Weights and shape tables from the reference coefficients (x12_jac = d_xt).  Built by the first SetRigidObstacles /
-// GetSurfacePointWeights after a CalcDsDuPre, which drops the cache.  d_xt is also the constraint target: targets moved
-// (UpdateConstraintTargets) between CalcDsDuPre and that first use would be taken for the reference, as they would by a
-// second CalcDsDuPre itself.
-static int ancf_points_build(tlfea_t10_t h) {
-  if (!h->h_ao_w.empty()) return 0;
-  const size_t N = h->N;
-  std::vector<double> xj(N), yj(N), zj(N);
-  HIP_TRY(hipMemcpy(xj.data(), h->d_xt, N * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(yj.data(), h->d_yt, N * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(zj.data(), h->d_zt, N * sizeof(double), hipMemcpyDeviceToHost));
-  ancf::ObstacleSetup su =
-      ancf::obstacle_setup(h->S, h->E, h->h_conn, h->Lv, h->Wv, h->Hv, h->Binv, xj.data(), yj.data(), zj.data());
-  h->h_ao_w.swap(su.w);
-  h->h_ao_cls.swap(su.cls);
-  h->h_ao_sval.swap(su.sval);
-  return 0;
-}
-static AncfObsView ancf_obs_view(tlfea_t10_t h) {
-  return AncfObsView{h->E, h->S, h->d_conn, h->d_ao_cls, h->d_ao_sval, h->d_ao_w, h->d_ao_cbuf, h->d_ao_blk,
-                     h->d_ao_fk, h->d_ao_touched};
-}
-static void ancf_obstacles_free(tlfea_t10_t h) {
-  for (double** p : {&h->d_ao_sval, &h->d_ao_w, &h->d_ao_cbuf, &h->d_ao_blk, &h->d_ao_fk, &h->d_ao_fc, &h->d_ao_pts,
-                     &h->d_ob_res}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  for (int** p : {&h->d_ao_cls, &h->d_ao_touched}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  h->ob_fk_cap = 0;
-  h->obs.n = h->ob_na = 0;
-}
-// The element-owned buffers for a list of n obstacles (analytic and field together): allocated on first use, fk grown,
-// zeroed -- no forces and no touched element before the first gradient evaluation.
-static int ancf_obstacle_buffers(tlfea_t10_t h, int n) {
-  TRY(ancf_points_build(h));
-  const size_t E = h->E, S = h->S, P = kAncfObsPoints;
-  if (!h->d_ao_w) {
-    TRY(dmalloc(&h->d_ao_cls, E));
-    TRY(dmalloc(&h->d_ao_touched, E));
-    TRY(dmalloc(&h->d_ao_sval, h->h_ao_sval.size()));
-    TRY(dmalloc(&h->d_ao_w, E * P));
-    TRY(dmalloc(&h->d_ao_cbuf, E * S * 3));
-    TRY(dmalloc(&h->d_ao_blk, E * P * 6));
-    TRY(dmalloc(&h->d_ao_fc, (size_t)3 * h->N));
-    TRY(dmalloc(&h->d_ob_res, (size_t)4 * kMaxObstacles));
-    HIP_TRY(hipMemcpy(h->d_ao_cls, h->h_ao_cls.data(), E * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_ao_sval, h->h_ao_sval.data(), h->h_ao_sval.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_ao_w, h->h_ao_w.data(), E * P * sizeof(double), hipMemcpyHostToDevice));
-  }
-  if (h->ob_fk_cap < n) {
-    if (h->d_ao_fk) (void)hipFree(h->d_ao_fk);
-    h->d_ao_fk = nullptr;
-    TRY(dmalloc(&h->d_ao_fk, (size_t)4 * n * E));
-    h->ob_fk_cap = n;
-  }
-  HIP_TRY(hipMemset(h->d_ao_touched, 0, E * sizeof(int)));
-  HIP_TRY(hipMemset(h->d_ao_cbuf, 0, E * S * 3 * sizeof(double)));
-  HIP_TRY(hipMemset(h->d_ao_fc, 0, (size_t)3 * h->N * sizeof(double)));
-  HIP_TRY(hipMemset(h->d_ao_fk, 0, (size_t)4 * n * E * sizeof(double)));
-  return 0;
-}
-extern "C" int tlfea_ancf_clear_obstacles(tlfea_t10_t h) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_clear_obstacles");
-  if (h->ob_na == 0) return 0;
-  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
-  if (h->fld.empty()) {
-    ancf_obstacles_free(h);
-  } else {  // the field list stays (DESIGN 3e'')
-    TRY(ancf_obstacle_buffers(h, (int)h->fld.size()));
-    obstacle_list_set(h, {});
-  }
-  return 0;
-}
-extern "C" int tlfea_ancf_set_obstacles(tlfea_t10_t h, const tlfea_obstacle* list, int n) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_set_obstacles");
-  if (n < 0 || n > kMaxObstacles)
-    return fail("tlfea_ancf_set_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
-  if (n > 0 && !list) return fail("tlfea_ancf_set_obstacles: null list");
-  for (int k = 0; k < n; k++) {
-    const std::string why = obstacle_check(list[k]);
-    if (!why.empty()) return fail("tlfea_ancf_set_obstacles: obstacle " + std::to_string(k) + ": " + why);
-  }
-  if (n + (int)h->fld.size() > kMaxObstacles)
-    return fail("tlfea_ancf_set_obstacles: " + obstacle_overflow(n, (int)h->fld.size()));
-  if (n == 0) return tlfea_ancf_clear_obstacles(h);
-  HIP_TRY(hipDeviceSynchronize());
-  TRY(ancf_obstacle_buffers(h, n + (int)h->fld.size()));
-  std::vector<ObstacleDev> a(n);
-  for (int k = 0; k < n; k++) a[k] = obstacle_dev(list[k]);
-  obstacle_list_set(h, a);
-  return 0;
-}
-extern "C" int tlfea_ancf_update_obstacle(tlfea_t10_t h, int k, const tlfea_obstacle* o) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_update_obstacle");
-  if (k < 0 || k >= h->ob_na)
-    return fail("tlfea_ancf_update_obstacle: index " + std::to_string(k) + " outside the " + std::to_string(h->ob_na) +
-                " obstacles set");
-  if (!o) return fail("tlfea_ancf_update_obstacle: null obstacle");
-  const std::string why = obstacle_check(*o);
-  if (!why.empty()) return fail("tlfea_ancf_update_obstacle: obstacle " + std::to_string(k) + ": " + why);
-  h->obs.o[k] = obstacle_dev(*o);  // a kernel argument: launches already queued keep the old value
-  return 0;
-}
-extern "C" int tlfea_ancf_get_obstacle_forces(tlfea_t10_t h, double* f) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_get_obstacle_forces");
-  if (!f) return fail("tlfea_ancf_get_obstacle_forces: null output");
-  if (h->obs.n == 0) {
-    std::fill(f, f + 3 * (size_t)h->N, 0.0);
-    return 0;
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(f, h->d_ao_fc, 3 * (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-extern "C" int tlfea_ancf_get_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_get_obstacle_resultant");
-  if (!out) return fail("tlfea_ancf_get_obstacle_resultant: null output");
-  if (k < 0 || k >= h->ob_na)
-    return fail("tlfea_ancf_get_obstacle_resultant: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->ob_na) + " obstacles set");
-  HIP_TRY(hipDeviceSynchronize());
-  launch_obstacle_resultant(h->stream, h->E, h->obs.n, h->d_ao_fk, h->d_ob_res);  // the elements' shares, element order
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, h->d_ob_res + 4 * k, 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-extern "C" int tlfea_ancf_get_surface_points(tlfea_t10_t h, double* w) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_get_surface_points");
-  if (!w) return fail("tlfea_ancf_get_surface_points: null output");
-  TRY(ancf_points_build(h));
-  std::copy(h->h_ao_w.begin(), h->h_ao_w.end(), w);
-  return 0;
-}
-extern "C" int tlfea_ancf_retrieve_contact_points(tlfea_t10_t h, double* out) {
-  NEED_ANCF_OBS(h, "tlfea_ancf_retrieve_contact_points");
-  if (!out) return fail("tlfea_ancf_retrieve_contact_points: null output");
-  if (h->obs.n == 0) return fail("tlfea_ancf_retrieve_contact_points: no obstacles are set");
-  const size_t n = (size_t)h->E * kAncfObsPoints * 5;
-  HIP_TRY(hipDeviceSynchronize());
-  if (!h->d_ao_pts) TRY(dmalloc(&h->d_ao_pts, n));
-  launch_ancf_obstacle_footprint(h->stream, ancf_obs_view(h), h->obs, h->d_x, h->d_y, h->d_z, h->d_ao_pts);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, h->d_ao_pts, n * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// ---- field obstacles (DESIGN 3e''), any handle ---------------------------------------------------------------------------
-#define NEED_FIELD_OBS(h, what)                                                                              \
-  NEED_SETUP(h, what ".");                                                                                   \
-  if ((h)->kind != kT10 && !(h)->have_dndu)                                                                  \
-  return fail(std::string(what) + ": CalcDsDuPre must run first (the point weights use the reference geometry)")
-static void field_storage_free(tlfea_t10_t h) {
-  for (double* p : h->d_fld_V)
-    if (p) (void)hipFree(p);
-  h->d_fld_V.clear();
-  h->fld.clear();
-}
-extern "C" int tlfea_clear_field_obstacles(tlfea_t10_t h) {
-  NEED_FIELD_OBS(h, "tlfea_clear_field_obstacles");
-  if (h->fld.empty()) return 0;
-  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the samples
-  field_storage_free(h);
-  if (h->ob_na == 0) {
-    if (h->kind == kT10)
-      obstacles_free(h);
-    else
-      ancf_obstacles_free(h);
-    if (h->d_fld) (void)hipFree(h->d_fld);
-    h->d_fld = nullptr;
-  } else {  // the analytic list stays
-    TRY(h->kind == kT10 ? obstacle_buffers(h, h->ob_na) : ancf_obstacle_buffers(h, h->ob_na));
-    obstacle_list_set(h, obstacle_list_analytic(h));
-  }
-  return 0;
-}
-extern "C" int tlfea_set_field_obstacles(tlfea_t10_t h, const tlfea_field_obstacle* list, const double* const* values,
-                                         int n) {
-  NEED_FIELD_OBS(h, "tlfea_set_field_obstacles");
-  if (n < 0 || n > kMaxObstacles)
-    return fail("tlfea_set_field_obstacles: n must be in 0.." + std::to_string(kMaxObstacles) + ", got " + std::to_string(n));
-  if (n > 0 && !list) return fail("tlfea_set_field_obstacles: null list");
-  if (n > 0 && !values) return fail("tlfea_set_field_obstacles: null sample pointer");
-  for (int k = 0; k < n; k++) {
-    if (!values[k]) return fail("tlfea_set_field_obstacles: field " + std::to_string(k) + ": null sample pointer");
-    std::string why = field_params_check(list[k]);
-    if (why.empty()) why = field_values_check(list[k], values[k]);
-    if (!why.empty()) return fail("tlfea_set_field_obstacles: field " + std::to_string(k) + ": " + why);
-  }
-  if (n + h->ob_na > kMaxObstacles) return fail("tlfea_set_field_obstacles: " + obstacle_overflow(h->ob_na, n));
-  if (n == 0) return tlfea_clear_field_obstacles(h);
-  HIP_TRY(hipDeviceSynchronize());
-  // the new samples are allocated and copied first and swapped in only when all of that has succeeded: a failure leaves
-  // the previous list as it was
-  std::vector<double*> fresh;
-  auto drop = [&](int r) {
-    for (double* p : fresh) (void)hipFree(p);
-    return r;
-  };
-  FieldDev desc[kMaxObstacles] = {};
-  for (int k = 0; k < n; k++) {
-    const size_t ns = (size_t)list[k].nx * list[k].ny * list[k].nz;
-    double* d_V = nullptr;
-    if (int r = dmalloc(&d_V, ns)) return drop(r);
-    fresh.push_back(d_V);
-    if (hipMemcpy(d_V, values[k], ns * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-      return drop(fail("tlfea_set_field_obstacles: copying the samples of field " + std::to_string(k) + " failed"));
-    desc[k] = field_dev(list[k], d_V);
-  }
-  // the descriptors go to a fresh device array: the one in use, which the list entries point into, is untouched until
-  // every allocation and copy has succeeded
-  FieldDev* d_fld_new = nullptr;
-  if (int r = dmalloc(&d_fld_new, (size_t)kMaxObstacles)) return drop(r);
-  if (hipMemcpy(d_fld_new, desc, (size_t)n * sizeof(FieldDev), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d_fld_new);
-    return drop(fail("tlfea_set_field_obstacles: copying the descriptors failed"));
-  }
-  if (int r = h->kind == kT10 ? obstacle_buffers(h, h->ob_na + n) : ancf_obstacle_buffers(h, h->ob_na + n)) {
-    (void)hipFree(d_fld_new);  // the shared buffers may have been re-zeroed: no forces until the next evaluation
-    return drop(r);
-  }
-  if (h->d_fld) (void)hipFree(h->d_fld);
-  h->d_fld = d_fld_new;
-  const std::vector<ObstacleDev> analytic = obstacle_list_analytic(h);
-  field_storage_free(h);
-  h->d_fld_V.swap(fresh);
-  std::copy(desc, desc + n, h->h_fld);
-  h->fld.assign(list, list + n);
-  obstacle_list_set(h, analytic);
-  return 0;
-}
-extern "C" int tlfea_update_field_obstacle(tlfea_t10_t h, int k, const tlfea_field_obstacle* o) {
-  NEED_FIELD_OBS(h, "tlfea_update_field_obstacle");
-  if (k < 0 || k >= (int)h->fld.size())
-    return fail("tlfea_update_field_obstacle: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->fld.size()) + " field obstacles set");
-  if (!o) return fail("tlfea_update_field_obstacle: null obstacle");
-  const std::string why = field_params_check(*o);
-  if (!why.empty()) return fail("tlfea_update_field_obstacle: field " + std::to_string(k) + ": " + why);
-  const tlfea_field_obstacle& old = h->fld[k];
-  if (o->nx != old.nx || o->ny != old.ny || o->nz != old.nz)
-    return fail("tlfea_update_field_obstacle: field " + std::to_string(k) + ": the grid is " + std::to_string(o->nx) +
-                " x " + std::to_string(o->ny) + " x " + std::to_string(o->nz) + ", the stored one " +
-                std::to_string(old.nx) + " x " + std::to_string(old.ny) + " x " + std::to_string(old.nz));
-  // the descriptor: a small copy ordered on the object's stream (the solvers' streams synchronise with it); position,
-  // velocity and the contact parameters are kernel arguments: launches already queued keep the old values
-  h->h_fld[k] = field_dev(*o, h->d_fld_V[k]);
-  HIP_TRY(hipMemcpyAsync(h->d_fld + k, &h->h_fld[k], sizeof(FieldDev), hipMemcpyHostToDevice, h->stream));
-  h->fld[k] = *o;
-  h->obs.o[h->ob_na + k] = field_obstacle_dev(*o, h->d_fld + k);
-  return 0;
-}
-extern "C" int tlfea_get_field_obstacle_resultant(tlfea_t10_t h, int k, double out[4]) {
-  NEED_FIELD_OBS(h, "tlfea_get_field_obstacle_resultant");
-  if (!out) return fail("tlfea_get_field_obstacle_resultant: null output");
-  if (k < 0 || k >= (int)h->fld.size())
-    return fail("tlfea_get_field_obstacle_resultant: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->fld.size()) + " field obstacles set");
-  HIP_TRY(hipDeviceSynchronize());
-  if (h->kind == kT10)
-    launch_obstacle_resultant(h->stream, (int)h->h_surf.size(), h->obs.n, h->d_ob_fk, h->d_ob_res);
-  else
-    launch_obstacle_resultant(h->stream, h->E, h->obs.n, h->d_ao_fk, h->d_ob_res);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, h->d_ob_res + 4 * (h->ob_na + k), 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-// Launches of at most kSdfPairsPerLaunch (sample, triangle) pairs each, so that none is long-running (DESIGN 3e'').
-constexpr long long kSdfPairsPerLaunch = 1ll << 32;
-constexpr int kSdfMaxTriangles = 1 << 24;  // 256 samples x 2^24 triangles = the bound: every launch holds a whole block
-extern "C" int tlfea_sdf_from_triangles(const double* verts, int n_verts, const int* tris, int n_tris, int nx, int ny,
-                                        int nz, const double origin[3], double spacing, double* values) {
-  if (!verts || !tris || !origin || !values) return fail("tlfea_sdf_from_triangles: null argument");
-  if (nx < 1 || ny < 1 || nz < 1) return fail("tlfea_sdf_from_triangles: the grid needs at least one sample per axis");
-  if ((long long)nx * ny * nz > kMaxFieldSamples) return fail("tlfea_sdf_from_triangles: more than 2^27 samples");
-  if (!(spacing > 0.0) || !std::isfinite(spacing)) return fail("tlfea_sdf_from_triangles: spacing must be > 0");
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(origin[c])) return fail("tlfea_sdf_from_triangles: non-finite origin");
-  if (n_verts < 0 || n_tris < 0) return fail("tlfea_sdf_from_triangles: negative count");
-  if (n_tris > kSdfMaxTriangles)  // a launch of one block of samples would exceed the pair bound
-    return fail("tlfea_sdf_from_triangles: more than 2^24 triangles");
-  const std::string why = surface_check(verts, n_verts, tris, n_tris);
-  if (!why.empty()) return fail("tlfea_sdf_from_triangles: " + why);
-  std::vector<double> tri((size_t)9 * n_tris);
-  for (int t = 0; t < n_tris; t++)
-    for (int c = 0; c < 3; c++)
-      for (int a = 0; a < 3; a++) tri[(size_t)9 * t + 3 * c + a] = verts[3 * (size_t)tris[3 * t + c] + a];
-  const long long ns = (long long)nx * ny * nz;
-  double *d_tri = nullptr, *d_out = nullptr;
-  TRY(dmalloc(&d_tri, tri.size()));
-  if (int r = dmalloc(&d_out, (size_t)ns)) {
-    (void)hipFree(d_tri);
-    return r;
-  }
-  hipError_t e = hipMemcpy(d_tri, tri.data(), tri.size() * sizeof(double), hipMemcpyHostToDevice);
-  const long long per = std::max(256ll, kSdfPairsPerLaunch / n_tris / 256 * 256);
-  for (long long first = 0; first < ns && e == hipSuccess; first += per) {
-    launch_sdf_from_triangles(nullptr, d_tri, n_tris, nx, ny, origin, spacing, first, std::min(per, ns - first), d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  }
-  if (e == hipSuccess) e = hipMemcpy(values, d_out, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d_tri);
-  (void)hipFree(d_out);
-  HIP_TRY(e);
   return 0;
 }
 
@@ -1831,7 +1205,6 @@ extern "C" int tlfea_t10_retrieve_mass_csr(tlfea_t10_t h, int* offsets, int* col
   offsets[h->N] = o;
   return 0;
 }
-#define D2H(dst, src, n) HIP_TRY(hipMemcpy(dst, src, (size_t)(n) * sizeof(*(dst)), hipMemcpyDeviceToHost))
 extern "C" int tlfea_t10_retrieve_internal_force(tlfea_t10_t h, double* f) { D2H(f, h->d_fint, 3 * h->N); return 0; }
 extern "C" int tlfea_t10_retrieve_external_force(tlfea_t10_t h, double* f) { D2H(f, h->d_fext, 3 * h->N); return 0; }
 extern "C" int tlfea_t10_retrieve_position(tlfea_t10_t h, double* x, double* y, double* z) {
@@ -1846,255 +1219,6 @@ extern "C" int tlfea_t10_retrieve_p_from_f(tlfea_t10_t h, double* P) {
 extern "C" int tlfea_t10_retrieve_deformation_gradient(tlfea_t10_t h, double* F) {
   if (!h->d_F) return fail("CalcP has not been called");
   D2H(F, h->d_F, (size_t)h->E * h->Q * 9);
-  return 0;
-}
-// ---- stress and energy recovery -----------------------------------------------------------------------------
-static int stress_prepare(tlfea_t10_t h, const double* d_vel, int want_points) {
-  if (h && h->kind != kT10) return fail("tlfea_t10_calc_stress: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "CalcStress.");
-  if (!h->have_dndu) return fail("tlfea_t10_calc_stress: CalcDnDuPre must be called first");
-  if (d_vel && h->mass_rho0 < 0.0)
-    return fail("tlfea_t10_calc_stress: a velocity was given but the mass matrix is not assembled (the kinetic energy "
-                "needs CalcMassMatrix)");
-  if (!h->is_csr_setup) TRY(tlfea_t10_build_mass_csr_pattern(h));  // the node -> element incidence of the nodal gather
-  if (!h->d_st_erec) {
-    TRY(dmalloc(&h->d_st_erec, (size_t)h->E * 10));
-    TRY(dmalloc(&h->d_st_contrib, (size_t)h->Epad * 4));
-    TRY(dmalloc(&h->d_st_nodal, (size_t)h->N * 7));
-    TRY(dmalloc(&h->d_st_part, (size_t)kStressMaxPart * 5));
-    TRY(dmalloc(&h->d_st_tot, (size_t)5));
-  }
-  if (want_points && !h->d_st_pts) TRY(dmalloc(&h->d_st_pts, (size_t)h->E * kNQ * 6));
-  return 0;
-}
-extern "C" int tlfea_t10_calc_stress(tlfea_t10_t h, const double* d_vel, int want_points) {
-  TRY(stress_prepare(h, d_vel, want_points));
-  h->st_valid = h->st_pts_valid = false;
-  launch_stress_points(h->stream, h->view(), h->mat, h->d_emat, d_vel, want_points ? h->d_st_pts : nullptr, h->d_st_erec,
-                       h->d_st_contrib);
-  launch_stress_nodal(h->stream, h->N, h->inc(), h->d_st_erec, h->d_st_nodal);
-  launch_stress_totals(h->stream, h->E, h->Epad, h->d_st_contrib, h->N, h->inc(), h->d_mval, d_vel, h->d_st_part,
-                       h->d_st_tot);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
-  h->st_valid = true;
-  h->st_pts_valid = want_points != 0;
-  return 0;
-}
-// the same with a velocity on the host (3N interleaved, or null), uploaded to a buffer of the object
-extern "C" int tlfea_t10_calc_stress_host(tlfea_t10_t h, const double* vel, int want_points) {
-  if (!vel) return tlfea_t10_calc_stress(h, nullptr, want_points);
-  if (h && h->kind != kT10) return fail("tlfea_t10_calc_stress: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "CalcStress.");
-  if (!h->d_st_vel) TRY(dmalloc(&h->d_st_vel, (size_t)3 * h->N));
-  HIP_TRY(hipMemcpy(h->d_st_vel, vel, (size_t)3 * h->N * sizeof(double), hipMemcpyHostToDevice));
-  return tlfea_t10_calc_stress(h, h->d_st_vel, want_points);
-}
-#define NEED_STRESS(h, what)                                                                            \
-  if ((h) && (h)->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)"); \
-  if (!(h) || !(h)->st_valid) return fail(std::string(what) + ": tlfea_t10_calc_stress has not been called")
-extern "C" int tlfea_t10_retrieve_point_stress(tlfea_t10_t h, double* sigma) {
-  NEED_STRESS(h, "tlfea_t10_retrieve_point_stress");
-  if (!h->st_pts_valid)
-    return fail("tlfea_t10_retrieve_point_stress: the last tlfea_t10_calc_stress did not ask for point stresses (want_points = 0)");
-  if (!sigma) return fail("tlfea_t10_retrieve_point_stress: null output");
-  D2H(sigma, h->d_st_pts, (size_t)h->E * kNQ * 6);
-  return 0;
-}
-extern "C" int tlfea_t10_retrieve_element_stress(tlfea_t10_t h, double* sigma, double* von_mises, double* psi, double* J,
-                                                 double* vol) {
-  NEED_STRESS(h, "tlfea_t10_retrieve_element_stress");
-  std::vector<double> rec((size_t)h->E * 10);
-  D2H(rec.data(), h->d_st_erec, rec.size());
-  for (int e = 0; e < h->E; e++) {
-    const double* r = &rec[(size_t)e * 10];
-    if (sigma) std::copy_n(r, 6, sigma + (size_t)e * 6);
-    if (von_mises) von_mises[e] = r[6];
-    if (psi) psi[e] = r[7];
-    if (J) J[e] = r[8];
-    if (vol) vol[e] = r[9];
-  }
-  return 0;
-}
-extern "C" int tlfea_t10_retrieve_nodal_stress(tlfea_t10_t h, double* sigma, double* von_mises) {
-  NEED_STRESS(h, "tlfea_t10_retrieve_nodal_stress");
-  std::vector<double> rec((size_t)h->N * 7);
-  D2H(rec.data(), h->d_st_nodal, rec.size());
-  for (int i = 0; i < h->N; i++) {
-    if (sigma) std::copy_n(&rec[(size_t)i * 7], 6, sigma + (size_t)i * 6);
-    if (von_mises) von_mises[i] = rec[(size_t)i * 7 + 6];
-  }
-  return 0;
-}
-extern "C" int tlfea_t10_get_energies(tlfea_t10_t h, double out[5]) {
-  NEED_STRESS(h, "tlfea_t10_get_energies");
-  if (!out) return fail("tlfea_t10_get_energies: null output");
-  std::copy_n(h->st_tot, 5, out);
-  return 0;
-}
-extern "C" double* tlfea_t10_nodal_stress_device_ptr(tlfea_t10_t h) { return h && h->st_valid ? h->d_st_nodal : nullptr; }
-// Mean duration (ms) over `reps` back-to-back launches of out[0] the point and element kernel, [1] the nodal gather,
-// [2] the two totals launches, each bracketed by one hipEvent pair (as tlfea_newton_time_kernels).
-extern "C" int tlfea_t10_time_stress_kernels(tlfea_t10_t h, const double* d_vel, int want_points, int reps, double* out_ms3) {
-  TRY(stress_prepare(h, d_vel, want_points));
-  if (!out_ms3) return fail("tlfea_t10_time_stress_kernels: null output");
-  if (reps < 1) reps = 1;
-  hipEvent_t ev[2];
-  HIP_TRY(hipEventCreate(&ev[0]));
-  HIP_TRY(hipEventCreate(&ev[1]));
-  for (int k = 0; k < 3; k++) {
-    HIP_TRY(hipEventRecord(ev[0], h->stream));
-    for (int r = 0; r < reps; r++) {
-      if (k == 0)
-        launch_stress_points(h->stream, h->view(), h->mat, h->d_emat, d_vel, want_points ? h->d_st_pts : nullptr,
-                             h->d_st_erec, h->d_st_contrib);
-      else if (k == 1) launch_stress_nodal(h->stream, h->N, h->inc(), h->d_st_erec, h->d_st_nodal);
-      else
-        launch_stress_totals(h->stream, h->E, h->Epad, h->d_st_contrib, h->N, h->inc(), h->d_mval, d_vel, h->d_st_part,
-                             h->d_st_tot);
-    }
-    HIP_TRY(hipEventRecord(ev[1], h->stream));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    out_ms3[k] = ms / reps;
-  }
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
-  h->st_valid = true;
-  h->st_pts_valid = want_points != 0;
-  return 0;
-}
-// ---- stress and energy recovery of the ANCF kinds (DESIGN 3f') ----------------------------------------------------------
-// Own entry points: the tlfea_t10_* ones above keep refusing ANCF handles.  The buffers are the d_st_* of the handle.
-#define NEED_ANCF(h, what) \
-  if ((h) && (h)->kind == kT10) return fail(std::string(what) + ": ANCF handles only (not a T10 handle)")
-static int ancf_stress_prepare(tlfea_t10_t h, const double* d_vel, int want_points) {
-  NEED_ANCF(h, "tlfea_ancf_calc_stress");
-  NEED_SETUP(h, "CalcElementStress.");
-  if (!h->have_dndu) return fail("tlfea_ancf_calc_stress: CalcDsDuPre must be called first");
-  if (d_vel && !h->ancf_mass)
-    return fail("tlfea_ancf_calc_stress: a velocity was given but the mass matrix is not assembled (the kinetic energy "
-                "needs CalcMassMatrix)");
-  if (!h->d_st_erec) {
-    // elements of every mesh node in ascending order: node = coefficient / 4, slot 0 of local node k is row 4 k of conn
-    const int E = h->E, nn = h->nn, n_nodes = h->n_nodes;
-    std::vector<int> off(n_nodes + 1, 0), el((size_t)E * nn);
-    for (int k = 0; k < nn; k++)
-      for (int e = 0; e < E; e++) off[h->h_conn[(size_t)(4 * k) * E + e] / 4 + 1]++;
-    for (int i = 0; i < n_nodes; i++) off[i + 1] += off[i];
-    std::vector<int> cur(off.begin(), off.end() - 1);
-    for (int e = 0; e < E; e++)
-      for (int k = 0; k < nn; k++) el[cur[h->h_conn[(size_t)(4 * k) * E + e] / 4]++] = e;
-    TRY(dmalloc(&h->d_st_noff, off.size()));
-    TRY(dmalloc(&h->d_st_nel, el.size()));
-    HIP_TRY(hipMemcpy(h->d_st_noff, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_st_nel, el.data(), el.size() * sizeof(int), hipMemcpyHostToDevice));
-    TRY(dmalloc(&h->d_st_contrib, (size_t)h->Epad * 4));
-    TRY(dmalloc(&h->d_st_nodal, (size_t)n_nodes * 7));
-    TRY(dmalloc(&h->d_st_part, (size_t)kStressMaxPart * 5));
-    TRY(dmalloc(&h->d_st_tot, (size_t)5));
-    TRY(dmalloc(&h->d_st_erec, (size_t)E * 10));
-  }
-  if (want_points && !h->d_st_pts) TRY(dmalloc(&h->d_st_pts, (size_t)h->E * h->Q * 6));
-  return 0;
-}
-static void ancf_stress_launch(tlfea_t10_t h, const double* d_vel, int want_points, int stage) {
-  if (stage == 0)
-    launch_ancf_stress_points(h->stream, h->view(), h->mat, d_vel, want_points ? h->d_st_pts : nullptr, h->d_st_erec,
-                              h->d_st_contrib);
-  else if (stage == 1)
-    launch_stress_node_gather(h->stream, h->n_nodes, h->d_st_noff, h->d_st_nel, h->d_st_erec, h->d_st_nodal);
-  else  // the kinetic energy runs over the n_coef rows of the mass matrix
-    launch_stress_totals(h->stream, h->E, h->Epad, h->d_st_contrib, h->N, h->inc(), h->d_mval, d_vel, h->d_st_part,
-                         h->d_st_tot);
-}
-extern "C" int tlfea_ancf_calc_stress(tlfea_t10_t h, const double* d_vel, int want_points) {
-  TRY(ancf_stress_prepare(h, d_vel, want_points));
-  h->st_valid = h->st_pts_valid = false;
-  for (int stage = 0; stage < 3; stage++) ancf_stress_launch(h, d_vel, want_points, stage);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
-  h->st_valid = true;
-  h->st_pts_valid = want_points != 0;
-  return 0;
-}
-extern "C" int tlfea_ancf_calc_stress_host(tlfea_t10_t h, const double* vel, int want_points) {
-  if (!vel) return tlfea_ancf_calc_stress(h, nullptr, want_points);
-  NEED_ANCF(h, "tlfea_ancf_calc_stress");
-  NEED_SETUP(h, "CalcElementStress.");
-  if (!h->d_st_vel) TRY(dmalloc(&h->d_st_vel, (size_t)3 * h->N));
-  HIP_TRY(hipMemcpy(h->d_st_vel, vel, (size_t)3 * h->N * sizeof(double), hipMemcpyHostToDevice));
-  return tlfea_ancf_calc_stress(h, h->d_st_vel, want_points);
-}
-#define NEED_ANCF_STRESS(h, what) \
-  NEED_ANCF(h, what);             \
-  if (!(h) || !(h)->st_valid) return fail(std::string(what) + ": tlfea_ancf_calc_stress has not been called")
-extern "C" int tlfea_ancf_retrieve_point_stress(tlfea_t10_t h, double* sigma) {
-  NEED_ANCF_STRESS(h, "tlfea_ancf_retrieve_point_stress");
-  if (!h->st_pts_valid)
-    return fail("tlfea_ancf_retrieve_point_stress: the last tlfea_ancf_calc_stress did not ask for point stresses (want_points = 0)");
-  if (!sigma) return fail("tlfea_ancf_retrieve_point_stress: null output");
-  D2H(sigma, h->d_st_pts, (size_t)h->E * h->Q * 6);
-  return 0;
-}
-extern "C" int tlfea_ancf_retrieve_element_stress(tlfea_t10_t h, double* sigma, double* von_mises, double* psi, double* J,
-                                                  double* vol) {
-  NEED_ANCF_STRESS(h, "tlfea_ancf_retrieve_element_stress");
-  std::vector<double> rec((size_t)h->E * 10);
-  D2H(rec.data(), h->d_st_erec, rec.size());
-  for (int e = 0; e < h->E; e++) {
-    const double* r = &rec[(size_t)e * 10];
-    if (sigma) std::copy_n(r, 6, sigma + (size_t)e * 6);
-    if (von_mises) von_mises[e] = r[6];
-    if (psi) psi[e] = r[7];
-    if (J) J[e] = r[8];
-    if (vol) vol[e] = r[9];
-  }
-  return 0;
-}
-extern "C" int tlfea_ancf_retrieve_nodal_stress(tlfea_t10_t h, double* sigma, double* von_mises) {
-  NEED_ANCF_STRESS(h, "tlfea_ancf_retrieve_nodal_stress");
-  std::vector<double> rec((size_t)h->n_nodes * 7);
-  D2H(rec.data(), h->d_st_nodal, rec.size());
-  for (int i = 0; i < h->n_nodes; i++) {
-    if (sigma) std::copy_n(&rec[(size_t)i * 7], 6, sigma + (size_t)i * 6);
-    if (von_mises) von_mises[i] = rec[(size_t)i * 7 + 6];
-  }
-  return 0;
-}
-extern "C" int tlfea_ancf_get_energies(tlfea_t10_t h, double out[5]) {
-  NEED_ANCF_STRESS(h, "tlfea_ancf_get_energies");
-  if (!out) return fail("tlfea_ancf_get_energies: null output");
-  std::copy_n(h->st_tot, 5, out);
-  return 0;
-}
-extern "C" double* tlfea_ancf_nodal_stress_device_ptr(tlfea_t10_t h) {
-  return h && h->kind != kT10 && h->st_valid ? h->d_st_nodal : nullptr;
-}
-// as tlfea_t10_time_stress_kernels: [0] the point kernel, [1] the mesh-node gather, [2] the two totals launches
-extern "C" int tlfea_ancf_time_stress_kernels(tlfea_t10_t h, const double* d_vel, int want_points, int reps, double* out_ms3) {
-  TRY(ancf_stress_prepare(h, d_vel, want_points));
-  if (!out_ms3) return fail("tlfea_ancf_time_stress_kernels: null output");
-  if (reps < 1) reps = 1;
-  hipEvent_t ev[2];
-  HIP_TRY(hipEventCreate(&ev[0]));
-  HIP_TRY(hipEventCreate(&ev[1]));
-  for (int k = 0; k < 3; k++) {
-    HIP_TRY(hipEventRecord(ev[0], h->stream));
-    for (int r = 0; r < reps; r++) ancf_stress_launch(h, d_vel, want_points, k);
-    HIP_TRY(hipEventRecord(ev[1], h->stream));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    out_ms3[k] = ms / reps;
-  }
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  HIP_TRY(hipMemcpy(h->st_tot, h->d_st_tot, 5 * sizeof(double), hipMemcpyDeviceToHost));
-  h->st_valid = true;
-  h->st_pts_valid = want_points != 0;
   return 0;
 }
 extern "C" int tlfea_t10_retrieve_dndu_pre(tlfea_t10_t h, double* g) { D2H(g, h->d_gradN, (size_t)h->E * h->Q * 3 * h->S); return 0; }
@@ -2505,7 +1629,7 @@ extern "C" int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_ne
   TRY(dmalloc(&s->d_scal, (size_t)4));
   HIP_TRY(hipHostMalloc((void**)&s->h_pin, (8 + kPmgTableCap) * sizeof(double)));
   TRY(dmalloc(&s->d_coef, (size_t)2 * kChebMaxDeg));
-  if (const char* e = std::getenv("TLFEA_GRAPH")) s->use_graphs = std::atoi(e) != 0;
+  s->use_graphs = env_flag("TLFEA_GRAPH", s->use_graphs);
   TRY(dmalloc(&s->d_Dinv, (size_t)9 * s->N));
   TRY(dmalloc(&s->d_D, (size_t)9 * s->N));
   TRY(dmalloc(&s->d_f32, (size_t)6 * n + (size_t)9 * s->N));
@@ -2514,12 +1638,12 @@ extern "C" int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_ne
   for (auto& e : s->ev) HIP_TRY(hipEventCreate(&e));
   HIP_TRY(hipStreamCreate(&s->stream_own));
   s->stream = s->stream_own;
-  if (const char* e = std::getenv("TLFEA_PCG_FUSED")) s->pcg_fused = std::atoi(e);
+  s->pcg_fused = env_int("TLFEA_PCG_FUSED", s->pcg_fused);
   if (const char* e = std::getenv("TLFEA_SPMV32")) s->spmv32_every = std::max(0, std::atoi(e)) & ~1;  // even: odd parity
   if (const char* e = std::getenv("TLFEA_CHEB_DEG")) s->lin.cheb_degree = std::min(kChebMaxDeg, std::max(0, std::atoi(e)));
-  if (const char* e = std::getenv("TLFEA_SPMV_NT")) s->spmv_nt = std::atoi(e) != 0;
-  if (const char* e = std::getenv("TLFEA_CHEB_BITS")) s->lin.cheb_bits = std::atoi(e);
-  if (const char* e = std::getenv("TLFEA_PRECOND")) s->lin.precond = std::atoi(e);
+  s->spmv_nt = env_flag("TLFEA_SPMV_NT", s->spmv_nt);
+  s->lin.cheb_bits = env_int("TLFEA_CHEB_BITS", s->lin.cheb_bits);
+  s->lin.precond = env_int("TLFEA_PRECOND", s->lin.precond);
   if (const char* e = std::getenv("TLFEA_ASSEMBLE"))
     s->asm_mode = (std::string(e) == "kbuf") ? 1 : (std::string(e) == "general") ? 2 : 0;
   if (const char* e = std::getenv("TLFEA_MASS")) s->mass_mode = (std::string(e) == "csr") ? 1 : 0;
@@ -3051,7 +2175,7 @@ extern "C" int tlfea_rccl_comm_create_timeout(const char* id128, int rank, int w
 // process once the self-check below finds that RCCL cannot be captured / replayed here
 static bool g_rccl_graph_ok = true;
 static bool halo_graph_wanted() {
-  static const bool on = !(std::getenv("TLFEA_HALO_GRAPH") && std::atoi(std::getenv("TLFEA_HALO_GRAPH")) == 0);
+  static const bool on = env_flag("TLFEA_HALO_GRAPH", true);
   return on && g_rccl_graph_ok;
 }
 extern "C" int tlfea_rccl_self_check(void* comm, int rank, int world, double timeout_s) {
@@ -3679,7 +2803,7 @@ static void fill_mass_shape(tlfea_newton_t s, MassTerm& mt) { shape_at_rule_poin
 // ---- matrix-free product of the CG iteration --------------------------------------------------------------
 // TLFEA_SPMV_MATFREE: 0 never, 1 wherever eligible, unset = eligible and at least kMatfreeMinRows node rows
 static int matfree_env() {
-  static const int m = std::getenv("TLFEA_SPMV_MATFREE") ? (std::atoi(std::getenv("TLFEA_SPMV_MATFREE")) != 0 ? 1 : 0) : -1;
+  static const int m = env_tristate("TLFEA_SPMV_MATFREE");
   return m;
 }
 // Two launches (plus the direction kernel on meshes that would run the fused SpMV) replace one.  Measured on the SVK bars
@@ -3696,7 +2820,7 @@ static bool matfree_chosen(tlfea_newton_t s) {
 // TLFEA_MATFREE_COMPACT: 1 (default) = a wavefront sums its element rows per node before they are stored
 // (matfree_compact.h), 0 = one row per (element, local node) in [10][Epad][3].  Read once per process.
 static bool matfree_compact_env() {
-  static const bool on = !std::getenv("TLFEA_MATFREE_COMPACT") || std::atoi(std::getenv("TLFEA_MATFREE_COMPACT")) != 0;
+  static const bool on = env_flag("TLFEA_MATFREE_COMPACT", true);
   return on;
 }
 // the element rows' buffer (233 MB at config C, 75 MB in the compact form) and the compact form's lists: on first use,
@@ -3923,7 +3047,7 @@ static int cheb_bits_eff(tlfea_newton_t s) {
 // fp8 e4m3 -- 13 instead of 22 bytes per block in the cycle's four fine passes; the coarser levels keep fp16
 static int precond_eff(tlfea_newton_t s);
 static int fine_bits(tlfea_newton_t s) {
-  static const int forced = std::getenv("TLFEA_FINE_BITS") ? std::atoi(std::getenv("TLFEA_FINE_BITS")) : 0;
+  static const int forced = env_int("TLFEA_FINE_BITS", 0);
   const int bits = cheb_bits_eff(s);
   return (forced == 8 && bits == 16 && precond_eff(s) == 2 && !s->ar) ? 8 : bits;
 }
@@ -3943,7 +3067,7 @@ static void c32_step(tlfea_newton_t s, const C32Level& L, C32Vecs& v, int rows, 
 static bool blk12_on(tlfea_newton_t s) {
   if (s->blk12 >= 0) return s->blk12 == 1;
   tlfea_t10_t d = s->d;
-  static const bool wanted = !(std::getenv("TLFEA_ANCF_BLOCK12") && std::atoi(std::getenv("TLFEA_ANCF_BLOCK12")) == 0);
+  static const bool wanted = env_flag("TLFEA_ANCF_BLOCK12", true);
   bool ok = wanted && d->kind != kT10 && !dist_on(s) && s->N % 4 == 0 && !d->h_off.empty();
   for (int p = 0; ok && p < s->N / 4; p++) {
     const int o0 = d->h_off[4 * p], deg = d->h_off[4 * p + 1] - o0;
@@ -4026,8 +3150,7 @@ static int estimate_lam_max_local(tlfea_newton_t s) {
   double ss = 0.0;
   TRY(fetch_scalar(s, s->d_scal, &ss));
   if (!(ss > 0.0)) return fail("lambda_max estimate failed");
-  const char* fe = std::getenv("TLFEA_CHEB_LMAX_SCALE");
-  s->lam_max_loc = std::sqrt(ss) * (fe ? std::atof(fe) : 1.0);
+  s->lam_max_loc = std::sqrt(ss) * env_double("TLFEA_CHEB_LMAX_SCALE", 1.0);
   s->lam_max = s->lam_max_loc;
   return 0;
 }
@@ -4035,7 +3158,7 @@ static int estimate_lam_max_local(tlfea_newton_t s) {
 // TLFEA_LMAX_MATFREE: 1 (default) = the fine power iteration's product runs through the matrix-free pair in
 // the solves whose CG iteration does, 0 = always the CSR product.  Read once per process.
 static bool lmax_matfree_env() {
-  static const bool on = !std::getenv("TLFEA_LMAX_MATFREE") || std::atoi(std::getenv("TLFEA_LMAX_MATFREE")) != 0;
+  static const bool on = env_flag("TLFEA_LMAX_MATFREE", true);
   return on;
 }
 
@@ -4047,7 +3170,7 @@ static int estimate_lam_max(tlfea_newton_t s, const double* d_b) {
   const bool cold = !(s->lam_max > 0.0);
   // warm: H moves little between Newton iterations and the vector is kept, so the power iteration simply continues across
   // solves -- one product per solve (each is a full fp64 SpMV: 0.7 ms at config C)
-  static const int warm_its = std::getenv("TLFEA_LMAX_WARM_ITERS") ? std::max(1, std::atoi(std::getenv("TLFEA_LMAX_WARM_ITERS"))) : 1;
+  static const int warm_its = std::max(1, env_int("TLFEA_LMAX_WARM_ITERS", 1));
   const int iters = cold ? 16 : warm_its;
   // v <- D^-1 H v / ||D^-1 H v||, the norm stays on the device between iterations: one host read at the end
   // overlapping partition: the iteration lives on the owned rows; ghost layer 1 of the vector is refreshed before every
@@ -4084,8 +3207,7 @@ static int estimate_lam_max(tlfea_newton_t s, const double* d_b) {
     return fail("lambda_max estimate failed");
   }
   // TLFEA_CHEB_LMAX_SCALE (tests only): scales the estimate to exercise the breakdown recovery in pcg()
-  const char* fe = std::getenv("TLFEA_CHEB_LMAX_SCALE");
-  const double fudge = fe ? std::atof(fe) : 1.0;
+  const double fudge = env_double("TLFEA_CHEB_LMAX_SCALE", 1.0);
   s->lam_max = lam * fudge;
   return 0;
 }
@@ -4182,11 +3304,11 @@ static int cheb_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* 
 // gives 159 ms, 48/3200 108 ms) -- about 3.2 per doubling of the node count, with kappa_c = 1.5 kc^2.  The fine
 // smoother stays the 2-term polynomial on [lmax/8, lmax] (kappa_s 5 / 8 / 12: 103 / 98 / 158 ms at config C).
 static double pmg_kappa_coarse(int kc) {
-  static const double forced = std::getenv("TLFEA_PMG_KAPPA_C") ? std::atof(std::getenv("TLFEA_PMG_KAPPA_C")) : 0.0;
+  static const double forced = env_double("TLFEA_PMG_KAPPA_C", 0.0);
   return forced > 1.0 ? forced : 1.5 * kc * kc;
 }
 static int pmg_coarse_degree_eff(tlfea_newton_t s) {
-  static const int forced = std::getenv("TLFEA_PMG_KC") ? std::atoi(std::getenv("TLFEA_PMG_KC")) : 0;
+  static const int forced = env_int("TLFEA_PMG_KC", 0);
   const int n_vertex = (dist_on(s) && s->pmg.Nc_glob > 0) ? s->pmg.Nc_glob : s->pmg.vertex.N;
   const int base = pmg_poly_degree(n_vertex, forced, kPmgMaxCoarseDeg);
   return std::min(kPmgMaxCoarseDeg, (int)std::lround(base * s->pmg.kc_boost));
@@ -4198,14 +3320,14 @@ static int pmg_coarse_degree_eff(tlfea_newton_t s) {
 // real meshes: 4 terms cut res16 from 7.9 to 6.4 ms and the badly graded teapot from 35.7 to 24.6 ms per Newton iteration,
 // profiles/r03_real_mesh_timing.txt).  The partitioned solve keeps 2 (the ghost depth it needs grows with ks).
 static int pmg_ks(tlfea_newton_t s) {
-  static const int forced = std::getenv("TLFEA_PMG_KS") ? std::atoi(std::getenv("TLFEA_PMG_KS")) : 0;
+  static const int forced = env_int("TLFEA_PMG_KS", 0);
   if (forced >= 1) return std::min(forced, kPmgMaxKs);
   if (dist_on(s)) return 2;
   return s->N <= 100000 ? 4 : (s->N <= 500000 ? 3 : 2);  // 3: M2 (172 k nodes) 10.4 -> 9.7 ms, M3 (402 k) 20.5 -> 19.9 ms; C keeps 2
 }
 // the smoother's interval [lmax / kappa_s, lmax]: 8 for two terms, 1.5 ks^2 beyond (TLFEA_PMG_KAPPA_S)
 static double pmg_kappa_s(tlfea_newton_t s) {
-  static const double forced = std::getenv("TLFEA_PMG_KAPPA_S") ? std::atof(std::getenv("TLFEA_PMG_KAPPA_S")) : 0.0;
+  static const double forced = env_double("TLFEA_PMG_KAPPA_S", 0.0);
   if (forced > 1.0) return forced;
   const int ks = pmg_ks(s);
   return ks <= 2 ? 8.0 : 1.5 * ks * ks;
@@ -4213,7 +3335,7 @@ static double pmg_kappa_s(tlfea_newton_t s) {
 // three levels: the vertex level smooths with ks2 terms (TLFEA_PMG_KS2) -- its table [steps | residual pass | restart]
 // sits where the two-level cycle keeps the vertex-level polynomial; the level-3 polynomial follows (pmg_coef.h, PmgTable)
 static int pmg_ks2(tlfea_newton_t s) {
-  static const int forced = std::getenv("TLFEA_PMG_KS2") ? std::atoi(std::getenv("TLFEA_PMG_KS2")) : 0;
+  static const int forced = env_int("TLFEA_PMG_KS2", 0);
   if (forced >= 1) return std::min(forced, kPmgMaxKs);
   // measured at config C with aggregates of ~2.2 mean vertex edges: 2 terms -> 80 ms, 4 -> 65, 6 -> 58, 10 -> 58, 12 -> 69.
   // Larger aggregates (the grid of bins is coarsened to keep the replicated level small on many ranks) leave the
@@ -4222,7 +3344,7 @@ static int pmg_ks2(tlfea_newton_t s) {
   return std::max(6, std::min(kPmgMaxKs, (int)std::lround(2.7 * ratio)));  // (5 terms at 2.0-edge cells: 63.5 ms against 59.0 with 6)
 }
 static double pmg_kappa_s2(tlfea_newton_t s) {
-  static const double forced = std::getenv("TLFEA_PMG_KAPPA_S2") ? std::atof(std::getenv("TLFEA_PMG_KAPPA_S2")) : 0.0;
+  static const double forced = env_double("TLFEA_PMG_KAPPA_S2", 0.0);
   const int k = pmg_ks2(s);
   return forced > 1.0 ? forced : 2.5 * k * k;  // 90 at 6 terms (measured optimum 60-100)
 }
@@ -4230,14 +3352,14 @@ static double pmg_kappa_s2(tlfea_newton_t s) {
 // 3 = fourth-kind Chebyshev (needs lmax only), 4 = fourth kind with the optimised weights of Lottes (2022),
 // "Optimal polynomial smoothers for multigrid V-cycles": the z^ update is weighted, z^_k = z^_{k-1} + beta_k d_{k-1}.
 static int pmg_smoother_kind() {
-  static const int k = std::getenv("TLFEA_PMG_SMOOTHER") ? std::atoi(std::getenv("TLFEA_PMG_SMOOTHER")) : 1;
+  static const int k = env_int("TLFEA_PMG_SMOOTHER", 1);
   return (k == 3 || k == 4) ? k : 1;
 }
 // Restriction through the stored operator R = S_c P^T S_f^-1 Hs instead of the fine (0, 0) residual pass (pmg_apply):
 // one GPU, first-kind smoother, fine copy in 16 or 32 bits, T10 hierarchy with R built.  TLFEA_PMG_RESTRICT_OP=0 keeps
 // the residual pass (A/B runs, and the sequence every other configuration runs).
 static bool pmg_rop_wanted() {
-  static const bool on = !(std::getenv("TLFEA_PMG_RESTRICT_OP") && std::atoi(std::getenv("TLFEA_PMG_RESTRICT_OP")) == 0);
+  static const bool on = env_flag("TLFEA_PMG_RESTRICT_OP", true);
   return on;
 }
 // The one statement of eligibility, in three stages: what the mesh and the process allow (pmg_prepare builds the lists
@@ -4255,8 +3377,7 @@ static bool pmg_rop_now(tlfea_newton_t s) { return pmg_rop_on(s) && s->pmg.rop.b
 // ---- fine smoother from the element records (DESIGN 3g') ----------------------------------------------------------------
 // TLFEA_PMG_FINE_MATFREE: 0 never, 1 wherever eligible, unset = eligible and at least kFineMatfreeMinRows node rows.  Read once.
 static int fine_matfree_env() {
-  static const int m =
-      std::getenv("TLFEA_PMG_FINE_MATFREE") ? (std::atoi(std::getenv("TLFEA_PMG_FINE_MATFREE")) != 0 ? 1 : 0) : -1;
+  static const int m = env_tristate("TLFEA_PMG_FINE_MATFREE");
   return m;
 }
 // Measured on the SVK bars (DESIGN 3g'): 172 k nodes lose 6 % (three smoother terms, and the fp16 copy of that size is
@@ -4355,17 +3476,17 @@ static int pmg_levels_wanted(int n_vertex) {
   // against 80 ms per Newton iteration at config C, 23 CG iterations instead of 30 (profiles/r03_sweep_pmg3_*.txt).  Default
   // from 20 000 vertex nodes up (below that the cycle is launch-latency-bound and the extra launches cost more than the
   // shorter polynomial saves: config B 2 197 vertices); TLFEA_PMG_LEVELS=2|3 forces either.
-  static const int forced = std::getenv("TLFEA_PMG_LEVELS") ? std::atoi(std::getenv("TLFEA_PMG_LEVELS")) : 0;
-  static const int min_v = std::getenv("TLFEA_PMG_L3_MIN") ? std::atoi(std::getenv("TLFEA_PMG_L3_MIN")) : 20000;
+  static const int forced = env_int("TLFEA_PMG_LEVELS", 0);
+  static const int min_v = env_int("TLFEA_PMG_L3_MIN", 20000);
   if (forced == 2 || forced == 3) return forced;
   return n_vertex >= min_v ? 3 : 2;
 }
 static int pmg_level3_degree(int n3) {
-  static const int forced = std::getenv("TLFEA_PMG_KC3") ? std::atoi(std::getenv("TLFEA_PMG_KC3")) : 0;
+  static const int forced = env_int("TLFEA_PMG_KC3", 0);
   return pmg_poly_degree(n3, forced, kPmgMaxLevel3Deg);
 }
 static double pmg_kappa_level3(int kc) {
-  static const double forced = std::getenv("TLFEA_PMG_KAPPA_C3") ? std::atof(std::getenv("TLFEA_PMG_KAPPA_C3")) : 0.0;
+  static const double forced = env_double("TLFEA_PMG_KAPPA_C3", 0.0);
   return forced > 1.0 ? forced : 1.5 * kc * kc;
 }
 // shape of the cycle a solve would run now, hence where its coefficients sit in pmg.d_coef
@@ -4605,8 +3726,8 @@ static int pmg_prepare(tlfea_newton_t s) {
         }
         n_own_glob = (double)m.Nc_glob;
       }
-      static const double factor = std::getenv("TLFEA_PMG_BIN") ? std::atof(std::getenv("TLFEA_PMG_BIN")) : 2.0;
-      static const double max_bins = std::getenv("TLFEA_PMG_BINS_MAX") ? std::atof(std::getenv("TLFEA_PMG_BINS_MAX")) : 12000.0;
+      static const double factor = env_double("TLFEA_PMG_BIN", 2.0);
+      static const double max_bins = env_double("TLFEA_PMG_BINS_MAX", 12000.0);
       const double mean_len = n_len > 0.0 ? sum_len / n_len : 1.0;
       BinGrid grid = bin_grid(lo, hi, mean_len, max_len, factor);
       // the replicated level stays small: at most max_bins cells, whatever the number of ranks
@@ -5205,9 +4326,9 @@ static int direct_prepare_native(tlfea_newton_t s, const std::vector<double>& X)
   const int N = s->N;
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  static const long long forced = std::getenv("TLFEA_DIRECT_MAX_NNZ") ? std::atoll(std::getenv("TLFEA_DIRECT_MAX_NNZ")) : 0;
+  static const long long forced = env_ll("TLFEA_DIRECT_MAX_NNZ", 0);
   const long long max_doubles = forced > 0 ? forced : (long long)(0.8 * (double)free_b / sizeof(double));
-  static const int leaf = std::getenv("TLFEA_DIRECT_LEAF") ? std::atoi(std::getenv("TLFEA_DIRECT_LEAF")) : 32;
+  static const int leaf = env_int("TLFEA_DIRECT_LEAF", 32);
   if (!mf_plan_build(N, d->h_off.data(), d->h_cols.data(), X.data(), X.data() + N, X.data() + 2 * (size_t)N, leaf, max_doubles,
                      m.plan))
     return fail("sparse direct solve: the Cholesky factor and front workspaces of this mesh do not fit the device memory "
@@ -5287,7 +4408,7 @@ static int direct_prepare(tlfea_newton_t s) {
     for (int i = 0; i < N; i++)
       for (int c = 0; c < 3; c++) X[(size_t)c * N + i] = X[(size_t)c * N + (i / 4) * 4];
   DirectHost h;
-  static const long long max_nnz = std::getenv("TLFEA_DIRECT_MAX_NNZ") ? std::atoll(std::getenv("TLFEA_DIRECT_MAX_NNZ")) : 400000000LL;
+  static const long long max_nnz = env_ll("TLFEA_DIRECT_MAX_NNZ", 400000000LL);
   if (!direct_symbolic(N, d->h_off.data(), d->h_cols.data(), X.data(), X.data() + N, X.data() + 2 * (size_t)N, max_nnz, h))
     return fail("sparse direct solve: the Cholesky factor of this mesh exceeds the size limit (TLFEA_DIRECT_MAX_NNZ, default "
                 "4e8 entries = 3.2 GB); use the iterative solver");
@@ -5524,7 +4645,7 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
     if (s->last_outer_iters > 1 && s->last_deg == deg && s->last_bits == bits) {
       // (a few iterations earlier, not one: the count can DROP by more than one between solves -- from the first Newton
       // iteration of a step to the second -- and starting at last - 1 then over-solves for several solves in a row)
-      static const int back = std::getenv("TLFEA_PCG_CHECK_BACK") ? std::max(1, std::atoi(std::getenv("TLFEA_PCG_CHECK_BACK"))) : 4;
+      static const int back = std::max(1, env_int("TLFEA_PCG_CHECK_BACK", 4));
       first_check = std::max(1, s->last_outer_iters - back);
       check_every = 1;
     }
@@ -5969,8 +5090,7 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
   const C32Level Lc = V.c32(cheb_bits_eff(s), -1);
   for (int k = 0; k < 7; k++) {
     if (k >= 5 && !(s->pmg.ok && s->pmg.vertex.d_B8)) break;
-    HIP_TRY(hipEventRecord(s->ev[6], s->stream));
-    for (int r = 0; r < reps; r++) {
+    auto launch = [&](int r) -> int {  // one repetition of kernel k
       if (k == 0) {
         MassTerm mt{};
         const bool mir = mass_in_residual(s);
@@ -5978,7 +5098,7 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
         launch_residual_newton(s, use_direct(s) ? s->d_Fq : nullptr, mir ? &mt : nullptr);
       }
       else if (k == 1) {
-        if (use_direct(s)) break;  // no separate tangent launch on the fused path: out[1] = 0
+        if (use_direct(s)) return kStopReps;  // no separate tangent launch on the fused path: out[1] = 0
         TRY(ensure_kbuf(s));
         launch_tangent_blocks(s->stream, d->view(), d->mat, p.time_step, s->d_Kbuf, d->d_emat);
       } else if (k == 2 && use_direct(s))  // out[2] = the fused tangent + assembly launch
@@ -6018,12 +5138,9 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
       else  // fp64 polynomial step
         launch_cheb_step(s->stream, N, d->inc(), s->d_H, s->d_Dinv, s->d_cd, s->d_coef + 2, s->d_cd2, s->d_zv, s->d_cres,
                          s->d_r, s->d_w, part(s, 0), false);
-    }
-    HIP_TRY(hipEventRecord(s->ev[7], s->stream));
-    HIP_TRY(hipEventSynchronize(s->ev[7]));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[6], s->ev[7]));
-    out_ms4[k] = ms / reps;
+      return 0;
+    };
+    TRY(time_reps(s->stream, reps, &out_ms4[k], launch));
     if (k == 6) out_ms4[k] /= (double)(pmg_coarse_degree_eff(s) + 2);  // per launch of the cycle pattern
   }
   HIP_TRY(hipGetLastError());
@@ -6401,7 +5518,7 @@ extern "C" int tlfea_newton_modal_solve(tlfea_newton_t s, const tlfea_modal_opts
   s->prm.time_step = 1.0 / std::sqrt(o.shift);
   int rc = assemble(s, /*fq_fresh=*/false);
   if (!rc) rc = modal_iterate(s, o, m, omega2, modes, resid, info);
-  const std::string why = rc ? g_err : std::string();
+  const std::string why = rc ? api_error() : std::string();
   (void)hipStreamSynchronize(s->stream);
   s->prm.time_step = h0;
   s->lam_safety = safety0;
@@ -6412,7 +5529,7 @@ extern "C" int tlfea_newton_modal_solve(tlfea_newton_t s, const tlfea_modal_opts
   const int rc2 = assemble(s, /*fq_fresh=*/false);  // H of the caller's time step again
   (void)hipStreamSynchronize(s->stream);
   if (rc) {
-    g_err = why;
+    api_error() = why;
     return rc;
   }
   return rc2;
@@ -6478,11 +5595,11 @@ extern "C" int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, 
     return 0;
   };
   const int rc = run();
-  const std::string why = rc ? g_err : std::string();
+  const std::string why = rc ? api_error() : std::string();
   (void)hipStreamSynchronize(s->stream);
   s->hook_lam[0] = s->lam_max; s->hook_lam[1] = s->pmg.vertex.lam; s->hook_lam[2] = s->pmg.agg.lvl.lam;
   keep.restore();
-  if (rc) g_err = why;
+  if (rc) api_error() = why;
   return rc;
 }
 extern "C" int tlfea_newton_apply_preconditioner(tlfea_newton_t s, const double* r, double* z) {
@@ -6537,14 +5654,8 @@ extern "C" int tlfea_newton_modal_time_spmm(tlfea_newton_t s, int m, int reps, d
   TRY(wk.alloc(&dX, (size_t)n * m)); TRY(wk.alloc(&dY, (size_t)n * m));
   launch_block_hash(s->stream, n, m, 0u, modal_mask(s), dX, m);
   modal_product(s, 0, m, dX, m, dY, m, modal_mask(s));
-  HIP_TRY(hipEventRecord(s->ev[0], s->stream));
-  for (int r = 0; r < reps; r++) modal_product(s, 0, m, dX, m, dY, m, modal_mask(s));
-  HIP_TRY(hipEventRecord(s->ev[1], s->stream));
-  HIP_TRY(hipEventSynchronize(s->ev[1]));
+  TRY(time_reps(s->stream, reps, ms_out, [&](int) { modal_product(s, 0, m, dX, m, dY, m, modal_mask(s)); return 0; }));
   HIP_TRY(hipGetLastError());
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-  *ms_out = (double)ms / reps;
   return 0;
 }
 extern "C" int tlfea_newton_modal_gram(tlfea_newton_t s, int p, int q, const double* X, const double* Y, double* G) {
@@ -6631,7 +5742,7 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
   TRY(begin_step(s));
   int n_outer = 0, n_newton = 0, pcg_total = 0;
   double norm_g = 0.0, norm_c = 0.0;
-  const int fail_hook = std::getenv("TLFEA_TEST_FAIL_LINSOLVE") ? std::atoi(std::getenv("TLFEA_TEST_FAIL_LINSOLVE")) : -1;
+  const int fail_hook = env_int("TLFEA_TEST_FAIL_LINSOLVE", -1);
   // Rigid obstacles with friction: the regularised Coulomb term switches between a stiff stick branch and a sliding branch
   // whose exact Hessian has no stiffness along the slip, so a full Newton step can jump across the stick window and back
   // forever.  The step is then halved (up to kMaxHalvings times) until ||g|| decreases; the gradient of the
@@ -6697,7 +5808,7 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
   const int rc_step = run();
   if (rc_step) {
     // put the state back to the start of the step (x = x_prev, v, v_prev, lambda as they came in) and report what ran
-    const std::string why = g_err;
+    const std::string why = api_error();
     const size_t nb = (size_t)s->N * sizeof(double);
     (void)hipMemcpyAsync(s->d_v, s->d_step0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream);
     (void)hipMemcpyAsync(s->d_vprev, s->d_step0 + n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream);
@@ -6710,7 +5821,7 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
     s->stats[0] = n_outer; s->stats[1] = n_newton; s->stats[2] = norm_g; s->stats[3] = norm_c;
     s->stats[4] = pcg_total; s->stats[5] = 0.0;
     s->adj_state = 3;
-    g_err = why;
+    api_error() = why;
     return rc_step;
   }
   HIP_TRY(hipEventRecord(e1, s->stream));
@@ -6892,23 +6003,8 @@ extern "C" int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, doubl
   HIP_TRY(hipMemset(h->d_sn_w, 0, n * sizeof(double)));
   HIP_TRY(hipMemcpy(h->d_sn_w, h->d_x, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice));
   HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
-  hipEvent_t ev[2];
-  HIP_TRY(hipEventCreate(&ev[0]));
-  HIP_TRY(hipEventCreate(&ev[1]));
-  for (int k = 0; k < 2; k++) {
-    HIP_TRY(hipEventRecord(ev[0], h->stream));
-    for (int r = 0; r < reps; r++) {
-      if (k == 0) sens_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u);
-      else sens_launch_sums(h, h->stream);
-    }
-    HIP_TRY(hipEventRecord(ev[1], h->stream));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    out_ms2[k] = ms / reps;
-  }
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
+  TRY(time_reps(h->stream, reps, &out_ms2[0], [&](int) { sens_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u); return 0; }));
+  TRY(time_reps(h->stream, reps, &out_ms2[1], [&](int) { sens_launch_sums(h, h->stream); return 0; }));
   return 0;
 }
 
@@ -6980,7 +6076,7 @@ extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_ad
   if (!rc && hipMemcpyAsync(s->d_b, vt, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream) != hipSuccess)
     rc = fail("tlfea_newton_adjoint_step: device copy failed");
   if (!rc) rc = pcg(s, s->d_b, s->d_dv, &it, &rel);
-  const std::string why = rc ? g_err : std::string();
+  const std::string why = rc ? api_error() : std::string();
   s->lam_safety = safety0;
   s->pmg.kc_boost = boost0;
   s->last_outer_iters = outer0; s->last_deg = deg0; s->last_bits = bits0; s->mf.last_mode = mode0;
@@ -6988,7 +6084,7 @@ extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_ad
   if (rc) {
     (void)hipStreamSynchronize(s->stream);
     keep.restore();
-    g_err = why;
+    api_error() = why;
     return rc;
   }
   const double* w = s->d_dv;
