@@ -421,6 +421,11 @@ int tlfea_newton_get_direct_info(tlfea_newton_t s, long long *out22);
 int tlfea_newton_get_direct_fronts(tlfea_newton_t s, int *order, int *fronts7);
 int tlfea_newton_pmg_restrict_op_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals);
 int tlfea_newton_pmg_fine_copy_retrieve(tlfea_newton_t s, int *off, int *cols, double *vals, double *sc_f, double *sc_c);
+/* Test hook of the fine level's low-precision copy.  A set-up that can still choose the fine smoother from the element
+ * records does not convert it; fine_copy_retrieve, tlfea_newton_time_kernels and every pass that streams the copy convert
+ * on demand from the H on the device and the scaling of the last set-up.  out3 = [0] bits of the copy allocated (0: none),
+ * [1] 1 when the copy is that of the last set-up's H, [2] fine-level conversions since the solver was created. */
+int tlfea_newton_get_fine_copy_state(tlfea_newton_t s, int *out3);
 int tlfea_newton_hessian_nnz(tlfea_newton_t s, int *nnz);
 /* H in the reference's DOF-level CSR (SyncedNewton.cu:163-205): rows 3N, sorted columns */
 int tlfea_newton_retrieve_hessian_csr(tlfea_newton_t s, int *row_offsets, int *col_indices, double *values);

@@ -284,7 +284,21 @@ struct RopHost {
   std::vector<int> con_off;         // [nnz+1] contributions to each R block
   std::vector<int> con_blk;         // fine block index off[i] + k
   std::vector<unsigned char> con_ord;  // position of the child i in ch[ch_off[I] ..]
+  // The same contributions by SOURCE, for the build that streams each child's row of H in order (pmg_rop_stream_kernel):
+  // con_pos[pos_off[t] + k] = position in R row I of the column of block k of child ch[t]'s fine row -- layout
+  // [I][child][k], pos_off one prefix entry per child (a row's own offset is pos_off[ch_off[I]]).  16 bits: only rows of at
+  // most 128 blocks take that build (pmg_rop_long_rows lists the others), a longer row's entries saturate and are never read.
+  std::vector<int> pos_off;              // [children + 1]
+  std::vector<unsigned short> con_pos;   // [n_con]
 };
+
+// Rows of R longer than `cap` blocks, ascending: the streamed build leaves them to the gather kernel.
+inline std::vector<int> pmg_rop_long_rows(const RopHost& o, int cap) {
+  std::vector<int> rows;
+  for (int I = 0; I < o.Nc; I++)
+    if (o.off[I + 1] - o.off[I] > cap) rows.push_back(I);
+  return rows;
+}
 
 // off/cols: fine node adjacency (sorted).  Returns false when R does not fit the 32-bit / 8-bit index types.
 inline bool pmg_restrict_op_build(int N, const int* off, const int* cols, const PmgHost& h, RopHost& o) {
@@ -360,6 +374,9 @@ inline bool pmg_restrict_op_build(int N, const int* off, const int* cols, const 
   for (int b = 0; b < o.nnz; b++) o.con_off[b + 1] += o.con_off[b];
   o.con_blk.assign((size_t)o.n_con, 0);
   o.con_ord.assign((size_t)o.n_con, 0);
+  o.con_pos.assign((size_t)o.n_con, 0);
+  o.pos_off.assign(o.ch.size() + 1, 0);
+  for (size_t t = 0; t < o.ch.size(); t++) o.pos_off[t + 1] = o.pos_off[t] + (off[o.ch[t] + 1] - off[o.ch[t]]);
   // pass 3: fill, children ascending (so every block's list is in ascending child order)
 #pragma omp parallel
   {
@@ -375,6 +392,7 @@ inline bool pmg_restrict_op_build(int N, const int* off, const int* cols, const 
           const int p = (int)(std::lower_bound(row, row + len, cols[g]) - row);
           o.con_blk[cur[p]] = g;
           o.con_ord[cur[p]++] = (unsigned char)(t - o.ch_off[I]);
+          o.con_pos[(size_t)o.pos_off[t] + (g - off[i])] = (unsigned short)std::min(p, 65535);
         }
       }
     }

@@ -1697,12 +1697,14 @@ __global__ __launch_bounds__(256) void pmg_rop_build_h_kernel(
     int Nc, const int* __restrict__ r_off, const int* __restrict__ r_cols, const int* __restrict__ con_off,
     const int* __restrict__ con_blk, const unsigned char* __restrict__ con_ord, const int* __restrict__ ch_off,
     const int* __restrict__ ch, const float* __restrict__ ch_w, const int* __restrict__ f_off, const double* __restrict__ Hval,
-    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8, float* __restrict__ R1) {
+    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8, float* __restrict__ R1,
+    const int* __restrict__ rows) {
   __shared__ double tabw[8][kRopTab];
   __shared__ int tabo[8][kRopTab][2];
   const int lane = threadIdx.x & 31, rw = threadIdx.x >> 5;
-  const int I = blockIdx.x * 8 + rw;
-  if (I >= Nc) return;
+  const int slot = blockIdx.x * 8 + rw;  // rows: the Nc rows of this launch (the streamed build's long rows), null = all
+  if (slot >= Nc) return;
+  const int I = rows ? rows[slot] : slot;
   const double sI[3] = {sc_c[3 * I], sc_c[3 * I + 1], sc_c[3 * I + 2]};
   const int c0 = ch_off[I], b1 = r_off[I + 1];
   const int n_tab = min(ch_off[I + 1] - c0, kRopTab);
@@ -1738,7 +1740,7 @@ __global__ __launch_bounds__(256) void pmg_rop_build_h_kernel(
 #pragma unroll
       for (int d = 0; d < 3; d++)
 #pragma unroll
-        for (int e = 0; e < 3; e++) acc[3 * d + e] += w * Hb[(size_t)d * 3 * deg + e];
+        for (int e = 0; e < 3; e++) acc[3 * d + e] = fma(w, Hb[(size_t)d * 3 * deg + e], acc[3 * d + e]);  // (as contracted before)
     }
     const int j = r_cols[b];
     const double sj[3] = {sc_f[3 * j], sc_f[3 * j + 1], sc_f[3 * j + 2]};
@@ -1749,11 +1751,151 @@ __global__ __launch_bounds__(256) void pmg_rop_build_h_kernel(
     R1[b] = (float)(sI[2] * acc[8] * sj[2]);
   }
 }
+// rows / n_rows: only these rows (n_rows of them), null = all Nc
 void launch_pmg_rop_build_h(hipStream_t s, int Nc, const int* r_off, const int* r_cols, const int* con_off, const int* con_blk,
                             const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const int* f_off,
-                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1) {
-  hipLaunchKernelGGL(pmg_rop_build_h_kernel, dim3((Nc + 7) / 8), dim3(256), 0, s, Nc, r_off, r_cols, con_off, con_blk, con_ord,
-                     ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, (Blk8<float>*)R8, R1);
+                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1, const int* rows,
+                            int n_rows) {
+  const int n = rows ? n_rows : Nc;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(pmg_rop_build_h_kernel, dim3((n + 7) / 8), dim3(256), 0, s, n, r_off, r_cols, con_off, con_blk, con_ord,
+                     ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, (Blk8<float>*)R8, R1, rows);
+}
+
+// The same R with the fine rows read whole and in order (DESIGN 3g').  One wavefront per coarse row keeps an image
+// [blocks][9] of the R row in LDS, zeroes it and takes the row's children in ascending order: child i's row of H is the
+// 9 deg contiguous doubles from 9 off[i], laid out [d][k][e], so lane m = d deg + k reads the 24 bytes at 9 off[i] + 3 m --
+// the lanes sweep the row front to back -- and adds w_i H into image[con_pos[k]][3 d + e] with one fma per entry.  A child
+// has every column once: no two lanes meet in one element within a child; between children a wave barrier with LDS
+// fences (the image is wave-private: no workgroup barrier).  Child order, the zero start, one fma per contribution and
+// the closing product are pmg_rop_build_h_kernel's, so R has the same bits.  The first kRopPre rounds of loads of the next
+// two children are in flight while the current child updates the image.  Rows longer than `cap` blocks are left alone: the
+// launcher sends them to the gather kernel.
+constexpr int kRopPre = 3;  // rounds of 64 lanes loaded ahead: a fine row of up to 64 blocks
+__global__ __launch_bounds__(256) void pmg_rop_stream_kernel(
+    int Nc, int cap, const int* __restrict__ r_off, const int* __restrict__ r_cols, const int* __restrict__ pos_off,
+    const unsigned short* __restrict__ con_pos, const int* __restrict__ ch_off, const int* __restrict__ ch,
+    const float* __restrict__ ch_w, const int* __restrict__ f_off, const double* __restrict__ Hval,
+    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8, float* __restrict__ R1) {
+  __shared__ double image[4][kRopStreamCap * 9];
+  __shared__ double tabw[4][kRopTab];
+  __shared__ int tabo[4][kRopTab][3];  // row start in H (blocks), row length, start in con_pos
+  const int lane = threadIdx.x & 63, rw = threadIdx.x >> 6;
+  const int I = blockIdx.x * 4 + rw;
+  if (I >= Nc) return;
+  const int r0 = r_off[I], len = r_off[I + 1] - r0;
+  if (len > cap || len > kRopStreamCap) return;
+  double* img = image[rw];
+  const int c0 = ch_off[I], nch = ch_off[I + 1] - c0;
+  for (int c = lane; c < min(nch, kRopTab); c += 64) {
+    const int i = ch[c0 + c];
+    tabw[rw][c] = (double)ch_w[c0 + c];
+    tabo[rw][c][0] = f_off[i];
+    tabo[rw][c][1] = f_off[i + 1] - f_off[i];
+    tabo[rw][c][2] = pos_off[c0 + c];
+  }
+  for (int t = lane; t < 9 * len; t += 64) img[t] = 0.0;
+  auto wave_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  wave_sync();
+  struct Child {
+    double w;
+    int o0, deg, pb;
+  };
+  auto child = [&](int c) {
+    Child k;
+    if (c < kRopTab) {
+      k.w = tabw[rw][c];
+      k.o0 = tabo[rw][c][0];
+      k.deg = tabo[rw][c][1];
+      k.pb = tabo[rw][c][2];
+    } else {
+      const int i = ch[c0 + c];
+      k.w = (double)ch_w[c0 + c];
+      k.o0 = f_off[i];
+      k.deg = f_off[i + 1] - k.o0;
+      k.pb = pos_off[c0 + c];
+    }
+    return k;
+  };
+  // entry m of a child: where it lands (element of the image) and its three values
+  auto target = [&](const Child& k, int m) {
+    const int d = (m >= k.deg ? 1 : 0) + (m >= 2 * k.deg ? 1 : 0);
+    return 9 * (int)con_pos[k.pb + (m - d * k.deg)] + 3 * d;
+  };
+  auto add3 = [&](int at, double w, const double h[3]) {
+#pragma unroll
+    for (int e = 0; e < 3; e++) img[at + e] = fma(w, h[e], img[at + e]);
+  };
+  // a ring of three register buffers: while child c updates the image, the loads of c + 1 and c + 2 are in flight
+  struct Ahead {
+    Child k;
+    double h[kRopPre][3];
+    int at[kRopPre];
+  };
+  auto load_ahead = [&](int c, Ahead& a) {
+#pragma unroll
+    for (int j = 0; j < kRopPre; j++) a.at[j] = -1;
+    if (c >= nch) return;
+    a.k = child(c);
+    const double* Hb = Hval + (size_t)9 * a.k.o0;
+#pragma unroll
+    for (int j = 0; j < kRopPre; j++) {
+      const int m = lane + 64 * j;
+      if (m < 3 * a.k.deg) {
+        a.at[j] = target(a.k, m);
+#pragma unroll
+        for (int e = 0; e < 3; e++) a.h[j][e] = Hb[3 * (size_t)m + e];
+      }
+    }
+  };
+  // child c from its buffer (the caller checks c < nch), after the loads of child c + 2 went out into the buffer `far`
+  auto take = [&](int c, const Ahead& a, Ahead& far) {
+    load_ahead(c + 2, far);
+#pragma unroll
+    for (int j = 0; j < kRopPre; j++)
+      if (a.at[j] >= 0) add3(a.at[j], a.k.w, a.h[j]);
+    const double* Hb = Hval + (size_t)9 * a.k.o0;
+    for (int m = lane + 64 * kRopPre; m < 3 * a.k.deg; m += 64) {  // a fine row beyond 64 blocks: the rest as it comes
+      const double h[3] = {Hb[3 * (size_t)m], Hb[3 * (size_t)m + 1], Hb[3 * (size_t)m + 2]};
+      add3(target(a.k, m), a.k.w, h);
+    }
+    wave_sync();
+  };
+  Ahead b0 = {}, b1 = {}, b2 = {};
+  load_ahead(0, b0);
+  load_ahead(1, b1);
+  for (int c = 0; c < nch; c += 3) {
+    take(c, b0, b2);
+    if (c + 1 < nch) take(c + 1, b1, b0);
+    if (c + 2 < nch) take(c + 2, b2, b1);
+  }
+  const double sI[3] = {sc_c[3 * I], sc_c[3 * I + 1], sc_c[3 * I + 2]};
+  for (int b = lane; b < len; b += 64) {
+    const int j = r_cols[r0 + b];
+    const double sj[3] = {sc_f[3 * j], sc_f[3 * j + 1], sc_f[3 * j + 2]};
+    const double* acc = img + 9 * b;
+    Blk8<float> out;
+#pragma unroll
+    for (int k = 0; k < 8; k++) out.v[k] = (float)(sI[k / 3] * acc[k] * sj[k % 3]);
+    R8[r0 + b] = out;
+    R1[r0 + b] = (float)(sI[2] * acc[8] * sj[2]);
+  }
+}
+// streamed build of the rows of at most `cap` blocks; the n_long rows beyond it (long_rows, ascending) by the gather kernel
+void launch_pmg_rop_stream(hipStream_t s, int Nc, int cap, const int* r_off, const int* r_cols, const int* pos_off,
+                           const unsigned short* con_pos, const int* con_off, const int* con_blk, const unsigned char* con_ord,
+                           const int* ch_off, const int* ch, const float* ch_w, const int* f_off, const double* Hval,
+                           const double* sc_f, const double* sc_c, void* R8, float* R1, const int* long_rows, int n_long) {
+  if (Nc <= 0) return;
+  hipLaunchKernelGGL(pmg_rop_stream_kernel, dim3((Nc + 3) / 4), dim3(256), 0, s, Nc, std::min(cap, kRopStreamCap), r_off, r_cols,
+                     pos_off, con_pos, ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, (Blk8<float>*)R8, R1);
+  if (n_long > 0)
+    launch_pmg_rop_build_h(s, Nc, r_off, r_cols, con_off, con_blk, con_ord, ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, R8, R1,
+                           long_rows, n_long);
 }
 void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
                           const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,

@@ -1370,6 +1370,11 @@ struct tlfea_newton_s {
   // low-precision scaled copy of H streamed by the Chebyshev steps (lin.cheb_bits 16/32): 8+1 entries per block
   void *d_B8 = nullptr, *d_B1 = nullptr;
   int lp_bits_alloc = 0;
+  // The copy belongs to the H, d_sc and d_D of ONE stage-0 set-up (precond_setup): lp_scaled = that stage ran the scaling,
+  // lp_current = the copy was converted from them since, lp_converts = fine-level conversions since creation.  A set-up
+  // that can still choose the matrix-free fine smoother defers the conversion (ensure_fine_copy, DESIGN 3g').
+  bool lp_scaled = false, lp_current = false;
+  int lp_converts = 0;
   double *d_sc = nullptr, *d_Dinv_s = nullptr;
   double *d_cz = nullptr, *d_cz2 = nullptr, *d_cres2 = nullptr;  // ping-pong partners of z / res in the LP steps
   // two-level p-multigrid preconditioner (T10, single GPU): see pmg_host.h / pmg_apply()
@@ -1404,6 +1409,10 @@ struct tlfea_newton_s {
       unsigned char* d_con_ord = nullptr;
       float *d_ch_w = nullptr, *d_R1 = nullptr;
       void* d_R8 = nullptr;
+      // the streamed build from H (pmg_rop_stream_kernel): positions by source, and the rows beyond its image
+      int *d_pos_off = nullptr, *d_long_rows = nullptr;
+      unsigned short* d_con_pos = nullptr;
+      int n_long = 0, stream_cap = 0;
     } rop;
     LevelIface iface() const { return LevelIface{n_ifc_loc, n_ifc_glob, d_ifc_node, d_ifc_slot, d_bslot_c}; }
     // third level: rigid-body-mode aggregates of the vertex level (pmg_host.h agg_build); lvl.N = 2 Na nodes
@@ -1695,7 +1704,7 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
     m.vertex.release();
     auto& ro = m.rop;
     void* rr[] = {ro.d_off, ro.d_cols, ro.d_ch_off, ro.d_ch, ro.d_con_off, ro.d_con_blk, ro.d_con_ord, ro.d_ch_w, ro.d_R1,
-                  ro.d_R8};
+                  ro.d_R8, ro.d_pos_off, ro.d_long_rows, ro.d_con_pos};
     for (void* q : rr)
       if (q) (void)hipFree(q);
     auto& g = m.agg;
@@ -3086,21 +3095,52 @@ static bool blk12_on(tlfea_newton_t s) {
 }
 static bool blk12_now(tlfea_newton_t s);
 
-// (re)build the low-precision copy from the current H and block diagonal (d_D, d_Dinv must be current)
-static int lp_build(tlfea_newton_t s) {
+// storage of the fine level's low-precision copy, (re)allocated where the width changes; a solver that never converts
+// never allocates it (0.75 GB at config C)
+static int lp_alloc(tlfea_newton_t s, int bits) {
+  if (s->lp_bits_alloc == bits && s->d_B8) return 0;
+  if (s->d_B8) (void)hipFree(s->d_B8);
+  if (s->d_B1) (void)hipFree(s->d_B1);
+  s->d_B8 = s->d_B1 = nullptr;
+  s->lp_bits_alloc = 0;
+  const size_t eb = std::max(1, bits / 8);
+  HIP_TRY(hipMalloc(&s->d_B8, (size_t)s->d->nnz_coef * 8 * eb));
+  HIP_TRY(hipMalloc(&s->d_B1, (size_t)s->d->nnz_coef * eb));
+  s->lp_bits_alloc = bits;
+  return 0;
+}
+// the conversion itself: the copy of the H on the device with the d_sc and d_D of the last stage-0 set-up
+static int lp_convert(tlfea_newton_t s) {
+  const int bits = fine_bits(s);
+  TRY(lp_alloc(s, bits));
+  const bool local = s->ar && s->d_own;  // rank-local preconditioner on the owned nodes
+  launch_lp_convert(s->stream, s->N, s->d->inc(), s->d_H, s->d_sc, local ? s->d_own : nullptr, s->d_D, s->d_B8, s->d_B1,
+                    bits);
+  HIP_TRY(hipGetLastError());
+  s->lp_current = true;
+  s->lp_converts++;
+  return 0;
+}
+// Whoever reads the stored copy calls this first: converts where the set-up deferred it and nothing has converted since.
+// No-op without a low-precision set-up on the device (nothing to convert from) and under the 12 x 12 form (never deferred).
+static int ensure_fine_copy(tlfea_newton_t s) {
+  if (s->lp_current || !s->lp_scaled || fine_bits(s) == 64) return 0;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail("the fine level's low-precision copy is stale inside a stream capture (a set-up must convert it before)");
+  return lp_convert(s);
+}
+
+// Block-Jacobi scaling of the fine level from the current block diagonal (d_D, d_Dinv must be current) and, unless
+// `defer`, the low-precision copy of the current H.  defer: this set-up can still choose the fine smoother from the element
+// records, which reads no copy; whoever does read it converts on demand (ensure_fine_copy).
+static int lp_build(tlfea_newton_t s, bool defer) {
   tlfea_t10_t d = s->d;
   const int bits = fine_bits(s);
+  s->lp_scaled = s->lp_current = false;
   if (bits == 64) return 0;
-  if (s->lp_bits_alloc != bits) {
-    if (s->d_B8) (void)hipFree(s->d_B8);
-    if (s->d_B1) (void)hipFree(s->d_B1);
-    s->d_B8 = s->d_B1 = nullptr;
-    const size_t eb = std::max(1, bits / 8);
-    HIP_TRY(hipMalloc(&s->d_B8, (size_t)d->nnz_coef * 8 * eb));
-    HIP_TRY(hipMalloc(&s->d_B1, (size_t)d->nnz_coef * eb));
-    s->lp_bits_alloc = bits;
-  }
   if (blk12_now(s)) {
+    TRY(lp_alloc(s, bits));
     if (!s->d_L12inv) {
       HIP_TRY(hipMalloc((void**)&s->d_L12inv, (size_t)36 * s->N * sizeof(double)));  // 144 per node of 4 coefficient vectors
       HIP_TRY(hipMalloc((void**)&s->d_L12inv_f, (size_t)36 * s->N * sizeof(float)));
@@ -3111,12 +3151,14 @@ static int lp_build(tlfea_newton_t s) {
     launch_lp_convert12(s->stream, s->N, d->inc(), s->d_H, s->d_L12inv, s->d_B8, s->d_B1, bits);
     launch_to_float(s->stream, (size_t)9 * s->N, s->d_Dinv_s, s->d_f32 + (size_t)18 * s->N);
     HIP_TRY(hipGetLastError());
+    s->lp_current = true;  // (lp_scaled stays false: the 3 x 3 conversion cannot rebuild this copy)
+    s->lp_converts++;
     return 0;
   }
   launch_lp_scale(s->stream, s->N, s->d_D, s->d_Dinv, s->d_sc, s->d_Dinv_s);
-  const bool local = s->ar && s->d_own;  // rank-local preconditioner on the owned nodes
-  launch_lp_convert(s->stream, s->N, d->inc(), s->d_H, s->d_sc, local ? s->d_own : nullptr, s->d_D, s->d_B8, s->d_B1,
-                    bits);
+  s->lp_scaled = true;
+  const bool local = s->ar && s->d_own;
+  if (!defer) TRY(lp_convert(s));
   if (local) launch_mask_scale(s->stream, s->N, s->d_sc, s->d_own, s->d_sc_mask);
   if (!s->ar || local || precond_eff(s) == 2)
     launch_to_float(s->stream, (size_t)9 * s->N, s->d_Dinv_s, s->d_f32 + (size_t)18 * s->N);
@@ -3232,6 +3274,7 @@ static int cheb_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* 
   const double* Dinv = lp ? s->d_Dinv_s : s->d_Dinv;
   const double* sc = lp ? s->d_sc : nullptr;
   const bool local = s->ar && s->d_own;
+  if (lp) TRY(ensure_fine_copy(s));  // every step below streams the stored copy
   if (lp && (!s->ar || local)) {
     // single GPU, or rank-local on the owned nodes: the whole polynomial in single precision (cheb32_kernel); d, z,
     // res ping-pong so that a row's stores never order against loads of other rows; the last step returns
@@ -3373,6 +3416,20 @@ static bool pmg_rop_on(tlfea_newton_t s) {
   return fb == 16 || fb == 32;
 }
 static bool pmg_rop_now(tlfea_newton_t s) { return pmg_rop_on(s) && s->pmg.rop.built; }
+// How R is built from H where the fine smoother is matrix-free (DESIGN 3g', 8b): TLFEA_ROP_BUILD=stream (default) reads each
+// child's row of H whole through an LDS image of the R row, gather walks the contribution lists.  TLFEA_ROP_STREAM_MAX
+// lowers the image's capacity in blocks (tests: rows on both kernels in one build).  Both read once per process.
+static bool rop_stream_env() {
+  static const bool on = [] {
+    const char* e = std::getenv("TLFEA_ROP_BUILD");
+    return !(e && std::strcmp(e, "gather") == 0);
+  }();
+  return on;
+}
+static int rop_stream_cap() {
+  static const int cap = std::max(1, std::min(kRopStreamCap, env_int("TLFEA_ROP_STREAM_MAX", kRopStreamCap)));
+  return cap;
+}
 
 // ---- fine smoother from the element records (DESIGN 3g') ----------------------------------------------------------------
 // TLFEA_PMG_FINE_MATFREE: 0 never, 1 wherever eligible, unset = eligible and at least kFineMatfreeMinRows node rows.  Read once.
@@ -3391,13 +3448,16 @@ static double fine_matfree_m0(tlfea_newton_t s) {  // the material scalars are d
   const MatfreeCoef& mc = s->mf.mc;
   return std::max(std::max(std::fabs(mc.a), std::fabs(mc.b)), std::max(std::fabs(mc.c1), std::fabs(mc.cl)));
 }
-static bool fine_matfree_chosen(tlfea_newton_t s) {
+// Everything of the choice that stage 0 of a set-up already knows: all but R having been built (pmg_prepare and
+// pmg_build_level run in stage 1).  Stage 0 defers the fine level's low-precision copy on it.
+static bool fine_matfree_possible(tlfea_newton_t s) {
   if (fine_matfree_env() == 0 || !matfree_eligible(s) || !matfree_compact_env()) return false;
-  if (cheb_degree_eff(s) <= 1 || precond_eff(s) != 2 || !pmg_rop_now(s) || pmg_smoother_kind() != 1) return false;
+  if (cheb_degree_eff(s) <= 1 || precond_eff(s) != 2 || !pmg_rop_possible(s) || pmg_smoother_kind() != 1) return false;
   if (!(fine_matfree_m0(s) > 0.0)) return false;
   if (s->ar || s->halo.on || s->lin.cheb_bits != 0 || fine_bits(s) != 16) return false;
   return fine_matfree_env() == 1 || s->N >= kFineMatfreeMinRows;
 }
+static bool fine_matfree_chosen(tlfea_newton_t s) { return fine_matfree_possible(s) && pmg_rop_now(s); }
 // The choice of a set-up is taken ONCE, by pmg_build_level before it builds R (rop.built already set), with the compact
 // lists in place; the build of R and fine_matfree_setup both follow fmf.now.
 static int fine_matfree_choose(tlfea_newton_t s) {
@@ -3556,6 +3616,15 @@ static int pmg_prepare(tlfea_newton_t s) {
       TRY(upload_vec(&r.d_ch_off, ro.ch_off)); TRY(upload_vec(&r.d_ch, ro.ch)); TRY(upload_vec(&r.d_ch_w, ro.ch_w));
       TRY(upload_vec(&r.d_con_off, ro.con_off)); TRY(upload_vec(&r.d_con_blk, ro.con_blk));
       TRY(upload_vec(&r.d_con_ord, ro.con_ord));
+      // the streamed build serves the matrix-free fine smoother only: its lists go up where a set-up can choose that form
+      r.stream_cap = 0;
+      if (rop_stream_env() && fine_matfree_env() != 0 && (fine_matfree_env() == 1 || s->N >= kFineMatfreeMinRows)) {
+        const std::vector<int> long_rows = pmg_rop_long_rows(ro, rop_stream_cap());
+        r.stream_cap = rop_stream_cap();
+        r.n_long = (int)long_rows.size();
+        TRY(upload_vec(&r.d_pos_off, ro.pos_off)); TRY(upload_vec(&r.d_con_pos, ro.con_pos));
+        TRY(upload_vec(&r.d_long_rows, long_rows));
+      }
       HIP_TRY(hipMalloc(&r.d_R8, ((size_t)r.nnz + 1) * 8 * sizeof(float)));
       TRY(dmalloc(&r.d_R1, (size_t)r.nnz + 1));
       r.ok = true;
@@ -3816,12 +3885,17 @@ static int pmg_build_level(tlfea_newton_t s) {
   TRY(halo_refresh_f64(s, 1, s->halo.depth, 9, V.d_D));
   level_scale_convert(s, V, bits);
   m.rop.built = false;
-  if (pmg_rop_on(s)) {  // R = S_c P^T S_f^-1 Hs from the fine copy as stored (lp_build ran before) and both scalings
+  if (pmg_rop_on(s)) {  // R = S_c P^T S_f^-1 Hs from the fine copy as stored (converted before it is read) and both scalings
     auto& r = m.rop;
     r.built = true;
     // the fine smoother will apply H itself (DESIGN 3g'): R from H's fp64 rows, so that both see one operator
     TRY(fine_matfree_choose(s));
-    if (s->fmf.now)
+    if (!s->fmf.now) TRY(ensure_fine_copy(s));  // a set-up that deferred the copy and does not take the form after all
+    if (s->fmf.now && r.stream_cap > 0)
+      launch_pmg_rop_stream(s->stream, V.N, r.stream_cap, r.d_off, r.d_cols, r.d_pos_off, r.d_con_pos, r.d_con_off, r.d_con_blk,
+                            r.d_con_ord, r.d_ch_off, r.d_ch, r.d_ch_w, s->d->d_off, s->d_H, s->d_sc, V.d_sc, r.d_R8, r.d_R1,
+                            r.d_long_rows, r.n_long);
+    else if (s->fmf.now)
       launch_pmg_rop_build_h(s->stream, V.N, r.d_off, r.d_cols, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch,
                              r.d_ch_w, s->d->d_off, s->d_H, s->d_sc, V.d_sc, r.d_R8, r.d_R1);
     else
@@ -3917,6 +3991,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
   const int ks = t.ks;
   const double* cf = m.d_coef;
   const double* cc = cf + t.coarse();  // the vertex level's pairs
+  if (!s->fmf.now) TRY(ensure_fine_copy(s));  // the fine passes stream the stored copy (before fine_c32 takes its pointers)
   const C32Level Lf = fine_c32(s), Lc = V.c32(bits, 1);
   C32Vecs f(s->d_f32, 3 * (size_t)N), c(V.d_f32, 3 * (size_t)Nc);
   if (s->ar) {
@@ -4212,7 +4287,9 @@ static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg,
                        bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0) + (s->mf.now && s->mf.compact ? 800000L : 0) +
                            (pmg_rop_now(s) ? 400000L : 0) + (fine_matfree_live(s) ? 1600000L : 0),
                        (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
-                       (long)(size_t)s->d_B8 ^ fine_matfree_key(s), (long)(size_t)s->pmg.vertex.d_B8};
+                       // the graphs of the matrix-free fine smoother read no fine copy: one built on demand between two
+                       // solves (a read-back, a timing run) must not force a re-capture
+                       (s->fmf.now ? 0L : (long)(size_t)s->d_B8) ^ fine_matfree_key(s), (long)(size_t)s->pmg.vertex.d_B8};
   if (s->cg_graph[0] && std::equal(key, key + 6, s->cg_graph_key)) return 0;
   cg_graphs_destroy(s);
   for (int k = 0; k < (s->spmv32_now ? 3 : 2); k++) {
@@ -4514,6 +4591,7 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
   const int N = s->N;
   if (stage == 0) {
     const bool lp = cheb_bits_eff(s) != 64;
+    s->lp_scaled = s->lp_current = false;  // the stored copy belonged to the last set-up's H
     if (s->ar || lp) {
       // diagonal blocks of partition-boundary nodes are partial per rank: sum them before inverting
       launch_extract_diag(s->stream, N, d->inc(), s->d_H, s->d_D);
@@ -4522,7 +4600,10 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
       // columns in every complete row) come from their owners
       TRY(halo_refresh_f64(s, 0, s->halo.depth, 9, s->d_D));
       launch_invert_diag(s->stream, N, s->d_D, s->d_Dinv);
-      if (lp) TRY(lp_build(s));
+      // The copy waits where stage 1 can still choose the fine smoother from the element records (only R having been
+      // built is open); every other configuration converts here, in the launch order it always had.  The mixed-precision
+      // iteration, which pcg() switches on after this stage, rules the form out.
+      if (lp) TRY(lp_build(s, fine_matfree_possible(s) && s->spmv32_every < 2));
     } else {
       launch_extract_dinv(s->stream, N, d->inc(), s->d_H, s->d_Dinv);
     }
@@ -4542,6 +4623,8 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
       }
     }
   }
+  // a deferred copy whose set-up never reached the choice (no hierarchy for this mesh, no R): everything but the form reads it
+  if (!s->fmf.now) TRY(ensure_fine_copy(s));
   return 0;
 }
 
@@ -4935,10 +5018,20 @@ extern "C" int tlfea_newton_pmg_restrict_op_retrieve(tlfea_newton_t s, int* off,
   D2H(cols, m.rop.d_cols, (size_t)m.rop.nnz);
   return widen_to_host(s, (size_t)m.rop.nnz, m.rop.d_R8, m.rop.d_R1, 32, vals);
 }
+// Test hook: [0] bits of the fine copy allocated (0: none), [1] the copy is that of the last set-up's H, [2] fine-level
+// conversions since creation
+extern "C" int tlfea_newton_get_fine_copy_state(tlfea_newton_t s, int* out3) {
+  if (!s || !out3) return fail("tlfea_newton_get_fine_copy_state: null argument");
+  out3[0] = s->d_B8 ? s->lp_bits_alloc : 0;
+  out3[1] = s->d_B8 && s->lp_current ? 1 : 0;
+  out3[2] = s->lp_converts;
+  return 0;
+}
 extern "C" int tlfea_newton_pmg_fine_copy_retrieve(tlfea_newton_t s, int* off, int* cols, double* vals, double* sc_f,
                                                    double* sc_c) {
   if (!s || !off || !cols || !vals || !sc_f || !sc_c) return fail("tlfea_newton_pmg_fine_copy_retrieve: null argument");
   const auto& m = s->pmg;
+  TRY(ensure_fine_copy(s));  // a set-up that chose the matrix-free fine smoother left it unconverted
   const int bits = s->d_B8 ? s->lp_bits_alloc : 0;
   if (!m.ok || !m.vertex.d_sc || !s->d_sc || (bits != 16 && bits != 32))
     return fail("tlfea_newton_pmg_fine_copy_retrieve: no p-multigrid set-up with a 16- or 32-bit fine copy on the device");
@@ -5083,6 +5176,8 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
   const int N = s->N;
   const bool fused = s->pcg_fused < 0 ? (N <= 200000) : (s->pcg_fused != 0);
   out_ms4[5] = out_ms4[6] = 0.0;
+  // cheb_step and the cycle pattern price the stream of the stored copy, whichever form the last set-up's smoother took
+  TRY(ensure_fine_copy(s));
   // geo -1: a measurement is no solve, the geometry read-back keeps the solver's last launch
   C32Level Lf = fine_c32(s);
   Lf.geo = -1;

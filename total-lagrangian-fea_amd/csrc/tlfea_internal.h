@@ -347,7 +347,15 @@ void launch_pmg_prolong(hipStream_t s, int N, const int* par0, const int* par1, 
 // per solve), and the restriction  r^_c = S_c P^T S_f^-1 res_f - R d_f  fused with the coarse start vectors
 void launch_pmg_rop_build_h(hipStream_t s, int Nc, const int* r_off, const int* r_cols, const int* con_off, const int* con_blk,
                             const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const int* f_off,
-                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1);
+                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1,
+                            const int* rows = nullptr, int n_rows = 0);
+// the same R, each child's row of H streamed through an LDS image of the R row (rows of at most cap <= kRopStreamCap blocks;
+// the n_long longer ones, listed ascending in long_rows, go to the gather kernel in a second launch)
+constexpr int kRopStreamCap = 128;  // blocks of the image: 9 KB per wavefront, 12 wavefronts per CU
+void launch_pmg_rop_stream(hipStream_t s, int Nc, int cap, const int* r_off, const int* r_cols, const int* pos_off,
+                           const unsigned short* con_pos, const int* con_off, const int* con_blk, const unsigned char* con_ord,
+                           const int* ch_off, const int* ch, const float* ch_w, const int* f_off, const double* Hval,
+                           const double* sc_f, const double* sc_c, void* R8, float* R1, const int* long_rows, int n_long);
 void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
                           const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,
                           const void* B1, int bits, const double* sc_f, const double* sc_c, void* R8, float* R1);

@@ -412,6 +412,14 @@ class SyncedNewtonSolver:
         element records (DESIGN 3g')"""
         return int(self._lib.tlfea_newton_get_fine_smoother(self._h))
 
+    def GetFineCopyState(self):
+        """(bits, current, conversions) of the fine level's low-precision copy: bits allocated (0: none), whether it is that
+        of the last set-up's H, fine-level conversions since creation.  A set-up that takes the fine smoother from the
+        element records converts nothing; read-backs and timings convert on demand (test hook)"""
+        out = (C.c_int * 3)()
+        check(self._lib.tlfea_newton_get_fine_copy_state(self._h, out))
+        return tuple(int(v) for v in out)
+
     def FineSmootherPass(self, d, res, z, r, coef, zw=0.0, last=False):
         """one fine smoother pass from the element records with the set-up the last ApplyPreconditioner left (test hook):
         (d', z^', res^') as float32, or with last (d', z = S z^' in float64, the 512 r.z slots)"""
