@@ -389,6 +389,11 @@ int tlfea_newton_pmg_coarse_degree(tlfea_newton_t s);
  * (9 nnz values in the DOF-level layout of H: node row -> [d][k][e]) */
 int tlfea_newton_pmg_sizes(tlfea_newton_t s, int *n_coarse, int *nnz_coarse_blocks);
 int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int *par0, int *par1, int *c_off, int *c_cols, double *Hc);
+/* Hc as the last preconditioner set-up (a solve or tlfea_newton_apply_preconditioner) left it on the device, nothing is
+ * recomputed: the 9 nnz values, and in *form the kernel that summed them -- 1 the gather over the contribution lists
+ * (ANCF), 2 the row kernel alone, 3 the row kernel fused with the streamed build of R.  Fails before the first set-up and
+ * after tlfea_newton_pmg_retrieve / tlfea_newton_pmg3_retrieve, which sum Hc again, until the next set-up. */
+int tlfea_newton_pmg_retrieve_built(tlfea_newton_t s, double *Hc, int *form);
 /* Test hooks of the restricted fine operator R = S_c P^T S_f^-1 Hs, through which the V-cycle restricts the fine residual
  * (one GPU, first-kind smoother, 16- or 32-bit fine copy; TLFEA_PMG_RESTRICT_OP=0 keeps the fine residual pass).  They
  * copy back what the LAST preconditioner set-up (a solve or tlfea_newton_apply_preconditioner) left on the device and

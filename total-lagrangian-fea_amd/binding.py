@@ -216,6 +216,9 @@ def _pmg_signatures(lib):
         lib.tlfea_newton_fine_smoother_pass.argtypes = [vp, c_fp, c_fp, c_fp, c_dp, c_dp, C.c_double, C.c_int, c_fp, c_fp, c_fp,
                                                         c_dp, c_dp]
         lib.tlfea_newton_fine_smoother_pass.restype = C.c_int
+    if hasattr(lib, "tlfea_newton_pmg_retrieve_built"):
+        lib.tlfea_newton_pmg_retrieve_built.argtypes = [vp, c_dp, c_ip]
+        lib.tlfea_newton_pmg_retrieve_built.restype = C.c_int
     if hasattr(lib, "tlfea_newton_get_fine_copy_state"):
         lib.tlfea_newton_get_fine_copy_state.argtypes = [vp, c_ip]
         lib.tlfea_newton_get_fine_copy_state.restype = C.c_int

@@ -284,15 +284,18 @@ struct RopHost {
   std::vector<int> con_off;         // [nnz+1] contributions to each R block
   std::vector<int> con_blk;         // fine block index off[i] + k
   std::vector<unsigned char> con_ord;  // position of the child i in ch[ch_off[I] ..]
-  // The same contributions by SOURCE, for the build that streams each child's row of H in order (pmg_rop_stream_kernel):
+  // The same contributions by SOURCE, for the kernels that stream each child's row of H in order into an image of the R
+  // row (pmg_galerkin_rows_kernel, pmg_galerkin_long_rows_kernel):
   // con_pos[pos_off[t] + k] = position in R row I of the column of block k of child ch[t]'s fine row -- layout
-  // [I][child][k], pos_off one prefix entry per child (a row's own offset is pos_off[ch_off[I]]).  16 bits: only rows of at
-  // most 128 blocks take that build (pmg_rop_long_rows lists the others), a longer row's entries saturate and are never read.
+  // [I][child][k], pos_off one prefix entry per child (a row's own offset is pos_off[ch_off[I]]).  16 bits: every row of up
+  // to 65 535 blocks is read through them, the short ones (pmg_rop_long_rows lists the others) with the image in LDS, the
+  // long ones with it in global memory; beyond that the entries saturate, pmg_galerkin_rows_build refuses the mesh and
+  // nothing reads them.
   std::vector<int> pos_off;              // [children + 1]
   std::vector<unsigned short> con_pos;   // [n_con]
 };
 
-// Rows of R longer than `cap` blocks, ascending: the streamed build leaves them to the gather kernel.
+// Rows of R longer than `cap` blocks, ascending: their image does not fit LDS, a second launch keeps it in global memory.
 inline std::vector<int> pmg_rop_long_rows(const RopHost& o, int cap) {
   std::vector<int> rows;
   for (int I = 0; I < o.Nc; I++)
@@ -396,6 +399,77 @@ inline bool pmg_restrict_op_build(int N, const int* off, const int* cols, const 
         }
       }
     }
+  }
+  return true;
+}
+
+// ---- Hc = P^T H P from the row image of R (DESIGN 3g') ------------------------------------------------------------------
+// The streamed build of R row I ends with the unscaled row T[I, :] = (P^T H)[I, :] in its image, one 3x3 block per column of
+// the R row.  Row I of the Galerkin operator is that image times P on the right:  Hc[I, J] = sum_j T[I, j] P[j, J], one term
+// per fine column j that has J among its parents, weight 1 (j is the vertex J) or 1/2 (a mid-edge node of J).  Here the
+// lists of that combine, for the blocks with J >= I only (the kernel mirrors the rest, as the gather does):
+//   row_off  [Nc + 1]      the upper blocks of row I are c_upper[row_off[I] .. row_off[I + 1]), the diagonal block first
+//   term_off [n_upper + 1] terms of every upper block, in the order of c_upper
+//   term_pos / term_w      per term the position in the R row of I (ascending within a block) and the weight bit
+//                          (1: weight 1, 0: weight 1/2)
+struct GalRowsHost {
+  std::vector<int> row_off, term_off;
+  std::vector<unsigned short> term_pos;
+  std::vector<unsigned char> term_w;
+};
+
+// False when a row of R has more positions than the 16-bit lists address (RopHost::con_pos saturates there): the mesh
+// then keeps the gather over the contribution lists of PmgHost.
+inline bool pmg_galerkin_rows_build(const PmgHost& h, const RopHost& r, GalRowsHost& g) {
+  g = GalRowsHost();
+  const int Nc = h.Nc, n_upper = (int)h.c_upper.size();
+  if (r.Nc != Nc) return false;
+  g.row_off.assign((size_t)Nc + 1, 0);
+  for (int I = 0; I < Nc; I++) {
+    if (r.off[I + 1] - r.off[I] > 65535) return false;
+    g.row_off[I + 1] = g.row_off[I] + (h.c_off[I + 1] - h.c_off[I] - h.c_diagpos[I]);
+  }
+  if (g.row_off[Nc] != n_upper) return false;
+  // upper block of (I, J), J >= I a coarse neighbour of I; -1 when the pattern lacks it
+  auto upper_of = [&](int I, int J) {
+    const int* row = h.c_cols.data() + h.c_off[I];
+    const int deg = h.c_off[I + 1] - h.c_off[I];
+    const int* p = std::lower_bound(row, row + deg, J);
+    if (p == row + deg || *p != J) return -1;
+    return g.row_off[I] + ((int)(p - row) - h.c_diagpos[I]);
+  };
+  g.term_off.assign((size_t)n_upper + 1, 0);
+  int bad = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    std::vector<int> cur;
+    if (pass) {
+      for (int u = 0; u < n_upper; u++) g.term_off[u + 1] += g.term_off[u];
+      g.term_pos.assign((size_t)g.term_off[n_upper], 0);
+      g.term_w.assign((size_t)g.term_off[n_upper], 0);
+      cur.assign(g.term_off.begin(), g.term_off.end() - 1);
+    }
+#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : bad)
+    for (int I = 0; I < Nc; I++) {  // the blocks of a row are a range of their own in every list: no race
+      const int r0 = r.off[I], len = r.off[I + 1] - r0;
+      for (int b = 0; b < len; b++) {  // ascending position: every block's list ascends
+        const int j = r.cols[r0 + b];
+        const int pj[2] = {h.par0[j], h.par1[j]};
+        const int npj = pj[0] == pj[1] ? 1 : 2;
+        for (int a = 0; a < npj; a++) {
+          if (pj[a] < I) continue;
+          const int u = upper_of(I, pj[a]);
+          if (u < 0) {
+            bad++;
+          } else if (!pass) {
+            g.term_off[(size_t)u + 1]++;
+          } else {
+            g.term_pos[cur[u]] = (unsigned short)b;
+            g.term_w[cur[u]++] = npj == 1 ? 1 : 0;
+          }
+        }
+      }
+    }
+    if (bad) return false;
   }
   return true;
 }

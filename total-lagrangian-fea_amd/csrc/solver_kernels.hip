@@ -558,6 +558,10 @@ struct alignas(8 * sizeof(HT)) Blk8 {
   HT v[8];
 };
 
+// the scaling of a DOF from its diagonal entry: the one expression of lp_scale_kernel and of the kernel that scales R's
+// rows from the diagonal block it has just summed (pmg_galerkin_rows)
+__device__ __forceinline__ double lp_scale_of(double dd) { return dd > 0.0 ? 1.0 / sqrt(dd) : 1.0; }
+
 // sc = diag(D)^-1/2 per DOF;  Dinv_s = (S D S)^-1 = Dinv / (sc sc^T)
 __global__ void lp_scale_kernel(int N, const double* __restrict__ D, const double* __restrict__ Dinv,
                                 double* __restrict__ sc, double* __restrict__ Dinv_s) {
@@ -566,8 +570,7 @@ __global__ void lp_scale_kernel(int N, const double* __restrict__ D, const doubl
   double s[3];
 #pragma unroll
   for (int c = 0; c < 3; c++) {
-    const double dd = D[(size_t)9 * i + 4 * c];
-    s[c] = dd > 0.0 ? 1.0 / sqrt(dd) : 1.0;
+    s[c] = lp_scale_of(D[(size_t)9 * i + 4 * c]);
     sc[3 * i + c] = s[c];
   }
 #pragma unroll
@@ -1697,14 +1700,12 @@ __global__ __launch_bounds__(256) void pmg_rop_build_h_kernel(
     int Nc, const int* __restrict__ r_off, const int* __restrict__ r_cols, const int* __restrict__ con_off,
     const int* __restrict__ con_blk, const unsigned char* __restrict__ con_ord, const int* __restrict__ ch_off,
     const int* __restrict__ ch, const float* __restrict__ ch_w, const int* __restrict__ f_off, const double* __restrict__ Hval,
-    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8, float* __restrict__ R1,
-    const int* __restrict__ rows) {
+    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8, float* __restrict__ R1) {
   __shared__ double tabw[8][kRopTab];
   __shared__ int tabo[8][kRopTab][2];
   const int lane = threadIdx.x & 31, rw = threadIdx.x >> 5;
-  const int slot = blockIdx.x * 8 + rw;  // rows: the Nc rows of this launch (the streamed build's long rows), null = all
-  if (slot >= Nc) return;
-  const int I = rows ? rows[slot] : slot;
+  const int I = blockIdx.x * 8 + rw;
+  if (I >= Nc) return;
   const double sI[3] = {sc_c[3 * I], sc_c[3 * I + 1], sc_c[3 * I + 2]};
   const int c0 = ch_off[I], b1 = r_off[I + 1];
   const int n_tab = min(ch_off[I + 1] - c0, kRopTab);
@@ -1751,15 +1752,12 @@ __global__ __launch_bounds__(256) void pmg_rop_build_h_kernel(
     R1[b] = (float)(sI[2] * acc[8] * sj[2]);
   }
 }
-// rows / n_rows: only these rows (n_rows of them), null = all Nc
 void launch_pmg_rop_build_h(hipStream_t s, int Nc, const int* r_off, const int* r_cols, const int* con_off, const int* con_blk,
                             const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const int* f_off,
-                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1, const int* rows,
-                            int n_rows) {
-  const int n = rows ? n_rows : Nc;
-  if (n <= 0) return;
-  hipLaunchKernelGGL(pmg_rop_build_h_kernel, dim3((n + 7) / 8), dim3(256), 0, s, n, r_off, r_cols, con_off, con_blk, con_ord,
-                     ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, (Blk8<float>*)R8, R1, rows);
+                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1) {
+  if (Nc <= 0) return;
+  hipLaunchKernelGGL(pmg_rop_build_h_kernel, dim3((Nc + 7) / 8), dim3(256), 0, s, Nc, r_off, r_cols, con_off, con_blk, con_ord,
+                     ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, (Blk8<float>*)R8, R1);
 }
 
 // The same R with the fine rows read whole and in order (DESIGN 3g').  One wavefront per coarse row keeps an image
@@ -1769,30 +1767,33 @@ void launch_pmg_rop_build_h(hipStream_t s, int Nc, const int* r_off, const int* 
 // has every column once: no two lanes meet in one element within a child; between children a wave barrier with LDS
 // fences (the image is wave-private: no workgroup barrier).  Child order, the zero start, one fma per contribution and
 // the closing product are pmg_rop_build_h_kernel's, so R has the same bits.  The first kRopPre rounds of loads of the next
-// two children are in flight while the current child updates the image.  Rows longer than `cap` blocks are left alone: the
-// launcher sends them to the gather kernel.
+// two children are in flight while the current child updates the image.
+//
+// The complete image is the unscaled row T[I, :] = (P^T H)[I, :], and row I of the Galerkin operator is that image times P
+// on the right (pmg_host.h GalRowsHost).  So the same wavefront sums the row's blocks of Hc = P^T H P with J >= I from the
+// image: lane <-> (block, entry) pairs in turn, every entry one chain acc = fma(w, T[I, b], acc) from zero over the block's
+// terms in ascending position b -- whichever lane runs a chain, its result is the same -- stored at its place and, for an
+// off-diagonal block, transposed at c_mirror (the lower triangle is never summed).  This is THE arithmetic of the T10
+// vertex level's Hc, in every mode: fused with the build of R (kR) where that build streams H, alone (no R) everywhere
+// else, the image in LDS or, for the rows beyond its capacity, in a slice of global memory -- the same statements through
+// a pointer into another memory, hence the same bits.  With kR the closing product's row scaling sc_c[I] is formed in the
+// wave from the diagonal block just summed (lp_scale_of, as lp_scale_kernel forms V.d_sc from the same entries later).
 constexpr int kRopPre = 3;  // rounds of 64 lanes loaded ahead: a fine row of up to 64 blocks
-__global__ __launch_bounds__(256) void pmg_rop_stream_kernel(
-    int Nc, int cap, const int* __restrict__ r_off, const int* __restrict__ r_cols, const int* __restrict__ pos_off,
-    const unsigned short* __restrict__ con_pos, const int* __restrict__ ch_off, const int* __restrict__ ch,
-    const float* __restrict__ ch_w, const int* __restrict__ f_off, const double* __restrict__ Hval,
-    const double* __restrict__ sc_f, const double* __restrict__ sc_c, Blk8<float>* __restrict__ R8, float* __restrict__ R1) {
-  __shared__ double image[4][kRopStreamCap * 9];
-  __shared__ double tabw[4][kRopTab];
-  __shared__ int tabo[4][kRopTab][3];  // row start in H (blocks), row length, start in con_pos
-  const int lane = threadIdx.x & 63, rw = threadIdx.x >> 6;
-  const int I = blockIdx.x * 4 + rw;
-  if (I >= Nc) return;
+// tabw / tabo: this wavefront's tables in LDS, kRopTab children: weight; row start in H (blocks), row length, start in con_pos
+template <bool kR>
+__device__ __forceinline__ void pmg_galerkin_row(int I, int lane, double* img, double* tabw, int (*tabo)[3], const PmgRows& a) {
+  const int *r_off = a.r_off, *r_cols = a.r_cols, *pos_off = a.pos_off, *ch_off = a.ch_off, *ch = a.ch, *f_off = a.f_off;
+  const unsigned short* con_pos = a.con_pos;
+  const float* ch_w = a.ch_w;
+  const double* Hval = a.Hval;
   const int r0 = r_off[I], len = r_off[I + 1] - r0;
-  if (len > cap || len > kRopStreamCap) return;
-  double* img = image[rw];
   const int c0 = ch_off[I], nch = ch_off[I + 1] - c0;
   for (int c = lane; c < min(nch, kRopTab); c += 64) {
     const int i = ch[c0 + c];
-    tabw[rw][c] = (double)ch_w[c0 + c];
-    tabo[rw][c][0] = f_off[i];
-    tabo[rw][c][1] = f_off[i + 1] - f_off[i];
-    tabo[rw][c][2] = pos_off[c0 + c];
+    tabw[c] = (double)ch_w[c0 + c];
+    tabo[c][0] = f_off[i];
+    tabo[c][1] = f_off[i + 1] - f_off[i];
+    tabo[c][2] = pos_off[c0 + c];
   }
   for (int t = lane; t < 9 * len; t += 64) img[t] = 0.0;
   auto wave_sync = [] {
@@ -1808,10 +1809,10 @@ __global__ __launch_bounds__(256) void pmg_rop_stream_kernel(
   auto child = [&](int c) {
     Child k;
     if (c < kRopTab) {
-      k.w = tabw[rw][c];
-      k.o0 = tabo[rw][c][0];
-      k.deg = tabo[rw][c][1];
-      k.pb = tabo[rw][c][2];
+      k.w = tabw[c];
+      k.o0 = tabo[c][0];
+      k.deg = tabo[c][1];
+      k.pb = tabo[c][2];
     } else {
       const int i = ch[c0 + c];
       k.w = (double)ch_w[c0 + c];
@@ -1873,7 +1874,36 @@ __global__ __launch_bounds__(256) void pmg_rop_stream_kernel(
     if (c + 1 < nch) take(c + 1, b1, b0);
     if (c + 2 < nch) take(c + 2, b2, b1);
   }
-  const double sI[3] = {sc_c[3 * I], sc_c[3 * I + 1], sc_c[3 * I + 2]};
+  // The image is complete and the last child's wave_sync has made it visible to every lane.  The combine: item = 9 block
+  // + entry over the row's upper blocks, 64 items a round; the diagonal block is the row's first (items 0..8).
+  const int u0 = a.g_row[I], n_item = 9 * (a.g_row[I + 1] - u0);
+  const int oc = a.c_off[I], degc = a.c_off[I + 1] - oc;
+  double sI[3] = {1.0, 1.0, 1.0};
+  for (int it0 = 0; it0 < n_item; it0 += 64) {
+    const int item = it0 + lane;
+    double acc = 0.0;
+    if (item < n_item) {
+      const int ub = item / 9, k = item - 9 * ub, u = u0 + ub;
+      const int t1 = a.g_off[u + 1];
+      for (int t = a.g_off[u]; t < t1; t++) acc = fma(a.g_w[t] ? 1.0 : 0.5, img[9 * (int)a.g_pos[t] + k], acc);
+      const int dd = k / 3, ee = k - 3 * dd;
+      const int cb = a.c_upper[u], cm = a.c_mirror[cb];
+      a.Hc[(size_t)9 * oc + (size_t)dd * 3 * degc + 3 * (cb - oc) + ee] = acc;
+      if (cm != cb) {
+        const int J = a.cblk_row[cm], om = a.c_off[J], degm = a.c_off[J + 1] - om;
+        a.Hc[(size_t)9 * om + (size_t)ee * 3 * degm + 3 * (cm - om) + dd] = acc;
+      } else if (a.D) {
+        a.D[(size_t)9 * I + k] = acc;
+      }
+    }
+    if (kR && it0 == 0) {  // every lane of the wave is here: entries (c, c) of the diagonal block sit in lanes 0, 4, 8
+#pragma unroll
+      for (int c = 0; c < 3; c++) sI[c] = lp_scale_of(__shfl(acc, 4 * c));
+    }
+  }
+  if (!kR) return;
+  const double* sc_f = a.sc_f;
+  Blk8<float>* R8 = (Blk8<float>*)a.R8;
   for (int b = lane; b < len; b += 64) {
     const int j = r_cols[r0 + b];
     const double sj[3] = {sc_f[3 * j], sc_f[3 * j + 1], sc_f[3 * j + 2]};
@@ -1882,20 +1912,51 @@ __global__ __launch_bounds__(256) void pmg_rop_stream_kernel(
 #pragma unroll
     for (int k = 0; k < 8; k++) out.v[k] = (float)(sI[k / 3] * acc[k] * sj[k % 3]);
     R8[r0 + b] = out;
-    R1[r0 + b] = (float)(sI[2] * acc[8] * sj[2]);
+    a.R1[r0 + b] = (float)(sI[2] * acc[8] * sj[2]);
   }
 }
-// streamed build of the rows of at most `cap` blocks; the n_long rows beyond it (long_rows, ascending) by the gather kernel
-void launch_pmg_rop_stream(hipStream_t s, int Nc, int cap, const int* r_off, const int* r_cols, const int* pos_off,
-                           const unsigned short* con_pos, const int* con_off, const int* con_blk, const unsigned char* con_ord,
-                           const int* ch_off, const int* ch, const float* ch_w, const int* f_off, const double* Hval,
-                           const double* sc_f, const double* sc_c, void* R8, float* R1, const int* long_rows, int n_long) {
+// the rows of at most `cap` blocks, a wavefront each, the image in LDS (12 wavefronts per CU)
+template <bool kR>
+__global__ __launch_bounds__(256) void pmg_galerkin_rows_kernel(int Nc, int cap, PmgRows a) {
+  __shared__ double image[4][kRopStreamCap * 9];
+  __shared__ double tabw[4][kRopTab];
+  __shared__ int tabo[4][kRopTab][3];
+  const int lane = threadIdx.x & 63, rw = threadIdx.x >> 6;
+  const int I = blockIdx.x * 4 + rw;
+  if (I >= Nc) return;
+  if (a.r_off[I + 1] - a.r_off[I] > cap) return;
+  pmg_galerkin_row<kR>(I, lane, image[rw], tabw[rw], tabo[rw], a);
+}
+// the rows beyond it (rows[0 .. n_rows)), a wavefront each, the image in slice `slot` of ws (stride doubles, at least nine
+// times the longest of these rows)
+template <bool kR>
+__global__ __launch_bounds__(256) void pmg_galerkin_long_rows_kernel(int n_rows, const int* __restrict__ rows, size_t stride,
+                                                                    double* __restrict__ ws, PmgRows a) {
+  __shared__ double tabw[4][kRopTab];
+  __shared__ int tabo[4][kRopTab][3];
+  const int lane = threadIdx.x & 63, rw = threadIdx.x >> 6;
+  const int slot = blockIdx.x * 4 + rw;
+  if (slot >= n_rows) return;
+  pmg_galerkin_row<kR>(rows[slot], lane, ws + stride * (size_t)slot, tabw[rw], tabo[rw], a);
+}
+// Hc (and D, and with_R the rows of R) of all Nc rows: one launch over the rows of at most `cap` blocks, then the n_long
+// longer ones (long_rows, ascending) ws_rows at a time through the workspace
+void launch_pmg_galerkin_rows(hipStream_t s, int Nc, int cap, const PmgRows& a, bool with_R, const int* long_rows, int n_long,
+                              size_t ws_stride, int ws_rows, double* ws) {
   if (Nc <= 0) return;
-  hipLaunchKernelGGL(pmg_rop_stream_kernel, dim3((Nc + 3) / 4), dim3(256), 0, s, Nc, std::min(cap, kRopStreamCap), r_off, r_cols,
-                     pos_off, con_pos, ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, (Blk8<float>*)R8, R1);
-  if (n_long > 0)
-    launch_pmg_rop_build_h(s, Nc, r_off, r_cols, con_off, con_blk, con_ord, ch_off, ch, ch_w, f_off, Hval, sc_f, sc_c, R8, R1,
-                           long_rows, n_long);
+  cap = std::min(cap, kRopStreamCap);
+  const dim3 g((Nc + 3) / 4), b(256);
+  if (with_R)
+    hipLaunchKernelGGL(pmg_galerkin_rows_kernel<true>, g, b, 0, s, Nc, cap, a);
+  else
+    hipLaunchKernelGGL(pmg_galerkin_rows_kernel<false>, g, b, 0, s, Nc, cap, a);
+  for (int k = 0; k < n_long && ws_rows > 0; k += ws_rows) {  // in stream order: a batch reuses the slices of the one before
+    const int n = std::min(ws_rows, n_long - k);
+    if (with_R)
+      hipLaunchKernelGGL(pmg_galerkin_long_rows_kernel<true>, dim3((n + 3) / 4), b, 0, s, n, long_rows + k, ws_stride, ws, a);
+    else
+      hipLaunchKernelGGL(pmg_galerkin_long_rows_kernel<false>, dim3((n + 3) / 4), b, 0, s, n, long_rows + k, ws_stride, ws, a);
+  }
 }
 void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
                           const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,

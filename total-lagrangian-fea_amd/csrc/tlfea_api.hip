@@ -1386,6 +1386,21 @@ struct tlfea_newton_s {
     int n_upper = 0;  // Galerkin gather: blocks with column >= row (d_c_upper), the rest mirrored through d_c_mirror
     int *d_c_upper = nullptr, *d_c_mirror = nullptr;
     float *d_child_w = nullptr, *d_con_w = nullptr;
+    // T10: Hc from an image of the R row (pmg_host.h GalRowsHost, pmg_galerkin_rows_kernel) -- the ONE arithmetic of every
+    // conforming T10 set-up whose lists fit; the gather lists above are then not on the device.  The row structure it walks
+    // is rop's (d_off .. d_ch_w, d_pos_off, d_con_pos), up whether or not R itself is built.
+    struct Rows {
+      bool ok = false;
+      int *d_row = nullptr, *d_off = nullptr, *d_long_rows = nullptr;
+      unsigned short* d_pos = nullptr;
+      unsigned char* d_w = nullptr;
+      int cap = 0, n_long = 0, ws_rows = 0;  // image capacity in blocks; the rows beyond it, and how many a launch takes
+      size_t ws_stride = 0;                  // doubles per slice of d_ws: nine times the longest of them
+      double* d_ws = nullptr;
+    } rows;
+    // which kernel of the last set-up left vertex.d_H: 1 the gather, 2 the row kernel alone, 3 fused with the build of R;
+    // 0: no set-up yet, or a read-back has summed Hc again since
+    int hc_form = 0;
     double* d_coef = nullptr;  // the cycle's coefficient table (pmg_coef.h, PmgTable), kPmgTableCap doubles
     // multi-GPU: the coarse level is partitioned like the fine one (vertex nodes of the partition boundary are
     // replicated); slots of the coarse exchange buffer are agreed once (pmg_prepare), child weights carry 1/multiplicity
@@ -1409,10 +1424,11 @@ struct tlfea_newton_s {
       unsigned char* d_con_ord = nullptr;
       float *d_ch_w = nullptr, *d_R1 = nullptr;
       void* d_R8 = nullptr;
-      // the streamed build from H (pmg_rop_stream_kernel): positions by source, and the rows beyond its image
-      int *d_pos_off = nullptr, *d_long_rows = nullptr;
+      // positions by source, for the kernels that stream each child's row of H (Rows); stream_cap > 0: a matrix-free
+      // set-up builds R in that pass too
+      int* d_pos_off = nullptr;
       unsigned short* d_con_pos = nullptr;
-      int n_long = 0, stream_cap = 0;
+      int stream_cap = 0;
     } rop;
     LevelIface iface() const { return LevelIface{n_ifc_loc, n_ifc_glob, d_ifc_node, d_ifc_slot, d_bslot_c}; }
     // third level: rigid-body-mode aggregates of the vertex level (pmg_host.h agg_build); lvl.N = 2 Na nodes
@@ -1704,8 +1720,12 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
     m.vertex.release();
     auto& ro = m.rop;
     void* rr[] = {ro.d_off, ro.d_cols, ro.d_ch_off, ro.d_ch, ro.d_con_off, ro.d_con_blk, ro.d_con_ord, ro.d_ch_w, ro.d_R1,
-                  ro.d_R8, ro.d_pos_off, ro.d_long_rows, ro.d_con_pos};
+                  ro.d_R8, ro.d_pos_off, ro.d_con_pos};
     for (void* q : rr)
+      if (q) (void)hipFree(q);
+    auto& gr = m.rows;
+    void* gq[] = {gr.d_row, gr.d_off, gr.d_long_rows, gr.d_pos, gr.d_w, gr.d_ws};
+    for (void* q : gq)
       if (q) (void)hipFree(q);
     auto& g = m.agg;
     void* gg[] = {g.d_agg, g.d_active, g.d_mem_off, g.d_mem, g.d_pair_A, g.d_pair_pos, g.d_pair_B, g.d_pcon_off,
@@ -3595,8 +3615,39 @@ static int pmg_prepare(tlfea_newton_t s) {
   TRY(upload_vec(&m.vertex.d_off, h.c_off)); TRY(upload_vec(&m.vertex.d_cols, h.c_cols)); TRY(upload_vec(&m.vertex.d_diagpos, h.c_diagpos));
   TRY(upload_vec(&m.d_cblk_row, h.cblk_row));
   TRY(upload_vec(&m.d_child_off, h.child_off)); TRY(upload_vec(&m.d_child, h.child)); TRY(upload_vec(&m.d_child_w, h.child_w));
-  TRY(upload_vec(&m.d_con_off, h.con_off)); TRY(upload_vec(&m.d_con_base, h.con_base)); TRY(upload_vec(&m.d_con_deg, h.con_deg));
-  TRY(upload_vec(&m.d_con_w, h.con_w));
+  // T10: the row structure of R and the lists of the combine, for every conforming mesh they fit -- whatever the switches,
+  // the size and the number of ranks: which kernel sums Hc depends on the mesh alone (DESIGN 3g')
+  RopHost ro;
+  const bool have_ro = d->kind == kT10 && pmg_restrict_op_build(d->N, d->h_off.data(), d->h_cols.data(), h, ro);
+  if (have_ro) {
+    auto& r = m.rop;
+    auto& g = m.rows;
+    GalRowsHost gr;
+    g.ok = pmg_galerkin_rows_build(h, ro, gr);
+    if (g.ok) {
+      r.nnz = ro.nnz;
+      r.n_con = ro.n_con;
+      TRY(upload_vec(&r.d_off, ro.off)); TRY(upload_vec(&r.d_cols, ro.cols));
+      TRY(upload_vec(&r.d_ch_off, ro.ch_off)); TRY(upload_vec(&r.d_ch, ro.ch)); TRY(upload_vec(&r.d_ch_w, ro.ch_w));
+      TRY(upload_vec(&r.d_pos_off, ro.pos_off)); TRY(upload_vec(&r.d_con_pos, ro.con_pos));
+      TRY(upload_vec(&g.d_row, gr.row_off)); TRY(upload_vec(&g.d_off, gr.term_off));
+      TRY(upload_vec(&g.d_pos, gr.term_pos)); TRY(upload_vec(&g.d_w, gr.term_w));
+      const std::vector<int> long_rows = pmg_rop_long_rows(ro, rop_stream_cap());
+      g.cap = rop_stream_cap();
+      g.n_long = (int)long_rows.size();
+      TRY(upload_vec(&g.d_long_rows, long_rows));
+      int longest = 0;
+      for (int I : long_rows) longest = std::max(longest, ro.off[I + 1] - ro.off[I]);
+      g.ws_stride = (size_t)9 * longest;
+      // at most 64 MB of images: the long rows are few unless TLFEA_ROP_STREAM_MAX makes every row one
+      g.ws_rows = g.n_long ? (int)std::min<size_t>((size_t)g.n_long, std::max<size_t>(4, ((size_t)8 << 20) / g.ws_stride)) : 0;
+      if (g.n_long) TRY(dmalloc(&g.d_ws, g.ws_stride * (size_t)g.ws_rows));
+    }
+  }
+  if (!m.rows.ok) {  // ANCF, or lists that do not fit: the gather over the contribution lists
+    TRY(upload_vec(&m.d_con_off, h.con_off)); TRY(upload_vec(&m.d_con_base, h.con_base)); TRY(upload_vec(&m.d_con_deg, h.con_deg));
+    TRY(upload_vec(&m.d_con_w, h.con_w));
+  }
   m.n_upper = (int)h.c_upper.size();
   TRY(upload_vec(&m.d_c_upper, h.c_upper)); TRY(upload_vec(&m.d_c_mirror, h.c_mirror));
   const size_t nc = 3 * (size_t)m.vertex.N;
@@ -3607,24 +3658,18 @@ static int pmg_prepare(tlfea_newton_t s) {
     std::printf("p-multigrid: %d fine nodes -> %d vertex nodes, %d coarse blocks (%d gathered from %zu contributions, the rest "
                 "mirrored)\n", d->N, m.vertex.N, m.vertex.nnz, m.n_upper, h.con_w.size());
   if (pmg_rop_possible(s)) {
-    RopHost ro;
-    if (pmg_restrict_op_build(d->N, d->h_off.data(), d->h_cols.data(), h, ro)) {
+    if (have_ro) {
       auto& r = m.rop;
-      r.nnz = ro.nnz;
-      r.n_con = ro.n_con;
-      TRY(upload_vec(&r.d_off, ro.off)); TRY(upload_vec(&r.d_cols, ro.cols));
-      TRY(upload_vec(&r.d_ch_off, ro.ch_off)); TRY(upload_vec(&r.d_ch, ro.ch)); TRY(upload_vec(&r.d_ch_w, ro.ch_w));
+      if (!m.rows.ok) {
+        r.nnz = ro.nnz;
+        r.n_con = ro.n_con;
+        TRY(upload_vec(&r.d_off, ro.off)); TRY(upload_vec(&r.d_cols, ro.cols));
+        TRY(upload_vec(&r.d_ch_off, ro.ch_off)); TRY(upload_vec(&r.d_ch, ro.ch)); TRY(upload_vec(&r.d_ch_w, ro.ch_w));
+      }
       TRY(upload_vec(&r.d_con_off, ro.con_off)); TRY(upload_vec(&r.d_con_blk, ro.con_blk));
       TRY(upload_vec(&r.d_con_ord, ro.con_ord));
-      // the streamed build serves the matrix-free fine smoother only: its lists go up where a set-up can choose that form
-      r.stream_cap = 0;
-      if (rop_stream_env() && fine_matfree_env() != 0 && (fine_matfree_env() == 1 || s->N >= kFineMatfreeMinRows)) {
-        const std::vector<int> long_rows = pmg_rop_long_rows(ro, rop_stream_cap());
-        r.stream_cap = rop_stream_cap();
-        r.n_long = (int)long_rows.size();
-        TRY(upload_vec(&r.d_pos_off, ro.pos_off)); TRY(upload_vec(&r.d_con_pos, ro.con_pos));
-        TRY(upload_vec(&r.d_long_rows, long_rows));
-      }
+      // a matrix-free set-up builds R in the pass that sums Hc, unless TLFEA_ROP_BUILD=gather keeps R on its lists
+      r.stream_cap = m.rows.ok && rop_stream_env() ? m.rows.cap : 0;
       HIP_TRY(hipMalloc(&r.d_R8, ((size_t)r.nnz + 1) * 8 * sizeof(float)));
       TRY(dmalloc(&r.d_R1, (size_t)r.nnz + 1));
       r.ok = true;
@@ -3851,10 +3896,30 @@ static int pmg_prepare(tlfea_newton_t s) {
 }
 
 // Galerkin operators of the current H: Hc = P^T H P, H3 = P2^T Hc P2
-static void vertex_galerkin(tlfea_newton_t s) {
+// The one place that picks the kernel.  T10 with the row lists (pmg_prepare: a property of the mesh): the row kernel --
+// with_R in the same pass as the streamed build of R (a matrix-free set-up), else alone; ANCF and meshes whose lists do
+// not fit: the gather.  setup: the call of a preconditioner set-up, which wants the diagonal blocks in vertex.d_D too;
+// returns whether they were written (the read-backs leave d_D alone).
+static bool vertex_galerkin(tlfea_newton_t s, bool setup = false, bool with_R = false) {
   auto& m = s->pmg;
-  launch_pmg_galerkin(s->stream, m.n_upper, m.d_c_upper, m.d_c_mirror, m.vertex.d_off, m.d_cblk_row, m.d_con_off,
-                      m.d_con_base, m.d_con_deg, m.d_con_w, s->d_H, m.vertex.d_H);
+  if (!m.rows.ok) {
+    launch_pmg_galerkin(s->stream, m.n_upper, m.d_c_upper, m.d_c_mirror, m.vertex.d_off, m.d_cblk_row, m.d_con_off,
+                        m.d_con_base, m.d_con_deg, m.d_con_w, s->d_H, m.vertex.d_H);
+    m.hc_form = setup ? 1 : 0;
+    return false;
+  }
+  const auto& r = m.rop;
+  const auto& g = m.rows;
+  PmgRows a;
+  a.r_off = r.d_off; a.r_cols = r.d_cols; a.pos_off = r.d_pos_off; a.con_pos = r.d_con_pos;
+  a.ch_off = r.d_ch_off; a.ch = r.d_ch; a.ch_w = r.d_ch_w; a.f_off = s->d->d_off; a.Hval = s->d_H;
+  a.g_row = g.d_row; a.g_off = g.d_off; a.g_pos = g.d_pos; a.g_w = g.d_w;
+  a.c_off = m.vertex.d_off; a.c_upper = m.d_c_upper; a.c_mirror = m.d_c_mirror; a.cblk_row = m.d_cblk_row;
+  a.Hc = m.vertex.d_H; a.D = setup ? m.vertex.d_D : nullptr;
+  a.sc_f = with_R ? s->d_sc : nullptr; a.R8 = with_R ? r.d_R8 : nullptr; a.R1 = with_R ? r.d_R1 : nullptr;
+  launch_pmg_galerkin_rows(s->stream, m.vertex.N, g.cap, a, with_R, g.d_long_rows, g.n_long, g.ws_stride, g.ws_rows, g.d_ws);
+  m.hc_form = !setup ? 0 : (with_R ? 3 : 2);
+  return setup;
 }
 static void level3_galerkin(tlfea_newton_t s) {
   auto& g = s->pmg.agg;
@@ -3875,27 +3940,29 @@ static int pmg_build_level(tlfea_newton_t s) {
   auto& m = s->pmg;
   PolyLevel& V = m.vertex;
   const int bits = cheb_bits_eff(s);
-  vertex_galerkin(s);
+  // The choice of the fine smoother comes first (it needs nothing computed below): where it falls on the matrix-free form
+  // and R is built streamed, the pass that sums Hc builds R too, scaled with sc_c formed from the diagonal blocks it sums --
+  // the bits the lp_scale launch below writes to V.d_sc from V.d_D (one GPU: no interface sum touches V.d_D in between).
+  m.rop.built = false;
+  const bool rop = pmg_rop_on(s);
+  if (rop) {
+    m.rop.built = true;
+    TRY(fine_matfree_choose(s));
+  }
+  const bool fused = rop && s->fmf.now && m.rop.stream_cap > 0;
   TRY(V.ensure_copy(bits));
-  launch_extract_diag(s->stream, V.N, V.inc(), V.d_H, V.d_D);
+  if (!vertex_galerkin(s, true, fused)) launch_extract_diag(s->stream, V.N, V.inc(), V.d_H, V.d_D);
   // multi-GPU: Hc = sum over ranks of P^T H_r P -- the diagonal blocks of boundary vertices are partial per rank
   if (s->ar) TRY(iface_sum_lvl(s, m.iface(), V.d_D, 9));
   // overlapping partition: rows of the outermost ghost layer are incomplete -- their diagonal blocks (hence the scaling of
   // their COLUMNS in every complete row) come from their owners
   TRY(halo_refresh_f64(s, 1, s->halo.depth, 9, V.d_D));
   level_scale_convert(s, V, bits);
-  m.rop.built = false;
-  if (pmg_rop_on(s)) {  // R = S_c P^T S_f^-1 Hs from the fine copy as stored (converted before it is read) and both scalings
+  if (rop && !fused) {  // R = S_c P^T S_f^-1 Hs from the fine copy as stored (converted before it is read) and both scalings
     auto& r = m.rop;
-    r.built = true;
-    // the fine smoother will apply H itself (DESIGN 3g'): R from H's fp64 rows, so that both see one operator
-    TRY(fine_matfree_choose(s));
     if (!s->fmf.now) TRY(ensure_fine_copy(s));  // a set-up that deferred the copy and does not take the form after all
-    if (s->fmf.now && r.stream_cap > 0)
-      launch_pmg_rop_stream(s->stream, V.N, r.stream_cap, r.d_off, r.d_cols, r.d_pos_off, r.d_con_pos, r.d_con_off, r.d_con_blk,
-                            r.d_con_ord, r.d_ch_off, r.d_ch, r.d_ch_w, s->d->d_off, s->d_H, s->d_sc, V.d_sc, r.d_R8, r.d_R1,
-                            r.d_long_rows, r.n_long);
-    else if (s->fmf.now)
+    // where the fine smoother applies H itself (DESIGN 3g'), R from H's fp64 rows, so that both see one operator
+    if (s->fmf.now)
       launch_pmg_rop_build_h(s->stream, V.N, r.d_off, r.d_cols, r.d_con_off, r.d_con_blk, r.d_con_ord, r.d_ch_off, r.d_ch,
                              r.d_ch_w, s->d->d_off, s->d_H, s->d_sc, V.d_sc, r.d_R8, r.d_R1);
     else
@@ -4926,6 +4993,20 @@ extern "C" int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int* par0, int* par1,
   D2H(c_off, m.vertex.d_off, (size_t)nc + 1);
   D2H(c_cols, m.vertex.d_cols, (size_t)nnz);
   D2H(Hc, m.vertex.d_H, (size_t)9 * nnz);
+  return 0;
+}
+// Hc as the LAST preconditioner set-up left it on the device, nothing recomputed (tlfea_newton_pmg_retrieve and
+// tlfea_newton_pmg3_retrieve sum it again, on their own): the values, and which kernel summed them -- 1 the gather over the
+// contribution lists, 2 the row kernel alone, 3 the row kernel fused with the build of R
+extern "C" int tlfea_newton_pmg_retrieve_built(tlfea_newton_t s, double* Hc, int* form) {
+  if (!s || !Hc || !form) return fail("tlfea_newton_pmg_retrieve_built: null argument");
+  const auto& m = s->pmg;
+  if (!m.ok || !m.hc_form || !m.vertex.d_H)
+    return fail("tlfea_newton_pmg_retrieve_built: no p-multigrid set-up has left Hc on this solver since the last read-back that "
+                "recomputes it");
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  D2H(Hc, m.vertex.d_H, (size_t)9 * m.vertex.nnz);
+  *form = m.hc_form;
   return 0;
 }
 

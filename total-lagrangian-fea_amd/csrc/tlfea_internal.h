@@ -347,15 +347,34 @@ void launch_pmg_prolong(hipStream_t s, int N, const int* par0, const int* par1, 
 // per solve), and the restriction  r^_c = S_c P^T S_f^-1 res_f - R d_f  fused with the coarse start vectors
 void launch_pmg_rop_build_h(hipStream_t s, int Nc, const int* r_off, const int* r_cols, const int* con_off, const int* con_blk,
                             const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const int* f_off,
-                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1,
-                            const int* rows = nullptr, int n_rows = 0);
-// the same R, each child's row of H streamed through an LDS image of the R row (rows of at most cap <= kRopStreamCap blocks;
-// the n_long longer ones, listed ascending in long_rows, go to the gather kernel in a second launch)
+                            const double* Hval, const double* sc_f, const double* sc_c, void* R8, float* R1);
+// The T10 vertex level's Hc = P^T H P, and with_R the same R, from an image of the R row (DESIGN 3g'): a wavefront per
+// coarse row streams its children's rows of H into the image, sums the row's blocks of Hc (column >= row, mirrored) from
+// it and, with_R, scales the image into the row of R with sc_c formed from the diagonal block just summed.  Rows of at
+// most cap <= kRopStreamCap blocks keep the image in LDS; the n_long longer ones (long_rows, ascending) take the same
+// code with the image in a slice of ws (ws_stride doubles each, ws_rows slices: that many rows a launch).
 constexpr int kRopStreamCap = 128;  // blocks of the image: 9 KB per wavefront, 12 wavefronts per CU
-void launch_pmg_rop_stream(hipStream_t s, int Nc, int cap, const int* r_off, const int* r_cols, const int* pos_off,
-                           const unsigned short* con_pos, const int* con_off, const int* con_blk, const unsigned char* con_ord,
-                           const int* ch_off, const int* ch, const float* ch_w, const int* f_off, const double* Hval,
-                           const double* sc_f, const double* sc_c, void* R8, float* R1, const int* long_rows, int n_long);
+struct PmgRows {
+  // the row structure of R (pmg_host.h RopHost), the fine row offsets and H
+  const int *r_off, *r_cols, *pos_off;
+  const unsigned short* con_pos;
+  const int *ch_off, *ch;
+  const float* ch_w;
+  const int* f_off;
+  const double* Hval;
+  // the combine (GalRowsHost) and the coarse pattern; D: the diagonal blocks [Nc][9] as well, null = not wanted
+  const int *g_row, *g_off;
+  const unsigned short* g_pos;
+  const unsigned char* g_w;
+  const int *c_off, *c_upper, *c_mirror, *cblk_row;
+  double *Hc, *D;
+  // with_R only: the fine scaling and R's values (8 + 1 floats per block)
+  const double* sc_f;
+  void* R8;
+  float* R1;
+};
+void launch_pmg_galerkin_rows(hipStream_t s, int Nc, int cap, const PmgRows& a, bool with_R, const int* long_rows, int n_long,
+                              size_t ws_stride, int ws_rows, double* ws);
 void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
                           const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,
                           const void* B1, int bits, const double* sc_f, const double* sc_c, void* R8, float* R1);

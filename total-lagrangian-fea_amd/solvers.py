@@ -131,6 +131,16 @@ class SyncedNewtonSolver:
         check(self._lib.tlfea_newton_pmg_retrieve(self._h, ip(par0), ip(par1), ip(c_off), ip(c_cols), dp(Hc)))
         return par0, par1, c_off, c_cols, Hc
 
+    def RetrievePmgLevelBuilt(self):
+        """(Hc_values, form): the Galerkin operator as the last preconditioner set-up left it on the device, nothing
+        recomputed, and the kernel that summed it (1 gather, 2 row kernel alone, 3 row kernel fused with the build of R).
+        Call it before RetrievePmgLevel / RetrievePmgLevel3, which sum Hc again (test hook)."""
+        nc, nnz, form = C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.tlfea_newton_pmg_sizes(self._h, C.byref(nc), C.byref(nnz)))
+        Hc = np.zeros(9 * nnz.value)
+        check(self._lib.tlfea_newton_pmg_retrieve_built(self._h, dp(Hc), C.byref(form)))
+        return Hc, form.value
+
     def GetRestrictOpInfo(self):
         """dict(active, n_coarse, blocks, contributions, fine_blocks, fine_bits) of the restricted fine operator
         R = S_c P^T S_f^-1 Hs as the last preconditioner set-up left it (active 0: the cycle runs the fine residual pass)"""
