@@ -513,6 +513,29 @@ int tlfea_t10_material_sensitivity(tlfea_t10_t h, const double *w, const double 
 int tlfea_t10_material_sensitivity_shape(tlfea_t10_t h, int *n_mat, int *slots);
 /* mean ms over `reps` launches of out[0] the element kernel, [1] its reduction (hipEvents; tools/adjoint_timing.py) */
 int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, double *out_ms2);
+/* ---- shape sensitivities of the implicit step (no reference counterpart) -----------------------------------
+ * The same adjoint step with one more output: X_bar [3N] (interleaved like the other vectors; NULL = not wanted), the
+ * cotangent of the reference coordinates of every node -- mid-edge nodes are coordinates of their own, a straight-sided
+ * parametrisation by the vertices is the caller's chain rule.  It covers f_int, the inertia and the body acceleration
+ * (both are M(X) times a vector); x_prev, the targets and f_ext do not depend on X.  tlfea_adjoint_in / tlfea_adjoint_out
+ * are those of tlfea_newton_adjoint_step, which is this call with X_bar = NULL.  With X_bar wanted the call refuses, on top
+ * of the list above, any rigid or field obstacle and any T10 face traction (their nodal weights are reference areas). */
+int tlfea_newton_adjoint_step_shape(tlfea_newton_t s, const tlfea_adjoint_in *in, const tlfea_adjoint_out *out, double *X_bar,
+                                    int *info, double *rel_res);
+int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tlfea_adjoint_in *in, const tlfea_adjoint_out *out,
+                                           double *X_bar, int *info, double *rel_res);
+/* The element kernel and its gather alone, at the current positions and reference geometry: host vectors w, u [3N] (u NULL:
+ * no mass term; u needs an assembled mass matrix, whose densities the term uses) -> X_bar [3N]. */
+int tlfea_t10_shape_sensitivity(tlfea_t10_t h, const double *w, const double *u, double *X_bar);
+/* mean ms over `reps` launches of out[0] the element kernel, [1] its gather (hipEvents; tools/shape_timing.py) */
+int tlfea_t10_time_shape_kernels(tlfea_t10_t h, int reps, double *out_ms2);
+/* A new reference geometry X [n = number of nodes] for the same connectivity: grad N, det J and, if a mass matrix was
+ * assembled, its values (same pattern, same densities) are recomputed; boundary-face geometry, traction vectors, the
+ * constant load vector and obstacle surface weights follow.  Current positions, velocities, multipliers and targets are
+ * left alone: the caller sets them.  The solver's sparsity, row groups and multigrid aggregates stay as analysed (they
+ * order work and build a preconditioner; they do not enter the residual or H).  Refused: an ANCF handle; an element
+ * with det J <= 0 at a quadrature point, which leaves the old geometry in place. */
+int tlfea_t10_set_reference_positions(tlfea_t10_t h, const double *x, const double *y, const double *z, int n);
 /* The same product from the matrix-free pair of the CG iteration (element records instead of the CSR values),
  * with the records of the last assembly.  Returns an error where that product is not eligible: anything but straight-sided
  * T10 elements with one St.Venant-Kirchhoff material on one GPU, general linear constraints, rigid obstacles, per-element

@@ -96,6 +96,9 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   int2* d_sn_blk = nullptr;
   int sn_nb = 0, sn_part_cap = 0, sn_out_cap = 0;
   long sn_gen = -1;
+  // shape sensitivities (tlfea_t10_shape_sensitivity): allocated on first use.  d_sh_rows [10][Epad][3] the
+  // element rows, d_sh_out [N][3] the gathered cotangent of the host form
+  double *d_sh_rows = nullptr, *d_sh_out = nullptr;
   // constraints
   double* d_cons = nullptr;
   int *d_fixed = nullptr, *d_fixed_slot = nullptr;
@@ -150,5 +153,7 @@ inline AncfObsView ancf_obs_view(tlfea_t10_t h) {
 
 // obstacle_api.hip
 int ancf_points_build(tlfea_t10_t h);
+// the reference geometry of a T10 object has moved (tlfea_t10_set_reference_positions): surface weights again from h_X0
+int t10_surface_refresh(tlfea_t10_t h);
 
 }  // namespace tlfea

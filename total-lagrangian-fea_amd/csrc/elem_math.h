@@ -115,6 +115,91 @@ __device__ __forceinline__ void elastic_P(const double F[3][3], const Material& 
   }
 }
 
+// Material tangent of elastic_P applied to D: dP = (dP/dF) : D (shape sensitivities).
+// SVK: D S2 + F (lambda tr(dE) I + 2 mu dE), dE = sym(F^T D), S2 = lambda tr(E) I + 2 mu E.
+// MR, term by term of elastic_P with g = G : D (dJ = J g), dI1 = 2 F : D, dC = F^T D + D^T F, dI2 = I1 dI1 - tr(C dC),
+// dG = -G D^T G.
+__device__ __forceinline__ void elastic_dP(const double F[3][3], const double D[3][3], const Material& mat, double dP[3][3]) {
+  double FD = 0.0, FtD[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      double a = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) a += F[k][i] * D[k][j];
+      FtD[i][j] = a;
+      FD += F[i][j] * D[i][j];
+    }
+  if (mat.model == kMooneyRivlin) {
+    MRState s;
+    mr_state(F, mat.mu10, mat.mu01, mat.kappa, s);
+    double g = 0.0, CdC = 0.0, dG[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        g += s.G[i][j] * D[i][j];
+        CdC += s.C[i][j] * (FtD[i][j] + FtD[j][i]);  // C and dC are symmetric: tr(C dC) = C : dC
+      }
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double a = 0.0;  // (G D^T G)_ij = sum_kl G_ik D_lk G_lj
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+          for (int l = 0; l < 3; l++) a += s.G[i][k] * D[l][k] * s.G[l][j];
+        dG[i][j] = -a;
+      }
+    const double dI1 = 2.0 * FD, dI2 = s.I1 * dI1 - CdC;
+    const double t3d = mat.kappa * (2.0 * s.J - 1.0) * s.J * g;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double DC = 0.0, FdC = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          DC += D[i][k] * s.C[k][j];
+          FdC += F[i][k] * (FtD[k][j] + FtD[j][k]);
+        }
+        const double term1 = F[i][j] - (s.I1 / 3.0) * s.G[i][j];
+        const double term2 = s.I1 * F[i][j] - s.FC[i][j] - (2.0 * s.I2 / 3.0) * s.G[i][j];
+        const double d1 = -(2.0 / 3.0) * g * term1 + D[i][j] - (dI1 / 3.0) * s.G[i][j] - (s.I1 / 3.0) * dG[i][j];
+        const double d2 = -(4.0 / 3.0) * g * term2 + dI1 * F[i][j] + s.I1 * D[i][j] - DC - FdC -
+                          (2.0 * dI2 / 3.0) * s.G[i][j] - (2.0 * s.I2 / 3.0) * dG[i][j];
+        dP[i][j] = s.t1 * d1 + s.t2 * d2 + t3d * s.G[i][j] + s.t3 * dG[i][j];
+      }
+  } else {
+    double C[3][3], trC = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double c = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) c += F[k][i] * F[k][j];
+        C[i][j] = c;
+      }
+    trC = C[0][0] + C[1][1] + C[2][2];
+    const double ltrE = mat.lambda * (0.5 * trC - 1.5), ltrdE = mat.lambda * FD;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double DC = 0.0, FdE2 = 0.0;  // D C, F (F^T D + D^T F) = 2 F dE
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          DC += D[i][k] * C[k][j];
+          FdE2 += F[i][k] * (FtD[k][j] + FtD[j][k]);
+        }
+        dP[i][j] = ltrE * D[i][j] + mat.mu * (DC - D[i][j]) + ltrdE * F[i][j] + mat.mu * FdE2;
+      }
+  }
+}
+
 // Wave-private LDS hand-offs (the fused assembly kernels' workgroup is ONE wavefront; the residual launch transposes its
 // stores inside each wavefront's own slice): a wavefront's LDS instructions execute in program order, so data written by one
 // lane is visible to the lanes of every later LDS instruction without a barrier.  What remains of __syncthreads() is the

@@ -15,6 +15,21 @@ static void surface_build(tlfea_t10_t h) {
   for (int i = 0; i < h->N; i++)
     if (h->h_surf_w[i] > 0.0) h->h_surf.push_back(i);
 }
+// The reference geometry moved: the weights are reference areas.  The connectivity and with it the set of surface nodes
+// stay, so the node list and every node-owned buffer keep their size; only the weights are replaced.
+int tlfea::t10_surface_refresh(tlfea_t10_t h) {
+  if (h->h_surf_w.empty()) return 0;  // never built: the first use builds them from the new geometry
+  const std::vector<int> nodes = h->h_surf;
+  h->h_surf_w.clear();
+  surface_build(h);
+  if (h->h_surf != nodes) return fail("tlfea_t10_set_reference_positions: the set of surface nodes changed (a boundary face of zero area)");
+  if (h->d_ob_w && !h->h_surf.empty()) {
+    std::vector<double> w(h->h_surf.size());
+    for (size_t k = 0; k < w.size(); k++) w[k] = h->h_surf_w[h->h_surf[k]];
+    HIP_TRY(hipMemcpy(h->d_ob_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return 0;
+}
 static void obstacles_free(tlfea_t10_t h) {
   for (double** p : {&h->d_ob_w, &h->d_ob_f, &h->d_ob_blk, &h->d_ob_fk, &h->d_ob_res}) dfree(*p);
   dfree(h->d_ob_node);

@@ -112,7 +112,7 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts, h->d_ld_fc, h->d_ld_tr, h->d_ld_f,
                   h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask, h->d_ld_fnodes, h->d_ld_foff,
                   h->d_ld_fslot, h->d_fld, h->d_sn_sens, h->d_sn_part, h->d_sn_out, h->d_sn_w, h->d_sn_u, h->d_sn_pe,
-                  h->d_sn_idx, h->d_sn_boff, h->d_sn_blk};
+                  h->d_sn_idx, h->d_sn_boff, h->d_sn_blk, h->d_sh_rows, h->d_sh_out};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (double* p : h->d_fld_V)
@@ -943,6 +943,82 @@ extern "C" int tlfea_t10_calc_mass_matrix(tlfea_t10_t h) {
   h->mass_rho0 = h->d_emat ? 1.0 : h->mat.rho0;
   h->mass_pe = h->d_emat != nullptr;
   h->ld_const_dirty = true;  // the body force follows the mass matrix
+  return 0;
+}
+
+// A new reference geometry for the same connectivity: grad N, det J and the mass values again from X, with
+// everything derived from the reference coordinates on the host marked stale.  The current positions, velocities,
+// multipliers and targets are the caller's.  An inverted element refuses the call before anything is touched.
+extern "C" int tlfea_t10_set_reference_positions(tlfea_t10_t h, const double* x, const double* y, const double* z, int n) {
+  const char* what = "tlfea_t10_set_reference_positions";
+  if (h && h->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, "setting reference positions.");
+  if (!x || !y || !z) return fail(std::string(what) + ": null coordinates");
+  if (n != h->N) return fail(std::string(what) + ": " + std::to_string(n) + " nodes given, the object has " + std::to_string(h->N));
+  const int E = h->E, N = h->N;
+  // det J at every point of the rule, as dndu_pre_kernel forms it
+  const int edges[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};
+  const double dL[4][3] = {{-1, -1, -1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  double dN[kNQ][kNN][3];
+  for (int q = 0; q < kNQ; q++) {
+    const double L[4] = {1.0 - h->h_q[0][q] - h->h_q[1][q] - h->h_q[2][q], h->h_q[0][q], h->h_q[1][q], h->h_q[2][q]};
+    for (int i = 0; i < 4; i++)
+      for (int d = 0; d < 3; d++) dN[q][i][d] = (4.0 * L[i] - 1.0) * dL[i][d];
+    for (int k = 0; k < 6; k++)
+      for (int d = 0; d < 3; d++)
+        dN[q][k + 4][d] = 4.0 * (L[edges[k][0]] * dL[edges[k][1]][d] + L[edges[k][1]] * dL[edges[k][0]][d]);
+  }
+  int bad = E;
+#pragma omp parallel for schedule(static) reduction(min : bad)
+  for (int e = 0; e < E; e++)
+    for (int q = 0; q < kNQ; q++) {
+      double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+      for (int a = 0; a < kNN; a++) {
+        const int g = h->h_conn[(size_t)a * E + e];
+        const double X[3] = {x[g], y[g], z[g]};
+        for (int i = 0; i < 3; i++)
+          for (int j = 0; j < 3; j++) J[i][j] += X[i] * dN[q][a][j];
+      }
+      const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+                         J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+      if (!(det > 0.0)) bad = std::min(bad, e);
+    }
+  if (bad < E)
+    return fail(std::string(what) + ": element " + std::to_string(bad) + " is inverted (det J <= 0 at a quadrature point); the "
+                "reference geometry is unchanged");
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the old geometry
+  double* d_X = nullptr;
+  TRY(dmalloc(&d_X, 3 * (size_t)N));
+  int rc = 0;
+  const double* src[3] = {x, y, z};
+  for (int c = 0; c < 3 && !rc; c++)
+    if (hipMemcpy(d_X + (size_t)c * N, src[c], (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(std::string(what) + ": upload failed");
+  if (!rc) {
+    launch_dndu_pre(h->stream, E, h->Epad, h->d_conn, d_X, d_X + N, d_X + 2 * (size_t)N, h->d_qx, h->d_qy, h->d_qz, h->d_gradN,
+                    h->d_gradN_t, h->d_detJ);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = fail(std::string(what) + ": grad N launch failed");
+  }
+  (void)hipFree(d_X);
+  if (rc) return rc;
+  h->have_dndu = true;
+  h->geom_gen++;
+  std::copy(x, x + N, h->h_X0.begin());
+  std::copy(y, y + N, h->h_X0.begin() + N);
+  std::copy(z, z + N, h->h_X0.begin() + 2 * (size_t)N);
+  if (h->mass_rho0 >= 0.0 && h->d_mval) {
+    // the same pattern and the densities the matrix was assembled with (under a table: slot kEmRhoM of the records)
+    launch_mass_values(h->stream, h->view(), h->inc(), h->d_qx, h->d_qy, h->d_qz, h->mass_rho0, h->d_mval, h->d_emat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  h->ld_const_dirty = true;  // M a and the traction vector follow the reference geometry
+  if (h->bf_built) {
+    h->bf_built = false;  // outward orientation is decided from the reference coordinates
+    boundary_faces_build(h);
+    if (h->ld_n_trac > 0) TRY(t10_loads_build_traction(h));
+  }
+  TRY(t10_surface_refresh(h));
   return 0;
 }
 
@@ -6184,6 +6260,61 @@ extern "C" int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, doubl
   return 0;
 }
 
+// ---- shape sensitivities (shape_kernels.hip) -----------------------------------------------------------------
+static int shape_prepare(tlfea_t10_t h, const char* what) {
+  if (h && h->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)");
+  NEED_SETUP(h, what);
+  if (!h->have_dndu) return fail(std::string(what) + ": CalcDnDuPre must be called first");
+  if (!h->is_csr_setup) TRY(tlfea_t10_build_mass_csr_pattern(h));  // the node -> element incidence of the gather
+  if (!h->d_sh_rows) TRY(dmalloc(&h->d_sh_rows, (size_t)3 * kNN * h->Epad));
+  return 0;
+}
+// the two launches after shape_prepare: device vectors w, u [3N] (u null: no mass term) -> d_xbar [N][3].  The density
+// of the mass term is the one the mass matrix was assembled with.
+static void shape_launch_points(tlfea_t10_t h, hipStream_t st, const double* d_w, const double* d_u) {
+  Material m = h->mat;
+  m.rho0 = h->mass_rho0 >= 0.0 ? h->mass_rho0 : 0.0;
+  launch_shape_points(st, h->view(), m, h->d_emat, h->h_q, d_w, d_u, h->d_sh_rows);
+}
+static void shape_launch_gather(tlfea_t10_t h, hipStream_t st, double* d_xbar) {
+  launch_shape_gather(st, h->N, h->Epad, h->inc(), h->d_sh_rows, d_xbar);
+}
+
+extern "C" int tlfea_t10_shape_sensitivity(tlfea_t10_t h, const double* w, const double* u, double* X_bar) {
+  TRY(shape_prepare(h, "tlfea_t10_shape_sensitivity"));
+  if (!w || !X_bar) return fail("tlfea_t10_shape_sensitivity: null w or X_bar");
+  if (u && h->mass_rho0 < 0.0) return fail("tlfea_t10_shape_sensitivity: u given but no mass matrix is assembled (CalcMassMatrix)");
+  const size_t n = 3 * (size_t)h->N;
+  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
+  if (u && !h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
+  if (!h->d_sh_out) TRY(dmalloc(&h->d_sh_out, n));
+  HIP_TRY(hipMemcpy(h->d_sn_w, w, n * sizeof(double), hipMemcpyHostToDevice));
+  if (u) HIP_TRY(hipMemcpy(h->d_sn_u, u, n * sizeof(double), hipMemcpyHostToDevice));
+  shape_launch_points(h, h->stream, h->d_sn_w, u ? h->d_sn_u : nullptr);
+  shape_launch_gather(h, h->stream, h->d_sh_out);
+  HIP_TRY(hipGetLastError());
+  D2H(X_bar, h->d_sh_out, n);
+  HIP_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+extern "C" int tlfea_t10_time_shape_kernels(tlfea_t10_t h, int reps, double* out_ms2) {
+  TRY(shape_prepare(h, "tlfea_t10_time_shape_kernels"));
+  if (!out_ms2) return fail("tlfea_t10_time_shape_kernels: null output");
+  if (reps < 1) reps = 1;
+  const size_t n = 3 * (size_t)h->N;
+  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
+  if (!h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
+  if (!h->d_sh_out) TRY(dmalloc(&h->d_sh_out, n));
+  // any finite vectors serve a timing (tlfea_t10_time_sensitivity_kernels): the positions as w, zeros as u
+  HIP_TRY(hipMemset(h->d_sn_w, 0, n * sizeof(double)));
+  HIP_TRY(hipMemcpy(h->d_sn_w, h->d_x, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice));
+  HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
+  TRY(time_reps(h->stream, reps, &out_ms2[0], [&](int) { shape_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u); return 0; }));
+  TRY(time_reps(h->stream, reps, &out_ms2[1], [&](int) { shape_launch_gather(h, h->stream, h->d_sh_out); return 0; }));
+  return 0;
+}
+
 // why the adjoint step cannot run on the solver's state now (0: it can)
 static int adjoint_refusal(tlfea_newton_t s) {
   if (!s) return fail("tlfea_newton_adjoint_step: null handle");
@@ -6214,12 +6345,28 @@ static int adjoint_refusal(tlfea_newton_t s) {
   return 0;
 }
 extern "C" int tlfea_newton_adjoint_ready(tlfea_newton_t s) { return adjoint_refusal(s); }
+// what X_bar adds to the refusals: loads whose nodal weights are reference areas, which the shape kernel does not carry
+static int adjoint_shape_refusal(tlfea_newton_t s) {
+  tlfea_t10_t d = s->d;
+  const std::string w = "tlfea_newton_adjoint_step_shape: ";
+  if (d->obs.n > 0)
+    return fail(w + "a rigid or field obstacle is set: its nodal weights are reference areas, whose dependence on the "
+                    "reference geometry X_bar does not carry");
+  if (d->ld_n_trac > 0)
+    return fail(w + "a face traction is set: its nodal loads are reference areas, whose dependence on the reference "
+                    "geometry X_bar does not carry");
+  return 0;
+}
 
-extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                                                int* info, double* rel_res) {
+extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tlfea_adjoint_in* in,
+                                                      const tlfea_adjoint_out* out, double* X_bar, int* info, double* rel_res) {
   TRY(adjoint_refusal(s));
   if (!in || !out) return fail("tlfea_newton_adjoint_step: null argument");
   tlfea_t10_t d = s->d;
+  if (X_bar) {
+    TRY(adjoint_shape_refusal(s));
+    TRY(shape_prepare(d, "tlfea_newton_adjoint_step_shape"));
+  }
   TRY(sens_prepare(d, "tlfea_newton_adjoint_step"));
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
   TRY(sync_constraints(s));
@@ -6284,6 +6431,10 @@ extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_ad
     }
     if (out->per_element) launch_sens_transpose(s->stream, d->E, d->Epad, slots, d->d_sn_sens, out->per_element);
   }
+  if (X_bar) {
+    shape_launch_points(d, s->stream, w, u);
+    shape_launch_gather(d, s->stream, X_bar);
+  }
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s->stream);
   keep.restore();
   HIP_TRY(e1);
@@ -6293,11 +6444,17 @@ extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_ad
   return 0;
 }
 
-extern "C" int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                                         int* info, double* rel_res) {
+extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                                                int* info, double* rel_res) {
+  return tlfea_newton_adjoint_step_shape_device(s, in, out, nullptr, info, rel_res);
+}
+
+extern "C" int tlfea_newton_adjoint_step_shape(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                                               double* X_bar, int* info, double* rel_res) {
   TRY(adjoint_refusal(s));
   if (!in || !out) return fail("tlfea_newton_adjoint_step: null argument");
   tlfea_t10_t d = s->d;
+  if (X_bar) TRY(adjoint_shape_refusal(s));
   const size_t n = 3 * (size_t)s->N, nc = (size_t)s->n_constraints;
   const size_t n_pm = (size_t)sens_n_mat(d) * sens_slots(d), n_pe = (size_t)d->E * sens_slots(d);
   ModalWork wk;
@@ -6316,16 +6473,23 @@ extern "C" int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_i
   TRY(up(in->lam_bar, nc, &din.lam_bar));
   TRY(up(in->v_prev, n, &din.v_prev));
   struct Ret { double* host; double** dev; size_t cnt; };
+  double* d_Xbar = nullptr;
   const Ret rets[] = {{out->f_ext_bar, &dout.f_ext_bar, n}, {out->v_prev_bar, &dout.v_prev_bar, n},
                       {out->x_prev_bar, &dout.x_prev_bar, n}, {out->lam_in_bar, &dout.lam_in_bar, nc},
                       {out->t_bar, &dout.t_bar, nc}, {out->a_bar, &dout.a_bar, 3},
-                      {out->per_material, &dout.per_material, n_pm}, {out->per_element, &dout.per_element, n_pe}};
+                      {out->per_material, &dout.per_material, n_pm}, {out->per_element, &dout.per_element, n_pe},
+                      {X_bar, &d_Xbar, n}};
   for (const Ret& r : rets)
     if (r.host && r.cnt > 0) TRY(wk.alloc(r.dev, r.cnt));
-  TRY(tlfea_newton_adjoint_step_device(s, &din, &dout, info, rel_res));
+  TRY(tlfea_newton_adjoint_step_shape_device(s, &din, &dout, d_Xbar, info, rel_res));
   for (const Ret& r : rets)
     if (r.host && r.cnt > 0) HIP_TRY(hipMemcpy(r.host, *r.dev, r.cnt * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
+}
+
+extern "C" int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                                         int* info, double* rel_res) {
+  return tlfea_newton_adjoint_step_shape(s, in, out, nullptr, info, rel_res);
 }
 
 

@@ -627,4 +627,12 @@ void launch_adj_out(hipStream_t s, int n, int nc, const AdjCons& J, const double
                     const double* vt, const double* lambar, double h, double rho, double* fext_bar, double* vprev_bar,
                     double* xprev_bar, double* lam_in_bar, double* t_bar);
 
+// Shape sensitivities of the implicit Newton step (shape_kernels.hip).  No atomics.
+// rows [10][Epad][3] per (local node, element): sum_q dV S_q G_b,q with S = (P : D + rho (N w).(N u)) I - F^T dP[D] - D^T P
+// at the current positions; mat.rho0 (emat: slot kEmRhoM of the element's record) is the density of the mass term, u null
+// = no mass term; q: the points of the mass matrix's rule (x | y | z).  Then X_bar [N][3] = - the sum of every node's rows in ascending element order.
+void launch_shape_points(hipStream_t s, const ElemView& m, const Material& mat, const double* emat, const double q[3][kNQ],
+                         const double* w, const double* u, double* rows);
+void launch_shape_gather(hipStream_t s, int N, int Epad, const Incidence& inc, const double* rows, double* xbar);
+
 }  // namespace tlfea

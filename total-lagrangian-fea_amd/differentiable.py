@@ -10,6 +10,12 @@ Mooney-Rivlin (mu10, mu01, kappa, rho0); lame_from_E_nu / E_nu_from_lame are wri
 (E, nu) is autograd's.  Densities enter the mass matrix: a forward whose densities differ from the ones the mass matrix
 was assembled with runs CalcMassMatrix again (and so does a backward that has to go back to them).
 
+The optional trailing `reference` tensor [N, 3] is the reference geometry X of all ten nodes of every element:
+a forward whose reference differs from the geometry last applied calls SetReferencePositions (and so does a backward that
+has to go back), and backward returns its cotangent.  straight_sided() places the mid-edge nodes at the means of their
+vertices in torch, so a vertex-only parametrisation differentiates through autograd.  With a reference that requires a
+gradient, obstacles and face tractions are refused as well.
+
 Not differentiated (refused by the adjoint step): ANCF kinds, damping, friction, follower pressure, a partitioned mesh,
 steps with more than one outer iteration.
 """
@@ -73,15 +79,43 @@ def _apply_inputs(solver, data, f_ext, targets, gravity, materials):
             data.UpdateConstraintTargets(full[:, 0], full[:, 1], full[:, 2])
 
 
+_EDGES = ((0, 1), (1, 2), (0, 2), (0, 3), (1, 3), (2, 3))  # mid-edge node 4 + k lies between these vertices
+
+
+def straight_sided(Xv, conn):
+    """All-node coordinates [N, 3] of a straight-sided mesh from Xv [N, 3], of which only the vertex rows are read: every
+    mid-edge node is the mean of its two vertices.  conn [E, 10] (numpy or tensor of node ids)."""
+    c = np.asarray(conn.cpu() if torch.is_tensor(conn) else conn).astype(np.int64)
+    mid = np.concatenate([c[:, 4 + k] for k in range(6)])
+    va = np.concatenate([c[:, i] for i, _ in _EDGES])
+    vb = np.concatenate([c[:, j] for _, j in _EDGES])
+    mid, first = np.unique(mid, return_index=True)  # an edge shared by several elements has the same two vertices in all
+    mid, va, vb = (torch.as_tensor(a, device=Xv.device) for a in (mid, va[first], vb[first]))
+    X = Xv.clone()
+    X[mid] = 0.5 * (Xv[va] + Xv[vb])
+    return X
+
+
+def _apply_reference(data, reference):
+    """Move the object's reference geometry where it differs from the one last applied (None = leave it)."""
+    if reference is None:
+        return
+    R = _np(reference).reshape(-1, 3)
+    if not np.array_equal(np.asarray(data._X0), R):
+        data.SetReferencePositions(R)
+
+
 class ImplicitStep(torch.autograd.Function):
-    """(x, v, lambda)_new = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials).
+    """(x, v, lambda)_new = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials[, reference]).
 
     x, v [N, 3], lam [n_constraints]; f_ext [N, 3]; targets [n_fixed, 3] (positions of data.fixed_nodes, in their order)
     or the right-hand side [n_constraints] of CSR constraints; gravity [3]; materials [n_mat, P + 1].  Any of the last four
-    may be None: the objects keep what is set and no gradient flows.  The solver's parameters must have max_outer = 1."""
+    may be None: the objects keep what is set and no gradient flows.  reference [N, 3] (optional): the reference geometry.
+    The solver's parameters must have max_outer = 1."""
 
     @staticmethod
-    def forward(ctx, solver, data, x, v, lam, f_ext, targets, gravity, materials):
+    def forward(ctx, solver, data, x, v, lam, f_ext, targets, gravity, materials, reference=None):
+        _apply_reference(data, reference)
         _apply_inputs(solver, data, f_ext, targets, gravity, materials)
         xn, vn = _np(x).reshape(-1, 3), _np(v).reshape(-1)
         data.UpdatePositions(xn[:, 0], xn[:, 1], xn[:, 2])
@@ -95,6 +129,7 @@ class ImplicitStep(torch.autograd.Function):
         lam1 = solver.RetrieveLambdaToCPU()
         ctx.solver, ctx.data = solver, data
         ctx.inputs = (f_ext, targets, gravity, materials)
+        ctx.reference = reference
         ctx.state = (x1, v1, lam1, vn.copy())
         ctx.shapes = (x.shape, v.shape, lam.shape)
         return (torch.tensor(x1).reshape(x.shape), torch.tensor(v1).reshape(v.shape), torch.tensor(lam1).reshape(lam.shape))
@@ -104,7 +139,9 @@ class ImplicitStep(torch.autograd.Function):
         solver, data = ctx.solver, ctx.data
         f_ext, targets, gravity, materials = ctx.inputs
         x1, v1, lam1, v0 = ctx.state
-        # that step's converged state and inputs again (H depends on x, the materials and the time step alone)
+        # that step's converged state and inputs again (H depends on x, the reference, the materials and the time step)
+        reference = ctx.reference
+        _apply_reference(data, reference)
         _apply_inputs(solver, data, None, None, gravity, materials)
         data.UpdatePositions(x1[:, 0], x1[:, 1], x1[:, 2])
         solver.SetVelocity(v1.reshape(-1), v1.reshape(-1))
@@ -122,25 +159,31 @@ class ImplicitStep(torch.autograd.Function):
         z = lambda k: torch.zeros(k, dtype=torch.float64, device=dev)  # noqa: E731
         outs = [z(3 * N), z(3 * N), z(3 * N), z(nc) if nc else None, z(nc) if nc and want["t"] else None,
                 z(3) if want["a"] else None, z(n_mat * slots) if want["m"] else None, None]
+        want_X = reference is not None and len(ctx.needs_input_grad) > 9 and ctx.needs_input_grad[9]
+        X_bar = z(3 * N) if want_X else None
         torch.cuda.synchronize()
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        solver.AdjointStepDevice(AdjointInC(*[ptr(t) for t in ins]), AdjointOutC(*[ptr(t) for t in outs]))
+        solver.AdjointStepDevice(AdjointInC(*[ptr(t) for t in ins]), AdjointOutC(*[ptr(t) for t in outs]), ptr(X_bar))
         sx, sv, sl = ctx.shapes
         back = lambda t, shape: None if t is None else t.cpu().reshape(shape)  # noqa: E731
         return (None, None, back(outs[2], sx), back(outs[1], sv), back(outs[3], sl) if nc else torch.zeros(sl, dtype=torch.float64),
                 back(outs[0], f_ext.shape) if want["f_ext"] else None,
                 back(outs[4], targets.shape) if want["t"] and nc else None,
                 back(outs[5], gravity.shape) if want["a"] else None,
-                back(outs[6], materials.shape) if want["m"] else None)
+                back(outs[6], materials.shape) if want["m"] else None,
+                back(X_bar, reference.shape) if want_X else None)  # a nine-argument call: torch drops the trailing None
 
 
-def rollout(solver, data, state, n_steps, f_ext=None, targets=None, gravity=None, materials=None):
+def rollout(solver, data, state, n_steps, f_ext=None, targets=None, gravity=None, materials=None, reference=None):
     """n_steps chained ImplicitStep calls from state = (x, v, lam); the inputs are the same tensors in every step (their
-    gradients add up).  -> the final (x, v, lam)."""
+    gradients add up).  A rollout that starts at x_0 = reference gets that path from autograd.  -> the final (x, v, lam)."""
     x, v, lam = state
     for _ in range(int(n_steps)):
-        x, v, lam = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials)
+        if reference is None:
+            x, v, lam = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials)
+        else:
+            x, v, lam = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials, reference)
     return x, v, lam
 
 
-__all__ = ["ImplicitStep", "rollout", "lame_from_E_nu", "E_nu_from_lame", "TlfeaError"]
+__all__ = ["ImplicitStep", "rollout", "straight_sided", "lame_from_E_nu", "E_nu_from_lame", "TlfeaError"]

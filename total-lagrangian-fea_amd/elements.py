@@ -423,6 +423,36 @@ class GPU_FEAT10_Data:
         check(self._lib.tlfea_t10_time_sensitivity_kernels(self._h, int(reps), dp(out)))
         return out
 
+    # -- shape sensitivities and the reference geometry ----------------------------------------------
+    def ShapeSensitivity(self, w, u=None):
+        """The element kernel of the shape adjoint and its gather alone, at the current positions: for an adjoint field w
+        and an acceleration field u [3N or N x 3] (None: no mass term) -> X_bar [N, 3], the cotangent of the reference
+        coordinates of every node."""
+        w = _f64(w).reshape(-1)
+        u = None if u is None else _f64(u).reshape(-1)
+        if w.size != 3 * self.n_coef or (u is not None and u.size != w.size):
+            raise ValueError(f"ShapeSensitivity: w and u need {3 * self.n_coef} entries")
+        out = np.zeros((self.n_coef, 3))
+        check(self._lib.tlfea_t10_shape_sensitivity(self._h, dp(w), dp(u), dp(out)))
+        return out
+
+    def TimeShapeKernels(self, reps=20):
+        """-> mean ms of (element kernel, gather) over `reps` back-to-back launches each."""
+        out = np.zeros(2)
+        check(self._lib.tlfea_t10_time_shape_kernels(self._h, int(reps), dp(out)))
+        return out
+
+    def SetReferencePositions(self, X):
+        """A new reference geometry X [N, 3] for the same connectivity: grad N, det J and an assembled mass matrix follow,
+        as do boundary-face geometry, traction vectors and obstacle surface weights.  Current positions, velocities,
+        multipliers and targets are left alone.  An inverted element is refused and leaves the old geometry in place."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.shape != (self.n_coef, 3):
+            raise ValueError(f"SetReferencePositions: X must be [{self.n_coef}, 3], got {X.shape}")
+        x, y, z = (np.ascontiguousarray(X[:, c]) for c in range(3))
+        check(self._lib.tlfea_t10_set_reference_positions(self._h, dp(x), dp(y), dp(z), int(self.n_coef)))
+        self._X0 = X.copy()
+
     def TimeStressKernels(self, velocity=None, points=False, reps=20):
         """-> mean ms of (point and element kernel, nodal gather, totals) over `reps` back-to-back launches each."""
         ptr, host = self._stress_velocity(velocity)

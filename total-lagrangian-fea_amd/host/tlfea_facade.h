@@ -995,6 +995,17 @@ struct GPU_FEAT10_Data : public ElementBase {
   void UpdateConstraintTargets(const tlfea::VectorXd& x, const tlfea::VectorXd& y, const tlfea::VectorXd& z) {
     TLFEA_SOFT(tlfea_t10_update_constraint_targets(h, x.data(), y.data(), z.data(), x.size()));
   }
+  // A new reference geometry for the same connectivity (no reference counterpart): grad N, det J and an assembled
+  // mass matrix follow; positions, velocities, multipliers and targets are the caller's.  An inverted element is refused.
+  void SetReferencePositions(const tlfea::VectorXd& x, const tlfea::VectorXd& y, const tlfea::VectorXd& z) {
+    TLFEA_HANDLE_ERROR(tlfea_t10_set_reference_positions(h, x.data(), y.data(), z.data(), x.size()));
+  }
+  // The shape adjoint's element kernel and gather alone: w, u [3 n_coef] (u empty: no mass term) -> X_bar [3 n_coef]
+  std::vector<double> ShapeSensitivity(const std::vector<double>& w, const std::vector<double>& u = {}) {
+    std::vector<double> out(w.size(), 0.0);
+    TLFEA_HANDLE_ERROR(tlfea_t10_shape_sensitivity(h, w.data(), u.size() == w.size() ? u.data() : nullptr, out.data()));
+    return out;
+  }
 
   void CalcDnDuPre() { TLFEA_HANDLE_ERROR(tlfea_t10_calc_dndu_pre(h)); }
   void CalcMassMatrix() override { TLFEA_HANDLE_ERROR(tlfea_t10_calc_mass_matrix(h)); }
@@ -1460,13 +1471,14 @@ class SyncedNewtonSolver : public SolverBase {
   // density slot only.  The solver's state is unchanged.
   struct AdjointResult {
     std::vector<double> f_ext, v_prev, x_prev, lam_in, targets, per_material, per_element;
+    std::vector<double> X_bar;  // [3 n_coef] cotangent of the reference coordinates (want_shape)
     double gravity[3] = {0.0, 0.0, 0.0};
     int n_mat = 0, slots = 0, iterations = 0;
     double rel_res = 0.0;
   };
   AdjointResult AdjointStep(const std::vector<double>& xbar, const std::vector<double>& vbar,
                             const std::vector<double>& lambar = {}, bool per_element = false,
-                            const std::vector<double>& v_prev = {}) {
+                            const std::vector<double>& v_prev = {}, bool want_shape = false) {
     const size_t n = 3 * (size_t)n_coef_, nc = (size_t)std::max(0, tlfea_newton_n_constraints(s_));
     AdjointResult r;
     TLFEA_HANDLE_ERROR(tlfea_t10_material_sensitivity_shape(data_, &r.n_mat, &r.slots));
@@ -1479,7 +1491,12 @@ class SyncedNewtonSolver : public SolverBase {
     tlfea_adjoint_out co{r.f_ext.data(), r.v_prev.data(), r.x_prev.data(), nc ? r.lam_in.data() : nullptr,
                          nc ? r.targets.data() : nullptr, r.gravity, r.per_material.data(),
                          per_element ? r.per_element.data() : nullptr};
-    TLFEA_HANDLE_ERROR(tlfea_newton_adjoint_step(s_, &ci, &co, &r.iterations, &r.rel_res));
+    if (want_shape) {
+      r.X_bar.assign(n, 0.0);
+      TLFEA_HANDLE_ERROR(tlfea_newton_adjoint_step_shape(s_, &ci, &co, r.X_bar.data(), &r.iterations, &r.rel_res));
+    } else {
+      TLFEA_HANDLE_ERROR(tlfea_newton_adjoint_step(s_, &ci, &co, &r.iterations, &r.rel_res));
+    }
     return r;
   }
 

@@ -65,6 +65,7 @@ class AdjointResult:
     per_element: object
     iterations: int
     rel_res: float
+    X_bar: object = None    # [N, 3] cotangent of the reference coordinates (AdjointStep(want_shape=True))
 
 
 MODAL_DEFAULT_SHIFT = (2.0 * np.pi * 1.0) ** 2   # (2 pi 1 Hz)^2
@@ -349,12 +350,13 @@ class SyncedNewtonSolver:
         """Raises TlfeaError with the reason when AdjointStep would refuse the solver's state now."""
         check(self._lib.tlfea_newton_adjoint_ready(self._h))
 
-    def AdjointStep(self, xbar=None, vbar=None, lambar=None, per_element=False, v_prev=None):
+    def AdjointStep(self, xbar=None, vbar=None, lambar=None, per_element=False, v_prev=None, want_shape=False):
         """Adjoint of the implicit step just solved (Solve() with max_outer = 1): given the cotangents of its
         outputs x, v [3N or N x 3] and lambda_new [n_constraints] (None = zero), one solve with the step's Hessian gives
         the cotangents of f_ext, v_prev, x_prev, lambda, the constraint targets, the body acceleration and the material
         parameters.  v_prev: the velocity the step started from (default: the one the last Solve() started from); it
-        enters the density slot only.  The solver's state is left as it was."""
+        enters the density slot only.  want_shape adds X_bar [N, 3], the cotangent of the reference coordinates of every
+        node (refused with an obstacle or a face traction set).  The solver's state is left as it was."""
         n, nc = 3 * self.n_coef, int(self._lib.tlfea_newton_n_constraints(self._h))
         self.n_constraints = nc
 
@@ -372,16 +374,26 @@ class SyncedNewtonSolver:
         ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
         cin, cout = AdjointInC(*[ptr(a) for a in ins]), AdjointOutC(*[ptr(a) for a in outs])
         it, rel = C.c_int(), C.c_double()
-        check(self._lib.tlfea_newton_adjoint_step(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
         N = self.n_coef
+        X_bar = np.zeros((N, 3)) if want_shape else None
+        if want_shape:
+            check(self._lib.tlfea_newton_adjoint_step_shape(self._h, C.byref(cin), C.byref(cout), X_bar.ctypes.data,
+                                                            C.byref(it), C.byref(rel)))
+        else:
+            check(self._lib.tlfea_newton_adjoint_step(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
         return AdjointResult(outs[0].reshape(N, 3), outs[1].reshape(N, 3), outs[2].reshape(N, 3), outs[3], outs[4],
-                             outs[5], outs[6], outs[7], it.value, rel.value)
+                             outs[5], outs[6], outs[7], it.value, rel.value, X_bar)
 
-    def AdjointStepDevice(self, cin, cout):
+    def AdjointStepDevice(self, cin, cout, X_bar=None):
         """The same on device pointers (binding.AdjointInC / AdjointOutC filled with device addresses, 0 / None = absent):
-        -> (iterations, rel_res).  differentiable.ImplicitStep calls this with torch tensors."""
+        -> (iterations, rel_res).  X_bar: device address of [3N] doubles for the cotangent of the reference coordinates
+        (None = not wanted).  differentiable.ImplicitStep calls this with torch tensors."""
         it, rel = C.c_int(), C.c_double()
-        check(self._lib.tlfea_newton_adjoint_step_device(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
+        if X_bar is None:
+            check(self._lib.tlfea_newton_adjoint_step_device(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
+        else:
+            check(self._lib.tlfea_newton_adjoint_step_shape_device(self._h, C.byref(cin), C.byref(cout), C.c_void_p(X_bar),
+                                                                   C.byref(it), C.byref(rel)))
         return it.value, rel.value
 
     def ModalApplyBlock(self, X, which=0, apply_mask=False):
