@@ -256,6 +256,35 @@ int tlfea_t10_get_energies(tlfea_t10_t h, double out[5]);
 double *tlfea_t10_nodal_stress_device_ptr(tlfea_t10_t h); /* N*7: sigma, von Mises per node; NULL before calc_stress */
 /* mean ms over reps launches of: the point and element kernel, the nodal gather, the totals (profiling hook) */
 int tlfea_t10_time_stress_kernels(tlfea_t10_t h, const double *d_vel, int want_points, int reps, double *out_ms3);
+/* Recovered stress of T10 objects (no reference counterpart; DESIGN 3f'').  Works from the stored point stresses of the
+ * last tlfea_t10_calc_stress(.., want_points = 1); changes nothing a solver reads and nothing of that stress recovery.
+ *   recovered nodal stress  per element a field linear in the reference coordinates is fitted to the five point values by
+ *                           unweighted least squares and evaluated at the ten nodes; node i takes the V_e-weighted mean of
+ *                           these values over its elements in ascending order; von Mises of that tensor beside it
+ *   principal stresses      of the recovered nodal tensors and of the element mean tensors: values = s1 >= s2 >= s3 |
+ *                           (s1 - s3) / 2; directions = the unit eigenvectors of s1, s2, s3 as rows of a right-handed frame
+ *                           (any orthonormal frame of the eigenspace at a multiple root)
+ *   error indicator         e_q = the recovered field, interpolated with the shape functions, minus the point stress;
+ *                           eta_e^2 = max(0, sum_q dV_q |e_q|^2), n_e^2 = sum_q dV_q |sigma_q|^2 with
+ *                           |s|^2 = dev(s):dev(s) / (2 mu) + tr(s)^2 / (9 K), mu and K the small-strain moduli of the
+ *                           element's material.  get_error_estimate: sum eta_e^2, sum n_e^2,
+ *                           eta_rel = sqrt(eta^2 / (n^2 + eta^2)) (0 when both vanish), elements clamped at 0
+ * want_directions implies want_principal.  recover_stress_from_points runs the same launches on point values given by
+ * the caller (host, E*5*6; needs CalcDnDuPre, no calc_stress).  A retrieve before a recovery is an error, as is asking for
+ * principal values or directions the last recovery did not compute.  Every output is bitwise reproducible.  ANCF handles
+ * are refused. */
+int tlfea_t10_recover_stress(tlfea_t10_t h, int want_principal, int want_directions);
+int tlfea_t10_recover_stress_from_points(tlfea_t10_t h, const double *points /* host, E*5*6 */, int want_principal,
+                                         int want_directions);
+int tlfea_t10_retrieve_recovered_stress(tlfea_t10_t h, double *sigma /*N*6*/, double *von_mises /*N*/); /* either may be NULL */
+int tlfea_t10_retrieve_principal_stress(tlfea_t10_t h, double *nodal_values /*N*4*/, double *nodal_directions /*N*9*/,
+                                        double *element_values /*E*4*/, double *element_directions /*E*9*/); /* any may be NULL */
+int tlfea_t10_retrieve_error_indicator(tlfea_t10_t h, double *eta2 /*E*/, double *n2 /*E*/); /* either may be NULL */
+int tlfea_t10_get_error_estimate(tlfea_t10_t h, double out[4]);
+double *tlfea_t10_recovered_stress_device_ptr(tlfea_t10_t h); /* N*7: sigma*, von Mises per node; NULL before a recovery */
+/* mean ms over reps launches of: the element records, the nodal gather from them, the nodal gather straight from the
+ * point blocks (the form not kept), the principal launches, the error indicator, its totals (profiling hook) */
+int tlfea_t10_time_recovery_kernels(tlfea_t10_t h, int reps, double *out_ms6);
 int tlfea_t10_set_external_force(tlfea_t10_t h, const double *f_ext, int n);   /* :636-646 (n must be 3N) */
 int tlfea_t10_set_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed);    /* FEAT10Data.cu:728-749 */
 int tlfea_t10_update_nodal_fixed(tlfea_t10_t h, const int *fixed_nodes, int n_fixed); /* FEAT10Data.cu:751-832 */

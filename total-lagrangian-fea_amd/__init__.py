@@ -9,7 +9,7 @@ Import with importlib (the directory name carries a hyphen):
     tl = importlib.import_module("total-lagrangian-fea_amd")
 """
 from .binding import (LIB_PATH, TlfeaError, load_library, device_count, exported_symbols)  # noqa: F401
-from .elements import ElementMaterial, GPU_ANCF3243_Data, GPU_ANCF3443_Data, GPU_FEAT10_Data  # noqa: F401
+from .elements import ElementMaterial, GPU_ANCF3243_Data, GPU_ANCF3443_Data, GPU_FEAT10_Data, size_factors  # noqa: F401
 from .solvers import (SyncedNewtonParams, SyncedNewtonSolver, LinSolveOpts, SyncedAdamWNocoopParams,  # noqa: F401
                       SyncedAdamWNocoopSolver, SyncedAdamWSolver, SyncedAdamWParams, SyncedNesterovParams, SyncedNesterovSolver, SyncedVBDParams,
                       SyncedVBDSolver)

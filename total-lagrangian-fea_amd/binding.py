@@ -142,6 +142,23 @@ def _stress_signatures(lib):
         getattr(lib, name).restype = vp
 
 
+def _recovery_signatures(lib):
+    """ctypes signatures of the recovered-stress entry points (DESIGN 3f'')."""
+    vp, i = C.c_void_p, C.c_int
+    sig = {"tlfea_t10_recover_stress": [vp, i, i], "tlfea_t10_recover_stress_from_points": [vp, c_dp, i, i],
+           "tlfea_t10_retrieve_recovered_stress": [vp, c_dp, c_dp],
+           "tlfea_t10_retrieve_principal_stress": [vp, c_dp, c_dp, c_dp, c_dp],
+           "tlfea_t10_retrieve_error_indicator": [vp, c_dp, c_dp], "tlfea_t10_get_error_estimate": [vp, c_dp],
+           "tlfea_t10_time_recovery_kernels": [vp, i, c_dp]}
+    if not hasattr(lib, "tlfea_t10_recover_stress"):
+        return  # an older build loaded through TLFEA_LIB_PATH (A/B runs) lacks these entry points
+    for name, args in sig.items():
+        getattr(lib, name).argtypes = args
+        getattr(lib, name).restype = C.c_int
+    lib.tlfea_t10_recovered_stress_device_ptr.argtypes = [vp]
+    lib.tlfea_t10_recovered_stress_device_ptr.restype = vp
+
+
 def _material_signatures(lib):
     """ctypes signatures of the per-element material entry points."""
     vp, i = C.c_void_p, C.c_int
@@ -298,6 +315,7 @@ def load_library():
     _material_signatures(lib)
     _obstacle_signatures(lib)
     _stress_signatures(lib)
+    _recovery_signatures(lib)
     _load_signatures(lib)
     _modal_signatures(lib)
     _adjoint_signatures(lib)

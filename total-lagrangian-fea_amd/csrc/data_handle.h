@@ -87,6 +87,13 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   bool st_valid = false, st_pts_valid = false;  // a calc_stress has run | its point stresses were asked for
   int *d_st_noff = nullptr, *d_st_nel = nullptr;  // ANCF (DESIGN 3f'): elements of every MESH node, ascending (n_nodes + 1 | E nn)
   bool ancf_mass = false;                         // ANCF: d_mval holds an assembled mass matrix (the kinetic energy's condition)
+  // recovered stress (tlfea_t10_recover_stress, DESIGN 3f''): allocated on first use, read by no solver.  d_rc_rec
+  // [E][kRecoveryRec], d_rc_nodal [N][7], d_rc_err [3][Epad], principal values d_rc_pn [N][4] / d_rc_pe [E][4] and
+  // directions d_rc_dn [N][9] / d_rc_de [E][9]; d_rc_pts [E][5][6] holds the point values of the _from_points hook
+  double *d_rc_rec = nullptr, *d_rc_nodal = nullptr, *d_rc_err = nullptr, *d_rc_part = nullptr, *d_rc_tot = nullptr,
+         *d_rc_pn = nullptr, *d_rc_pe = nullptr, *d_rc_dn = nullptr, *d_rc_de = nullptr, *d_rc_pts = nullptr;
+  double rc_tot[4] = {0, 0, 0, 0};  // eta^2, n^2, eta_rel, clamped elements
+  bool rc_valid = false, rc_principal = false, rc_directions = false;
   // material sensitivities (tlfea_t10_material_sensitivity): allocated on first use.  d_sn_sens [4][Epad],
   // d_sn_out [n_mat][P + 1]; under a table the ascending element list of every material (d_sn_idx [E], concatenated),
   // its chunks (d_sn_blk) and the first chunk of every material (d_sn_boff), rebuilt when `gen` has moved on

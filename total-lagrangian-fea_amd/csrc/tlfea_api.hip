@@ -112,7 +112,8 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts, h->d_ld_fc, h->d_ld_tr, h->d_ld_f,
                   h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask, h->d_ld_fnodes, h->d_ld_foff,
                   h->d_ld_fslot, h->d_fld, h->d_sn_sens, h->d_sn_part, h->d_sn_out, h->d_sn_w, h->d_sn_u, h->d_sn_pe,
-                  h->d_sn_idx, h->d_sn_boff, h->d_sn_blk, h->d_sh_rows, h->d_sh_out};
+                  h->d_sn_idx, h->d_sn_boff, h->d_sn_blk, h->d_sh_rows, h->d_sh_out, h->d_rc_rec, h->d_rc_nodal, h->d_rc_err,
+                  h->d_rc_part, h->d_rc_tot, h->d_rc_pn, h->d_rc_pe, h->d_rc_dn, h->d_rc_de, h->d_rc_pts};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (double* p : h->d_fld_V)

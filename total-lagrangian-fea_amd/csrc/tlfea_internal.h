@@ -592,6 +592,29 @@ constexpr int kStressMaxPart = 1024;
 void launch_stress_totals(hipStream_t s, int E, int Epad, const double* contrib, int N, const Incidence& inc,
                           const double* mval, const double* v, double* partial, double* out5);
 
+// Recovered nodal stress, principal stresses and the ZZ error indicator of T10 objects (tlfea_t10_recover_stress, DESIGN
+// 3f''; stress_recovery_kernels.hip).  No atomics.
+struct RecoveryTable {
+  double T[kNN][kNQ];   // least-squares linear fit of the rule's point values, evaluated at the element's ten nodes
+  double Nq[kNQ][kNN];  // shape functions at the rule's points
+  double qw[kNQ];
+};
+// rec [E][kRecoveryRec] = V_e x the fit at the four vertices (4 x 6) | V_e | 0 | the volume-weighted mean stress (6)
+constexpr int kRecoveryRec = 32;
+void launch_recovery_elem(hipStream_t s, int E, const double* detJ, const RecoveryTable& tb, const double* pts /*[E][5][6]*/,
+                          double* rec);
+// nodal [N][7] = sum_e V_e (T[a(e,i)] . sigma_e) / sum_e V_e over the node's elements in ascending order | its von Mises:
+// from the element records, or (direct) from the point blocks themselves
+void launch_recovery_nodal(hipStream_t s, int N, const Incidence& inc, const double* rec, double* nodal);
+void launch_recovery_nodal_direct(hipStream_t s, int N, const Incidence& inc, const RecoveryTable& tb, const double* pts,
+                                  const double* rec, double* nodal);
+// tensor k = src[k stride + offset ..+6] -> val [n][4] = s1 >= s2 >= s3 | (s1 - s3) / 2, dir (may be null) [n][9] = the unit
+// eigenvectors as rows of a right-handed frame; cyclic Jacobi, a fixed number of sweeps
+void launch_principal(hipStream_t s, int n, const double* src, int stride, int offset, double* val, double* dir);
+// err [3][Epad] = eta_e^2 (clamped at 0) | n_e^2 | 1 where clamped, of the recovered field nodal [N][7] against pts
+void launch_zz_error(hipStream_t s, const ElemView& m, const Material& mat, const double* emat, const RecoveryTable& tb,
+                     const double* pts, const double* nodal, double* err);
+
 // Adjoint sensitivities of the implicit Newton step of T10 objects (tlfea_newton_adjoint_step, DESIGN 3j;
 // adjoint_kernels.hip).  No atomics.
 struct SensShape {

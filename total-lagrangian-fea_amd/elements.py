@@ -32,6 +32,19 @@ class ElementMaterial:
 ElementStress = collections.namedtuple("ElementStress", "sigma von_mises psi J volume")
 NodalStress = collections.namedtuple("NodalStress", "sigma von_mises")
 Energies = collections.namedtuple("Energies", "strain kinetic viscous_power reference_volume current_volume")
+PrincipalStress = collections.namedtuple(
+    "PrincipalStress", "nodal_values nodal_tau_max nodal_directions element_values element_tau_max element_directions")
+ErrorEstimate = collections.namedtuple("ErrorEstimate", "eta2 n2 eta_rel clamped")
+
+
+def size_factors(eta2, n2, target_rel):
+    """Element size factors for a target relative error from the retrieved indicator arrays (numpy only):
+    clip(sqrt(target_rel sqrt((n^2 + eta^2) / E) / eta_e), 0.25, 4), the totals summed in element order."""
+    eta2, n2 = np.asarray(eta2, dtype=np.float64), np.asarray(n2, dtype=np.float64)
+    allowed = target_rel * np.sqrt((n2.sum() + eta2.sum()) / eta2.size)   # the error every element may carry
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.sqrt(allowed / np.sqrt(eta2))
+    return np.clip(np.where(np.isnan(f), 4.0, f), 0.25, 4.0)
 
 
 def _f64(a):
@@ -395,6 +408,60 @@ class GPU_FEAT10_Data:
 
     def GetNodalStressDevicePtr(self):
         return self._lib.tlfea_t10_nodal_stress_device_ptr(self._h)
+
+    # -- recovered stress, principal stresses, ZZ error indicator (DESIGN 3f'') ----------------------------------
+    def RecoverStress(self, principal=True, directions=False):
+        """Extrapolated nodal stress, principal stresses and the ZZ error indicator from the point stresses of the last
+        CalcStress(points=True).  `directions` also keeps the principal directions (and implies `principal`)."""
+        check(self._lib.tlfea_t10_recover_stress(self._h, int(bool(principal)), int(bool(directions))))
+
+    def RecoverStressFromPoints(self, points, principal=True, directions=False):
+        """The same launches on point stresses [E][5][6] given by the caller (needs CalcDnDuPre, no CalcStress)."""
+        p = _f64(points)
+        if p.size != self.n_elem * 30:
+            raise ValueError(f"RecoverStressFromPoints: the point stresses need {self.n_elem * 30} entries, got {p.size}")
+        check(self._lib.tlfea_t10_recover_stress_from_points(self._h, dp(p), int(bool(principal)), int(bool(directions))))
+
+    def RetrieveRecoveredStressToCPU(self):
+        """Recovered nodal stress [N][6] and the von Mises stress of that tensor [N]."""
+        s, vm = np.zeros((self.n_coef, 6)), np.zeros(self.n_coef)
+        check(self._lib.tlfea_t10_retrieve_recovered_stress(self._h, dp(s), dp(vm)))
+        return NodalStress(s, vm)
+
+    def RetrievePrincipalStressToCPU(self, directions=False):
+        """Principal stresses of the recovered nodal tensors and of the element mean tensors: values [.][3] descending,
+        tau_max = (s1 - s3) / 2 and, with `directions`, the unit eigenvectors [.][3][3] as rows of a right-handed frame
+        (else None)."""
+        N, E = self.n_coef, self.n_elem
+        vn, ve = np.zeros((N, 4)), np.zeros((E, 4))
+        dn, de = (np.zeros((N, 3, 3)), np.zeros((E, 3, 3))) if directions else (None, None)
+        check(self._lib.tlfea_t10_retrieve_principal_stress(self._h, dp(vn), dp(dn), dp(ve), dp(de)))
+        return PrincipalStress(vn[:, :3].copy(), vn[:, 3].copy(), dn, ve[:, :3].copy(), ve[:, 3].copy(), de)
+
+    def RetrieveErrorIndicatorToCPU(self):
+        """(eta_e^2 [E], n_e^2 [E]) of the ZZ error indicator."""
+        eta2, n2 = np.zeros(self.n_elem), np.zeros(self.n_elem)
+        check(self._lib.tlfea_t10_retrieve_error_indicator(self._h, dp(eta2), dp(n2)))
+        return eta2, n2
+
+    def GetErrorEstimate(self):
+        out = np.zeros(4)
+        check(self._lib.tlfea_t10_get_error_estimate(self._h, dp(out)))
+        return ErrorEstimate(out[0], out[1], out[2], int(out[3]))
+
+    def size_factors(self, target_rel):
+        """Element size factors [E] for a target relative error, from the retrieved indicator (module size_factors)."""
+        return size_factors(*self.RetrieveErrorIndicatorToCPU(), target_rel)
+
+    def GetRecoveredStressDevicePtr(self):
+        return self._lib.tlfea_t10_recovered_stress_device_ptr(self._h)
+
+    def TimeRecoveryKernels(self, reps=20):
+        """-> mean ms of (element records, nodal gather, nodal gather straight from the point blocks, principal
+        stresses, error indicator, totals) over `reps` back-to-back launches each."""
+        out = np.zeros(6)
+        check(self._lib.tlfea_t10_time_recovery_kernels(self._h, int(reps), dp(out)))
+        return out
 
     # -- material sensitivities (DESIGN 3j) ------------------------------------------------------------------
     def MaterialSensitivityShape(self):

@@ -879,6 +879,75 @@ struct GPU_FEAT10_Data : public ElementBase {
     return Energies{o[0], o[1], o[2], o[3], o[4]};
   }
   double* GetNodalStressDevicePtr() { return tlfea_t10_nodal_stress_device_ptr(h); }
+  // recovered stress (DESIGN 3f''; no reference counterpart): extrapolated nodal stress, principal stresses and the ZZ error
+  // indicator from the point stresses of the last CalcStress(.., points = true).  Status 0 = done.
+  int RecoverStress(bool principal = true, bool directions = false) {
+    return tlfea_t10_recover_stress(h, principal ? 1 : 0, directions ? 1 : 0);
+  }
+  // the same launches on point stresses given by the caller, [e][q][6] flattened (E * 30 values)
+  int RecoverStressFromPoints(const std::vector<double>& points, bool principal = true, bool directions = false) {
+    return tlfea_t10_recover_stress_from_points(h, points.size() == static_cast<size_t>(n_elem) * 30 ? points.data() : nullptr,
+                                                principal ? 1 : 0, directions ? 1 : 0);
+  }
+  // sigma: N x 6 recovered nodal stress, von_mises: N (of that tensor)
+  void RetrieveRecoveredStressToCPU(tlfea::MatrixXd& sigma, tlfea::VectorXd& von_mises) {
+    std::vector<double> flat(static_cast<size_t>(n_coef) * 6);
+    von_mises.resize(n_coef);
+    TLFEA_HANDLE_ERROR(tlfea_t10_retrieve_recovered_stress(h, flat.data(), von_mises.data()));
+    sigma.resize(n_coef, 6);
+    for (int i = 0; i < n_coef; i++)
+      for (int c = 0; c < 6; c++) sigma(i, c) = flat[static_cast<size_t>(i) * 6 + c];
+  }
+  // values: rows of s1 >= s2 >= s3 | (s1 - s3) / 2, N x 4 nodal and E x 4 element; directions (null: not wanted): rows of
+  // the 3 x 3 right-handed frame flattened, N x 9 and E x 9
+  void RetrievePrincipalStressToCPU(tlfea::MatrixXd& nodal_values, tlfea::MatrixXd& element_values,
+                                    tlfea::MatrixXd* nodal_directions = nullptr,
+                                    tlfea::MatrixXd* element_directions = nullptr) {
+    std::vector<double> vn(static_cast<size_t>(n_coef) * 4), ve(static_cast<size_t>(n_elem) * 4), dn, de;
+    if (nodal_directions) dn.resize(static_cast<size_t>(n_coef) * 9);
+    if (element_directions) de.resize(static_cast<size_t>(n_elem) * 9);
+    TLFEA_HANDLE_ERROR(tlfea_t10_retrieve_principal_stress(h, vn.data(), nodal_directions ? dn.data() : nullptr, ve.data(),
+                                                           element_directions ? de.data() : nullptr));
+    auto fill = [](tlfea::MatrixXd& m, const std::vector<double>& flat, int rows, int cols) {
+      m.resize(rows, cols);
+      for (int i = 0; i < rows; i++)
+        for (int c = 0; c < cols; c++) m(i, c) = flat[static_cast<size_t>(i) * cols + c];
+    };
+    fill(nodal_values, vn, n_coef, 4);
+    fill(element_values, ve, n_elem, 4);
+    if (nodal_directions) fill(*nodal_directions, dn, n_coef, 9);
+    if (element_directions) fill(*element_directions, de, n_elem, 9);
+  }
+  void RetrieveErrorIndicatorToCPU(tlfea::VectorXd& eta2, tlfea::VectorXd& n2) {
+    eta2.resize(n_elem);
+    n2.resize(n_elem);
+    TLFEA_HANDLE_ERROR(tlfea_t10_retrieve_error_indicator(h, eta2.data(), n2.data()));
+  }
+  struct ErrorEstimate {
+    double eta2, n2, eta_rel;
+    int clamped;
+  };
+  ErrorEstimate GetErrorEstimate() {
+    double o[4];
+    TLFEA_HANDLE_ERROR(tlfea_t10_get_error_estimate(h, o));
+    return ErrorEstimate{o[0], o[1], o[2], static_cast<int>(o[3])};
+  }
+  // element size factors for a target relative error: clip(sqrt(target_rel sqrt((n^2 + eta^2) / E) / eta_e), 0.25, 4)
+  std::vector<double> SizeFactors(double target_rel) {
+    tlfea::VectorXd eta2, n2;
+    RetrieveErrorIndicatorToCPU(eta2, n2);
+    double se = 0.0, sn = 0.0;
+    for (int e = 0; e < n_elem; e++) se += eta2(e), sn += n2(e);
+    const double allowed = target_rel * std::sqrt((sn + se) / n_elem);
+    std::vector<double> f(n_elem);
+    for (int e = 0; e < n_elem; e++) {
+      const double eta = std::sqrt(eta2(e));
+      const double r = eta > 0.0 ? std::sqrt(allowed / eta) : 4.0;
+      f[e] = std::min(4.0, std::max(0.25, r));
+    }
+    return f;
+  }
+  double* GetRecoveredStressDevicePtr() { return tlfea_t10_recovered_stress_device_ptr(h); }
   // distributed loads (no reference counterpart): beside f_ext, not in it.  SetGravity: the load M a on the
   // position coefficients, from the mass matrix on the device (after CalcMassMatrix).  Status 0 = accepted.
   int SetGravity(double ax, double ay, double az) {

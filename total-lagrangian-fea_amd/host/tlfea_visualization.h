@@ -30,6 +30,7 @@ struct VisualizationUtils {
     std::vector<int> cells;
     int arity, vtk_type;
     std::vector<PointField> fields;
+    std::vector<PointField> cell_fields = {};  // one tuple per cell (<CellData>)
   };
   static bool WriteVTU(const std::string& filename, const std::vector<P3>& points, const std::vector<int>& cells,
                        int arity, int vtk_type, const std::vector<PointField>& fields = {}) {
@@ -57,12 +58,13 @@ struct VisualizationUtils {
       }
       file << "    </FieldData>\n";
     }
-    for (const Piece& p : pieces) write_piece(file, p.points, p.cells, p.arity, p.vtk_type, p.fields);
+    for (const Piece& p : pieces) write_piece(file, p.points, p.cells, p.arity, p.vtk_type, p.fields, p.cell_fields);
     file << "  </UnstructuredGrid>\n</VTKFile>\n";
     return static_cast<bool>(file);
   }
   static void write_piece(std::ofstream& file, const std::vector<P3>& points, const std::vector<int>& cells, int arity,
-                          int vtk_type, const std::vector<PointField>& fields) {
+                          int vtk_type, const std::vector<PointField>& fields,
+                          const std::vector<PointField>& cell_fields = {}) {
     const size_t n_cells = arity ? cells.size() / arity : 0;
     file << "    <Piece NumberOfPoints=\"" << points.size() << "\" NumberOfCells=\"" << n_cells << "\">\n"
          << "      <Points>\n"
@@ -97,6 +99,24 @@ struct VisualizationUtils {
         file << "        </DataArray>\n";
       }
       file << "      </PointData>\n";
+    }
+    if (!cell_fields.empty()) {
+      file << "      <CellData>\n";
+      for (const PointField& f : cell_fields) {
+        file << "        <DataArray type=\"Float64\" Name=\"" << f.name << "\"";
+        if (f.components > 1) file << " NumberOfComponents=\"" << f.components << "\"";
+        file << " format=\"ascii\">\n";
+        for (size_t i = 0; i < n_cells; i++) {
+          file << "         ";
+          for (int c = 0; c < f.components; c++) {
+            const size_t k = i * f.components + c;
+            file << " " << (k < f.values.size() ? f.values[k] : 0.0);
+          }
+          file << "\n";
+        }
+        file << "        </DataArray>\n";
+      }
+      file << "      </CellData>\n";
     }
     file << "      <Cells>\n        <DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";
     for (size_t c = 0; c < n_cells; c++) {
@@ -164,6 +184,34 @@ struct VisualizationUtils {
       if (i < nodal_von_mises.size()) m.values[i] = nodal_von_mises(i);
     }
     return WriteVTU(filename, pts, corner_tets(elements), 4, 10, {m, d, s});
+  }
+
+  // T10 mesh at `nodes` + point data "stress" (6), "von_mises" (1) and "principal" (3: s1 s2 s3) of the recovered nodal
+  // field and cell data "eta" (1: the element's ZZ error indicator eta_e), as GPU_FEAT10_Data::RetrieveRecoveredStressToCPU,
+  // RetrievePrincipalStressToCPU (N x 4 values) and RetrieveErrorIndicatorToCPU (eta_e^2) return them (no reference
+  // counterpart)
+  static bool ExportMeshWithRecoveredStress(const tlfea::MatrixXd& nodes, const tlfea::MatrixXi& elements,
+                                            const tlfea::MatrixXd& nodal_sigma6, const tlfea::VectorXd& nodal_von_mises,
+                                            const tlfea::MatrixXd& nodal_principal, const tlfea::VectorXd& eta2,
+                                            const std::string& filename) {
+    const int n = nodes.rows(), E = elements.rows();
+    if (nodal_sigma6.rows() != n || nodal_sigma6.cols() != 6 || nodal_von_mises.size() != n || nodal_principal.rows() != n ||
+        nodal_principal.cols() < 3 || eta2.size() != E) {
+      std::cerr << "ExportMeshWithRecoveredStress: N x 6 stresses, N von Mises values, N x 3 (or 4) principal values and E "
+                   "indicator values expected" << std::endl;
+      return false;
+    }
+    std::vector<P3> pts(n);
+    PointField s{"stress", 6, std::vector<double>(6 * (size_t)n)}, m{"von_mises", 1, std::vector<double>(n)},
+        p{"principal", 3, std::vector<double>(3 * (size_t)n)}, eta{"eta", 1, std::vector<double>(E)};
+    for (int i = 0; i < n; i++) {
+      pts[i] = {nodes(i, 0), nodes(i, 1), nodes(i, 2)};
+      for (int c = 0; c < 6; c++) s.values[6 * (size_t)i + c] = nodal_sigma6(i, c);
+      for (int c = 0; c < 3; c++) p.values[3 * (size_t)i + c] = nodal_principal(i, c);
+      m.values[i] = nodal_von_mises(i);
+    }
+    for (int e = 0; e < E; e++) eta.values[e] = std::sqrt(std::max(0.0, eta2(e)));
+    return WriteVTU(filename, std::vector<Piece>{Piece{pts, corner_tets(elements), 4, 10, {m, p, s}, {eta}}});
   }
 
   // One hexahedron per shell: the four corner positions (coefficient slot 0 of each node) pushed -/+ thickness/2 along
