@@ -403,9 +403,21 @@ int tlfea_newton_get_linsolve_info(tlfea_newton_t s, int *cheb_degree, int *cheb
 /* preconditioner a solve would use now: 0 block-Jacobi, 1 Chebyshev polynomial, 2 p-multigrid */
 int tlfea_newton_get_precond(tlfea_newton_t s);
 /* how compute_hessian_assemble_csr (FEAT10DataFunc.cuh:513-791) + the CSR scatter (SyncedNewton.cu:214-341) run now:
- * 1 = tangent blocks into an element-major buffer + row-owner gather (two launches; Mooney-Rivlin, ANCF kinds),
- * 2 = fused row-owner tangent + assembly (one launch, no block buffer; T10 with St.Venant-Kirchhoff) */
+ * 1 = tangent blocks into an element-major buffer + row-owner gather (two launches; the ANCF kinds, TLFEA_ASSEMBLE=kbuf,
+ *     meshes whose row groups do not fit the fused forms),
+ * 2 = fused row-owner tangent + assembly, general form (one launch, no block buffer; T10 with curved elements or
+ *     Mooney-Rivlin, TLFEA_ASSEMBLE=general),
+ * 3 = fused row-owner tangent + assembly, affine-element form (T10, straight-sided elements, St.Venant-Kirchhoff) */
 int tlfea_newton_get_assembly_mode(tlfea_newton_t s);
+/* the launch an assembly would issue now (test hook), out8 = mode as above | 1 rolled kernel, 0 unrolled (general form;
+ * 1 elsewhere) | wavefronts per workgroup of the tangent-block launch (mode 1; 0 in the fused modes) | row groups G (mode
+ * 1: node rows) | doubles of LDS accumulator of the largest group (mode 1: of the longest row) | dynamic LDS bytes of the
+ * assembly launch | workgroups it launches | entries of the pass table (mode 1: 1).  Runs the sparsity analysis if needed. */
+int tlfea_newton_get_assembly_form(tlfea_newton_t s, int *out8);
+/* how grad L gets its inertia term now (test hook): 1 = the mass CSR product with gathered velocities inside grad_kernel
+ * (the ANCF kinds, TLFEA_MASS=csr), 2 = element inertia rows written by the residual launch and summed by
+ * grad_light_kernel (T10 default) */
+int tlfea_newton_get_gradient_form(tlfea_newton_t s);
 /* degree of the coarse-level polynomial of the p-multigrid cycle (grows with the coarse mesh); 0 without p-multigrid */
 /* third level of the cycle (rigid-body-mode aggregates of the vertex level; opt-in, TLFEA_PMG_LEVELS=3): number of
  * aggregates (0: two levels), 3x3 blocks of H3 (2 nodes per aggregate: translation, rotation), polynomial degree there;

@@ -42,7 +42,7 @@ def test_library_exports_every_declared_symbol():
     assert lib.tlfea_version() >= 100
     # the read-back hooks tests assert kernel regimes through are part of the declared surface
     for hook in ("tlfea_newton_get_c32_geometry", "tlfea_newton_get_direct_info", "tlfea_newton_get_direct_fronts",
-                 "tlfea_newton_cg_trace"):
+                 "tlfea_newton_cg_trace", "tlfea_newton_get_assembly_form"):
         assert hook in syms and hasattr(lib, hook), hook
 
 

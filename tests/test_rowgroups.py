@@ -47,12 +47,21 @@ def dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-@pytest.mark.parametrize("mesh", ["res2", "bunny", "box"])
-def test_row_groups_invariants(shim, mesh):
+EDGE_MESHES = ["star2", "star3", "isolated_box"]   # tests/edge_meshes.py: a hub row of 325 / 1 285 blocks, nodes of no element
+
+
+def mesh_by_name(mesh):
     if mesh == "box":
-        X, conn = mu.structured_t10_box(5, 4, 3, 2.5, 2.0, 1.5)
-    else:
-        X, conn = load_mesh(mesh)
+        return mu.structured_t10_box(5, 4, 3, 2.5, 2.0, 1.5)
+    if mesh in EDGE_MESHES:
+        from tests import edge_meshes
+        return edge_meshes.build(mesh)
+    return load_mesh(mesh)
+
+
+@pytest.mark.parametrize("mesh", ["res2", "bunny", "box"] + EDGE_MESHES)
+def test_row_groups_invariants(shim, mesh):
+    X, conn = mesh_by_name(mesh)
     conn = np.ascontiguousarray(conn, dtype=np.int32)
     N, (E, S) = X.shape[0], conn.shape
     off, cols, n2e_off, n2e = adjacency(conn, N)
@@ -133,15 +142,12 @@ def test_row_groups_invariants(shim, mesh):
     assert np.median(hop) < 0.35 * np.linalg.norm(X.max(0) - X.min(0))
 
 
-@pytest.mark.parametrize("mesh", ["res2", "bunny", "box"])
+@pytest.mark.parametrize("mesh", ["res2", "bunny", "box"] + EDGE_MESHES)
 def test_row_groups_affine_form(shim, mesh):
     """Work lists of the affine-element kernel (build_row_groups4): rows and instances owned once, the header and the
     sixteen 16-bit block offsets of every instance -- entry (n, p) is the column of vertex n (p == n) or of the mid-edge
     node of (n, p) --, passes of at most 16 instances that walk every group once."""
-    if mesh == "box":
-        X, conn = mu.structured_t10_box(5, 4, 3, 2.5, 2.0, 1.5)
-    else:
-        X, conn = load_mesh(mesh)
+    X, conn = mesh_by_name(mesh)
     conn = np.ascontiguousarray(conn, dtype=np.int32)
     N, (E, S) = X.shape[0], conn.shape
     off, cols, n2e_off, n2e = adjacency(conn, N)

@@ -231,6 +231,9 @@ def _pmg_signatures(lib):
     for name, args in sig.items():
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "tlfea_newton_get_assembly_form"):  # (as below: an older build lacks it)
+        lib.tlfea_newton_get_assembly_form.argtypes = [vp, c_ip]
+        lib.tlfea_newton_get_assembly_form.restype = C.c_int
     if hasattr(lib, "tlfea_newton_get_lambda_max"):  # an older build loaded through TLFEA_LIB_PATH (A/B runs) lacks it
         lib.tlfea_newton_get_lambda_max.argtypes = [vp, c_dp]
         lib.tlfea_newton_get_lambda_max.restype = C.c_int

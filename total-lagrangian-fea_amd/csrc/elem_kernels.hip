@@ -984,9 +984,15 @@ __global__ __launch_bounds__(64 * WPB, (S == 16 && MODEL == kSVK && WPB == 1) ? 
     for (int t = lane; t < P * 9; t += 64) out[t] = lds[t];
 }
 
+static int tangent_wpb_env() {
+  static const int wpb = std::getenv("TLFEA_TANGENT_WPB") ? std::atoi(std::getenv("TLFEA_TANGENT_WPB")) : 1;
+  return wpb;
+}
+int tangent_blocks_wpb(bool per_element) { return (!per_element && tangent_wpb_env() == 4) ? 4 : 1; }
+
 template <int S, int Q, int QC>
 static void launch_tangent_t(hipStream_t s, const ElemView& m, const Material& mat, double h, double* Kbuf) {
-  static const int wpb = std::getenv("TLFEA_TANGENT_WPB") ? std::atoi(std::getenv("TLFEA_TANGENT_WPB")) : 1;
+  const int wpb = tangent_wpb_env();
   if (wpb == 4) {
     const dim3 g((m.E + 3) / 4), b(256);
     if (mat.model == kMooneyRivlin)
@@ -1044,7 +1050,7 @@ __global__ __launch_bounds__(64) void assemble_rows_kernel(int N, Incidence inc,
   }
   __syncthreads();
   // h^2 rho J^T J: one 1.0 per pinned DOF (SyncedNewton.cu:292-341, FEAT10Data.cu:443-459)
-  if (lane < 3 && fixed_slot && fixed_slot[i] >= 0)
+  if (lane < 3 && deg > 0 && fixed_slot && fixed_slot[i] >= 0)  // (a node of no element has an empty row, pinned or not)
     acc[lane * row + 3 * inc.diagpos[i] + lane] += (nw ? nw[i] : 1.0) * penalty;
   __syncthreads();
   // The node's incident elements, ascending (fixed summation order).  A row is a chain of dependent memory
@@ -1097,10 +1103,30 @@ __global__ __launch_bounds__(64) void assemble_rows_kernel(int N, Incidence inc,
   for (int t = lane; t < n9; t += 64) out[t] = acc[t];
 }
 
+size_t assemble_rows_lds(int maxdeg) { return (size_t)9 * maxdeg * sizeof(double); }
+size_t device_lds_limit() {
+  static size_t limit = ~(size_t)0;
+  if (limit == ~(size_t)0) {
+    int dev = 0, v = 0;
+    limit = (hipGetDevice(&dev) == hipSuccess &&
+             hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0)
+                ? (size_t)v
+                : (size_t)64 * 1024;  // no answer: what every launch may have without asking
+  }
+  return limit;
+}
+
 void launch_assemble_rows(hipStream_t s, int N, int S, int maxdeg, const Incidence& inc, const double* Kbuf,
                           const double* mval, double inv_h, const int* fixed_slot, const double* nw, double penalty,
                           double* Hval) {
-  const size_t lds = (size_t)9 * maxdeg * sizeof(double);
+  const size_t lds = assemble_rows_lds(maxdeg);
+  static size_t lds_attr = 0;
+  if (lds > 64 * 1024 && lds > lds_attr) {  // as the fused launchers: more than the default 64 KiB is asked for by attribute
+    for (const void* f : {(const void*)assemble_rows_kernel<10>, (const void*)assemble_rows_kernel<8>,
+                          (const void*)assemble_rows_kernel<16>})
+      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    lds_attr = lds;
+  }
   if (S == 10)
     hipLaunchKernelGGL((assemble_rows_kernel<10>), dim3(N), dim3(64), lds, s, N, inc, Kbuf, mval, inv_h, fixed_slot, nw,
                        penalty, Hval);
@@ -1453,7 +1479,7 @@ __global__ __launch_bounds__(64, (ROLLED && !MR) ? 3 : 2) void assemble_direct_k
     // ---- (6) last pass of a group: h^2 rho J^T J on pinned rows (SyncedNewton.cu:292-341), rows stream out once ----
     if (last) {
       wave_sync();
-      if (lane < nrows && pen != 0.0) {
+      if (lane < nrows && pen != 0.0 && ri.z > 0) {  // (a pinned node of no element has no diagonal block: an empty row)
         const int a0 = ri.x & 0xffff, dpos = ri.x >> 16, row = 3 * ri.z;
 #pragma unroll
         for (int d = 0; d < 3; d++) acc[a0 + d * row + 3 * dpos + d] += pen;
@@ -1476,27 +1502,53 @@ __global__ __launch_bounds__(64, (ROLLED && !MR) ? 3 : 2) void assemble_direct_k
   }
 }
 
-void launch_assemble_direct(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups& rg,
-                            const double* Fq, const double* mval, const int* fixed_slot, const double* nw,
-                            double penalty, double* Hval, const double* emat) {
-  if (emat) {
+static int device_cu_count() {
+  static int n_cu = 0;
+  if (!n_cu) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (n_cu <= 0) n_cu = 256;
+  }
+  return n_cu;
+}
+size_t assemble_direct_lds_max(int acc_max) {  // the Mooney-Rivlin records are the largest
+  return (size_t)(kAdInst * kNQ * kAdRecMR + kAdHraw + acc_max) * sizeof(double);
+}
+// experiment switches: TLFEA_AD_ROLLED=0|1 kernel form, TLFEA_AD_WAVES resident waves per CU assumed
+// by the persistent grid; TLFEA_AD_TUNE=1 re-reads them at every launch (tools/tune_assemble.py)
+namespace {
+struct AdSwitches {
+  bool tune;
+  int rolled, occ_env, store_mode;
+};
+}  // namespace
+static AdSwitches ad_switches() {
+  auto read = [] {
+    return AdSwitches{std::getenv("TLFEA_AD_TUNE") != nullptr,
+                      std::getenv("TLFEA_AD_ROLLED") ? std::atoi(std::getenv("TLFEA_AD_ROLLED")) : 1,
+                      std::getenv("TLFEA_AD_WAVES") ? std::atoi(std::getenv("TLFEA_AD_WAVES")) : 0,
+                      std::getenv("TLFEA_AD_STORE") ? std::atoi(std::getenv("TLFEA_AD_STORE")) : 0};
+  };
+  static AdSwitches sw = read();
+  if (sw.tune) sw = read();
+  return sw;
+}
+// LDS, grid and kernel form of the general form's launch for these work lists and this material.  Persistent grid: as many
+// single-wave workgroups as the chip holds at once (8 XCDs x 32 CUs x resident waves per CU), never more than there are
+// groups; a wave that starts late (fewer resident than assumed) still does its share.
+AssemblyLaunchForm assemble_direct_form(const RowGroups& rg, const Material& mat, bool per_element) {
+  const bool mr = mat.model == kMooneyRivlin;
+  const size_t lds = (size_t)((mr ? kAdInst * kNQ * kAdRecMR : kAdRecTotal) + kAdHraw + rg.acc_max) * sizeof(double);
+  const int n_cu = device_cu_count();
+  if (per_element) {
     // per-element materials: the default forms (rolled SVK, Mooney-Rivlin) with the records; no tuning knobs
-    const MaterialPE pe{mat, emat};
-    const bool mr = mat.model == kMooneyRivlin;
-    const size_t lds = (size_t)((mr ? kAdInst * kNQ * kAdRecMR : kAdRecTotal) + kAdHraw + rg.acc_max) * sizeof(double);
     const void* fn = mr ? (const void*)assemble_direct_kernel<1, 0, 1, MaterialPE>
                         : (const void*)assemble_direct_kernel<1, 0, 0, MaterialPE>;
     static size_t lds_attr_pe[2] = {0, 0};
     if (lds > 64 * 1024 && lds > lds_attr_pe[mr]) {
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       lds_attr_pe[mr] = lds;
-    }
-    static int n_cu_pe = 0;
-    if (!n_cu_pe) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&n_cu_pe, hipDeviceAttributeMultiprocessorCount, dev);
-      if (n_cu_pe <= 0) n_cu_pe = 256;
     }
     static size_t occ_lds_pe[2] = {~(size_t)0, ~(size_t)0};
     static int occ_pe[2] = {4, 4};
@@ -1505,43 +1557,27 @@ void launch_assemble_direct(hipStream_t s, const ElemView& m, const Material& ma
       occ_pe[mr] = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, 64, lds) == hipSuccess && o > 0) ? o : 4;
       occ_lds_pe[mr] = lds;
     }
-    const int per_xcd = std::max(1, std::min((n_cu_pe / 8) * std::min(occ_pe[mr], mr ? 8 : 12), (rg.G + 7) / 8));
-    if (mr)
-      hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 1, MaterialPE>), dim3(8 * per_xcd), dim3(64), lds, s, m, pe, h, rg, Fq,
-                         mval, 1.0 / h, fixed_slot, nw, penalty, Hval, 0);
-    else
-      hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 0, MaterialPE>), dim3(8 * per_xcd), dim3(64), lds, s, m, pe, h, rg, Fq,
-                         mval, 1.0 / h, fixed_slot, nw, penalty, Hval, 0);
-    return;
+    const int per_xcd = std::max(1, std::min((n_cu / 8) * std::min(occ_pe[mr], mr ? 8 : 12), (rg.G + 7) / 8));
+    return AssemblyLaunchForm{lds, 8 * per_xcd, 1};
   }
-  if (mat.model == kMooneyRivlin) {
+  if (mr) {
     // Mooney-Rivlin: the same walk with 60-double records (assemble_direct_kernel<1, 0, 1>); one form, no tuning knobs
-    const size_t lds = (size_t)(kAdInst * kNQ * kAdRecMR + kAdHraw + rg.acc_max) * sizeof(double);
     const void* fn = (const void*)assemble_direct_kernel<1, 0, 1>;
     static size_t lds_attr_mr = 0;
     if (lds > 64 * 1024 && lds > lds_attr_mr) {
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       lds_attr_mr = lds;
     }
-    static int n_cu_mr = 0, occ_mr = 0;
+    static int occ_mr = 0;
     static size_t occ_lds_mr = ~(size_t)0;
-    if (!n_cu_mr) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&n_cu_mr, hipDeviceAttributeMultiprocessorCount, dev);
-      if (n_cu_mr <= 0) n_cu_mr = 256;
-    }
     if (occ_lds_mr != lds) {
       int o = 0;
       occ_mr = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, 64, lds) == hipSuccess && o > 0) ? o : 4;
       occ_lds_mr = lds;
     }
-    const int per_xcd = std::max(1, std::min((n_cu_mr / 8) * std::min(occ_mr, 8), (rg.G + 7) / 8));
-    hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 1>), dim3(8 * per_xcd), dim3(64), lds, s, m, mat, h, rg, Fq, mval, 1.0 / h,
-                       fixed_slot, nw, penalty, Hval, 0);
-    return;
+    const int per_xcd = std::max(1, std::min((n_cu / 8) * std::min(occ_mr, 8), (rg.G + 7) / 8));
+    return AssemblyLaunchForm{lds, 8 * per_xcd, 1};
   }
-  const size_t lds = (size_t)(kAdRecTotal + kAdHraw + rg.acc_max) * sizeof(double);
   static size_t lds_attr = 0;
   if (lds > 64 * 1024 && lds > lds_attr) {
     for (const void* f : {(const void*)assemble_direct_kernel<1, 0>, (const void*)assemble_direct_kernel<0, 0>,
@@ -1549,46 +1585,53 @@ void launch_assemble_direct(hipStream_t s, const ElemView& m, const Material& ma
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_attr = lds;
   }
-  // persistent grid: as many single-wave workgroups as the chip holds at once (8 XCDs x 32 CUs x resident waves per CU),
-  // never more than there are groups; a wave that starts late (fewer resident than assumed) still does its share
-  static int n_cu = 0;
   static size_t occ_lds = ~(size_t)0;
   static int occ = 8;
-  if (!n_cu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (n_cu <= 0) n_cu = 256;
-  }
   if (occ_lds != lds) {
     int o = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)assemble_direct_kernel<1, 0>, 64, lds) == hipSuccess && o > 0)
       occ = o;
     occ_lds = lds;
   }
-  // experiment switches: TLFEA_AD_ROLLED=0|1 kernel form, TLFEA_AD_WAVES resident waves per CU assumed
-  // by the persistent grid; TLFEA_AD_TUNE=1 re-reads both at every launch (tools/tune_assemble.py)
-  static const bool tune = std::getenv("TLFEA_AD_TUNE") != nullptr;
-  static int rolled = std::getenv("TLFEA_AD_ROLLED") ? std::atoi(std::getenv("TLFEA_AD_ROLLED")) : 1;
-  static int occ_env = std::getenv("TLFEA_AD_WAVES") ? std::atoi(std::getenv("TLFEA_AD_WAVES")) : 0;
-  static int store_mode = std::getenv("TLFEA_AD_STORE") ? std::atoi(std::getenv("TLFEA_AD_STORE")) : 0;
-  if (tune) {
-    store_mode = std::getenv("TLFEA_AD_STORE") ? std::atoi(std::getenv("TLFEA_AD_STORE")) : 0;
-    rolled = std::getenv("TLFEA_AD_ROLLED") ? std::atoi(std::getenv("TLFEA_AD_ROLLED")) : 1;
-    occ_env = std::getenv("TLFEA_AD_WAVES") ? std::atoi(std::getenv("TLFEA_AD_WAVES")) : 0;
-  }
+  const AdSwitches sw = ad_switches();
   // measured at config C (tools/tune_assemble.py): every resident slot of the rolled form (12 per CU: 168 VGPRs, 12 KiB of
   // LDS), 8 of the unrolled one; more workgroups than fit leave a tail
-  const int occ_eff = occ_env > 0 ? occ_env : std::min(occ, rolled ? 12 : 8);
+  const int occ_eff = sw.occ_env > 0 ? sw.occ_env : std::min(occ, sw.rolled ? 12 : 8);
   const int per_xcd = std::max(1, std::min((n_cu / 8) * occ_eff, (rg.G + 7) / 8));
-  const bool expm = tune && (store_mode & ~3);  // work-skipping experiments: tools only (TLFEA_AD_TUNE), own instantiation
-#define TLFEA_AD_LAUNCH(R, X)                                                                                              \
-  hipLaunchKernelGGL((assemble_direct_kernel<R, X>), dim3(8 * per_xcd), dim3(64), lds, s, m, mat, h, rg, Fq, mval, 1.0 / h, \
+  return AssemblyLaunchForm{lds, 8 * per_xcd, sw.rolled ? 1 : 0};
+}
+
+void launch_assemble_direct(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups& rg,
+                            const double* Fq, const double* mval, const int* fixed_slot, const double* nw,
+                            double penalty, double* Hval, const double* emat) {
+  const AssemblyLaunchForm lf = assemble_direct_form(rg, mat, emat != nullptr);
+  const size_t lds = lf.lds;
+  const dim3 grid(lf.grid);
+  if (emat) {
+    const MaterialPE pe{mat, emat};
+    if (mat.model == kMooneyRivlin)
+      hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 1, MaterialPE>), grid, dim3(64), lds, s, m, pe, h, rg, Fq,
+                         mval, 1.0 / h, fixed_slot, nw, penalty, Hval, 0);
+    else
+      hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 0, MaterialPE>), grid, dim3(64), lds, s, m, pe, h, rg, Fq,
+                         mval, 1.0 / h, fixed_slot, nw, penalty, Hval, 0);
+    return;
+  }
+  if (mat.model == kMooneyRivlin) {
+    hipLaunchKernelGGL((assemble_direct_kernel<1, 0, 1>), grid, dim3(64), lds, s, m, mat, h, rg, Fq, mval, 1.0 / h,
+                       fixed_slot, nw, penalty, Hval, 0);
+    return;
+  }
+  const AdSwitches sw = ad_switches();
+  const int store_mode = sw.store_mode;
+  const bool expm = sw.tune && (store_mode & ~3);  // work-skipping experiments: tools only (TLFEA_AD_TUNE), own instantiation
+#define TLFEA_AD_LAUNCH(R, X)                                                                                     \
+  hipLaunchKernelGGL((assemble_direct_kernel<R, X>), grid, dim3(64), lds, s, m, mat, h, rg, Fq, mval, 1.0 / h, \
                      fixed_slot, nw, penalty, Hval, store_mode)
   if (expm) {
-    if (rolled) TLFEA_AD_LAUNCH(1, 1); else TLFEA_AD_LAUNCH(0, 1);
+    if (lf.rolled) TLFEA_AD_LAUNCH(1, 1); else TLFEA_AD_LAUNCH(0, 1);
   } else {
-    if (rolled) TLFEA_AD_LAUNCH(1, 0); else TLFEA_AD_LAUNCH(0, 0);
+    if (lf.rolled) TLFEA_AD_LAUNCH(1, 0); else TLFEA_AD_LAUNCH(0, 0);
   }
 #undef TLFEA_AD_LAUNCH
 }
@@ -1985,7 +2028,7 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
     // ---- (6) last pass of a group: h^2 rho J^T J on pinned rows (SyncedNewton.cu:292-341), rows stream out once ----
     if (last) {
       wave_sync();
-      if (lane < nrows && fs >= 0) {
+      if (lane < nrows && fs >= 0 && ri.z > 0) {  // (a pinned node of no element has no diagonal block: an empty row)
         const double pen = wv * penalty;
         const int a0 = ri.x & 0xffff, dpos = ri.x >> 16, row = 3 * ri.z;
 #pragma unroll
@@ -2020,39 +2063,28 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
 #undef TLFEA_TICK
 }
 
-void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups4& rg,
-                            const AffineView& av, const double* Fq16, const double* cmass, double rho0,
-                            const int* fixed_slot, const double* nw, double penalty, double* Hval, const double* emat) {
-  if (emat) {
+size_t assemble_affine_lds_max(int acc_max) {  // the records of per-element materials are the largest
+  return (size_t)(kAfInst * kAfRecPE + 160 + acc_max) * sizeof(double);
+}
+// LDS and grid of the affine form's launch for these work lists (the persistent grid of assemble_direct_form)
+AssemblyLaunchForm assemble_affine_form(const RowGroups4& rg, bool per_element) {
+  const int n_cu = device_cu_count();
+  if (per_element) {
     // per-element materials: the default form (no timing, no experiment bits) on 72-double records
     const void* fpe = (const void*)assemble_affine_kernel<0, 0, AffineCoefPE>;
     const size_t lds = (size_t)(kAfInst * kAfRecPE + 160 + rg.acc_max) * sizeof(double);
     static size_t lds_attr_pe = 0, occ_lds_pe = ~(size_t)0;
-    static int n_cu_pe = 0, occ_pe = 8;
+    static int occ_pe = 8;
     if (lds > 64 * 1024 && lds > lds_attr_pe) {
       (void)hipFuncSetAttribute(fpe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       lds_attr_pe = lds;
-    }
-    if (!n_cu_pe) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&n_cu_pe, hipDeviceAttributeMultiprocessorCount, dev);
-      if (n_cu_pe <= 0) n_cu_pe = 256;
     }
     if (occ_lds_pe != lds) {
       int o = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fpe, 64, lds) == hipSuccess && o > 0) occ_pe = o;
       occ_lds_pe = lds;
     }
-    const int per_xcd = std::max(1, std::min((n_cu_pe / 8) * occ_pe, (rg.G + 7) / 8));
-    AffineCoefPE ac;
-    ac.qw[0] = m.qw[av.q0];
-    ac.qw[1] = m.qw[av.qv[0]];  // the four outer points carry one weight (checked by the solver's set-up)
-    ac.h = h;
-    ac.emat = emat;
-    hipLaunchKernelGGL((assemble_affine_kernel<0, 0, AffineCoefPE>), dim3(8 * per_xcd), dim3(64), lds, s, rg, ac, av.gvec, Fq16,
-                       cmass, rho0 / h, fixed_slot, nw, penalty, Hval, 0, nullptr);
-    return;
+    return AssemblyLaunchForm{lds, 8 * std::max(1, std::min((n_cu / 8) * occ_pe, (rg.G + 7) / 8)), 1};
   }
   const void* fn = (const void*)assemble_affine_kernel<0, 0>;
   const size_t lds = (size_t)(kAfStage + 160 + rg.acc_max) * sizeof(double);
@@ -2062,29 +2094,37 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_attr = lds;
   }
-  static int n_cu = 0;
   static size_t occ_lds = ~(size_t)0;
   static int occ = 8;
-  if (!n_cu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (n_cu <= 0) n_cu = 256;
-  }
   if (occ_lds != lds) {
     int o = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, 64, lds) == hipSuccess && o > 0) occ = o;
     occ_lds = lds;
   }
-  static const bool tune = std::getenv("TLFEA_AD_TUNE") != nullptr;
-  static int occ_env = std::getenv("TLFEA_AD_WAVES") ? std::atoi(std::getenv("TLFEA_AD_WAVES")) : 0;
-  static int store_mode = std::getenv("TLFEA_AD_STORE") ? std::atoi(std::getenv("TLFEA_AD_STORE")) : 0;
-  if (tune) {
-    store_mode = std::getenv("TLFEA_AD_STORE") ? std::atoi(std::getenv("TLFEA_AD_STORE")) : 0;
-    occ_env = std::getenv("TLFEA_AD_WAVES") ? std::atoi(std::getenv("TLFEA_AD_WAVES")) : 0;
-  }
+  const int occ_env = ad_switches().occ_env;
   const int occ_eff = occ_env > 0 ? occ_env : occ;
-  const int per_xcd = std::max(1, std::min((n_cu / 8) * occ_eff, (rg.G + 7) / 8));
+  return AssemblyLaunchForm{lds, 8 * std::max(1, std::min((n_cu / 8) * occ_eff, (rg.G + 7) / 8)), 1};
+}
+
+void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups4& rg,
+                            const AffineView& av, const double* Fq16, const double* cmass, double rho0,
+                            const int* fixed_slot, const double* nw, double penalty, double* Hval, const double* emat) {
+  const AssemblyLaunchForm lf = assemble_affine_form(rg, emat != nullptr);
+  const size_t lds = lf.lds;
+  const int per_xcd = lf.grid / 8;
+  if (emat) {
+    AffineCoefPE ac;
+    ac.qw[0] = m.qw[av.q0];
+    ac.qw[1] = m.qw[av.qv[0]];  // the four outer points carry one weight (checked by the solver's set-up)
+    ac.h = h;
+    ac.emat = emat;
+    hipLaunchKernelGGL((assemble_affine_kernel<0, 0, AffineCoefPE>), dim3(8 * per_xcd), dim3(64), lds, s, rg, ac, av.gvec, Fq16,
+                       cmass, rho0 / h, fixed_slot, nw, penalty, Hval, 0, nullptr);
+    return;
+  }
+  const AdSwitches sw = ad_switches();
+  const bool tune = sw.tune;
+  const int store_mode = sw.store_mode;
   AffineCoef ac;
   for (int sdx = 0; sdx < 5; sdx++) {
     const int q = sdx == 0 ? av.q0 : av.qv[sdx - 1];

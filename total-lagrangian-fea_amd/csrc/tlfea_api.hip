@@ -1549,6 +1549,9 @@ struct tlfea_newton_s {
   bool rg_ok = false;
   bool fq_in_residual = true;  // first-order solvers (AdamW, Nesterov, VBD) never assemble: their residual skips Fq
   int asm_mode = 0;
+  int rg_passes = 0, rg4_passes = 0;  // entries of the pass tables of rg / rg4
+  // nodes whose row of H is empty (no element, no general linear constraint row): the first and how many (analyze_hessian_sparsity)
+  int iso_first = -1, iso_count = 0;
   double* d_Fq = nullptr;
   // affine-element form of the fused kernel (straight-sided elements + the 5-point Keast rule): its work lists, the
   // per-element vertex gradients; d_Fq then holds F per point, [E][5][10].  TLFEA_ASSEMBLE=general keeps the general form.
@@ -1936,6 +1939,9 @@ static int setup_affine_form(tlfea_newton_t s, bool* affine_out) {
     if (!build_row_groups4(N, d->E, d->h_conn.data(), d->h_off.data(), d->h_cols.data(), d->h_n2e_off.data(),
                            d->h_n2e.data(), d->h_X0.data(), d->h_X0.data() + N, d->h_X0.data() + 2 * (size_t)N, rh))
       return 0;
+    // a group's accumulator plus the kernel's staging must fit a workgroup's LDS (the builder only knows its 16-bit packing)
+    if (assemble_affine_lds_max(rh.acc_max) > device_lds_limit()) return 0;
+    s->rg4_passes = (int)(rh.pt.size() / 4);
     const std::vector<int>* src[5] = {&rh.g_pass_off, &rh.pt, &rh.gr_info, &rh.gi_head, &rh.gi_ent};
     for (int k = 0; k < 5; k++) {
       TRY(dmalloc(&s->d_rg4[k], src[k]->size() + 4));
@@ -1979,6 +1985,8 @@ static int setup_general_form(tlfea_newton_t s) {
     if (!build_row_groups(N, d->E, d->S, d->h_conn.data(), d->h_off.data(), d->h_cols.data(), d->h_n2e_off.data(),
                           d->h_n2e.data(), d->h_X0.data(), d->h_X0.data() + N, d->h_X0.data() + 2 * (size_t)N, rh))
       return 0;
+    if (assemble_direct_lds_max(rh.acc_max) > device_lds_limit()) return 0;  // as setup_affine_form: the two-kernel path is next
+    s->rg_passes = (int)(rh.pt.size() / 4);
     const std::vector<int>* src[6] = {&rh.g_pass_off, &rh.pt, &rh.gr_info, &rh.gi_code, &rh.gi_mb, &rh.gi_pack};
     for (int k = 0; k < 6; k++) {
       TRY(dmalloc(&s->d_rg[k], src[k]->size() + 4));
@@ -2010,6 +2018,26 @@ extern "C" int tlfea_newton_analyze_hessian_sparsity(tlfea_newton_t s) {
   tlfea_t10_t d = s->d;
   TRY(tlfea_t10_build_mass_csr_pattern(d));
   const int N = s->N;
+  // The longest node row must fit a workgroup's LDS in assemble_rows_kernel, the form every mesh can fall back to (the fused
+  // forms need more than that for the same row).  Checked before anything of the solver changes and before any launch.
+  if (assemble_rows_lds(d->maxdeg) > device_lds_limit()) {
+    int worst = 0;
+    for (int i = 0; i < N; i++)
+      if (d->h_off[i + 1] - d->h_off[i] == d->maxdeg) {
+        worst = i;
+        break;
+      }
+    return fail("tlfea_newton_analyze_hessian_sparsity: node " + std::to_string(worst) + " has " + std::to_string(d->maxdeg) +
+                " neighbours: its row of H needs " + std::to_string(assemble_rows_lds(d->maxdeg)) +
+                " bytes of LDS in the assembly, a workgroup of this device has " + std::to_string(device_lds_limit()));
+  }
+  s->iso_first = -1;
+  s->iso_count = 0;
+  for (int i = 0; i < N; i++)
+    if (d->h_off[i + 1] == d->h_off[i]) {
+      if (s->iso_first < 0) s->iso_first = i;
+      s->iso_count++;
+    }
   s->h_nnz = 9 * d->nnz_coef;
   s->h_row_offsets.resize(3 * (size_t)N + 1);
   s->h_col_indices.resize((size_t)s->h_nnz);
@@ -2042,6 +2070,21 @@ extern "C" int tlfea_newton_analyze_hessian_sparsity(tlfea_newton_t s) {
   if (s->verbose)
     std::printf("Sparse Hessian: %d x %d, nnz = %d\n", 3 * N, 3 * N, s->h_nnz);
   return 0;
+}
+
+// A node of no element (and of no general linear constraint row, which would seed its diagonal) has an empty row in H:
+// the element-level results stay defined (zero mass, zero internal force, that empty row), a solve with H does not --
+// extract_dinv_kernel would invert the next node's diagonal block for it.  Found on the host by
+// tlfea_newton_analyze_hessian_sparsity.  The guard stands at the two places every use of H^-1 or of its diagonal blocks
+// goes through -- pcg() (the direct solve included) and stage 0 of precond_setup (solves, the modal iteration, the
+// preconditioner test hooks) -- and, so that a step does not launch its gradient and assembly first, at the top of the
+// entry points that begin a step.
+static int refuse_empty_rows(tlfea_newton_t s, const char* who) {
+  if (s->iso_count == 0) return 0;
+  return fail(std::string(who) + ": node " + std::to_string(s->iso_first) + " belongs to no element (" +
+              std::to_string(s->iso_count) + " such node" + (s->iso_count > 1 ? "s" : "") +
+              " found by tlfea_newton_analyze_hessian_sparsity): its row of H is empty, so a solve with H is not defined; "
+              "remove unused nodes from the mesh, or use a solver that never forms H (AdamW, Nesterov)");
 }
 
 extern "C" int tlfea_newton_hessian_nnz(tlfea_newton_t s, int* nnz) {
@@ -4734,6 +4777,7 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
   tlfea_t10_t d = s->d;
   const int N = s->N;
   if (stage == 0) {
+    TRY(refuse_empty_rows(s, "preconditioner set-up"));  // extract_dinv_kernel / extract_diag read every row's diagonal block
     const bool lp = cheb_bits_eff(s) != 64;
     s->lp_scaled = s->lp_current = false;  // the stored copy belonged to the last set-up's H
     if (s->ar || lp) {
@@ -4822,6 +4866,7 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
   s->mf.last_mode = 0;
   s->fmf.now = false;
   s->fmf.last = 0;
+  TRY(refuse_empty_rows(s, "linear solve"));
   if (s->lin.method == 1) return direct_solve(s, d_b, d_x, iters_out, rel_out);
   tlfea_t10_t d = s->d;
   const int N = s->N;
@@ -5265,6 +5310,46 @@ extern "C" int tlfea_newton_get_assembly_mode(tlfea_newton_t s) {
   if (ensure_form_for_material(s)) return 0;
   return (use_direct(s) && (affine_now(s) || s->d_rg[0])) ? (affine_now(s) ? 3 : 2) : 1;
 }
+extern "C" int tlfea_newton_get_assembly_form(tlfea_newton_t s, int* out8) {
+  if (!s || !out8) return fail("tlfea_newton_get_assembly_form: null argument");
+  std::fill(out8, out8 + 8, 0);
+  TRY(tlfea_newton_analyze_hessian_sparsity(s));
+  TRY(ensure_form_for_material(s));
+  tlfea_t10_t d = s->d;
+  const bool pe = d->d_emat != nullptr;
+  const int mode = tlfea_newton_get_assembly_mode(s);
+  out8[0] = mode;
+  if (mode == 3) {
+    const AssemblyLaunchForm f = assemble_affine_form(s->rg4, pe);
+    out8[1] = 1;
+    out8[3] = s->rg4.G;
+    out8[4] = s->rg4.acc_max;
+    out8[5] = (int)f.lds;
+    out8[6] = f.grid;
+    out8[7] = s->rg4_passes;
+  } else if (mode == 2) {
+    const AssemblyLaunchForm f = assemble_direct_form(s->rg, d->mat, pe);
+    out8[1] = f.rolled;
+    out8[3] = s->rg.G;
+    out8[4] = s->rg.acc_max;
+    out8[5] = (int)f.lds;
+    out8[6] = f.grid;
+    out8[7] = s->rg_passes;
+  } else {  // tangent blocks + one workgroup per node row
+    out8[1] = 1;
+    out8[2] = tangent_blocks_wpb(pe && d->S == 10);
+    out8[3] = s->N;
+    out8[4] = 9 * d->maxdeg;
+    out8[5] = (int)assemble_rows_lds(d->maxdeg);
+    out8[6] = s->N;
+    out8[7] = 1;
+  }
+  return 0;
+}
+extern "C" int tlfea_newton_get_gradient_form(tlfea_newton_t s) {
+  if (!s) return 0;
+  return mass_in_residual(s) ? 2 : 1;
+}
 extern "C" int tlfea_newton_get_linsolve_info(tlfea_newton_t s, int* cheb_degree, int* cheb_bits, int* cheb_vector_bits) {
   if (!s) return fail("null argument");
   if (cheb_degree) *cheb_degree = cheb_degree_eff(s);
@@ -5285,6 +5370,7 @@ extern "C" int tlfea_newton_assemble_hessian(tlfea_newton_t s) {
   return 0;
 }
 extern "C" int tlfea_newton_linear_solve(tlfea_newton_t s, const double* b, double* x, int* iters, double* rel_res) {
+  TRY(refuse_empty_rows(s, "tlfea_newton_linear_solve"));
   const size_t n = 3 * (size_t)s->N;
   HIP_TRY(hipMemcpy(s->d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
   TRY(pcg(s, s->d_b, s->d_dv, iters, rel_res));
@@ -5302,6 +5388,7 @@ extern "C" int tlfea_newton_cg_trace(tlfea_newton_t s, const double* b, int k, d
   if (!s->d_H) return fail("tlfea_newton_cg_trace: no assembled H");
   if (dist_on(s)) return fail("tlfea_newton_cg_trace: not available on a partitioned mesh (set_interface / set_halo is active)");
   if (s->lin.method == 1) return fail("tlfea_newton_cg_trace: method = 1 (sparse direct) has no iteration");
+  TRY(refuse_empty_rows(s, "tlfea_newton_cg_trace"));
   const size_t n = 3 * (size_t)s->N;
   HIP_TRY(hipMemcpy(s->d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
   tlfea_newton_s::CgTrace tr;
@@ -5749,6 +5836,7 @@ extern "C" int tlfea_newton_modal_solve(tlfea_newton_t s, const tlfea_modal_opts
   if (!d->have_dndu || !modal_has_mass(d))
     return fail("tlfea_newton_modal_solve: needs the mass matrix and its sparsity (CalcDnDuPre, CalcMassMatrix) first");
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
+  TRY(refuse_empty_rows(s, "tlfea_newton_modal_solve"));
   TRY(sync_constraints(s));
   int n_free = s->N;
   if (pinned_on(s)) {
@@ -5950,6 +6038,7 @@ static int begin_step(tlfea_newton_t s) {  // cudss_solve_update_pos_prev (Synce
 
 extern "C" int tlfea_newton_iteration(tlfea_newton_t s, double* norm_g, int* iters) {
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
+  TRY(refuse_empty_rows(s, "tlfea_newton_iteration"));
   TRY(sync_constraints(s));
   s->lin_worst_rel = 0.0;
   s->lin_all_ok = true;
@@ -5972,6 +6061,7 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
   tlfea_t10_t d = s->d;
   if (!d->have_dndu) return fail("CalcDnDuPre must be called before Solve");
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
+  TRY(refuse_empty_rows(s, "tlfea_newton_solve"));
   TRY(sync_constraints(s));
   s->lin_worst_rel = 0.0;
   s->lin_all_ok = true;
@@ -6965,6 +7055,19 @@ extern "C" int tlfea_vbd_solve(tlfea_vbd_t a) {
                 "AdamW or Nesterov solver, or clear the loads");
   TRY(sync_constraints(s));
   if (!a->mass_ready && !d->is_csr_setup) TRY(tlfea_vbd_initialize_mass_diag_blocks(a));
+  if (d->is_csr_setup && d->h_off.size() == (size_t)s->N + 1) {
+    // vbd_color_kernel reads every node's diagonal mass entry mval[off[i] + diagpos[i]]: a node of no element has none
+    int first = -1, count = 0;
+    for (int i = 0; i < s->N; i++)
+      if (d->h_off[i + 1] == d->h_off[i]) {
+        if (first < 0) first = i;
+        count++;
+      }
+    if (count)
+      return fail("SyncedVBDSolver: node " + std::to_string(first) + " belongs to no element (" + std::to_string(count) +
+                  " such node" + (count > 1 ? "s" : "") + "): the vertex solve needs the node's diagonal mass entry, which "
+                  "an empty row does not have; remove unused nodes from the mesh, or use the AdamW or Nesterov solver");
+  }
   TRY(tlfea_vbd_initialize_coloring(a));
   if (!a->fixed_ready) TRY(tlfea_vbd_initialize_fixed_map(a));
   if (s->n_constraints > 0 && !d->is_constraints_setup)

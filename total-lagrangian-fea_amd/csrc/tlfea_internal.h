@@ -212,6 +212,27 @@ void launch_fine_matfree_step(hipStream_t s, int N, const FineMatfree& f, const 
                               double* rz_part, bool last);
 // scn = float(sc / sigma) with sigma^2 = ss[0] * inv_n
 void launch_fine_matfree_scale(hipStream_t s, int n, const double* sc, const double* ss, double inv_n, float* scn);
+// What a launch of the assembly would use now -- the launchers' own arithmetic, not a restatement of it: dynamic LDS
+// bytes, workgroups, and (general form) whether the rolled kernel runs.  The fused launchers call these themselves.
+// They are not pure queries: the first call for a given LDS size also PREPARES the kernels as the launch needs them
+// (hipFuncSetAttribute(MaxDynamicSharedMemorySize) above 64 KiB, the occupancy query behind the persistent grid) and
+// caches the answers in function-local statics, exactly as the launchers did before the split.
+struct AssemblyLaunchForm {
+  size_t lds;
+  int grid;
+  int rolled;
+};
+AssemblyLaunchForm assemble_direct_form(const RowGroups& rg, const Material& mat, bool per_element);
+AssemblyLaunchForm assemble_affine_form(const RowGroups4& rg, bool per_element);
+// the largest dynamic LDS any instantiation of a fused form takes for an accumulator of acc_max doubles (the material,
+// hence the instantiation, may be switched between solves), and what assemble_rows_kernel takes for a longest row
+size_t assemble_direct_lds_max(int acc_max);
+size_t assemble_affine_lds_max(int acc_max);
+size_t assemble_rows_lds(int maxdeg);
+// LDS a workgroup can have on this device (hipDeviceAttributeMaxSharedMemoryPerBlock, queried once; MI355X: 163 840)
+size_t device_lds_limit();
+// wavefronts per workgroup of the tangent-block launch of the two-kernel path (TLFEA_TANGENT_WPB; 1 with per-element materials)
+int tangent_blocks_wpb(bool per_element);
 void launch_tangent_blocks(hipStream_t s, const ElemView& m, const Material& mat, double h,
                            double* Kbuf /*[E][55][9]*/, const double* emat = nullptr);
 void launch_assemble_rows(hipStream_t s, int N, int S, int maxdeg, const Incidence& inc, const double* Kbuf,

@@ -118,8 +118,22 @@ class SyncedNewtonSolver:
         return int(self._lib.tlfea_newton_collectives(self._h))
 
     def GetAssemblyMode(self):
-        """1: tangent blocks + row-owner gather (two launches), 2: fused row-owner tangent + assembly (T10, SVK)"""
+        """1: tangent blocks + row-owner gather (two launches), 2: fused tangent + assembly, general form, 3: its
+        affine-element form (straight-sided T10, St.Venant-Kirchhoff)"""
         return int(self._lib.tlfea_newton_get_assembly_mode(self._h))
+
+    ASSEMBLY_FORM_KEYS = ("mode", "rolled", "tangent_wpb", "groups", "acc_max", "lds_bytes", "workgroups", "passes")
+
+    def GetAssemblyForm(self):
+        """dict of the launch an assembly would issue now: mode (1 two kernels, 2 fused general, 3 fused affine), rolled,
+        tangent_wpb (two-kernel path), groups, acc_max (doubles), lds_bytes, workgroups, passes (test hook)"""
+        out = (C.c_int * 8)()
+        check(self._lib.tlfea_newton_get_assembly_form(self._h, out))
+        return dict(zip(self.ASSEMBLY_FORM_KEYS, (int(v) for v in out)))
+
+    def GetGradientForm(self):
+        """1: mass CSR product inside grad_kernel (TLFEA_MASS=csr, ANCF), 2: element inertia rows + grad_light_kernel (test hook)"""
+        return int(self._lib.tlfea_newton_get_gradient_form(self._h))
 
     def RetrievePmgLevel(self):
         """(par0, par1, c_off, c_cols, Hc_values): parent map of the fine nodes, coarse node adjacency and the Galerkin
