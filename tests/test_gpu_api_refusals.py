@@ -1,8 +1,9 @@
-"""The text of the refusals of the stress, obstacle and load entry points of the C-ABI, for both kinds of handle: each
-call below is refused, and tlfea_last_error() is compared with the exact message.  The T10 and ANCF entry points of these
-subsystems share their implementation, and their preconditions differ in small ways (the tlfea_t10_* obstacle calls other
-than set_obstacles refuse an ANCF handle only while it holds a list); this pins every one of them.  The meshes are the
-smallest at hand: beam_3x2x1 (36 T10 elements) and the welded 20 x 20 ANCF3243 net."""
+"""The text of the refusals of the stress, obstacle and load entry points of the C-ABI, for both kinds of handle, and of the
+first-order solvers: each call below is refused, and tlfea_last_error() is compared with the exact message.  The T10 and
+ANCF entry points of these subsystems share their implementation, and their preconditions differ in small ways (the
+tlfea_t10_* obstacle calls other than set_obstacles refuse an ANCF handle only while it holds a list; an ANCF surface load
+names a face of its elements, a T10 one does not); this pins every one of them.  The meshes are the smallest at hand:
+beam_3x2x1 (36 T10 elements) and the welded 20 x 20 ANCF3243 net."""
 import ctypes as C
 
 import numpy as np
@@ -172,3 +173,150 @@ def test_load_calls_on_the_other_kind(lib):
     refused(lib, lib.tlfea_ancf_update_load_scale(t._h, 0, 1.0), "tlfea_ancf_update_load_scale" + NOT_T10)
     t.Destroy()
     a.Destroy()
+
+
+def load_array(kind, entries):
+    """the ctypes list of tlfea_<kind>_set_surface_loads from (load kind, face, value[3], scale, indices) entries, and the
+    index arrays it points into (to be kept alive during the call); an empty index list travels as a null pointer"""
+    keep = [np.asarray(e[4], dtype=np.int32) for e in entries]
+    ptr = lambda a: B.ip(a) if a.size else None
+    if kind == "t10":
+        items = [B.T10SurfaceLoadC(k, tuple(v), sc, ptr(a), int(a.size)) for (k, _, v, sc, _), a in zip(entries, keep)]
+        return (B.T10SurfaceLoadC * len(items))(*items), keep
+    items = [B.SurfaceLoadC(k, f, tuple(v), sc, ptr(a), int(a.size)) for (k, f, v, sc, _), a in zip(entries, keep)]
+    return (B.SurfaceLoadC * len(items))(*items), keep
+
+
+@pytest.mark.parametrize("kind", ("t10", "ancf"))
+def test_surface_load_refusals(lib, kind):
+    """every refusal of set_surface_loads and update_load_scale, in the order the checks run; a refused call leaves the
+    load of the last gradient evaluation (tlfea_get_load_resultant) and the stored list (the load of the next gradient
+    evaluation) as they were, and a valid list is still taken after it"""
+    h = t10_handle() if kind == "t10" else ancf_handle()
+    P, U = f"tlfea_{kind}_set_surface_loads", f"tlfea_{kind}_update_load_scale"
+    set_loads, update = getattr(lib, P), getattr(lib, U)
+    if kind == "t10":
+        n = C.c_int()
+        assert lib.tlfea_t10_get_boundary_faces(h._h, C.byref(n), None, None, None) == 0
+        R, noun = n.value, "face"
+    else:
+        R, noun = h.get_n_elem(), "element"
+    v, nan = (0.0, 0.0, -1e3), float("nan")
+    good = [(0, 1, v, 1.0, [0, 1, 2]), (1, 1, (2e3, 0.0, 0.0), 0.5, [1, 2])]
+    good_arr, good_keep = load_array(kind, good)
+
+    def resultant():
+        out = np.zeros(3)
+        assert lib.tlfea_get_load_resultant(h._h, B.dp(out)) == 0
+        return out
+
+    assert set_loads(h._h, good_arr, 2) == 0
+    s = tl.SyncedNewtonSolver(h, 0)
+    s.EvalGradient()
+    R0 = resultant()
+    assert np.linalg.norm(R0) > 0.0
+
+    def after_refusal():
+        assert np.array_equal(resultant(), R0)      # the buffers of the last evaluation were not touched ...
+        s.EvalGradient()                            # ... and the list the handle holds is still the one that was set:
+        assert np.allclose(resultant(), R0, rtol=1e-12, atol=1e-12 * np.max(np.abs(R0)))  # the same sums, to rounding
+        assert set_loads(h._h, good_arr, 2) == 0
+
+    # the count and the list pointer
+    for n in (-1, 17):
+        refused(lib, set_loads(h._h, good_arr, n), f"{P}: n must be in 0..16, got {n}")
+        after_refusal()
+    refused(lib, set_loads(h._h, None, 2), f"{P}: null list")
+    after_refusal()
+    # one bad load behind a good one: named by its index
+    cases = [((2, 1, v, 1.0, [0]), "kind must be 0 (traction) or 1 (pressure), got 2"),
+             ((-1, 1, v, 1.0, [0]), "kind must be 0 (traction) or 1 (pressure), got -1"),
+             ((0, 1, (0.0, 0.0, nan), 1.0, [0]), "the value must be finite"),
+             ((1, 1, (nan, 0.0, 0.0), 1.0, [0]), "the value must be finite"),
+             ((0, 1, v, nan, [0]), "the scale must be finite"),
+             ((0, 1, v, 1.0, []), f"empty {noun} list"),
+             ((0, 1, v, 1.0, [0, -1]), f"{noun} -1 outside 0..{R - 1}"),
+             ((0, 1, v, 1.0, [0, R]), f"{noun} {R} outside 0..{R - 1}"),
+             ((0, 1, v, 1.0, [3, 0, 3]), f"{noun} 3 is listed twice" + (" for face 1" if kind == "ancf" else ""))]
+    if kind == "ancf":  # the 3243 beam has faces 0..3; the face is looked at before the value
+        cases += [((0, -1, v, 1.0, [0]), "face -1 outside 0..3"), ((0, 4, (nan, 0.0, 0.0), 1.0, [0]), "face 4 outside 0..3")]
+    for bad, text in cases:
+        arr, keep = load_array(kind, [good[0], bad])
+        refused(lib, set_loads(h._h, arr, 2), f"{P}: load 1: {text}")
+        after_refusal()
+    # the scale update
+    for k in (2, -1):
+        refused(lib, update(h._h, k, 1.0), f"{U}: index {k} outside the 2 surface loads set")
+        after_refusal()
+    refused(lib, update(h._h, 0, nan), f"{U}: the scale must be finite")
+    after_refusal()
+    # the list is the one that was set: the same load again (sums of the same terms: to rounding of their order at most)
+    s.EvalGradient()
+    assert np.allclose(resultant(), R0, rtol=1e-12, atol=1e-12 * np.max(np.abs(R0)))
+    del s, good_keep
+    h.Destroy()
+
+
+# ---- first-order solvers -------------------------------------------------------------------------------------------------
+FIRST_ORDER = {"adamw": ("SyncedAdamWNocoopSolver", "SyncedAdamWNocoop"), "nesterov": ("SyncedNesterovSolver", "SyncedNesterov"),
+               "vbd": ("SyncedVBDSolver", "SyncedVBDSolver")}
+
+
+def test_first_order_create_and_parameter_refusals(lib):
+    t = t10_handle()
+    out = C.c_void_p()
+    for name, (cls, _) in FIRST_ORDER.items():
+        create = getattr(lib, f"tlfea_{name}_create")
+        refused(lib, create(None, 0, C.byref(out)), f"tlfea_{name}_create: null argument")
+        refused(lib, create(t._h, 0, None), f"tlfea_{name}_create: null argument")
+        s = getattr(tl, cls)(t, 0)
+        refused(lib, getattr(lib, f"tlfea_{name}_set_parameters")(s._h, None), "null argument")
+        del s
+    t.Destroy()
+
+
+def test_first_order_solve_refusals(lib):
+    # AdamW and Nesterov before CalcMassMatrix: the gradient needs the mass pattern
+    a = make_ancf_gpu(SHAPES["net"](), MATERIALS["svk"], mass=False)
+    for name in ("adamw", "nesterov"):
+        cls, who = FIRST_ORDER[name]
+        s = getattr(tl, cls)(a, 0)
+        refused(lib, getattr(lib, f"tlfea_{name}_solve")(s._h),
+                f"{who}: CalcMassMatrix() must precede Solve() (the gradient uses the mass CSR)")
+        del s
+    a.Destroy()
+    # Nesterov with general linear constraints (cons_mode 2): the pinned DOFs of the beam's end face as CSR rows
+    X, conn = load_mesh("beam_3x2x1")
+    m, q = MATERIALS["svk"], tl.quadrature
+    d = tl.GPU_FEAT10_Data(conn.shape[0], X.shape[0])
+    d.Initialize()
+    d.Setup(q.tet5pt_x, q.tet5pt_y, q.tet5pt_z, q.tet5pt_weights, X[:, 0], X[:, 1], X[:, 2], conn)
+    d.SetDensity(m["rho0"])
+    d.SetDamping(m["eta"], m["lamd"])
+    d.SetSVK(m["E"], m["nu"])
+    fx = np.where(np.abs(X[:, 0]) < 1e-8)[0]
+    cols = (3 * fx[:, None] + np.arange(3)[None, :]).reshape(-1)
+    d.SetLinearConstraintsCSR(np.arange(len(cols) + 1), cols, np.ones(len(cols)), X[fx].reshape(-1))
+    d.CalcDnDuPre()
+    d.CalcMassMatrix()
+    d.CalcConstraintData()
+    assert d.GetConstraintMode() == 2
+    s = tl.SyncedNesterovSolver(d, d.get_n_constraint())
+    refused(lib, lib.tlfea_nesterov_solve(s._h), "SyncedNesterov: fixed-coefficient constraints only (as the reference, :197-200)")
+    del s
+    d.Destroy()
+    # VBD has neither a contact nor a load term: an obstacle is looked at first, then the loads
+    t = t10_handle()
+    s = tl.SyncedVBDSolver(t, 0)
+    assert lib.tlfea_t10_set_obstacles(t._h, obstacle_list(1), 1) == 0
+    g = np.array([0.0, 0.0, -9.81])
+    assert lib.tlfea_set_body_acceleration(t._h, B.dp(g)) == 0
+    refused(lib, lib.tlfea_vbd_solve(s._h),
+            "SyncedVBDSolver: rigid obstacles are set, and the VBD vertex solve has no contact term; use the Newton, AdamW or "
+            "Nesterov solver, or clear the obstacles")
+    assert lib.tlfea_t10_clear_obstacles(t._h) == 0
+    refused(lib, lib.tlfea_vbd_solve(s._h),
+            "SyncedVBDSolver: distributed loads are set, and the VBD vertex solve has no load term; use the Newton, AdamW or "
+            "Nesterov solver, or clear the loads")
+    del s
+    t.Destroy()

@@ -1,6 +1,6 @@
 // ancf_load_host.h -- host side of the follower pressure on the ANCF kinds: the Gauss points of a face and,
 // per distinct (L, W, H), the shape values and the two tangential shape derivatives at them.  The dead traction needs no
-// table of its own: it uses the sample points and weights of ancf_obstacle_host.h.  Included by tlfea_api.hip only.
+// table of its own: it uses the sample points and weights of ancf_obstacle_host.h.  Included by loads_api.hip only.
 #pragma once
 #include <array>
 #include <map>

@@ -1,6 +1,6 @@
 // ancf_obstacle_host.h -- host side of the rigid obstacles on the ANCF kinds (DESIGN 3e'): the 32 sample points of an
 // element, their shape values (one table per distinct (L, W, H)) and their weights.  Included by
-// obstacle_api.hip and, through ancf_load_host.h, tlfea_api.hip.
+// obstacle_api.hip and, through ancf_load_host.h, loads_api.hip.
 #pragma once
 #include <array>
 #include <cmath>

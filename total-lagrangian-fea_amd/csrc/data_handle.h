@@ -1,5 +1,5 @@
 // data_handle.h -- the data object behind tlfea_t10_t (any element kind) and what of the units split off tlfea_api.hip
-// (obstacle_api.hip, stress_api.hip) the rest of the host code calls.  Private to csrc/.
+// (loads_api.hip, obstacle_api.hip) the rest of the host code calls.  Private to csrc/.
 #pragma once
 #include "api_common.h"
 #include "t10_load_host.h"
@@ -158,6 +158,13 @@ inline AncfObsView ancf_obs_view(tlfea_t10_t h) {
                      h->d_ao_fk, h->d_ao_touched};
 }
 
+inline bool mass_assembled(tlfea_t10_t h) { return h->kind == kT10 ? h->mass_rho0 >= 0.0 : h->ancf_mass; }
+
+// loads_api.hip: the boundary faces of a T10 mesh (built once, kept in the handle) and the traction vector of the loads
+// set, which follow the reference geometry
+void boundary_faces_build(tlfea_t10_t h);
+int loads_build_traction(tlfea_t10_t h);
+int t10_loads_build_traction(tlfea_t10_t h);
 // obstacle_api.hip
 int ancf_points_build(tlfea_t10_t h);
 // the reference geometry of a T10 object has moved (tlfea_t10_set_reference_positions): surface weights again from h_X0

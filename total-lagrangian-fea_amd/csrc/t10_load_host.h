@@ -1,6 +1,6 @@
 // t10_load_host.h -- host side of the surface loads on the boundary faces of a T10 mesh (DESIGN 3h'): the boundary faces
 // with their nodes ordered outward, the 6-point triangle rule and the traction weights of a face.  Included by
-// data_handle.h (the handle keeps the faces) for tlfea_api.hip.
+// data_handle.h (the handle keeps the faces) for loads_api.hip.
 #pragma once
 #include <algorithm>
 #include <array>

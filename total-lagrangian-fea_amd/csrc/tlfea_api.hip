@@ -1,39 +1,25 @@
 // tlfea_api.hip -- C-ABI (include/tlfea_c.h) over the gfx950 kernels: buffer ownership, the host
 // side of the sparsity analysis, and the ALM/Newton control flow of the reference
 // (SyncedNewton.cu:909-1146) with the device PCG in place of cuDSS.
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
-#include <map>
 #include <string>
-#include <thread>
+#include <tuple>
 #include <vector>
-#include <unistd.h>
 
 #include "ancf_host.h"
-#include "data_handle.h"
+#include "newton_handle.h"
 #include "pmg_host.h"
 #include "pmg_coef.h"
 #include "rowgroup_host.h"
-#include "direct_host.h"
 #include "vbd_host.h"
-#include "ancf_load_host.h"
-#include "t10_load_host.h"
 #include "modal_host.h"
 
 using namespace tlfea;
-
-struct RcclUniqueId {  // == ncclUniqueId (rccl.h): 128 opaque bytes, passed BY VALUE to ncclCommInitRank
-  char internal[128];
-};
 
 std::string& tlfea::api_error() {
   thread_local std::string err;
@@ -298,360 +284,6 @@ extern "C" int tlfea_t10_get_element_materials(tlfea_t10_t h, int* n_mat, int* e
   if (!h) return fail("null handle");
   if (n_mat) *n_mat = h->n_mat;
   if (elem_material && h->d_emat) std::copy(h->h_eid.begin(), h->h_eid.end(), elem_material);
-  return 0;
-}
-
-// ---- distributed loads -------------------------------------------------------------------------------------------
-static bool mass_assembled(tlfea_t10_t h) { return h->kind == kT10 ? h->mass_rho0 >= 0.0 : h->ancf_mass; }
-static AncfLoadView ancf_load_view(tlfea_t10_t h) {
-  return AncfLoadView{h->E, h->S, h->d_conn, h->d_ld_cls, h->d_ld_tab, h->d_ld_qw, h->d_ld_mask, h->d_ld_pe, h->d_ld_lbuf};
-}
-static void surface_loads_free(tlfea_t10_t h) {
-  for (double** p : {&h->d_ld_tr, &h->d_ld_lbuf, &h->d_ld_tab, &h->d_ld_qw, &h->d_ld_pe}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  for (int** p : {&h->d_ld_cls, &h->d_ld_mask, &h->d_ld_fnodes, &h->d_ld_foff, &h->d_ld_fslot}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  h->h_ld_lf.clear();
-  h->ld_list.clear();
-  h->ld_n_trac = h->ld_n_press = 0;
-}
-static void loads_free(tlfea_t10_t h) {
-  surface_loads_free(h);
-  for (double** p : {&h->d_ld_fc, &h->d_ld_f}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  h->ld_have_a = h->ld_const_dirty = false;
-  h->ld_a[0] = h->ld_a[1] = h->ld_a[2] = 0.0;
-}
-// the two [N][3] vectors every load needs; the total starts at zero (no gradient evaluation yet)
-static int loads_alloc_common(tlfea_t10_t h) {
-  if (h->d_ld_f) return 0;
-  TRY(dmalloc(&h->d_ld_fc, (size_t)3 * h->N));
-  TRY(dmalloc(&h->d_ld_f, (size_t)3 * h->N));
-  HIP_TRY(hipMemset(h->d_ld_fc, 0, (size_t)3 * h->N * sizeof(double)));
-  HIP_TRY(hipMemset(h->d_ld_f, 0, (size_t)3 * h->N * sizeof(double)));
-  return 0;
-}
-static int t10_loads_build_traction(tlfea_t10_t h);  // the same two on the boundary faces of a T10 mesh (DESIGN 3h')
-static int t10_loads_build_pressure_scale(tlfea_t10_t h);
-// Traction vector [N][3] = sum over the traction loads (list order), their elements (list order), the element's
-// coefficients and the face's sample points (point order) of scale t w_p S_a(p): on the host, once per change.
-static int loads_build_traction(tlfea_t10_t h) {
-  if (h->ld_n_trac == 0) return 0;
-  if (h->kind == kT10) return t10_loads_build_traction(h);
-  TRY(ancf_points_build(h));
-  const int S = h->S, E = h->E, ppf = kAncfObsPoints / ancf::load_faces(S);
-  std::vector<double> tr((size_t)3 * h->N, 0.0);
-  for (const auto& L : h->ld_list) {
-    if (L.kind != 0) continue;
-    for (int e : L.elems) {
-      const double* sv = &h->h_ao_sval[(size_t)h->h_ao_cls[e] * kAncfObsPoints * S];
-      const double* w = &h->h_ao_w[(size_t)e * kAncfObsPoints];
-      for (int a = 0; a < S; a++) {
-        double ws = 0.0;
-        for (int p = L.face * ppf; p < (L.face + 1) * ppf; p++) ws += w[p] * sv[(size_t)p * S + a];
-        const int id = h->h_conn[(size_t)a * E + e];
-        for (int c = 0; c < 3; c++) tr[3 * (size_t)id + c] += L.scale * L.value[c] * ws;
-      }
-    }
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_ld_tr, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
-  h->ld_const_dirty = true;
-  return 0;
-}
-// pe [E][faces] = -(orientation sign) x sum over the pressure loads (list order) of scale x pressure
-static int loads_build_pressure_scale(tlfea_t10_t h) {
-  if (h->ld_n_press == 0) return 0;
-  if (h->kind == kT10) return t10_loads_build_pressure_scale(h);
-  const int NF = ancf::load_faces(h->S);
-  std::vector<double> pe((size_t)h->E * NF, 0.0);
-  for (const auto& L : h->ld_list)
-    if (L.kind == 1)
-      for (int e : L.elems) pe[(size_t)e * NF + L.face] += L.scale * L.value[0];
-  for (size_t k = 0; k < pe.size(); k++) pe[k] *= -ancf::load_face_sign(h->S, (int)(k % NF));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_ld_pe, pe.data(), pe.size() * sizeof(double), hipMemcpyHostToDevice));
-  return 0;
-}
-
-extern "C" int tlfea_clear_loads(tlfea_t10_t h) {
-  NEED_SETUP(h, "clearing loads.");
-  if (!h->loads_on()) return 0;
-  HIP_TRY(hipDeviceSynchronize());  // launches in flight on a solver's stream may still read the buffers
-  loads_free(h);
-  return 0;
-}
-extern "C" int tlfea_set_body_acceleration(tlfea_t10_t h, const double a[3]) {
-  NEED_SETUP(h, "setting a body acceleration.");
-  if (h->kind != kT10 && !h->have_dndu) return fail("tlfea_set_body_acceleration: CalcDsDuPre must run first");
-  if (!a) return fail("tlfea_set_body_acceleration: null acceleration");
-  if (!(std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2])))
-    return fail("tlfea_set_body_acceleration: the acceleration must be finite");
-  if (!mass_assembled(h))
-    return fail("tlfea_set_body_acceleration: CalcMassMatrix must run first (the load is the mass matrix times the acceleration)");
-  HIP_TRY(hipDeviceSynchronize());
-  if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0) {  // no body force: as if never set
-    h->ld_have_a = false;
-    h->ld_a[0] = h->ld_a[1] = h->ld_a[2] = 0.0;
-    if (!h->loads_on()) loads_free(h);
-    h->ld_const_dirty = true;
-    return 0;
-  }
-  TRY(loads_alloc_common(h));
-  h->ld_have_a = true;
-  std::copy(a, a + 3, h->ld_a);
-  h->ld_const_dirty = true;
-  return 0;
-}
-extern "C" int tlfea_ancf_set_surface_loads(tlfea_t10_t h, const tlfea_surface_load* list, int n) {
-  if (h && h->kind == kT10)
-    return fail("tlfea_ancf_set_surface_loads: ANCF handles only (a T10 handle takes the body acceleration alone)");
-  NEED_SETUP(h, "setting surface loads.");
-  if (!h->have_dndu)
-    return fail("tlfea_ancf_set_surface_loads: CalcDsDuPre must run first (the traction weights use the reference geometry)");
-  if (n < 0 || n > kMaxLoads)
-    return fail("tlfea_ancf_set_surface_loads: n must be in 0.." + std::to_string(kMaxLoads) + ", got " + std::to_string(n));
-  if (n > 0 && !list) return fail("tlfea_ancf_set_surface_loads: null list");
-  const int NF = ancf::load_faces(h->S), P = ancf::load_points(h->S), E = h->E, S = h->S;
-  std::vector<tlfea_t10_s::SurfaceLoad> fresh((size_t)n);
-  std::vector<char> seen;
-  for (int k = 0; k < n; k++) {
-    const tlfea_surface_load& L = list[k];
-    const std::string who = "tlfea_ancf_set_surface_loads: load " + std::to_string(k) + ": ";
-    if (L.kind != 0 && L.kind != 1) return fail(who + "kind must be 0 (traction) or 1 (pressure), got " + std::to_string(L.kind));
-    if (L.face < 0 || L.face >= NF)
-      return fail(who + "face " + std::to_string(L.face) + " outside 0.." + std::to_string(NF - 1));
-    for (int c = 0; c < (L.kind == 0 ? 3 : 1); c++)
-      if (!std::isfinite(L.value[c])) return fail(who + "the value must be finite");
-    if (!std::isfinite(L.scale)) return fail(who + "the scale must be finite");
-    if (L.n_elems <= 0 || !L.elems) return fail(who + "empty element list");
-    seen.assign((size_t)E, 0);
-    for (int i = 0; i < L.n_elems; i++) {
-      const int e = L.elems[i];
-      if (e < 0 || e >= E) return fail(who + "element " + std::to_string(e) + " outside 0.." + std::to_string(E - 1));
-      if (seen[e]) return fail(who + "element " + std::to_string(e) + " is listed twice for face " + std::to_string(L.face));
-      seen[e] = 1;
-    }
-    fresh[k].kind = L.kind;
-    fresh[k].face = L.face;
-    fresh[k].scale = L.scale;
-    for (int c = 0; c < 3; c++) fresh[k].value[c] = L.kind == 0 || c == 0 ? L.value[c] : 0.0;
-    fresh[k].elems.assign(L.elems, L.elems + L.n_elems);
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  surface_loads_free(h);
-  h->ld_const_dirty = true;
-  if (n == 0) {
-    if (!h->loads_on()) loads_free(h);
-    return 0;
-  }
-  TRY(loads_alloc_common(h));
-  h->ld_list.swap(fresh);
-  for (const auto& L : h->ld_list) (L.kind == 0 ? h->ld_n_trac : h->ld_n_press)++;
-  if (h->ld_n_trac > 0) {
-    TRY(dmalloc(&h->d_ld_tr, (size_t)3 * h->N));
-    TRY(loads_build_traction(h));
-  }
-  if (h->ld_n_press > 0) {
-    const ancf::PressureSetup su = ancf::pressure_setup(S, E, h->Lv, h->Wv, h->Hv, h->Binv);
-    std::vector<int> mask((size_t)E, 0);
-    for (const auto& L : h->ld_list)
-      if (L.kind == 1)
-        for (int e : L.elems) mask[e] |= 1 << L.face;
-    TRY(dmalloc(&h->d_ld_cls, (size_t)E));
-    TRY(dmalloc(&h->d_ld_mask, (size_t)E));
-    TRY(dmalloc(&h->d_ld_tab, su.tab.size()));
-    TRY(dmalloc(&h->d_ld_qw, (size_t)P));
-    TRY(dmalloc(&h->d_ld_pe, (size_t)E * NF));
-    TRY(dmalloc(&h->d_ld_lbuf, (size_t)E * S * 3));
-    HIP_TRY(hipMemcpy(h->d_ld_cls, su.cls.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_ld_mask, mask.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_ld_tab, su.tab.data(), su.tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_ld_qw, su.qw.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice));
-    // zeroed once: only the rows of loaded elements are ever rewritten
-    HIP_TRY(hipMemset(h->d_ld_lbuf, 0, (size_t)E * S * 3 * sizeof(double)));
-    TRY(loads_build_pressure_scale(h));
-  }
-  return 0;
-}
-extern "C" int tlfea_ancf_update_load_scale(tlfea_t10_t h, int k, double scale) {
-  if (h && h->kind == kT10) return fail("tlfea_ancf_update_load_scale: ANCF handles only (not a T10 handle)");
-  NEED_SETUP(h, "updating a load scale.");
-  if (k < 0 || k >= (int)h->ld_list.size())
-    return fail("tlfea_ancf_update_load_scale: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->ld_list.size()) + " surface loads set");
-  if (!std::isfinite(scale)) return fail("tlfea_ancf_update_load_scale: the scale must be finite");
-  h->ld_list[k].scale = scale;
-  return h->ld_list[k].kind == 0 ? loads_build_traction(h) : loads_build_pressure_scale(h);
-}
-
-// ---- surface loads on the boundary faces of a T10 mesh (DESIGN 3h') ---------------------------------------------------------
-#define NEED_T10_LOADS(h, what) \
-  if ((h) && (h)->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)")
-static void boundary_faces_build(tlfea_t10_t h) {
-  if (h->bf_built) return;
-  h->bf = t10load::boundary_faces(h->E, h->N, h->h_conn, h->h_X0);
-  h->bf_built = true;
-}
-// Traction vector [N][3] = sum over the traction loads (list order), their faces (list order), the face's nodes and the
-// points of the rule (point order) of scale t w_q N_a(q) |X_xi x X_eta|(q): on the host, once per change.
-static int t10_loads_build_traction(tlfea_t10_t h) {
-  std::vector<double> tr((size_t)3 * h->N, 0.0);
-  for (const auto& L : h->ld_list) {
-    if (L.kind != 0) continue;
-    for (int k : L.elems) {
-      const int* nd = &h->bf.nodes[(size_t)k * 6];
-      double w[6];
-      t10load::traction_weights(nd, h->N, h->h_X0, w);
-      for (int a = 0; a < 6; a++)
-        for (int c = 0; c < 3; c++) tr[3 * (size_t)nd[a] + c] += L.scale * L.value[c] * w[a];
-    }
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_ld_tr, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
-  h->ld_const_dirty = true;
-  return 0;
-}
-// pe [loaded faces] = -(sum over the pressure loads (list order) of scale x pressure): the nodes are ordered outward
-static int t10_loads_build_pressure_scale(tlfea_t10_t h) {
-  std::vector<double> pf((size_t)h->bf.count(), 0.0);
-  for (const auto& L : h->ld_list)
-    if (L.kind == 1)
-      for (int k : L.elems) pf[k] += L.scale * L.value[0];
-  std::vector<double> pe(h->h_ld_lf.size());
-  for (size_t i = 0; i < pe.size(); i++) pe[i] = -pf[h->h_ld_lf[i]];
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_ld_pe, pe.data(), pe.size() * sizeof(double), hipMemcpyHostToDevice));
-  return 0;
-}
-static T10LoadView t10_load_view(tlfea_t10_t h) {
-  return T10LoadView{(int)h->h_ld_lf.size(), h->d_ld_fnodes, h->d_ld_pe, h->d_ld_lbuf};
-}
-
-extern "C" int tlfea_t10_get_boundary_faces(tlfea_t10_t h, int* n_faces, int* elem, int* local_face, int* nodes) {
-  NEED_T10_LOADS(h, "tlfea_t10_get_boundary_faces");
-  NEED_SETUP(h, "reading boundary faces.");
-  if (!n_faces) return fail("tlfea_t10_get_boundary_faces: null count");
-  boundary_faces_build(h);
-  *n_faces = h->bf.count();
-  if (elem) std::copy(h->bf.elem.begin(), h->bf.elem.end(), elem);
-  if (local_face) std::copy(h->bf.local_face.begin(), h->bf.local_face.end(), local_face);
-  if (nodes) std::copy(h->bf.nodes.begin(), h->bf.nodes.end(), nodes);
-  return 0;
-}
-extern "C" int tlfea_t10_set_surface_loads(tlfea_t10_t h, const tlfea_t10_surface_load* list, int n) {
-  NEED_T10_LOADS(h, "tlfea_t10_set_surface_loads");
-  NEED_SETUP(h, "setting surface loads.");
-  if (n < 0 || n > kMaxLoads)
-    return fail("tlfea_t10_set_surface_loads: n must be in 0.." + std::to_string(kMaxLoads) + ", got " + std::to_string(n));
-  if (n > 0 && !list) return fail("tlfea_t10_set_surface_loads: null list");
-  boundary_faces_build(h);
-  const int F = h->bf.count();
-  std::vector<tlfea_t10_s::SurfaceLoad> fresh((size_t)n);
-  std::vector<char> seen;
-  for (int k = 0; k < n; k++) {
-    const tlfea_t10_surface_load& L = list[k];
-    const std::string who = "tlfea_t10_set_surface_loads: load " + std::to_string(k) + ": ";
-    if (L.kind != 0 && L.kind != 1) return fail(who + "kind must be 0 (traction) or 1 (pressure), got " + std::to_string(L.kind));
-    for (int c = 0; c < (L.kind == 0 ? 3 : 1); c++)
-      if (!std::isfinite(L.value[c])) return fail(who + "the value must be finite");
-    if (!std::isfinite(L.scale)) return fail(who + "the scale must be finite");
-    if (L.n_faces <= 0 || !L.faces) return fail(who + "empty face list");
-    seen.assign((size_t)F, 0);
-    for (int i = 0; i < L.n_faces; i++) {
-      const int f = L.faces[i];
-      if (f < 0 || f >= F) return fail(who + "face " + std::to_string(f) + " outside 0.." + std::to_string(F - 1));
-      if (seen[f]) return fail(who + "face " + std::to_string(f) + " is listed twice");
-      seen[f] = 1;
-    }
-    fresh[k].kind = L.kind;
-    fresh[k].face = -1;
-    fresh[k].scale = L.scale;
-    for (int c = 0; c < 3; c++) fresh[k].value[c] = L.kind == 0 || c == 0 ? L.value[c] : 0.0;
-    fresh[k].elems.assign(L.faces, L.faces + L.n_faces);
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  surface_loads_free(h);
-  h->ld_const_dirty = true;
-  if (n == 0) {
-    if (!h->loads_on()) loads_free(h);
-    return 0;
-  }
-  TRY(loads_alloc_common(h));
-  h->ld_list.swap(fresh);
-  for (const auto& L : h->ld_list) (L.kind == 0 ? h->ld_n_trac : h->ld_n_press)++;
-  if (h->ld_n_trac > 0) {
-    TRY(dmalloc(&h->d_ld_tr, (size_t)3 * h->N));
-    TRY(loads_build_traction(h));
-  }
-  if (h->ld_n_press > 0) {
-    // the loaded faces, ascending; the rows of a node in ascending (loaded face, local node) order
-    std::vector<char> loaded((size_t)F, 0);
-    for (const auto& L : h->ld_list)
-      if (L.kind == 1)
-        for (int f : L.elems) loaded[f] = 1;
-    for (int f = 0; f < F; f++)
-      if (loaded[f]) h->h_ld_lf.push_back(f);
-    const size_t nlf = h->h_ld_lf.size();
-    std::vector<int> fnodes(nlf * 6), off((size_t)h->N + 1, 0), slot(nlf * 6);
-    for (size_t i = 0; i < nlf; i++)
-      for (int a = 0; a < 6; a++) {
-        fnodes[i * 6 + a] = h->bf.nodes[(size_t)h->h_ld_lf[i] * 6 + a];
-        off[fnodes[i * 6 + a] + 1]++;
-      }
-    for (int i = 0; i < h->N; i++) off[i + 1] += off[i];
-    std::vector<int> fill(off.begin(), off.end() - 1);
-    for (size_t r = 0; r < nlf * 6; r++) slot[fill[fnodes[r]]++] = (int)r;
-    TRY(dmalloc(&h->d_ld_fnodes, nlf * 6));
-    TRY(dmalloc(&h->d_ld_foff, (size_t)h->N + 1));
-    TRY(dmalloc(&h->d_ld_fslot, nlf * 6));
-    TRY(dmalloc(&h->d_ld_pe, nlf));
-    TRY(dmalloc(&h->d_ld_lbuf, nlf * 18));
-    HIP_TRY(hipMemcpy(h->d_ld_fnodes, fnodes.data(), fnodes.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_ld_foff, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_ld_fslot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->d_ld_lbuf, 0, nlf * 18 * sizeof(double)));
-    TRY(loads_build_pressure_scale(h));
-  }
-  return 0;
-}
-extern "C" int tlfea_t10_update_load_scale(tlfea_t10_t h, int k, double scale) {
-  NEED_T10_LOADS(h, "tlfea_t10_update_load_scale");
-  NEED_SETUP(h, "updating a load scale.");
-  if (k < 0 || k >= (int)h->ld_list.size())
-    return fail("tlfea_t10_update_load_scale: index " + std::to_string(k) + " outside the " +
-                std::to_string(h->ld_list.size()) + " surface loads set");
-  if (!std::isfinite(scale)) return fail("tlfea_t10_update_load_scale: the scale must be finite");
-  h->ld_list[k].scale = scale;
-  return h->ld_list[k].kind == 0 ? loads_build_traction(h) : loads_build_pressure_scale(h);
-}
-
-extern "C" int tlfea_get_load_forces(tlfea_t10_t h, double* f) {
-  NEED_SETUP(h, "reading load forces.");
-  if (!f) return fail("tlfea_get_load_forces: null output");
-  if (!h->loads_on()) {
-    std::fill(f, f + 3 * (size_t)h->N, 0.0);
-    return 0;
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(f, h->d_ld_f, 3 * (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-extern "C" int tlfea_get_load_resultant(tlfea_t10_t h, double out[3]) {
-  NEED_SETUP(h, "reading the load resultant.");
-  if (!out) return fail("tlfea_get_load_resultant: null output");
-  std::vector<double> f((size_t)3 * h->N);
-  TRY(tlfea_get_load_forces(h, f.data()));
-  const int stride = h->kind == kT10 ? 1 : 4;  // the position coefficients, ascending
-  out[0] = out[1] = out[2] = 0.0;
-  for (int i = 0; i < h->N; i += stride)
-    for (int c = 0; c < 3; c++) out[c] += f[3 * (size_t)i + c];
   return 0;
 }
 
@@ -1366,350 +998,6 @@ extern "C" const double* tlfea_t10_z12_device_ptr(tlfea_t10_t h) { return h->d_z
 extern "C" double* tlfea_t10_external_force_device_ptr(tlfea_t10_t h) { return h->d_fext; }
 extern "C" double* tlfea_t10_constraint_device_ptr(tlfea_t10_t h) { return h->d_cons; }
 
-// =================================================================================================
-// One single-precision polynomial step (launch_cheb32) takes its operands from three places: the level (C32Level), the
-// level's ping-pong vectors (C32Vecs) and the call (rows, coefficient pair, outputs of the last step); c32_step() below.
-struct C32Level {
-  int nnz;
-  Incidence inc;
-  const void *B8, *B1;  // the level's low-precision scaled copy, 8 + 1 entries per block
-  int bits;
-  const double* sc;
-  int geo;  // slot of tlfea_newton_s::c32_geo the launch geometry is recorded in; -1: not recorded
-};
-struct C32Vecs {  // d, z^, res^ and their ping-pong partners (6 x n floats), then (S D S)^-1 (3 n)
-  float *d, *d2, *z, *z2, *r, *r2;
-  const float* Dinv_f;
-  C32Vecs(float* base, size_t n)
-      : d(base), d2(base + n), z(base + 2 * n), z2(base + 3 * n), r(base + 4 * n), r2(base + 5 * n), Dinv_f(base + 6 * n) {}
-  void swap() { std::swap(d, d2); std::swap(z, z2); std::swap(r, r2); }
-};
-// partition-boundary nodes of a level (tlfea_newton_set_interface): their rows are summed over ranks
-struct LevelIface {
-  int n_loc, n_glob;  // boundary nodes on this rank / slots of the exchange buffer
-  const int *d_node, *d_slot;
-  const int* d_bslot;  // [N] exchange slot of a boundary node, -1 inside
-};
-
-// A coarse level of the p-multigrid cycle (vertex level, third level): pattern, operator, block-Jacobi scaling, the
-// low-precision copy its polynomial streams, and the work vectors.  The fine level keeps its members in tlfea_newton_s.
-struct PolyLevel {
-  int N = 0, nnz = 0;  // nodes, 3 x 3 blocks
-  int *d_off = nullptr, *d_cols = nullptr, *d_diagpos = nullptr;
-  double *d_H = nullptr, *d_D = nullptr, *d_Dinv = nullptr, *d_sc = nullptr, *d_Dinv_s = nullptr;
-  double *d_eigv = nullptr, *d_q = nullptr, *d_p = nullptr;  // power iteration: the kept vector and two work vectors
-  void *d_B8 = nullptr, *d_B1 = nullptr;
-  int bits_alloc = 0;
-  float* d_f32 = nullptr;  // C32Vecs(d_f32, 3 N)
-  double lam = 0.0;        // lambda_max(D^-1 H) estimate, warm-started across solves
-  Incidence inc() const { return Incidence{nullptr, nullptr, nullptr, d_off, d_cols, d_diagpos}; }
-  C32Level c32(int bits, int geo) const { return C32Level{nnz, inc(), d_B8, d_B1, bits, d_sc, geo}; }
-  int alloc_work() {  // once N and nnz are known
-    const size_t n = 3 * (size_t)N;
-    TRY(dmalloc(&d_H, (size_t)9 * nnz));
-    TRY(dmalloc(&d_D, (size_t)9 * N)); TRY(dmalloc(&d_Dinv, (size_t)9 * N));
-    TRY(dmalloc(&d_sc, n)); TRY(dmalloc(&d_Dinv_s, (size_t)9 * N));
-    TRY(dmalloc(&d_eigv, n)); TRY(dmalloc(&d_q, n)); TRY(dmalloc(&d_p, n));
-    TRY(dmalloc(&d_f32, 6 * n + (size_t)9 * N));
-    return 0;
-  }
-  int ensure_copy(int bits) {  // storage of the low-precision copy at `bits` per entry
-    if (bits_alloc == bits) return 0;
-    if (d_B8) (void)hipFree(d_B8);
-    if (d_B1) (void)hipFree(d_B1);
-    d_B8 = d_B1 = nullptr;
-    HIP_TRY(hipMalloc(&d_B8, (size_t)nnz * 8 * (bits / 8)));
-    HIP_TRY(hipMalloc(&d_B1, (size_t)nnz * (bits / 8)));
-    bits_alloc = bits;
-    return 0;
-  }
-  void release() {
-    void* p[] = {d_off, d_cols, d_diagpos, d_H, d_D, d_Dinv, d_sc, d_Dinv_s, d_eigv, d_q, d_p, d_B8, d_B1, d_f32};
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-    *this = PolyLevel();
-  }
-};
-
-struct tlfea_newton_s {
-  tlfea_t10_t d = nullptr;
-  int N = 0, n_constraints = 0;
-  bool cons_enabled = false;     // constructed with n_constraints > 0: the reference gates every constraint term on it
-  int n_constraints_global = 0;  // over all ranks (control flow must be identical on every rank)
-  tlfea_newton_params prm{1e-4, 1e-4, 1e-4, 1e14, 5, 10, 1e-3};
-  tlfea_linsolve_opts lin{1e-12, 20000, 25, 0, 0.0, 0, 0, 0, 0};
-  double lin_last_rel = 0.0, lin_worst_rel = 0.0;  // ||r||/||b|| of the last linear solve / the worst since the step began
-  bool lin_last_ok = true, lin_all_ok = true;
-  double lam_max = 0.0;       // estimate of lambda_max(D^-1 H) (power iteration, warm-started across solves)
-  double lam_safety = 1.15;   // the polynomial's interval ends at lam_safety * lam_max (power iteration converges from below)
-  double* d_eigv = nullptr;   // its vector
-  double *d_cd = nullptr, *d_cd2 = nullptr, *d_cres = nullptr;  // Chebyshev work vectors
-  // low-precision scaled copy of H streamed by the Chebyshev steps (lin.cheb_bits 16/32): 8+1 entries per block
-  void *d_B8 = nullptr, *d_B1 = nullptr;
-  int lp_bits_alloc = 0;
-  // The copy belongs to the H, d_sc and d_D of ONE stage-0 set-up (precond_setup): lp_scaled = that stage ran the scaling,
-  // lp_current = the copy was converted from them since, lp_converts = fine-level conversions since creation.  A set-up
-  // that can still choose the matrix-free fine smoother defers the conversion (ensure_fine_copy, DESIGN 3g').
-  bool lp_scaled = false, lp_current = false;
-  int lp_converts = 0;
-  double *d_sc = nullptr, *d_Dinv_s = nullptr;
-  double *d_cz = nullptr, *d_cz2 = nullptr, *d_cres2 = nullptr;  // ping-pong partners of z / res in the LP steps
-  // two-level p-multigrid preconditioner (T10, single GPU): see pmg_host.h / pmg_apply()
-  struct Pmg {
-    bool tried = false, ok = false;
-    PolyLevel vertex;  // the vertex level: Hc = P^T H P
-    int *d_par0 = nullptr, *d_par1 = nullptr, *d_cblk_row = nullptr, *d_child_off = nullptr, *d_child = nullptr,
-        *d_con_off = nullptr, *d_con_base = nullptr, *d_con_deg = nullptr;
-    int n_upper = 0;  // Galerkin gather: blocks with column >= row (d_c_upper), the rest mirrored through d_c_mirror
-    int *d_c_upper = nullptr, *d_c_mirror = nullptr;
-    float *d_child_w = nullptr, *d_con_w = nullptr;
-    // T10: Hc from an image of the R row (pmg_host.h GalRowsHost, pmg_galerkin_rows_kernel) -- the ONE arithmetic of every
-    // conforming T10 set-up whose lists fit; the gather lists above are then not on the device.  The row structure it walks
-    // is rop's (d_off .. d_ch_w, d_pos_off, d_con_pos), up whether or not R itself is built.
-    struct Rows {
-      bool ok = false;
-      int *d_row = nullptr, *d_off = nullptr, *d_long_rows = nullptr;
-      unsigned short* d_pos = nullptr;
-      unsigned char* d_w = nullptr;
-      int cap = 0, n_long = 0, ws_rows = 0;  // image capacity in blocks; the rows beyond it, and how many a launch takes
-      size_t ws_stride = 0;                  // doubles per slice of d_ws: nine times the longest of them
-      double* d_ws = nullptr;
-    } rows;
-    // which kernel of the last set-up left vertex.d_H: 1 the gather, 2 the row kernel alone, 3 fused with the build of R;
-    // 0: no set-up yet, or a read-back has summed Hc again since
-    int hc_form = 0;
-    double* d_coef = nullptr;  // the cycle's coefficient table (pmg_coef.h, PmgTable), kPmgTableCap doubles
-    // multi-GPU: the coarse level is partitioned like the fine one (vertex nodes of the partition boundary are
-    // replicated); slots of the coarse exchange buffer are agreed once (pmg_prepare), child weights carry 1/multiplicity
-    int n_ifc_loc = 0, n_ifc_glob = 0;
-    int Nc_glob = 0;                  // coarse nodes over all ranks: what the coarse polynomial's degree goes by (every
-                                      // rank must run the same number of steps -- each is a collective)
-    int *d_ifc_node = nullptr, *d_ifc_slot = nullptr, *d_bslot_c = nullptr;
-    double* d_wc3 = nullptr;          // [3 Nc] 1/multiplicity of the coarse DOFs
-    float* d_child_w_dist = nullptr;  // child weights x 1/multiplicity of the child
-    // the coarse polynomial's degree is a size-based guess (fitted on configs B, C); when a solve stalls because the
-    // vertex-level operator is worse conditioned than the guess covers (a 5 x 3.3 x 1.7 bar of 4.5 M elements needs
-    // degree ~50 where the guess says 39), the solver raises it for this and all later solves
-    double kc_boost = 1.0;
-    // restricted fine operator R = S_c P^T S_f^-1 Hs (pmg_host.h pmg_restrict_op_build; one GPU, first-kind smoother):
-    // pattern and contribution lists with the hierarchy, values (fp32, 8 + 1 per block) rebuilt by pmg_build_level
-    struct Rop {
-      bool ok = false, built = false;
-      int nnz = 0, n_con = 0;
-      int *d_off = nullptr, *d_cols = nullptr, *d_ch_off = nullptr, *d_ch = nullptr, *d_con_off = nullptr,
-          *d_con_blk = nullptr;
-      unsigned char* d_con_ord = nullptr;
-      float *d_ch_w = nullptr, *d_R1 = nullptr;
-      void* d_R8 = nullptr;
-      // positions by source, for the kernels that stream each child's row of H (Rows); stream_cap > 0: a matrix-free
-      // set-up builds R in that pass too
-      int* d_pos_off = nullptr;
-      unsigned short* d_con_pos = nullptr;
-      int stream_cap = 0;
-    } rop;
-    LevelIface iface() const { return LevelIface{n_ifc_loc, n_ifc_glob, d_ifc_node, d_ifc_slot, d_bslot_c}; }
-    // third level: rigid-body-mode aggregates of the vertex level (pmg_host.h agg_build); lvl.N = 2 Na nodes
-    struct Agg {
-      bool ok = false, bins = false;
-      double size_ratio = 0.0;  // bins: cell size in mean vertex edges (0: greedy aggregates, ~2.2)
-      double* d_r3 = nullptr;  // overlapping partition: this rank's share of the level-3 residual (summed over ranks)
-      int Na = 0, n_pairs = 0;
-      PolyLevel lvl;           // H3 = P2^T Hc P2
-      int *d_agg = nullptr, *d_active = nullptr, *d_mem_off = nullptr, *d_mem = nullptr, *d_pair_A = nullptr,
-          *d_pair_pos = nullptr, *d_pair_B = nullptr, *d_pcon_off = nullptr, *d_pcon_base = nullptr, *d_pcon_deg = nullptr,
-          *d_pcon_i = nullptr, *d_pcon_j = nullptr;
-      double* d_rvec = nullptr;
-    } agg;
-  } pmg;
-  LevelIface iface() const { return LevelIface{n_if_loc, n_if_glob, d_if_node, d_if_slot, d_bslot_f}; }
-  float* d_f32 = nullptr;  // single-precision polynomial (single GPU): d, z, res ping-pong pairs (6 x 3N) + (SDS)^-1 (9N)
-  bool fixed_pattern = false, sparsity_done = false;
-  int verbose = 0;
-  // Launch stream.  Single GPU: an own (blocking) stream, so that the CG iteration can be captured as a hipGraph
-  // (the legacy default stream cannot be captured; a blocking stream still orders against the data object's
-  // default-stream copies and kernels).  With a multi-GPU interface set: the default stream, the one the host's
-  // collective (torch.distributed) orders against.
-  hipStream_t stream = nullptr, stream_own = nullptr;
-  double *d_v = nullptr, *d_vprev = nullptr, *d_lam = nullptr, *d_g = nullptr, *d_dv = nullptr, *d_r = nullptr,
-         *d_b = nullptr;
-  double *d_step0 = nullptr, *d_lam0 = nullptr;  // v | v_prev and lambda at the start of the running step (roll-back)
-  int lam0_cap = 0;
-  // what the last Solve() left for tlfea_newton_adjoint_step: 0 no Solve yet, 1 one outer iteration whose Newton loop met
-  // its tolerance, 2 more than one outer iteration, 3 the step failed, 4 the Newton loop ran out of iterations
-  int adj_state = 0;
-  bool profiling = false;  // per-stage hipEvent timing (adds a host sync per stage)
-  int pcg_fused = -1;  // -1 auto (fused direction update below 200k nodes), 0/1 forced (TLFEA_PCG_FUSED)
-  bool spmv_nt = false; // non-temporal loads of H in the SpMV (TLFEA_SPMV_NT): measured slower at config C
-  double *d_xp = nullptr, *d_yp = nullptr, *d_zp = nullptr;
-  double *d_H = nullptr, *d_Kbuf = nullptr, *d_Dinv = nullptr;
-  // fused tangent + assembly (T10, SVK): row groups (rowgroup_host.h) and the per-point F of the last residual launch.
-  // asm_mode (TLFEA_ASSEMBLE=kbuf|direct): 0 auto = fused where it applies, 1 always the two-kernel path via Kbuf
-  RowGroups rg{0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int* d_rg[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool rg_ok = false;
-  bool fq_in_residual = true;  // first-order solvers (AdamW, Nesterov, VBD) never assemble: their residual skips Fq
-  int asm_mode = 0;
-  int rg_passes = 0, rg4_passes = 0;  // entries of the pass tables of rg / rg4
-  // nodes whose row of H is empty (no element, no general linear constraint row): the first and how many (analyze_hessian_sparsity)
-  int iso_first = -1, iso_count = 0;
-  double* d_Fq = nullptr;
-  // affine-element form of the fused kernel (straight-sided elements + the 5-point Keast rule): its work lists, the
-  // per-element vertex gradients; d_Fq then holds F per point, [E][5][10].  TLFEA_ASSEMBLE=general keeps the general form.
-  RowGroups4 rg4{0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int* d_rg4[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  AffineView av{nullptr, 0, {0, 0, 0, 0}};
-  double* d_gvec = nullptr;
-  double* d_cmass = nullptr;  // [10][16] element mass coefficients in the kernel's (row node, vertex n, p) order
-  bool affine_ok = false;
-  long geom_gen_seen = -1;   // data->geom_gen the affine cache (gvec, affine_ok) was built from
-  double affine_dev = -1.0;  // largest relative deviation from the affine form found at set-up (-1: not checked)
-  // Matrix-free product of the CG iteration: q = H p from gvec and the F records in d_Fq instead of the CSR
-  // stream.  `valid`: d_Fq, gvec and the scalars below are those H was assembled from -- set by the affine assembly,
-  // cleared by every residual launch that rewrites d_Fq (the next assembly sets it again) and by a new affine set-up.
-  struct Matfree {
-    bool valid = false;
-    MatfreeCoef mc{};
-    const int* fixed = nullptr;  // pinned rows of the assembled H (null: none)
-    double penalty = 0.0;
-    double* d_ybuf = nullptr;    // [10][Epad][3] element rows, allocated on first use; compact form: [rows][3]
-    // compact form (matfree_compact.h, TLFEA_MATFREE_COMPACT): the lists, built and uploaded with d_ybuf
-    bool compact = false;
-    MatfreeCompact cp{nullptr, nullptr, nullptr, nullptr, nullptr};
-    void* d_cp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    long cp_rows = 0;
-    double cp_ratio = 0.0;       // 10 E / rows
-    bool now = false;           // the running / last solve takes the matrix-free product
-    int last_mode = 0;           // tlfea_newton_get_spmv_mode
-    long gen = 0;                // counts the assemblies that claimed the records (fine smoother: whose records its copies are)
-  } mf;
-  // Fine smoother of the p-multigrid cycle from the element records (DESIGN 3g'): float copies of gvec and d_Fq, the
-  // normalised scaling, and the choice the last preconditioner set-up took.  The copies belong to assembly `gen`; an
-  // application that finds mf.valid cleared or another assembly fails (pmg_apply).
-  struct FineMf {
-    bool now = false;            // the last preconditioner set-up chose it (taken once, before R is built)
-    int last = 0;                // tlfea_newton_get_fine_smoother
-    long gen = -1;               // mf.gen the float F records were converted at
-    bool g_ok = false;           // the float g records are those of the current affine set-up
-    float *d_g32 = nullptr, *d_F32 = nullptr, *d_scn = nullptr;
-    double* d_ss = nullptr;      // sum(sc^2)
-    FineMatfree v{};
-  } fmf;
-  // sparse direct solve (lin.method == 1): rocSOLVER re-factorisation on a host-computed ordering + factor pattern
-  struct Direct {
-    bool tried = false, ok = false;
-    int backend = 0;  // 0: the engine's multifrontal Cholesky (direct_kernels.hip), 1: rocSOLVER (TLFEA_DIRECT_BACKEND=rocsolver)
-    int n = 0, nnzT = 0;
-    void *blas = nullptr, *rfinfo = nullptr;
-    int *d_ptrA = nullptr, *d_indA = nullptr, *d_ptrT = nullptr, *d_indT = nullptr, *d_pivQ = nullptr;
-    double* d_valT = nullptr;
-    MfPlan plan;      // host plan (levels, panel steps); the device copies below
-    MfDev dev{};
-    MfTally tally;    // launches of the last native factorisation + solve (tlfea_newton_get_direct_info)
-    std::vector<void*> owned;  // device allocations of the native backend
-    double factor_ms = 0.0, solve_ms = 0.0;
-  } direct;
-  double* d_mbuf = nullptr;   // T10: per (element, node) force row | inertia row M_e (v - v_prev) / h of the residual launch
-  int mass_mode = 0;          // TLFEA_MASS=csr: always the mass CSR product in grad_kernel
-  double *d_p = nullptr, *d_p2 = nullptr, *d_q = nullptr, *d_zv = nullptr;
-  double* d_parts = nullptr;  // 6 x kNPart: rz[2], pq, rr, bb, norm
-  // read-back hook (tlfea_newton_get_c32_geometry): the last NON-FINAL polynomial step launched on the fine level [0],
-  // the vertex level [1] and the third level [2]; regime -1 = none yet
-  C32Geometry c32_geo[3] = {{-1}, {-1}, {-1}};
-  C32Geometry* geo_out(int level, bool last) { return last ? nullptr : &c32_geo[level]; }
-  double* d_scal = nullptr;   // 4 scalars
-  double* h_pin = nullptr;    // pinned host words: [0..7] scalars read back, [8..] Chebyshev coefficients to upload
-  double* d_coef = nullptr;   // Chebyshev coefficients on the device (2 per step)
-  hipGraphExec_t cg_graph[3] = {nullptr, nullptr, nullptr};  // CG iteration of even / odd parity / odd + residual replacement
-  // Mixed-precision outer iteration (single GPU, fp32 polynomial path): the CG's SpMV streams a single-precision copy of
-  // H (half the bytes of the iteration's largest launch); every `spmv32_every` iterations -- and before convergence is
-  // declared -- the residual is replaced by b - H x in fp64 on H itself (reliable updates), so the attained residual
-  // and the stopping test are those of the fp64 system.  OPT-IN (TLFEA_SPMV32 = replacement period, even; 0 = off = the
-  // default): measured at config C it saves 2.6 % of a Newton iteration with period 8, stagnates at 5e-11 with period
-  // 16, and on ill-conditioned systems (welded ANCF net, penalty 1e14: cond(H) eps_fp32 > 1) it stagnates at 7e-9 --
-  // each replacement restarts from the error of the fp32 copy.  Kept as an experiment switch, not a default.
-  float* d_H32 = nullptr;
-  int spmv32_every = 0;
-  bool spmv32_now = false;       // this solve runs the mixed-precision iteration
-  const double* cur_b = nullptr; // right-hand side of the running solve (residual replacement)
-  long n_replacements = 0;
-  long cg_graph_key[6] = {0, 0, 0, 0, 0, 0};
-  // test hook tlfea_newton_cg_trace: while set, pcg() runs exactly `k` iterations without convergence tests and copies the
-  // iterates to the host after its start and after every iteration (cg_trace_record)
-  struct CgTrace {
-    int k = 0;
-    double *vecs = nullptr, *sums = nullptr, *slots = nullptr;  // host: [(k+1)][5][3N], [(k+1)][4], [(k+1)][5][kNPart]
-    int* form = nullptr;                                        // host: kCgTraceForm ints
-  };
-  CgTrace* trace = nullptr;
-  bool use_graphs = true;     // TLFEA_GRAPH=0 launches every kernel eagerly
-  int last_outer_iters = 0;   // CG iterations of the previous solve: where the next one starts testing convergence
-  // ANCF: 12 x 12 node-block scaling of the polynomial's operator (solver_kernels.hip, blk12_*): -1 not decided yet
-  int blk12 = -1;
-  double* d_L12inv = nullptr;
-  float* d_L12inv_f = nullptr;
-  int* d_blk12_err = nullptr;
-  int last_deg = 0, last_bits = 0;
-  int h_nnz = 0;
-  std::vector<int> h_row_offsets, h_col_indices;  // reference DOF-level CSR index arrays (host)
-  double stats[6] = {0, 0, 0, 0, 0, 0};
-  double stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double stage_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hipEvent_t ev[8] = {nullptr};
-  // multi-GPU interface
-  int n_if_loc = 0, n_if_glob = 0;  // local interface nodes / slots of the global exchange buffer
-  int *d_if_node = nullptr, *d_if_slot = nullptr;
-  int* d_bslot_f = nullptr;         // [N] exchange slot of a partition-boundary node, -1 inside
-  std::vector<int> h_if_node, h_if_slot;
-  std::vector<double> h_nw;
-  long n_collectives = 0;           // all-reduce calls since the solver was built (tests: collectives per CG iteration)
-  double *d_ibuf = nullptr, *d_w = nullptr, *d_nw = nullptr, *d_wc = nullptr, *d_D = nullptr;
-  // rank-local polynomial preconditioner (multi-GPU): 1 for the nodes this rank owns (every replicated node has
-  // exactly one owner), and the scaling vector masked by it
-  int* d_own = nullptr;
-  double* d_sc_mask = nullptr;
-  double lam_max_loc = 0.0;
-  bool lmax_mf_ok = false;    // set by pcg() around its own set-up call: the fine lambda_max product may be matrix-free
-  bool lmax_used_mf = false;  // the last fine estimate used the matrix-free product (tlfea_newton_get_lambda_max)
-  double hook_lam[3] = {0.0, 0.0, 0.0};  // lambda_max estimates of the last tlfea_newton_apply_preconditioner set-up
-  bool sync_before_cb = true;
-  tlfea_allreduce_fn ar = nullptr;
-  void* ar_user = nullptr;
-  // Overlapping partition (tlfea_newton_set_halo): owner-computes with ghost layers.  `ar` stays null -- no boundary
-  // sums exist -- so every launch sequence is the single-GPU one; the hooks are ghost refreshes, owner-weighted dot
-  // products summed with halo.arfn, and row counts that stop at the layers a launch can still compute correctly.
-  struct HaloPlan {   // "refresh ghost layers <= D" of one level: concatenated per-peer prefixes of the send / recv lists
-    int n_send = 0, n_recv = 0;
-    int *d_sidx = nullptr, *d_ridx = nullptr;
-    std::vector<long long> soff, roff;   // [n_peers + 1], in nodes
-  };
-  struct HaloLevel {  // per-peer segments, each ordered by (layer on the receiving side, global id)
-    std::vector<int> send_off, send_nodes, send_layer, recv_off, recv_nodes, recv_layer;
-    std::map<int, HaloPlan> plans;
-  };
-  struct Halo {
-    bool on = false, native = false;
-    int depth = 0, rank = 0, world = 0;
-    std::vector<int> peers, layer, n_upto;   // n_upto[k] = local nodes of layers <= k (k = 0 .. depth)
-    std::vector<int> n_upto_c;               // the same for the coarse (vertex) level
-    HaloLevel lv[2];                         // 0 fine, 1 coarse
-    void *d_sbuf = nullptr, *d_rbuf = nullptr;
-    size_t cap_s = 0, cap_r = 0;
-    double* d_red = nullptr;                 // staging of the reduction slots
-    tlfea_halo_exchange_fn xfn = nullptr;
-    tlfea_allreduce_fn arfn = nullptr;
-    void* user = nullptr;
-    bool sync_cb = true;
-    long n_exch = 0, n_allred = 0, n_cg_iters = 0, n_exch_cg = 0, n_allred_cg = 0;
-    double bytes_exch = 0.0, bytes_allred = 0.0, comm_ms = 0.0;
-    bool in_cg = false;                       // inside enqueue_cg_iteration: what the per-iteration budget counts
-    double graph_cost[3][5] = {{0}};          // per captured graph: exchanges, all-reduces, bytes, bytes, iterations (added per replay)
-    std::vector<long long> so_b, ro_b;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int rows(int k) const { return n_upto[std::max(0, std::min(k, depth))]; }
-    int rows_c(int k) const { return n_upto_c[std::max(0, std::min(k, depth))]; }
-  } halo;
-};
-
 extern "C" int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_newton_t* out) {
   if (!data || !out) return fail("tlfea_newton_create: null argument");
   // The reference sizes lambda from this count and indexes it with the data object's constraint ids: any other value
@@ -1757,7 +1045,6 @@ extern "C" int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_ne
 }
 
 static void cg_graphs_destroy(tlfea_newton_t s);
-static void direct_destroy(tlfea_newton_t s);
 static void halo_free_plans(tlfea_newton_s::HaloLevel& L);
 extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
   if (!s) return 0;
@@ -2187,260 +1474,18 @@ extern "C" int tlfea_newton_set_interface(tlfea_newton_t s, const int* iface_nod
   return 0;
 }
 
-// ---- built-in RCCL all-reduce (opt-in): the collective is enqueued from C++ on the stream the solver launches on -------
-namespace {
-struct RcclApi {
-  void* lib = nullptr;
-  int (*get_unique_id)(void*) = nullptr;
-  int (*comm_init_rank)(void**, int, RcclUniqueId, int) = nullptr;
-  int (*all_reduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*comm_destroy)(void*) = nullptr;
-  const char* (*error_string)(int) = nullptr;
-  int (*send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*group_start)() = nullptr;
-  int (*group_end)() = nullptr;
-};
-RcclApi& rccl_api() {
-  static RcclApi a;
-  if (a.lib) return a;
-  for (const char* name : {"librccl.so", "librccl.so.1"}) {
-    a.lib = dlopen(name, RTLD_NOW | RTLD_NOLOAD);  // the copy the process already uses (torch's), if any
-    if (a.lib) break;
-  }
-  if (!a.lib)
-    for (const char* name : {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
-      a.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-      if (a.lib) break;
-    }
-  if (!a.lib) return a;
-  a.get_unique_id = (int (*)(void*))dlsym(a.lib, "ncclGetUniqueId");
-  a.comm_init_rank = (int (*)(void**, int, RcclUniqueId, int))dlsym(a.lib, "ncclCommInitRank");
-  a.all_reduce = (int (*)(const void*, void*, size_t, int, int, void*, hipStream_t))dlsym(a.lib, "ncclAllReduce");
-  a.comm_destroy = (int (*)(void*))dlsym(a.lib, "ncclCommDestroy");
-  a.error_string = (const char* (*)(int))dlsym(a.lib, "ncclGetErrorString");
-  a.send = (int (*)(const void*, size_t, int, int, void*, hipStream_t))dlsym(a.lib, "ncclSend");
-  a.recv = (int (*)(void*, size_t, int, int, void*, hipStream_t))dlsym(a.lib, "ncclRecv");
-  a.group_start = (int (*)())dlsym(a.lib, "ncclGroupStart");
-  a.group_end = (int (*)())dlsym(a.lib, "ncclGroupEnd");
-  if (!a.get_unique_id || !a.comm_init_rank || !a.all_reduce || !a.comm_destroy) a.lib = nullptr;
-  return a;
-}
-int rccl_fail(const char* what, int rc) {
-  RcclApi& a = rccl_api();
-  return fail(std::string(what) + ": " + (a.error_string ? a.error_string(rc) : "RCCL error " + std::to_string(rc)));
-}
-// stream the built-in callbacks enqueue on: the null stream on the boundary-sum path (its launch stream once an interface
-// is set), the solver's own stream on the overlapping-partition path (set by the engine around every call)
-thread_local hipStream_t g_rccl_stream = nullptr;
-int rccl_allreduce_cb(void* comm, double* d_buf, int n) {  // sum of n doubles in place
-  RcclApi& a = rccl_api();
-  const int rc = a.all_reduce(d_buf, d_buf, (size_t)n, /*ncclDouble*/ 8, /*ncclSum*/ 0, comm, g_rccl_stream);
-  return rc == 0 ? 0 : 1;
-}
-// one group of send / recv pairs per ghost refresh (ncclGroup makes the pairs deadlock-free in any order)
-int rccl_halo_exchange_cb(void* comm, const void* d_send, void* d_recv, int n_peers, const int* peers,
-                          const long long* so, const long long* ro) {
-  RcclApi& a = rccl_api();
-  if (!a.send || !a.recv || !a.group_start || !a.group_end) return 1;
-  int rc = a.group_start();
-  for (int k = 0; k < n_peers && rc == 0; k++) {
-    const long long ns = so[k + 1] - so[k], nr = ro[k + 1] - ro[k];
-    if (ns > 0) rc = a.send((const char*)d_send + so[k], (size_t)ns, /*ncclInt8*/ 0, peers[k], comm, g_rccl_stream);
-    if (rc == 0 && nr > 0) rc = a.recv((char*)d_recv + ro[k], (size_t)nr, /*ncclInt8*/ 0, peers[k], comm, g_rccl_stream);
-  }
-  const int rc2 = a.group_end();
-  return (rc == 0 && rc2 == 0) ? 0 : 1;
-}
-}  // namespace
-
-extern "C" int tlfea_rccl_unique_id(char* id128) {
-  RcclApi& a = rccl_api();
-  if (!a.lib) return fail("tlfea_rccl: librccl.so could not be resolved");
-  RcclUniqueId id;
-  const int rc = a.get_unique_id(&id);
-  if (rc) return rccl_fail("ncclGetUniqueId", rc);
-  std::memcpy(id128, id.internal, 128);
-  return 0;
-}
-extern "C" int tlfea_rccl_comm_create(const char* id128, int rank, int world, void** comm_out) {
-  RcclApi& a = rccl_api();
-  if (!a.lib) return fail("tlfea_rccl: librccl.so could not be resolved");
-  RcclUniqueId id;
-  std::memcpy(id.internal, id128, 128);
-  void* comm = nullptr;
-  const int rc = a.comm_init_rank(&comm, world, id, rank);
-  if (rc) return rccl_fail("ncclCommInitRank", rc);
-  *comm_out = comm;
-  return 0;
-}
-extern "C" int tlfea_rccl_comm_destroy(void* comm) {
-  RcclApi& a = rccl_api();
-  if (!a.lib || !comm) return 0;
-  HIP_TRY(hipDeviceSynchronize());
-  const int rc = a.comm_destroy(comm);
-  return rc ? rccl_fail("ncclCommDestroy", rc) : 0;
-}
-extern "C" tlfea_allreduce_fn tlfea_rccl_allreduce_fn(void) { return rccl_allreduce_cb; }
-
-extern "C" tlfea_halo_exchange_fn tlfea_rccl_halo_exchange_fn(void) { return rccl_halo_exchange_cb; }
-
-// A collective that never completes cannot be abandoned: the watchdog reports and ends the process (exit code 97), so the
-// launcher sees a failed rank instead of a hang.
-[[noreturn]] static void rccl_watchdog_abort(const char* what, int rank, double timeout_s) {
-  std::fprintf(stderr, "tlfea: rank %d: %s did not complete within %.0f s -- giving up (exit 97)\n", rank, what, timeout_s);
-  std::fflush(stderr);
-  _exit(97);
-}
-extern "C" int tlfea_rccl_comm_create_timeout(const char* id128, int rank, int world, double timeout_s, void** comm_out) {
-  RcclApi& a = rccl_api();
-  if (!a.lib) return fail("tlfea_rccl: librccl.so could not be resolved");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::atomic<int> done{0};
-  int rc = 0;
-  void* comm = nullptr;
-  RcclUniqueId id;
-  std::memcpy(id.internal, id128, 128);
-  std::thread t([&] {
-    (void)hipSetDevice(dev);
-    rc = a.comm_init_rank(&comm, world, id, rank);
-    done.store(1);
-  });
-  const auto t0 = std::chrono::steady_clock::now();
-  while (!done.load()) {
-    std::this_thread::sleep_for(std::chrono::milliseconds(20));
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) {
-      t.detach();
-      rccl_watchdog_abort("ncclCommInitRank", rank, timeout_s);
-    }
-  }
-  t.join();
-  if (rc) return rccl_fail("ncclCommInitRank", rc);
-  *comm_out = comm;
-  return 0;
-}
+// ---- overlapping partition ------------------------------------------------------------------------------------------------
 // hipGraph replay of the partitioned CG iteration (collectives included): on unless TLFEA_HALO_GRAPH=0, and off for the
-// process once the self-check below finds that RCCL cannot be captured / replayed here
+// process once the self-check (rccl_api.hip) or a failed capture of the iteration finds that RCCL cannot be captured /
+// replayed here
 static bool g_rccl_graph_ok = true;
-static bool halo_graph_wanted() {
+bool tlfea::halo_graph_wanted() {
   static const bool on = env_flag("TLFEA_HALO_GRAPH", true);
   return on && g_rccl_graph_ok;
 }
-extern "C" int tlfea_rccl_self_check(void* comm, int rank, int world, double timeout_s) {
-  RcclApi& a = rccl_api();
-  if (!a.lib || !comm) return fail("tlfea_rccl_self_check: no communicator");
-  hipStream_t st = nullptr;
-  HIP_TRY(hipStreamCreate(&st));
-  double* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 8 * sizeof(double)));
-  // all-reduce: sum over ranks of (rank + 1) and of (rank + 1)^2; ring: every rank sends 1000 + rank to rank + 1
-  double h[8] = {rank + 1.0, (rank + 1.0) * (rank + 1.0), 1000.0 + rank, 0, -1.0, 0, 0, 0};
-  HIP_TRY(hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice));
-  g_rccl_stream = st;
-  int rc = rccl_allreduce_cb(comm, d, 2);
-  if (rc == 0 && world > 1) {
-    const int next = (rank + 1) % world, prev = (rank + world - 1) % world;
-    rc = a.group_start();
-    if (rc == 0) rc = a.send(d + 2, sizeof(double), 0, next, comm, st);
-    if (rc == 0) rc = a.recv(d + 4, sizeof(double), 0, prev, comm, st);
-    const int rc2 = a.group_end();
-    rc = rc ? rc : rc2;
-  }
-  g_rccl_stream = nullptr;
-  if (rc) {
-    (void)hipFree(d);
-    (void)hipStreamDestroy(st);
-    return fail("tlfea_rccl_self_check: RCCL refused the check collectives");
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  while (hipStreamQuery(st) == hipErrorNotReady) {
-    std::this_thread::sleep_for(std::chrono::milliseconds(5));
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s)
-      rccl_watchdog_abort("the RCCL self-check (all-reduce + ring send/recv)", rank, timeout_s);
-  }
-  HIP_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-  const double s1 = world * (world + 1.0) / 2.0, s2 = world * (world + 1.0) * (2.0 * world + 1.0) / 6.0;
-  const double ring = world > 1 ? 1000.0 + (rank + world - 1) % world : -1.0;
-  if (h[0] != s1 || h[1] != s2 || h[4] != ring) {
-    std::fprintf(stderr, "tlfea: rank %d: RCCL self-check WRONG ANSWER: all-reduce %.17g %.17g (expected %.17g %.17g), ring %.17g "
-                 "(expected %.17g) -- giving up (exit 97)\n", rank, h[0], h[1], s1, s2, h[4], ring);
-    std::fflush(stderr);
-    _exit(97);
-  }
-  // The same collectives once more, captured in a hipGraph and replayed -- what the solver does with its CG iteration.
-  // A capture RCCL refuses, or a replay with the wrong answer, switches the partitioned solve to eager launches on EVERY
-  // rank (agreed with an eager all-reduce); a replay that never finishes ends the job through the watchdog.
-  double ok = 1.0;
-  if (halo_graph_wanted()) {
-    const double h2[8] = {rank + 1.0, (rank + 1.0) * (rank + 1.0), 1000.0 + rank, 0, -1.0, 0, 0, 0};
-    double hr[8];
-    HIP_TRY(hipMemcpy(d, h2, sizeof(h2), hipMemcpyHostToDevice));
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    g_rccl_stream = st;
-    bool captured = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (captured) {
-      int rc3 = rccl_allreduce_cb(comm, d, 2);
-      if (rc3 == 0 && world > 1) {
-        const int next = (rank + 1) % world, prev = (rank + world - 1) % world;
-        rc3 = a.group_start();
-        if (rc3 == 0) rc3 = a.send(d + 2, sizeof(double), 0, next, comm, st);
-        if (rc3 == 0) rc3 = a.recv(d + 4, sizeof(double), 0, prev, comm, st);
-        const int rc4 = a.group_end();
-        rc3 = rc3 ? rc3 : rc4;
-      }
-      captured = hipStreamEndCapture(st, &g) == hipSuccess && rc3 == 0 && g &&
-                 hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess;
-    }
-    g_rccl_stream = nullptr;
-    (void)hipGetLastError();
-    if (captured && hipGraphLaunch(ge, st) == hipSuccess) {
-      const auto t1 = std::chrono::steady_clock::now();
-      while (hipStreamQuery(st) == hipErrorNotReady) {
-        std::this_thread::sleep_for(std::chrono::milliseconds(5));
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count() > timeout_s)
-          rccl_watchdog_abort("the hipGraph replay of the RCCL self-check (set TLFEA_HALO_GRAPH=0 to run the partitioned "
-                              "solve without graph capture)", rank, timeout_s);
-      }
-      HIP_TRY(hipMemcpy(hr, d, sizeof(hr), hipMemcpyDeviceToHost));
-      if (hr[0] != s1 || hr[1] != s2 || hr[4] != ring) ok = 0.0;
-    } else {
-      ok = 0.0;
-    }
-    if (ge) (void)hipGraphExecDestroy(ge);
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    // agree: every rank replays graphs, or none does
-    HIP_TRY(hipMemcpy(d, &ok, sizeof(double), hipMemcpyHostToDevice));
-    g_rccl_stream = st;
-    const int rc5 = rccl_allreduce_cb(comm, d, 1);
-    g_rccl_stream = nullptr;
-    if (rc5) return fail("tlfea_rccl_self_check: RCCL refused the agreement all-reduce");
-    const auto t2 = std::chrono::steady_clock::now();
-    while (hipStreamQuery(st) == hipErrorNotReady) {
-      std::this_thread::sleep_for(std::chrono::milliseconds(5));
-      if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count() > timeout_s)
-        rccl_watchdog_abort("the RCCL self-check (agreement all-reduce)", rank, timeout_s);
-    }
-    double sum = 0.0;
-    HIP_TRY(hipMemcpy(&sum, d, sizeof(double), hipMemcpyDeviceToHost));
-    if (sum != (double)world) {
-      g_rccl_graph_ok = false;
-      if (rank == 0)
-        std::fprintf(stderr, "tlfea: RCCL collectives could not be captured / replayed in a hipGraph on %d of %d ranks: the "
-                     "partitioned CG iteration runs with eager launches\n", world - (int)sum, world);
-    }
-  }
-  (void)hipFree(d);
-  (void)hipStreamDestroy(st);
-  return 0;
-}
-
-// ---- overlapping partition ------------------------------------------------------------------------------------------------
+void tlfea::halo_graph_give_up() { g_rccl_graph_ok = false; }
 template <typename T>
 static int upload_vec(T** dst, const std::vector<T>& v);
-static bool dist_on(tlfea_newton_t s) { return s->ar != nullptr || s->halo.on; }
 static int precond_eff(tlfea_newton_t s);
 static int pmg_ks(tlfea_newton_t s);
 // Ghost layers on which the CG residual must be exact when the preconditioner starts: the V-cycle's ks pre-smoothing
@@ -2501,7 +1546,7 @@ extern "C" int tlfea_newton_set_halo(tlfea_newton_t s, const int* node_layer, in
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
   h.on = true;
-  h.native = exchange == rccl_halo_exchange_cb && allreduce == rccl_allreduce_cb;
+  h.native = exchange == tlfea_rccl_halo_exchange_fn() && allreduce == tlfea_rccl_allreduce_fn();
   h.depth = depth;
   h.rank = lists->rank;
   h.world = lists->world;
@@ -2755,7 +1800,6 @@ static int parts_sum(tlfea_newton_t s, double* d_a, double* d_b = nullptr) {
   return 0;
 }
 
-static double* part(tlfea_newton_t s, int k) { return s->d_parts + (size_t)k * kNPart; }
 
 // sum of squares (over ranks) left in s->d_scal[0]; no host synchronisation on the single-GPU path
 static int device_sumsq_async(tlfea_newton_t s, const double* d_vec, const double* w, int n) {
@@ -2773,7 +1817,7 @@ static int fetch_scalar(tlfea_newton_t s, const double* d_src, double* out) {
   *out = s->h_pin[0];
   return 0;
 }
-static int fetch_scalar2(tlfea_newton_t s, const double* d_src, double* out0, double* out1) {
+int tlfea::fetch_scalar2(tlfea_newton_t s, const double* d_src, double* out0, double* out1) {
   HIP_TRY(hipMemcpyAsync(s->h_pin, d_src, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   *out0 = s->h_pin[0];
@@ -2791,23 +1835,6 @@ static int device_norm(tlfea_newton_t s, const double* d_vec, const double* w, i
 extern "C" int tlfea_newton_l2_norm(tlfea_newton_t s, const double* d_vec, int n, double* out) {
   return device_norm(s, d_vec, nullptr, n, out);
 }
-
-struct StageTimer {  // hipEvent pair on the launch stream around one stage (profiling mode only)
-  tlfea_newton_t s;
-  int stage;
-  StageTimer(tlfea_newton_t s_, int st) : s(s_), stage(st) {
-    if (s->profiling) (void)hipEventRecord(s->ev[0], s->stream);
-  }
-  void stop() {
-    if (!s->profiling) return;
-    (void)hipEventRecord(s->ev[1], s->stream);
-    (void)hipEventSynchronize(s->ev[1]);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-    s->stage_ms[stage] += ms;
-    s->stage_n[stage] += 1;
-  }
-};
 
 // UpdateNodalFixed may have changed the size of the fixed set since the solver was built: the multipliers follow it
 // (restarting from zero) before anything indexes them with the new constraint ids.
@@ -3044,6 +2071,12 @@ static void launch_ancf_obstacles_tangent(tlfea_newton_t s, bool buffers_fresh) 
   launch_ancf_obstacle_tangent(s->stream, ancf_obs_view(d), s->prm.time_step, s->d_Kbuf);
 }
 
+static AncfLoadView ancf_load_view(tlfea_t10_t h) {
+  return AncfLoadView{h->E, h->S, h->d_conn, h->d_ld_cls, h->d_ld_tab, h->d_ld_qw, h->d_ld_mask, h->d_ld_pe, h->d_ld_lbuf};
+}
+static T10LoadView t10_load_view(tlfea_t10_t h) {
+  return T10LoadView{(int)h->h_ld_lf.size(), h->d_ld_fnodes, h->d_ld_pe, h->d_ld_lbuf};
+}
 // g -= f_load(x): the constant part is rebuilt when the mass matrix, the acceleration or a traction changed;
 // the pressure rows follow the current coefficients
 static int launch_loads_grad(tlfea_newton_t s) {
@@ -4503,272 +3536,6 @@ static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg,
   return 0;
 }
 
-// ---- sparse direct solve: rocSOLVER's re-factorisation path in place of cuDSS (SyncedNewton.cu:995-1029 analysis once,
-// :1103-1114 REFACTORIZATION + SOLVE per Newton iteration) ------------------------------------------------------------
-// rocSOLVER (and the rocBLAS handle it needs) are resolved at run time, like RCCL: the default iterative path never
-// depends on them.  rocsolver_dcsrrf_* re-factorise a matrix of FIXED pattern given the permutation and the pattern of
-// its Cholesky factor, which direct_host.h computes once per mesh (nested dissection + symbolic factorisation).
-namespace {
-struct RocsolverApi {
-  void* lib = nullptr;
-  int (*blas_create)(void**) = nullptr;
-  int (*blas_destroy)(void*) = nullptr;
-  int (*blas_set_stream)(void*, hipStream_t) = nullptr;
-  int (*rf_create)(void**, void*) = nullptr;
-  int (*rf_destroy)(void*) = nullptr;
-  int (*rf_set_mode)(void*, int) = nullptr;
-  int (*analysis)(void*, int, int, int, int*, int*, double*, int, int*, int*, double*, int*, int*, double*, int, void*) = nullptr;
-  int (*refactchol)(void*, int, int, int*, int*, double*, int, int*, int*, double*, int*, void*) = nullptr;
-  int (*solve)(void*, int, int, int, int*, int*, double*, int*, int*, double*, int, void*) = nullptr;
-};
-RocsolverApi& rocsolver_api() {
-  static RocsolverApi a;
-  static bool tried = false;
-  if (tried) return a;
-  tried = true;
-  for (const char* name : {"librocsolver.so.0", "librocsolver.so", "/opt/rocm/lib/librocsolver.so.0"}) {
-    a.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-    if (a.lib) break;
-  }
-  if (!a.lib) return a;
-  auto sym = [&](const char* n) { return dlsym(a.lib, n) ? dlsym(a.lib, n) : dlsym(RTLD_DEFAULT, n); };
-  a.blas_create = (int (*)(void**))sym("rocblas_create_handle");
-  a.blas_destroy = (int (*)(void*))sym("rocblas_destroy_handle");
-  a.blas_set_stream = (int (*)(void*, hipStream_t))sym("rocblas_set_stream");
-  a.rf_create = (int (*)(void**, void*))sym("rocsolver_create_rfinfo");
-  a.rf_destroy = (int (*)(void*))sym("rocsolver_destroy_rfinfo");
-  a.rf_set_mode = (int (*)(void*, int))sym("rocsolver_set_rfinfo_mode");
-  a.analysis = (decltype(a.analysis))sym("rocsolver_dcsrrf_analysis");
-  a.refactchol = (decltype(a.refactchol))sym("rocsolver_dcsrrf_refactchol");
-  a.solve = (decltype(a.solve))sym("rocsolver_dcsrrf_solve");
-  if (!a.blas_create || !a.blas_destroy || !a.blas_set_stream || !a.rf_create || !a.rf_destroy || !a.rf_set_mode ||
-      !a.analysis || !a.refactchol || !a.solve)
-    a.lib = nullptr;
-  return a;
-}
-}  // namespace
-
-static void direct_destroy(tlfea_newton_t s) {
-  auto& m = s->direct;
-  if (!m.tried) return;  // never used: do not resolve (dlopen) rocSOLVER / rocBLAS just to tear nothing down
-  for (void* q : m.owned)
-    if (q) (void)hipFree(q);
-  if (m.backend == 0) {
-    m = tlfea_newton_s::Direct();
-    return;
-  }
-  RocsolverApi& a = rocsolver_api();
-  if (m.rfinfo && a.lib) (void)a.rf_destroy(m.rfinfo);
-  if (m.blas && a.lib) (void)a.blas_destroy(m.blas);
-  void* pp[] = {m.d_ptrA, m.d_indA, m.d_ptrT, m.d_indT, m.d_pivQ, m.d_valT};
-  for (void* q : pp)
-    if (q) (void)hipFree(q);
-  m = tlfea_newton_s::Direct();
-}
-
-// once per mesh: ordering + symbolic factor on the host, rocSOLVER's analysis on the device
-#define DTRACE(msg)                                                          \
-  do {                                                                       \
-    if (std::getenv("TLFEA_DIRECT_TRACE")) {                                 \
-      std::fprintf(stderr, "tlfea direct: %s\n", msg);                       \
-      std::fflush(stderr);                                                   \
-    }                                                                        \
-  } while (0)
-// the engine's own backend: plan on the host (mf_host.h), everything else on the device
-template <typename T>
-static int mf_upload(tlfea_newton_s::Direct& m, const std::vector<T>& h, const T** out) {
-  T* p = nullptr;
-  HIP_TRY(hipMalloc(&p, std::max<size_t>(1, h.size()) * sizeof(T)));
-  m.owned.push_back(p);
-  if (!h.empty()) HIP_TRY(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = p;
-  return 0;
-}
-static int direct_prepare_native(tlfea_newton_t s, const std::vector<double>& X) {
-  auto& m = s->direct;
-  tlfea_t10_t d = s->d;
-  const int N = s->N;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  static const long long forced = env_ll("TLFEA_DIRECT_MAX_NNZ", 0);
-  const long long max_doubles = forced > 0 ? forced : (long long)(0.8 * (double)free_b / sizeof(double));
-  static const int leaf = env_int("TLFEA_DIRECT_LEAF", 32);
-  if (!mf_plan_build(N, d->h_off.data(), d->h_cols.data(), X.data(), X.data() + N, X.data() + 2 * (size_t)N, leaf, max_doubles,
-                     m.plan))
-    return fail("sparse direct solve: the Cholesky factor and front workspaces of this mesh do not fit the device memory "
-                "that is free (TLFEA_DIRECT_MAX_NNZ overrides the bound, in doubles); use the iterative solver");
-  const MfPlan& P = m.plan;
-  std::vector<MfFrontDev> fr(P.fronts.size());
-  for (size_t f = 0; f < P.fronts.size(); f++) {
-    const MfFront& F = P.fronts[f];
-    fr[f] = MfFrontDev{F.F_off, F.L_off, F.v_off, F.map_off, F.row_off, F.cF_off, 3 * F.nrows, 3 * (F.c1 - F.c0), F.c0,
-                       F.child[0], F.child[1], F.c_ld, F.c_k0, 0};
-  }
-  MfDev& D = m.dev;
-  TRY(mf_upload(m, fr, &D.fr));
-  TRY(mf_upload(m, P.level_fronts, &D.lvl));
-  TRY(mf_upload(m, P.batch_fronts, &D.blvl));
-  TRY(mf_upload(m, P.map, &D.map));
-  TRY(mf_upload(m, P.rows, &D.rows));
-  TRY(mf_upload(m, P.order, &D.order));
-  TRY(mf_upload(m, P.h_src, &D.hsrc));
-  TRY(mf_upload(m, P.h_dst, &D.hdst));
-  TRY(mf_upload(m, P.h_sld, &D.hsld));
-  TRY(mf_upload(m, P.h_dld, &D.hdld));
-  auto dalloc = [&](double** p, long long n) {
-    HIP_TRY(hipMalloc(p, (size_t)std::max(1LL, n) * sizeof(double)));
-    m.owned.push_back(*p);
-    return 0;
-  };
-  TRY(dalloc(&D.L, P.L_total));
-  for (int t = 0; t < 4; t++) TRY(dalloc(&D.F[t], P.F_cap[t]));
-  TRY(dalloc(&D.v, P.v_total));
-  TRY(dalloc(&D.y, 3LL * N));
-  TRY(dalloc(&D.xp, 3LL * N));
-  HIP_TRY(hipMalloc(&D.err, sizeof(int)));
-  m.owned.push_back(D.err);
-  m.n = 3 * N;
-  m.ok = true;
-  if (s->verbose || std::getenv("TLFEA_DIRECT_TRACE"))
-    std::printf("sparse direct solve: %d DOF, %zu fronts in %d levels, factor %.3g doubles (%.1f x the lower triangle of H), "
-                "workspaces %.3g doubles (fronts down to depth %d one by one with a stack), %.3g flop per factorisation\n",
-                m.n, P.fronts.size(), P.n_levels(), (double)P.L_total, (double)P.L_total / (0.5 * s->h_nnz),
-                (double)P.F_total(), P.top_depth, (double)P.flops);
-  return 0;
-}
-
-static int direct_prepare(tlfea_newton_t s) {
-  auto& m = s->direct;
-  if (m.tried) return m.ok ? 0 : fail("sparse direct solve is not available (see the earlier message)");
-  m.tried = true;
-  tlfea_t10_t d = s->d;
-  if (dist_on(s)) return fail("sparse direct solve: single-GPU path only");
-  {
-    const char* be = std::getenv("TLFEA_DIRECT_BACKEND");
-    m.backend = (be && std::string(be) == "rocsolver") ? 1 : 0;
-  }
-  if (m.backend == 0) {
-    const int N0 = s->N;
-    std::vector<double> X0(3 * (size_t)N0);
-    D2H(X0.data(), d->d_xt, (size_t)N0);
-    D2H(X0.data() + N0, d->d_yt, (size_t)N0);
-    D2H(X0.data() + 2 * (size_t)N0, d->d_zt, (size_t)N0);
-    if (d->kind != kT10)  // ANCF: the 4 coefficient vectors of a node share its position
-      for (int i = 0; i < N0; i++)
-        for (int c = 0; c < 3; c++) X0[(size_t)c * N0 + i] = X0[(size_t)c * N0 + (i / 4) * 4];
-    return direct_prepare_native(s, X0);
-  }
-  DTRACE("resolving rocsolver");
-  RocsolverApi& a = rocsolver_api();
-  DTRACE("resolved");
-  if (!a.lib) return fail("sparse direct solve: librocsolver / librocblas could not be resolved at run time");
-  // coordinates of the coefficient vectors for the dissection planes (ANCF: the 4 vectors of a node share its position)
-  const int N = s->N;
-  std::vector<double> X(3 * (size_t)N);
-  D2H(X.data(), d->d_xt, (size_t)N);
-  D2H(X.data() + N, d->d_yt, (size_t)N);
-  D2H(X.data() + 2 * (size_t)N, d->d_zt, (size_t)N);
-  if (d->kind != kT10)
-    for (int i = 0; i < N; i++)
-      for (int c = 0; c < 3; c++) X[(size_t)c * N + i] = X[(size_t)c * N + (i / 4) * 4];
-  DirectHost h;
-  static const long long max_nnz = env_ll("TLFEA_DIRECT_MAX_NNZ", 400000000LL);
-  if (!direct_symbolic(N, d->h_off.data(), d->h_cols.data(), X.data(), X.data() + N, X.data() + 2 * (size_t)N, max_nnz, h))
-    return fail("sparse direct solve: the Cholesky factor of this mesh exceeds the size limit (TLFEA_DIRECT_MAX_NNZ, default "
-                "4e8 entries = 3.2 GB); use the iterative solver");
-  m.n = h.n;
-  m.nnzT = (int)h.indT.size();
-  TRY(dmalloc(&m.d_ptrA, s->h_row_offsets.size()));
-  TRY(dmalloc(&m.d_indA, s->h_col_indices.size()));
-  TRY(dmalloc(&m.d_ptrT, h.ptrT.size()));
-  TRY(dmalloc(&m.d_indT, h.indT.size()));
-  TRY(dmalloc(&m.d_pivQ, h.perm.size()));
-  TRY(dmalloc(&m.d_valT, h.indT.size()));
-  HIP_TRY(hipMemcpy(m.d_ptrA, s->h_row_offsets.data(), s->h_row_offsets.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m.d_indA, s->h_col_indices.data(), s->h_col_indices.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m.d_ptrT, h.ptrT.data(), h.ptrT.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m.d_indT, h.indT.data(), h.indT.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m.d_pivQ, h.perm.data(), h.perm.size() * sizeof(int), hipMemcpyHostToDevice));
-  {  // a valid factor for the analysis phase (it inspects the pattern): the identity on T's pattern
-    std::vector<double> vT(h.indT.size(), 0.0);
-    for (int r = 0; r < h.n; r++) vT[(size_t)h.ptrT[r + 1] - 1] = 1.0;  // the diagonal is the last entry of a row
-    HIP_TRY(hipMemcpy(m.d_valT, vT.data(), vT.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  DTRACE("symbolic done, creating rocblas handle");
-  if (a.blas_create(&m.blas)) return fail("rocblas_create_handle failed");
-  DTRACE("handle created");
-  if (a.blas_set_stream(m.blas, s->stream)) return fail("rocblas_set_stream failed");
-  if (a.rf_create(&m.rfinfo, m.blas)) return fail("rocsolver_create_rfinfo failed");
-  if (a.rf_set_mode(m.rfinfo, /*rocsolver_rfinfo_mode_cholesky*/ 272)) return fail("rocsolver_set_rfinfo_mode failed");
-  DTRACE("rfinfo ready, analysis");
-  const int rc = a.analysis(m.blas, m.n, 1, s->h_nnz, m.d_ptrA, m.d_indA, s->d_H, m.nnzT, m.d_ptrT, m.d_indT, m.d_valT,
-                            nullptr, m.d_pivQ, s->d_dv, m.n, m.rfinfo);
-  if (rc) return fail("rocsolver_dcsrrf_analysis failed with status " + std::to_string(rc));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  DTRACE("analysis done");
-  m.ok = true;
-  if (s->verbose)
-    std::printf("sparse direct solve: %d DOF, factor %d entries (%.1f x the lower triangle of H), nested dissection\n", m.n,
-                m.nnzT, (double)m.nnzT / (0.5 * s->h_nnz));
-  return 0;
-}
-
-// H x = b by re-factorisation + triangular solves; the true residual is measured with the fp64 SpMV of the CG
-static int direct_solve(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out) {
-  TRY(direct_prepare(s));
-  auto& m = s->direct;
-  static RocsolverApi none;
-  RocsolverApi& a = m.backend == 1 ? rocsolver_api() : none;
-  tlfea_t10_t d = s->d;
-  StageTimer t(s, 4);
-  const size_t nb = (size_t)m.n * sizeof(double);
-  if (m.backend == 0) {
-    launch_mf_factor(s->stream, m.plan, m.dev, s->d_H, m.tally);
-    launch_mf_solve(s->stream, m.plan, m.dev, d_b, d_x, m.tally);
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, m.dev.err, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipGetLastError());
-    if (bad) return fail("sparse direct solve: a pivot of the Cholesky factorisation is not positive (H not positive definite)");
-  } else {
-  int rc = a.refactchol(m.blas, m.n, s->h_nnz, m.d_ptrA, m.d_indA, s->d_H, m.nnzT, m.d_ptrT, m.d_indT, m.d_valT, m.d_pivQ,
-                        m.rfinfo);
-  if (rc) return fail("rocsolver_dcsrrf_refactchol failed with status " + std::to_string(rc) + " (H not positive definite?)");
-  DTRACE("refactchol enqueued");
-  HIP_TRY(hipMemcpyAsync(d_x, d_b, nb, hipMemcpyDeviceToDevice, s->stream));
-  rc = a.solve(m.blas, m.n, 1, m.nnzT, m.d_ptrT, m.d_indT, m.d_valT, nullptr, m.d_pivQ, d_x, m.n, m.rfinfo);
-  if (rc) return fail("rocsolver_dcsrrf_solve failed with status " + std::to_string(rc));
-  DTRACE("solve enqueued");
-  }
-  // r = b - H x, ||r|| / ||b||
-  HIP_TRY(hipMemsetAsync(s->d_parts, 0, (size_t)5 * kNPart * sizeof(double), s->stream));
-  launch_spmv_dir_dot(s->stream, s->N, d->inc(), s->d_H, d_x, s->d_p, 1, part(s, 1), part(s, 0), s->d_p2, s->d_q, part(s, 2),
-                      true, s->spmv_nt);
-  launch_diff(s->stream, m.n, d_b, s->d_q, s->d_r);
-  double rr = 0.0, bb = 0.0;
-  launch_norm2(s->stream, s->d_r, nullptr, m.n, part(s, 5), s->d_scal);
-  launch_norm2(s->stream, d_b, nullptr, m.n, part(s, 4), s->d_scal + 1);
-  TRY(fetch_scalar2(s, s->d_scal, &rr, &bb));
-  HIP_TRY(hipGetLastError());
-  t.stop();
-  const double rel = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-  if (iters_out) *iters_out = 1;
-  if (rel_out) *rel_out = rel;
-  // a backward-stable factorisation leaves ||r||/||b|| at a few ulp times the growth of the factor: the tolerance of the
-  // iterative path does not apply; what is reported (and tested) is the measured residual
-  s->lin_last_rel = rel;
-  s->lin_last_ok = rel == rel && rel <= 1e-8;
-  s->lin_worst_rel = (rel != rel) ? rel : std::max(s->lin_worst_rel, rel);
-  s->lin_all_ok = s->lin_all_ok && s->lin_last_ok;
-  if (!s->lin_last_ok && !s->lin.on_unconverged) {
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "sparse direct solve left ||r||/||b|| = %.3e (H not positive definite, or ill-conditioned "
-                  "beyond fp64)", rel);
-    return fail(msg);
-  }
-  return 0;
-}
-
 // What the preconditioner needs from the current H, in the launches and the order pcg() has always issued them.
 // Stage 0, before the start residual: the block diagonal, its inverse and the scaled low-precision copy.  Stage 1, after
 // it (d_b: start vector of a cold lambda_max estimate): lambda_max, the polynomial's coefficients and the p-multigrid
@@ -4943,7 +3710,7 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
       }
       (void)hipGetLastError();
       cg_graphs_destroy(s);
-      g_rccl_graph_ok = false;
+      halo_graph_give_up();
       graphs = false;
       std::fprintf(stderr, "tlfea: hipGraph capture of the partitioned CG iteration failed (%s): eager launches from here on\n",
                    tlfea_last_error());
@@ -5152,40 +3919,6 @@ extern "C" int tlfea_newton_get_c32_geometry(tlfea_newton_t s, int level, int* o
   out7[4] = g.rows_per_group;
   out7[5] = g.grid;
   out7[6] = g.resident;
-  return 0;
-}
-// Test hooks of the native sparse direct solve: the plan the solver holds and the launches its last factorisation + solve
-// issued (host counters next to the launches, direct_kernels.hip), so that a test can assert which kernels a mesh and the
-// TLFEA_DIRECT_* switches reached.  Available once a direct solve has built the plan.
-extern "C" int tlfea_newton_get_direct_info(tlfea_newton_t s, long long* out22) {
-  if (!s || !out22) return fail("tlfea_newton_get_direct_info: null argument");
-  const auto& m = s->direct;
-  if (!m.ok || m.backend != 0) return fail("tlfea_newton_get_direct_info: no native direct solve has run on this solver");
-  const MfPlan& P = m.plan;
-  long long m_max = 0, k_max = 0, k_zero = 0;
-  for (const MfFront& F : P.fronts) {
-    m_max = std::max(m_max, 3LL * F.nrows);
-    k_max = std::max(k_max, 3LL * (F.c1 - F.c0));
-    k_zero += F.c1 == F.c0;
-  }
-  const MfTally& t = m.tally;
-  const long long v[22] = {(long long)P.fronts.size(), P.n_levels(), P.top_depth, P.L_total, P.F_cap[0], P.F_cap[1], P.F_cap[2],
-                           P.F_cap[3], m_max, k_max, k_zero, P.N, t.panel, t.update_inner, t.update_trailing, t.update_wide,
-                           t.extend_add, t.push, t.levels_one_wg, t.levels_stepwise, t.fwd_step, t.bwd_step};
-  std::copy(v, v + 22, out22);
-  return 0;
-}
-extern "C" int tlfea_newton_get_direct_fronts(tlfea_newton_t s, int* order, int* fronts7) {
-  if (!s || !order || !fronts7) return fail("tlfea_newton_get_direct_fronts: null argument");
-  const auto& m = s->direct;
-  if (!m.ok || m.backend != 0) return fail("tlfea_newton_get_direct_fronts: no native direct solve has run on this solver");
-  const MfPlan& P = m.plan;
-  std::copy(P.order.begin(), P.order.end(), order);
-  for (size_t f = 0; f < P.fronts.size(); f++) {
-    const MfFront& F = P.fronts[f];
-    const int v[7] = {F.c0, F.c1, F.depth, F.parent, F.nrows, F.child[0], F.child[1]};
-    std::copy(v, v + 7, fronts7 + 7 * f);
-  }
   return 0;
 }
 extern "C" int tlfea_newton_pmg_restrict_op_sizes(tlfea_newton_t s, int* out6) {
@@ -5582,6 +4315,7 @@ extern "C" int tlfea_newton_get_matfree_rows(tlfea_newton_t s, long long* rows, 
 // H x = nu M x with nu = h (omega^2 + sigma).  M need not be definite (the T10 mass of the 5-point Keast rule is not), so
 // the block is kept H-orthonormal and the Rayleigh-Ritz step takes the largest theta = 1 / nu (tests/modal_np.py).
 namespace {
+// device scratch of one call, released when the call returns
 struct ModalWork {
   std::vector<void*> owned;
   ~ModalWork() {
@@ -5596,12 +4330,19 @@ struct ModalWork {
 };
 // Warm-start state of the lambda_max estimates (fine level and the coarse levels that exist): save() keeps it and sets the
 // estimates cold, so that what follows depends on no earlier solve; restore() puts it back.  A level built in between did
-// not exist at the save: its vector stays, its estimate goes back to 0.
+// not exist at the save: its vector stays, its estimate goes back to 0.  solve_state: a call that runs solves of its own
+// (modal solve, adjoint step) also keeps the scalars a linear solve leaves for the next one and for the status read-backs.
 struct LamKeep {
   std::vector<std::pair<double*, size_t>> vecs;  // the kept vectors that exist at the save
   std::vector<std::pair<double*, double>> lams;  // the estimates
   double* d_save = nullptr;
-  int save(tlfea_newton_t s, ModalWork& wk) {
+  tlfea_newton_t kept_of = nullptr;              // solve_state: the solver whose scalars `kept` holds
+  std::tuple<double, double, int, int, int, int, double, double, bool, bool> kept;
+  static auto solve_scalars(tlfea_newton_t s) {
+    return std::tie(s->lam_safety, s->pmg.kc_boost, s->last_outer_iters, s->last_deg, s->last_bits, s->mf.last_mode,
+                    s->lin_last_rel, s->lin_worst_rel, s->lin_last_ok, s->lin_all_ok);
+  }
+  int save(tlfea_newton_t s, ModalWork& wk, bool solve_state = false) {
     size_t total = 0;
     for (PolyLevel* L : {&s->pmg.vertex, &s->pmg.agg.lvl})
       if (L->d_eigv) vecs.push_back({L->d_eigv, 3 * (size_t)L->N});
@@ -5614,10 +4355,15 @@ struct LamKeep {
       lams.push_back({p, *p});
       *p = 0.0;
     }
+    if (solve_state) {
+      kept_of = s;
+      kept = solve_scalars(s);
+    }
     return 0;
   }
   void restore() {
     for (auto& l : lams) *l.first = l.second;
+    if (kept_of) solve_scalars(kept_of) = kept;
     (void)copy(false);
   }
   hipError_t copy(bool out) {
@@ -5634,9 +4380,7 @@ struct LamKeep {
 }  // namespace
 
 static const int* modal_mask(tlfea_newton_t s) { return pinned_on(s) ? s->d->d_fixed_slot : nullptr; }
-static bool modal_has_mass(tlfea_t10_t d) {
-  return d->is_csr_setup && d->d_mval && (d->kind == kT10 ? d->mass_rho0 >= 0.0 : d->ancf_mass);
-}
+static bool modal_has_mass(tlfea_t10_t d) { return d->is_csr_setup && d->d_mval && mass_assembled(d); }
 static void modal_product(tlfea_newton_t s, int which, int m, const double* X, int ldx, double* Y, int ldy, const int* mask) {
   tlfea_t10_t d = s->d;
   if (which == 0) launch_spmm_block(s->stream, s->N, m, d->d_off, d->d_cols, s->d_H, X, ldx, Y, ldy, mask);
@@ -5851,21 +4595,14 @@ extern "C" int tlfea_newton_modal_solve(tlfea_newton_t s, const tlfea_modal_opts
   // what the call must leave as it found it: the time step, the warm-start state of the linear solver
   ModalWork wk;
   LamKeep keep;
-  const double h0 = s->prm.time_step, safety0 = s->lam_safety, boost0 = s->pmg.kc_boost, last_rel0 = s->lin_last_rel,
-               worst_rel0 = s->lin_worst_rel;
-  const int outer0 = s->last_outer_iters, deg0 = s->last_deg, bits0 = s->last_bits, mode0 = s->mf.last_mode;
-  const bool last_ok0 = s->lin_last_ok, all_ok0 = s->lin_all_ok;
-  TRY(keep.save(s, wk));  // cold estimates: the result depends on no earlier solve
+  const double h0 = s->prm.time_step;
+  TRY(keep.save(s, wk, /*solve_state=*/true));  // cold estimates: the result depends on no earlier solve
   s->prm.time_step = 1.0 / std::sqrt(o.shift);
   int rc = assemble(s, /*fq_fresh=*/false);
   if (!rc) rc = modal_iterate(s, o, m, omega2, modes, resid, info);
   const std::string why = rc ? api_error() : std::string();
   (void)hipStreamSynchronize(s->stream);
   s->prm.time_step = h0;
-  s->lam_safety = safety0;
-  s->pmg.kc_boost = boost0;
-  s->last_outer_iters = outer0; s->last_deg = deg0; s->last_bits = bits0; s->mf.last_mode = mode0;
-  s->lin_last_rel = last_rel0; s->lin_worst_rel = worst_rel0; s->lin_last_ok = last_ok0; s->lin_all_ok = all_ok0;
   keep.restore();
   const int rc2 = assemble(s, /*fq_fresh=*/false);  // H of the caller's time step again
   (void)hipStreamSynchronize(s->stream);
@@ -6241,11 +4978,26 @@ extern "C" int tlfea_newton_begin_step(tlfea_newton_t s) {
 // Adjoint sensitivities of the implicit step (adjoint_kernels.hip)
 static int sens_slots(tlfea_t10_t h) { return (h->mat.model == kMooneyRivlin ? 3 : 2) + 1; }
 static int sens_n_mat(tlfea_t10_t h) { return h->d_emat ? h->n_mat : 1; }
-// buffers and, under a material table, the ascending element list of every material with its chunks of kAdjChunk
-static int sens_prepare(tlfea_t10_t h, const char* what) {
+// what both sensitivities need of the handle: a T10 mesh, set up, with its reference-geometry tables
+static int sens_need_t10(tlfea_t10_t h, const char* what) {
   if (h && h->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)");
   NEED_SETUP(h, what);
   if (!h->have_dndu) return fail(std::string(what) + ": CalcDnDuPre must be called first");
+  return 0;
+}
+// the vectors of the two timing entry points -- any finite ones serve a timing: the positions as w, zeros as u
+static int sens_timing_vectors(tlfea_t10_t h) {
+  const size_t n = 3 * (size_t)h->N;
+  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
+  if (!h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
+  HIP_TRY(hipMemset(h->d_sn_w, 0, n * sizeof(double)));
+  HIP_TRY(hipMemcpy(h->d_sn_w, h->d_x, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice));
+  HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
+  return 0;
+}
+// buffers and, under a material table, the ascending element list of every material with its chunks of kAdjChunk
+static int sens_prepare(tlfea_t10_t h, const char* what) {
+  TRY(sens_need_t10(h, what));
   if (!h->d_sn_sens) TRY(dmalloc(&h->d_sn_sens, (size_t)4 * h->Epad));
   const int n_mat = sens_n_mat(h);
   if (n_mat > h->sn_out_cap) {
@@ -6267,10 +5019,9 @@ static int sens_prepare(tlfea_t10_t h, const char* what) {
     }
     boff[n_mat] = (int)blk.size();
     HIP_TRY(hipDeviceSynchronize());
-    for (void* p : {(void*)h->d_sn_idx, (void*)h->d_sn_boff, (void*)h->d_sn_blk})
-      if (p) (void)hipFree(p);
-    h->d_sn_idx = h->d_sn_boff = nullptr;
-    h->d_sn_blk = nullptr;
+    dfree(h->d_sn_idx);
+    dfree(h->d_sn_boff);
+    dfree(h->d_sn_blk);
     TRY(dmalloc(&h->d_sn_idx, idx.size()));
     TRY(dmalloc(&h->d_sn_boff, boff.size()));
     TRY(dmalloc(&h->d_sn_blk, blk.size()));
@@ -6339,13 +5090,7 @@ extern "C" int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, doubl
   TRY(sens_prepare(h, "tlfea_t10_time_sensitivity_kernels"));
   if (!out_ms2) return fail("tlfea_t10_time_sensitivity_kernels: null output");
   if (reps < 1) reps = 1;
-  const size_t n = 3 * (size_t)h->N;
-  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
-  if (!h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
-  // any finite vectors serve a timing: the positions as w, zeros as u
-  HIP_TRY(hipMemset(h->d_sn_w, 0, n * sizeof(double)));
-  HIP_TRY(hipMemcpy(h->d_sn_w, h->d_x, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice));
-  HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
+  TRY(sens_timing_vectors(h));
   TRY(time_reps(h->stream, reps, &out_ms2[0], [&](int) { sens_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u); return 0; }));
   TRY(time_reps(h->stream, reps, &out_ms2[1], [&](int) { sens_launch_sums(h, h->stream); return 0; }));
   return 0;
@@ -6353,9 +5098,7 @@ extern "C" int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, doubl
 
 // ---- shape sensitivities (shape_kernels.hip) -----------------------------------------------------------------
 static int shape_prepare(tlfea_t10_t h, const char* what) {
-  if (h && h->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, what);
-  if (!h->have_dndu) return fail(std::string(what) + ": CalcDnDuPre must be called first");
+  TRY(sens_need_t10(h, what));
   if (!h->is_csr_setup) TRY(tlfea_t10_build_mass_csr_pattern(h));  // the node -> element incidence of the gather
   if (!h->d_sh_rows) TRY(dmalloc(&h->d_sh_rows, (size_t)3 * kNN * h->Epad));
   return 0;
@@ -6393,14 +5136,8 @@ extern "C" int tlfea_t10_time_shape_kernels(tlfea_t10_t h, int reps, double* out
   TRY(shape_prepare(h, "tlfea_t10_time_shape_kernels"));
   if (!out_ms2) return fail("tlfea_t10_time_shape_kernels: null output");
   if (reps < 1) reps = 1;
-  const size_t n = 3 * (size_t)h->N;
-  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
-  if (!h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
-  if (!h->d_sh_out) TRY(dmalloc(&h->d_sh_out, n));
-  // any finite vectors serve a timing (tlfea_t10_time_sensitivity_kernels): the positions as w, zeros as u
-  HIP_TRY(hipMemset(h->d_sn_w, 0, n * sizeof(double)));
-  HIP_TRY(hipMemcpy(h->d_sn_w, h->d_x, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice));
-  HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
+  TRY(sens_timing_vectors(h));
+  if (!h->d_sh_out) TRY(dmalloc(&h->d_sh_out, 3 * (size_t)h->N));
   TRY(time_reps(h->stream, reps, &out_ms2[0], [&](int) { shape_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u); return 0; }));
   TRY(time_reps(h->stream, reps, &out_ms2[1], [&](int) { shape_launch_gather(h, h->stream, h->d_sh_out); return 0; }));
   return 0;
@@ -6476,10 +5213,7 @@ extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tl
   TRY(wk.alloc(&Mw, (size_t)n));
   // what the call must leave as it found it: the warm-start state of the linear solver (tlfea_newton_modal_solve)
   LamKeep keep;
-  const double safety0 = s->lam_safety, boost0 = s->pmg.kc_boost, last_rel0 = s->lin_last_rel, worst_rel0 = s->lin_worst_rel;
-  const int outer0 = s->last_outer_iters, deg0 = s->last_deg, bits0 = s->last_bits, mode0 = s->mf.last_mode;
-  const bool last_ok0 = s->lin_last_ok, all_ok0 = s->lin_all_ok;
-  TRY(keep.save(s, wk));  // cold estimates: the result depends on no earlier solve
+  TRY(keep.save(s, wk, /*solve_state=*/true));  // cold estimates: the result depends on no earlier solve
   launch_adj_rhs(s->stream, n, J, in->x_bar, in->v_bar, J.mode ? in->lam_bar : nullptr, s->d_v, vprev,
                  d->ld_have_a ? d->ld_a : zero3, h, rho, xt, vt, u);
   int it = 0;
@@ -6491,10 +5225,6 @@ extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tl
     rc = fail("tlfea_newton_adjoint_step: device copy failed");
   if (!rc) rc = pcg(s, s->d_b, s->d_dv, &it, &rel);
   const std::string why = rc ? api_error() : std::string();
-  s->lam_safety = safety0;
-  s->pmg.kc_boost = boost0;
-  s->last_outer_iters = outer0; s->last_deg = deg0; s->last_bits = bits0; s->mf.last_mode = mode0;
-  s->lin_last_rel = last_rel0; s->lin_worst_rel = worst_rel0; s->lin_last_ok = last_ok0; s->lin_all_ok = all_ok0;
   if (rc) {
     (void)hipStreamSynchronize(s->stream);
     keep.restore();
@@ -6584,17 +5314,79 @@ extern "C" int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_i
 }
 
 
+// What the three handles share: the Newton core whose gradient evaluation they loop around, the six stats words of the
+// last Solve (outer iterations, inner iterations or sweeps, ||g||, ||c||, inner flag, ms) and the verbosity.
+struct FirstOrder {
+  tlfea_newton_t core = nullptr;
+  double stats[6] = {0, 0, 0, 0, 0, 0};
+  int verbose = 0;
+};
+// the handle with its core; no solver here assembles, so the core's residual skips the Fq by-product
+// (null: refused, the message is set)
+template <typename H>
+static H* fo_create(const char* who, tlfea_t10_t data, int n_constraints, const void* out) {
+  if (!data || !out) return fail(std::string(who) + ": null argument"), nullptr;
+  H* a = new H();
+  if (tlfea_newton_create(data, n_constraints, &a->core)) return nullptr;
+  a->core->fq_in_residual = false;
+  return a;
+}
+template <typename H>
+static int fo_destroy(H* a, std::initializer_list<void*> buffers) {
+  for (void* p : buffers)
+    if (p) (void)hipFree(p);
+  (void)tlfea_newton_destroy(a->core);
+  delete a;
+  return 0;
+}
+// the reference's SetParameters also clears v_guess, v_prev and lambda (SyncedAdamWNocoop.cuh:175-177,
+// SyncedNesterov.cuh:135-137, SyncedVBD.cuh:258-260)
+static int fo_clear_state(FirstOrder* a) {
+  tlfea_newton_t s = a->core;
+  const size_t n = 3 * (size_t)s->N;
+  HIP_TRY(hipMemset(s->d_v, 0, n * sizeof(double)));
+  HIP_TRY(hipMemset(s->d_vprev, 0, n * sizeof(double)));
+  HIP_TRY(hipMemset(s->d_lam, 0, (size_t)std::max(1, s->n_constraints) * sizeof(double)));
+  return 0;
+}
+// Head of a Solve: the core evaluates grad L with ITS parameters, so it takes the time step and rho of this solver; the
+// timed span opens; x_prev = x.  Tail: the span closes and the stats words are written.
+static int fo_begin(FirstOrder* a, double time_step, double rho) {
+  tlfea_newton_t s = a->core;
+  s->prm.time_step = time_step;
+  s->prm.rho = rho;
+  HIP_TRY(hipEventRecord(s->ev[2], s->stream));
+  return begin_step(s);
+}
+static int fo_end(FirstOrder* a, int n_outer, int n_inner, double norm_g, double norm_c, int inner_flag) {
+  tlfea_newton_t s = a->core;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(s->ev[3], s->stream));
+  HIP_TRY(hipEventSynchronize(s->ev[3]));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+  a->stats[0] = n_outer; a->stats[1] = n_inner; a->stats[2] = norm_g; a->stats[3] = norm_c;
+  a->stats[4] = inner_flag; a->stats[5] = ms;
+  return 0;
+}
+// what the pass-through entry points of the three solvers call
+static int fo_set_verbose(FirstOrder* a, int v) {
+  a->verbose = v;
+  return 0;
+}
+static int fo_get_stats(const FirstOrder* a, double* out6) {
+  std::copy(a->stats, a->stats + 6, out6);
+  return 0;
+}
+
 // =================================================================================================
 // SyncedAdamWNocoopSolver (SyncedAdamWNocoop.cuh:22-198, SyncedAdamWNocoop.cu:262-500): first-order ALM solver on the
 // same velocity unknowns.  It needs the residual / gradient path only (compute_p + internal force + constraints +
 // grad L: the same functions the Newton solver calls), so it is a thin loop around the Newton core's gradient
 // evaluation plus the AdamW moment update; no Hessian is built or allocated.
-struct tlfea_adamw_s {
-  tlfea_newton_t core = nullptr;
+struct tlfea_adamw_s : FirstOrder {
   tlfea_adamw_params prm{2e-4, 0.9, 0.999, 1e-8, 1e-4, 0.998, 1e-1, 1e-6, 1e14, 5, 500, 1e-3, 10, 0.0};
   double *d_m = nullptr, *d_va = nullptr;
-  double stats[6] = {0, 0, 0, 0, 0, 0};  // outer iterations, inner iterations (total), ||g||, ||c||, inner flag, ms
-  int verbose = 0;
   // 1: SyncedAdamWSolver, the cooperative-kernel sibling (SyncedAdamW.cu:96-345): same moments and step; as written
   // there the inner-converged flag is cleared once per Solve(), lam += rho dt c is applied once, and the outer loop
   // stops on ||c|| < outer_tol alone
@@ -6602,10 +5394,8 @@ struct tlfea_adamw_s {
 };
 
 extern "C" int tlfea_adamw_create(tlfea_t10_t data, int n_constraints, tlfea_adamw_t* out) {
-  if (!data || !out) return fail("tlfea_adamw_create: null argument");
-  auto* a = new tlfea_adamw_s();
-  TRY(tlfea_newton_create(data, n_constraints, &a->core));
-  a->core->fq_in_residual = false;
+  tlfea_adamw_t a = fo_create<tlfea_adamw_s>("tlfea_adamw_create", data, n_constraints, out);
+  if (!a) return 1;
   const size_t n = 3 * (size_t)a->core->N;
   TRY(dmalloc(&a->d_m, n));
   TRY(dmalloc(&a->d_va, n));
@@ -6616,11 +5406,7 @@ extern "C" int tlfea_adamw_create(tlfea_t10_t data, int n_constraints, tlfea_ada
 }
 extern "C" int tlfea_adamw_destroy(tlfea_adamw_t a) {
   if (!a) return 0;
-  if (a->d_m) (void)hipFree(a->d_m);
-  if (a->d_va) (void)hipFree(a->d_va);
-  (void)tlfea_newton_destroy(a->core);
-  delete a;
-  return 0;
+  return fo_destroy(a, {a->d_m, a->d_va});
 }
 extern "C" int tlfea_adamw_setup(tlfea_adamw_t a) {  // Setup(): zero state (SyncedAdamWNocoop.cuh:180-198)
   const size_t n = 3 * (size_t)a->core->N;
@@ -6632,29 +5418,17 @@ extern "C" int tlfea_adamw_setup(tlfea_adamw_t a) {  // Setup(): zero state (Syn
 extern "C" int tlfea_adamw_set_parameters(tlfea_adamw_t a, const tlfea_adamw_params* p) {
   if (!a || !p) return fail("null argument");
   a->prm = *p;
-  // the reference's SetParameters also clears v_guess, v_prev and lambda (SyncedAdamWNocoop.cuh:175-177)
-  tlfea_newton_t s = a->core;
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipMemset(s->d_v, 0, n * sizeof(double)));
-  HIP_TRY(hipMemset(s->d_vprev, 0, n * sizeof(double)));
-  HIP_TRY(hipMemset(s->d_lam, 0, (size_t)std::max(1, s->n_constraints) * sizeof(double)));
-  return 0;
+  return fo_clear_state(a);
 }
 extern "C" int tlfea_adamw_set_cooperative_semantics(tlfea_adamw_t a, int on) {
   a->coop = on ? 1 : 0;
   return 0;
 }
-extern "C" int tlfea_adamw_set_verbose(tlfea_adamw_t a, int v) {
-  a->verbose = v;
-  return 0;
-}
+extern "C" int tlfea_adamw_set_verbose(tlfea_adamw_t a, int v) { return fo_set_verbose(a, v); }
 extern "C" double* tlfea_adamw_velocity_guess_device_ptr(tlfea_adamw_t a) { return a->core->d_v; }
 extern "C" int tlfea_adamw_retrieve_velocity(tlfea_adamw_t a, double* v) { return tlfea_newton_retrieve_velocity(a->core, v); }
 extern "C" int tlfea_adamw_retrieve_lambda(tlfea_adamw_t a, double* lam) { return tlfea_newton_retrieve_lambda(a->core, lam); }
-extern "C" int tlfea_adamw_get_stats(tlfea_adamw_t a, double* out6) {
-  std::copy(a->stats, a->stats + 6, out6);
-  return 0;
-}
+extern "C" int tlfea_adamw_get_stats(tlfea_adamw_t a, double* out6) { return fo_get_stats(a, out6); }
 
 // OneStepAdamWNocoop (SyncedAdamWNocoop.cu:262-500)
 extern "C" int tlfea_adamw_solve(tlfea_adamw_t a) {
@@ -6666,14 +5440,9 @@ extern "C" int tlfea_adamw_solve(tlfea_adamw_t a) {
   TRY(sync_constraints(s));
   const int N = s->N, n = 3 * N;
   const double dt = p.time_step;
-  // the core evaluates grad L with ITS parameters: time step and rho of this solver
-  s->prm.time_step = dt;
-  s->prm.rho = p.rho;
   const int check_every = p.convergence_check_interval > 0 ? p.convergence_check_interval : 1;
   const int max_outer = s->n_constraints > 0 ? p.max_outer : 1;
-  hipEvent_t e0 = s->ev[2], e1 = s->ev[3];
-  HIP_TRY(hipEventRecord(e0, s->stream));
-  TRY(begin_step(s));  // x_prev = x   (adamw_save_prev_pos_kernel)
+  TRY(fo_begin(a, dt, p.rho));  // x_prev = x   (adamw_save_prev_pos_kernel)
   int outer_flag = 0, n_outer = 0, n_inner_total = 0, inner_flag = 0;
   double norm_g = 0.0, norm_c = 0.0;
   for (int outer = 0; outer < max_outer; outer++) {
@@ -6724,14 +5493,7 @@ extern "C" int tlfea_adamw_solve(tlfea_adamw_t a) {
     }
   }
   launch_positions_from_prev(s->stream, N, s->d_v, s->d_xp, s->d_yp, s->d_zp, dt, d->d_x, d->d_y, d->d_z);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e1, s->stream));
-  HIP_TRY(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  a->stats[0] = n_outer; a->stats[1] = n_inner_total; a->stats[2] = norm_g; a->stats[3] = norm_c;
-  a->stats[4] = inner_flag; a->stats[5] = ms;
-  return 0;
+  return fo_end(a, n_outer, n_inner_total, norm_g, norm_c, inner_flag);
 }
 
 
@@ -6741,18 +5503,13 @@ extern "C" int tlfea_adamw_solve(tlfea_adamw_t a) {
 // norms; here the same phases are ordinary launches of the engine's residual / gradient path.  Reproduced as
 // written: the inner-converged flag is cleared once per Solve(), not per outer iteration (:110-113), so after the
 // inner loop has converged once the later outer iterations only update the multipliers.
-struct tlfea_nesterov_s {
-  tlfea_newton_t core = nullptr;
+struct tlfea_nesterov_s : FirstOrder {
   tlfea_nesterov_params prm{1e-8, 1e14, 1e-6, 1e-6, 5, 200, 1e-3};
   double *d_vk = nullptr, *d_vkm1 = nullptr, *d_vnext = nullptr;
-  double stats[6] = {0, 0, 0, 0, 0, 0};
-  int verbose = 0;
 };
 extern "C" int tlfea_nesterov_create(tlfea_t10_t data, int n_constraints, tlfea_nesterov_t* out) {
-  if (!data || !out) return fail("tlfea_nesterov_create: null argument");
-  auto* a = new tlfea_nesterov_s();
-  TRY(tlfea_newton_create(data, n_constraints, &a->core));
-  a->core->fq_in_residual = false;
+  tlfea_nesterov_t a = fo_create<tlfea_nesterov_s>("tlfea_nesterov_create", data, n_constraints, out);
+  if (!a) return 1;
   const size_t n = 3 * (size_t)a->core->N;
   TRY(dmalloc(&a->d_vk, n)); TRY(dmalloc(&a->d_vkm1, n)); TRY(dmalloc(&a->d_vnext, n));
   *out = a;
@@ -6760,34 +5517,19 @@ extern "C" int tlfea_nesterov_create(tlfea_t10_t data, int n_constraints, tlfea_
 }
 extern "C" int tlfea_nesterov_destroy(tlfea_nesterov_t a) {
   if (!a) return 0;
-  for (double* p : {a->d_vk, a->d_vkm1, a->d_vnext})
-    if (p) (void)hipFree(p);
-  (void)tlfea_newton_destroy(a->core);
-  delete a;
-  return 0;
+  return fo_destroy(a, {a->d_vk, a->d_vkm1, a->d_vnext});
 }
 extern "C" int tlfea_nesterov_setup(tlfea_nesterov_t a) { return tlfea_newton_setup(a->core); }  // :140-156
 extern "C" int tlfea_nesterov_set_parameters(tlfea_nesterov_t a, const tlfea_nesterov_params* p) {
   if (!a || !p) return fail("null argument");
   a->prm = *p;
-  tlfea_newton_t s = a->core;  // SetParameters clears v_guess, v_prev, lambda (SyncedNesterov.cuh:135-137)
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipMemset(s->d_v, 0, n * sizeof(double)));
-  HIP_TRY(hipMemset(s->d_vprev, 0, n * sizeof(double)));
-  HIP_TRY(hipMemset(s->d_lam, 0, (size_t)std::max(1, s->n_constraints) * sizeof(double)));
-  return 0;
+  return fo_clear_state(a);
 }
-extern "C" int tlfea_nesterov_set_verbose(tlfea_nesterov_t a, int v) {
-  a->verbose = v;
-  return 0;
-}
+extern "C" int tlfea_nesterov_set_verbose(tlfea_nesterov_t a, int v) { return fo_set_verbose(a, v); }
 extern "C" double* tlfea_nesterov_velocity_guess_device_ptr(tlfea_nesterov_t a) { return a->core->d_v; }
 extern "C" int tlfea_nesterov_retrieve_velocity(tlfea_nesterov_t a, double* v) { return tlfea_newton_retrieve_velocity(a->core, v); }
 extern "C" int tlfea_nesterov_retrieve_lambda(tlfea_nesterov_t a, double* lam) { return tlfea_newton_retrieve_lambda(a->core, lam); }
-extern "C" int tlfea_nesterov_get_stats(tlfea_nesterov_t a, double* out6) {
-  std::copy(a->stats, a->stats + 6, out6);
-  return 0;
-}
+extern "C" int tlfea_nesterov_get_stats(tlfea_nesterov_t a, double* out6) { return fo_get_stats(a, out6); }
 
 // OneStepNesterov (SyncedNesterov.cu:95-372)
 extern "C" int tlfea_nesterov_solve(tlfea_nesterov_t a) {
@@ -6801,11 +5543,7 @@ extern "C" int tlfea_nesterov_solve(tlfea_nesterov_t a) {
   const int N = s->N, n = 3 * N;
   const double dt = p.time_step;
   const size_t nb = (size_t)n * sizeof(double);
-  s->prm.time_step = dt;
-  s->prm.rho = p.rho;
-  hipEvent_t e0 = s->ev[2], e1 = s->ev[3];
-  HIP_TRY(hipEventRecord(e0, s->stream));
-  TRY(begin_step(s));  // x_prev = x
+  TRY(fo_begin(a, dt, p.rho));  // x_prev = x
   int inner_flag = 0, outer_flag = 0, n_outer = 0, n_inner_total = 0;
   double norm_g = 0.0, norm_c = 0.0;
   for (int outer = 0; outer < p.max_outer; outer++) {
@@ -6849,14 +5587,7 @@ extern "C" int tlfea_nesterov_solve(tlfea_nesterov_t a) {
     if (std::fabs(norm_c) < p.outer_tol) outer_flag = 1;
   }
   launch_positions_from_prev(s->stream, N, s->d_v, s->d_xp, s->d_yp, s->d_zp, dt, d->d_x, d->d_y, d->d_z);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e1, s->stream));
-  HIP_TRY(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  a->stats[0] = n_outer; a->stats[1] = n_inner_total; a->stats[2] = norm_g; a->stats[3] = norm_c;
-  a->stats[4] = inner_flag; a->stats[5] = ms;
-  return 0;
+  return fo_end(a, n_outer, n_inner_total, norm_g, norm_c, inner_flag);
 }
 
 // =================================================================================================
@@ -6865,8 +5596,7 @@ extern "C" int tlfea_nesterov_solve(tlfea_nesterov_t a) {
 // because it rebuilds F from the coordinates -- the reference's compute_p refresh); the convergence checks reuse the
 // Newton core's gradient evaluation, the dual update its kernel.  The sweep of all colours is captured in a hipGraph,
 // as the reference captures its sweep in a CUDA graph (:1233-1330).
-struct tlfea_vbd_s {
-  tlfea_newton_t core = nullptr;
+struct tlfea_vbd_s : FirstOrder {
   tlfea_vbd_params prm{1e-4, 1e-4, 1e-4, 1e14, 5, 500, 1e-3, 1.0, 1e-12, 25, 1};
   VbdColoring col;
   std::vector<int> color_lanes;  // lanes per node of each colour's launch (16 | 32 | 64)
@@ -6879,8 +5609,6 @@ struct tlfea_vbd_s {
   // what the captured launches have baked in: h, rho, omega, hess_eps, pinned?, the data object's generation (material
   // scalars by value, the fixed-slot buffer re-allocated by UpdateNodalFixed) and the multiplier buffer
   double graph_key[7] = {0, 0, 0, 0, 0, -1, 0};
-  double stats[6] = {0, 0, 0, 0, 0, 0};
-  int verbose = 0;
 };
 
 static void vbd_drop_graph(tlfea_vbd_t a) {
@@ -6889,34 +5617,22 @@ static void vbd_drop_graph(tlfea_vbd_t a) {
 }
 
 extern "C" int tlfea_vbd_create(tlfea_t10_t data, int n_constraints, tlfea_vbd_t* out) {
-  if (!data || !out) return fail("tlfea_vbd_create: null argument");
-  auto* a = new tlfea_vbd_s();
-  TRY(tlfea_newton_create(data, n_constraints, &a->core));
-  a->core->fq_in_residual = false;
+  tlfea_vbd_t a = fo_create<tlfea_vbd_s>("tlfea_vbd_create", data, n_constraints, out);
+  if (!a) return 1;
   *out = a;
   return 0;
 }
 extern "C" int tlfea_vbd_destroy(tlfea_vbd_t a) {
   if (!a) return 0;
   vbd_drop_graph(a);
-  if (a->d_color_nodes) (void)hipFree(a->d_color_nodes);
-  if (a->d_conn_rm) (void)hipFree(a->d_conn_rm);
-  if (a->d_xyz) (void)hipFree(a->d_xyz);
-  (void)tlfea_newton_destroy(a->core);
-  delete a;
-  return 0;
+  return fo_destroy(a, {a->d_color_nodes, a->d_conn_rm, a->d_xyz});
 }
 extern "C" int tlfea_vbd_setup(tlfea_vbd_t a) { return tlfea_newton_setup(a->core); }
 extern "C" int tlfea_vbd_set_parameters(tlfea_vbd_t a, const tlfea_vbd_params* p) {
   if (!a || !p) return fail("null argument");
   a->prm = *p;
   if (a->prm.color_group_size <= 0) a->prm.color_group_size = 1;
-  tlfea_newton_t s = a->core;  // SetParameters clears v_guess, v_prev and lambda (SyncedVBD.cuh:258-260)
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipMemset(s->d_v, 0, n * sizeof(double)));
-  HIP_TRY(hipMemset(s->d_vprev, 0, n * sizeof(double)));
-  HIP_TRY(hipMemset(s->d_lam, 0, (size_t)std::max(1, s->n_constraints) * sizeof(double)));
-  return 0;
+  return fo_clear_state(a);
 }
 extern "C" int tlfea_vbd_initialize_mass_diag_blocks(tlfea_vbd_t a) {
   TRY(tlfea_t10_calc_mass_matrix(a->core->d));  // the reference recomputes the mass matrix here (:1041-1052)
@@ -6931,8 +5647,7 @@ extern "C" int tlfea_vbd_initialize_coloring(tlfea_vbd_t a) {
   vbd_build_coloring(d->S, d->E, d->N, d->h_conn.data(), d->h_off.data(), d->h_cols.data(), a->prm.color_group_size, a->col);
   if (!a->col.valid) std::fprintf(stderr, "Warning: Invalid coloring detected!\n");
   if (a->verbose) std::printf("VBD coloring: %d colors for %d nodes\n", a->col.n_colors, d->N);
-  if (a->d_color_nodes) (void)hipFree(a->d_color_nodes);
-  a->d_color_nodes = nullptr;
+  dfree(a->d_color_nodes);
   TRY(dmalloc(&a->d_color_nodes, (size_t)d->N));
   HIP_TRY(hipMemcpy(a->d_color_nodes, a->col.color_nodes.data(), (size_t)d->N * sizeof(int), hipMemcpyHostToDevice));
   if (!a->d_conn_rm) {
@@ -6987,17 +5702,11 @@ extern "C" int tlfea_vbd_retrieve_coloring(tlfea_vbd_t a, int* colors, int* colo
   if (group_colors) std::copy(c.group_colors.begin(), c.group_colors.end(), group_colors);
   return 0;
 }
+extern "C" int tlfea_vbd_set_verbose(tlfea_vbd_t a, int v) { return fo_set_verbose(a, v); }
 extern "C" double* tlfea_vbd_velocity_guess_device_ptr(tlfea_vbd_t a) { return a->core->d_v; }
 extern "C" int tlfea_vbd_retrieve_velocity(tlfea_vbd_t a, double* v) { return tlfea_newton_retrieve_velocity(a->core, v); }
 extern "C" int tlfea_vbd_retrieve_lambda(tlfea_vbd_t a, double* lam) { return tlfea_newton_retrieve_lambda(a->core, lam); }
-extern "C" int tlfea_vbd_get_stats(tlfea_vbd_t a, double* out6) {
-  std::copy(a->stats, a->stats + 6, out6);
-  return 0;
-}
-extern "C" int tlfea_vbd_set_verbose(tlfea_vbd_t a, int v) {
-  a->verbose = v;
-  return 0;
-}
+extern "C" int tlfea_vbd_get_stats(tlfea_vbd_t a, double* out6) { return fo_get_stats(a, out6); }
 
 // one sweep = every colour once, in group order; colours of a group share no element, so they are launched as they
 // come (the reference's refresh after the group changes nothing a colour of the same group reads)
@@ -7074,11 +5783,7 @@ extern "C" int tlfea_vbd_solve(tlfea_vbd_t a) {
     return fail("SyncedVBDSolver: n_constraints_ > 0 but constraint buffer is unavailable (did you call element constraint setup?)");
   const int N = s->N, n = 3 * N;
   const double dt = p.time_step;
-  s->prm.time_step = dt;  // the core's gradient (convergence checks) uses this solver's h and rho
-  s->prm.rho = p.rho;
-  hipEvent_t e0 = s->ev[2], e1 = s->ev[3];
-  HIP_TRY(hipEventRecord(e0, s->stream));
-  TRY(begin_step(s));  // vbd_update_pos_prev
+  TRY(fo_begin(a, dt, p.rho));  // vbd_update_pos_prev
   int n_outer = 0, n_sweeps = 0;
   double norm_g = 0.0, norm_c = 0.0;
   for (int outer = 0; outer < p.max_outer; outer++) {
@@ -7112,13 +5817,7 @@ extern "C" int tlfea_vbd_solve(tlfea_vbd_t a) {
     }
   }
   HIP_TRY(hipMemcpyAsync(s->d_vprev, s->d_v, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e1, s->stream));
-  HIP_TRY(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  a->stats[0] = n_outer; a->stats[1] = n_sweeps; a->stats[2] = norm_g; a->stats[3] = norm_c; a->stats[4] = 0.0;
-  a->stats[5] = ms;
-  if (a->verbose) std::printf("OneStepVBD kernel time: %.3f ms\n", ms);
+  TRY(fo_end(a, n_outer, n_sweeps, norm_g, norm_c, 0));
+  if (a->verbose) std::printf("OneStepVBD kernel time: %.3f ms\n", a->stats[5]);
   return 0;
 }
