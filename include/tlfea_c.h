@@ -554,6 +554,36 @@ int tlfea_t10_material_sensitivity(tlfea_t10_t h, const double *w, const double 
 int tlfea_t10_material_sensitivity_shape(tlfea_t10_t h, int *n_mat, int *slots);
 /* mean ms over `reps` launches of out[0] the element kernel, [1] its reduction (hipEvents; tools/adjoint_timing.py) */
 int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, double *out_ms2);
+/* ---- the same on ANCF-3243 beams and ANCF-3443 shells (DESIGN 3j'; no reference counterpart) ---------------------------
+ * The step, tlfea_adjoint_in and tlfea_adjoint_out are those above with N = n_coef: every vector runs over the coefficient
+ * vectors, positions and gradients alike.  What differs:
+ *   - the body acceleration acts on the position coefficients (index % 4 == 0) only, so a_bar sums M w over those;
+ *   - constraints are the fixed coefficients (constraint 3 slot + c = component c of coefficient fixed[slot]) or CSR rows;
+ *   - the object has one material: per_material is [1][P + 1], per_element [E][P] (stiffness slots only: there is no
+ *     per-element density, and the mass matrix is integrated with a rule of its own);
+ *   - the density slot is -(M w) . u / rho0 with u = (v - v_prev)/h - a and rho0 the density the mass matrix was assembled
+ *     with; a density <= 0 there is refused when per_material is wanted, and only then.
+ * Refused (tlfea_last_error says why): a T10 handle, damping, an obstacle with friction, an ANCF follower pressure (dead
+ * tractions and gravity are fine), a partitioned mesh, no CalcDsDuPre / BuildMassCSRPattern / CalcMassMatrix, and the
+ * four states of the last tlfea_newton_solve that tlfea_newton_adjoint_step refuses.  The call leaves x, v, v_prev, lambda
+ * and the warm-start state of the linear solver as they were and re-assembles H. */
+int tlfea_newton_ancf_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_in *in, const tlfea_adjoint_out *out, int *info,
+                                   double *rel_res);
+/* the same on device pointers (a_bar and per_material included) */
+int tlfea_newton_ancf_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in *in, const tlfea_adjoint_out *out,
+                                          int *info, double *rel_res);
+/* 0 when tlfea_newton_ancf_adjoint_step would accept the solver's state now, else the refusal (tlfea_last_error) */
+int tlfea_newton_ancf_adjoint_ready(tlfea_newton_t s);
+/* The element kernel and the sums alone, at the current coefficients: host vectors w, u [3 n_coef] -> per_element [E][P]
+ * and per_material [1][P + 1] (either may be NULL).  u NULL: density slot 0; u given: -(M w) . u / rho0, which needs the
+ * mass matrix. */
+int tlfea_ancf_material_sensitivity(tlfea_t10_t h, const double *w, const double *u, double *per_element,
+                                    double *per_material);
+/* n_mat (always 1) and P + 1 of the object's model as it is set now */
+int tlfea_ancf_material_sensitivity_shape(tlfea_t10_t h, int *n_mat, int *slots);
+/* mean ms over `reps` launches of out[0] the element kernel, [1] the sums of its P planes (hipEvents;
+ * tools/ancf_adjoint_timing.py) */
+int tlfea_ancf_time_sensitivity_kernels(tlfea_t10_t h, int reps, double *out_ms2);
 /* ---- shape sensitivities of the implicit step (no reference counterpart) -----------------------------------
  * The same adjoint step with one more output: X_bar [3N] (interleaved like the other vectors; NULL = not wanted), the
  * cotangent of the reference coordinates of every node -- mid-edge nodes are coordinates of their own, a straight-sided

@@ -207,8 +207,13 @@ def _adjoint_signatures(lib):
            "tlfea_newton_adjoint_step_shape": step[:3] + [vp] + step[3:],
            "tlfea_newton_adjoint_step_shape_device": step[:3] + [vp] + step[3:],
            "tlfea_t10_shape_sensitivity": [vp, c_dp, c_dp, c_dp], "tlfea_t10_time_shape_kernels": [vp, i, c_dp],
-           "tlfea_t10_set_reference_positions": [vp, c_dp, c_dp, c_dp, i]}
+           "tlfea_t10_set_reference_positions": [vp, c_dp, c_dp, c_dp, i],
+           # the ANCF kinds (DESIGN 3j')
+           "tlfea_newton_ancf_adjoint_step": step, "tlfea_newton_ancf_adjoint_step_device": step,
+           "tlfea_newton_ancf_adjoint_ready": [vp], "tlfea_ancf_material_sensitivity": [vp, c_dp, c_dp, c_dp, c_dp],
+           "tlfea_ancf_material_sensitivity_shape": [vp, c_ip, c_ip], "tlfea_ancf_time_sensitivity_kernels": [vp, i, c_dp]}
     newer = {n for n in sig if "_shape" in n and n != "tlfea_t10_material_sensitivity_shape"} | {"tlfea_t10_set_reference_positions"}
+    newer |= {n for n in sig if "ancf" in n}
     for name, args in sig.items():
         if name in newer and not hasattr(lib, name):
             continue  # an older build loaded through TLFEA_LIB_PATH (A/B runs) lacks the shape entry points

@@ -1,4 +1,4 @@
-// adjoint_kernels.hip -- adjoint sensitivities of the implicit Newton step of T10 objects.
+// adjoint_kernels.hip -- adjoint sensitivities of the implicit Newton step (the ANCF kinds: 3j').
 //
 //   sens_point_kernel    thread per element (stress_point_kernel's lane mapping and reads: the coalesced element-fastest
 //                        grad-N copy, next point's gradients in flight): F and the gradient D = grad w of the adjoint field
@@ -13,7 +13,10 @@
 //                        group's chunk sums the same way.  The chunks depend on the group sizes alone, never on a launch
 //                        shape.  Groups: the ascending element list of every material (sens -> per_material), or all
 //                        nodes (M w -> the three sums of a_bar)
+//   ancf_sens_point_kernel / ancf_rho_terms_kernel
+//                        the ANCF kinds (DESIGN 3j'): lanes own quadrature points; the density slot from M w and u
 //   adj_rhs_kernel       thread per DOF: x_t = x_bar + rho J^T lam_bar, v_t = v_bar + h x_t, u = (v - v_prev)/h - a
+//                        (a on the position coefficients: every coefficient of a T10 mesh, every fourth of an ANCF mesh)
 //   adj_out_kernel       thread per DOF: f_ext_bar, v_prev_bar, x_prev_bar from w and M w; thread per constraint row:
 //                        J w, lam_in_bar, t_bar
 // J is the fixed-node selector (constraint 3 slot + c <-> component c of node fixed[slot]) or the CSR rows.
@@ -165,6 +168,75 @@ __global__ __launch_bounds__(128) void sens_point_kernel(ElemView m, SensShape s
   sens[(size_t)P * m.Epad + e] = -am;
 }
 
+// The ANCF kinds (DESIGN 3j'): lanes own quadrature points, the mapping of ancf_stress_point_kernel (3f').  A wavefront
+// takes G = 64 / Q elements of Q lanes each (shell <16,48>: 1 x 48, beam <8,12>: 5 x 12); the elements' coefficient vectors x
+// and the adjoint field w sit in the wavefront's LDS slice (3 S + 1 doubles per element each: the G rows start on different
+// banks) and are read as broadcasts; every lane streams its own contiguous 3 S gradient doubles of gradN [E][Q][3][S] once,
+// into F and D = sum_a w_a (x) grad s_a alike, and forms the P contractions of its point.  The element sums are
+// elem_lane_sum's fixed tree; lanes past the wavefront's last element recompute element e0 with dV = 0.  The four
+// wavefronts of a block share nothing.  sens [P][Epad]: stiffness slots only (the density slot of an ANCF object is a
+// vector product, ancf_rho_terms_kernel).
+template <int S, int Q, int MODEL>
+__global__ __launch_bounds__(64 * kAncfWaves) void ancf_sens_point_kernel(ElemView m, const double* __restrict__ w,
+                                                                         double* __restrict__ sens) {
+  constexpr int G = 64 / Q, kRow = 3 * S + 1, P = MODEL == kMooneyRivlin ? 3 : 2;
+  __shared__ double xs_all[kAncfWaves][G * kRow], ws_all[kAncfWaves][G * kRow];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int e0 = (blockIdx.x * kAncfWaves + wv) * G;  // first element of this wavefront
+  if (e0 >= m.E) return;                              // the whole wavefront: nothing below synchronises across wavefronts
+  double *xs = xs_all[wv], *ws = ws_all[wv];
+  const int n_el = min(G, m.E - e0);
+  for (int idx = lane; idx < n_el * S; idx += 64) {
+    const int el = idx / S, a = idx - el * S;
+    const int c = m.conn[(size_t)a * m.E + e0 + el];
+    double* xo = xs + el * kRow + 3 * a;
+    xo[0] = m.x[c];
+    xo[1] = m.y[c];
+    xo[2] = m.z[c];
+    double* wo = ws + el * kRow + 3 * a;
+    wo[0] = w[3 * (size_t)c];
+    wo[1] = w[3 * (size_t)c + 1];
+    wo[2] = w[3 * (size_t)c + 2];
+  }
+  wave_sync();
+  const int g_raw = lane / Q, p = lane - g_raw * Q;
+  const bool active = g_raw < n_el;
+  const int g = active ? g_raw : 0, e = e0 + g;
+  const double2* gr = reinterpret_cast<const double2*>(m.gradN + ((size_t)e * Q + p) * (3 * S));  // 3 S doubles: 16-byte aligned
+  const double* xe = xs + g * kRow;
+  const double* we = ws + g * kRow;
+  double F[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, D[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+  for (int d = 0; d < 3; d++)
+#pragma unroll
+    for (int a = 0; a < S; a += 2) {
+      const double2 h = gr[(d * S + a) >> 1];
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        F[i][d] += xe[3 * a + i] * h.x + xe[3 * a + 3 + i] * h.y;
+        D[i][d] += we[3 * a + i] * h.x + we[3 * a + 3 + i] * h.y;
+      }
+    }
+  double s[3];
+  dP_contract<MODEL>(F, D, s);
+  const double dV = active ? m.detJ[(size_t)e * Q + p] * m.qw[p] : 0.0;
+#pragma unroll
+  for (int k = 0; k < P; k++) {
+    const double acc = elem_lane_sum<Q>(s[k] * dV, lane, p);
+    if (active && p == 0) sens[(size_t)k * m.Epad + e] = -acc;
+  }
+}
+
+// The density slot of an ANCF object, whose mass matrix is linear in its one density: item i = scale (M w)_i . u_i per
+// coefficient vector (scale = -1 / rho0 of the assembled matrix); adj_partial / adj_final add the items up
+__global__ __launch_bounds__(256) void ancf_rho_terms_kernel(int N, const double* __restrict__ Mw, const double* __restrict__ u,
+                                                            double scale, double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const size_t k = 3 * (size_t)i;
+  out[i] = scale * (Mw[k] * u[k] + Mw[k + 1] * u[k + 1] + Mw[k + 2] * u[k + 2]);
+}
+
 // value (slot c, item k) = src[c * slot_stride + item * item_stride], item = idx ? idx[k] : k.  Block b adds the items
 // [blk[b].x, blk[b].y) (blk null: [b kAdjChunk, min(n, (b + 1) kAdjChunk))); partial [blocks][SLOTS].
 template <int SLOTS>
@@ -235,8 +307,8 @@ __device__ __forceinline__ double jt_times(const AdjCons& J, int i, const double
 __global__ __launch_bounds__(256) void adj_rhs_kernel(int n, AdjCons J, const double* __restrict__ xbar,
                                                      const double* __restrict__ vbar, const double* __restrict__ lambar,
                                                      const double* __restrict__ v, const double* __restrict__ vprev,
-                                                     double ax, double ay, double az, double h, double rho,
-                                                     double* __restrict__ xt, double* __restrict__ vt,
+                                                     double ax, double ay, double az, int stride, double h,
+                                                     double rho, double* __restrict__ xt, double* __restrict__ vt,
                                                      double* __restrict__ u) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -244,7 +316,8 @@ __global__ __launch_bounds__(256) void adj_rhs_kernel(int n, AdjCons J, const do
   xt[i] = x;
   vt[i] = (vbar ? vbar[i] : 0.0) + h * x;
   const int c = i % 3;
-  u[i] = (v[i] - vprev[i]) / h - (c == 0 ? ax : (c == 1 ? ay : az));
+  const double a = (i / 3) % stride ? 0.0 : (c == 0 ? ax : (c == 1 ? ay : az));  // a gradient coefficient: a_i = 0 (body_force_kernel)
+  u[i] = (v[i] - vprev[i]) / h - a;
 }
 
 __global__ __launch_bounds__(256) void adj_out_kernel(int n, int nc, AdjCons J, const double* __restrict__ w,
@@ -302,6 +375,25 @@ void launch_sens_points(hipStream_t s, const ElemView& m, int model, const SensS
     hipLaunchKernelGGL(sens_point_kernel<kSVK>, grid, block, 0, s, m, sh, w, u, sens);
 }
 
+template <int S, int Q>
+static void launch_ancf_sens_t(hipStream_t s, const ElemView& m, int model, const double* w, double* sens) {
+  constexpr int G = 64 / Q;
+  const dim3 grid((m.E + kAncfWaves * G - 1) / (kAncfWaves * G)), block(64 * kAncfWaves);
+  if (model == kMooneyRivlin)
+    hipLaunchKernelGGL((ancf_sens_point_kernel<S, Q, kMooneyRivlin>), grid, block, 0, s, m, w, sens);
+  else
+    hipLaunchKernelGGL((ancf_sens_point_kernel<S, Q, kSVK>), grid, block, 0, s, m, w, sens);
+}
+
+void launch_ancf_sens_points(hipStream_t s, const ElemView& m, int model, const double* w, double* sens) {
+  if (m.S == 8) launch_ancf_sens_t<8, 12>(s, m, model, w, sens);
+  else launch_ancf_sens_t<16, 48>(s, m, model, w, sens);
+}
+
+void launch_ancf_rho_terms(hipStream_t s, int N, const double* Mw, const double* u, double scale, double* out) {
+  hipLaunchKernelGGL(ancf_rho_terms_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, Mw, u, scale, out);
+}
+
 void launch_sens_transpose(hipStream_t s, int E, int Epad, int slots, const double* sens, double* out) {
   const size_t n = (size_t)E * slots;
   hipLaunchKernelGGL(sens_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, E, Epad, slots, sens, out);
@@ -310,14 +402,16 @@ void launch_sens_transpose(hipStream_t s, int E, int Epad, int slots, const doub
 void launch_adj_sums(hipStream_t s, int slots, int n, int nb, const int2* blk, const int* idx, const double* src,
                      size_t slot_stride, int item_stride, int groups, const int* boff, double* partial, double* out) {
   if (slots == 4) launch_sums_t<4>(s, n, nb, blk, idx, src, slot_stride, item_stride, groups, boff, partial, out);
+  else if (slots == 2) launch_sums_t<2>(s, n, nb, blk, idx, src, slot_stride, item_stride, groups, boff, partial, out);
+  else if (slots == 1) launch_sums_t<1>(s, n, nb, blk, idx, src, slot_stride, item_stride, groups, boff, partial, out);
   else launch_sums_t<3>(s, n, nb, blk, idx, src, slot_stride, item_stride, groups, boff, partial, out);
 }
 
 void launch_adj_rhs(hipStream_t s, int n, const AdjCons& J, const double* xbar, const double* vbar, const double* lambar,
-                    const double* v, const double* vprev, const double a[3], double h, double rho, double* xt, double* vt,
-                    double* u) {
+                    const double* v, const double* vprev, const double a[3], int stride, double h, double rho, double* xt,
+                    double* vt, double* u) {
   hipLaunchKernelGGL(adj_rhs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, J, xbar, vbar, lambar, v, vprev, a[0],
-                     a[1], a[2], h, rho, xt, vt, u);
+                     a[1], a[2], stride, h, rho, xt, vt, u);
 }
 
 void launch_adj_out(hipStream_t s, int n, int nc, const AdjCons& J, const double* w, const double* Mw, const double* xt,

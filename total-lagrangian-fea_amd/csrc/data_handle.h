@@ -87,6 +87,8 @@ struct tlfea_t10_s {  // any element type; the name is kept for the ABI's first 
   bool st_valid = false, st_pts_valid = false;  // a calc_stress has run | its point stresses were asked for
   int *d_st_noff = nullptr, *d_st_nel = nullptr;  // ANCF (DESIGN 3f'): elements of every MESH node, ascending (n_nodes + 1 | E nn)
   bool ancf_mass = false;                         // ANCF: d_mval holds an assembled mass matrix (the kinetic energy's condition)
+  double ancf_mass_rho0 = 0.0;                    // ... and the density it was assembled with (the adjoint's density slot, 3j')
+  double* d_sn_rho = nullptr;                     // ANCF adjoint: [N] terms of the density slot (ancf_rho_terms_kernel)
   // recovered stress (tlfea_t10_recover_stress, DESIGN 3f''): allocated on first use, read by no solver.  d_rc_rec
   // [E][kRecoveryRec], d_rc_nodal [N][7], d_rc_err [3][Epad], principal values d_rc_pn [N][4] / d_rc_pe [E][4] and
   // directions d_rc_dn [N][9] / d_rc_de [E][9]; d_rc_pts [E][5][6] holds the point values of the _from_points hook

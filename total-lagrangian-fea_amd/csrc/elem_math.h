@@ -211,4 +211,20 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- lanes own quadrature points (the ANCF kinds: stress_kernels.hip, adjoint_kernels.hip; DESIGN 3f') -----------------
+constexpr int kAncfWaves = 4;  // wavefronts of a block; each works on its own elements through its own LDS slice
+// sum of `val` over the Q lanes of an element, valid in the element's lane 0 (p = lane within the element).  Every lane
+// of the wavefront takes part in every shuffle; the shape depends on Q alone, so a launch is bitwise reproducible.
+template <int Q>
+__device__ __forceinline__ double elem_lane_sum(double val, int lane, int p) {
+  static_assert(Q % 3 == 0 && ((Q / 3) & (Q / 3 - 1)) == 0, "Q = 3 * 2^k");
+#pragma unroll
+  for (int off = Q / 2; off >= 3; off >>= 1) {
+    const double t = __shfl(val, (lane + off) & 63);
+    if (p < off) val += t;
+  }
+  const double t1 = __shfl(val, (lane + 1) & 63), t2 = __shfl(val, (lane + 2) & 63);
+  return (val + t1) + t2;
+}
+
 }  // namespace tlfea

@@ -378,6 +378,27 @@ inline double* part(tlfea_newton_t s, int k) { return s->d_parts + (size_t)k * k
 bool halo_graph_wanted();
 void halo_graph_give_up();  // RCCL cannot be captured / replayed here: eager launches for the rest of the process
 int fetch_scalar2(tlfea_newton_t s, const double* d_src, double* out0, double* out1);
+// The adjoint step of the implicit Newton step (DESIGN 3j, 3j') is one function for every element kind; the kind supplies
+// what differs.  tlfea_api.hip holds the step and the T10 kind, ancf_adjoint_api.hip the ANCF kind.
+struct AdjointKind {
+  const char* what;                        // the entry point's name in messages
+  int stride;                              // the position coefficients are every stride-th coefficient vector (T10: 1, ANCF: 4)
+  int (*refusal)(tlfea_newton_t s);        // why the step cannot run on the solver's state now (0: it can)
+  int (*prepare)(tlfea_t10_t d);           // the buffers `materials` writes to
+  // enqueues the material slots from the device vectors w, u = (v - v_prev)/h - a and M w: per_material (device, null: not
+  // wanted) and per_element (the same)
+  void (*materials)(tlfea_t10_t d, hipStream_t st, const double* w, const double* u, const double* Mw, double* per_material,
+                    double* per_element);
+  size_t (*pm_doubles)(tlfea_t10_t d);     // doubles of per_material and per_element
+  size_t (*pe_doubles)(tlfea_t10_t d);
+};
+int adjoint_step_device(tlfea_newton_t s, const AdjointKind& K, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                        double* X_bar, int* info, double* rel_res);
+int adjoint_step_host(tlfea_newton_t s, const AdjointKind& K, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                      double* X_bar, int* info, double* rel_res);
+int adjoint_refusal_terms(tlfea_newton_t s, const std::string& w);  // damping, friction, follower pressure, a partitioned mesh
+int adjoint_refusal_state(tlfea_newton_t s, const std::string& w);  // what the last Solve() left
+int sens_buffers(tlfea_t10_t h);  // d_sn_sens, d_sn_out, d_sn_part and the per-material element lists
 // direct_api.hip
 void direct_destroy(tlfea_newton_t s);
 int direct_solve(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out);

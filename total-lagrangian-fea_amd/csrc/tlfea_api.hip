@@ -98,7 +98,7 @@ extern "C" int tlfea_t10_destroy(tlfea_t10_t h) {
                   h->d_ao_cbuf, h->d_ao_blk, h->d_ao_fk, h->d_ao_fc, h->d_ao_pts, h->d_ld_fc, h->d_ld_tr, h->d_ld_f,
                   h->d_ld_lbuf, h->d_ld_tab, h->d_ld_qw, h->d_ld_pe, h->d_ld_cls, h->d_ld_mask, h->d_ld_fnodes, h->d_ld_foff,
                   h->d_ld_fslot, h->d_fld, h->d_sn_sens, h->d_sn_part, h->d_sn_out, h->d_sn_w, h->d_sn_u, h->d_sn_pe,
-                  h->d_sn_idx, h->d_sn_boff, h->d_sn_blk, h->d_sh_rows, h->d_sh_out, h->d_rc_rec, h->d_rc_nodal, h->d_rc_err,
+                  h->d_sn_rho, h->d_sn_idx, h->d_sn_boff, h->d_sn_blk, h->d_sh_rows, h->d_sh_out, h->d_rc_rec, h->d_rc_nodal, h->d_rc_err,
                   h->d_rc_part, h->d_rc_tot, h->d_rc_pn, h->d_rc_pe, h->d_rc_dn, h->d_rc_de, h->d_rc_pts};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -803,6 +803,7 @@ static int ancf_mass_host(tlfea_t10_t h) {
   }
   HIP_TRY(hipMemcpy(h->d_mval, mval.data(), mval.size() * sizeof(double), hipMemcpyHostToDevice));
   h->ancf_mass = true;
+  h->ancf_mass_rho0 = h->mat.rho0;
   h->ld_const_dirty = true;  // the body force follows the mass matrix
   return 0;
 }
@@ -4995,9 +4996,9 @@ static int sens_timing_vectors(tlfea_t10_t h) {
   HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
   return 0;
 }
-// buffers and, under a material table, the ascending element list of every material with its chunks of kAdjChunk
-static int sens_prepare(tlfea_t10_t h, const char* what) {
-  TRY(sens_need_t10(h, what));
+// buffers and, under a material table, the ascending element list of every material with its chunks of kAdjChunk (any
+// element kind; newton_handle.h)
+int tlfea::sens_buffers(tlfea_t10_t h) {
   if (!h->d_sn_sens) TRY(dmalloc(&h->d_sn_sens, (size_t)4 * h->Epad));
   const int n_mat = sens_n_mat(h);
   if (n_mat > h->sn_out_cap) {
@@ -5039,6 +5040,10 @@ static int sens_prepare(tlfea_t10_t h, const char* what) {
     h->sn_part_cap = cap;
   }
   return 0;
+}
+static int sens_prepare(tlfea_t10_t h, const char* what) {
+  TRY(sens_need_t10(h, what));
+  return sens_buffers(h);
 }
 // the two launches after sens_prepare: d_sn_sens from device vectors w, u, then d_sn_out [n_mat][slots]
 static void sens_launch_points(tlfea_t10_t h, hipStream_t st, const double* d_w, const double* d_u) {
@@ -5149,6 +5154,14 @@ static int adjoint_refusal(tlfea_newton_t s) {
   tlfea_t10_t d = s->d;
   const std::string w = "tlfea_newton_adjoint_step: ";
   if (d->kind != kT10) return fail(w + "T10 handles only (not an ANCF handle)");
+  TRY(adjoint_refusal_terms(s, w));
+  if (!d->have_dndu || !d->is_csr_setup || !d->d_mval || d->mass_rho0 < 0.0)
+    return fail(w + "needs the mass matrix (CalcDnDuPre, CalcMassMatrix) first");
+  return adjoint_refusal_state(s, w);
+}
+// the terms of the step the adjoint does not carry, on any element kind (w: the entry point's name and ": ")
+int tlfea::adjoint_refusal_terms(tlfea_newton_t s, const std::string& w) {
+  tlfea_t10_t d = s->d;
   if (d->mat.eta != 0.0 || d->mat.lamd != 0.0 || d->emat_damp)
     return fail(w + "damping is set (eta / lambda_damp != 0, uniform or in the material table): the viscous stress depends "
                     "on v and x separately, which the adjoint of the undamped step does not carry");
@@ -5159,8 +5172,10 @@ static int adjoint_refusal(tlfea_newton_t s) {
   if (d->ld_n_press > 0)
     return fail(w + "a follower pressure is set: its load stiffness is not in H, so H is not the Jacobian of the residual");
   if (dist_on(s)) return fail(w + "not available on a partitioned mesh (set_interface / set_halo is active)");
-  if (!d->have_dndu || !d->is_csr_setup || !d->d_mval || d->mass_rho0 < 0.0)
-    return fail(w + "needs the mass matrix (CalcDnDuPre, CalcMassMatrix) first");
+  return 0;
+}
+// what the last Solve() left
+int tlfea::adjoint_refusal_state(tlfea_newton_t s, const std::string& w) {
   switch (s->adj_state) {
     case 1: break;
     case 0: return fail(w + "no Solve() has run: the state must be that of a step just solved");
@@ -5186,22 +5201,42 @@ static int adjoint_shape_refusal(tlfea_newton_t s) {
   return 0;
 }
 
-extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tlfea_adjoint_in* in,
-                                                      const tlfea_adjoint_out* out, double* X_bar, int* info, double* rel_res) {
-  TRY(adjoint_refusal(s));
-  if (!in || !out) return fail("tlfea_newton_adjoint_step: null argument");
+// the T10 kind of the adjoint step (AdjointKind, newton_handle.h): the material slots come from sens_point_kernel, the
+// density slot among them
+static int t10_adjoint_prepare(tlfea_t10_t d) { return sens_prepare(d, "tlfea_newton_adjoint_step"); }
+static void t10_adjoint_materials(tlfea_t10_t d, hipStream_t st, const double* w, const double* u, const double*,
+                                  double* per_material, double* per_element) {
+  const int slots = sens_slots(d);
+  sens_launch_points(d, st, w, u);
+  if (per_material) {
+    sens_launch_sums(d, st);
+    (void)hipMemcpyAsync(per_material, d->d_sn_out, (size_t)sens_n_mat(d) * slots * sizeof(double), hipMemcpyDeviceToDevice, st);
+  }
+  if (per_element) launch_sens_transpose(st, d->E, d->Epad, slots, d->d_sn_sens, per_element);
+}
+static size_t t10_pm_doubles(tlfea_t10_t d) { return (size_t)sens_n_mat(d) * sens_slots(d); }
+static size_t t10_pe_doubles(tlfea_t10_t d) { return (size_t)d->E * sens_slots(d); }
+static const AdjointKind kT10Adjoint{"tlfea_newton_adjoint_step", 1, adjoint_refusal, t10_adjoint_prepare, t10_adjoint_materials,
+                                    t10_pm_doubles, t10_pe_doubles};
+
+// The adjoint step on device pointers, for the element kind K (X_bar: T10 only).
+int tlfea::adjoint_step_device(tlfea_newton_t s, const AdjointKind& K, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                               double* X_bar, int* info, double* rel_res) {
+  TRY(K.refusal(s));
+  const std::string what = K.what;
+  if (!in || !out) return fail(what + ": null argument");
   tlfea_t10_t d = s->d;
   if (X_bar) {
     TRY(adjoint_shape_refusal(s));
     TRY(shape_prepare(d, "tlfea_newton_adjoint_step_shape"));
   }
-  TRY(sens_prepare(d, "tlfea_newton_adjoint_step"));
+  TRY(K.prepare(d));
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
   TRY(sync_constraints(s));
   const int n = 3 * s->N, nc = s->n_constraints;
   const double h = s->prm.time_step, rho = s->prm.rho;
   const double* vprev = in->v_prev ? in->v_prev : (s->d_step0 ? s->d_step0 + n : nullptr);
-  if (!vprev) return fail("tlfea_newton_adjoint_step: no v_prev given and no Solve() has kept one");
+  if (!vprev) return fail(what + ": no v_prev given and no Solve() has kept one");
   AdjCons J{0, d->d_fixed, d->d_fixed_slot, d->d_joff, d->d_jcol, d->d_jtoff, d->d_jtcol, d->d_jval, d->d_jtval};
   J.mode = pinned_on(s) ? 1 : (lincons_on(s) ? 2 : 0);
   const double zero3[3] = {0.0, 0.0, 0.0};
@@ -5215,14 +5250,14 @@ extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tl
   LamKeep keep;
   TRY(keep.save(s, wk, /*solve_state=*/true));  // cold estimates: the result depends on no earlier solve
   launch_adj_rhs(s->stream, n, J, in->x_bar, in->v_bar, J.mode ? in->lam_bar : nullptr, s->d_v, vprev,
-                 d->ld_have_a ? d->ld_a : zero3, h, rho, xt, vt, u);
+                 d->ld_have_a ? d->ld_a : zero3, K.stride, h, rho, xt, vt, u);
   int it = 0;
   double rel = 0.0;
   int rc = assemble(s, /*fq_fresh=*/false);
   // the solve runs on the Newton iteration's own right-hand side and solution vectors (scratch between Solve() calls), so
   // the captured CG graphs stay those of the forward step
   if (!rc && hipMemcpyAsync(s->d_b, vt, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream) != hipSuccess)
-    rc = fail("tlfea_newton_adjoint_step: device copy failed");
+    rc = fail(what + ": device copy failed");
   if (!rc) rc = pcg(s, s->d_b, s->d_dv, &it, &rel);
   const std::string why = rc ? api_error() : std::string();
   if (rc) {
@@ -5239,19 +5274,12 @@ extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tl
     for (double* p : {out->lam_in_bar, out->t_bar})
       if (p) (void)hipMemsetAsync(p, 0, (size_t)nc * sizeof(double), s->stream);
   }
-  if (out->a_bar)
-    launch_adj_sums(s->stream, 3, s->N, (s->N + kAdjChunk - 1) / kAdjChunk, nullptr, nullptr, Mw, 1, 3, 1, nullptr,
+  if (out->a_bar) {  // over the position coefficients: every K.stride-th coefficient vector
+    const int n_pos = s->N / K.stride;
+    launch_adj_sums(s->stream, 3, n_pos, (n_pos + kAdjChunk - 1) / kAdjChunk, nullptr, nullptr, Mw, 1, 3 * K.stride, 1, nullptr,
                     d->d_sn_part, out->a_bar);
-  if (out->per_material || out->per_element) {
-    const int slots = sens_slots(d);
-    sens_launch_points(d, s->stream, w, u);
-    if (out->per_material) {
-      sens_launch_sums(d, s->stream);
-      (void)hipMemcpyAsync(out->per_material, d->d_sn_out, (size_t)sens_n_mat(d) * slots * sizeof(double),
-                           hipMemcpyDeviceToDevice, s->stream);
-    }
-    if (out->per_element) launch_sens_transpose(s->stream, d->E, d->Epad, slots, d->d_sn_sens, out->per_element);
   }
+  if (out->per_material || out->per_element) K.materials(d, s->stream, w, u, Mw, out->per_material, out->per_element);
   if (X_bar) {
     shape_launch_points(d, s->stream, w, u);
     shape_launch_gather(d, s->stream, X_bar);
@@ -5265,19 +5293,25 @@ extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tl
   return 0;
 }
 
-extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                                                int* info, double* rel_res) {
-  return tlfea_newton_adjoint_step_shape_device(s, in, out, nullptr, info, rel_res);
+extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tlfea_adjoint_in* in,
+                                                      const tlfea_adjoint_out* out, double* X_bar, int* info, double* rel_res) {
+  return adjoint_step_device(s, kT10Adjoint, in, out, X_bar, info, rel_res);
 }
 
-extern "C" int tlfea_newton_adjoint_step_shape(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                                               double* X_bar, int* info, double* rel_res) {
-  TRY(adjoint_refusal(s));
-  if (!in || !out) return fail("tlfea_newton_adjoint_step: null argument");
+extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                                                int* info, double* rel_res) {
+  return adjoint_step_device(s, kT10Adjoint, in, out, nullptr, info, rel_res);
+}
+
+// The same on host arrays: device copies of what is given and wanted around adjoint_step_device.
+int tlfea::adjoint_step_host(tlfea_newton_t s, const AdjointKind& K, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                             double* X_bar, int* info, double* rel_res) {
+  TRY(K.refusal(s));
+  if (!in || !out) return fail(std::string(K.what) + ": null argument");
   tlfea_t10_t d = s->d;
   if (X_bar) TRY(adjoint_shape_refusal(s));
   const size_t n = 3 * (size_t)s->N, nc = (size_t)s->n_constraints;
-  const size_t n_pm = (size_t)sens_n_mat(d) * sens_slots(d), n_pe = (size_t)d->E * sens_slots(d);
+  const size_t n_pm = K.pm_doubles(d), n_pe = K.pe_doubles(d);
   ModalWork wk;
   tlfea_adjoint_in din{nullptr, nullptr, nullptr, nullptr};
   tlfea_adjoint_out dout{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -5302,15 +5336,20 @@ extern "C" int tlfea_newton_adjoint_step_shape(tlfea_newton_t s, const tlfea_adj
                       {X_bar, &d_Xbar, n}};
   for (const Ret& r : rets)
     if (r.host && r.cnt > 0) TRY(wk.alloc(r.dev, r.cnt));
-  TRY(tlfea_newton_adjoint_step_shape_device(s, &din, &dout, d_Xbar, info, rel_res));
+  TRY(adjoint_step_device(s, K, &din, &dout, d_Xbar, info, rel_res));
   for (const Ret& r : rets)
     if (r.host && r.cnt > 0) HIP_TRY(hipMemcpy(r.host, *r.dev, r.cnt * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
+extern "C" int tlfea_newton_adjoint_step_shape(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
+                                               double* X_bar, int* info, double* rel_res) {
+  return adjoint_step_host(s, kT10Adjoint, in, out, X_bar, info, rel_res);
+}
+
 extern "C" int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
                                          int* info, double* rel_res) {
-  return tlfea_newton_adjoint_step_shape(s, in, out, nullptr, info, rel_res);
+  return adjoint_step_host(s, kT10Adjoint, in, out, nullptr, info, rel_res);
 }
 
 

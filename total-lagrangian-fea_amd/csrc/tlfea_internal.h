@@ -645,8 +645,12 @@ struct SensShape {
 // -sum_q dV (dP/dtheta_p)(F) : grad w, then the density slot -sum_q dV (N w).(N u) (u null: zeros).  w, u [3N] interleaved.
 void launch_sens_points(hipStream_t s, const ElemView& m, int model, const SensShape& sh, const double* w, const double* u,
                         double* sens);
+// The ANCF kinds (DESIGN 3j'): sens [P][Epad], stiffness slots only; w [3 n_coef] interleaved.  The density slot is
+// sum_i out_i of launch_ancf_rho_terms: out [N], out_i = scale (M w)_i . u_i.
+void launch_ancf_sens_points(hipStream_t s, const ElemView& m, int model, const double* w, double* sens);
+void launch_ancf_rho_terms(hipStream_t s, int N, const double* Mw, const double* u, double scale, double* out);
 void launch_sens_transpose(hipStream_t s, int E, int Epad, int slots, const double* sens, double* out /*[E][slots]*/);
-// Fixed-order sums of `slots` (3 | 4) values per item over groups of items: value (c, k) = src[c slot_stride +
+// Fixed-order sums of `slots` (1 .. 4) values per item over groups of items: value (c, k) = src[c slot_stride +
 // item item_stride], item = idx ? idx[k] : k.  Partial block b adds the items [blk[b].x, blk[b].y) (blk null: chunks of
 // kAdjChunk over [0, n)), then block g of the final launch adds the partial rows [boff[g], boff[g + 1]) (boff null: one
 // group of all nb rows) into out [groups][slots].  partial: nb x slots doubles.
@@ -661,10 +665,11 @@ struct AdjCons {
   const int *joff, *jcol, *jtoff, *jtcol;   // mode 2
   const double *jval, *jtval;
 };
-// x_t = x_bar + rho J^T lam_bar, v_t = v_bar + h x_t, u = (v - v_prev) / h - a over the n = 3N DOFs (null cotangent = 0)
+// x_t = x_bar + rho J^T lam_bar, v_t = v_bar + h x_t, u = (v - v_prev) / h - a over the n = 3N DOFs (null cotangent = 0);
+// a acts on every stride-th coefficient vector (T10: 1, every node; ANCF: 4, the position coefficients) and is 0 elsewhere
 void launch_adj_rhs(hipStream_t s, int n, const AdjCons& J, const double* xbar, const double* vbar, const double* lambar,
-                    const double* v, const double* vprev, const double a[3], double h, double rho, double* xt, double* vt,
-                    double* u);
+                    const double* v, const double* vprev, const double a[3], int stride, double h, double rho, double* xt,
+                    double* vt, double* u);
 // f_ext_bar = w, v_prev_bar = M w / h, x_prev_bar = x_t - (v_t - M w / h) / h per DOF; lam_in_bar = lam_bar - h J w,
 // t_bar = h rho J w - rho lam_bar per constraint row (null output = not wanted)
 void launch_adj_out(hipStream_t s, int n, int nc, const AdjCons& J, const double* w, const double* Mw, const double* xt,

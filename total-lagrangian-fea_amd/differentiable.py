@@ -1,4 +1,5 @@
-"""Differentiable implicit step of a T10 body: torch.autograd over SyncedNewtonSolver.Solve().
+"""Differentiable implicit step of a T10 body or an ANCF beam / shell body (DESIGN 3j'): torch.autograd over
+SyncedNewtonSolver.Solve().
 
 One step with max_outer = 1 maps the state (x, v, lambda) and the inputs f_ext, constraint targets, body acceleration
 and material parameters to the next state.  ImplicitStep runs the engine's own forward step and, in backward, the
@@ -16,14 +17,19 @@ has to go back), and backward returns its cotangent.  straight_sided() places th
 vertices in torch, so a vertex-only parametrisation differentiates through autograd.  With a reference that requires a
 gradient, obstacles and face tractions are refused as well.
 
-Not differentiated (refused by the adjoint step): ANCF kinds, damping, friction, follower pressure, a partitioned mesh,
-steps with more than one outer iteration.
+An ANCF data object (GPU_ANCF3243_Data, GPU_ANCF3443_Data) dispatches to the ANCF entry points by its class: x and v are
+[n_coef, 3] over all coefficient vectors, targets [n_fixed, 3] those of the fixed coefficients (or the CSR right-hand side),
+materials [1, P + 1] (one material per object), gravity acts on the position coefficients.  A density change reruns
+CalcMassMatrix, on the host for these kinds.  `reference` is refused: ANCF shape sensitivities are not built.
+
+Not differentiated (refused by the adjoint step): damping, friction, follower pressure, a partitioned mesh, steps with more
+than one outer iteration; on ANCF bodies also the reference geometry and the cross-section.
 """
 import numpy as np
 import torch
 
 from .binding import AdjointInC, AdjointOutC, TlfeaError
-from .elements import ElementMaterial
+from .elements import ElementMaterial, _GPU_ANCF_Data
 
 
 def lame_from_E_nu(E, nu):
@@ -40,14 +46,30 @@ def _np(t):
     return None if t is None else t.detach().cpu().numpy().astype(np.float64)
 
 
+def _is_ancf(data):
+    return isinstance(data, _GPU_ANCF_Data)
+
+
+def _material_shape(data):
+    return data.ANCFMaterialSensitivityShape() if _is_ancf(data) else data.MaterialSensitivityShape()
+
+
+def _fixed_targets(data, t):
+    """full target arrays from the [n_fixed, 3] rows of the fixed nodes / coefficients (targets of free ones are never read)"""
+    full = np.array(data._X0, dtype=np.float64)
+    if t is not None:
+        full[data.fixed_nodes] = t.reshape(-1, 3)
+    return full
+
+
 def _apply_inputs(solver, data, f_ext, targets, gravity, materials):
     """Write one step's differentiable inputs into the objects (None = leave what is set)."""
     if materials is not None:
         m = _np(materials)
-        n_mat, slots = data.MaterialSensitivityShape()
+        n_mat, slots = _material_shape(data)
         if m.shape != (n_mat, slots):
             raise ValueError(f"materials must be [{n_mat}, {slots}] for the model and table set, got {tuple(m.shape)}")
-        ids = data.GetElementMaterialIds()
+        ids = None if _is_ancf(data) else data.GetElementMaterialIds()
         if slots == 3:
             En = [E_nu_from_lame(r[0], r[1]) for r in m]
             mats = [ElementMaterial(E=e, nu=nu, rho0=r[2]) for (e, nu), r in zip(En, m)]
@@ -63,7 +85,14 @@ def _apply_inputs(solver, data, f_ext, targets, gravity, materials):
             data.SetDensity(mats[0].rho0)
         rho = m[:, -1].copy()
         if getattr(data, "_mass_rho", None) is None or not np.array_equal(data._mass_rho, rho):
+            moved = _is_ancf(data) and getattr(data, "_targets_applied", None) is not None
+            if moved:  # an ANCF object keeps its targets where its reference coefficients are, and the mass rule reads those
+                X0 = data._X0
+                data.UpdateConstraintTargets(X0[:, 0], X0[:, 1], X0[:, 2])
             data.CalcMassMatrix()
+            if moved:
+                full = data._targets_applied
+                data.UpdateConstraintTargets(full[:, 0], full[:, 1], full[:, 2])
             data._mass_rho = rho
     if gravity is not None:
         data.SetGravity(_np(gravity).reshape(3))
@@ -74,9 +103,9 @@ def _apply_inputs(solver, data, f_ext, targets, gravity, materials):
         if data.GetConstraintMode() == 2:
             data.UpdateLinearConstraintRHS(t.reshape(-1))
         else:
-            full = np.array(data._X0, dtype=np.float64)  # targets of free nodes are never read
-            full[data.fixed_nodes] = t.reshape(-1, 3)
+            full = _fixed_targets(data, t)
             data.UpdateConstraintTargets(full[:, 0], full[:, 1], full[:, 2])
+            data._targets_applied = full
 
 
 _EDGES = ((0, 1), (1, 2), (0, 2), (0, 3), (1, 3), (2, 3))  # mid-edge node 4 + k lies between these vertices
@@ -108,13 +137,17 @@ def _apply_reference(data, reference):
 class ImplicitStep(torch.autograd.Function):
     """(x, v, lambda)_new = ImplicitStep.apply(solver, data, x, v, lam, f_ext, targets, gravity, materials[, reference]).
 
-    x, v [N, 3], lam [n_constraints]; f_ext [N, 3]; targets [n_fixed, 3] (positions of data.fixed_nodes, in their order)
+    x, v [N, 3] (N = n_coef), lam [n_constraints]; f_ext [N, 3]; targets [n_fixed, 3] (positions of data.fixed_nodes, in their order)
     or the right-hand side [n_constraints] of CSR constraints; gravity [3]; materials [n_mat, P + 1].  Any of the last four
     may be None: the objects keep what is set and no gradient flows.  reference [N, 3] (optional): the reference geometry.
     The solver's parameters must have max_outer = 1."""
 
     @staticmethod
     def forward(ctx, solver, data, x, v, lam, f_ext, targets, gravity, materials, reference=None):
+        ancf = _is_ancf(data)
+        if ancf and reference is not None:
+            raise ValueError("ImplicitStep: `reference` is not available on an ANCF object -- shape and cross-section "
+                             "sensitivities of the ANCF kinds are not built (DESIGN 9)")
         _apply_reference(data, reference)
         _apply_inputs(solver, data, f_ext, targets, gravity, materials)
         xn, vn = _np(x).reshape(-1, 3), _np(v).reshape(-1)
@@ -123,7 +156,8 @@ class ImplicitStep(torch.autograd.Function):
         if solver.n_constraints:
             solver.SetLambda(_np(lam).reshape(-1))
         solver.Solve()
-        solver.AdjointReady()  # a step the adjoint would refuse is refused here, where the cause is
+        # a step the adjoint would refuse is refused here, where the cause is
+        solver.ANCFAdjointReady() if ancf else solver.AdjointReady()
         x1 = np.stack(data.RetrievePositionToCPU(), axis=1)
         v1 = solver.RetrieveVelocityToCPU().reshape(-1, 3)
         lam1 = solver.RetrieveLambdaToCPU()
@@ -149,7 +183,7 @@ class ImplicitStep(torch.autograd.Function):
             solver.SetLambda(lam1)
         dev = torch.device("cuda")
         N, nc = data.n_coef, solver.n_constraints
-        n_mat, slots = data.MaterialSensitivityShape()
+        n_mat, slots = _material_shape(data)
 
         def up(t):
             return None if t is None else t.detach().to(dev, torch.float64).contiguous().reshape(-1)
@@ -163,7 +197,11 @@ class ImplicitStep(torch.autograd.Function):
         X_bar = z(3 * N) if want_X else None
         torch.cuda.synchronize()
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        solver.AdjointStepDevice(AdjointInC(*[ptr(t) for t in ins]), AdjointOutC(*[ptr(t) for t in outs]), ptr(X_bar))
+        cin, cout = AdjointInC(*[ptr(t) for t in ins]), AdjointOutC(*[ptr(t) for t in outs])
+        if _is_ancf(data):
+            solver.ANCFAdjointStepDevice(cin, cout)
+        else:
+            solver.AdjointStepDevice(cin, cout, ptr(X_bar))
         sx, sv, sl = ctx.shapes
         back = lambda t, shape: None if t is None else t.cpu().reshape(shape)  # noqa: E731
         return (None, None, back(outs[2], sx), back(outs[1], sv), back(outs[3], sl) if nc else torch.zeros(sl, dtype=torch.float64),

@@ -676,6 +676,7 @@ class _GPU_ANCF_Data(GPU_FEAT10_Data):
         check(self._lib.tlfea_ancf_setup(self._h, dp(L), dp(W), dp(H), dp(mr[0]), dp(mr[1]), dp(mr[2]), dp(mr[3]),
                                          dp(mr[4]), dp(mr[5]), ip(nqm), dp(fr[0]), dp(fr[1]), dp(fr[2]), dp(fr[3]),
                                          dp(fr[4]), dp(fr[5]), ip(nq), dp(x), dp(y), dp(z), ip(conn), 0))
+        self._X0 = np.stack([x, y, z], axis=1)                    # reference coefficients: the targets of fixed ones
 
     def CalcDsDuPre(self):
         check(self._lib.tlfea_ancf_calc_dsdu_pre(self._h))
@@ -736,6 +737,34 @@ class _GPU_ANCF_Data(GPU_FEAT10_Data):
             raise ValueError("TimeANCFStressKernels: pass a solver or None")
         out = np.zeros(3)
         check(self._lib.tlfea_ancf_time_stress_kernels(self._h, C.c_void_p(ptr), int(bool(want_points)), int(reps), dp(out)))
+        return out
+
+    # -- material sensitivities (DESIGN 3j'); MaterialSensitivity stays T10-only and keeps refusing ---------------------
+    def ANCFMaterialSensitivityShape(self):
+        """(1, P + 1): the object's one material and the slots of the model set now -- SVK (lambda, mu, rho0),
+        Mooney-Rivlin (mu10, mu01, kappa, rho0)."""
+        n_mat, slots = C.c_int(), C.c_int()
+        check(self._lib.tlfea_ancf_material_sensitivity_shape(self._h, C.byref(n_mat), C.byref(slots)))
+        return n_mat.value, slots.value
+
+    def ANCFMaterialSensitivity(self, w, u=None):
+        """The element kernel of the ANCF adjoint step and the sums alone, at the current coefficients: for an adjoint
+        field w [3 n_coef or n_coef x 3], per element -sum_q dV (dP/dtheta_p)(F) : grad w over the force rule's points for
+        every stiffness parameter; the density slot is -(M w) . u / rho0 for an acceleration field u (None: 0), with the
+        density the mass matrix was assembled with.  -> (per_element [E, P], per_material [1, P + 1])."""
+        w = _f64(w).reshape(-1)
+        u = None if u is None else _f64(u).reshape(-1)
+        if w.size != 3 * self.n_coef or (u is not None and u.size != w.size):
+            raise ValueError(f"ANCFMaterialSensitivity: w and u need {3 * self.n_coef} entries")
+        n_mat, slots = self.ANCFMaterialSensitivityShape()
+        pe, pm = np.zeros((self.n_elem, slots - 1)), np.zeros((n_mat, slots))
+        check(self._lib.tlfea_ancf_material_sensitivity(self._h, dp(w), dp(u), dp(pe), dp(pm)))
+        return pe, pm
+
+    def TimeANCFSensitivityKernels(self, reps=20):
+        """-> mean ms of (element kernel, sums of its P planes) over `reps` back-to-back launches each."""
+        out = np.zeros(2)
+        check(self._lib.tlfea_ancf_time_sensitivity_kernels(self._h, int(reps), dp(out)))
         return out
 
     # -- surface loads (DESIGN 3h): dead traction and follower pressure on element faces -------------------------------

@@ -1336,6 +1336,25 @@ struct GPU_ANCF_DataBase : public GPU_FEAT10_Data {
   void TimeANCFStressKernels(const double* d_velocity, bool want_points, int reps, double out_ms3[3]) {
     TLFEA_HANDLE_ERROR(tlfea_ancf_time_stress_kernels(h, d_velocity, want_points ? 1 : 0, reps, out_ms3));
   }
+  // material sensitivities (DESIGN 3j', no reference counterpart): the element kernel of the ANCF adjoint step and the
+  // sums alone, at the current coefficients.  w, u [3 n_coef] (u empty: density slot 0; given: -(M w).u / rho0 with the
+  // density of the assembled mass matrix) -> per_element [E][P] (stiffness slots), per_material [P + 1]
+  void ANCFMaterialSensitivityShape(int& n_mat, int& slots) {
+    TLFEA_HANDLE_ERROR(tlfea_ancf_material_sensitivity_shape(h, &n_mat, &slots));
+  }
+  void ANCFMaterialSensitivity(const std::vector<double>& w, const std::vector<double>& u, std::vector<double>& per_element,
+                               std::vector<double>& per_material) {
+    int n_mat = 0, slots = 0;
+    ANCFMaterialSensitivityShape(n_mat, slots);
+    per_element.assign(static_cast<size_t>(n_elem) * (slots - 1), 0.0);
+    per_material.assign(static_cast<size_t>(slots), 0.0);
+    TLFEA_HANDLE_ERROR(tlfea_ancf_material_sensitivity(h, w.data(), u.empty() ? nullptr : u.data(), per_element.data(),
+                                                       per_material.data()));
+  }
+  // mean ms of (element kernel, sums of its P planes) over `reps` launches each
+  void TimeANCFSensitivityKernels(int reps, double out_ms2[2]) {
+    TLFEA_HANDLE_ERROR(tlfea_ancf_time_sensitivity_kernels(h, reps, out_ms2));
+  }
   // element connectivity in NODE ids, n_beam x (2 | 4) (ANCF3243Data.cu:630-642, ANCF3443Data.cu:597-603); the handle
   // keeps coefficient ids [S][E] (slot 0 of node n of the element = 4 * node)
   void RetrieveConnectivityToCPU(tlfea::MatrixXi& connectivity) {
@@ -1567,6 +1586,35 @@ class SyncedNewtonSolver : public SolverBase {
       TLFEA_HANDLE_ERROR(tlfea_newton_adjoint_step(s_, &ci, &co, &r.iterations, &r.rel_res));
     }
     return r;
+  }
+
+  // The same on an ANCF beam or shell object (DESIGN 3j'): every vector runs over the n_coef coefficient vectors, the body
+  // acceleration acts on the position coefficients (gravity sums M w over those), per_material is [1][P + 1] (the density
+  // slot is -(M w).u / rho0) and per_element [E][P] (stiffness slots only).  AdjointStep itself keeps refusing such an object.
+  void ANCFAdjointReady() { TLFEA_HANDLE_ERROR(tlfea_newton_ancf_adjoint_ready(s_)); }
+  AdjointResult ANCFAdjointStep(const std::vector<double>& xbar, const std::vector<double>& vbar,
+                                const std::vector<double>& lambar = {}, const std::vector<double>& v_prev = {},
+                                bool per_material = true, bool per_element = false) {
+    const size_t n = 3 * (size_t)n_coef_, nc = (size_t)std::max(0, tlfea_newton_n_constraints(s_));
+    AdjointResult r;
+    TLFEA_HANDLE_ERROR(tlfea_ancf_material_sensitivity_shape(data_, &r.n_mat, &r.slots));
+    auto in = [](const std::vector<double>& a, size_t want) { return a.size() == want && want ? a.data() : nullptr; };
+    r.f_ext.assign(n, 0.0); r.v_prev.assign(n, 0.0); r.x_prev.assign(n, 0.0);
+    r.lam_in.assign(nc, 0.0); r.targets.assign(nc, 0.0);
+    if (per_material) r.per_material.assign((size_t)r.slots, 0.0);
+    if (per_element) r.per_element.assign((size_t)tlfea_t10_get_n_elem(data_) * (r.slots - 1), 0.0);
+    tlfea_adjoint_in ci{in(xbar, n), in(vbar, n), in(lambar, nc), in(v_prev, n)};
+    tlfea_adjoint_out co{r.f_ext.data(), r.v_prev.data(), r.x_prev.data(), nc ? r.lam_in.data() : nullptr,
+                         nc ? r.targets.data() : nullptr, r.gravity, per_material ? r.per_material.data() : nullptr,
+                         per_element ? r.per_element.data() : nullptr};
+    TLFEA_HANDLE_ERROR(tlfea_newton_ancf_adjoint_step(s_, &ci, &co, &r.iterations, &r.rel_res));
+    return r;
+  }
+  // the same on device pointers (a_bar and per_material included): -> iterations; rel_res optional
+  int ANCFAdjointStepDevice(const tlfea_adjoint_in& in, const tlfea_adjoint_out& out, double* rel_res = nullptr) {
+    int it = 0;
+    TLFEA_HANDLE_ERROR(tlfea_newton_ancf_adjoint_step_device(s_, &in, &out, &it, rel_res));
+    return it;
   }
 
  private:

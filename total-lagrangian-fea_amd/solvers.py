@@ -410,6 +410,50 @@ class SyncedNewtonSolver:
                                                                    C.byref(it), C.byref(rel)))
         return it.value, rel.value
 
+    # -- the same on ANCF beam and shell objects (DESIGN 3j'); AdjointStep stays T10-only and keeps refusing -----------------
+    def ANCFAdjointReady(self):
+        """Raises TlfeaError with the reason when ANCFAdjointStep would refuse the solver's state now."""
+        check(self._lib.tlfea_newton_ancf_adjoint_ready(self._h))
+
+    def ANCFAdjointStep(self, x_bar=None, v_bar=None, lam_bar=None, v_prev=None, want=("per_material",)):
+        """AdjointStep on an ANCF object: every vector runs over the n_coef coefficient vectors; the body acceleration
+        acts on the position coefficients (index % 4 == 0), so `gravity` sums M w over those; targets are those of the
+        fixed coefficients (3 slot + component) or the right-hand side of the CSR rows.  `want`: which of "per_material"
+        [1, P + 1] (stiffness slots, then the density: -(M w).u / rho0) and "per_element" [E, P] (stiffness slots only)
+        to compute; the vector outputs always come.  The solver's state is left as it was."""
+        n, nc = 3 * self.n_coef, int(self._lib.tlfea_newton_n_constraints(self._h))
+        self.n_constraints = nc
+        unknown = set(want) - {"per_material", "per_element"}
+        if unknown:
+            raise ValueError(f"ANCFAdjointStep: want holds {sorted(unknown)}; it takes 'per_material' and 'per_element'")
+
+        def arr(a, size, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            if a.size != size:
+                raise ValueError(f"ANCFAdjointStep: {name} needs {size} entries, got {a.size}")
+            return a
+        ins = [arr(x_bar, n, "x_bar"), arr(v_bar, n, "v_bar"), arr(lam_bar, nc, "lam_bar"), arr(v_prev, n, "v_prev")]
+        n_mat, slots = self._data.ANCFMaterialSensitivityShape()
+        outs = [np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(nc), np.zeros(nc), np.zeros(3),
+                np.zeros((n_mat, slots)) if "per_material" in want else None,
+                np.zeros((self._data.n_elem, slots - 1)) if "per_element" in want else None]
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
+        cin, cout = AdjointInC(*[ptr(a) for a in ins]), AdjointOutC(*[ptr(a) for a in outs])
+        it, rel = C.c_int(), C.c_double()
+        check(self._lib.tlfea_newton_ancf_adjoint_step(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
+        N = self.n_coef
+        return AdjointResult(outs[0].reshape(N, 3), outs[1].reshape(N, 3), outs[2].reshape(N, 3), outs[3], outs[4],
+                             outs[5], outs[6], outs[7], it.value, rel.value)
+
+    def ANCFAdjointStepDevice(self, cin, cout):
+        """The same on device pointers (binding.AdjointInC / AdjointOutC filled with device addresses, 0 / None = absent):
+        -> (iterations, rel_res).  differentiable.ImplicitStep calls this with torch tensors."""
+        it, rel = C.c_int(), C.c_double()
+        check(self._lib.tlfea_newton_ancf_adjoint_step_device(self._h, C.byref(cin), C.byref(cout), C.byref(it), C.byref(rel)))
+        return it.value, rel.value
+
     def ModalApplyBlock(self, X, which=0, apply_mask=False):
         """Y = H X (which 0) or (M (x) I3) X (which 1) for a block X [3N, m], m <= 32, with the current H (test hook)"""
         X = np.ascontiguousarray(X, dtype=np.float64)
