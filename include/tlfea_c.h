@@ -634,6 +634,12 @@ int tlfea_newton_get_lambda_max(tlfea_newton_t s, double out[4]);
  * before storing them (TLFEA_MATFREE_COMPACT, default 1), 0 for one row per (element, local node), -1 before the first
  * product.  rows = rows of the buffer, ratio = 10 E / rows (1 for the element form); either may be null. */
 int tlfea_newton_get_matfree_rows(tlfea_newton_t s, long long *rows, double *ratio);
+/* Test hook: the element records of the matrix-free passes of the assembled H.  which 0 / 1 = the element-major records
+ * g [E][16] / F [E][5][10] in double; 2 / 3 = the packed lane-major g / F the kernels read (csrc/matfree_records.h): of the
+ * fp64 product (single = 0, double; once a product has run) or of the fine smoother passes (single = 1, float; after a
+ * preconditioner set-up that chose them).  len = values in that buffer, out may be null.  points = the stored points of
+ * the packed F of that type (4 | 5: TLFEA_MATFREE_POINTS, or the default).  An error where those records do not exist. */
+int tlfea_newton_get_matfree_records(tlfea_newton_t s, int single, int which, void *out, long long *len, int *points);
 /* One full Newton iteration without the convergence test (gradient, assembly, solve, update):
  * the unit bench.py times.  iters = PCG iterations used. */
 int tlfea_newton_iteration(tlfea_newton_t s, double *norm_g, int *iters);

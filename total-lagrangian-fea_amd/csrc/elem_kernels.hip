@@ -2163,7 +2163,8 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
 // vertex gradients + det J, 400 bytes of F at the five points, 40 bytes of connectivity -- instead of the 2 950 bytes
 // of CSR stream per element.  Two launches in the shape of residual_kernel + grad_light_kernel:
 //   tangent_apply_affine_kernel  thread per element: dF(q) = sum_n U_n(q) (x) g_n, dP = dF S_h + F dS, one 24-byte row
-//                                per (element, local node) into ybuf [a][Epad][3]
+//                                per (element, local node) into ybuf [a][Epad][3].  It reads packed copies of the records
+//                                (matfree_records.h): 80 bytes of g_0..g_2 + det J and 72 bytes of F per stored point
 //   matfree_gather_kernel        8 lanes per node sum the node's rows in ascending element order (fixed-order butterfly),
 //                                add h^2 rho p on pinned rows, store q and the p.q partial slots
 // With L the barycentric coordinates of a point, grad N of vertex n is (4 L_n - 1) g_n and of mid-edge (n, m)
@@ -2177,30 +2178,110 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
 // CP (compact rows, matfree_compact.h): instead of one row per (element, local node), the wavefront parks its 640 rows in
 // LDS, sums them per node in the list order of the host builder (ascending element) and stores one row per unique node:
 // ybuf [rows][3], rows of wavefront w from cp.row_off[w].  No atomics: the order is the list's.
+// NP (packed records, matfree_records.h): the g and F records are read lane-major, every lane its own values with whole
+// wavefront loads, nothing through LDS.  NP = 5: F at the five points; NP = 4: the outer points only, they come first and
+// the centroid's F = 1/4 ((F_1 + F_2) + (F_3 + F_4)) last.  g_3 = -(g_0 + g_1 + g_2).
 namespace {
-constexpr int kMfG = 18;            // doubles per staged g record (16 + pad: 144 bytes, own-record reads spread over the banks)
-constexpr int kMfLds = 64 * kMfG;   // doubles of wave-private LDS (g records, then 64 x 10 of F per point, then 64 x 3 rows)
-// compact form: [0, 1920) the 640 parked rows (over the g / F staging), [1920, 2112) 64 summed rows on their way out,
-// then 640 source entries and 640 descriptors of 16 bits: 19 456 bytes per wavefront, 4 workgroups in a CU's 160 KB
+constexpr int kMfLds = 64 * 3;      // reals of wave-private LDS: the 64 rows of one local node on their way out
+static_assert(2 * kMfLds * 8 <= 4 * 1024, "tangent_apply_affine_kernel<false>: LDS never limits the waves per SIMD");
+// compact form: [0, 1920) the 640 parked rows, [1920, 2112) 64 summed rows on their way out, then 640 source entries and
+// 640 descriptors of 16 bits: 19 456 bytes per wavefront, 4 workgroups in a CU's 160 KB
 constexpr int kMfcRows = 3 * kMfcSrc, kMfcOut = 3 * 64;
 constexpr int kMfLdsCp = kMfcRows + kMfcOut + 2 * kMfcSrc / 4;
 static_assert(4 * 2 * kMfLdsCp * 8 <= 160 * 1024, "four workgroups of tangent_apply_affine_kernel<true> per CU");
 // single precision (the fine smoother, DESIGN 3g'): the same layout in floats, the lists take twice the slots
 constexpr int kMfLdsCpF = kMfcRows + kMfcOut + kMfcSrc;
-// three waves per SIMD: 162 VGPRs and no scratch; four would need 128 VGPRs, which the compiler reaches with 272 bytes of scratch
+// three waves per SIMD: 168 VGPRs (20 bytes of scratch per lane with NP = 5, 84 with NP = 4; DESIGN 3g'); four would need 128
 static_assert(6 * 2 * kMfLdsCpF * 4 <= 160 * 1024, "six workgroups of tangent_apply_affine_kernel<true, float> per CU");
 template <typename R> struct MfPair;
 template <> struct MfPair<double> { using type = double2; };
 template <> struct MfPair<float> { using type = float2; };
+
+// one lane's T values of a tile's sub-record (matfree_records.h): a load (store) of 16 bytes per full group, the rest
+// of the sub-record in one shorter piece
+template <typename R, int N> struct MfrVec { typedef R type __attribute__((ext_vector_type(N))); };
+template <typename R, int T, int Q = 0>
+__device__ __forceinline__ void mfr_load(const R* __restrict__ sub, const int lane, R* v) {
+  constexpr int G = mfr_group(sizeof(R));
+  if constexpr (Q * G < T) {
+    constexpr int n = mfr_group_len(T, G, Q * G);
+    using V = typename MfrVec<R, n>::type;
+    const V x = *reinterpret_cast<const V*>(sub + (unsigned)mfr_sub_index(T, G, lane, Q * G));
+#pragma unroll
+    for (int k = 0; k < n; k++) v[Q * G + k] = x[k];
+    mfr_load<R, T, Q + 1>(sub, lane, v);
+  }
+}
+template <typename R, int T, int Q = 0>
+__device__ __forceinline__ void mfr_store(R* __restrict__ sub, const int lane, const R* v) {
+  constexpr int G = mfr_group(sizeof(R));
+  if constexpr (Q * G < T) {
+    constexpr int n = mfr_group_len(T, G, Q * G);
+    using V = typename MfrVec<R, n>::type;
+    V x;
+#pragma unroll
+    for (int k = 0; k < n; k++) x[k] = v[Q * G + k];
+    *reinterpret_cast<V*>(sub + mfr_sub_index(T, G, lane, Q * G)) = x;
+    mfr_store<R, T, Q + 1>(sub, lane, v);
+  }
+}
 }  // namespace
 
+// Packed copies of the records in R (matfree_records.h): thread per lane of a tile, the lanes past E copy the last element.
+// Fq16 (may be null): [E][5][10] as the residual launch writes it -> Fp; gvec (may be null): [E][16] -> gp.
+template <typename R, int NP>
+__global__ __launch_bounds__(256) void matfree_pack_kernel(int E, const double* __restrict__ Fq16, const double* __restrict__ gvec,
+                                                           R* __restrict__ Fp, R* __restrict__ gp) {
+  const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t e = min(slot, (size_t)E - 1), tile = slot / kMfrWave;
+  const int lane = (int)(slot % kMfrWave);
+  if (tile >= mfr_tiles((size_t)E)) return;  // the grid is whole workgroups of four tiles
+  if (gvec) {
+    const double2* src = reinterpret_cast<const double2*>(gvec + e * 16);
+    double rec[16];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const double2 a = src[j];
+      rec[2 * j] = a.x;
+      rec[2 * j + 1] = a.y;
+    }
+    R v[kMfrGVals];
+#pragma unroll
+    for (int t = 0; t < kMfrGVals; t++) v[t] = (R)rec[mfr_g_source(t)];
+    mfr_store<R, kMfrGVals>(gp + tile * (kMfrGVals * kMfrWave), lane, v);
+  }
+  if (Fq16) {
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+      const double2* src = reinterpret_cast<const double2*>(Fq16 + e * 50 + mfr_F_slot(NP, p) * 10);
+      const double2 a0 = src[0], a1 = src[1], a2 = src[2], a3 = src[3];
+      const double a4 = Fq16[e * 50 + mfr_F_slot(NP, p) * 10 + 8];
+      const R v[kMfrFVals] = {(R)a0.x, (R)a0.y, (R)a1.x, (R)a1.y, (R)a2.x, (R)a2.y, (R)a3.x, (R)a3.y, (R)a4};
+      mfr_store<R, kMfrFVals>(Fp + (tile * NP + p) * (size_t)(kMfrFVals * kMfrWave), lane, v);
+    }
+  }
+}
+
+template <typename R>
+void launch_matfree_pack(hipStream_t s, int E, int np, const double* Fq16, const double* gvec, R* Fp, R* gp) {
+  const dim3 grid((unsigned)((mfr_tiles((size_t)E) + 3) / 4)), block(4 * kMfrWave);  // four tiles per workgroup
+  if (np == 4)
+    hipLaunchKernelGGL((matfree_pack_kernel<R, 4>), grid, block, 0, s, E, Fq16, gvec, Fp, gp);
+  else
+    hipLaunchKernelGGL((matfree_pack_kernel<R, 5>), grid, block, 0, s, E, Fq16, gvec, Fp, gp);
+}
+template void launch_matfree_pack<double>(hipStream_t, int, int, const double*, const double*, double*, double*);
+template void launch_matfree_pack<float>(hipStream_t, int, int, const double*, const double*, float*, float*);
+
 // R: the real type of the records, the direction and the rows.  float: the direction is scl[c] p[c], formed at the load.
-template <bool CP, typename R = double>
+// gp, Fp: the packed records with NP stored points.
+template <bool CP, typename R, int NP>
 __global__ __launch_bounds__(128, sizeof(R) == 8 ? 2 : 3) void tangent_apply_affine_kernel(
-    int E, int Epad, const int* __restrict__ conn, const R* __restrict__ gvec, const R* __restrict__ Fq16, MatfreeCoefT<R> mc,
+    int E, int Epad, const int* __restrict__ conn, const R* __restrict__ gp, const R* __restrict__ Fp, MatfreeCoefT<R> mc,
     const R* __restrict__ p, R* __restrict__ ybuf, MatfreeCompact cp, const R* __restrict__ scl) {
   using R2 = typename MfPair<R>::type;
   constexpr bool kF = sizeof(R) == 4;
+  static_assert(NP == 4 || NP == 5, "stored points of the packed F records");
   constexpr int kLds = CP ? (kF ? kMfLdsCpF : kMfLdsCp) : kMfLds;
   __shared__ __attribute__((aligned(16))) R st_all[2 * kLds];
   R* st = st_all + (threadIdx.x >> 6) * kLds;  // this wavefront's slice
@@ -2208,7 +2289,8 @@ __global__ __launch_bounds__(128, sizeof(R) == 8 ? 2 : 3) void tangent_apply_aff
   const int lane = threadIdx.x & 63;
   const int e0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);  // first element of this wavefront
   const int last = E - 1;
-  // lanes past the end stay for the transposes (every read is clamped to the last element, the stores stay inside Epad)
+  // lanes past the end stay for the LDS hand-offs: they read the last tile's padding lanes (copies of the last element)
+  // and the last element's connectivity, and the stores stay inside Epad
   const int e = min(blockIdx.x * blockDim.x + threadIdx.x, last);
 
   // ---- compact form: this wavefront's source list and row descriptors into LDS, long before the reduction reads them ---
@@ -2233,38 +2315,27 @@ __global__ __launch_bounds__(128, sizeof(R) == 8 ? 2 : 3) void tangent_apply_aff
     }
   }
 
-  // ---- g records: 64 x 128 contiguous bytes, whole-line loads, each lane takes its own record from LDS ---------------
-  {
-    const R2* src = reinterpret_cast<const R2*>(gvec);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const int idx = lane + 64 * j, el = idx >> 3, c = idx & 7;
-      st2[el * (kMfG / 2) + c] = src[(size_t)min(e0 + el, last) * 8 + c];
-    }
-  }
-  // F records of the first point in flight: 64 x 80 bytes, 16 per lane and instruction
-  R2 nx[5];
-  auto fetch = [&](const int sdx) __attribute__((always_inline)) {
-    const R2* src = reinterpret_cast<const R2*>(Fq16);
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-      const int idx = lane + 64 * j, el = idx / 5, c = idx - 5 * el;
-      nx[j] = src[(size_t)min(e0 + el, last) * 25 + sdx * 5 + c];
-    }
-  };
-  fetch(0);
-  wave_sync();
   R g[4][3], detJ;
-  {
-    const R* gr = st + lane * kMfG;
+  R Fn[kMfrFVals];  // the next point's F of this lane
+  // this wavefront's tile (a wavefront wholly past E reads the last tile: its lanes are padding); wave-uniform, so the
+  // base is scalar and the lane offsets are 32 bits
+  const size_t tile = (size_t)(__builtin_amdgcn_readfirstlane(min(e0, last)) >> 6);
+  const R* Fsub = Fp + tile * (size_t)(NP * kMfrFVals * kMfrWave);
+  auto fetch = [&](const int pt) __attribute__((always_inline)) {
+    mfr_load<R, kMfrFVals>(Fsub + pt * (kMfrFVals * kMfrWave), lane, Fn);
+  };
+  {  // ---- g record: ten values of this lane, g_3 from sum_n g_n = 0; the first point's F in flight ---------------------
+    R gv[kMfrGVals];
+    mfr_load<R, kMfrGVals>(gp + tile * (kMfrGVals * kMfrWave), lane, gv);
+    fetch(0);
 #pragma unroll
-    for (int n = 0; n < 4; n++) {
-      const R2 a = *reinterpret_cast<const R2*>(gr + 4 * n);
-      g[n][0] = a.x;
-      g[n][1] = a.y;
-      g[n][2] = gr[4 * n + 2];
+    for (int d = 0; d < 3; d++) {
+      g[0][d] = gv[d];
+      g[1][d] = gv[3 + d];
+      g[2][d] = gv[6 + d];
+      g[3][d] = -((gv[d] + gv[3 + d]) + gv[6 + d]);
     }
-    detJ = gr[3];
+    detJ = gv[9];
   }
 
   // ---- dF at the five points (slot order: centroid, then the point of vertex 0..3), one component of p at a time -------
@@ -2322,16 +2393,31 @@ __global__ __launch_bounds__(128, sizeof(R) == 8 ? 2 : 3) void tangent_apply_aff
   }
 
   // ---- P_q = w_q det J (dF S_h + F dS) in place of dF(q); the next point's records are in flight meanwhile ------------
+  // NP = 4: the outer points first; their F is summed in two halves for the centroid, which comes last
+  R Fa[NP == 4 ? 9 : 1], Fb[NP == 4 ? 9 : 1];
 #pragma unroll
-  for (int sdx = 0; sdx < 5; sdx++) {
-    wave_sync();  // the g records / the previous point have been read
+  for (int k = 0; k < 5; k++) {
+    const int sdx = NP == 4 ? (k < 4 ? k + 1 : 0) : k;
+    R F[3][3];
+    if (k < NP) {
 #pragma unroll
-    for (int j = 0; j < 5; j++) st2[lane + 64 * j] = nx[j];
-    if (sdx < 4) fetch(sdx + 1);
-    wave_sync();
-    const R2* Fr = reinterpret_cast<const R2*>(st + lane * 10);
-    const R2 r0 = Fr[0], r1 = Fr[1], r2 = Fr[2], r3 = Fr[3], r4 = Fr[4];
-    const R F[3][3] = {{r0.x, r0.y, r1.x}, {r1.y, r2.x, r2.y}, {r3.x, r3.y, r4.x}};
+      for (int t = 0; t < 9; t++) F[t / 3][t % 3] = Fn[t];
+      // One point ahead and no further.  Without LDS hand-offs nothing orders these loads, the scheduler hoists those of
+      // every point to the top, and the float form loses its three waves per SIMD: an empty statement that memory
+      // operations do not cross keeps them in program order.
+      if (k + 1 < NP) fetch(k + 1);
+      asm volatile("" ::: "memory");
+    }
+    if constexpr (NP == 4) {
+#pragma unroll
+      for (int t = 0; t < 9; t++) {
+        if (k == 4) F[t / 3][t % 3] = R(0.25) * Fa[t];
+        else if (k == 0) Fa[t] = F[t / 3][t % 3];
+        else if (k == 1) Fa[t] += F[t / 3][t % 3];
+        else if (k == 2) Fb[t] = F[t / 3][t % 3];
+        else Fa[t] += Fb[t] + F[t / 3][t % 3];
+      }
+    }
     R(&dF)[9] = D[sdx];
     R C[3][3], G[3][3];
 #pragma unroll
@@ -2399,8 +2485,7 @@ __global__ __launch_bounds__(128, sizeof(R) == 8 ? 2 : 3) void tangent_apply_aff
       for (int q = 0; q < kNQ; q++) mr += mc.Nq[q][a] * Wm[q][i];
       y[i] += mr;
     }
-    if (CP) {  // parked: row a * 64 + lane (the F records of the last point have been read: the barrier before a = 0)
-      if (a == 0) wave_sync();
+    if (CP) {  // parked: row a * 64 + lane
       R* r = st + 3 * (a * 64 + lane);
       r[0] = y[0];
       r[1] = y[1];
@@ -2449,19 +2534,29 @@ __global__ __launch_bounds__(128, sizeof(R) == 8 ? 2 : 3) void tangent_apply_aff
   }
 }
 
-void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineView& av, const double* Fq16,
+namespace {
+template <bool CP, typename R, int NP>
+void launch_apply(hipStream_t s, const ElemView& m, const R* g, const R* F, const MatfreeCoefT<R>& mc, const R* p, R* ybuf,
+                  const MatfreeCompact& cp, const R* scl) {
+  hipLaunchKernelGGL((tangent_apply_affine_kernel<CP, R, NP>), dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn, g, F,
+                     mc, p, ybuf, cp, scl);
+}
+template <bool CP, typename R>
+void launch_apply_np(hipStream_t s, int np, const ElemView& m, const R* g, const R* F, const MatfreeCoefT<R>& mc, const R* p,
+                     R* ybuf, const MatfreeCompact& cp, const R* scl) {
+  if (np == 4) launch_apply<CP, R, 4>(s, m, g, F, mc, p, ybuf, cp, scl);
+  else launch_apply<CP, R, 5>(s, m, g, F, mc, p, ybuf, cp, scl);
+}
+}  // namespace
+
+void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, int np, const double* gp, const double* Fp,
                                  const MatfreeCoef& mc, const double* p, double* ybuf, const MatfreeCompact* cp) {
-  if (cp)
-    hipLaunchKernelGGL((tangent_apply_affine_kernel<true, double>), dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
-                       av.gvec, Fq16, mc, p, ybuf, *cp, (const double*)nullptr);
-  else
-    hipLaunchKernelGGL((tangent_apply_affine_kernel<false, double>), dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
-                       av.gvec, Fq16, mc, p, ybuf, MatfreeCompact{}, (const double*)nullptr);
+  if (cp) launch_apply_np<true, double>(s, np, m, gp, Fp, mc, p, ybuf, *cp, nullptr);
+  else launch_apply_np<false, double>(s, np, m, gp, Fp, mc, p, ybuf, MatfreeCompact{}, nullptr);
 }
 
 void launch_fine_matfree_apply(hipStream_t s, const ElemView& m, const FineMatfree& f, const float* d, const MatfreeCompact& cp) {
-  hipLaunchKernelGGL((tangent_apply_affine_kernel<true, float>), dim3((m.E + 127) / 128), dim3(128), 0, s, m.E, m.Epad, m.conn,
-                     f.gvec, f.Fq, f.mc, d, f.ybuf, cp, f.scn);
+  launch_apply_np<true, float>(s, f.np, m, f.gvec, f.Fq, f.mc, d, f.ybuf, cp, f.scn);
 }
 
 // q = sum of the node's element rows (+ h^2 rho p on pinned rows, as the "rows out" phase of assemble_affine_kernel adds

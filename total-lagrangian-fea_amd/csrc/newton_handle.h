@@ -223,6 +223,11 @@ struct tlfea_newton_s {
     bool now = false;           // the running / last solve takes the matrix-free product
     int last_mode = 0;           // tlfea_newton_get_spmv_mode
     long gen = 0;                // counts the assemblies that claimed the records (fine smoother: whose records its copies are)
+    // packed lane-major fp64 copies the product reads (matfree_records.h): g of the current affine set-up (gp_ok), F of
+    // assembly rec_gen; a product that finds another assembly fails
+    double *d_gp = nullptr, *d_Fp = nullptr;
+    bool gp_ok = false;
+    long rec_gen = -1;
   } mf;
   // Fine smoother of the p-multigrid cycle from the element records (DESIGN 3g'): float copies of gvec and d_Fq, the
   // normalised scaling, and the choice the last preconditioner set-up took.  The copies belong to assembly `gen`; an
@@ -232,7 +237,7 @@ struct tlfea_newton_s {
     int last = 0;                // tlfea_newton_get_fine_smoother
     long gen = -1;               // mf.gen the float F records were converted at
     bool g_ok = false;           // the float g records are those of the current affine set-up
-    float *d_g32 = nullptr, *d_F32 = nullptr, *d_scn = nullptr;
+    float *d_g32 = nullptr, *d_F32 = nullptr, *d_scn = nullptr;  // g and F packed (matfree_records.h)
     double* d_ss = nullptr;      // sum(sc^2)
     FineMatfree v{};
   } fmf;

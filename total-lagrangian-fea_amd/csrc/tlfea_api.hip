@@ -1065,6 +1065,8 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
   if (s->d_Fq) (void)hipFree(s->d_Fq);
   if (s->d_mbuf) (void)hipFree(s->d_mbuf);
   if (s->mf.d_ybuf) (void)hipFree(s->mf.d_ybuf);
+  if (s->mf.d_gp) (void)hipFree(s->mf.d_gp);
+  if (s->mf.d_Fp) (void)hipFree(s->mf.d_Fp);
   if (s->fmf.d_g32) (void)hipFree(s->fmf.d_g32);
   if (s->fmf.d_F32) (void)hipFree(s->fmf.d_F32);
   if (s->fmf.d_scn) (void)hipFree(s->fmf.d_scn);
@@ -1214,6 +1216,7 @@ static int setup_affine_form(tlfea_newton_t s, bool* affine_out) {
   HIP_TRY(hipMemsetAsync(d_dev, 0, sizeof(double), d->stream));
   av.gvec = s->d_gvec;
   s->fmf.g_ok = false;
+  s->mf.gp_ok = false;
   launch_affine_pre(d->stream, d->view(), av, s->d_gvec, d_dev);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(d->stream));
@@ -2000,6 +2003,15 @@ static bool matfree_compact_env() {
   static const bool on = env_flag("TLFEA_MATFREE_COMPACT", true);
   return on;
 }
+// TLFEA_MATFREE_POINTS: stored points of the packed F records (matfree_records.h) of both real types, 4 = the
+// outer points (the centroid's F is their mean), 5 = all.  Unset: the measured choice per type (DESIGN 3g, 3g').  Read once
+// per process.
+constexpr int kMatfreePoints64 = 5, kMatfreePoints32 = 5;
+static int matfree_points(bool single) {
+  static const int forced = env_int("TLFEA_MATFREE_POINTS", 0);
+  if (forced == 4 || forced == 5) return forced;
+  return single ? kMatfreePoints32 : kMatfreePoints64;
+}
 // the element rows' buffer (233 MB at config C, 75 MB in the compact form) and the compact form's lists: on first use,
 // and outside any stream capture
 static int matfree_ensure_buffer(tlfea_newton_t s) {
@@ -2032,12 +2044,33 @@ static int matfree_ensure_buffer(tlfea_newton_t s) {
   f.compact = true;
   return dmalloc(&f.d_ybuf, (size_t)f.cp_rows * 3);
 }
+// The packed fp64 records the product reads: g once per affine set-up, F once per assembly (mf.gen).  Allocates on first
+// use: before the first product of an assembly and outside any stream capture.
+static int matfree_ensure_records(tlfea_newton_t s) {
+  auto& f = s->mf;
+  tlfea_t10_t d = s->d;
+  const int np = matfree_points(false);
+  if (!f.d_gp) {
+    TRY(dmalloc(&f.d_gp, mfr_g_len((size_t)d->E)));
+    TRY(dmalloc(&f.d_Fp, mfr_F_len((size_t)d->E, np)));
+    f.gp_ok = false;
+    f.rec_gen = -1;
+  }
+  const bool g = !f.gp_ok, F = f.rec_gen != f.gen;
+  if (g || F) launch_matfree_pack<double>(s->stream, d->E, np, F ? s->d_Fq : nullptr, g ? s->d_gvec : nullptr, f.d_Fp, f.d_gp);
+  f.gp_ok = true;
+  f.rec_gen = f.gen;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // q = H p and the p.q slots from the element records (p as pcg_direction_kernel left it)
 static int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part) {
   tlfea_t10_t d = s->d;
   auto& f = s->mf;
   const MatfreeCompact* cp = f.compact ? &f.cp : nullptr;
-  launch_tangent_apply_affine(s->stream, d->view(), s->av, s->d_Fq, f.mc, p, f.d_ybuf, cp);
+  if (!f.gp_ok || f.rec_gen != f.gen)
+    return fail("matrix-free Hessian product: the packed element records are not those of the assembled H");
+  launch_tangent_apply_affine(s->stream, d->view(), matfree_points(false), f.d_gp, f.d_Fp, f.mc, p, f.d_ybuf, cp);
   launch_matfree_gather(s->stream, s->N, d->Epad, d->inc(), f.d_ybuf, p, f.fixed, s->d_nw, f.penalty, q, pq_part, cp);
   return 0;
 }
@@ -2653,16 +2686,17 @@ static int fine_matfree_setup(tlfea_newton_t s) {
   const double m0 = fine_matfree_m0(s);
   if (!f.now) return 0;
   const size_t n = 3 * (size_t)s->N;
+  const int np = matfree_points(true);
   if (!f.d_g32) {
-    TRY(dmalloc(&f.d_g32, (size_t)d->E * 16));
-    TRY(dmalloc(&f.d_F32, (size_t)d->E * 50));
+    TRY(dmalloc(&f.d_g32, mfr_g_len((size_t)d->E)));
+    TRY(dmalloc(&f.d_F32, mfr_F_len((size_t)d->E, np)));
     TRY(dmalloc(&f.d_scn, n));
     TRY(dmalloc(&f.d_ss, 1));
     f.g_ok = false;
   }
-  if (!f.g_ok) launch_to_float(s->stream, (size_t)d->E * 16, s->d_gvec, f.d_g32);
+  // the packed float records (matfree_records.h): g once per affine set-up, F of this assembly
+  launch_matfree_pack<float>(s->stream, d->E, np, s->d_Fq, f.g_ok ? nullptr : s->d_gvec, f.d_F32, f.d_g32);
   f.g_ok = true;
-  launch_to_float(s->stream, (size_t)d->E * 50, s->d_Fq, f.d_F32);
   f.gen = s->mf.gen;
   launch_norm2(s->stream, s->d_sc, nullptr, (int)n, part(s, 5), f.d_ss);
   launch_fine_matfree_scale(s->stream, (int)n, s->d_sc, f.d_ss, 1.0 / (double)n, f.d_scn);
@@ -2676,7 +2710,7 @@ static int fine_matfree_setup(tlfea_newton_t s) {
   }
   v.m0 = m0;
   v.pen_m0 = s->mf.penalty / m0;
-  v.gvec = f.d_g32; v.Fq = f.d_F32; v.scn = f.d_scn; v.ss = f.d_ss;
+  v.gvec = f.d_g32; v.Fq = f.d_F32; v.np = np; v.scn = f.d_scn; v.ss = f.d_ss;
   v.inv_n = 1.0 / (double)n;
   v.ybuf = reinterpret_cast<float*>(s->mf.d_ybuf);  // the CG's product and the smoother never overlap: one buffer
   v.fixed_slot = s->mf.fixed; v.nw = s->d_nw;
@@ -3510,7 +3544,10 @@ static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg,
                        (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
                        // the graphs of the matrix-free fine smoother read no fine copy: one built on demand between two
                        // solves (a read-back, a timing run) must not force a re-capture
-                       (s->fmf.now ? 0L : (long)(size_t)s->d_B8) ^ fine_matfree_key(s), (long)(size_t)s->pmg.vertex.d_B8};
+                       (s->fmf.now ? 0L : (long)(size_t)s->d_B8) ^ fine_matfree_key(s),
+                       // the packed records the captured apply launches read
+                       (long)(size_t)s->pmg.vertex.d_B8 ^ (s->mf.now ? 3 * (long)(size_t)s->mf.d_Fp + 5 * (long)(size_t)s->mf.d_gp : 0L) ^
+                           (s->fmf.now ? 7 * (long)(size_t)s->fmf.d_F32 + 11 * (long)(size_t)s->fmf.d_g32 : 0L)};
   if (s->cg_graph[0] && std::equal(key, key + 6, s->cg_graph_key)) return 0;
   cg_graphs_destroy(s);
   for (int k = 0; k < (s->spmv32_now ? 3 : 2); k++) {
@@ -3674,6 +3711,7 @@ static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
     s->mf.now = matfree_chosen(s);
     s->mf.last_mode = s->mf.now ? 1 : 0;
     if (s->mf.now) TRY(matfree_ensure_buffer(s));
+    if (s->mf.now) TRY(matfree_ensure_records(s));
     const bool fused = fused_csr && !s->mf.now;
     // an outer iteration costs `deg` SpMV launches: test convergence proportionally more often
     int check_every = std::max(1, s->lin.check_every / deg);
@@ -4244,6 +4282,7 @@ extern "C" int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double
   const size_t n = 3 * (size_t)s->N;
   HIP_TRY(hipMemcpy(s->d_zv, x, n * sizeof(double), hipMemcpyHostToDevice));
   TRY(matfree_ensure_buffer(s));
+  TRY(matfree_ensure_records(s));
   TRY(launch_matfree_product(s, s->d_zv, s->d_q, part(s, 2)));
   HIP_TRY(hipGetLastError());
   D2H(y, s->d_q, n);
@@ -4309,6 +4348,38 @@ extern "C" int tlfea_newton_get_matfree_rows(tlfea_newton_t s, long long* rows, 
   if (rows) *rows = s->mf.compact ? s->mf.cp_rows : (long long)kNN * s->d->E;
   if (ratio) *ratio = s->mf.compact ? s->mf.cp_ratio : 1.0;
   return s->mf.compact ? 1 : 0;
+}
+// Test hook: the element records of the matrix-free passes.  which 0 / 1 = the element-major g [E][16] / F [E][5][10] in
+// fp64, 2 / 3 = the packed g / F (matfree_records.h) of the fp64 product (single = 0) or of the float smoother passes.
+// len = values of that buffer; out may be null (length only); points = stored points of the packed F of that type.
+extern "C" int tlfea_newton_get_matfree_records(tlfea_newton_t s, int single, int which, void* out, long long* len,
+                                                int* points) {
+  if (!s || which < 0 || which > 3) return fail("tlfea_newton_get_matfree_records: bad argument");
+  if (!s->d_gvec || !s->d_Fq || !s->mf.valid)
+    return fail("tlfea_newton_get_matfree_records: no element records of an assembled H (affine T10 form only)");
+  const size_t E = (size_t)s->d->E;
+  const int np = matfree_points(single != 0);
+  const void* src = nullptr;
+  size_t n = 0, width = which < 2 || !single ? sizeof(double) : sizeof(float);
+  if (which == 0) src = s->d_gvec, n = E * 16;
+  else if (which == 1) src = s->d_Fq, n = E * 50;
+  else if (single) {
+    if (!fine_matfree_live(s)) return fail("tlfea_newton_get_matfree_records: no float records of the assembled H");
+    src = which == 2 ? s->fmf.d_g32 : s->fmf.d_F32;
+    n = which == 2 ? mfr_g_len(E) : mfr_F_len(E, np);
+  } else {
+    if (!s->mf.d_gp || !s->mf.gp_ok || s->mf.rec_gen != s->mf.gen)
+      return fail("tlfea_newton_get_matfree_records: no packed fp64 records of the assembled H");
+    src = which == 2 ? s->mf.d_gp : s->mf.d_Fp;
+    n = which == 2 ? mfr_g_len(E) : mfr_F_len(E, np);
+  }
+  if (len) *len = (long long)n;
+  if (out) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(out, src, n * width, hipMemcpyDeviceToHost));
+  }
+  if (points) *points = np;
+  return 0;
 }
 
 // ---- modal analysis: the lowest pairs of K phi = omega^2 M phi by LOBPCG on the shifted pencil ------------

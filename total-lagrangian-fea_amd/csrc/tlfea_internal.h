@@ -11,6 +11,7 @@
 #include "row_sweep.h"
 #include "mf_host.h"
 #include "matfree_compact.h"
+#include "matfree_records.h"
 
 namespace tlfea {
 
@@ -178,9 +179,13 @@ struct MatfreeCompact {
   const int* n2r_off;           // [N + 1]
   const int* n2r;               // [rows] compact rows of a node, ascending
 };
-// element rows of H p: ybuf [10][Epad][3], or with cp one row per (wavefront, node): ybuf [rows][3]; Fq16 = the
-// [E][5][10] records H was assembled from
-void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, const AffineView& av, const double* Fq16,
+// Packed copies in R of the records H was assembled from (matfree_records.h): Fq16 [E][5][10] -> Fp with np = 4 | 5
+// stored points, gvec [E][16] -> gp; a null source is skipped
+template <typename R>
+void launch_matfree_pack(hipStream_t s, int E, int np, const double* Fq16, const double* gvec, R* Fp, R* gp);
+// element rows of H p: ybuf [10][Epad][3], or with cp one row per (wavefront, node): ybuf [rows][3]; gp, Fp = the packed
+// records with np = 4 | 5 stored points
+void launch_tangent_apply_affine(hipStream_t s, const ElemView& m, int np, const double* gp, const double* Fp,
                                  const MatfreeCoef& mc, const double* p, double* ybuf, const MatfreeCompact* cp = nullptr);
 // q = node-owner sum of the element rows (+ penalty x nw x p on pinned rows), p.q partials into the kNPart slots
 void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc, const double* ybuf, const double* p,
@@ -197,7 +202,8 @@ void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc,
 struct FineMatfree {
   MatfreeCoefT<float> mc;       // scalars / m0
   double m0, pen_m0;            // m0 | h^2 rho / m0
-  const float *gvec, *Fq;       // float copies of the records
+  const float *gvec, *Fq;       // float copies of the records, packed (matfree_records.h)
+  int np;                       // stored points of Fq: 4 | 5
   const float* scn;             // [3N] float(sc / sigma)
   const double* ss;             // device scalar sum(sc^2)
   double inv_n;                 // 1 / 3N

@@ -529,6 +529,22 @@ class SyncedNewtonSolver:
         form = int(self._lib.tlfea_newton_get_matfree_rows(self._h, C.byref(rows), C.byref(ratio)))
         return form, int(rows.value), float(ratio.value)
 
+    def GetMatfreeRecords(self, which, single=False):
+        """(points, values): element records of the matrix-free passes (test hook).  which 0 / 1: the element-major g
+        [E, 16] / F [E, 5, 10] in float64; 2 / 3: the packed g / F (csrc/matfree_records.h) of the fp64 product, or with
+        single of the float smoother passes, as a flat array.  points = stored points of the packed F of that type"""
+        n, pts = C.c_longlong(), C.c_int()
+        f = self._lib.tlfea_newton_get_matfree_records
+        check(f(self._h, int(bool(single)), int(which), None, C.byref(n), C.byref(pts)))
+        out = np.zeros(n.value, dtype=np.float32 if single and which >= 2 else np.float64)
+        check(f(self._h, int(bool(single)), int(which), out.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(pts)))
+        pts = int(pts.value)
+        if which == 0:
+            out = out.reshape(-1, 16)
+        elif which == 1:
+            out = out.reshape(-1, 5, 10)
+        return pts, out
+
     def NewtonIteration(self):
         ng, it = C.c_double(), C.c_int()
         check(self._lib.tlfea_newton_iteration(self._h, C.byref(ng), C.byref(it)))
