@@ -1,5 +1,5 @@
 // ancf_adjoint_api.hip -- C-ABI (include/tlfea_c.h) of the adjoint sensitivities of the implicit Newton step on ANCF beam
-// and shell objects (DESIGN 3j').  The step itself is adjoint_step_device / adjoint_step_host of tlfea_api.hip; this unit
+// and shell objects (DESIGN 3j').  The step itself is adjoint_step_device / adjoint_step_host of adjoint_api.hip; this unit
 // holds the ANCF kind (AdjointKind, newton_handle.h): the refusals, the element kernel's launches, the stride of the
 // position coefficients and the density rule.
 //

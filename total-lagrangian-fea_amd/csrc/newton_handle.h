@@ -1,8 +1,9 @@
 // newton_handle.h -- the Newton solver object behind tlfea_newton_t with the level types of its preconditioner, and the
-// functions of tlfea_api.hip, direct_api.hip and rccl_api.hip that another unit calls.  Included by the host units that
-// take a tlfea_newton_t apart; private to csrc/.
+// functions of tlfea_api.hip, cg_api.hip, adjoint_api.hip, direct_api.hip and rccl_api.hip that another unit calls.
+// Included by the host units that take a tlfea_newton_t apart; private to csrc/.
 #pragma once
 #include <map>
+#include <tuple>
 
 #include "data_handle.h"
 
@@ -379,12 +380,111 @@ namespace tlfea {
 inline bool dist_on(tlfea_newton_t s) { return s->ar != nullptr || s->halo.on; }
 inline double* part(tlfea_newton_t s, int k) { return s->d_parts + (size_t)k * kNPart; }
 
-// tlfea_api.hip
+// device scratch of one call, released when the call returns
+struct ModalWork {
+  std::vector<void*> owned;
+  ~ModalWork() {
+    for (void* p : owned)
+      if (p) (void)hipFree(p);
+  }
+  int alloc(double** p, size_t n) {
+    TRY(dmalloc(p, n));
+    owned.push_back(*p);
+    return 0;
+  }
+};
+// Warm-start state of the lambda_max estimates (fine level and the coarse levels that exist): save() keeps it and sets the
+// estimates cold, so that what follows depends on no earlier solve; restore() puts it back.  A level built in between did
+// not exist at the save: its vector stays, its estimate goes back to 0.  solve_state: a call that runs solves of its own
+// (modal solve, adjoint step) also keeps the scalars a linear solve leaves for the next one and for the status read-backs.
+struct LamKeep {
+  std::vector<std::pair<double*, size_t>> vecs;  // the kept vectors that exist at the save
+  std::vector<std::pair<double*, double>> lams;  // the estimates
+  double* d_save = nullptr;
+  tlfea_newton_t kept_of = nullptr;              // solve_state: the solver whose scalars `kept` holds
+  std::tuple<double, double, int, int, int, int, double, double, bool, bool> kept;
+  static auto solve_scalars(tlfea_newton_t s) {
+    return std::tie(s->lam_safety, s->pmg.kc_boost, s->last_outer_iters, s->last_deg, s->last_bits, s->mf.last_mode,
+                    s->lin_last_rel, s->lin_worst_rel, s->lin_last_ok, s->lin_all_ok);
+  }
+  int save(tlfea_newton_t s, ModalWork& wk, bool solve_state = false) {
+    size_t total = 0;
+    for (PolyLevel* L : {&s->pmg.vertex, &s->pmg.agg.lvl})
+      if (L->d_eigv) vecs.push_back({L->d_eigv, 3 * (size_t)L->N});
+    vecs.push_back({s->d_eigv, 3 * (size_t)s->N});
+    for (auto& v : vecs) total += v.second;
+    TRY(wk.alloc(&d_save, total));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(copy(true));
+    for (double* p : {&s->lam_max, &s->lam_max_loc, &s->pmg.vertex.lam, &s->pmg.agg.lvl.lam}) {
+      lams.push_back({p, *p});
+      *p = 0.0;
+    }
+    if (solve_state) {
+      kept_of = s;
+      kept = solve_scalars(s);
+    }
+    return 0;
+  }
+  void restore() {
+    for (auto& l : lams) *l.first = l.second;
+    if (kept_of) solve_scalars(kept_of) = kept;
+    (void)copy(false);
+  }
+  hipError_t copy(bool out) {
+    hipError_t e = hipSuccess;
+    double* at = d_save;
+    for (auto& v : vecs) {
+      const hipError_t e1 = hipMemcpy(out ? at : v.first, out ? v.first : at, v.second * sizeof(double), hipMemcpyDeviceToDevice);
+      if (e == hipSuccess) e = e1;
+      at += v.second;
+    }
+    return e;
+  }
+};
+
+// tlfea_api.hip: the partition plumbing
 bool halo_graph_wanted();
 void halo_graph_give_up();  // RCCL cannot be captured / replayed here: eager launches for the rest of the process
+int halo_refresh_f64(tlfea_newton_t s, int level, int D, int dim, double* a, double* b = nullptr, double* c = nullptr);
+int iface_sum(tlfea_newton_t s, double* d_vec, int dim, double* d_extra = nullptr, int n_extra = 0,
+              double* d_extra2 = nullptr);
+int parts_sum(tlfea_newton_t s, double* d_a, double* d_b = nullptr);
+int fetch_scalar(tlfea_newton_t s, const double* d_src, double* out);
 int fetch_scalar2(tlfea_newton_t s, const double* d_src, double* out0, double* out1);
+// tlfea_api.hip: the Newton solver's element stage and the fp64 matrix-free product
+int refuse_empty_rows(tlfea_newton_t s, const char* who);
+int sync_constraints(tlfea_newton_t s);
+bool pinned_on(tlfea_newton_t s);
+bool lincons_on(tlfea_newton_t s);
+void shape_at_rule_points(tlfea_t10_t d, double Nq[kNQ][kNN]);
+bool matfree_eligible(tlfea_newton_t s);
+bool matfree_chosen(tlfea_newton_t s);
+int matfree_ensure_buffer(tlfea_newton_t s);
+int matfree_ensure_records(tlfea_newton_t s);
+int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part);
+int assemble(tlfea_newton_t s, bool fq_fresh = true);
+// tlfea_api.hip: the preconditioners
+int halo_dr(tlfea_newton_t s);
+int cheb_degree_eff(tlfea_newton_t s);
+int cheb_bits_eff(tlfea_newton_t s);
+int precond_eff(tlfea_newton_t s);
+bool blk12_now(tlfea_newton_t s);
+int cheb_upload_coefficients(tlfea_newton_t s);
+int pmg_coarse_degree_eff(tlfea_newton_t s);
+bool pmg_rop_now(tlfea_newton_t s);
+long fine_matfree_key(tlfea_newton_t s);
+bool fine_matfree_live(tlfea_newton_t s);
+int pmg_coefficients(tlfea_newton_t s);
+int precond_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* rz_part, bool init_done);
+int precond_setup(tlfea_newton_t s, const double* d_b, int stage);
+// stages 0 and 1 back to back from the start vector d_b, then the check of the 12 x 12 node blocks; `who` leads the message
+int precond_setup_whole(tlfea_newton_t s, const double* d_b, const char* who);
+// cg_api.hip
+void cg_graphs_destroy(tlfea_newton_t s);
+int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out);
 // The adjoint step of the implicit Newton step (DESIGN 3j, 3j') is one function for every element kind; the kind supplies
-// what differs.  tlfea_api.hip holds the step and the T10 kind, ancf_adjoint_api.hip the ANCF kind.
+// what differs.  adjoint_api.hip holds the step and the T10 kind, ancf_adjoint_api.hip the ANCF kind.
 struct AdjointKind {
   const char* what;                        // the entry point's name in messages
   int stride;                              // the position coefficients are every stride-th coefficient vector (T10: 1, ANCF: 4)

@@ -189,7 +189,7 @@ __device__ __forceinline__ double ld_stream(const HT* p) {
 // FUSED: p_new = z + beta p_old is formed on the fly (small meshes: one launch fewer per iteration).
 // !FUSED: p was written by pcg_direction_kernel; only p is gathered (large meshes: half the gather traffic).
 // HT: double = H itself; float = its single-precision copy (same layout), the CG's working operator between two
-// fp64 residual replacements (tlfea_api.hip, pcg()): products and sums stay fp64.
+// fp64 residual replacements (cg_api.hip, pcg()): products and sums stay fp64.
 template <typename HT, bool FUSED, bool NT, int LANES>
 __global__ __launch_bounds__(1024) void spmv_dir_dot_kernel(int N, Incidence inc, const HT* __restrict__ Hval,
                                                            const double* __restrict__ z,

@@ -1,6 +1,6 @@
 // tlfea_api.hip -- C-ABI (include/tlfea_c.h) over the gfx950 kernels: buffer ownership, the host
 // side of the sparsity analysis, and the ALM/Newton control flow of the reference
-// (SyncedNewton.cu:909-1146) with the device PCG in place of cuDSS.
+// (SyncedNewton.cu:909-1146) with the preconditioners of the device PCG (cg_api.hip) that stands in place of cuDSS.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -17,7 +17,6 @@
 #include "pmg_coef.h"
 #include "rowgroup_host.h"
 #include "vbd_host.h"
-#include "modal_host.h"
 
 using namespace tlfea;
 
@@ -1045,7 +1044,6 @@ extern "C" int tlfea_newton_create(tlfea_t10_t data, int n_constraints, tlfea_ne
   return tlfea_newton_setup(s);
 }
 
-static void cg_graphs_destroy(tlfea_newton_t s);
 static void halo_free_plans(tlfea_newton_s::HaloLevel& L);
 extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
   if (!s) return 0;
@@ -1175,13 +1173,6 @@ static int ensure_fq(tlfea_newton_t s) {
   if (s->d_Fq) return 0;
   tlfea_t10_t d = s->d;
   return dmalloc(&s->d_Fq, std::max((size_t)d->Epad * 50, (size_t)d->E * d->Q * 9));
-}
-static void free_ints(int** p, int n) {
-  for (int k = 0; k < n; k++)
-    if (p[k]) {
-      (void)hipFree(p[k]);
-      p[k] = nullptr;
-    }
 }
 // Affine form: every element straight-sided (checked on the device against the stored grad N / det J) and the rule the
 // 5-point Keast rule (L = 1/4 at one point, one vertex at 1/2 and three at 1/6 at the others).
@@ -1370,7 +1361,7 @@ extern "C" int tlfea_newton_analyze_hessian_sparsity(tlfea_newton_t s) {
 // goes through -- pcg() (the direct solve included) and stage 0 of precond_setup (solves, the modal iteration, the
 // preconditioner test hooks) -- and, so that a step does not launch its gradient and assembly first, at the top of the
 // entry points that begin a step.
-static int refuse_empty_rows(tlfea_newton_t s, const char* who) {
+int tlfea::refuse_empty_rows(tlfea_newton_t s, const char* who) {
   if (s->iso_count == 0) return 0;
   return fail(std::string(who) + ": node " + std::to_string(s->iso_first) + " belongs to no element (" +
               std::to_string(s->iso_count) + " such node" + (s->iso_count > 1 ? "s" : "") +
@@ -1490,13 +1481,12 @@ bool tlfea::halo_graph_wanted() {
 void tlfea::halo_graph_give_up() { g_rccl_graph_ok = false; }
 template <typename T>
 static int upload_vec(T** dst, const std::vector<T>& v);
-static int precond_eff(tlfea_newton_t s);
 static int pmg_ks(tlfea_newton_t s);
 // Ghost layers on which the CG residual must be exact when the preconditioner starts: the V-cycle's ks pre-smoothing
 // passes give up one layer each and must leave layer 1 (restriction) and layer ks - 1 (the post-smoother's own-row
 // operands); the polynomial fallback refreshes its direction before every step instead.  The direction z is refreshed
 // one layer deeper (the CG's SpMV gives up one).
-static int halo_dr(tlfea_newton_t s) {
+int tlfea::halo_dr(tlfea_newton_t s) {
   if (precond_eff(s) != 2) return 0;
   const int ks = pmg_ks(s);
   return std::max(ks + 1, 2 * ks - 1);
@@ -1680,7 +1670,7 @@ static int halo_reserve(tlfea_newton_t s, size_t bs, size_t br) {
   return 0;
 }
 // ghost layers <= D of up to three fp64 / fp32 nodal fields (dim values per node) take their owners' values
-static int halo_refresh_f64(tlfea_newton_t s, int level, int D, int dim, double* a, double* b = nullptr, double* c = nullptr) {
+int tlfea::halo_refresh_f64(tlfea_newton_t s, int level, int D, int dim, double* a, double* b, double* c) {
   if (!s->halo.on || s->halo.peers.empty()) return 0;
   tlfea_newton_s::HaloPlan* pl = nullptr;
   TRY(halo_plan(s, level, D, &pl));
@@ -1760,8 +1750,8 @@ static int allreduce_host(tlfea_newton_t s, double* d_buf, double* h, size_t n) 
 // vectors, 9 for diagonal blocks), optionally fused with `n_extra` reduction slots (one collective).
 static int iface_sum_lvl(tlfea_newton_t s, const LevelIface& I, double* d_vec, int dim, double* d_extra = nullptr,
                          int n_extra = 0, double* d_extra2 = nullptr);
-static int iface_sum(tlfea_newton_t s, double* d_vec, int dim, double* d_extra = nullptr, int n_extra = 0,
-                     double* d_extra2 = nullptr) {
+int tlfea::iface_sum(tlfea_newton_t s, double* d_vec, int dim, double* d_extra, int n_extra,
+                     double* d_extra2) {
   return iface_sum_lvl(s, s->iface(), d_vec, dim, d_extra, n_extra, d_extra2);
 }
 // the same for any level of the multigrid hierarchy (its own boundary node / slot lists)
@@ -1793,7 +1783,7 @@ static int iface_sum_lvl(tlfea_newton_t s, const LevelIface& I, double* d_vec, i
   return 0;
 }
 // sum over ranks of reduction slots only (element-wise), so every rank re-adds identical partials
-static int parts_sum(tlfea_newton_t s, double* d_a, double* d_b = nullptr) {
+int tlfea::parts_sum(tlfea_newton_t s, double* d_a, double* d_b) {
   if (!dist_on(s)) return 0;
   double* buf = s->halo.on ? s->halo.d_red : s->d_ibuf;
   HIP_TRY(hipMemcpyAsync(buf, d_a, (size_t)kNPart * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
@@ -1815,7 +1805,7 @@ static int device_sumsq_async(tlfea_newton_t s, const double* d_vec, const doubl
   return 0;
 }
 // one device scalar to the host through the pinned staging word
-static int fetch_scalar(tlfea_newton_t s, const double* d_src, double* out) {
+int tlfea::fetch_scalar(tlfea_newton_t s, const double* d_src, double* out) {
   HIP_TRY(hipMemcpyAsync(s->h_pin, d_src, sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   *out = s->h_pin[0];
@@ -1842,7 +1832,7 @@ extern "C" int tlfea_newton_l2_norm(tlfea_newton_t s, const double* d_vec, int n
 
 // UpdateNodalFixed may have changed the size of the fixed set since the solver was built: the multipliers follow it
 // (restarting from zero) before anything indexes them with the new constraint ids.
-static int sync_constraints(tlfea_newton_t s) {
+int tlfea::sync_constraints(tlfea_newton_t s) {
   tlfea_t10_t d = s->d;
   if (!s->cons_enabled || d->n_constraint == s->n_constraints) return 0;
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1870,10 +1860,10 @@ static int sync_constraints(tlfea_newton_t s) {
   s->n_constraints_global = (int)(cnt + 0.5);
   return 0;
 }
-static bool pinned_on(tlfea_newton_t s) {
+bool tlfea::pinned_on(tlfea_newton_t s) {
   return s->n_constraints > 0 && s->d->is_constraints_setup && s->d->cons_mode == 1;
 }
-static bool lincons_on(tlfea_newton_t s) { return s->n_constraints > 0 && s->d->cons_mode == 2 && s->d->n_constraint > 0; }
+bool tlfea::lincons_on(tlfea_newton_t s) { return s->n_constraints > 0 && s->d->cons_mode == 2 && s->d->n_constraint > 0; }
 
 // the fused tangent + assembly kernel covers T10 with St.Venant-Kirchhoff (+ Kelvin-Voigt); Mooney-Rivlin and the
 // ANCF kinds keep the element-block buffer (tangent_blocks + assemble_rows)
@@ -1970,7 +1960,7 @@ static int fill_mass_term(tlfea_newton_t s, MassTerm& mt) {
   return 0;
 }
 // shape functions at the rule's points (the rule of the mass matrix, FEAT10Data.cu:206-278)
-static void shape_at_rule_points(tlfea_t10_t d, double Nq[kNQ][kNN]) {
+void tlfea::shape_at_rule_points(tlfea_t10_t d, double Nq[kNQ][kNN]) {
   const int edges[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};  // FEAT10Data.cu:143
   for (int q = 0; q < kNQ; q++) {
     const double L[4] = {1.0 - d->h_q[0][q] - d->h_q[1][q] - d->h_q[2][q], d->h_q[0][q], d->h_q[1][q], d->h_q[2][q]};
@@ -1990,10 +1980,10 @@ static int matfree_env() {
 // (DESIGN 3g): a tie at 30 k nodes, -12 % per Newton iteration at 172 k, -10 % at 402 k, -13 % at 1.34 M; between 30 k and
 // 172 k nothing was measured, so the pick starts just below the smallest size measured to win.
 constexpr int kMatfreeMinRows = 150000;
-static bool matfree_eligible(tlfea_newton_t s) {
+bool tlfea::matfree_eligible(tlfea_newton_t s) {
   return affine_now(s) && s->mf.valid && !dist_on(s) && !lincons_on(s) && s->d->obs.n == 0 && !s->d->d_emat && !s->spmv32_now;
 }
-static bool matfree_chosen(tlfea_newton_t s) {
+bool tlfea::matfree_chosen(tlfea_newton_t s) {
   if (matfree_env() == 0 || !matfree_eligible(s)) return false;
   return matfree_env() == 1 || s->N >= kMatfreeMinRows;
 }
@@ -2014,7 +2004,7 @@ static int matfree_points(bool single) {
 }
 // the element rows' buffer (233 MB at config C, 75 MB in the compact form) and the compact form's lists: on first use,
 // and outside any stream capture
-static int matfree_ensure_buffer(tlfea_newton_t s) {
+int tlfea::matfree_ensure_buffer(tlfea_newton_t s) {
   auto& f = s->mf;
   if (f.d_ybuf) return 0;
   tlfea_t10_t d = s->d;
@@ -2046,7 +2036,7 @@ static int matfree_ensure_buffer(tlfea_newton_t s) {
 }
 // The packed fp64 records the product reads: g once per affine set-up, F once per assembly (mf.gen).  Allocates on first
 // use: before the first product of an assembly and outside any stream capture.
-static int matfree_ensure_records(tlfea_newton_t s) {
+int tlfea::matfree_ensure_records(tlfea_newton_t s) {
   auto& f = s->mf;
   tlfea_t10_t d = s->d;
   const int np = matfree_points(false);
@@ -2064,7 +2054,7 @@ static int matfree_ensure_records(tlfea_newton_t s) {
   return 0;
 }
 // q = H p and the p.q slots from the element records (p as pcg_direction_kernel left it)
-static int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part) {
+int tlfea::launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part) {
   tlfea_t10_t d = s->d;
   auto& f = s->mf;
   const MatfreeCompact* cp = f.compact ? &f.cp : nullptr;
@@ -2186,7 +2176,7 @@ static int eval_gradient(tlfea_newton_t s, double* norm_g) {
 
 // fq_fresh: the per-point F buffer holds the F of the CURRENT coordinates (true right after eval_gradient, which is
 // how the Newton loop calls it); a stand-alone assembly refreshes it with a residual launch first
-static int assemble(tlfea_newton_t s, bool fq_fresh = true) {
+int tlfea::assemble(tlfea_newton_t s, bool fq_fresh) {
   tlfea_t10_t d = s->d;
   const bool after_grad = fq_fresh;  // the obstacle buffers hold the current coordinates' blocks
   {
@@ -2241,7 +2231,7 @@ static bool blk12_on(tlfea_newton_t s);
 // auto: T10 (the polynomial alone, where no p-multigrid hierarchy exists) degree 24 on [lmax/1600, lmax]; the ANCF kinds
 // degree 16 on [lmax/200, lmax] with the 12 x 12 node-block scaling, [lmax/400, lmax] without (config D sweep,
 // profiles/r03_sweep_ancf_block12.txt: 140.7 ms at 24/1600 -> 82.8 at 16/400 -> 73.8 with the node blocks)
-static int cheb_degree_eff(tlfea_newton_t s) {
+int tlfea::cheb_degree_eff(tlfea_newton_t s) {
   if (s->lin.cheb_degree > 0) return s->lin.cheb_degree;
   return s->d->kind != kT10 ? 16 : 24;
 }
@@ -2254,14 +2244,13 @@ static double cheb_kappa_eff(tlfea_newton_t s) {
 
 // storage precision of the matrix streamed by the Chebyshev steps: 0 = auto = fp16 (scaled copy, see
 // solver_kernels.hip); 64 streams H itself
-static int cheb_bits_eff(tlfea_newton_t s) {
+int tlfea::cheb_bits_eff(tlfea_newton_t s) {
   if (cheb_degree_eff(s) <= 1) return 64;
   return s->lin.cheb_bits == 0 ? 16 : s->lin.cheb_bits;
 }
 
 // storage of the FINE level's streamed copy inside the p-multigrid cycle: TLFEA_FINE_BITS=8 (experiment) stores it as
 // fp8 e4m3 -- 13 instead of 22 bytes per block in the cycle's four fine passes; the coarser levels keep fp16
-static int precond_eff(tlfea_newton_t s);
 static int fine_bits(tlfea_newton_t s) {
   static const int forced = env_int("TLFEA_FINE_BITS", 0);
   const int bits = cheb_bits_eff(s);
@@ -2300,7 +2289,6 @@ static bool blk12_on(tlfea_newton_t s) {
   s->blk12 = ok ? 1 : 0;
   return ok;
 }
-static bool blk12_now(tlfea_newton_t s);
 
 // storage of the fine level's low-precision copy, (re)allocated where the width changes; a solver that never converts
 // never allocates it (0.75 GB at config C)
@@ -2373,7 +2361,7 @@ static int lp_build(tlfea_newton_t s, bool defer) {
   return 0;
 }
 
-static bool blk12_now(tlfea_newton_t s) {
+bool tlfea::blk12_now(tlfea_newton_t s) {
   return blk12_on(s) && precond_eff(s) != 2 && cheb_degree_eff(s) > 1 && cheb_bits_eff(s) != 64 && s->lin.method == 0;
 }
 
@@ -2463,7 +2451,7 @@ static int estimate_lam_max(tlfea_newton_t s, const double* d_b) {
 
 // Chebyshev coefficients of this solve to the device: coef[0] = 1/theta, step k reads coef[2k], coef[2k+1].  They live
 // in device memory (not kernel arguments) so that the captured launch sequence stays valid when lambda_max moves.
-static int cheb_upload_coefficients(tlfea_newton_t s) {
+int tlfea::cheb_upload_coefficients(tlfea_newton_t s) {
   const int deg = cheb_degree_eff(s);
   double* h = s->h_pin + 8;
   cheb_pairs(s->lam_safety * s->lam_max, cheb_kappa_eff(s), deg, h);
@@ -2557,7 +2545,7 @@ static double pmg_kappa_coarse(int kc) {
   static const double forced = env_double("TLFEA_PMG_KAPPA_C", 0.0);
   return forced > 1.0 ? forced : 1.5 * kc * kc;
 }
-static int pmg_coarse_degree_eff(tlfea_newton_t s) {
+int tlfea::pmg_coarse_degree_eff(tlfea_newton_t s) {
   static const int forced = env_int("TLFEA_PMG_KC", 0);
   const int n_vertex = (dist_on(s) && s->pmg.Nc_glob > 0) ? s->pmg.Nc_glob : s->pmg.vertex.N;
   const int base = pmg_poly_degree(n_vertex, forced, kPmgMaxCoarseDeg);
@@ -2622,7 +2610,7 @@ static bool pmg_rop_on(tlfea_newton_t s) {
   const int fb = fine_bits(s);
   return fb == 16 || fb == 32;
 }
-static bool pmg_rop_now(tlfea_newton_t s) { return pmg_rop_on(s) && s->pmg.rop.built; }
+bool tlfea::pmg_rop_now(tlfea_newton_t s) { return pmg_rop_on(s) && s->pmg.rop.built; }
 // How R is built from H where the fine smoother is matrix-free (DESIGN 3g', 8b): TLFEA_ROP_BUILD=stream (default) reads each
 // child's row of H whole through an LDS image of the R row, gather walks the contribution lists.  TLFEA_ROP_STREAM_MAX
 // lowers the image's capacity in blocks (tests: rows on both kernels in one build).  Both read once per process.
@@ -2718,7 +2706,7 @@ static int fine_matfree_setup(tlfea_newton_t s) {
   return 0;
 }
 // the scalars the pair's kernels take BY VALUE (a captured graph holds them): part of the CG graphs' key
-static long fine_matfree_key(tlfea_newton_t s) {
+long tlfea::fine_matfree_key(tlfea_newton_t s) {
   if (!s->fmf.now) return 0;
   const FineMatfree& v = s->fmf.v;
   const double dv[3] = {v.m0, v.pen_m0, v.inv_n};
@@ -2732,7 +2720,7 @@ static long fine_matfree_key(tlfea_newton_t s) {
   return (long)h;
 }
 // this pass may read the float records: chosen at the set-up, and the records are still those of that assembly
-static bool fine_matfree_live(tlfea_newton_t s) { return s->fmf.now && s->mf.valid && s->fmf.gen == s->mf.gen; }
+bool tlfea::fine_matfree_live(tlfea_newton_t s) { return s->fmf.now && s->mf.valid && s->fmf.gen == s->mf.gen; }
 // Third level (rigid-body-mode aggregates below the vertex level): opt-in with TLFEA_PMG_LEVELS=3.  Measured at config C
 // it makes a CG iteration 10-12 % cheaper (4 vertex-level steps + a degree-20..32 polynomial on ~20 000 level-3 nodes
 // instead of 31 vertex-level steps) and costs 10-17 % more iterations (33-35 instead of 30, whatever the accuracy of
@@ -2772,7 +2760,7 @@ static int upload_vec(T** dst, const std::vector<T>& v) {
 
 // 1 = Chebyshev polynomial, 2 = p-multigrid.  Auto: p-multigrid wherever it exists (T10, one GPU, low-precision path,
 // no general linear constraint rows -- they couple coefficients the vertex hierarchy does not know about).
-static int precond_eff(tlfea_newton_t s) {
+int tlfea::precond_eff(tlfea_newton_t s) {
   if (s->lin.precond == 1) return 1;
   tlfea_t10_t d = s->d;
   // T10: quadratic tets -> vertex mesh.  ANCF kinds: all coefficients -> position coefficients (pmg_build_ancf), an
@@ -3207,7 +3195,7 @@ static int level_lam_max(tlfea_newton_t s, PolyLevel& L, int rows, const double*
 }
 
 // lambda_max of the coarse levels, then the cycle's coefficient table (pmg_coef.h) to the device
-static int pmg_coefficients(tlfea_newton_t s) {
+int tlfea::pmg_coefficients(tlfea_newton_t s) {
   auto& m = s->pmg;
   const LevelIface ic = m.iface();
   // overlapping partition: the vertex level's iteration lives on the owned rows
@@ -3384,7 +3372,7 @@ static int pmg_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* r
 // 3 x 3 diagonal blocks.  The one function behind a CG iteration of pcg(), the modal solve and the test hook
 // tlfea_newton_apply_preconditioner; the last fine step leaves the r.z slots in rz_part.  init_done: the previous CG
 // iteration's update kernel already wrote the fp32 start vectors.
-static int precond_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* rz_part, bool init_done) {
+int tlfea::precond_apply(tlfea_newton_t s, const double* d_r, double* d_z, double* rz_part, bool init_done) {
   if (cheb_degree_eff(s) <= 1) {
     launch_apply_dinv(s->stream, s->N, s->d_Dinv, d_r, d_z);
     return 0;
@@ -3399,186 +3387,11 @@ static int precond_apply(tlfea_newton_t s, const double* d_r, double* d_z, doubl
   return cheb_apply(s, d_r, d_z, rz_part, init_done);
 }
 
-// Enqueue CG iteration `it` (parity cur = it & 1 selects the r.z slot pair and, in the fused variant, which of the
-// two direction buffers is read).  Everything an iteration needs from the previous one (alpha, beta, Chebyshev
-// coefficients) is read from device memory, so iterations >= 1 of either parity are the SAME launch sequence.
-// Overlapping partition: ghost layers <= Dr of the CG residual take their owners' values, and the next polynomial's fp32
-// start vectors of those rows are formed from them (the owned rows' came out of the update kernel).
-static int halo_residual_to_ghosts(tlfea_newton_t s) {
-  const int N = s->N, Dr = halo_dr(s);
-  const size_t n = 3 * (size_t)N;
-  if (Dr < 1) return 0;
-  TRY(halo_refresh_f64(s, 0, Dr, 3, s->d_r));
-  float* f = s->d_f32;
-  launch_cheb32_init(s->stream, s->halo.rows(Dr), f + 6 * n, s->d_r, s->d_sc, precond_eff(s) == 2 ? s->pmg.d_coef : s->d_coef,
-                     f, f + 2 * n, f + 4 * n, s->halo.rows(0));
-  return 0;
-}
-static int enqueue_residual_replacement(tlfea_newton_t s, double* d_x);
-static int enqueue_cg_iteration_impl(tlfea_newton_t s, double* d_x, bool first, int cur, bool fused, int deg, bool replace);
-static int enqueue_cg_iteration(tlfea_newton_t s, double* d_x, bool first, int cur, bool fused, int deg,
-                                bool replace = false) {
-  s->halo.in_cg = true;
-  const int rc = enqueue_cg_iteration_impl(s, d_x, first, cur, fused, deg, replace);
-  s->halo.in_cg = false;
-  return rc;
-}
-static int enqueue_cg_iteration_impl(tlfea_newton_t s, double* d_x, bool first, int cur, bool fused, int deg, bool replace) {
-  tlfea_t10_t d = s->d;
-  const int N = s->N;
-  const double* w = s->d_w;
-  double* pq_part = part(s, 2);
-  double *p_old = s->d_p, *p_new = s->d_p2;
-  if (fused && cur) std::swap(p_old, p_new);
-  // single-GPU fp32 polynomial: its start vectors come out of the previous iteration's update kernel
-  const bool b12 = blk12_now(s);
-  const bool fuse_init = deg > 1 && cheb_bits_eff(s) != 64 && !s->ar && !b12;
-  // Overlapping partition: the CG recurrences (x, r, p, q) live on the OWNED rows.  Two neighbour exchanges per iteration on
-  // this level: layer 1 of the direction z (the SpMV's ghost columns) and layers <= Dr of the updated residual (what the
-  // next V-cycle starts from).  The residual of a ghost is its OWNER's, bit for bit: recomputing it redundantly (q = H p on
-  // ghost rows) differs by round-off, each rank would precondition its own version of r, and at ||r|| ~ 1e-12 ||b|| that
-  // inconsistency stalled the iteration (two config-C slabs: floor 1.6e-12).  Dot products weigh owned DOFs (wown) and
-  // are summed over ranks: r.z after the preconditioner, p.q after the SpMV; the r.r slots only when the host tests
-  // convergence (pcg()).
-  const bool hal = s->halo.on;
-  const int Dr = hal ? halo_dr(s) : 0;
-  const int Nr = hal ? s->halo.rows(0) : N, Np = hal ? s->halo.rows(1) : N;
-  const double* wown = hal ? s->d_w : nullptr;
-  if (deg > 1) {
-    // polynomial preconditioner: z = Cheb(r), r.z slots -> part(cur)   (deg-1 SpMV launches, no reductions)
-    TRY(precond_apply(s, s->d_r, s->d_zv, part(s, cur), fuse_init && !first));
-    if ((s->ar && !(s->d_own && cheb_bits_eff(s) != 64)) || hal) TRY(parts_sum(s, part(s, cur)));
-    if (hal) TRY(halo_refresh_f64(s, 0, 1, 3, s->d_zv));
-  }
-  if (s->profiling) (void)hipEventRecord(s->ev[4], s->stream);
-  // beta = rz(cur)/rz(1-cur); p = z + beta p; q = H p; partials of p.q
-  if (fused) {
-    if (s->spmv32_now)
-      launch_spmv_dir_dot_f32(s->stream, N, d->inc(), s->d_H32, s->d_zv, p_old, first, part(s, 1 - cur), part(s, cur), p_new,
-                              s->d_q, pq_part, true);
-    else
-      launch_spmv_dir_dot(s->stream, N, d->inc(), s->d_H, s->d_zv, p_old, first, part(s, 1 - cur), part(s, cur), p_new,
-                          s->d_q, pq_part, true, s->spmv_nt);
-  } else {
-    launch_pcg_direction(s->stream, 3 * Np, s->d_zv, first, part(s, 1 - cur), part(s, cur), p_old);
-    if (s->mf.now)
-      TRY(launch_matfree_product(s, p_old, s->d_q, pq_part));
-    else if (s->spmv32_now)
-      launch_spmv_dir_dot_f32(s->stream, Nr, d->inc(), s->d_H32, s->d_zv, p_old, first, part(s, 1 - cur), part(s, cur), p_old,
-                              s->d_q, pq_part, false, wown);
-    else
-      launch_spmv_dir_dot(s->stream, Nr, d->inc(), s->d_H, s->d_zv, p_old, first, part(s, 1 - cur), part(s, cur), p_old,
-                          s->d_q, pq_part, false, s->spmv_nt, wown);
-  }
-  if (s->profiling) {
-    (void)hipEventRecord(s->ev[5], s->stream);
-    (void)hipEventSynchronize(s->ev[5]);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, s->ev[4], s->ev[5]);
-    s->stage_ms[6] += ms;
-    s->stage_n[6] += deg;  // SpMV launches of this iteration (Chebyshev steps included)
-  }
-  if (s->ar) TRY(iface_sum(s, s->d_q, 3, pq_part, kNPart));  // boundary rows of q + p.q slots, one collective
-  if (hal) TRY(parts_sum(s, pq_part));
-  if (deg > 1) {
-    // alpha = rz(cur)/pq; x += alpha p; r -= alpha q; r.r slots
-    if (fuse_init) {
-      const size_t n = 3 * (size_t)N;
-      float* f = s->d_f32;  // d, z^, res^ start buffers of cheb_apply and (SDS)^-1
-      launch_pcg_update_init32(s->stream, Nr, fused ? p_new : p_old, s->d_q, part(s, cur), pq_part, d_x, s->d_r,
-                               part(s, 3), s->d_scal + 3, f + 6 * n, s->d_sc,
-                               precond_eff(s) == 2 ? s->pmg.d_coef : s->d_coef, f, f + 2 * n, f + 4 * n, wown);
-      if (hal && !replace) TRY(halo_residual_to_ghosts(s));
-    } else {
-      launch_pcg_update_noz(s->stream, N, w, fused ? p_new : p_old, s->d_q, part(s, cur), pq_part, d_x, s->d_r,
-                            part(s, 3), s->d_scal + 3);
-    }
-    if (s->ar) TRY(parts_sum(s, part(s, 3)));
-    if (replace) TRY(enqueue_residual_replacement(s, d_x));
-  } else {
-    // ... and z = Dinv r with the new r.z slots into part(1-cur)
-    launch_pcg_update(s->stream, N, s->d_Dinv, w, fused ? p_new : p_old, s->d_q, part(s, cur), pq_part, d_x, s->d_r,
-                      s->d_zv, part(s, 1 - cur), part(s, 3));
-    if (s->ar) TRY(parts_sum(s, part(s, 1 - cur), part(s, 3)));  // r.z and r.r slots, one collective
-  }
-  if (hal) s->halo.n_cg_iters++;
-  return 0;
-}
-
-// r = b - H x in fp64 on H itself, the r.r slots of the TRUE residual and the next polynomial's start vectors (mixed-
-// precision iteration only: s->spmv32_now).  q is free between the update and the next iteration's SpMV.
-static int enqueue_residual_replacement(tlfea_newton_t s, double* d_x) {
-  tlfea_t10_t d = s->d;
-  const int N = s->N;
-  const size_t n = 3 * (size_t)N;
-  // un-fused form: reads x only; its p.q slots go to the scratch slot array of the norms
-  // overlapping partition: x lives on the owned rows; layer 1 comes from its owners for the product
-  const int Nr = s->halo.on ? s->halo.rows(0) : N;
-  if (s->halo.on) TRY(halo_refresh_f64(s, 0, 1, 3, d_x));
-  launch_spmv_dir_dot(s->stream, Nr, d->inc(), s->d_H, d_x, d_x, 1, part(s, 0), part(s, 1), s->d_cd, s->d_q, part(s, 5), false,
-                      s->spmv_nt);
-  float* f = s->d_f32;
-  launch_residual_replace_init32(s->stream, Nr, s->cur_b, s->d_q, s->d_r, part(s, 3), f + 6 * n, s->d_sc,
-                                 precond_eff(s) == 2 ? s->pmg.d_coef : s->d_coef, f, f + 2 * n, f + 4 * n,
-                                 s->halo.on ? s->d_w : nullptr);
-  if (s->halo.on) TRY(halo_residual_to_ghosts(s));
-  return 0;
-}
-
-static void cg_graphs_destroy(tlfea_newton_t s) {
-  for (auto& g : s->cg_graph)
-    if (g) {
-      (void)hipGraphExecDestroy(g);
-      g = nullptr;
-    }
-}
-
-// The launch sequences (even / odd iteration, odd iteration followed by a residual replacement) captured once as
-// hipGraphs and replayed: one host call per CG iteration instead of deg+2 launches.  On small meshes the kernels last
-// 5-10 us and the launch rate of the host is what an iteration costs otherwise.  Single-GPU path only (the multi-GPU
-// path calls back into the host between kernels).
-static int cg_graphs_prepare(tlfea_newton_t s, double* d_x, bool fused, int deg, int bits) {
-  const long key[6] = {deg + 1000 * precond_eff(s) + 100000L * (s->pmg.ok ? pmg_coarse_degree_eff(s) : 0),
-                       bits + (s->spmv32_now ? 100000L : 0) + (s->mf.now ? 200000L : 0) + (s->mf.now && s->mf.compact ? 800000L : 0) +
-                           (pmg_rop_now(s) ? 400000L : 0) + (fine_matfree_live(s) ? 1600000L : 0),
-                       (fused ? 1 : 0) + 2 * (long)(size_t)s->cur_b, (long)(size_t)d_x,
-                       // the graphs of the matrix-free fine smoother read no fine copy: one built on demand between two
-                       // solves (a read-back, a timing run) must not force a re-capture
-                       (s->fmf.now ? 0L : (long)(size_t)s->d_B8) ^ fine_matfree_key(s),
-                       // the packed records the captured apply launches read
-                       (long)(size_t)s->pmg.vertex.d_B8 ^ (s->mf.now ? 3 * (long)(size_t)s->mf.d_Fp + 5 * (long)(size_t)s->mf.d_gp : 0L) ^
-                           (s->fmf.now ? 7 * (long)(size_t)s->fmf.d_F32 + 11 * (long)(size_t)s->fmf.d_g32 : 0L)};
-  if (s->cg_graph[0] && std::equal(key, key + 6, s->cg_graph_key)) return 0;
-  cg_graphs_destroy(s);
-  for (int k = 0; k < (s->spmv32_now ? 3 : 2); k++) {
-    hipGraph_t g = nullptr;
-    auto& hh = s->halo;
-    const double c0[5] = {(double)hh.n_exch, (double)hh.n_allred, hh.bytes_exch, hh.bytes_allred, (double)hh.n_cg_iters};
-    HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_cg_iteration(s, d_x, false, k & 1 ? 1 : (k == 2 ? 1 : 0), fused, deg, k == 2);
-    const hipError_t e = hipStreamEndCapture(s->stream, &g);
-    {  // nothing ran: the counters go back, the cost of one replay is kept
-      const double c1[5] = {(double)hh.n_exch, (double)hh.n_allred, hh.bytes_exch, hh.bytes_allred, (double)hh.n_cg_iters};
-      for (int t = 0; t < 5; t++) hh.graph_cost[k][t] = c1[t] - c0[t];
-      hh.n_exch_cg -= (long)(c1[0] - c0[0]);
-      hh.n_allred_cg -= (long)(c1[1] - c0[1]);
-      hh.n_exch = (long)c0[0]; hh.n_allred = (long)c0[1]; hh.bytes_exch = c0[2]; hh.bytes_allred = c0[3]; hh.n_cg_iters = (long)c0[4];
-      s->n_collectives -= (long)(c1[1] - c0[1]);
-    }
-    if (rc) return rc;
-    HIP_TRY(e);
-    HIP_TRY(hipGraphInstantiate(&s->cg_graph[k], g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
-  }
-  std::copy(key, key + 6, s->cg_graph_key);
-  return 0;
-}
-
 // What the preconditioner needs from the current H, in the launches and the order pcg() has always issued them.
 // Stage 0, before the start residual: the block diagonal, its inverse and the scaled low-precision copy.  Stage 1, after
 // it (d_b: start vector of a cold lambda_max estimate): lambda_max, the polynomial's coefficients and the p-multigrid
 // levels.  pcg() runs its start residual between the two; the modal solve calls them back to back.
-static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
+int tlfea::precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
   tlfea_t10_t d = s->d;
   const int N = s->N;
   if (stage == 0) {
@@ -3621,280 +3434,16 @@ static int precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
   return 0;
 }
 
-// Test hook tlfea_newton_cg_trace: record `rec` (0: after launch_pcg_init, j: after iteration j - 1) of the running solve.
-// Drains the stream and copies x, r, z, the direction of this iteration (d_p_now: whichever of d_p / d_p2 holds it; null
-// before the first iteration) and q, the device's own totals of the slot arrays r.z (both parities), p.q and r.r, and the
-// raw slot arrays (r.z even, r.z odd, p.q, r.r, b.b).
-constexpr int kCgTraceForm = 24;
-static int cg_trace_record(tlfea_newton_t s, int rec, const double* d_x, const double* d_p_now) {
-  auto& tr = *s->trace;
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  double* v = tr.vecs + (size_t)rec * 5 * n;
-  const double* src[5] = {d_x, s->d_r, s->d_zv, d_p_now, d_p_now ? s->d_q : nullptr};
-  for (int k = 0; k < 5; k++) {
-    if (src[k]) D2H(v + k * n, src[k], n);
-    else std::fill(v + k * n, v + (k + 1) * n, 0.0);
-  }
-  for (int k = 0; k < 4; k++) {
-    launch_sum_parts(s->stream, part(s, k), s->d_scal);
-    TRY(fetch_scalar(s, s->d_scal, tr.sums + 4 * (size_t)rec + k));
-  }
-  D2H(tr.slots + (size_t)rec * 5 * kNPart, s->d_parts, (size_t)5 * kNPart);  // the five arrays pcg() zeroes; the sixth is scratch
-  return 0;
-}
-// ... and what the iterations of this solve launch, from the expressions the launchers themselves evaluate:
-// [0] fused [1] lanes [2] non-temporal [3] tiled [4] XCD eighths taken [5] grid of the product [6] graphs replayed
-// [7] mixed-precision iteration [8] bit j: iteration j ended with a residual replacement [9] update kernel (0 block-Jacobi
-// pcg_update, 1 pcg_update_noz, 2 pcg_update_init32) [10] matrix-free product [11] polynomial degree [12] preconditioner
-// [13] bits of the polynomial's matrix [14] 12 x 12 node blocks [15] grid of the update kernel [16] lanes, [17] grid and
-// [18] XCD eighths of the fp64 product of a residual replacement [19] TLFEA_XCD_ROWS mode
-static void cg_trace_form(tlfea_newton_t s, bool fused, int deg, bool graphs) {
-  int* f = s->trace->form;
-  const int N = s->N;
-  const SpmvForm sf = spmv_form(N, fused, s->spmv_nt, s->spmv32_now), rf = spmv_form(N, false, s->spmv_nt, false);
-  const bool fuse_init = deg > 1 && cheb_bits_eff(s) != 64 && !s->ar && !blk12_now(s);  // as enqueue_cg_iteration_impl
-  f[0] = sf.fused; f[1] = sf.lanes; f[2] = sf.nt; f[3] = sf.tiled; f[4] = sf.xcd; f[5] = sf.grid;
-  f[6] = graphs ? 1 : 0;
-  f[7] = s->spmv32_now ? 1 : 0;
-  f[9] = deg > 1 ? (fuse_init ? 2 : 1) : 0;
-  f[10] = s->mf.now ? 1 : 0;
-  f[11] = deg; f[12] = deg > 1 ? precond_eff(s) : 0; f[13] = cheb_bits_eff(s); f[14] = blk12_now(s) ? 1 : 0;
-  f[15] = slot_grid_256(f[9] == 1 ? 3 * N : N);
-  f[16] = rf.lanes; f[17] = rf.grid; f[18] = rf.xcd; f[19] = sf.xcd_mode;
-}
-
-// Solve H x = b on the device (b, x device vectors of 3N).  Standard PCG, block-Jacobi.
-static int pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out) {
-  s->mf.now = false;
-  s->mf.last_mode = 0;
-  s->fmf.now = false;
-  s->fmf.last = 0;
-  TRY(refuse_empty_rows(s, "linear solve"));
-  if (s->lin.method == 1) return direct_solve(s, d_b, d_x, iters_out, rel_out);
-  tlfea_t10_t d = s->d;
-  const int N = s->N;
-  StageTimer t(s, 4);
-  const double* w = s->d_w;
-  const bool lp = cheb_bits_eff(s) != 64;
-  if (s->halo.on) {
-    if (!lp || cheb_degree_eff(s) <= 1)
-      return fail("overlapping partition: needs the polynomial / p-multigrid preconditioner on the scaled low-precision copy "
-                  "(cheb_degree > 1, cheb_bits 16 or 32)");
-    if (halo_dr(s) + 1 > s->halo.depth)
-      return fail("overlapping partition: halo depth " + std::to_string(s->halo.depth) + " is below the " +
-                  std::to_string(halo_dr(s) + 1) + " layers the fine level needs");
-  }
+// The set-up of a call that runs no start residual between the stages (modal solve, the operator hook): both stages, then
+// the flag of the node-block factorisation once the stream is drained.
+int tlfea::precond_setup_whole(tlfea_newton_t s, const double* d_b, const char* who) {
   TRY(precond_setup(s, d_b, 0));
-  HIP_TRY(hipMemsetAsync(s->d_parts, 0, (size_t)5 * kNPart * sizeof(double), s->stream));
-  launch_pcg_init(s->stream, N, d_b, s->d_Dinv, w, d_x, s->d_r, s->d_zv, part(s, 0), part(s, 4));
-  TRY(parts_sum(s, part(s, 0), part(s, 4)));
-  launch_sum_parts(s->stream, part(s, 4), s->d_scal + 1);
-  double bb = 0.0;
-  TRY(fetch_scalar(s, s->d_scal + 1, &bb));
-  if (s->trace) TRY(cg_trace_record(s, 0, d_x, nullptr));
-  if (lp && blk12_now(s)) {  // the stream is drained: the flag of this solve's node-block factorisation is final
+  TRY(precond_setup(s, d_b, 1));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (cheb_bits_eff(s) != 64 && blk12_now(s)) {
     int bad = 0;
     HIP_TRY(hipMemcpy(&bad, s->d_blk12_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bad) return fail("a 12 x 12 node block of H is not positive definite (H is not SPD)");
-  }
-  int it = 0;
-  double rr = bb;
-  if (bb > 0.0) {
-    const double target = s->lin.rel_tol * s->lin.rel_tol * bb;
-    const bool fused_csr = s->pcg_fused < 0 ? (N <= 200000) : (s->pcg_fused != 0);
-    const int deg = cheb_degree_eff(s);
-    // matrix-free product (serves the un-fused form: p from the direction kernel); everything before the iteration -- the
-    // diagonal, the low-precision copy, the lambda_max estimate, the Galerkin operators -- stays on the CSR H
-    s->spmv32_now = s->spmv32_every >= 2 && deg > 1 && lp && !s->ar;
-    s->mf.now = matfree_chosen(s);
-    s->mf.last_mode = s->mf.now ? 1 : 0;
-    if (s->mf.now) TRY(matfree_ensure_buffer(s));
-    if (s->mf.now) TRY(matfree_ensure_records(s));
-    const bool fused = fused_csr && !s->mf.now;
-    // an outer iteration costs `deg` SpMV launches: test convergence proportionally more often
-    int check_every = std::max(1, s->lin.check_every / deg);
-    // Every convergence test drains the launch queue (tens of microseconds: as much as an iteration on a small
-    // mesh).  Consecutive Newton iterations need nearly the same number of CG iterations, so after the first solve
-    // the tests start four iterations before the previous solve's count and then run every iteration.
-    const int bits = cheb_bits_eff(s) + 1000 * precond_eff(s);
-    int first_check = check_every;
-    if (s->last_outer_iters > 1 && s->last_deg == deg && s->last_bits == bits) {
-      // (a few iterations earlier, not one: the count can DROP by more than one between solves -- from the first Newton
-      // iteration of a step to the second -- and starting at last - 1 then over-solves for several solves in a row)
-      static const int back = std::max(1, env_int("TLFEA_PCG_CHECK_BACK", 4));
-      first_check = std::max(1, s->last_outer_iters - back);
-      check_every = 1;
-    }
-    s->last_deg = deg;
-    s->last_bits = bits;
-    s->lmax_mf_ok = true;  // only this call may take the matrix-free lambda_max product (estimate_lam_max)
-    const int rc_setup = precond_setup(s, d_b, 1);
-    s->lmax_mf_ok = false;
-    if (rc_setup) return rc_setup;
-    // hipGraph replay: single GPU, and the overlapping partition when its exchange is the built-in RCCL one (enqueued
-    // from C++ on this stream, so the neighbour exchanges and all-reduces are captured with the kernels)
-    bool graphs = s->use_graphs && !s->ar && !s->profiling && (!s->halo.on || (s->halo.native && halo_graph_wanted()));
-    // a capture that fails with collectives inside (RCCL refusing it) is not fatal: back to eager launches, once
-    auto prepare_graphs = [&]() -> int {
-      if (!graphs) return 0;
-      const int rc = cg_graphs_prepare(s, d_x, fused, deg, bits);
-      if (rc == 0 || !s->halo.on) return rc;
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(s->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-        hipGraph_t g = nullptr;
-        (void)hipStreamEndCapture(s->stream, &g);
-        if (g) (void)hipGraphDestroy(g);
-      }
-      (void)hipGetLastError();
-      cg_graphs_destroy(s);
-      halo_graph_give_up();
-      graphs = false;
-      std::fprintf(stderr, "tlfea: hipGraph capture of the partitioned CG iteration failed (%s): eager launches from here on\n",
-                   tlfea_last_error());
-      return 0;
-    };
-    // mixed-precision iteration: where the fp32 polynomial path runs (its update kernel writes the start vectors the
-    // replacement rewrites), on one GPU
-    s->cur_b = d_b;
-    s->spmv32_now = s->spmv32_every >= 2 && deg > 1 && lp && !s->ar;
-    if (s->spmv32_now) {
-      if (!s->d_H32) HIP_TRY(hipMalloc((void**)&s->d_H32, (size_t)9 * d->nnz_coef * sizeof(float)));
-      launch_to_float(s->stream, (size_t)9 * d->nnz_coef, s->d_H, s->d_H32);
-    }
-    const int R = s->spmv32_every;
-    static const bool pcg_trace = std::getenv("TLFEA_PCG_TRACE") != nullptr;  // tools: test every iteration, print r.z, p.q
-    if (pcg_trace) {
-      first_check = 1;
-      check_every = 1;
-    }
-    bool r_is_true = !s->spmv32_now;  // the residual vector is b - H x of the fp64 system (not the recurrence's)
-    // overlapping partition: the start residual r = b of a ghost is its owner's (grad L is evaluated redundantly on the
-    // overlap and differs by round-off)
-    if (s->halo.on) TRY(halo_refresh_f64(s, 0, halo_dr(s), 3, s->d_r));
-    TRY(prepare_graphs());
-    double indefinite = 0.0;
-    HIP_TRY(hipMemsetAsync(s->d_scal + 3, 0, sizeof(double), s->stream));
-    // p-multigrid converges in 30-45 iterations when its coarse polynomial covers the vertex-level spectrum; far more
-    // means the size-based degree is too low for this mesh: raise it (kept for later solves) and start over
-    const int kStallIters = 56;
-    bool stalled = false;
-    int stall_check = (precond_eff(s) == 2 && s->pmg.ok && pmg_coarse_degree_eff(s) < kPmgMaxCoarseDeg) ? kStallIters : 0;
-    for (int attempt = 0;; attempt++) {
-      while (it < s->lin.max_iter) {
-        // r.z slots of iteration `it` live in part(it & 1), the previous ones in the other pair
-        const bool replace = s->spmv32_now && it > 0 && (it + 1) % R == 0;  // R is even: always an odd iteration
-        if (graphs && it > 0) {
-          const int gk = replace ? 2 : (it & 1);
-          HIP_TRY(hipGraphLaunch(s->cg_graph[gk], s->stream));
-          if (s->halo.on) {
-            auto& hh = s->halo;
-            const double* c = hh.graph_cost[gk];
-            hh.n_exch += (long)c[0]; hh.n_exch_cg += (long)c[0];
-            hh.n_allred += (long)c[1]; hh.n_allred_cg += (long)c[1];
-            hh.bytes_exch += c[2]; hh.bytes_allred += c[3]; hh.n_cg_iters += (long)c[4];
-            s->n_collectives += (long)c[1];
-          }
-        } else
-          TRY(enqueue_cg_iteration(s, d_x, it == 0, it & 1, fused, deg, replace));
-        if (s->spmv32_now) {
-          r_is_true = replace;
-          s->n_replacements += replace ? 1 : 0;
-        }
-        it++;
-        if (s->trace) {  // the hook's max_iter is its k: no test before the last iteration
-          if (it == 1) cg_trace_form(s, fused, deg, graphs);
-          if (replace) s->trace->form[8] |= 1 << (it - 1);
-          TRY(cg_trace_record(s, it, d_x, fused ? (((it - 1) & 1) ? s->d_p : s->d_p2) : s->d_p));
-        }
-        if ((!s->trace && it >= first_check && (it - first_check) % check_every == 0) || it == s->lin.max_iter ||
-            (!s->trace && it == stall_check)) {
-          if (s->halo.on) TRY(parts_sum(s, part(s, 3)));  // the r.r slots are summed over ranks only when tested
-          launch_sum_parts(s->stream, part(s, 3), s->d_scal + 2);
-          TRY(fetch_scalar2(s, s->d_scal + 2, &rr, &indefinite));  // ||r||^2 and the r.z < 0 flag
-          if (pcg_trace) {
-            double rz = 0.0, pq = 0.0;
-            launch_sum_parts(s->stream, part(s, (it - 1) & 1), s->d_scal);
-            TRY(fetch_scalar(s, s->d_scal, &rz));
-            launch_sum_parts(s->stream, part(s, 2), s->d_scal);
-            TRY(fetch_scalar(s, s->d_scal, &pq));
-            std::fprintf(stderr, "pcg trace: attempt %d it %d rel %.3e rz %.6e pq %.6e indefinite %g\n", attempt, it,
-                         std::sqrt(rr / bb), rz, pq, indefinite);
-          }
-          if (!(rr > target) && rr == rr && !r_is_true) {
-            // the recurrence says converged: the verdict is the fp64 system's -- replace the residual and test that
-            TRY(enqueue_residual_replacement(s, d_x));
-            s->n_replacements++;
-            r_is_true = true;
-            if (s->halo.on) TRY(parts_sum(s, part(s, 3)));
-            launch_sum_parts(s->stream, part(s, 3), s->d_scal + 2);
-            TRY(fetch_scalar2(s, s->d_scal + 2, &rr, &indefinite));
-          }
-          if (!(rr > target)) break;                       // also leaves on NaN
-          if (rr > 1e8 * bb || indefinite != 0.0) break;   // the preconditioner is not positive definite
-          if (it >= stall_check && stall_check > 0) {      // p-multigrid far beyond its usual 30-45 iterations
-            stalled = true;
-            break;
-          }
-        }
-      }
-      // A Chebyshev polynomial is positive only up to the upper end of its interval: if the power iteration
-      // underestimated lambda_max by more than the safety margin, CG breaks down (NaN or growth).  Widen and redo.
-      const bool broke = (rr != rr) || rr > 1e8 * bb || (indefinite != 0.0 && rr > target);
-      if (stalled && !broke && (attempt >= 3 || pmg_coarse_degree_eff(s) >= kPmgMaxCoarseDeg)) {
-        stalled = false;  // nothing left to raise: keep iterating with what there is
-        stall_check = 0;
-        continue;
-      }
-      if ((!broke && !stalled) || deg <= 1 || attempt >= 3) break;
-      if (stalled && !broke) {
-        s->pmg.kc_boost *= 1.45;
-        if (s->verbose)
-          std::printf("p-multigrid: %d CG iterations without convergence, coarse polynomial degree raised to %d\n", it,
-                      pmg_coarse_degree_eff(s));
-        stalled = false;
-        stall_check = pmg_coarse_degree_eff(s) < kPmgMaxCoarseDeg ? kStallIters : 0;
-        TRY(pmg_coefficients(s));
-        TRY(prepare_graphs());
-      } else {
-        s->lam_safety *= 1.5;  // kept for the following solves: the estimate is systematically low on this mesh
-        if (s->verbose) std::printf("PCG breakdown: Chebyshev interval widened to %.3g x lambda_max estimate\n", s->lam_safety);
-        TRY(cheb_upload_coefficients(s));
-        if (precond_eff(s) == 2) TRY(pmg_coefficients(s));
-      }
-      launch_pcg_init(s->stream, N, d_b, s->d_Dinv, w, d_x, s->d_r, s->d_zv, part(s, 0), part(s, 4));
-      TRY(parts_sum(s, part(s, 0), part(s, 4)));
-      if (s->halo.on) TRY(halo_refresh_f64(s, 0, halo_dr(s), 3, s->d_r));
-      HIP_TRY(hipMemsetAsync(s->d_scal + 3, 0, sizeof(double), s->stream));
-      indefinite = 0.0;
-      it = 0;
-      rr = bb;
-      r_is_true = !s->spmv32_now;
-      first_check = std::max(1, s->lin.check_every / deg);
-      check_every = first_check;
-    }
-    s->last_outer_iters = it;
-  } else {
-    HIP_TRY(hipMemsetAsync(d_x, 0, 3 * (size_t)N * sizeof(double), s->stream));
-  }
-  HIP_TRY(hipGetLastError());
-  t.stop();
-  const double rel = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-  if (iters_out) *iters_out = it;
-  if (rel_out) *rel_out = rel;
-  s->lin_last_rel = rel;
-  s->lin_last_ok = rel == rel && rel <= s->lin.rel_tol;
-  s->lin_worst_rel = (rel != rel) ? rel : std::max(s->lin_worst_rel, rel);
-  s->lin_all_ok = s->lin_all_ok && s->lin_last_ok;
-  if (rr != rr) return fail("PCG produced NaN (Hessian not SPD?)");
-  // The solve stands in for the reference's cuDSS factor + solve, which aborts on failure: an iterate that missed the
-  // tolerance (max_iter, or breakdown after the last interval widening) is not applied unless the caller asked for it.
-  if (!s->lin_last_ok && !s->lin.on_unconverged) {
-    char msg[256];
-    std::snprintf(msg, sizeof msg, "PCG did not converge: ||r||/||b|| = %.3e > rel_tol %.1e after %d iterations (max_iter %d)",
-                  rel, s->lin.rel_tol, it, s->lin.max_iter);
-    return fail(msg);
+    if (bad) return fail(std::string(who) + ": a 12 x 12 node block of H is not positive definite (H is not SPD)");
   }
   return 0;
 }
@@ -4122,14 +3671,6 @@ extern "C" int tlfea_newton_get_gradient_form(tlfea_newton_t s) {
   if (!s) return 0;
   return mass_in_residual(s) ? 2 : 1;
 }
-extern "C" int tlfea_newton_get_linsolve_info(tlfea_newton_t s, int* cheb_degree, int* cheb_bits, int* cheb_vector_bits) {
-  if (!s) return fail("null argument");
-  if (cheb_degree) *cheb_degree = cheb_degree_eff(s);
-  if (cheb_bits) *cheb_bits = cheb_bits_eff(s);
-  if (cheb_vector_bits)
-    *cheb_vector_bits = (cheb_bits_eff(s) != 64 && (!s->ar || s->d_own || precond_eff(s) == 2)) ? 32 : 64;
-  return 0;
-}
 extern "C" int tlfea_newton_eval_gradient(tlfea_newton_t s, double* norm_g) {
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
   TRY(sync_constraints(s));
@@ -4139,44 +3680,6 @@ extern "C" int tlfea_newton_assemble_hessian(tlfea_newton_t s) {
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
   TRY(assemble(s, /*fq_fresh=*/false));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  return 0;
-}
-extern "C" int tlfea_newton_linear_solve(tlfea_newton_t s, const double* b, double* x, int* iters, double* rel_res) {
-  TRY(refuse_empty_rows(s, "tlfea_newton_linear_solve"));
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipMemcpy(s->d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
-  TRY(pcg(s, s->d_b, s->d_dv, iters, rel_res));
-  D2H(x, s->d_dv, n);
-  return 0;
-}
-
-// Test hook (tests/test_gpu_cg_trace.py): the solver's own iterative solve of H x = b for exactly k <= 8 iterations -- pcg()
-// itself with max_iter = k and no convergence test before the last iteration -- with every iterate copied out on the way
-// (cg_trace_record, cg_trace_form).  The warm state is left as that solve leaves it.
-extern "C" int tlfea_newton_cg_trace(tlfea_newton_t s, const double* b, int k, double* vecs, double* sums, double* slots,
-                                     int* form) {
-  if (!s || !b || !vecs || !sums || !slots || !form) return fail("tlfea_newton_cg_trace: null argument");
-  if (k < 1 || k > 8) return fail("tlfea_newton_cg_trace: k must be 1..8");
-  if (!s->d_H) return fail("tlfea_newton_cg_trace: no assembled H");
-  if (dist_on(s)) return fail("tlfea_newton_cg_trace: not available on a partitioned mesh (set_interface / set_halo is active)");
-  if (s->lin.method == 1) return fail("tlfea_newton_cg_trace: method = 1 (sparse direct) has no iteration");
-  TRY(refuse_empty_rows(s, "tlfea_newton_cg_trace"));
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipMemcpy(s->d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
-  tlfea_newton_s::CgTrace tr;
-  tr.k = k; tr.vecs = vecs; tr.sums = sums; tr.slots = slots; tr.form = form;
-  std::fill(form, form + kCgTraceForm, 0);
-  const auto lin = s->lin;
-  s->lin.max_iter = k;
-  s->lin.on_unconverged = 1;  // k iterations are not meant to converge
-  s->trace = &tr;
-  int its = 0;
-  double rel = 0.0;
-  const int rc = pcg(s, s->d_b, s->d_dv, &its, &rel);
-  s->trace = nullptr;
-  s->lin = lin;
-  if (rc) return rc;
-  if (its != k) return fail("tlfea_newton_cg_trace: the solve ended after " + std::to_string(its) + " of " + std::to_string(k) + " iterations");
   return 0;
 }
 
@@ -4258,37 +3761,6 @@ extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out
   HIP_TRY(hipGetLastError());
   return 0;
 }
-
-// y = H x for host vectors with the current H (partition-boundary rows summed over ranks)
-extern "C" int tlfea_newton_apply_hessian(tlfea_newton_t s, const double* x, double* y) {
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipMemcpy(s->d_zv, x, n * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemsetAsync(s->d_parts, 0, (size_t)5 * kNPart * sizeof(double), s->stream));
-  launch_spmv_dir_dot(s->stream, s->N, s->d->inc(), s->d_H, s->d_zv, s->d_p, 1, part(s, 1), part(s, 0), s->d_p2,
-                      s->d_q, part(s, 2), true, s->spmv_nt);
-  if (s->ar) TRY(iface_sum(s, s->d_q, 3, part(s, 2), kNPart));
-  HIP_TRY(hipGetLastError());
-  D2H(y, s->d_q, n);
-  return 0;
-}
-
-// y = H x from the matrix-free pair with the current records (tests); an error where the product is not eligible
-extern "C" int tlfea_newton_apply_hessian_matfree(tlfea_newton_t s, const double* x, double* y) {
-  if (!s || !x || !y) return fail("null argument");
-  if (!s->sparsity_done || !matfree_eligible(s))
-    return fail("matrix-free Hessian product: not eligible (needs an assembled H of straight-sided T10 elements with one "
-                "St.Venant-Kirchhoff material, one GPU, no linear constraints, no obstacles, and no residual evaluation "
-                "since the assembly)");
-  const size_t n = 3 * (size_t)s->N;
-  HIP_TRY(hipMemcpy(s->d_zv, x, n * sizeof(double), hipMemcpyHostToDevice));
-  TRY(matfree_ensure_buffer(s));
-  TRY(matfree_ensure_records(s));
-  TRY(launch_matfree_product(s, s->d_zv, s->d_q, part(s, 2)));
-  HIP_TRY(hipGetLastError());
-  D2H(y, s->d_q, n);
-  return 0;
-}
-extern "C" int tlfea_newton_get_spmv_mode(tlfea_newton_t s) { return s ? s->mf.last_mode : -1; }
 // Test hook: ONE fine pass of the form of DESIGN 3g' (apply + gather-and-step) with the set-up a preceding
 // tlfea_newton_apply_preconditioner left, on host vectors: d, res, z float [3N], r double [3N], the pair coef[2], zw (0:
 // none), last.  Out: d', and either z^', res^' (float) or z = S z^' (double) and the kNPart r.z slots.
@@ -4381,327 +3853,6 @@ extern "C" int tlfea_newton_get_matfree_records(tlfea_newton_t s, int single, in
   if (points) *points = np;
   return 0;
 }
-
-// ---- modal analysis: the lowest pairs of K phi = omega^2 M phi by LOBPCG on the shifted pencil ------------
-// A = K + sigma M is H / h assembled with h = 1 / sqrt(sigma), so the iteration runs on the pencil (H, M) itself:
-// H x = nu M x with nu = h (omega^2 + sigma).  M need not be definite (the T10 mass of the 5-point Keast rule is not), so
-// the block is kept H-orthonormal and the Rayleigh-Ritz step takes the largest theta = 1 / nu (tests/modal_np.py).
-namespace {
-// device scratch of one call, released when the call returns
-struct ModalWork {
-  std::vector<void*> owned;
-  ~ModalWork() {
-    for (void* p : owned)
-      if (p) (void)hipFree(p);
-  }
-  int alloc(double** p, size_t n) {
-    TRY(dmalloc(p, n));
-    owned.push_back(*p);
-    return 0;
-  }
-};
-// Warm-start state of the lambda_max estimates (fine level and the coarse levels that exist): save() keeps it and sets the
-// estimates cold, so that what follows depends on no earlier solve; restore() puts it back.  A level built in between did
-// not exist at the save: its vector stays, its estimate goes back to 0.  solve_state: a call that runs solves of its own
-// (modal solve, adjoint step) also keeps the scalars a linear solve leaves for the next one and for the status read-backs.
-struct LamKeep {
-  std::vector<std::pair<double*, size_t>> vecs;  // the kept vectors that exist at the save
-  std::vector<std::pair<double*, double>> lams;  // the estimates
-  double* d_save = nullptr;
-  tlfea_newton_t kept_of = nullptr;              // solve_state: the solver whose scalars `kept` holds
-  std::tuple<double, double, int, int, int, int, double, double, bool, bool> kept;
-  static auto solve_scalars(tlfea_newton_t s) {
-    return std::tie(s->lam_safety, s->pmg.kc_boost, s->last_outer_iters, s->last_deg, s->last_bits, s->mf.last_mode,
-                    s->lin_last_rel, s->lin_worst_rel, s->lin_last_ok, s->lin_all_ok);
-  }
-  int save(tlfea_newton_t s, ModalWork& wk, bool solve_state = false) {
-    size_t total = 0;
-    for (PolyLevel* L : {&s->pmg.vertex, &s->pmg.agg.lvl})
-      if (L->d_eigv) vecs.push_back({L->d_eigv, 3 * (size_t)L->N});
-    vecs.push_back({s->d_eigv, 3 * (size_t)s->N});
-    for (auto& v : vecs) total += v.second;
-    TRY(wk.alloc(&d_save, total));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(copy(true));
-    for (double* p : {&s->lam_max, &s->lam_max_loc, &s->pmg.vertex.lam, &s->pmg.agg.lvl.lam}) {
-      lams.push_back({p, *p});
-      *p = 0.0;
-    }
-    if (solve_state) {
-      kept_of = s;
-      kept = solve_scalars(s);
-    }
-    return 0;
-  }
-  void restore() {
-    for (auto& l : lams) *l.first = l.second;
-    if (kept_of) solve_scalars(kept_of) = kept;
-    (void)copy(false);
-  }
-  hipError_t copy(bool out) {
-    hipError_t e = hipSuccess;
-    double* at = d_save;
-    for (auto& v : vecs) {
-      const hipError_t e1 = hipMemcpy(out ? at : v.first, out ? v.first : at, v.second * sizeof(double), hipMemcpyDeviceToDevice);
-      if (e == hipSuccess) e = e1;
-      at += v.second;
-    }
-    return e;
-  }
-};
-}  // namespace
-
-static const int* modal_mask(tlfea_newton_t s) { return pinned_on(s) ? s->d->d_fixed_slot : nullptr; }
-static bool modal_has_mass(tlfea_t10_t d) { return d->is_csr_setup && d->d_mval && mass_assembled(d); }
-static void modal_product(tlfea_newton_t s, int which, int m, const double* X, int ldx, double* Y, int ldy, const int* mask) {
-  tlfea_t10_t d = s->d;
-  if (which == 0) launch_spmm_block(s->stream, s->N, m, d->d_off, d->d_cols, s->d_H, X, ldx, Y, ldy, mask);
-  else launch_massmm_block(s->stream, s->N, m, d->d_off, d->d_cols, d->d_mval, X, ldx, Y, ldy, mask);
-}
-
-static int modal_iterate(tlfea_newton_t s, const tlfea_modal_opts& o, int m, double* omega2, double* modes, double* resid,
-                         int* info) {
-  const int N = s->N, n = 3 * N, ld = 3 * m, nm = o.n_modes;
-  const int* mask = modal_mask(s);
-  const double h = s->prm.time_step;
-  // Memory of a call: S, HS, MS of 3N x 3m doubles each and R of 3N x m -- 80 m bytes per DOF (2.6 kB at m = 32, 0.7 kB at
-  // the default m = 9 of six modes), freed on return.  Scratch of the linear solver that is free between solves is
-  // borrowed: d_b (start vector of the lambda_max estimate), d_r / d_zv (one column in, T of it out), and inside T what a
-  // CG iteration uses (d_cd, d_cd2, the fp32 work vectors, part(0)).  None of it carries state across solves.
-  ModalWork wk;
-  double *S, *AS, *MS, *R, *slots, *dG, *dC, *dmu, *dnrm;
-  TRY(wk.alloc(&S, (size_t)n * ld)); TRY(wk.alloc(&AS, (size_t)n * ld)); TRY(wk.alloc(&MS, (size_t)n * ld));
-  TRY(wk.alloc(&R, (size_t)n * m)); TRY(wk.alloc(&slots, gram_slot_doubles(n, ld, ld)));
-  TRY(wk.alloc(&dG, (size_t)2 * 96 * 96)); TRY(wk.alloc(&dC, (size_t)96 * 64)); TRY(wk.alloc(&dmu, 32)); TRY(wk.alloc(&dnrm, 64));
-  for (double* b : {S, AS, MS}) HIP_TRY(hipMemsetAsync(b, 0, (size_t)n * ld * sizeof(double), s->stream));
-  launch_block_hash(s->stream, n, m, o.seed, mask, S, ld);
-  // the preconditioner of this H, from a cold lambda_max estimate started at the block's first column
-  launch_block_get_col(s->stream, n, S, ld, 0, s->d_b);
-  TRY(precond_setup(s, s->d_b, 0));
-  TRY(precond_setup(s, s->d_b, 1));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (cheb_bits_eff(s) != 64 && blk12_now(s)) {
-    int bad = 0;
-    HIP_TRY(hipMemcpy(&bad, s->d_blk12_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bad) return fail("tlfea_newton_modal_solve: a 12 x 12 node block of H is not positive definite (H is not SPD)");
-  }
-  info[3] = cheb_degree_eff(s) > 1 ? precond_eff(s) : 0;
-
-  std::vector<double> GA, GM, theta, Ck, Cfull, nu(m, 0.0), nrm(2 * (size_t)m, 0.0), hG((size_t)2 * ld * ld);
-  auto gram_pair = [&](int k) -> int {  // G_A = S^T AS, G_M = S^T MS over the first k columns, to the host
-    launch_gram(s->stream, n, k, k, S, ld, AS, ld, slots, dG);
-    launch_gram(s->stream, n, k, k, S, ld, MS, ld, slots, dG + (size_t)k * k);
-    HIP_TRY(hipMemcpyAsync(hG.data(), dG, (size_t)2 * k * k * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return 0;
-  };
-  auto sub = [&](const double* G, int k, const std::vector<int>& idx, std::vector<double>& out) {
-    const int kk = (int)idx.size();
-    out.resize((size_t)kk * kk);
-    for (int a = 0; a < kk; a++)
-      for (int b = 0; b < kk; b++) out[(size_t)a * kk + b] = G[(size_t)idx[a] * k + idx[b]];
-  };
-  auto set_nu = [&]() {
-    for (int j = 0; j < m; j++) nu[j] = theta[j] != 0.0 ? 1.0 / theta[j] : 0.0;
-  };
-  auto combine_all = [&](int k, const std::vector<double>& C, int nz, int nz0, int z0, int z1) -> int {
-    HIP_TRY(hipMemcpyAsync(dC, C.data(), (size_t)k * nz * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    for (double* b : {S, AS, MS}) launch_block_combine(s->stream, n, k, b, ld, dC, nz, nz0, z0, z1);
-    HIP_TRY(hipStreamSynchronize(s->stream));  // C's host copy is reused
-    return 0;
-  };
-  auto products_of_x = [&]() {
-    modal_product(s, 0, m, S, ld, AS, ld, mask);
-    modal_product(s, 1, m, S, ld, MS, ld, mask);
-  };
-  // start: Rayleigh-Ritz on the hashed block alone
-  products_of_x();
-  TRY(gram_pair(m));
-  {
-    std::vector<int> idx(m);
-    for (int j = 0; j < m; j++) idx[j] = j;
-    sub(hG.data(), m, idx, GA);
-    sub(hG.data() + (size_t)m * m, m, idx, GM);
-    if (modal::rayleigh_ritz(m, GA, GM, m, theta, Ck) < m)
-      return fail("tlfea_newton_modal_solve: the start block is rank deficient (try another seed or a smaller block)");
-    set_nu();
-    TRY(combine_all(m, Ck, m, m, 0, 0));
-  }
-  std::vector<char> conv(m, 0), p_valid(m, 0);
-  int it = 0, n_conv = 0;
-  bool verified = false;
-  for (;;) {
-    HIP_TRY(hipMemcpyAsync(dmu, nu.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    launch_block_residual(s->stream, n, m, AS, MS, ld, dmu, R, m, slots, dnrm);
-    HIP_TRY(hipMemcpyAsync(nrm.data(), dnrm, (size_t)2 * m * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    n_conv = 0;
-    bool all = true;
-    for (int j = 0; j < m; j++) {
-      const double rn = std::sqrt(nrm[j]), mn = std::sqrt(nrm[m + j]);
-      conv[j] = theta[j] > 0.0 && rn <= o.tol * nu[j] * mn;
-      if (j < nm) {
-        n_conv += conv[j] ? 1 : 0;
-        all = all && conv[j];
-      }
-    }
-    if (all) {
-      if (verified) break;
-      products_of_x();  // the products kept by recurrence drift: convergence is declared on recomputed ones only
-      verified = true;
-      continue;
-    }
-    verified = false;
-    if (it == o.max_iter) break;
-    it++;
-    // W = T R on the unconverged columns, masked, then made H-orthogonal to X
-    std::vector<int> idx;
-    for (int j = 0; j < m; j++) idx.push_back(j);
-    for (int j = 0; j < m; j++) {
-      if (conv[j]) {
-        launch_block_set_col(s->stream, n, nullptr, mask, S, ld, m + j);
-        continue;
-      }
-      launch_block_get_col(s->stream, n, R, m, j, s->d_r);
-      TRY(precond_apply(s, s->d_r, s->d_zv, part(s, 0), false));
-      launch_block_set_col(s->stream, n, s->d_zv, mask, S, ld, m + j);
-      idx.push_back(m + j);
-    }
-    for (int j = 0; j < m; j++)
-      if (!conv[j] && p_valid[j]) idx.push_back(2 * m + j);
-    launch_gram(s->stream, n, m, m, AS, ld, S + m, ld, slots, dG);
-    HIP_TRY(hipMemcpyAsync(hG.data(), dG, (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    {
-      std::vector<double> C((size_t)2 * m * m, 0.0);
-      for (int i = 0; i < m; i++)
-        for (int j = 0; j < m; j++) C[(size_t)i * m + j] = -hG[(size_t)i * m + j];
-      for (int j = 0; j < m; j++) C[(size_t)(m + j) * m + j] = 1.0;
-      HIP_TRY(hipMemcpyAsync(dC, C.data(), C.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      launch_block_combine(s->stream, n, 2 * m, S, ld, dC, m, m, m, m);
-      HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    modal_product(s, 0, m, S + m, ld, AS + m, ld, mask);   // the iteration's one product with H and with M
-    modal_product(s, 1, m, S + m, ld, MS + m, ld, mask);
-    TRY(gram_pair(ld));
-    sub(hG.data(), ld, idx, GA);
-    sub(hG.data() + (size_t)ld * ld, ld, idx, GM);
-    const int k = (int)idx.size();
-    if (modal::rayleigh_ritz(k, GA, GM, m, theta, Ck) < m)
-      return fail("tlfea_newton_modal_solve: the Rayleigh-Ritz basis lost rank (H not positive definite on the free DOFs?)");
-    set_nu();
-    // new X = S C and new P = its W and P part, both written in one pass over S, AS, MS
-    Cfull.assign((size_t)ld * 2 * m, 0.0);
-    for (int a = 0; a < k; a++)
-      for (int j = 0; j < m; j++) {
-        const double c = Ck[(size_t)a * m + j];
-        Cfull[(size_t)idx[a] * 2 * m + j] = c;
-        if (idx[a] >= m && !conv[j]) Cfull[(size_t)idx[a] * 2 * m + m + j] = c;  // a locked column keeps no direction
-      }
-    TRY(combine_all(ld, Cfull, 2 * m, m, 0, 2 * m));
-    for (int j = 0; j < m; j++) p_valid[j] = !conv[j];
-  }
-  info[0] = it;
-  info[1] = n_conv;
-  for (int j = 0; j < nm; j++) {
-    const bool pos = theta[j] > 0.0;
-    omega2[j] = pos ? nu[j] / h - o.shift : std::nan("");
-    const double rn = std::sqrt(nrm[j]), mn = std::sqrt(nrm[m + j]);
-    resid[j] = pos && mn > 0.0 ? rn / (nu[j] * mn) : std::nan("");
-    if (modes) {
-      // x^T H x = 1 and x^T M x = theta: phi = x / sqrt(theta) has phi^T M phi = 1
-      launch_block_get_col(s->stream, n, S, ld, j, s->d_r);
-      launch_scale(s->stream, n, pos ? 1.0 / std::sqrt(theta[j]) : 0.0, s->d_r);
-      HIP_TRY(hipMemcpyAsync(modes + (size_t)j * n, s->d_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipGetLastError());
-  if (n_conv < nm) {
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "tlfea_newton_modal_solve: %d of %d modes converged to tol %.1e in %d iterations", n_conv, nm,
-                  o.tol, it);
-    return fail(msg);
-  }
-  return 0;
-}
-
-extern "C" int tlfea_newton_modal_solve(tlfea_newton_t s, const tlfea_modal_opts* opts, double* omega2, double* modes,
-                                        double* resid, int* info) {
-  if (!s || !opts || !omega2 || !resid || !info) return fail("tlfea_newton_modal_solve: null argument");
-  tlfea_t10_t d = s->d;
-  tlfea_modal_opts o = *opts;
-  info[0] = info[1] = info[2] = info[3] = 0;
-  if (o.n_modes < 1) return fail("tlfea_newton_modal_solve: n_modes must be at least 1");
-  if (!(o.shift > 0.0) || !std::isfinite(o.shift)) return fail("tlfea_newton_modal_solve: shift must be finite and positive");
-  if (!(o.tol > 0.0) || o.max_iter < 1) return fail("tlfea_newton_modal_solve: tol must be positive and max_iter at least 1");
-  if (o.block_extra < 0) o.block_extra = std::max(0, std::min(std::max(2, o.n_modes / 2), 32 - o.n_modes));
-  const int m = o.n_modes + o.block_extra;
-  if (m > 32) return fail("tlfea_newton_modal_solve: block size n_modes + block_extra = " + std::to_string(m) + " exceeds 32");
-  if (d->mat.eta != 0.0 || d->mat.lamd != 0.0 || d->emat_damp)
-    return fail("tlfea_newton_modal_solve: damping is set (eta / lambda_damp != 0, uniform or in the material table): C_vis "
-                "would enter the pencil; undamped modes only");
-  for (int k = 0; k < d->obs.n; k++)
-    if (d->obs.o[k].mu > 0.0)
-      return fail("tlfea_newton_modal_solve: obstacle " + std::to_string(k) + " has friction: its tangent depends on the time "
-                  "step and on the start-of-step positions, so H / h would not be K + shift M; frictionless obstacles only");
-  if (dist_on(s)) return fail("tlfea_newton_modal_solve: not available on a partitioned mesh (set_interface / set_halo is active)");
-  if (s->lin.method == 1)
-    return fail("tlfea_newton_modal_solve: method = 1 (sparse direct) is refused: the direct solve factorises on every call "
-                "and has no solve-only entry; use the iterative method for the modal call");
-  if (!d->have_dndu || !modal_has_mass(d))
-    return fail("tlfea_newton_modal_solve: needs the mass matrix and its sparsity (CalcDnDuPre, CalcMassMatrix) first");
-  TRY(tlfea_newton_analyze_hessian_sparsity(s));
-  TRY(refuse_empty_rows(s, "tlfea_newton_modal_solve"));
-  TRY(sync_constraints(s));
-  int n_free = s->N;
-  if (pinned_on(s)) {
-    std::vector<char> fx(s->N, 0);
-    for (int i : d->h_fixed) fx[i] = 1;
-    for (char c : fx) n_free -= c;
-  }
-  if (3 * m > 3 * n_free)
-    return fail("tlfea_newton_modal_solve: 3 x block size = " + std::to_string(3 * m) + " exceeds the " +
-                std::to_string(3 * n_free) + " free DOFs");
-  info[2] = m;
-  // what the call must leave as it found it: the time step, the warm-start state of the linear solver
-  ModalWork wk;
-  LamKeep keep;
-  const double h0 = s->prm.time_step;
-  TRY(keep.save(s, wk, /*solve_state=*/true));  // cold estimates: the result depends on no earlier solve
-  s->prm.time_step = 1.0 / std::sqrt(o.shift);
-  int rc = assemble(s, /*fq_fresh=*/false);
-  if (!rc) rc = modal_iterate(s, o, m, omega2, modes, resid, info);
-  const std::string why = rc ? api_error() : std::string();
-  (void)hipStreamSynchronize(s->stream);
-  s->prm.time_step = h0;
-  keep.restore();
-  const int rc2 = assemble(s, /*fq_fresh=*/false);  // H of the caller's time step again
-  (void)hipStreamSynchronize(s->stream);
-  if (rc) {
-    api_error() = why;
-    return rc;
-  }
-  return rc2;
-}
-
-// Test hooks: Y = H X (which 0) or (M (x) I3) X (which 1) for a host block [3N][m] with the current H; G = X^T Y
-extern "C" int tlfea_newton_modal_apply_block(tlfea_newton_t s, int which, int m, const double* X, double* Y, int apply_mask) {
-  if (!s || !X || !Y) return fail("tlfea_newton_modal_apply_block: null argument");
-  if (m < 1 || m > 32 || which < 0 || which > 1) return fail("tlfea_newton_modal_apply_block: m must be 1..32, which 0 or 1");
-  if (which == 0 && !s->d_H) return fail("tlfea_newton_modal_apply_block: no assembled H");
-  if (which == 1 && !modal_has_mass(s->d)) return fail("tlfea_newton_modal_apply_block: no mass matrix");
-  const size_t cnt = 3 * (size_t)s->N * m;
-  ModalWork wk;
-  double *dX, *dY;
-  TRY(wk.alloc(&dX, cnt)); TRY(wk.alloc(&dY, cnt));
-  HIP_TRY(hipMemcpy(dX, X, cnt * sizeof(double), hipMemcpyHostToDevice));
-  modal_product(s, which, m, dX, m, dY, m, apply_mask ? modal_mask(s) : nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(Y, dY, cnt * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
 // Test hooks: the preconditioner as an operator (tests/test_gpu_precond_operator.py).  The set-up is the one of a solve
 // (precond_setup stages 0 and 1 back to back, as the modal solve runs them) from cold lambda_max estimates; the warm state
 // of the linear solver is put back afterwards, as tlfea_newton_modal_solve does.
@@ -4730,14 +3881,7 @@ extern "C" int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, 
     } else {
       HIP_TRY(hipMemcpy(s->d_b, dR, n * sizeof(double), hipMemcpyDeviceToDevice));
     }
-    TRY(precond_setup(s, s->d_b, 0));
-    TRY(precond_setup(s, s->d_b, 1));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (cheb_bits_eff(s) != 64 && blk12_now(s)) {
-      int bad = 0;
-      HIP_TRY(hipMemcpy(&bad, s->d_blk12_err, sizeof(int), hipMemcpyDeviceToHost));
-      if (bad) return fail("tlfea_newton_apply_preconditioner: a 12 x 12 node block of H is not positive definite (H is not SPD)");
-    }
+    TRY(precond_setup_whole(s, s->d_b, "tlfea_newton_apply_preconditioner"));
     for (int k = 0; k < m; k++) TRY(precond_apply(s, dR + k * n, dZ + k * n, part(s, 0), false));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -4790,37 +3934,6 @@ extern "C" int tlfea_newton_preconditioner_state(tlfea_newton_t s, int* iout16, 
   if (n_coef) HIP_TRY(hipMemcpy(coef, src, (size_t)n_coef * sizeof(double), hipMemcpyDeviceToHost));
   dout8[0] = s->lam_max; dout8[1] = s->pmg.vertex.lam; dout8[2] = s->pmg.agg.lvl.lam; dout8[3] = s->lam_safety;
   dout8[4] = s->hook_lam[0]; dout8[5] = s->hook_lam[1]; dout8[6] = s->hook_lam[2];
-  return 0;
-}
-// Mean milliseconds of one spmm_block launch (Y = H X, m columns, masked) over `reps` back-to-back launches between one
-// hipEvent pair, after one untimed launch (tools/modal_timing.py); X is the hashed start block
-extern "C" int tlfea_newton_modal_time_spmm(tlfea_newton_t s, int m, int reps, double* ms_out) {
-  if (!s || !ms_out) return fail("tlfea_newton_modal_time_spmm: null argument");
-  if (m < 1 || m > 32 || reps < 1) return fail("tlfea_newton_modal_time_spmm: m must be 1..32, reps at least 1");
-  if (!s->d_H) return fail("tlfea_newton_modal_time_spmm: no assembled H");
-  const int n = 3 * s->N;
-  ModalWork wk;
-  double *dX, *dY;
-  TRY(wk.alloc(&dX, (size_t)n * m)); TRY(wk.alloc(&dY, (size_t)n * m));
-  launch_block_hash(s->stream, n, m, 0u, modal_mask(s), dX, m);
-  modal_product(s, 0, m, dX, m, dY, m, modal_mask(s));
-  TRY(time_reps(s->stream, reps, ms_out, [&](int) { modal_product(s, 0, m, dX, m, dY, m, modal_mask(s)); return 0; }));
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-extern "C" int tlfea_newton_modal_gram(tlfea_newton_t s, int p, int q, const double* X, const double* Y, double* G) {
-  if (!s || !X || !Y || !G) return fail("tlfea_newton_modal_gram: null argument");
-  if (p < 1 || p > 96 || q < 1 || q > 96) return fail("tlfea_newton_modal_gram: p and q must be 1..96");
-  const size_t n = 3 * (size_t)s->N;
-  ModalWork wk;
-  double *dX, *dY, *slots, *dG;
-  TRY(wk.alloc(&dX, n * p)); TRY(wk.alloc(&dY, n * q)); TRY(wk.alloc(&slots, gram_slot_doubles((int)n, p, q))); TRY(wk.alloc(&dG, (size_t)p * q));
-  HIP_TRY(hipMemcpy(dX, X, n * p * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dY, Y, n * q * sizeof(double), hipMemcpyHostToDevice));
-  launch_gram(s->stream, (int)n, p, q, dX, p, dY, q, slots, dG);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(G, dG, (size_t)p * q * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -5022,14 +4135,6 @@ extern "C" int tlfea_newton_get_comm_stats(tlfea_newton_t s, double* out8) {
   return 0;
 }
 extern "C" int tlfea_newton_n_constraints(tlfea_newton_t s) { return s ? s->n_constraints : -1; }
-extern "C" int tlfea_newton_get_linsolve_status(tlfea_newton_t s, double* out4) {
-  if (!s || !out4) return fail("null argument");
-  out4[0] = s->lin_last_rel;
-  out4[1] = s->lin_last_ok ? 1.0 : 0.0;
-  out4[2] = s->lin_worst_rel;
-  out4[3] = s->lin_all_ok ? 1.0 : 0.0;
-  return 0;
-}
 extern "C" int tlfea_newton_get_stage_ms(tlfea_newton_t s, double* ms, double* counts, int reset) {
   std::copy(s->stage_ms, s->stage_ms + 8, ms);
   if (counts) std::copy(s->stage_n, s->stage_n + 8, counts);
@@ -5044,383 +4149,6 @@ extern "C" int tlfea_newton_begin_step(tlfea_newton_t s) {
   TRY(begin_step(s));
   HIP_TRY(hipMemcpyAsync(s->d_vprev, s->d_v, 3 * (size_t)s->N * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   return 0;
-}
-
-// =================================================================================================
-// Adjoint sensitivities of the implicit step (adjoint_kernels.hip)
-static int sens_slots(tlfea_t10_t h) { return (h->mat.model == kMooneyRivlin ? 3 : 2) + 1; }
-static int sens_n_mat(tlfea_t10_t h) { return h->d_emat ? h->n_mat : 1; }
-// what both sensitivities need of the handle: a T10 mesh, set up, with its reference-geometry tables
-static int sens_need_t10(tlfea_t10_t h, const char* what) {
-  if (h && h->kind != kT10) return fail(std::string(what) + ": T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, what);
-  if (!h->have_dndu) return fail(std::string(what) + ": CalcDnDuPre must be called first");
-  return 0;
-}
-// the vectors of the two timing entry points -- any finite ones serve a timing: the positions as w, zeros as u
-static int sens_timing_vectors(tlfea_t10_t h) {
-  const size_t n = 3 * (size_t)h->N;
-  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
-  if (!h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
-  HIP_TRY(hipMemset(h->d_sn_w, 0, n * sizeof(double)));
-  HIP_TRY(hipMemcpy(h->d_sn_w, h->d_x, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice));
-  HIP_TRY(hipMemset(h->d_sn_u, 0, n * sizeof(double)));
-  return 0;
-}
-// buffers and, under a material table, the ascending element list of every material with its chunks of kAdjChunk (any
-// element kind; newton_handle.h)
-int tlfea::sens_buffers(tlfea_t10_t h) {
-  if (!h->d_sn_sens) TRY(dmalloc(&h->d_sn_sens, (size_t)4 * h->Epad));
-  const int n_mat = sens_n_mat(h);
-  if (n_mat > h->sn_out_cap) {
-    if (h->d_sn_out) (void)hipFree(h->d_sn_out);
-    TRY(dmalloc(&h->d_sn_out, (size_t)n_mat * 4));
-    h->sn_out_cap = n_mat;
-  }
-  int nb = (h->E + kAdjChunk - 1) / kAdjChunk;
-  if (h->d_emat && h->sn_gen != h->gen) {
-    std::vector<int> cnt(n_mat + 1, 0), idx(h->E), boff(n_mat + 1, 0);
-    for (int e = 0; e < h->E; e++) cnt[h->h_eid[e] + 1]++;
-    for (int k = 0; k < n_mat; k++) cnt[k + 1] += cnt[k];
-    std::vector<int> at(cnt.begin(), cnt.end() - 1);
-    for (int e = 0; e < h->E; e++) idx[at[h->h_eid[e]]++] = e;  // ascending inside every material
-    std::vector<int2> blk;
-    for (int k = 0; k < n_mat; k++) {
-      boff[k] = (int)blk.size();
-      for (int a = cnt[k]; a < cnt[k + 1]; a += kAdjChunk) blk.push_back(make_int2(a, std::min(cnt[k + 1], a + kAdjChunk)));
-    }
-    boff[n_mat] = (int)blk.size();
-    HIP_TRY(hipDeviceSynchronize());
-    dfree(h->d_sn_idx);
-    dfree(h->d_sn_boff);
-    dfree(h->d_sn_blk);
-    TRY(dmalloc(&h->d_sn_idx, idx.size()));
-    TRY(dmalloc(&h->d_sn_boff, boff.size()));
-    TRY(dmalloc(&h->d_sn_blk, blk.size()));
-    HIP_TRY(hipMemcpy(h->d_sn_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_sn_boff, boff.data(), boff.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (!blk.empty()) HIP_TRY(hipMemcpy(h->d_sn_blk, blk.data(), blk.size() * sizeof(int2), hipMemcpyHostToDevice));
-    h->sn_nb = (int)blk.size();
-    h->sn_gen = h->gen;
-  }
-  if (h->d_emat) nb = h->sn_nb;
-  const int cap = std::max(nb, (h->N + kAdjChunk - 1) / kAdjChunk);  // the node sums of a_bar share the buffer
-  if (cap > h->sn_part_cap) {
-    if (h->d_sn_part) (void)hipFree(h->d_sn_part);
-    TRY(dmalloc(&h->d_sn_part, (size_t)cap * 4));
-    h->sn_part_cap = cap;
-  }
-  return 0;
-}
-static int sens_prepare(tlfea_t10_t h, const char* what) {
-  TRY(sens_need_t10(h, what));
-  return sens_buffers(h);
-}
-// the two launches after sens_prepare: d_sn_sens from device vectors w, u, then d_sn_out [n_mat][slots]
-static void sens_launch_points(tlfea_t10_t h, hipStream_t st, const double* d_w, const double* d_u) {
-  SensShape sh;
-  shape_at_rule_points(h, sh.Nq);
-  launch_sens_points(st, h->view(), h->mat.model, sh, d_w, d_u, h->d_sn_sens);
-}
-static void sens_launch_sums(tlfea_t10_t h, hipStream_t st) {
-  if (h->d_emat)
-    launch_adj_sums(st, sens_slots(h), h->E, h->sn_nb, h->d_sn_blk, h->d_sn_idx, h->d_sn_sens, (size_t)h->Epad, 1, h->n_mat,
-                    h->d_sn_boff, h->d_sn_part, h->d_sn_out);
-  else
-    launch_adj_sums(st, sens_slots(h), h->E, (h->E + kAdjChunk - 1) / kAdjChunk, nullptr, nullptr, h->d_sn_sens,
-                    (size_t)h->Epad, 1, 1, nullptr, h->d_sn_part, h->d_sn_out);
-}
-
-extern "C" int tlfea_t10_material_sensitivity_shape(tlfea_t10_t h, int* n_mat, int* slots) {
-  if (h && h->kind != kT10) return fail("tlfea_t10_material_sensitivity_shape: T10 handles only (not an ANCF handle)");
-  NEED_SETUP(h, "tlfea_t10_material_sensitivity_shape");
-  if (n_mat) *n_mat = sens_n_mat(h);
-  if (slots) *slots = sens_slots(h);
-  return 0;
-}
-
-extern "C" int tlfea_t10_material_sensitivity(tlfea_t10_t h, const double* w, const double* u, double* per_element,
-                                              double* per_material) {
-  TRY(sens_prepare(h, "tlfea_t10_material_sensitivity"));
-  if (!w) return fail("tlfea_t10_material_sensitivity: null w");
-  const size_t n = 3 * (size_t)h->N;
-  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
-  if (u && !h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
-  HIP_TRY(hipMemcpy(h->d_sn_w, w, n * sizeof(double), hipMemcpyHostToDevice));
-  if (u) HIP_TRY(hipMemcpy(h->d_sn_u, u, n * sizeof(double), hipMemcpyHostToDevice));
-  const int slots = sens_slots(h);
-  sens_launch_points(h, h->stream, h->d_sn_w, u ? h->d_sn_u : nullptr);
-  sens_launch_sums(h, h->stream);
-  HIP_TRY(hipGetLastError());
-  if (per_element) {
-    if (!h->d_sn_pe) TRY(dmalloc(&h->d_sn_pe, (size_t)h->E * 4));
-    launch_sens_transpose(h->stream, h->E, h->Epad, slots, h->d_sn_sens, h->d_sn_pe);
-    D2H(per_element, h->d_sn_pe, (size_t)h->E * slots);
-  }
-  if (per_material) D2H(per_material, h->d_sn_out, (size_t)sens_n_mat(h) * slots);
-  HIP_TRY(hipDeviceSynchronize());
-  return 0;
-}
-
-extern "C" int tlfea_t10_time_sensitivity_kernels(tlfea_t10_t h, int reps, double* out_ms2) {
-  TRY(sens_prepare(h, "tlfea_t10_time_sensitivity_kernels"));
-  if (!out_ms2) return fail("tlfea_t10_time_sensitivity_kernels: null output");
-  if (reps < 1) reps = 1;
-  TRY(sens_timing_vectors(h));
-  TRY(time_reps(h->stream, reps, &out_ms2[0], [&](int) { sens_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u); return 0; }));
-  TRY(time_reps(h->stream, reps, &out_ms2[1], [&](int) { sens_launch_sums(h, h->stream); return 0; }));
-  return 0;
-}
-
-// ---- shape sensitivities (shape_kernels.hip) -----------------------------------------------------------------
-static int shape_prepare(tlfea_t10_t h, const char* what) {
-  TRY(sens_need_t10(h, what));
-  if (!h->is_csr_setup) TRY(tlfea_t10_build_mass_csr_pattern(h));  // the node -> element incidence of the gather
-  if (!h->d_sh_rows) TRY(dmalloc(&h->d_sh_rows, (size_t)3 * kNN * h->Epad));
-  return 0;
-}
-// the two launches after shape_prepare: device vectors w, u [3N] (u null: no mass term) -> d_xbar [N][3].  The density
-// of the mass term is the one the mass matrix was assembled with.
-static void shape_launch_points(tlfea_t10_t h, hipStream_t st, const double* d_w, const double* d_u) {
-  Material m = h->mat;
-  m.rho0 = h->mass_rho0 >= 0.0 ? h->mass_rho0 : 0.0;
-  launch_shape_points(st, h->view(), m, h->d_emat, h->h_q, d_w, d_u, h->d_sh_rows);
-}
-static void shape_launch_gather(tlfea_t10_t h, hipStream_t st, double* d_xbar) {
-  launch_shape_gather(st, h->N, h->Epad, h->inc(), h->d_sh_rows, d_xbar);
-}
-
-extern "C" int tlfea_t10_shape_sensitivity(tlfea_t10_t h, const double* w, const double* u, double* X_bar) {
-  TRY(shape_prepare(h, "tlfea_t10_shape_sensitivity"));
-  if (!w || !X_bar) return fail("tlfea_t10_shape_sensitivity: null w or X_bar");
-  if (u && h->mass_rho0 < 0.0) return fail("tlfea_t10_shape_sensitivity: u given but no mass matrix is assembled (CalcMassMatrix)");
-  const size_t n = 3 * (size_t)h->N;
-  if (!h->d_sn_w) TRY(dmalloc(&h->d_sn_w, n));
-  if (u && !h->d_sn_u) TRY(dmalloc(&h->d_sn_u, n));
-  if (!h->d_sh_out) TRY(dmalloc(&h->d_sh_out, n));
-  HIP_TRY(hipMemcpy(h->d_sn_w, w, n * sizeof(double), hipMemcpyHostToDevice));
-  if (u) HIP_TRY(hipMemcpy(h->d_sn_u, u, n * sizeof(double), hipMemcpyHostToDevice));
-  shape_launch_points(h, h->stream, h->d_sn_w, u ? h->d_sn_u : nullptr);
-  shape_launch_gather(h, h->stream, h->d_sh_out);
-  HIP_TRY(hipGetLastError());
-  D2H(X_bar, h->d_sh_out, n);
-  HIP_TRY(hipDeviceSynchronize());
-  return 0;
-}
-
-extern "C" int tlfea_t10_time_shape_kernels(tlfea_t10_t h, int reps, double* out_ms2) {
-  TRY(shape_prepare(h, "tlfea_t10_time_shape_kernels"));
-  if (!out_ms2) return fail("tlfea_t10_time_shape_kernels: null output");
-  if (reps < 1) reps = 1;
-  TRY(sens_timing_vectors(h));
-  if (!h->d_sh_out) TRY(dmalloc(&h->d_sh_out, 3 * (size_t)h->N));
-  TRY(time_reps(h->stream, reps, &out_ms2[0], [&](int) { shape_launch_points(h, h->stream, h->d_sn_w, h->d_sn_u); return 0; }));
-  TRY(time_reps(h->stream, reps, &out_ms2[1], [&](int) { shape_launch_gather(h, h->stream, h->d_sh_out); return 0; }));
-  return 0;
-}
-
-// why the adjoint step cannot run on the solver's state now (0: it can)
-static int adjoint_refusal(tlfea_newton_t s) {
-  if (!s) return fail("tlfea_newton_adjoint_step: null handle");
-  tlfea_t10_t d = s->d;
-  const std::string w = "tlfea_newton_adjoint_step: ";
-  if (d->kind != kT10) return fail(w + "T10 handles only (not an ANCF handle)");
-  TRY(adjoint_refusal_terms(s, w));
-  if (!d->have_dndu || !d->is_csr_setup || !d->d_mval || d->mass_rho0 < 0.0)
-    return fail(w + "needs the mass matrix (CalcDnDuPre, CalcMassMatrix) first");
-  return adjoint_refusal_state(s, w);
-}
-// the terms of the step the adjoint does not carry, on any element kind (w: the entry point's name and ": ")
-int tlfea::adjoint_refusal_terms(tlfea_newton_t s, const std::string& w) {
-  tlfea_t10_t d = s->d;
-  if (d->mat.eta != 0.0 || d->mat.lamd != 0.0 || d->emat_damp)
-    return fail(w + "damping is set (eta / lambda_damp != 0, uniform or in the material table): the viscous stress depends "
-                    "on v and x separately, which the adjoint of the undamped step does not carry");
-  for (int k = 0; k < d->obs.n; k++)
-    if (d->obs.o[k].mu > 0.0)
-      return fail(w + "obstacle " + std::to_string(k) + " has friction: its force depends on the start-of-step positions "
-                      "and its step is line-searched; frictionless obstacles only");
-  if (d->ld_n_press > 0)
-    return fail(w + "a follower pressure is set: its load stiffness is not in H, so H is not the Jacobian of the residual");
-  if (dist_on(s)) return fail(w + "not available on a partitioned mesh (set_interface / set_halo is active)");
-  return 0;
-}
-// what the last Solve() left
-int tlfea::adjoint_refusal_state(tlfea_newton_t s, const std::string& w) {
-  switch (s->adj_state) {
-    case 1: break;
-    case 0: return fail(w + "no Solve() has run: the state must be that of a step just solved");
-    case 2: return fail(w + "the last Solve() ran more than one outer iteration: one differentiated step is one outer "
-                            "iteration (max_outer = 1)");
-    case 3: return fail(w + "the last Solve() failed");
-    default: return fail(w + "the last Solve() left its Newton loop without meeting inner_atol / inner_rtol: H is the "
-                             "Jacobian of the residual at a converged step only");
-  }
-  return 0;
-}
-extern "C" int tlfea_newton_adjoint_ready(tlfea_newton_t s) { return adjoint_refusal(s); }
-// what X_bar adds to the refusals: loads whose nodal weights are reference areas, which the shape kernel does not carry
-static int adjoint_shape_refusal(tlfea_newton_t s) {
-  tlfea_t10_t d = s->d;
-  const std::string w = "tlfea_newton_adjoint_step_shape: ";
-  if (d->obs.n > 0)
-    return fail(w + "a rigid or field obstacle is set: its nodal weights are reference areas, whose dependence on the "
-                    "reference geometry X_bar does not carry");
-  if (d->ld_n_trac > 0)
-    return fail(w + "a face traction is set: its nodal loads are reference areas, whose dependence on the reference "
-                    "geometry X_bar does not carry");
-  return 0;
-}
-
-// the T10 kind of the adjoint step (AdjointKind, newton_handle.h): the material slots come from sens_point_kernel, the
-// density slot among them
-static int t10_adjoint_prepare(tlfea_t10_t d) { return sens_prepare(d, "tlfea_newton_adjoint_step"); }
-static void t10_adjoint_materials(tlfea_t10_t d, hipStream_t st, const double* w, const double* u, const double*,
-                                  double* per_material, double* per_element) {
-  const int slots = sens_slots(d);
-  sens_launch_points(d, st, w, u);
-  if (per_material) {
-    sens_launch_sums(d, st);
-    (void)hipMemcpyAsync(per_material, d->d_sn_out, (size_t)sens_n_mat(d) * slots * sizeof(double), hipMemcpyDeviceToDevice, st);
-  }
-  if (per_element) launch_sens_transpose(st, d->E, d->Epad, slots, d->d_sn_sens, per_element);
-}
-static size_t t10_pm_doubles(tlfea_t10_t d) { return (size_t)sens_n_mat(d) * sens_slots(d); }
-static size_t t10_pe_doubles(tlfea_t10_t d) { return (size_t)d->E * sens_slots(d); }
-static const AdjointKind kT10Adjoint{"tlfea_newton_adjoint_step", 1, adjoint_refusal, t10_adjoint_prepare, t10_adjoint_materials,
-                                    t10_pm_doubles, t10_pe_doubles};
-
-// The adjoint step on device pointers, for the element kind K (X_bar: T10 only).
-int tlfea::adjoint_step_device(tlfea_newton_t s, const AdjointKind& K, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                               double* X_bar, int* info, double* rel_res) {
-  TRY(K.refusal(s));
-  const std::string what = K.what;
-  if (!in || !out) return fail(what + ": null argument");
-  tlfea_t10_t d = s->d;
-  if (X_bar) {
-    TRY(adjoint_shape_refusal(s));
-    TRY(shape_prepare(d, "tlfea_newton_adjoint_step_shape"));
-  }
-  TRY(K.prepare(d));
-  TRY(tlfea_newton_analyze_hessian_sparsity(s));
-  TRY(sync_constraints(s));
-  const int n = 3 * s->N, nc = s->n_constraints;
-  const double h = s->prm.time_step, rho = s->prm.rho;
-  const double* vprev = in->v_prev ? in->v_prev : (s->d_step0 ? s->d_step0 + n : nullptr);
-  if (!vprev) return fail(what + ": no v_prev given and no Solve() has kept one");
-  AdjCons J{0, d->d_fixed, d->d_fixed_slot, d->d_joff, d->d_jcol, d->d_jtoff, d->d_jtcol, d->d_jval, d->d_jtval};
-  J.mode = pinned_on(s) ? 1 : (lincons_on(s) ? 2 : 0);
-  const double zero3[3] = {0.0, 0.0, 0.0};
-  ModalWork wk;
-  double *xt, *vt, *u, *Mw;
-  TRY(wk.alloc(&xt, (size_t)n));
-  TRY(wk.alloc(&vt, (size_t)n));
-  TRY(wk.alloc(&u, (size_t)n));
-  TRY(wk.alloc(&Mw, (size_t)n));
-  // what the call must leave as it found it: the warm-start state of the linear solver (tlfea_newton_modal_solve)
-  LamKeep keep;
-  TRY(keep.save(s, wk, /*solve_state=*/true));  // cold estimates: the result depends on no earlier solve
-  launch_adj_rhs(s->stream, n, J, in->x_bar, in->v_bar, J.mode ? in->lam_bar : nullptr, s->d_v, vprev,
-                 d->ld_have_a ? d->ld_a : zero3, K.stride, h, rho, xt, vt, u);
-  int it = 0;
-  double rel = 0.0;
-  int rc = assemble(s, /*fq_fresh=*/false);
-  // the solve runs on the Newton iteration's own right-hand side and solution vectors (scratch between Solve() calls), so
-  // the captured CG graphs stay those of the forward step
-  if (!rc && hipMemcpyAsync(s->d_b, vt, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream) != hipSuccess)
-    rc = fail(what + ": device copy failed");
-  if (!rc) rc = pcg(s, s->d_b, s->d_dv, &it, &rel);
-  const std::string why = rc ? api_error() : std::string();
-  if (rc) {
-    (void)hipStreamSynchronize(s->stream);
-    keep.restore();
-    api_error() = why;
-    return rc;
-  }
-  const double* w = s->d_dv;
-  launch_massmm_block(s->stream, s->N, 1, d->d_off, d->d_cols, d->d_mval, w, 1, Mw, 1, nullptr);
-  launch_adj_out(s->stream, n, nc, J, w, Mw, xt, vt, J.mode ? in->lam_bar : nullptr, h, rho, out->f_ext_bar,
-                 out->v_prev_bar, out->x_prev_bar, out->lam_in_bar, out->t_bar);
-  if (J.mode == 0 && nc > 0) {  // constraint terms off: the multipliers pass through
-    for (double* p : {out->lam_in_bar, out->t_bar})
-      if (p) (void)hipMemsetAsync(p, 0, (size_t)nc * sizeof(double), s->stream);
-  }
-  if (out->a_bar) {  // over the position coefficients: every K.stride-th coefficient vector
-    const int n_pos = s->N / K.stride;
-    launch_adj_sums(s->stream, 3, n_pos, (n_pos + kAdjChunk - 1) / kAdjChunk, nullptr, nullptr, Mw, 1, 3 * K.stride, 1, nullptr,
-                    d->d_sn_part, out->a_bar);
-  }
-  if (out->per_material || out->per_element) K.materials(d, s->stream, w, u, Mw, out->per_material, out->per_element);
-  if (X_bar) {
-    shape_launch_points(d, s->stream, w, u);
-    shape_launch_gather(d, s->stream, X_bar);
-  }
-  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s->stream);
-  keep.restore();
-  HIP_TRY(e1);
-  HIP_TRY(e2);
-  if (info) info[0] = it;
-  if (rel_res) *rel_res = rel;
-  return 0;
-}
-
-extern "C" int tlfea_newton_adjoint_step_shape_device(tlfea_newton_t s, const tlfea_adjoint_in* in,
-                                                      const tlfea_adjoint_out* out, double* X_bar, int* info, double* rel_res) {
-  return adjoint_step_device(s, kT10Adjoint, in, out, X_bar, info, rel_res);
-}
-
-extern "C" int tlfea_newton_adjoint_step_device(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                                                int* info, double* rel_res) {
-  return adjoint_step_device(s, kT10Adjoint, in, out, nullptr, info, rel_res);
-}
-
-// The same on host arrays: device copies of what is given and wanted around adjoint_step_device.
-int tlfea::adjoint_step_host(tlfea_newton_t s, const AdjointKind& K, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                             double* X_bar, int* info, double* rel_res) {
-  TRY(K.refusal(s));
-  if (!in || !out) return fail(std::string(K.what) + ": null argument");
-  tlfea_t10_t d = s->d;
-  if (X_bar) TRY(adjoint_shape_refusal(s));
-  const size_t n = 3 * (size_t)s->N, nc = (size_t)s->n_constraints;
-  const size_t n_pm = K.pm_doubles(d), n_pe = K.pe_doubles(d);
-  ModalWork wk;
-  tlfea_adjoint_in din{nullptr, nullptr, nullptr, nullptr};
-  tlfea_adjoint_out dout{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  auto up = [&](const double* src, size_t cnt, const double** dst) -> int {
-    if (!src || cnt == 0) return 0;
-    double* p;
-    TRY(wk.alloc(&p, cnt));
-    HIP_TRY(hipMemcpy(p, src, cnt * sizeof(double), hipMemcpyHostToDevice));
-    *dst = p;
-    return 0;
-  };
-  TRY(up(in->x_bar, n, &din.x_bar));
-  TRY(up(in->v_bar, n, &din.v_bar));
-  TRY(up(in->lam_bar, nc, &din.lam_bar));
-  TRY(up(in->v_prev, n, &din.v_prev));
-  struct Ret { double* host; double** dev; size_t cnt; };
-  double* d_Xbar = nullptr;
-  const Ret rets[] = {{out->f_ext_bar, &dout.f_ext_bar, n}, {out->v_prev_bar, &dout.v_prev_bar, n},
-                      {out->x_prev_bar, &dout.x_prev_bar, n}, {out->lam_in_bar, &dout.lam_in_bar, nc},
-                      {out->t_bar, &dout.t_bar, nc}, {out->a_bar, &dout.a_bar, 3},
-                      {out->per_material, &dout.per_material, n_pm}, {out->per_element, &dout.per_element, n_pe},
-                      {X_bar, &d_Xbar, n}};
-  for (const Ret& r : rets)
-    if (r.host && r.cnt > 0) TRY(wk.alloc(r.dev, r.cnt));
-  TRY(adjoint_step_device(s, K, &din, &dout, d_Xbar, info, rel_res));
-  for (const Ret& r : rets)
-    if (r.host && r.cnt > 0) HIP_TRY(hipMemcpy(r.host, *r.dev, r.cnt * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-extern "C" int tlfea_newton_adjoint_step_shape(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                                               double* X_bar, int* info, double* rel_res) {
-  return adjoint_step_host(s, kT10Adjoint, in, out, X_bar, info, rel_res);
-}
-
-extern "C" int tlfea_newton_adjoint_step(tlfea_newton_t s, const tlfea_adjoint_in* in, const tlfea_adjoint_out* out,
-                                         int* info, double* rel_res) {
-  return adjoint_step_host(s, kT10Adjoint, in, out, nullptr, info, rel_res);
 }
 
 
