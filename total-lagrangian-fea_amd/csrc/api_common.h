@@ -1,5 +1,5 @@
-// api_common.h -- what every host unit of the C-ABI (*_api.hip) shares: the error path, the device allocation helper,
-// the event-pair timer of the tlfea_*_time_* entry points and the readers of the environment switches.  Private to csrc/.
+// api_common.h -- what every host unit of the C-ABI (*_api.hip) shares: the error path, the device allocation and upload
+// helpers, the event-pair timer of the tlfea_*_time_* entry points and the readers of the environment switches.  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +47,13 @@ template <typename T>
 void dfree(T*& p) {
   if (p) (void)hipFree(p);
   p = nullptr;
+}
+
+template <typename T>
+int upload_vec(T** dst, const std::vector<T>& v) {
+  TRY(dmalloc(dst, std::max<size_t>(1, v.size())));
+  if (!v.empty()) HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
 }
 
 // Milliseconds per call over `reps` calls fn(0), ..., fn(reps - 1) between one pair of events on `st`.  fn returns 0 to

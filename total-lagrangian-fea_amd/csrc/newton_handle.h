@@ -1,5 +1,6 @@
 // newton_handle.h -- the Newton solver object behind tlfea_newton_t with the level types of its preconditioner, and the
-// functions of tlfea_api.hip, cg_api.hip, adjoint_api.hip, direct_api.hip and rccl_api.hip that another unit calls.
+// functions of tlfea_api.hip, precond_api.hip, cg_api.hip, adjoint_api.hip, direct_api.hip and rccl_api.hip that another
+// unit calls.
 // Included by the host units that take a tlfea_newton_t apart; private to csrc/.
 #pragma once
 #include <map>
@@ -446,10 +447,18 @@ struct LamKeep {
 // tlfea_api.hip: the partition plumbing
 bool halo_graph_wanted();
 void halo_graph_give_up();  // RCCL cannot be captured / replayed here: eager launches for the rest of the process
+int halo_dr(tlfea_newton_t s);
+void halo_free_plans(tlfea_newton_s::HaloLevel& L);
 int halo_refresh_f64(tlfea_newton_t s, int level, int D, int dim, double* a, double* b = nullptr, double* c = nullptr);
+int halo_refresh_f32(tlfea_newton_t s, int level, int D, int dim, float* a, float* b = nullptr, float* c = nullptr);
+int call_allreduce(tlfea_newton_t s, double* d_buf, int n);
+int allreduce_host(tlfea_newton_t s, double* d_buf, double* h, size_t n);
+int iface_sum_lvl(tlfea_newton_t s, const LevelIface& I, double* d_vec, int dim, double* d_extra = nullptr,
+                  int n_extra = 0, double* d_extra2 = nullptr);
 int iface_sum(tlfea_newton_t s, double* d_vec, int dim, double* d_extra = nullptr, int n_extra = 0,
               double* d_extra2 = nullptr);
 int parts_sum(tlfea_newton_t s, double* d_a, double* d_b = nullptr);
+int device_sumsq_async(tlfea_newton_t s, const double* d_vec, const double* w, int n);
 int fetch_scalar(tlfea_newton_t s, const double* d_src, double* out);
 int fetch_scalar2(tlfea_newton_t s, const double* d_src, double* out0, double* out1);
 // tlfea_api.hip: the Newton solver's element stage and the fp64 matrix-free product
@@ -460,18 +469,26 @@ bool lincons_on(tlfea_newton_t s);
 void shape_at_rule_points(tlfea_t10_t d, double Nq[kNQ][kNN]);
 bool matfree_eligible(tlfea_newton_t s);
 bool matfree_chosen(tlfea_newton_t s);
+bool matfree_compact_env();
+int matfree_points(bool single);
 int matfree_ensure_buffer(tlfea_newton_t s);
 int matfree_ensure_records(tlfea_newton_t s);
 int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part);
 int assemble(tlfea_newton_t s, bool fq_fresh = true);
-// tlfea_api.hip: the preconditioners
-int halo_dr(tlfea_newton_t s);
+// precond_api.hip: the preconditioners
+struct PmgTable;  // pmg_coef.h
 int cheb_degree_eff(tlfea_newton_t s);
 int cheb_bits_eff(tlfea_newton_t s);
 int precond_eff(tlfea_newton_t s);
 bool blk12_now(tlfea_newton_t s);
 int cheb_upload_coefficients(tlfea_newton_t s);
 int pmg_coarse_degree_eff(tlfea_newton_t s);
+int pmg_ks(tlfea_newton_t s);
+PmgTable pmg_table(tlfea_newton_t s);
+C32Level fine_c32(tlfea_newton_t s);
+void c32_step(tlfea_newton_t s, const C32Level& L, C32Vecs& v, int rows, const double* coef, const double* d_r, double* d_z,
+              double* rz_part, bool last, C32Bnd bnd = C32Bnd());
+int ensure_fine_copy(tlfea_newton_t s);
 bool pmg_rop_now(tlfea_newton_t s);
 long fine_matfree_key(tlfea_newton_t s);
 bool fine_matfree_live(tlfea_newton_t s);

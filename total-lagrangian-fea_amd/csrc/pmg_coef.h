@@ -1,6 +1,6 @@
 // pmg_coef.h -- coefficients of the CG preconditioner's polynomials and the layout of the V-cycle's coefficient table.
 //
-// Pure host code: no HIP, no environment, no state.  tlfea_api.hip reads the switches and the lambda_max estimates, this
+// Pure host code: no HIP, no environment, no state.  precond_api.hip reads the switches and the lambda_max estimates, this
 // header turns them into the pairs (c1, c2) a polynomial step reads at coef[2k]: d' = c1 d + c2 (SDS)^-1 res'.
 //
 // Table of the cycle (pmg.d_coef), in doubles:
