@@ -432,9 +432,29 @@ int tlfea_newton_pmg_sizes(tlfea_newton_t s, int *n_coarse, int *nnz_coarse_bloc
 int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int *par0, int *par1, int *c_off, int *c_cols, double *Hc);
 /* Hc as the last preconditioner set-up (a solve or tlfea_newton_apply_preconditioner) left it on the device, nothing is
  * recomputed: the 9 nnz values, and in *form the kernel that summed them -- 1 the gather over the contribution lists
- * (ANCF), 2 the row kernel alone, 3 the row kernel fused with the streamed build of R.  Fails before the first set-up and
- * after tlfea_newton_pmg_retrieve / tlfea_newton_pmg3_retrieve, which sum Hc again, until the next set-up. */
+ * (ANCF), 2 the row kernel alone, 3 the row kernel fused with the streamed build of R, 4 the same fused pass on the image
+ * rows of R assembled from the element records, with H itself left unassembled (TLFEA_SETUP_RECORDS).  Fails before the
+ * first set-up and after tlfea_newton_pmg_retrieve / tlfea_newton_pmg3_retrieve, which sum Hc again, until the next set-up. */
 int tlfea_newton_pmg_retrieve_built(tlfea_newton_t s, double *Hc, int *form);
+/* Solve set-up from the element records (TLFEA_SETUP_RECORDS: 0 never, 1 wherever eligible, unset = eligible and at least
+ * 400 000 node rows).  Where the CG's product, the fine smoother and the lambda_max product of a solve all run from the
+ * element records and R is built in the pass that sums Hc (one GPU, uniform material, no term added to H after the fused
+ * assembly), the Newton loop does not assemble H: it assembles the image rows of R, sum over the children of w H[child, :],
+ * as rows of their own (the row function of a vertex is its linear hat function) and the fine block diagonal, and the set-up
+ * sums Hc, D_c, sc_c and R from them.  Everything else that reads H (the read-backs, the hooks, the modal, direct and
+ * adjoint solves, the CSR fall-backs of a solve) gets it assembled on demand from the point records while they are still
+ * those of that assembly, and fails with a message that says so once they have moved (tlfea_newton_eval_gradient);
+ * tlfea_newton_assemble_hessian always assembles.
+ * out[0] = 1 if the last p-multigrid set-up ran on the image rows, 0 on the CSR H; out[1] = assemblies of H since the solver
+ * was created; out[2] = 1 if the H on the device is the one of the last assembly. */
+int tlfea_newton_get_setup_form(tlfea_newton_t s, long long out[3]);
+/* Test hook: the image rows of the last such assembly, row I in H's row layout [d][len][3] at 9 r_off[I] (r_off: the row
+ * offsets of tlfea_newton_pmg_restrict_op_retrieve); *len = 9 x blocks of R, image may be null (length only).  Fails when no
+ * Newton iteration has taken the form yet. */
+int tlfea_newton_get_setup_image(tlfea_newton_t s, double *image, long long *len);
+/* Test hook: the fine level's 3x3 diagonal blocks [N][9], row-major, as the last preconditioner set-up read them off H or
+ * the last assembly from the element records wrote them. */
+int tlfea_newton_get_block_diagonal(tlfea_newton_t s, double *D);
 /* Test hooks of the restricted fine operator R = S_c P^T S_f^-1 Hs, through which the V-cycle restricts the fine residual
  * (one GPU, first-kind smoother, 16- or 32-bit fine copy; TLFEA_PMG_RESTRICT_OP=0 keeps the fine residual pass).  They
  * copy back what the LAST preconditioner set-up (a solve or tlfea_newton_apply_preconditioner) left on the device and

@@ -249,6 +249,13 @@ def _pmg_signatures(lib):
         lib.tlfea_newton_fine_smoother_pass.argtypes = [vp, c_fp, c_fp, c_fp, c_dp, c_dp, C.c_double, C.c_int, c_fp, c_fp, c_fp,
                                                         c_dp, c_dp]
         lib.tlfea_newton_fine_smoother_pass.restype = C.c_int
+    if hasattr(lib, "tlfea_newton_get_setup_form"):
+        lib.tlfea_newton_get_setup_form.argtypes = [vp, C.POINTER(C.c_longlong)]
+        lib.tlfea_newton_get_setup_form.restype = C.c_int
+        lib.tlfea_newton_get_setup_image.argtypes = [vp, c_dp, C.POINTER(C.c_longlong)]
+        lib.tlfea_newton_get_setup_image.restype = C.c_int
+        lib.tlfea_newton_get_block_diagonal.argtypes = [vp, c_dp]
+        lib.tlfea_newton_get_block_diagonal.restype = C.c_int
     if hasattr(lib, "tlfea_newton_pmg_retrieve_built"):
         lib.tlfea_newton_pmg_retrieve_built.argtypes = [vp, c_dp, c_ip]
         lib.tlfea_newton_pmg_retrieve_built.restype = C.c_int

@@ -272,6 +272,7 @@ int tlfea::pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
     s->mf.last_mode = s->mf.now ? 1 : 0;
     if (s->mf.now) TRY(matfree_ensure_buffer(s));
     if (s->mf.now) TRY(matfree_ensure_records(s));
+    if (!s->mf.now) TRY(hessian_current(s));  // the iteration's product streams H (before any capture)
     const bool fused = fused_csr && !s->mf.now;
     // an outer iteration costs `deg` SpMV launches: test convergence proportionally more often
     int check_every = std::max(1, s->lin.check_every / deg);
@@ -320,6 +321,7 @@ int tlfea::pcg(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out,
     s->cur_b = d_b;
     s->spmv32_now = s->spmv32_every >= 2 && deg > 1 && lp && !s->ar;
     if (s->spmv32_now) {
+      TRY(hessian_current(s));
       if (!s->d_H32) HIP_TRY(hipMalloc((void**)&s->d_H32, (size_t)9 * d->nnz_coef * sizeof(float)));
       launch_to_float(s->stream, (size_t)9 * d->nnz_coef, s->d_H, s->d_H32);
     }
@@ -483,6 +485,7 @@ extern "C" int tlfea_newton_cg_trace(tlfea_newton_t s, const double* b, int k, d
   if (!s || !b || !vecs || !sums || !slots || !form) return fail("tlfea_newton_cg_trace: null argument");
   if (k < 1 || k > 8) return fail("tlfea_newton_cg_trace: k must be 1..8");
   if (!s->d_H) return fail("tlfea_newton_cg_trace: no assembled H");
+  TRY(hessian_current(s));  // the hook's iteration is the one on the CSR H
   if (dist_on(s)) return fail("tlfea_newton_cg_trace: not available on a partitioned mesh (set_interface / set_halo is active)");
   if (s->lin.method == 1) return fail("tlfea_newton_cg_trace: method = 1 (sparse direct) has no iteration");
   TRY(refuse_empty_rows(s, "tlfea_newton_cg_trace"));
@@ -508,6 +511,7 @@ extern "C" int tlfea_newton_cg_trace(tlfea_newton_t s, const double* b, int k, d
 // y = H x for host vectors with the current H (partition-boundary rows summed over ranks)
 extern "C" int tlfea_newton_apply_hessian(tlfea_newton_t s, const double* x, double* y) {
   const size_t n = 3 * (size_t)s->N;
+  TRY(hessian_current(s));
   HIP_TRY(hipMemcpy(s->d_zv, x, n * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemsetAsync(s->d_parts, 0, (size_t)5 * kNPart * sizeof(double), s->stream));
   launch_spmv_dir_dot(s->stream, s->N, s->d->inc(), s->d_H, s->d_zv, s->d_p, 1, part(s, 1), part(s, 0), s->d_p2,

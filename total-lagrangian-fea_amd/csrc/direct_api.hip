@@ -209,6 +209,7 @@ static int direct_prepare(tlfea_newton_t s) {
 
 // H x = b by re-factorisation + triangular solves; the true residual is measured with the fp64 SpMV of the CG
 int tlfea::direct_solve(tlfea_newton_t s, const double* d_b, double* d_x, int* iters_out, double* rel_out) {
+  TRY(hessian_current(s));  // the factorisation and the residual's SpMV read H
   TRY(direct_prepare(s));
   auto& m = s->direct;
   static RocsolverApi none;

@@ -1721,8 +1721,13 @@ struct AffineCoefPE {
 };
 
 // EXP: as assemble_direct_kernel (experiment bits honoured by the tools-only instantiation); AC: AffineCoef, or
-// AffineCoefPE for per-element materials
-template <int TIMING, int EXP, class AC = AffineCoef>
+// AffineCoefPE for per-element materials.
+// COARSE (uniform material only; DESIGN 3g'): the rows are those of the unscaled image of R, (P^T H)[I, :].  On a straight-
+// sided element N_c + 1/2 sum of N_mid over the edges at c is the linear hat function L_c, whose gradient is g_c at every
+// point: an instance is (element, corner c), its row function has al = 1, be = 0 everywhere, cmass is the [4][16] table of
+// the corners' summed mass coefficients, and the work lists are those of the coarse rows over R's columns.  No pinned rows:
+// the launch passes no fixed_slot (launch_image_pinned adds the children's penalties afterwards).
+template <int TIMING, int EXP, class AC = AffineCoef, bool COARSE = false>
 __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, AC ac,
                                                                 const double* __restrict__ gvec,
                                                                 const double* __restrict__ Fq16,
@@ -1745,7 +1750,7 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
   if (gbeg + (int)(blockIdx.x >> 3) >= gend) return;
   const int lane = threadIdx.x;
   const int k = lane >> 2, n = lane & 3;  // instance k of the pass, vertex n
-  for (int t = lane; t < 160; t += 64) cml[t] = cmass[t] * mscale;
+  for (int t = lane; t < (COARSE ? 64 : 160); t += 64) cml[t] = cmass[t] * mscale;
   const int last_inst = rg.n_inst - 1;
   // The walk over the pass table is wave-uniform, but its loads inside the loop are VECTOR loads (every lane the same
   // address, made opaque to the compiler by zl) read back with readfirstlane one pass later: a scalar load shares its
@@ -1871,7 +1876,7 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
     // row node: vertex A (corner il) or edge (A, B) (mid-edge il) -- FEAT10Data.cu:143 packed 2 bits per entry
     const int A = (0x904e4 >> (2 * il)) & 3;   // {0,1,2,3,0,1,0,0,1,2}
     const int B = (0xfe9e4 >> (2 * il)) & 3;   // {0,1,2,3,1,2,2,3,3,3}
-    const bool mid = il >= 4;
+    const bool mid = !COARSE && il >= 4;       // COARSE: il is the corner, A = B = il
     double gA[3], gB[3], gn[3], detJ;
     {
       const double2 a01 = *reinterpret_cast<const double2*>(Sk + 4 * A), b01 = *reinterpret_cast<const double2*>(Sk + 4 * B),
@@ -1912,7 +1917,10 @@ __global__ __launch_bounds__(64, 2) void assemble_affine_kernel(RowGroups4 rg, A
       const double trE = 0.5 * (T00 + T11 + T22 - 3.0);
       // grad N_i at this point = al g_A + be g_B
       double al, be;
-      if (sdx == 0) {
+      if constexpr (COARSE) {  // grad L_A = g_A at every point
+        al = 1.0;
+        be = 0.0;
+      } else if (sdx == 0) {
         al = mid ? 1.0 : 0.0;
         be = al;
       } else {
@@ -2155,6 +2163,39 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
   else
     hipLaunchKernelGGL((assemble_affine_kernel<0, 0>), dim3(8 * per_xcd), dim3(64), lds, s, rg, ac, av.gvec, Fq16, cmass,
                        rho0 / h, fixed_slot, nw, penalty, Hval, store_mode, nullptr);
+}
+
+// The image rows of R, (P^T H)[I, :] in H's row layout at 9 r_off[I], from the same records (COARSE above): rg are the work
+// lists of the coarse rows (build_row_groups4 on R's pattern, corner instances only), cmass4 the [4][16] table.
+AssemblyLaunchForm assemble_image_form(const RowGroups4& rg) {
+  const void* fn = (const void*)assemble_affine_kernel<0, 0, AffineCoef, true>;
+  const size_t lds = (size_t)(kAfStage + 160 + rg.acc_max) * sizeof(double);
+  static size_t lds_attr = 0, occ_lds = ~(size_t)0;
+  static int occ = 8;
+  if (lds > 64 * 1024 && lds > lds_attr) {
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    lds_attr = lds;
+  }
+  if (occ_lds != lds) {
+    int o = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, 64, lds) == hipSuccess && o > 0) occ = o;
+    occ_lds = lds;
+  }
+  return AssemblyLaunchForm{lds, 8 * std::max(1, std::min((device_cu_count() / 8) * occ, (rg.G + 7) / 8)), 1};
+}
+void launch_assemble_image(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups4& rg,
+                           const AffineView& av, const double* Fq16, const double* cmass4, double rho0, double* image) {
+  const AssemblyLaunchForm lf = assemble_image_form(rg);
+  AffineCoef ac;
+  for (int sdx = 0; sdx < 5; sdx++) {
+    const int q = sdx == 0 ? av.q0 : av.qv[sdx - 1];
+    ac.cA[sdx] = m.qw[q] * (h * mat.lambda + mat.lamd);
+    ac.cB[sdx] = m.qw[q] * (h * mat.mu + mat.eta);
+    ac.cC[sdx] = m.qw[q] * h * mat.mu;
+    ac.cL[sdx] = m.qw[q] * h * mat.lambda;
+  }
+  hipLaunchKernelGGL((assemble_affine_kernel<0, 0, AffineCoef, true>), dim3(lf.grid), dim3(64), lf.lds, s, rg, ac, av.gvec, Fq16,
+                     cmass4, rho0 / h, nullptr, nullptr, 0.0, image, ad_switches().store_mode & 3, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2623,6 +2664,138 @@ void launch_matfree_gather(hipStream_t s, int N, int Epad, const Incidence& inc,
   } else
     hipLaunchKernelGGL(matfree_gather_kernel<false>, dim3(grid), dim3(1024), 0, s, N, Epad, inc, ybuf, p, fixed_slot, nw,
                        penalty, q, pq_part);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fine block diagonal from the packed element records (DESIGN 3g'): what extract_diag_kernel reads off the assembled H.
+//   elem_diag_kernel    thread per element: the ten diagonal blocks sum_q block(grad N_a(q), grad N_a(q); F(q)) + the element's
+//                       share of M/h, six symmetric values each, into dbuf [10][Epad][6].  With h = grad N_a(q), f = F h:
+//                       block = (A1 + B1) f f^T + (h.h) B1 F F^T + (C0 h.h + C1 f.f) I   (assemble_affine_kernel's block at
+//                       g_n = h)
+//   node_diag_kernel    8 lanes per node sum the node's blocks in ascending element order (the fixed-order butterfly of
+//                       matfree_gather_kernel), add the pinned rows' penalty and write D [N][9].
+// ------------------------------------------------------------------------------------------------
+template <int NP>
+__global__ __launch_bounds__(128) void elem_diag_kernel(int E, int Epad, const double* __restrict__ gp,
+                                                        const double* __restrict__ Fp, MatfreeCoef mc, ElemDiagMass cd,
+                                                        double* __restrict__ dbuf) {
+  const int lane = threadIdx.x & 63;
+  const int e0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);
+  if (e0 >= E) return;  // wave-uniform
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t tile = (size_t)(e0 >> 6);
+  double g[4][3], detJ;
+  {
+    double gv[kMfrGVals];
+    mfr_load<double, kMfrGVals>(gp + tile * (kMfrGVals * kMfrWave), lane, gv);
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      g[0][d] = gv[d];
+      g[1][d] = gv[3 + d];
+      g[2][d] = gv[6 + d];
+      g[3][d] = -((gv[d] + gv[3 + d]) + gv[6 + d]);
+    }
+    detJ = gv[9];
+  }
+  const double* Fsub = Fp + tile * (size_t)(NP * kMfrFVals * kMfrWave);
+  double F5[5][9];  // slot order: centroid, then the points of vertices 0..3
+#pragma unroll
+  for (int p = 0; p < NP; p++) mfr_load<double, kMfrFVals>(Fsub + p * (kMfrFVals * kMfrWave), lane, F5[NP == 4 ? p + 1 : p]);
+  if constexpr (NP == 4) {
+#pragma unroll
+    for (int t = 0; t < 9; t++) F5[0][t] = 0.25 * ((F5[1][t] + F5[2][t]) + (F5[3][t] + F5[4][t]));
+  }
+  double acc[kNN][6];
+#pragma unroll
+  for (int a = 0; a < kNN; a++)
+#pragma unroll
+    for (int t = 0; t < 6; t++) acc[a][t] = 0.0;
+#pragma unroll
+  for (int sdx = 0; sdx < 5; sdx++) {
+    const double* F = F5[sdx];
+    const double T00 = F[0] * F[0] + F[1] * F[1] + F[2] * F[2], T01 = F[0] * F[3] + F[1] * F[4] + F[2] * F[5],
+                 T02 = F[0] * F[6] + F[1] * F[7] + F[2] * F[8], T11 = F[3] * F[3] + F[4] * F[4] + F[5] * F[5],
+                 T12 = F[3] * F[6] + F[4] * F[7] + F[5] * F[8], T22 = F[6] * F[6] + F[7] * F[7] + F[8] * F[8];
+    const double trE = 0.5 * (T00 + T11 + T22 - 3.0);
+    const double dV = detJ * (sdx == 0 ? mc.w0 : mc.w1);
+    const double AB = dV * (mc.a + mc.b), B1 = dV * mc.b, C1 = dV * mc.c1, C0 = dV * mc.cl * trE - C1;
+#pragma unroll
+    for (int a = 0; a < kNN; a++) {
+      const int A = (0x904e4 >> (2 * a)) & 3, B = (0xfe9e4 >> (2 * a)) & 3;
+      double al, be;  // grad N_a at this point = al g_A + be g_B (assemble_affine_kernel)
+      if (sdx == 0) {
+        al = a >= 4 ? 1.0 : 0.0;
+        be = al;
+      } else {
+        const int p = sdx - 1;
+        al = a >= 4 ? (B == p ? 2.0 : 2.0 / 3.0) : (A == p ? 1.0 : -1.0 / 3.0);
+        be = a >= 4 ? (A == p ? 2.0 : 2.0 / 3.0) : 0.0;
+      }
+      if (sdx == 0 && a < 4) continue;  // a vertex function has no gradient at the centroid
+      const double h0 = al * g[A][0] + be * g[B][0], h1 = al * g[A][1] + be * g[B][1], h2 = al * g[A][2] + be * g[B][2];
+      const double f0 = F[0] * h0 + F[1] * h1 + F[2] * h2, f1 = F[3] * h0 + F[4] * h1 + F[5] * h2,
+                   f2 = F[6] * h0 + F[7] * h1 + F[8] * h2;
+      const double sv = h0 * h0 + h1 * h1 + h2 * h2, tv = f0 * f0 + f1 * f1 + f2 * f2;
+      const double cdv = C0 * sv + C1 * tv, sb = sv * B1;
+      acc[a][0] += AB * f0 * f0 + sb * T00 + cdv;
+      acc[a][1] += AB * f0 * f1 + sb * T01;
+      acc[a][2] += AB * f0 * f2 + sb * T02;
+      acc[a][3] += AB * f1 * f1 + sb * T11 + cdv;
+      acc[a][4] += AB * f1 * f2 + sb * T12;
+      acc[a][5] += AB * f2 * f2 + sb * T22 + cdv;
+    }
+  }
+  if (e >= E) return;  // padding lanes of the last tile
+#pragma unroll
+  for (int a = 0; a < kNN; a++) {
+    const double mh = detJ * cd.c[a];
+    double2* o = reinterpret_cast<double2*>(dbuf + ((size_t)a * Epad + e) * 6);
+    o[0] = make_double2(acc[a][0] + mh, acc[a][1]);
+    o[1] = make_double2(acc[a][2], acc[a][3] + mh);
+    o[2] = make_double2(acc[a][4], acc[a][5] + mh);
+  }
+}
+__global__ __launch_bounds__(1024) void node_diag_kernel(int N, int Epad, Incidence inc, const double* __restrict__ dbuf,
+                                                         const int* __restrict__ fixed_slot, const double* __restrict__ nw,
+                                                         double penalty, double* __restrict__ D) {
+  const int l8 = threadIdx.x & 7;
+  const int i = blockIdx.x * 128 + (threadIdx.x >> 3);
+  if (i >= N) return;  // the eight lanes of a node leave together
+  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = inc.n2e_off[i] + l8; k < inc.n2e_off[i + 1]; k += 8) {
+    const int code = inc.n2e[k], e = code / kNN, la = code - kNN * e;
+    const double2* r = reinterpret_cast<const double2*>(dbuf + ((size_t)la * Epad + e) * 6);
+    const double2 r0 = r[0], r1 = r[1], r2 = r[2];
+    a[0] += r0.x; a[1] += r0.y; a[2] += r1.x; a[3] += r1.y; a[4] += r2.x; a[5] += r2.y;
+  }
+#pragma unroll
+  for (int o = 4; o > 0; o >>= 1)
+#pragma unroll
+    for (int t = 0; t < 6; t++) a[t] += __shfl_xor(a[t], o);
+  if (l8 == 0) {
+    // (a pinned node of no element has no diagonal block in H: extract_diag_kernel never meets one, refuse_empty_rows)
+    const double pen = (fixed_slot && fixed_slot[i] >= 0 && inc.n2e_off[i + 1] > inc.n2e_off[i]) ? (nw ? nw[i] : 1.0) * penalty : 0.0;
+    double* o = D + (size_t)9 * i;
+    o[0] = a[0] + pen; o[1] = a[1]; o[2] = a[2];
+    o[3] = a[1]; o[4] = a[3] + pen; o[5] = a[4];
+    o[6] = a[2]; o[7] = a[4]; o[8] = a[5] + pen;
+  }
+}
+void launch_records_diag(hipStream_t s, const ElemView& m, int np, const double* gp, const double* Fp, const MatfreeCoef& mc,
+                         int N, const Incidence& inc, const int* fixed_slot, const double* nw, double penalty, double* dbuf,
+                         double* D) {
+  ElemDiagMass cd;
+  for (int a = 0; a < kNN; a++) {
+    double c = 0.0;
+    for (int q = 0; q < kNQ; q++) c += mc.mw[q] * mc.Nq[q][a] * mc.Nq[q][a];
+    cd.c[a] = mc.rho_inv_h * c;
+  }
+  const dim3 grid((m.E + 127) / 128), block(128);
+  if (np == 4)
+    hipLaunchKernelGGL(elem_diag_kernel<4>, grid, block, 0, s, m.E, m.Epad, gp, Fp, mc, cd, dbuf);
+  else
+    hipLaunchKernelGGL(elem_diag_kernel<5>, grid, block, 0, s, m.E, m.Epad, gp, Fp, mc, cd, dbuf);
+  hipLaunchKernelGGL(node_diag_kernel, dim3((N + 127) / 128), dim3(1024), 0, s, N, m.Epad, inc, dbuf, fixed_slot, nw, penalty, D);
 }
 
 // Second launch of a fine smoother pass from the element records (FineMatfree, DESIGN 3g'): matfree_gather_kernel<true> in

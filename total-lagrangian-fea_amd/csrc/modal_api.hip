@@ -242,6 +242,7 @@ extern "C" int tlfea_newton_modal_apply_block(tlfea_newton_t s, int which, int m
   if (!s || !X || !Y) return fail("tlfea_newton_modal_apply_block: null argument");
   if (m < 1 || m > 32 || which < 0 || which > 1) return fail("tlfea_newton_modal_apply_block: m must be 1..32, which 0 or 1");
   if (which == 0 && !s->d_H) return fail("tlfea_newton_modal_apply_block: no assembled H");
+  if (which == 0) TRY(hessian_current(s));
   if (which == 1 && !modal_has_mass(s->d)) return fail("tlfea_newton_modal_apply_block: no mass matrix");
   const size_t cnt = 3 * (size_t)s->N * m;
   ModalWork wk;
@@ -260,6 +261,7 @@ extern "C" int tlfea_newton_modal_time_spmm(tlfea_newton_t s, int m, int reps, d
   if (!s || !ms_out) return fail("tlfea_newton_modal_time_spmm: null argument");
   if (m < 1 || m > 32 || reps < 1) return fail("tlfea_newton_modal_time_spmm: m must be 1..32, reps at least 1");
   if (!s->d_H) return fail("tlfea_newton_modal_time_spmm: no assembled H");
+  TRY(hessian_current(s));
   const int n = 3 * s->N;
   ModalWork wk;
   double *dX, *dY;

@@ -243,6 +243,26 @@ struct tlfea_newton_s {
     double* d_ss = nullptr;      // sum(sc^2)
     FineMatfree v{};
   } fmf;
+  // Solve set-up from the element records (DESIGN 3g', TLFEA_SETUP_RECORDS): where nothing of a solve reads the CSR H, the
+  // Newton loop's assemble() leaves H unassembled and writes instead the image rows of R (d_img, 9 rop.nnz doubles, H's row
+  // layout at 9 rop.d_off[I]) and the fine block diagonal (d_D); pmg_build_level sums Hc, D_c, sc_c and R from the image.
+  // h_current: d_H holds the H of the last assembly.  Whoever reads d_H calls hessian_current() first, which assembles it
+  // from the point records while they are still that assembly's (gen == mf.gen, mf.valid) and fails otherwise.
+  struct SetupRec {
+    bool tried = false, ok = false;  // the coarse work lists: built once per mesh, and they fit
+    RowGroups4 rg{0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int* d_rg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int passes = 0, n_ch = 0;
+    double* d_cmass4 = nullptr;      // [4][16] (pmg_host.h image_mass_table)
+    int *d_ch_row = nullptr, *d_ch_pos = nullptr, *d_id_off = nullptr, *d_id_ch = nullptr;
+    float* d_id_w = nullptr;
+    unsigned short* d_id_pos = nullptr;
+    double *d_img = nullptr, *d_dbuf = nullptr;  // the image rows; the elements' diagonal blocks [10][Epad][6]
+    bool h_current = true;           // (true before any assembly: the readers keep their own "no H yet" checks)
+    long gen = -1;                   // mf.gen of the assembly that wrote d_img and d_D from the records
+    long n_asm = 0;                  // assemblies of H since the solver was created
+    int last_form = 0;               // the last set-up summed Hc and R from: 0 the CSR H, 1 the image
+  } sr;
   // sparse direct solve (lin.method == 1): rocSOLVER re-factorisation on a host-computed ordering + factor pattern
   struct Direct {
     bool tried = false, ok = false;
@@ -474,7 +494,16 @@ int matfree_points(bool single);
 int matfree_ensure_buffer(tlfea_newton_t s);
 int matfree_ensure_records(tlfea_newton_t s);
 int launch_matfree_product(tlfea_newton_t s, const double* p, double* q, double* pq_part);
-int assemble(tlfea_newton_t s, bool fq_fresh = true);
+// lazy: the Newton loop's call -- where the solve's set-up can run from the element records (setup_records_decide) H is
+// left unassembled and the image rows of R and the fine block diagonal are written instead
+int assemble(tlfea_newton_t s, bool fq_fresh = true, bool lazy = false);
+// Every reader of s->d_H calls this first: no-op while d_H holds the H of the last assembly, else H is assembled now from
+// the point records if they are still that assembly's; fails otherwise, and inside a stream capture.
+int hessian_current(tlfea_newton_t s);
+// precond_api.hip: the solve set-up from the element records (DESIGN 3g')
+int setup_records_decide(tlfea_newton_t s, bool* on);  // after the records are claimed (mf.valid): may this assembly skip H?
+int setup_records_assemble(tlfea_newton_t s);          // the image rows of R and d_D from the records
+bool setup_records_live(tlfea_newton_t s);             // H is not assembled and d_img / d_D are those of the current records
 // precond_api.hip: the preconditioners
 struct PmgTable;  // pmg_coef.h
 int cheb_degree_eff(tlfea_newton_t s);

@@ -16,6 +16,8 @@
 #include <utility>
 #include <vector>
 
+#include "rowgroup_host.h"
+
 namespace tlfea {
 
 struct PmgHost {
@@ -471,6 +473,91 @@ inline bool pmg_galerkin_rows_build(const PmgHost& h, const RopHost& r, GalRowsH
     }
     if (bad) return false;
   }
+  return true;
+}
+
+// ---- the image rows of R assembled from the element records (DESIGN 3g') -------------------------------------------------
+// Row I of the unscaled image is sum over the children of w H[child, :], and on a straight-sided element
+// N_c + 1/2 sum_{edges at c} N_mid = L_c, the linear hat function: the image row of vertex c is what the affine assembly
+// would assemble for a row whose test function is L_c.  Here its work lists -- build_row_groups4 on the coarse problem: rows
+// = the Nc coarse nodes, pattern = R's, instances = the (element, corner) pairs, coordinates = the vertices' -- and what goes
+// with them:
+//   cmass4   [4][16] the corner's mass coefficients: cmass[c] + 1/2 sum of cmass over the three mid-edge nodes at c
+//   ch_row / ch_pos   per child t of RopHost::ch its row and the position of its OWN column in that row: where a pinned
+//                     child's penalty lands (image_pinned_kernel)
+//   id_*     the tables that let pmg_galerkin_rows_kernel read the finished image as ONE child of weight 1 per row:
+//            children id_off / id_ch = 0, 1, .., weights 1, positions 0 .. len - 1 at pos_off = f_off = RopHost::off
+struct ImageHost {
+  RowGroups4Host rg;
+  int n_inst = 0;
+  std::vector<int> ch_row, ch_pos;
+  std::vector<int> id_off, id_ch;
+  std::vector<float> id_w;
+  std::vector<unsigned short> id_pos;
+};
+inline void image_mass_table(const double* cm /*[10][16]*/, double* cm4 /*[4][16]*/) {
+  for (int c = 0; c < 4; c++)
+    for (int k = 0; k < 16; k++) {
+      double half = 0.0;
+      for (int p = 0; p < 4; p++)
+        if (p != c) half += cm[t10_mid_of(c, p) * 16 + k];
+      cm4[c * 16 + k] = cm[c * 16 + k] + 0.5 * half;
+    }
+}
+// conn: column-major [10][E]; x, y, z: reference coordinates of the fine nodes.  inst_budget / acc_budget: as
+// build_row_groups4.  False when the lists do not fit (the solver then keeps the CSR set-up).
+inline bool build_image_groups(int E, const int* conn, const double* x, const double* y, const double* z, const PmgHost& h,
+                               const RopHost& r, int inst_budget, int acc_budget, ImageHost& o) {
+  o = ImageHost();
+  const int Nc = h.Nc;
+  if (Nc <= 0 || E <= 0 || r.Nc != Nc) return false;
+  // the corner instances of every coarse row, ascending element (code = element * 10 + corner)
+  std::vector<int> n2e_off((size_t)Nc + 1, 0), n2e((size_t)4 * E);
+  for (int e = 0; e < E; e++)
+    for (int a = 0; a < 4; a++) {
+      const int v = conn[(size_t)a * E + e];
+      if (h.par0[v] != h.par1[v]) return false;
+      n2e_off[(size_t)h.par0[v] + 1]++;
+    }
+  for (int I = 0; I < Nc; I++) n2e_off[I + 1] += n2e_off[I];
+  {
+    std::vector<int> cur(n2e_off.begin(), n2e_off.end() - 1);
+    for (int e = 0; e < E; e++)
+      for (int a = 0; a < 4; a++) n2e[cur[h.par0[conn[(size_t)a * E + e]]]++] = e * 10 + a;
+  }
+  std::vector<double> cx((size_t)Nc), cy((size_t)Nc), cz((size_t)Nc);
+  for (int I = 0; I < Nc; I++) {
+    const int v = h.child[h.child_off[I]];  // the vertex itself comes first
+    cx[I] = x[v];
+    cy[I] = y[v];
+    cz[I] = z[v];
+  }
+  if (!build_row_groups4(Nc, E, conn, r.off.data(), r.cols.data(), n2e_off.data(), n2e.data(), cx.data(), cy.data(), cz.data(),
+                         o.rg, inst_budget, acc_budget))
+    return false;
+  o.n_inst = n2e_off[Nc];
+  const size_t n_ch = r.ch.size();
+  o.ch_row.resize(n_ch);
+  o.ch_pos.resize(n_ch);
+  o.id_off.resize((size_t)Nc + 1);
+  o.id_ch.resize((size_t)Nc);
+  o.id_w.assign((size_t)Nc, 1.f);
+  o.id_pos.resize((size_t)r.nnz);
+  for (int I = 0; I < Nc; I++) {
+    const int r0 = r.off[I], len = r.off[I + 1] - r0;
+    if (len > 65535) return false;
+    const int* row = r.cols.data() + r0;
+    for (int t = r.ch_off[I]; t < r.ch_off[I + 1]; t++) {
+      const int* p = std::lower_bound(row, row + len, r.ch[t]);
+      // (a child without a row in H -- a node of no element -- has no column either: nothing is ever added for it)
+      o.ch_row[t] = I;
+      o.ch_pos[t] = (p != row + len && *p == r.ch[t]) ? (int)(p - row) : 0;
+    }
+    o.id_off[I] = I;
+    o.id_ch[I] = I;
+    for (int k = 0; k < len; k++) o.id_pos[(size_t)r0 + k] = (unsigned short)k;
+  }
+  o.id_off[Nc] = Nc;
   return true;
 }
 

@@ -101,6 +101,7 @@ static int lp_convert(tlfea_newton_t s) {
   const int bits = fine_bits(s);
   TRY(lp_alloc(s, bits));
   const bool local = s->ar && s->d_own;  // rank-local preconditioner on the owned nodes
+  TRY(hessian_current(s));
   launch_lp_convert(s->stream, s->N, s->d->inc(), s->d_H, s->d_sc, local ? s->d_own : nullptr, s->d_D, s->d_B8, s->d_B1,
                     bits);
   HIP_TRY(hipGetLastError());
@@ -134,6 +135,7 @@ static int lp_build(tlfea_newton_t s, bool defer) {
       HIP_TRY(hipMalloc((void**)&s->d_blk12_err, sizeof(int)));
       HIP_TRY(hipMemsetAsync(s->d_blk12_err, 0, sizeof(int), s->stream));
     }
+    TRY(hessian_current(s));
     launch_blk12_factor(s->stream, s->N / 4, d->inc(), s->d_H, s->d_L12inv, s->d_L12inv_f, s->d_sc, s->d_Dinv_s, s->d_blk12_err);
     launch_lp_convert12(s->stream, s->N, d->inc(), s->d_H, s->d_L12inv, s->d_B8, s->d_B1, bits);
     launch_to_float(s->stream, (size_t)9 * s->N, s->d_Dinv_s, s->d_f32 + (size_t)18 * s->N);
@@ -213,6 +215,7 @@ static int estimate_lam_max(tlfea_newton_t s, const double* d_b) {
   // at config C).  Every other caller, the partitioned paths and the 12 x 12 scaling keep the CSR product.
   const bool mf = s->lmax_mf_ok && s->mf.now && s->mf.d_ybuf && lmax_matfree_env() && !b12 && !s->ar && !s->halo.on;
   s->lmax_used_mf = mf;
+  if (!mf) TRY(hessian_current(s));
   for (int k = 0; k < iters; k++) {
     TRY(halo_refresh_f64(s, 0, 1, 3, s->d_eigv));
     if (b12) launch_blk12_apply(s->stream, N / 4, s->d_L12inv_f, true, s->d_eigv, s->d_cd);
@@ -856,13 +859,140 @@ static int pmg_prepare(tlfea_newton_t s) {
   return 0;
 }
 
+// ---- solve set-up from the element records (DESIGN 3g') -----------------------------------------------------------------
+// TLFEA_SETUP_RECORDS: 0 never, 1 wherever eligible, unset = eligible and at least kFineMatfreeMinRows node rows (the size
+// from which the fine smoother takes the matrix-free form by itself: forcing that smoother on a small mesh does not bring
+// this form with it).  Read once.
+static int setup_records_env() {
+  static const int m = env_tristate("TLFEA_SETUP_RECORDS");
+  return m;
+}
+// Budgets of the coarse rows' groups (build_row_groups4): a vertex row of a tet mesh has ~24 corner instances, so a group
+// of 32 instances would hold one row and fill its second pass to a half; 48 pairs two rows into three full passes.
+// TLFEA_IMG_INST / TLFEA_IMG_ACC (tools: the sweep of profiles/setup_records.txt).
+static int image_inst_budget() {
+  static const int v = std::max(16, env_int("TLFEA_IMG_INST", 48));
+  return v;
+}
+static int image_acc_budget() {
+  static const int v = std::max(64, env_int("TLFEA_IMG_ACC", 1536));
+  return v;
+}
+// the coarse work lists, the one-child tables and the buffers: once per mesh, after pmg_prepare
+static int setup_records_prepare(tlfea_newton_t s) {
+  auto& r = s->sr;
+  if (r.tried) return 0;
+  r.tried = true;
+  tlfea_t10_t d = s->d;
+  auto& m = s->pmg;
+  if (!m.ok || !m.rop.ok || !m.rows.ok || !s->d_cmass) return 0;
+  // the hierarchy's host lists are not kept: build them again (integer work, once)
+  PmgHost h;
+  RopHost ro;
+  ImageHost ih;
+  if (!pmg_build(d->N, d->E, d->h_conn.data(), d->h_off.data(), d->h_cols.data(), h)) return 0;
+  if (!pmg_restrict_op_build(d->N, d->h_off.data(), d->h_cols.data(), h, ro)) return 0;
+  const size_t N = (size_t)d->N;
+  if (!build_image_groups(d->E, d->h_conn.data(), d->h_X0.data(), d->h_X0.data() + N, d->h_X0.data() + 2 * N, h, ro,
+                          image_inst_budget(), image_acc_budget(), ih))
+    return 0;
+  if (ro.nnz != m.rop.nnz || assemble_affine_lds_max(ih.rg.acc_max) > device_lds_limit()) return 0;
+  const std::vector<int>* src[5] = {&ih.rg.g_pass_off, &ih.rg.pt, &ih.rg.gr_info, &ih.rg.gi_head, &ih.rg.gi_ent};
+  for (int k = 0; k < 5; k++) {
+    TRY(dmalloc(&r.d_rg[k], src[k]->size() + 4));
+    HIP_TRY(hipMemcpy(r.d_rg[k], src[k]->data(), src[k]->size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  r.rg = RowGroups4{ih.rg.G(), std::max(1, ih.n_inst), ih.rg.acc_max, r.d_rg[0], reinterpret_cast<const int4*>(r.d_rg[1]),
+                    reinterpret_cast<const int4*>(r.d_rg[2]), reinterpret_cast<const int2*>(r.d_rg[3]),
+                    reinterpret_cast<const int2*>(r.d_rg[4])};
+  r.passes = (int)(ih.rg.pt.size() / 4);
+  r.n_ch = (int)ih.ch_row.size();
+  double cm[160], cm4[64];
+  HIP_TRY(hipMemcpy(cm, s->d_cmass, sizeof cm, hipMemcpyDeviceToHost));
+  image_mass_table(cm, cm4);
+  TRY(dmalloc(&r.d_cmass4, 64));
+  HIP_TRY(hipMemcpy(r.d_cmass4, cm4, sizeof cm4, hipMemcpyHostToDevice));
+  TRY(upload_vec(&r.d_ch_row, ih.ch_row)); TRY(upload_vec(&r.d_ch_pos, ih.ch_pos));
+  TRY(upload_vec(&r.d_id_off, ih.id_off)); TRY(upload_vec(&r.d_id_ch, ih.id_ch));
+  TRY(upload_vec(&r.d_id_w, ih.id_w)); TRY(upload_vec(&r.d_id_pos, ih.id_pos));
+  TRY(dmalloc(&r.d_img, (size_t)9 * ro.nnz + 9));
+  TRY(dmalloc(&r.d_dbuf, (size_t)d->Epad * 6 * kNN));
+  r.ok = true;
+  if (s->verbose)
+    std::printf("set-up from the element records: %d coarse rows in %d groups, %d passes of %d instances, accumulator %d doubles, "
+                "image %.1f MB\n", ro.Nc, r.rg.G, r.passes, ih.n_inst, r.rg.acc_max, 72.0 * ro.nnz / 1048576.0);
+  return 0;
+}
+// What the form needs beyond the records being claimed: everything of the solve runs from the records (the CG's product,
+// the fine smoother, the lambda_max product), R is built in the pass that sums Hc, one GPU, the iterative solve.  Terms
+// added to H after the fused launch and per-element materials are ruled out by mf.valid (claim_records).
+static bool setup_records_eligible(tlfea_newton_t s) {
+  if (setup_records_env() == 0 || (setup_records_env() < 0 && s->N < kFineMatfreeMinRows)) return false;
+  if (s->lin.method != 0 || s->spmv32_every >= 2 || !lmax_matfree_env() || s->trace) return false;
+  if (!matfree_chosen(s) || !fine_matfree_possible(s)) return false;
+  const auto& m = s->pmg;
+  return m.ok && pmg_rop_on(s) && m.rows.ok && m.rop.stream_cap > 0;
+}
+int tlfea::setup_records_decide(tlfea_newton_t s, bool* on) {
+  *on = false;
+  if (setup_records_env() == 0 || (setup_records_env() < 0 && s->N < kFineMatfreeMinRows)) return 0;
+  if (!matfree_chosen(s) || !fine_matfree_possible(s)) return 0;
+  TRY(pmg_prepare(s));
+  if (!setup_records_eligible(s)) return 0;
+  TRY(matfree_ensure_buffer(s));
+  if (!s->mf.compact) return 0;
+  TRY(setup_records_prepare(s));
+  *on = s->sr.ok;
+  return 0;
+}
+bool tlfea::setup_records_live(tlfea_newton_t s) {
+  const auto& r = s->sr;
+  return !r.h_current && r.ok && s->mf.valid && r.gen == s->mf.gen && setup_records_eligible(s) && s->mf.compact;
+}
+// In H's place: the image rows of R (with the pinned children's penalties) and the fine block diagonal d_D, from the
+// records the assembly has just claimed.  The packed fp64 records are the CG product's: packed here, once per assembly.
+int tlfea::setup_records_assemble(tlfea_newton_t s) {
+  tlfea_t10_t d = s->d;
+  auto& r = s->sr;
+  const auto& f = s->mf;
+  const auto& ro = s->pmg.rop;
+  TRY(matfree_ensure_records(s));
+  launch_assemble_image(s->stream, d->view(), d->mat, s->prm.time_step, r.rg, s->av, s->d_Fq, r.d_cmass4,
+                        d->mass_rho0 > 0.0 ? d->mass_rho0 : 0.0, r.d_img);
+  launch_image_pinned(s->stream, r.n_ch, ro.d_ch, ro.d_ch_w, r.d_ch_row, r.d_ch_pos, ro.d_off, d->d_off, f.fixed, s->d_nw,
+                      f.penalty, r.d_img);
+  launch_records_diag(s->stream, d->view(), matfree_points(false), f.d_gp, f.d_Fp, f.mc, s->N, d->inc(), f.fixed, s->d_nw,
+                      f.penalty, r.d_dbuf, s->d_D);
+  r.gen = f.gen;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // Galerkin operators of the current H: Hc = P^T H P, H3 = P2^T Hc P2
 // The one place that picks the kernel.  T10 with the row lists (pmg_prepare: a property of the mesh): the row kernel --
 // with_R in the same pass as the streamed build of R (a matrix-free set-up), else alone; ANCF and meshes whose lists do
 // not fit: the gather.  setup: the call of a preconditioner set-up, which wants the diagonal blocks in vertex.d_D too;
 // returns whether they were written (the read-backs leave d_D alone).
-static bool vertex_galerkin(tlfea_newton_t s, bool setup = false, bool with_R = false) {
+// image: the rows of sr.d_img, assembled from the element records, stand in for the children's rows of H -- the same
+// kernels through a second set of tables, one child of weight 1 per row whose "fine row" is the image row itself
+// (hc_form 4; a set-up with R only).
+static bool vertex_galerkin(tlfea_newton_t s, bool setup = false, bool with_R = false, bool image = false) {
   auto& m = s->pmg;
+  if (image) {
+    const auto& r = m.rop;
+    const auto& g = m.rows;
+    const auto& q = s->sr;
+    PmgRows a;
+    a.r_off = r.d_off; a.r_cols = r.d_cols; a.pos_off = r.d_off; a.con_pos = q.d_id_pos;
+    a.ch_off = q.d_id_off; a.ch = q.d_id_ch; a.ch_w = q.d_id_w; a.f_off = r.d_off; a.Hval = q.d_img;
+    a.g_row = g.d_row; a.g_off = g.d_off; a.g_pos = g.d_pos; a.g_w = g.d_w;
+    a.c_off = m.vertex.d_off; a.c_upper = m.d_c_upper; a.c_mirror = m.d_c_mirror; a.cblk_row = m.d_cblk_row;
+    a.Hc = m.vertex.d_H; a.D = m.vertex.d_D;
+    a.sc_f = s->d_sc; a.R8 = r.d_R8; a.R1 = r.d_R1;
+    launch_pmg_galerkin_rows(s->stream, m.vertex.N, g.cap, a, true, g.d_long_rows, g.n_long, g.ws_stride, g.ws_rows, g.d_ws);
+    m.hc_form = 4;
+    return true;
+  }
   if (!m.rows.ok) {
     launch_pmg_galerkin(s->stream, m.n_upper, m.d_c_upper, m.d_c_mirror, m.vertex.d_off, m.d_cblk_row, m.d_con_off,
                         m.d_con_base, m.d_con_deg, m.d_con_w, s->d_H, m.vertex.d_H);
@@ -911,8 +1041,13 @@ static int pmg_build_level(tlfea_newton_t s) {
     TRY(fine_matfree_choose(s));
   }
   const bool fused = rop && s->fmf.now && m.rop.stream_cap > 0;
+  // H was left unassembled (DESIGN 3g'): the fused pass runs on the image rows; a set-up that does not take the matrix-free
+  // smoother and the streamed build of R after all gets H now and finishes on the CSR path
+  const bool image = fused && setup_records_live(s);
+  if (!image) TRY(hessian_current(s));
+  s->sr.last_form = image ? 1 : 0;
   TRY(V.ensure_copy(bits));
-  if (!vertex_galerkin(s, true, fused)) launch_extract_diag(s->stream, V.N, V.inc(), V.d_H, V.d_D);
+  if (!vertex_galerkin(s, true, fused, image)) launch_extract_diag(s->stream, V.N, V.inc(), V.d_H, V.d_D);
   // multi-GPU: Hc = sum over ranks of P^T H_r P -- the diagonal blocks of boundary vertices are partial per rank
   if (s->ar) TRY(iface_sum_lvl(s, m.iface(), V.d_D, 9));
   // overlapping partition: rows of the outermost ghost layer are incomplete -- their diagonal blocks (hence the scaling of
@@ -1183,9 +1318,14 @@ int tlfea::precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
     TRY(refuse_empty_rows(s, "preconditioner set-up"));  // extract_dinv_kernel / extract_diag read every row's diagonal block
     const bool lp = cheb_bits_eff(s) != 64;
     s->lp_scaled = s->lp_current = false;  // the stored copy belonged to the last set-up's H
+    // H left unassembled by the Newton loop (DESIGN 3g'): d_D is already the block diagonal of the records' H
+    // (setup_records_assemble); a set-up that can no longer run from the records gets H first
+    const bool rec = lp && setup_records_live(s);
+    if (!rec) TRY(hessian_current(s));
+    s->sr.last_form = 0;
     if (s->ar || lp) {
       // diagonal blocks of partition-boundary nodes are partial per rank: sum them before inverting
-      launch_extract_diag(s->stream, N, d->inc(), s->d_H, s->d_D);
+      if (!rec) launch_extract_diag(s->stream, N, d->inc(), s->d_H, s->d_D);
       TRY(iface_sum(s, s->d_D, 9));
       // overlapping partition: the outermost ghost layer's rows are incomplete -- its diagonal blocks (the scaling of its
       // columns in every complete row) come from their owners
@@ -1247,6 +1387,7 @@ extern "C" int tlfea_newton_pmg_retrieve(tlfea_newton_t s, int* par0, int* par1,
   int nc = 0, nnz = 0;
   TRY(tlfea_newton_pmg_sizes(s, &nc, &nnz));
   auto& m = s->pmg;
+  TRY(hessian_current(s));
   vertex_galerkin(s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1269,6 +1410,27 @@ extern "C" int tlfea_newton_pmg_retrieve_built(tlfea_newton_t s, double* Hc, int
   HIP_TRY(hipStreamSynchronize(s->stream));
   D2H(Hc, m.vertex.d_H, (size_t)9 * m.vertex.nnz);
   *form = m.hc_form;
+  return 0;
+}
+// the fine block diagonal [N][9] as the last stage-0 set-up (or the last assembly from the element records) left it
+extern "C" int tlfea_newton_get_block_diagonal(tlfea_newton_t s, double* D) {
+  if (!s || !D) return fail("tlfea_newton_get_block_diagonal: null argument");
+  if (!s->d_D) return fail("tlfea_newton_get_block_diagonal: this solver keeps no block diagonal (no low-precision set-up)");
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  D2H(D, s->d_D, (size_t)9 * s->N);
+  return 0;
+}
+// the image rows of R as the last assembly from the element records left them (DESIGN 3g'), nothing recomputed
+extern "C" int tlfea_newton_get_setup_image(tlfea_newton_t s, double* image, long long* len) {
+  if (!s || !len) return fail("tlfea_newton_get_setup_image: null argument");
+  const auto& r = s->sr;
+  if (!r.ok || !r.d_img || r.gen < 0)
+    return fail("tlfea_newton_get_setup_image: no Newton iteration of this solver has been set up from the element records");
+  *len = (long long)9 * s->pmg.rop.nnz;
+  if (image) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    D2H(image, r.d_img, (size_t)9 * s->pmg.rop.nnz);
+  }
   return 0;
 }
 
@@ -1370,6 +1532,7 @@ extern "C" int tlfea_newton_pmg3_retrieve(tlfea_newton_t s, int* agg, double* rv
   TRY(tlfea_newton_pmg_sizes(s, &nc, &nnz));
   auto& g = s->pmg.agg;
   if (!g.ok) return fail("p-multigrid: no third level on this mesh");
+  TRY(hessian_current(s));
   vertex_galerkin(s);
   level3_galerkin(s);
   HIP_TRY(hipGetLastError());
@@ -1471,6 +1634,7 @@ extern "C" int tlfea_newton_apply_preconditioner_block(tlfea_newton_t s, int m, 
   if (!s || !R || !Z) return fail("tlfea_newton_apply_preconditioner: null argument");
   if (m < 1) return fail("tlfea_newton_apply_preconditioner: needs at least one vector");
   if (!s->d_H) return fail("tlfea_newton_apply_preconditioner: no assembled H");
+  TRY(hessian_current(s));  // the hook's set-up and its operator are those of the CSR H
   if (dist_on(s)) return fail("tlfea_newton_apply_preconditioner: not available on a partitioned mesh (set_interface / set_halo is active)");
   if (s->lin.method == 1) return fail("tlfea_newton_apply_preconditioner: method = 1 (sparse direct) has no preconditioner");
   const size_t n = 3 * (size_t)s->N;

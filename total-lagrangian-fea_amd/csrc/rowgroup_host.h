@@ -189,11 +189,16 @@ inline int t10_mid_of(int a, int b) {  // local index of the mid-edge node of ve
   return tab[a][b];
 }
 
+// inst_budget / acc_budget: instances and accumulator doubles a group may hold; 0 = the fine assembly's (TLFEA_AF_INST,
+// TLFEA_AF_ACC, read once per process).  The rows need not be the nodes of the mesh: the image rows of R (pmg_host.h
+// build_image_groups) pass the coarse rows, R's pattern and the corner instances.
 inline bool build_row_groups4(int N, int E, const int* conn, const int* off, const int* cols, const int* n2e_off,
-                              const int* n2e, const double* x, const double* y, const double* z, RowGroups4Host& out) {
+                              const int* n2e, const double* x, const double* y, const double* z, RowGroups4Host& out,
+                              int inst_budget = 0, int acc_budget = 0) {
   constexpr int S = 10, kMaxRows = 16, kPassInst = 16;
-  static const int kInstBudget = std::getenv("TLFEA_AF_INST") ? std::atoi(std::getenv("TLFEA_AF_INST")) : 32;
-  static const int kAccBudget = std::getenv("TLFEA_AF_ACC") ? std::atoi(std::getenv("TLFEA_AF_ACC")) : 1024;  // doubles
+  static const int kInstDefault = std::getenv("TLFEA_AF_INST") ? std::atoi(std::getenv("TLFEA_AF_INST")) : 32;
+  static const int kAccDefault = std::getenv("TLFEA_AF_ACC") ? std::atoi(std::getenv("TLFEA_AF_ACC")) : 1024;  // doubles
+  const int kInstBudget = inst_budget > 0 ? inst_budget : kInstDefault, kAccBudget = acc_budget > 0 ? acc_budget : kAccDefault;
   if (N <= 0 || E <= 0) return false;
   std::vector<std::pair<uint64_t, int>> key;
   morton_order(N, x, y, z, key);

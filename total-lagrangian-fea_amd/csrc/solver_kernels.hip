@@ -1958,6 +1958,30 @@ void launch_pmg_galerkin_rows(hipStream_t s, int Nc, int cap, const PmgRows& a, 
       hipLaunchKernelGGL(pmg_galerkin_long_rows_kernel<false>, dim3((n + 3) / 4), b, 0, s, n, long_rows + k, ws_stride, ws, a);
   }
 }
+// Image rows assembled from the element records (launch_assemble_image) carry no pinned rows' penalty: a pinned child i of
+// row I adds w_i nw_i penalty to the diagonal of its own column's block, as assemble_affine_kernel does in H[i, i] (a pinned
+// node without a row in H has none).  (I, i) -> one block: no two threads meet.
+__global__ void image_pinned_kernel(int n_ch, const int* __restrict__ ch, const float* __restrict__ ch_w,
+                                    const int* __restrict__ ch_row, const int* __restrict__ ch_pos, const int* __restrict__ r_off,
+                                    const int* __restrict__ f_off, const int* __restrict__ fixed_slot,
+                                    const double* __restrict__ nw, double penalty, double* __restrict__ image) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_ch) return;
+  const int i = ch[t];
+  if (fixed_slot[i] < 0 || f_off[i + 1] == f_off[i]) return;
+  const int I = ch_row[t], r0 = r_off[I], len = r_off[I + 1] - r0;
+  const double pen = (double)ch_w[t] * ((nw ? nw[i] : 1.0) * penalty);
+  double* row = image + (size_t)9 * r0 + 3 * ch_pos[t];
+#pragma unroll
+  for (int d = 0; d < 3; d++) row[(size_t)d * 3 * len + d] += pen;
+}
+void launch_image_pinned(hipStream_t s, int n_ch, const int* ch, const float* ch_w, const int* ch_row, const int* ch_pos,
+                         const int* r_off, const int* f_off, const int* fixed_slot, const double* nw, double penalty,
+                         double* image) {
+  if (n_ch <= 0 || !fixed_slot) return;
+  hipLaunchKernelGGL(image_pinned_kernel, dim3((n_ch + 255) / 256), dim3(256), 0, s, n_ch, ch, ch_w, ch_row, ch_pos, r_off, f_off,
+                     fixed_slot, nw, penalty, image);
+}
 void launch_pmg_rop_build(hipStream_t s, int Nc, const int* r_off, const int* con_off, const int* con_blk,
                           const unsigned char* con_ord, const int* ch_off, const int* ch, const float* ch_w, const void* B8,
                           const void* B1, int bits, const double* sc_f, const double* sc_c, void* R8, float* R1) {

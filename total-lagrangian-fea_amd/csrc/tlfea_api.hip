@@ -1069,6 +1069,13 @@ extern "C" int tlfea_newton_destroy(tlfea_newton_t s) {
   if (s->fmf.d_ss) (void)hipFree(s->fmf.d_ss);
   for (void* p : s->mf.d_cp)
     if (p) (void)hipFree(p);
+  {
+    auto& r = s->sr;
+    void* rp[] = {r.d_rg[0], r.d_rg[1], r.d_rg[2], r.d_rg[3], r.d_rg[4], r.d_cmass4, r.d_ch_row, r.d_ch_pos, r.d_id_off, r.d_id_ch,
+                  r.d_id_w, r.d_id_pos, r.d_img, r.d_dbuf};
+    for (void* p : rp)
+      if (p) (void)hipFree(p);
+  }
   direct_destroy(s);
   for (auto& e : s->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1376,7 +1383,21 @@ extern "C" int tlfea_newton_retrieve_hessian_csr(tlfea_newton_t s, int* ro, int*
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
   if (ro) std::copy(s->h_row_offsets.begin(), s->h_row_offsets.end(), ro);
   if (ci) std::copy(s->h_col_indices.begin(), s->h_col_indices.end(), ci);
-  if (val) D2H(val, s->d_H, s->h_nnz);
+  if (val) {
+    TRY(hessian_current(s));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    D2H(val, s->d_H, s->h_nnz);
+  }
+  return 0;
+}
+// What the last Newton assembly and solve set-up ran on (DESIGN 3g'): out[0] = 1 the last p-multigrid set-up summed Hc and
+// R from the image rows assembled from the element records, 0 from the CSR H; out[1] = assemblies of H since the solver
+// was created; out[2] = 1 d_H holds the H of the last assembly.
+extern "C" int tlfea_newton_get_setup_form(tlfea_newton_t s, long long* out3) {
+  if (!s || !out3) return fail("tlfea_newton_get_setup_form: null argument");
+  out3[0] = s->sr.last_form;
+  out3[1] = s->sr.n_asm;
+  out3[2] = s->sr.h_current ? 1 : 0;
   return 0;
 }
 
@@ -1897,15 +1918,28 @@ static int fq_slots(tlfea_newton_t s) {
   return w;
 }
 static void fill_mass_shape(tlfea_newton_t s, MassTerm& mt);
-static void launch_fused(tlfea_newton_t s) {
+// the fused launch itself: H of the point records in d_Fq, by the form of the moment
+static void launch_fused_kernel(tlfea_newton_t s) {
   tlfea_t10_t d = s->d;
   const tlfea_newton_params& p = s->prm;
   const int* fixed = pinned_on(s) ? d->d_fixed_slot : nullptr;
-  s->mf.valid = false;
-  if (affine_now(s)) {
+  if (affine_now(s))
     launch_assemble_affine(s->stream, d->view(), d->mat, p.time_step, s->rg4, s->av, s->d_Fq, s->d_cmass,
                            d->d_emat ? 1.0 : (d->mass_rho0 > 0.0 ? d->mass_rho0 : 0.0), fixed, s->d_nw,
                            p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
+  else
+    launch_assemble_direct(s->stream, d->view(), d->mat, p.time_step, s->rg, s->d_Fq, d->d_mval, fixed, s->d_nw,
+                           p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
+  s->sr.h_current = true;
+  s->sr.n_asm++;
+}
+// The affine assembly claims the point records: the matrix-free passes (and the set-up from the records) apply the H of
+// THESE records and scalars, whether or not that H is on the device.
+static void claim_records(tlfea_newton_t s) {
+  tlfea_t10_t d = s->d;
+  const tlfea_newton_params& p = s->prm;
+  const int* fixed = pinned_on(s) ? d->d_fixed_slot : nullptr;
+  {
     // The matrix-free product applies THIS H: the same records and the same scalars, kept as they are now.  Terms that
     // the callers add to H after this launch (general linear constraints, obstacle blocks) and per-element materials
     // are not reproduced by the element map: such an H is served by the CSR kernel only.
@@ -1928,9 +1962,25 @@ static void launch_fused(tlfea_newton_t s) {
     f.penalty = p.time_step * p.time_step * p.rho;
     f.valid = !d->d_emat && !lincons_on(s) && d->obs.n == 0;
     f.gen++;
-  } else
-    launch_assemble_direct(s->stream, d->view(), d->mat, p.time_step, s->rg, s->d_Fq, d->d_mval, fixed, s->d_nw,
-                           p.time_step * p.time_step * p.rho, s->d_H, d->d_emat);
+  }
+}
+static void launch_fused(tlfea_newton_t s) {
+  s->mf.valid = false;
+  launch_fused_kernel(s);
+  if (affine_now(s)) claim_records(s);
+}
+int tlfea::hessian_current(tlfea_newton_t s) {
+  auto& r = s->sr;
+  if (r.h_current) return 0;
+  if (!affine_now(s) || !s->mf.valid || r.gen != s->mf.gen)
+    return fail("the Hessian of the last Newton iteration was not assembled (its solve was set up from the element records) and "
+                "the point records are no longer those of that assembly: assemble again (tlfea_newton_assemble_hessian)");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail("the Hessian is not assembled inside a stream capture (whoever reads it must call hessian_current before)");
+  launch_fused_kernel(s);  // the same kernel on the same records: the H an eager assembly would have left
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 static int ensure_kbuf(tlfea_newton_t s) {
   if (s->d_Kbuf) return 0;
@@ -2169,7 +2219,7 @@ static int eval_gradient(tlfea_newton_t s, double* norm_g) {
 
 // fq_fresh: the per-point F buffer holds the F of the CURRENT coordinates (true right after eval_gradient, which is
 // how the Newton loop calls it); a stand-alone assembly refreshes it with a residual launch first
-int tlfea::assemble(tlfea_newton_t s, bool fq_fresh) {
+int tlfea::assemble(tlfea_newton_t s, bool fq_fresh, bool lazy) {
   tlfea_t10_t d = s->d;
   const bool after_grad = fq_fresh;  // the obstacle buffers hold the current coordinates' blocks
   {
@@ -2186,7 +2236,24 @@ int tlfea::assemble(tlfea_newton_t s, bool fq_fresh) {
     StageTimer t(s, 3);
     if (!fq_fresh)
       launch_residual_newton(s, s->d_Fq, nullptr);
-    launch_fused(s);
+    // The Newton loop's assembly, where nothing of the solve would read the CSR H (DESIGN 3g'): the records are claimed as
+    // the assembly claims them, and the image rows of R and the fine block diagonal are written in H's place.  Whoever
+    // needs H after all gets it from hessian_current().
+    if (lazy && affine_now(s)) {
+      s->mf.valid = false;
+      claim_records(s);
+      bool rec = false;
+      TRY(setup_records_decide(s, &rec));
+      if (rec) {
+        s->sr.h_current = false;
+        TRY(setup_records_assemble(s));
+        HIP_TRY(hipGetLastError());
+        t.stop();
+        return 0;
+      }
+      launch_fused_kernel(s);
+    } else
+      launch_fused(s);
     if (lincons_on(s))  // + h^2 rho J^T J  (SyncedNewton.cu:292-341)
       launch_lin_constraint_hessian(s->stream, 3 * s->N, d->d_jtoff, d->d_jtcol, d->d_jtval, d->d_joff, d->d_jcol,
                                     d->d_jval, d->d_off, d->d_cols, p.time_step * p.time_step * p.rho, s->d_H);
@@ -2206,6 +2273,8 @@ int tlfea::assemble(tlfea_newton_t s, bool fq_fresh) {
     launch_ancf_obstacles_tangent(s, after_grad);
     launch_assemble_rows(s->stream, s->N, d->S, d->maxdeg, d->inc(), s->d_Kbuf, d->d_mval, 1.0 / p.time_step,
                          pinned ? d->d_fixed_slot : nullptr, s->d_nw, p.time_step * p.time_step * p.rho, s->d_H);
+    s->sr.h_current = true;
+    s->sr.n_asm++;
     if (lincons_on(s))  // + h^2 rho J^T J  (SyncedNewton.cu:292-341)
       launch_lin_constraint_hessian(s->stream, 3 * s->N, d->d_jtoff, d->d_jtcol, d->d_jtval, d->d_joff, d->d_jcol,
                                     d->d_jval, d->d_off, d->d_cols, p.time_step * p.time_step * p.rho, s->d_H);
@@ -2281,6 +2350,9 @@ extern "C" int tlfea_newton_assemble_hessian(tlfea_newton_t s) {
 // out[0] residual, [1] tangent blocks, [2] row assembly, [3] CG SpMV, [4] Chebyshev step (SpMV + vector updates).
 extern "C" int tlfea_newton_time_kernels(tlfea_newton_t s, int reps, double* out_ms4) {  // out: 6 entries
   TRY(tlfea_newton_analyze_hessian_sparsity(s));
+  // the CSR launches below read H: where the last Newton iteration left it unassembled and its records have moved since,
+  // a measurement takes the H of the current coordinates
+  if (!s->sr.h_current && hessian_current(s)) TRY(assemble(s, /*fq_fresh=*/false));
   tlfea_t10_t d = s->d;
   const tlfea_newton_params& p = s->prm;
   if (reps < 1) reps = 1;
@@ -2421,7 +2493,7 @@ extern "C" int tlfea_newton_iteration(tlfea_newton_t s, double* norm_g, int* ite
   double ng = 0.0;
   TRY(eval_gradient(s, &ng));
   launch_axpy_neg(s->stream, 3 * s->N, s->d_g, s->d_b);  // b = -g
-  TRY(assemble(s));
+  TRY(assemble(s, true, true));
   int it = 0;
   TRY(pcg(s, s->d_b, s->d_dv, &it, nullptr));
   TRY(newton_update(s));
@@ -2486,7 +2558,7 @@ extern "C" int tlfea_newton_solve(tlfea_newton_t s) {
           break;
         }
         launch_axpy_neg(s->stream, n, s->d_g, s->d_b);                       // r = -g  (:494-502)
-        TRY(assemble(s));                                                    // (:1080-1097)
+        TRY(assemble(s, true, true));                                                    // (:1080-1097)
         int iters = 0;
         int rc = pcg(s, s->d_b, s->d_dv, &iters, nullptr);                   // cuDSS factor+solve (:1103-1114)
         pcg_total += iters;

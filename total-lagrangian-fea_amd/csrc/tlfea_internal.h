@@ -161,6 +161,27 @@ void launch_assemble_affine(hipStream_t s, const ElemView& m, const Material& ma
                             double rho0 /*density of the assembled mass matrix, 0 = none (per-element: 1 = the
                                            records' kEmRhoM)*/, const int* fixed_slot,
                             const double* nw, double penalty, double* Hval, const double* emat = nullptr);
+// Solve set-up from the element records (DESIGN 3g'): the unscaled image rows of R, (P^T H)[I, :] = sum over the children
+// of w H[child, :], assembled as rows of their own -- the row function of coarse node I is the linear hat function of its
+// vertex -- in H's row layout [d][len][3] at 9 r_off[I].  rg: build_row_groups4 on R's pattern with the (element, corner)
+// instances; cmass4 [4][16]: cmass of the corner plus half that of its three mid-edge nodes (uniform material only).
+void launch_assemble_image(hipStream_t s, const ElemView& m, const Material& mat, double h, const RowGroups4& rg,
+                           const AffineView& av, const double* Fq16, const double* cmass4, double rho0, double* image);
+// what the rows-out phase of the fine assembly adds to a pinned child's diagonal block, times the child's weight: one thread
+// per (row, child) of R's child lists (ch_row: the row, ch_pos: position of the child's column in it); each entry has one writer
+void launch_image_pinned(hipStream_t s, int n_ch, const int* ch, const float* ch_w, const int* ch_row, const int* ch_pos,
+                         const int* r_off, const int* f_off, const int* fixed_slot, const double* nw, double penalty,
+                         double* image);
+template <typename R>
+struct MatfreeCoefT;
+struct ElemDiagMass {
+  double c[kNN];  // rho / h x sum_q w_q N_a(q)^2
+};
+// the fine block diagonal D [N][9] from the packed fp64 records (np stored points): the element's ten diagonal blocks
+// into dbuf [10][Epad][6], then the per-node sum in ascending element order + the pinned rows' penalty
+void launch_records_diag(hipStream_t s, const ElemView& m, int np, const double* gp, const double* Fp,
+                         const MatfreeCoefT<double>& mc, int N, const Incidence& inc, const int* fixed_slot, const double* nw,
+                         double penalty, double* dbuf, double* D);
 // Matrix-free product q = H p on affine elements (one material): the scalars of the assembled H, as
 // launch_assemble_affine forms them, and the mass rule (N_j at the rule's points in the rule's order, its weights).
 template <typename R>
@@ -230,6 +251,7 @@ struct AssemblyLaunchForm {
 };
 AssemblyLaunchForm assemble_direct_form(const RowGroups& rg, const Material& mat, bool per_element);
 AssemblyLaunchForm assemble_affine_form(const RowGroups4& rg, bool per_element);
+AssemblyLaunchForm assemble_image_form(const RowGroups4& rg);  // launch_assemble_image
 // the largest dynamic LDS any instantiation of a fused form takes for an accumulator of acc_max doubles (the material,
 // hence the instantiation, may be switched between solves), and what assemble_rows_kernel takes for a longest row
 size_t assemble_direct_lds_max(int acc_max);

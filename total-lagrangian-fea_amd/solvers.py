@@ -156,6 +156,29 @@ class SyncedNewtonSolver:
         check(self._lib.tlfea_newton_pmg_retrieve_built(self._h, dp(Hc), C.byref(form)))
         return Hc, form.value
 
+    def GetSetupForm(self):
+        """dict(records, h_assemblies, h_current): 1 if the last p-multigrid set-up ran on the image rows of R assembled from
+        the element records (TLFEA_SETUP_RECORDS), assemblies of H since the solver was created, and whether the H on the
+        device is the one of the last assembly"""
+        out = (C.c_longlong * 3)()
+        check(self._lib.tlfea_newton_get_setup_form(self._h, out))
+        return dict(records=int(out[0]), h_assemblies=int(out[1]), h_current=bool(out[2]))
+
+    def RetrieveBlockDiagonal(self):
+        """[N, 3, 3]: the fine level's diagonal blocks as the last set-up (or assembly from the records) left them (test hook)"""
+        D = np.zeros(9 * self.n_coef)
+        check(self._lib.tlfea_newton_get_block_diagonal(self._h, dp(D)))
+        return D.reshape(-1, 3, 3)
+
+    def RetrieveSetupImage(self):
+        """the image rows of R of the last assembly from the element records, row I in H's row layout [d][len][3] at
+        9 off[I] of RetrieveRestrictOp (test hook)"""
+        n = C.c_longlong()
+        check(self._lib.tlfea_newton_get_setup_image(self._h, None, C.byref(n)))
+        img = np.zeros(max(1, n.value))
+        check(self._lib.tlfea_newton_get_setup_image(self._h, dp(img), C.byref(n)))
+        return img[:n.value]
+
     def GetRestrictOpInfo(self):
         """dict(active, n_coarse, blocks, contributions, fine_blocks, fine_bits) of the restricted fine operator
         R = S_c P^T S_f^-1 Hs as the last preconditioner set-up left it (active 0: the cycle runs the fine residual pass)"""
