@@ -1,5 +1,5 @@
-// data_handle.h -- the data object behind tlfea_t10_t (any element kind) and what of the units split off tlfea_api.hip
-// (loads_api.hip, obstacle_api.hip) the rest of the host code calls.  Private to csrc/.
+// data_handle.h -- the data object behind tlfea_t10_t (any element kind; its C-ABI is data_api.hip) and what of the units
+// beside it (loads_api.hip, obstacle_api.hip) the rest of the host code calls.  Private to csrc/.
 #pragma once
 #include "api_common.h"
 #include "t10_load_host.h"

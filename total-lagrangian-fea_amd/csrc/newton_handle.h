@@ -1,6 +1,6 @@
 // newton_handle.h -- the Newton solver object behind tlfea_newton_t with the level types of its preconditioner, and the
-// functions of tlfea_api.hip, precond_api.hip, cg_api.hip, adjoint_api.hip, direct_api.hip and rccl_api.hip that another
-// unit calls.
+// functions of tlfea_api.hip, partition_api.hip, precond_api.hip, cg_api.hip, adjoint_api.hip, direct_api.hip and
+// rccl_api.hip that another unit calls.
 // Included by the host units that take a tlfea_newton_t apart; private to csrc/.
 #pragma once
 #include <map>
@@ -464,7 +464,7 @@ struct LamKeep {
   }
 };
 
-// tlfea_api.hip: the partition plumbing
+// partition_api.hip: the partition plumbing
 bool halo_graph_wanted();
 void halo_graph_give_up();  // RCCL cannot be captured / replayed here: eager launches for the rest of the process
 int halo_dr(tlfea_newton_t s);
@@ -481,6 +481,7 @@ int parts_sum(tlfea_newton_t s, double* d_a, double* d_b = nullptr);
 int device_sumsq_async(tlfea_newton_t s, const double* d_vec, const double* w, int n);
 int fetch_scalar(tlfea_newton_t s, const double* d_src, double* out);
 int fetch_scalar2(tlfea_newton_t s, const double* d_src, double* out0, double* out1);
+int device_norm(tlfea_newton_t s, const double* d_vec, const double* w, int n, double* out);
 // tlfea_api.hip: the Newton solver's element stage and the fp64 matrix-free product
 int refuse_empty_rows(tlfea_newton_t s, const char* who);
 int sync_constraints(tlfea_newton_t s);

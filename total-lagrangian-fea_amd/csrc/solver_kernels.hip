@@ -2683,20 +2683,20 @@ __global__ __launch_bounds__(256) void halo_unpack_kernel(int n, const int* __re
   }
 }
 static int halo_grid(size_t n) { return (int)std::max<size_t>(1, std::min<size_t>(2048, (n + 255) / 256)); }
-void launch_halo_pack_f64(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* a, const double* b,
-                          const double* c, double* msg) {
+void launch_halo_pack(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* a, const double* b,
+                      const double* c, double* msg) {
   if (n > 0) hipLaunchKernelGGL(halo_pack_kernel<double>, dim3(halo_grid((size_t)n * dim * nvec)), dim3(256), 0, s, n, idx, dim, nvec, a, b, c, msg);
 }
-void launch_halo_unpack_f64(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* msg, double* a, double* b,
-                            double* c) {
+void launch_halo_unpack(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* msg, double* a, double* b,
+                        double* c) {
   if (n > 0) hipLaunchKernelGGL(halo_unpack_kernel<double>, dim3(halo_grid((size_t)n * dim * nvec)), dim3(256), 0, s, n, idx, dim, nvec, msg, a, b, c);
 }
-void launch_halo_pack_f32(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* a, const float* b,
-                          const float* c, float* msg) {
+void launch_halo_pack(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* a, const float* b,
+                      const float* c, float* msg) {
   if (n > 0) hipLaunchKernelGGL(halo_pack_kernel<float>, dim3(halo_grid((size_t)n * dim * nvec)), dim3(256), 0, s, n, idx, dim, nvec, a, b, c, msg);
 }
-void launch_halo_unpack_f32(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* msg, float* a, float* b,
-                            float* c) {
+void launch_halo_unpack(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* msg, float* a, float* b,
+                        float* c) {
   if (n > 0) hipLaunchKernelGGL(halo_unpack_kernel<float>, dim3(halo_grid((size_t)n * dim * nvec)), dim3(256), 0, s, n, idx, dim, nvec, msg, a, b, c);
 }
 

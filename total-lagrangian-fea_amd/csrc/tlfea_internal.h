@@ -337,14 +337,14 @@ void launch_residual_replace_init32(hipStream_t s, int N, const double* b, const
                                     const float* Dinv_f, const double* sc, const double* coef, float* d, float* z,
                                     float* res, const double* wown = nullptr);
 // overlapping partition: ghost refresh messages (nvec fields of dim values per node, interleaved per node)
-void launch_halo_pack_f64(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* a, const double* b,
-                          const double* c, double* msg);
-void launch_halo_unpack_f64(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* msg, double* a, double* b,
-                            double* c);
-void launch_halo_pack_f32(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* a, const float* b,
-                          const float* c, float* msg);
-void launch_halo_unpack_f32(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* msg, float* a, float* b,
-                            float* c);
+void launch_halo_pack(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* a, const double* b,
+                      const double* c, double* msg);
+void launch_halo_unpack(hipStream_t s, int n, const int* idx, int dim, int nvec, const double* msg, double* a, double* b,
+                        double* c);
+void launch_halo_pack(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* a, const float* b,
+                      const float* c, float* msg);
+void launch_halo_unpack(hipStream_t s, int n, const int* idx, int dim, int nvec, const float* msg, float* a, float* b,
+                        float* c);
 void launch_to_float(hipStream_t s, size_t n, const double* a, float* b);
 void launch_cheb32_init(hipStream_t s, int N, const float* Dinv_f, const double* r, const double* sc,
                         const double* coef, float* d, float* z, float* res, int row0 = 0);
