@@ -133,9 +133,11 @@ static int lp_build(tlfea_newton_t s, bool defer) {
       HIP_TRY(hipMalloc((void**)&s->d_L12inv, (size_t)36 * s->N * sizeof(double)));  // 144 per node of 4 coefficient vectors
       HIP_TRY(hipMalloc((void**)&s->d_L12inv_f, (size_t)36 * s->N * sizeof(float)));
       HIP_TRY(hipMalloc((void**)&s->d_blk12_err, sizeof(int)));
-      HIP_TRY(hipMemsetAsync(s->d_blk12_err, 0, sizeof(int), s->stream));
     }
     TRY(hessian_current(s));
+    // the flag reports this factorisation alone: a non-SPD block of an earlier H (a rolled-back trial step) must not
+    // refuse the solves on the H that followed it
+    HIP_TRY(hipMemsetAsync(s->d_blk12_err, 0, sizeof(int), s->stream));
     launch_blk12_factor(s->stream, s->N / 4, d->inc(), s->d_H, s->d_L12inv, s->d_L12inv_f, s->d_sc, s->d_Dinv_s, s->d_blk12_err);
     launch_lp_convert12(s->stream, s->N, d->inc(), s->d_H, s->d_L12inv, s->d_B8, s->d_B1, bits);
     launch_to_float(s->stream, (size_t)9 * s->N, s->d_Dinv_s, s->d_f32 + (size_t)18 * s->N);
@@ -1360,17 +1362,21 @@ int tlfea::precond_setup(tlfea_newton_t s, const double* d_b, int stage) {
 }
 
 // The set-up of a call that runs no start residual between the stages (modal solve, the operator hook): both stages, then
-// the flag of the node-block factorisation once the stream is drained.
+// the flag of the node-block factorisation once the stream is drained.  Stage 1 runs on the factors stage 0 left: where
+// a block was not positive definite they are not those of H, and the lambda_max estimate on them can fail first (NaN) -- the
+// flag names the cause, so it is read before a failure of stage 1 is reported.
 int tlfea::precond_setup_whole(tlfea_newton_t s, const double* d_b, const char* who) {
   TRY(precond_setup(s, d_b, 0));
-  TRY(precond_setup(s, d_b, 1));
+  const int rc1 = precond_setup(s, d_b, 1);
+  const std::string why1 = rc1 ? api_error() : std::string();
   HIP_TRY(hipStreamSynchronize(s->stream));
   if (cheb_bits_eff(s) != 64 && blk12_now(s)) {
     int bad = 0;
     HIP_TRY(hipMemcpy(&bad, s->d_blk12_err, sizeof(int), hipMemcpyDeviceToHost));
     if (bad) return fail(std::string(who) + ": a 12 x 12 node block of H is not positive definite (H is not SPD)");
   }
-  return 0;
+  if (rc1) api_error() = why1;
+  return rc1;
 }
 
 // Test hooks of the p-multigrid level: sizes, then the parent map and the Galerkin operator Hc = P^T H P of the CURRENT H
